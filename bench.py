@@ -4,11 +4,11 @@
 One *step* = one pass of the whole path over one batch of synthetic 3 s @ 24 kHz chunks that are
 already resident in HBM:  windowed STFT magnitude -> hybrid mel mixer -> PWL -> DS-CNN -> scores.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype i8|f32] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype i8|f32] [--batch B] [--dump-outputs DIR] [--full]
 
 * N = 1 (default): BASELINE.json configs[2] — the shipped birdnet_stm32n6_100 INT8 DS-CNN (int8 MFMA 1x1 convolutions)
   with the hybrid+pwl frontend at batch 4096, the largest single-GPU configuration (``--dtype f32`` gives configs[1],
-  float32 at batch 1024; the default run reports it under ``also_measured``).
+  float32 at batch 1024; a ``--full`` run reports it under ``also_measured``).
 * N > 1: BASELINE.json configs[3] — the INT8 chunk stream sharded over N GPUs, one process per GPU.  Started bare
   (``python bench.py --gpus N`` with WORLD_SIZE unset) the parent launches ``python -m torch.distributed.run
   --nproc-per-node N`` on itself BEFORE anything touches a GPU and relays the workers' output; started by the driver's
@@ -17,18 +17,21 @@ already resident in HBM:  windowed STFT magnitude -> hybrid mel mixer -> PWL -> 
   ``[K * 4096, 100]`` buffer (``evaluation/sharding.py: run_sharded`` — the same function ``evaluate`` shards with) and
   the job ends with ONE RCCL all-gather of those scores (12.8 MB per rank at K = 8), inside the timed region.
 
-The timed job (K steps between barrier + device synchronisation on both sides, MAX over ranks) is REPEATED ``--repeats`` R times
-(default 25: more than a second of timed work at the default sizes); ``value`` / ``ms_per_step`` are the MEDIAN repeat, ``value_min`` /
-``value_max`` the slowest / fastest one.  ``--collective`` initialises RCCL even on one GPU and runs the all-gather inside the timed
-region at world size 1 (the collective code path on hardware without a second GPU); without it a one-GPU run still probes RCCL after
-the measurement and reports what it saw under ``collective``.
+The timed job (K steps between barrier + device synchronisation on both sides, MAX over ranks) runs ``--repeats`` R times (default 1,
+so that ``--steps`` is the number of timed steps); ``value`` / ``ms_per_step`` are the MEDIAN repeat, ``value_min`` / ``value_max`` the
+slowest / fastest one.  ``--collective`` initialises RCCL even on one GPU and runs the all-gather inside the timed region at world
+size 1 (the collective code path on hardware without a second GPU).
 
 Every rank keeps ``min(K, 8)`` distinct synthetic batches in HBM (9.4 GB) and walks them round-robin, so no step re-reads a
-cache-warm input.  Rank 0 prints ONE JSON line: the throughput contract fields plus ``roofline`` (dominant kernel — named by
-the fully profiled warm-up steps, then timed with HIP events on the launch stream during the timed region, where it is the
-only bracketed operator; ``stages`` are the warm-up measurements of the other operators) and ``cpu_baseline`` (the C/OpenMP
-restatement of the reference path under ``oracle/`` timed on this host on a bounded sample — a reported baseline, not a
-target).
+cache-warm input; the inputs depend on the arguments only (seeded generator on the device).  A plain run sets up, warms up, times,
+writes the scores of its last timed step if ``--dump-outputs DIR`` is given (``DIR/scores.npy``, float32 ``[N x B, classes]``: every
+rank's last batch, a fixed seeded sample of rows beyond 64 MB) and prints ONE JSON line with the throughput contract fields.
+
+``--full`` adds, behind the measurement: ``roofline`` / ``stages`` (a pass of its own: one step with every operator bracketed by HIP
+events names the dominant kernel, then K steps with only that kernel bracketed time it), ``collective`` (what RCCL saw; without
+``--collective`` a one-GPU run probes RCCL after the measurement), on one GPU without ``--batch`` the other configurations,
+``hard_inputs`` and ``evaluate`` end to end, and ``cpu_baseline`` (the C/OpenMP restatement of the reference path under
+``oracle/`` timed on this host on a bounded sample — a reported baseline, not a target).
 """
 
 from __future__ import annotations
@@ -267,7 +270,7 @@ def roofline_of(rows: list[dict], batch: int, dtype: str, dom_op: int = -1) -> t
     roof["layer"] = dom["layer"]
     roof["avg_launch_ms"] = dom["avg_ms"]
     roof["algorithmic_bytes_per_launch"] = dom["bytes"]
-    roof["timing"] = "HIP events on the launch stream around this kernel only, averaged over the timed region"
+    roof["timing"] = "HIP events on the launch stream around this kernel only, averaged over a pass of --steps steps behind the timed region"
     roof.update(sq_counters(dom, batch, dtype))
     # the two longest kernels of the INT8 path (STFT, fused tail) are within a few per cent of each other and swap places from run to
     # run: the runner-up is named with its own roof (from the warm-up profile) so that the line reads the same either way
@@ -618,6 +621,40 @@ def timed_job(score_batch, steps: int, batch: int, n_classes: int, device, barri
     return time.perf_counter() - t0, gathered
 
 
+def profiled_pass(torch, runner, pool: list, steps: int, out, device) -> tuple[list[dict], int]:
+    """The per-operator table behind ``roofline`` / ``stages`` (``--full``), in a pass of its own behind the headline: one step with an
+    event pair around EVERY operator names the dominant operator, then ``steps`` steps with only that operator bracketed time it (26 event
+    records per step would cost ~6 % of it).  Returns (rows with the dominant operator's entry from the bracketed steps, its index)."""
+    runner.profile(True)
+    runner.profile_collect()
+    runner.infer_audio_device(pool[0], hop=HOP, out=out)
+    torch.cuda.synchronize(device)
+    table = runner.profile_collect()
+    dom_op = max((r for r in table if r["launches"]), key=lambda r: r["ms"] / r["launches"])["op"]
+    runner.profile_only(dom_op)
+    for k in range(steps):
+        runner.infer_audio_device(pool[k % len(pool)], hop=HOP, out=out)
+    torch.cuda.synchronize(device)
+    runner.profile(False)
+    timed = {r["op"]: r for r in runner.profile_collect() if r["launches"]}
+    runner.profile_only(-1)
+    return [timed.get(r["op"], r) if r["op"] == dom_op else r for r in table], dom_op
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_scores(gathered, world: int, steps: int, batch: int, out_dir: str) -> None:
+    """``out_dir/scores.npy``: the scores of every rank's LAST timed step (rows of rank r's last batch at ``r * batch``), float32; beyond
+    ``DUMP_LIMIT_BYTES`` a fixed seeded sample of rows, in order."""
+    last = gathered.view(world, steps, batch, -1)[:, -1].reshape(world * batch, -1).cpu().numpy().astype(np.float32)
+    max_rows = DUMP_LIMIT_BYTES // (last.shape[1] * 4)
+    if last.shape[0] > max_rows:
+        last = last[np.sort(np.random.default_rng(0).choice(last.shape[0], max_rows, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "scores.npy"), last)
+
+
 def self_launch(args, argv: list[str]) -> int:
     """``python bench.py --gpus N`` with WORLD_SIZE unset: start N workers (one per GPU) with torch.distributed.run as a CHILD
     process before this process has touched a GPU, relay their output, return their exit code."""
@@ -682,12 +719,17 @@ def main() -> None:
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=0, help="timed steps per repeat (default 20 on one GPU, 8 = BASELINE configs[3] on several)")
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=25, help="how often the timed job of --steps steps is repeated (value = the median repeat)")
+    ap.add_argument("--repeats", type=int, default=1, help="how often the timed job of --steps steps runs (value = the median repeat)")
     ap.add_argument("--dtype", choices=["f32", "i8"], default="i8")
     ap.add_argument("--batch", type=int, default=0, help="chunks per GPU per step (default 4096 i8, 1024 f32)")
     ap.add_argument("--collective", action="store_true", help="initialise RCCL even on one GPU and run the all-gather inside the timed region")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the legs beside the main measurement (other configurations, hard inputs, evaluate end to end)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the scores of the last timed step to DIR/scores.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline and stages, collective, other configurations, hard inputs, "
+                         "evaluate end to end, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the legs beside the main measurement (other configurations, hard inputs, evaluate end to end)")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args, sys.argv[1:]))
@@ -743,47 +785,35 @@ def main() -> None:
         if use_dist:
             dist.barrier()
 
-    # Warm-up steps carry an event pair around EVERY operator: they give the per-stage table and name the dominant kernel.
-    # In the timed region only that kernel is bracketed (26 event records per step would cost ~6 % of it).
-    runner.profile(True)
-    for w in range(args.warmup):
-        if w == args.warmup - 1 and w > 0:  # first launches carry module loading: the table comes from the last warm-up step
-            torch.cuda.synchronize(device)
-            runner.profile_collect()
+    for w in range(args.warmup):  # the timed path itself (first launches carry module loading)
         runner.infer_audio_device(pool[w % n_distinct], hop=HOP, out=scratch)
     if use_dist:  # warm the RCCL communicator (and its buffers for this message size) outside the timed region
         warm = torch.empty((world * steps * batch, runner.num_classes), dtype=torch.float32, device=device)
         dist.all_gather_into_tensor(warm, warm[rank * steps * batch : (rank + 1) * steps * batch].clone())
         del warm
     torch.cuda.synchronize(device)
-    warm_rows = runner.profile_collect()
-    dom_op = max((r for r in warm_rows if r["launches"]), key=lambda r: r["ms"] / r["launches"])["op"] if args.warmup else -1
-    runner.profile_only(dom_op)
 
-    elapsed_all, finite = [], True
+    elapsed_all = []
     for _ in range(repeats):
         elapsed, gathered = timed_job(lambda k, out: runner.infer_audio_device(pool[k % n_distinct], hop=HOP, out=out), steps, batch,
                                       runner.num_classes, device, barrier, lambda: torch.cuda.synchronize(device))
         assert gathered.shape == (world * steps * batch, runner.num_classes)
         elapsed_all.append(elapsed)
     finite = bool(torch.isfinite(gathered).all().item())
+    if args.dump_outputs and rank == 0:
+        dump_scores(gathered, world, steps, batch, args.dump_outputs)
     del gathered
-    runner.profile(False)
-    rows = runner.profile_collect()
-    runner.profile_only(-1)
-    if args.warmup:  # stages from the warm-up profile, the dominant kernel's entry replaced by its timed-region measurement
-        timed = {r["op"]: r for r in rows if r["launches"]}
-        rows = [timed.get(r["op"], r) if r["op"] == dom_op else r for r in warm_rows]
 
     if world > 1:  # every repeat's time is the MAX over the ranks
         tt = torch.tensor(elapsed_all, dtype=torch.float64, device=device)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed_all = [float(v) for v in tt.cpu()]
     elapsed = float(np.median(elapsed_all))
-    coll = collective_block(torch, dist, device, steps * batch, runner.num_classes) if use_dist else None
+    if args.full:
+        rows, dom_op = profiled_pass(torch, runner, pool, steps, scratch, device)
+        coll = collective_block(torch, dist, device, steps * batch, runner.num_classes) if use_dist else None
 
     if rank == 0:
-        roof, stages = roofline_of(rows, batch, args.dtype, dom_op)
         total_chunks = world * batch * steps
         name = "birdnet_stm32n6_100 " + ("float32" if args.dtype == "f32" else "INT8") + " DS-CNN, hybrid+pwl frontend"
         if world > 1:
@@ -822,15 +852,15 @@ def main() -> None:
                                      "bn_set_option('stft_exact', 1) computes every bin in float64 and needs no bound") if args.dtype == "i8" else None,
             },
             "scores_finite": finite,
-            "whole_path_mfma_frac": round(total_chunks / world * MOP_PER_CHUNK * 1e6 / elapsed / 1e12 /
-                                          (I8_MFMA_PEAK_TOPS if args.dtype == "i8" else F32_MFMA_PEAK_TFLOPS), 4),
-            "roofline": roof,
-            "stages": stages,
         }
-        if coll is not None:
-            coll["in_timed_region"] = True
-            out["collective"] = coll
-        if world == 1 and not args.batch and not args.no_extras:  # the other single-GPU BASELINE configurations, for reference (not the reported value)
+        if args.full:
+            out["whole_path_mfma_frac"] = round(total_chunks / world * MOP_PER_CHUNK * 1e6 / elapsed / 1e12 /
+                                                (I8_MFMA_PEAK_TOPS if args.dtype == "i8" else F32_MFMA_PEAK_TFLOPS), 4)
+            out["roofline"], out["stages"] = roofline_of(rows, batch, args.dtype, dom_op)
+            if coll is not None:
+                coll["in_timed_region"] = True
+                out["collective"] = coll
+        if args.full and world == 1 and not args.batch and not args.no_extras:  # the other single-GPU BASELINE configurations, for reference (not the reported value)
             runner.close()
             runner = None
             del pool
@@ -848,7 +878,7 @@ def main() -> None:
                     out[key] = config4_rate(torch, device, local_rank, **kw)
                 except Exception as e:  # noqa: BLE001
                     out[key] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not use_dist:
+        if args.full and world == 1 and not use_dist:
             # one GPU, no collective in the path: still show that RCCL comes up on this box and moves the score tensor (outside the timed region)
             try:
                 init_rccl()
@@ -856,12 +886,12 @@ def main() -> None:
                                          note="probe behind the measurement; `--collective` puts the all-gather inside the timed region")
             except Exception as e:  # noqa: BLE001
                 out["collective"] = {"backend": None, "ranks_seen": 1, "error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not args.batch and not args.no_extras and not use_dist:
+        if args.full and world == 1 and not args.batch and not args.no_extras and not use_dist:
             try:
                 out["also_measured_evaluate"] = evaluate_leg()
             except Exception as e:  # noqa: BLE001
                 out["also_measured_evaluate"] = {"error": f"{type(e).__name__}: {e}"}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args.dtype)
         print(json.dumps(out))
     if dist.is_initialized():

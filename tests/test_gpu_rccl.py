@@ -8,6 +8,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -35,18 +36,20 @@ def _torchrun(script_and_args, timeout=600):
     return json.loads(lines[-1])
 
 
-def test_bench_collective_runs_rccl_inside_the_timed_region():
+def test_bench_collective_runs_rccl_inside_the_timed_region(tmp_path):
     """``bench.py --gpus 1 --collective``: RCCL initialised with ``device_id``, warm-up + timed ``all_gather_into_tensor`` of the score
-    buffer inside every repeat, the JSON line says what RCCL saw; the rate stays that of the plain one-GPU line (the gather of
-    1.6 MB is microseconds)."""
+    buffer inside every repeat, the JSON line (``--full``) says what RCCL saw; the rate stays that of the plain one-GPU line (the gather of
+    1.6 MB is microseconds).  ``--dump-outputs``: the last step's gathered scores."""
     out = _torchrun([os.path.join(REPO, "bench.py"), "--gpus", "1", "--collective", "--steps", "4", "--repeats", "5", "--warmup", "2", "--batch", "1024",
-                     "--no-cpu-baseline"])
+                     "--full", "--no-cpu-baseline", "--dump-outputs", str(tmp_path)])
     c = out["collective"]
     assert c["backend"] == "nccl" and c["ranks_seen"] == 1 and c["in_timed_region"] is True
     assert c["bytes_per_rank"] == 4 * 1024 * 100 * 4 and c["all_gather_ms"] > 0 and c["nccl_version"]
     assert out["n_gpus"] == 1 and out["repeats"] == 5 and out["scores_finite"] and out["value"] > 1e5
     assert "all-gather" in out["config"]["path"]
     assert out["value_min"] <= out["value"] <= out["value_max"]
+    scores = np.load(tmp_path / "scores.npy")
+    assert scores.shape == (1024, 100) and scores.dtype == np.float32 and np.isfinite(scores).all()
 
 
 def test_sharded_scoring_over_rccl_equals_unsharded():

@@ -242,3 +242,24 @@ def test_bench_self_launch_command(monkeypatch):
     assert cmd[cmd.index("--master-port") + 2] == os.path.join(REPO, "bench.py")
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
     assert bench.self_launch(argparse.Namespace(gpus=8), ["--gpus", "8"]) == 2
+
+
+def test_bench_dump_outputs_last_step_of_every_rank(tmp_path, monkeypatch):
+    """``bench.py --dump-outputs``: from the gathered scores of a sharded job, every rank's last batch in rank order, float32; past the
+    size limit a fixed seeded sample of those rows, in order."""
+    import torch
+
+    import bench
+
+    world, K, B, C = 2, 3, 4, 7
+    gathered = torch.arange(world * K * B, dtype=torch.float32)[:, None] * torch.arange(1, C + 1, dtype=torch.float32)[None, :]
+    bench.dump_scores(gathered, world, K, B, str(tmp_path / "all"))
+    got = np.load(tmp_path / "all" / "scores.npy")
+    last = [(r * K + K - 1) * B + j for r in range(world) for j in range(B)]
+    assert got.dtype == np.float32 and np.array_equal(got, gathered.numpy()[last])
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 5 * C * 4)
+    for d in ("s1", "s2"):
+        bench.dump_scores(gathered, world, K, B, str(tmp_path / d))
+    s1, s2 = np.load(tmp_path / "s1" / "scores.npy"), np.load(tmp_path / "s2" / "scores.npy")
+    assert s1.shape == (5, C) and np.array_equal(s1, s2)
+    assert set(s1[:, 0]) <= set(got[:, 0]) and (np.diff(s1[:, 0]) > 0).all()

@@ -7,7 +7,7 @@ OLD=$(realpath "$1"); NEW=$(realpath "$2"); shift 2
 LAYERS="${*:-stft tail}"
 for r in 1 2 3; do
   for v in "$OLD" "$NEW"; do
-    BIRDNET_HIP_LIB=$v python bench.py --no-extras --no-cpu-baseline --repeats 10 2>/dev/null | LAYERS="$LAYERS" python -c "
+    BIRDNET_HIP_LIB=$v python bench.py --full --no-extras --no-cpu-baseline --repeats 10 2>/dev/null | LAYERS="$LAYERS" python -c "
 import sys, json, os
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 st = {s['layer']: s['avg_ms'] for s in d['stages']}
