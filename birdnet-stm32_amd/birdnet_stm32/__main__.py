@@ -1,12 +1,12 @@
 """``python -m birdnet_stm32 <command>`` dispatcher (reference: birdnet_stm32/__main__.py:12-47).
 
-``evaluate`` and ``convert`` (own post-training quantisation, no TensorFlow) exist in this build; the reference's train /
+``evaluate``, ``embed`` (embeddings of audio files, this build only) and ``convert`` (own post-training quantisation, no TensorFlow) exist in this build; the reference's train /
 deploy / board-test commands are outside the accelerated path and answer with a pointer to the reference package.
 """
 
 import sys
 
-USAGE = "Usage: birdnet-stm32 {train,convert,evaluate,deploy,board-test}"
+USAGE = "Usage: birdnet-stm32 {train,convert,evaluate,embed,deploy,board-test}"
 
 
 def main():
@@ -17,6 +17,10 @@ def main():
     sys.argv = [f"birdnet-stm32 {command}"] + sys.argv[2:]
     if command == "evaluate":
         from birdnet_stm32.cli.evaluate import main as run
+
+        run()
+    elif command == "embed":
+        from birdnet_stm32.cli.embed import main as run
 
         run()
     elif command == "convert":

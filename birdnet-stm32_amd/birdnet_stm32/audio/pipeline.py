@@ -458,6 +458,10 @@ class EvaluatePipeline:
         self._trace = None
         self._t0 = 0.0
         self._preloaded = False
+        # embedding output (evaluation/embeddings.py): None = scores only; "float32" / "int8" = run() also fills self.embeddings [N, D]
+        self.emb_dtype: str | None = None
+        self.embeddings = None
+        self._emb = None
 
     def _mark(self, name: str) -> None:
         """Timeline of one run (``BN_PIPELINE_TRACE=1``: ``stats["trace"]`` = [(what, seconds since run() started, thread)]) — where a COLD call's
@@ -642,27 +646,35 @@ class EvaluatePipeline:
         ev[1].record(cur)
         self._mark("compute: ingest launched")
         n = g.n_chunks
+        emb = self._emb
         if n:
-            if lat_events is None:
+            if lat_events is None and emb is not None:
+                self.runner.infer_audio_device(self._chunks[:n], out=scores[row0 : row0 + n], return_embeddings=True, emb_dtype=self.emb_dtype,
+                                               emb_out=emb[row0 : row0 + n])
+            elif lat_events is None:
                 self.runner.infer_audio_device(self._chunks[:n], out=scores[row0 : row0 + n])
             else:
                 for b0 in range(0, n, batch):
                     nb = min(batch, n - b0)
                     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     a.record(cur)
-                    self.runner.infer_audio_device(self._chunks[b0 : b0 + nb], out=scores[row0 + b0 : row0 + b0 + nb])
+                    kw = {} if emb is None else dict(return_embeddings=True, emb_dtype=self.emb_dtype, emb_out=emb[row0 + b0 : row0 + b0 + nb])
+                    self.runner.infer_audio_device(self._chunks[b0 : b0 + nb], out=scores[row0 + b0 : row0 + b0 + nb], **kw)
                     b.record(cur)
                     lat_events.append((a, b, nb))
         ev[2].record(cur)
         self._mark("compute: inference launched")
         stats["_events"].append((st.h2d_events, ev, g.used + 8 * g.tab_len))
 
-    def run(self, paths: list[str], batch_size: int | None = None, measure_latency: bool = False):
+    def run(self, paths: list[str], batch_size: int | None = None, measure_latency: bool = False, table: FileTable | None = None):
         """Score every chunk of ``paths``: ``(scores [N, C] CUDA, chunks per file (list), stats dict, per-chunk latencies in ms)``.
 
         ``batch_size`` only matters with ``measure_latency``: inference then runs in slices of that many chunks, each bracketed by
         events on the launch stream (the reference's accounting: time of one ``predict`` / its batch size, replicated per chunk,
         evaluation/metrics.py:130-136) — without a host synchronisation per slice.  Otherwise slices are the runner's ``max_batch``.
+
+        ``table``: the ``plan_files`` result for ``paths`` when the caller has it already.  With ``emb_dtype`` set, ``self.embeddings``
+        holds the ``[N, D]`` CUDA embeddings of the same rows afterwards.
         """
         torch = self.torch
         t_start = time.perf_counter()
@@ -678,7 +690,7 @@ class EvaluatePipeline:
                     if key not in _COPY_STREAMS:
                         _COPY_STREAMS[key] = torch.cuda.Stream(device=self.dev)
                     self.copy_stream = _COPY_STREAMS[key]
-            tab = plan_files(paths, self.sr, self.cd, self.ov, self.max_duration, self.readers)
+            tab = table if table is not None else plan_files(paths, self.sr, self.cd, self.ov, self.max_duration, self.readers)
             stats["probe_s"] = time.perf_counter() - t_start
             groups = cut_groups(tab.nbytes, tab.n_chunks, self.slab_bytes, self.group_chunks, self.ramp)
             planned = int(tab.n_chunks.sum())
@@ -695,6 +707,10 @@ class EvaluatePipeline:
             self._pinned_free = [None] * self._n_ring
             self._stop.clear()
             scores = torch.empty((max(planned, 1), self.runner.num_classes), dtype=torch.float32, device=self.dev)
+            self.embeddings = self._emb = None
+            if self.emb_dtype is not None:
+                D = self.runner.embedding_info()["dim"]
+                self._emb = torch.empty((max(planned, 1), D), dtype=torch.int8 if self.emb_dtype == "int8" else torch.float32, device=self.dev)
             q: queue.Queue = queue.Queue(maxsize=max(1, self._n_ring - 1))
             stop = self._stop
 
@@ -764,6 +780,8 @@ class EvaluatePipeline:
                      read_s_per_group=read_groups[:32])
         if self._trace is not None:
             stats["trace"] = list(self._trace)
+        if self._emb is not None:
+            self.embeddings, self._emb = self._emb[:row], None
         return scores[:row], counts.tolist(), stats, lat
 
 

@@ -382,8 +382,9 @@ def lower_f32(spec: ns.NetSpec, keep_all: bool = False, fuse: bool = True) -> pk
             cout = int(head.attrs["units"])
             act = {"linear": 0, "sigmoid": 1, "softmax": 2}[head.attrs.get("activation", "linear")]
             bias = head.weights.get("bias", np.zeros(cout, np.float32))
-            pb.op(pk.F32_GAPDENSE, val[ly.inputs[0]], pk.SLOT_SCORES, p=[H * Wd, C, cout, act],
-                  t=[pb.tensor(head.weights["kernel"], np.float32), pb.tensor(bias, np.float32)], name=head.name, out_shape=(cout,))
+            o = pb.op(pk.F32_GAPDENSE, val[ly.inputs[0]], pk.SLOT_SCORES, p=[H * Wd, C, cout, act],
+                      t=[pb.tensor(head.weights["kernel"], np.float32), pb.tensor(bias, np.float32)], name=head.name, out_shape=(cout,))
+            pk.mark_embedding(o, C)  # the kernel pools the embedding on chip
             done.update(range(i + 1, head_i + 1))
         elif k == ns.GAP:
             H, Wd, C = shape[ly.inputs[0]]
@@ -402,6 +403,9 @@ def lower_f32(spec: ns.NetSpec, keep_all: bool = False, fuse: bool = True) -> pk
             if ly is not layers[-1]:
                 raise NotImplementedError("Dense layers are only lowered as the classifier head or inside squeeze-excite")
             (cin,) = shape[ly.inputs[0]]
+            pool = [o for o in plan.ops if o.out == val[ly.inputs[0]]]
+            if len(pool) == 1 and pool[0].kind in (pk.F32_GAP, pk.F32_ATTNPOOL):
+                pk.mark_embedding(pool[0], cin)  # the pooled vector the classifier reads is the embedding (not found by kind: SE pools are SEGATE)
             cout = int(ly.attrs["units"])
             act = {"linear": 0, "sigmoid": 1, "softmax": 2}[ly.attrs.get("activation", "linear")]
             bias = ly.weights.get("bias", np.zeros(cout, np.float32))

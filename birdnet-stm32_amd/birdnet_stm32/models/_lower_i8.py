@@ -1117,12 +1117,33 @@ def lower_i8(model, keep_all: bool = False, fuse: bool = True, softmax_form: str
             _expect(i == len(ops), "operators after the head")
         else:
             _expect(False, f"operator #{op.index} {op.name} in the backbone")
+    _mark_embedding(g, plan)
     if fuse and not keep_all:
         _add_tail_op(pb, plan, tail_blocks, tail_head)
         _tag_scale_pairs(pb)
         _tag_se_gates(pb)
         _tag_pwdw_pairs(pb)
     return pb.finalize(reuse=not keep_all)
+
+
+def _mark_embedding(g: _Graph, plan: pk.Plan) -> None:
+    """Mark the embedding: the pooled vector (MEAN / attention pooling) the classifier FULLY_CONNECTED reads, the TFLite tensor a user
+    of the reference reads as the backbone output (reference training/linear_probe.py:57-68; tensor 127 of the shipped model).  Found by
+    data flow from the head backwards, so squeeze-excite MEANs (whose FULLY_CONNECTED feeds a MUL) are never marked.  Runs on value ids,
+    before slots are assigned."""
+    ops = plan.ops
+    writer = {o.out: i for i, o in enumerate(ops) if o.out >= 0}
+    heads = [o for o in ops if o.kind == pk.I8_HEAD]
+    if len(heads) != 1 or heads[0].in0 not in writer:
+        return
+    fc = ops[writer[heads[0].in0]]
+    if fc.kind != pk.I8_FC or fc.in0 not in writer:
+        return
+    pool = ops[writer[fc.in0]]
+    if pool.kind not in (pk.I8_MEAN, pk.I8_ATTNPOOL) or not pool.name.startswith("t"):
+        return
+    s, z = g.q(int(pool.name[1:]))
+    pk.mark_embedding(pool, pool.p[1], float(np.float32(s)), z)
 
 
 def _tag_se_gates(pb: pk.PlanBuilder) -> None:
@@ -1257,3 +1278,6 @@ def _add_tail_op(pb, plan, blocks: list[dict], head: dict) -> None:
              first["H"], first["W"], first["C"], head["P"], head["C"], *([0] * (pk.TAIL_TAG - 11)), pk.TAIL_OP],
           t=[pb.tensor(cst, np.int32), pb.tensor(desc, np.int32)] + ([pb.tensor(packed2[0], np.int32), pb.tensor(packed2[1], np.int32)] if packed2 is not None else []),
           f=[head["s_fc"], head["s_head"]], name="tail", out_shape=(head["NC"],))
+    mean = plan.ops[head["mean_op"]]
+    if mean.p[pk.EMB_TAG] == pk.EMB_OP:  # the fused operator pools the same vector on chip: it carries the mark as well
+        pk.mark_embedding(plan.ops[-1], mean.p[pk.EMB_DIM], mean.f[pk.EMB_SCALE], mean.p[pk.EMB_ZP])

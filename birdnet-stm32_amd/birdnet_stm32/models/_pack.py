@@ -33,6 +33,9 @@ I8_QUANT, I8_MEL, I8_STEM, I8_DW, I8_PW, I8_MEAN, I8_FC, I8_HEAD, I8_DWPW, I8_FR
 TAIL_TAG = 38  # OpRec.p[TAIL_TAG] = TAIL_COVERED: the operator is covered by the plan's fused tail operator; TAIL_OP: it is that operator
 TAIL_COVERED, TAIL_OP = 0x7A110001, 0x7A110002  # (bn_blob.h; values no other use of p[38] can take)
 MID_COVERED, MID_OP = 0x7A11000E, 0x7A11000F    # the same for the fused stage-2 chain (i8_mid2_kernel)
+EMB_TAG, EMB_DIM, EMB_ZP, EMB_SCALE = 36, 35, 34, 7  # OpRec.p[EMB_TAG] = EMB_OP: the operator's result is the embedding (bn_blob.h);
+EMB_OP = 0x7A110010                                  # p[EMB_DIM] = D, INT8: p[EMB_ZP] = zero point, f[EMB_SCALE] = scale
+EMB_KINDS = (25, 30, 34, 9, 11, 16)                  # I8_MEAN, I8_TAIL, I8_ATTNPOOL, F32_GAP, F32_ATTNPOOL, F32_GAPDENSE
 FRONT2_HEAD, FRONT2_COVERED = 0x7A110003, 0x7A110004  # front block + the residual block FRONT2_DIST operators further on may run as one kernel
 FRONT2_DIST = 37
 PWDW8_HEAD, PWDW8_COVERED = 0x7A11000C, 0x7A11000D  # the INT8 counterpart (i8_pwdw_kernel)
@@ -50,6 +53,20 @@ KIND_NAMES = {
 
 ACT_CODES = {"none": 0, "linear": 0, "relu": 1, "relu6": 2}
 MAG_CODES = {"none": 0, "pwl": 1, "pcen": 2, "db": 3}
+
+
+@dataclass(frozen=True)
+class PlanEmbedding:
+    """Where a plan's embedding comes from: ``ops`` maps each entry path ("input": bn_forward, "audio": bn_infer_audio) to the marked
+    operator that produces it with the default launcher options; ``marked`` lists every marked operator (an INT8 plan marks its unfused
+    MEAN and the fused tail operator that covers it).  ``scale`` / ``zero_point`` dequantise the int8 form (1.0 / 0 on float32 plans)."""
+
+    ops: dict
+    marked: tuple
+    dim: int
+    dtype: str
+    scale: float
+    zero_point: int
 
 
 def _align(n: int, a: int = 256) -> int:
@@ -89,6 +106,22 @@ class Plan:
 
     def to_blob(self) -> bytes:
         return pack_plan(self)
+
+    @property
+    def embedding(self) -> PlanEmbedding | None:
+        """The marked embedding operator(s) of this plan, or None when lowering found no pooled vector in front of a classifier."""
+        marked = tuple(i for i, o in enumerate(self.ops) if o.p[EMB_TAG] == EMB_OP)
+        if not marked:
+            return None
+        first = self.ops[marked[0]]
+        i8 = self.dtype == DTYPE_I8
+        ops = {}
+        for name, path in (("input", PATH_INPUT), ("audio", PATH_AUDIO)):
+            run = [i for i in marked if self.ops[i].p[OP_PATH] in (PATH_BOTH, path)]
+            fused = [i for i in run if self.ops[i].p[TAIL_TAG] == TAIL_OP]   # the fused tail covers the MEAN whenever it runs
+            ops[name] = (fused or run or [None])[0]
+        return PlanEmbedding(ops, marked, int(first.p[EMB_DIM]), "int8" if i8 else "float32",
+                             float(first.f[EMB_SCALE]) if i8 else 1.0, int(first.p[EMB_ZP]) if i8 else 0)
 
 
 class PlanBuilder:
@@ -172,6 +205,16 @@ class PlanBuilder:
                 o.p[pi] = slot_of[o.p[pi]]
         self.plan.slot_bytes = slot_bytes
         return self.plan
+
+
+def mark_embedding(op: PlanOp, dim: int, scale: float = 0.0, zero_point: int = 0) -> None:
+    """Tag ``op`` as the producer of the plan's embedding (see :class:`PlanEmbedding`)."""
+    if op.kind not in EMB_KINDS:
+        raise ValueError(f"operator kind {op.kind} cannot carry the embedding")
+    op.p[EMB_TAG] = EMB_OP
+    op.p[EMB_DIM] = int(dim)
+    op.p[EMB_ZP] = int(zero_point)
+    op.f[EMB_SCALE] = float(scale)
 
 
 def pack_plan(plan: Plan) -> bytes:

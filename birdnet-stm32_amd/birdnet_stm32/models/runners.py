@@ -77,9 +77,50 @@ class HipRunner:
             out[b0 : b0 + xb.shape[0]] = self.predict_device(xb).cpu().numpy()
         return out
 
+    def embed(self, x_batch: np.ndarray, dtype: str = "float32") -> np.ndarray:
+        """Embeddings of a host batch (same input contract as :meth:`predict`): ``[B, D]`` float32, or int8 bytes on an INT8 model."""
+        torch = self._torch
+        x = np.ascontiguousarray(np.asarray(x_batch).astype(np.float32, copy=False))
+        if x.ndim < 2 or int(np.prod(x.shape[1:])) != self.input_elems:
+            want = f"[B, {self.fft_bins}, {self.spec_width}, 1]" if self.fft_bins else f"[B, {self.input_elems}, 1]"
+            raise ValueError(f"expected input of shape {want}, got {x.shape}")
+        D = self.embedding_info()["dim"]
+        B = x.shape[0]
+        out = np.empty((B, D), np.dtype(dtype))
+        for b0 in range(0, B, self.max_batch):
+            xb = torch.from_numpy(x[b0 : b0 + self.max_batch].reshape(-1, self.input_elems)).to(self.device)
+            out[b0 : b0 + xb.shape[0]] = self.predict_device(xb, return_embeddings=True, emb_dtype=dtype)[1].cpu().numpy()
+        return out
+
+    def embedding_info(self) -> dict:
+        """``{"dim", "dtype", "scale", "zero_point"}`` of the model's embedding (the pooled vector in front of the classifier head);
+        ``dtype`` is the plan's native form ("int8" on INT8 models: ``(q - zero_point) * scale`` is the float32 form)."""
+        dim, dt, zp, sc = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_float()
+        _hip.check(self.lib.bn_model_get_embedding_info(self.model.handle, ctypes.byref(dim), ctypes.byref(dt), ctypes.byref(sc), ctypes.byref(zp)))
+        return {"dim": int(dim.value), "dtype": "int8" if dt.value == _hip.EMB_I8 else "float32", "scale": float(sc.value), "zero_point": int(zp.value)}
+
+    def _emb_buffer(self, B: int, emb_dtype: str, emb_out=None):
+        """(tensor [B, D], BN_EMB_* code) for an embedding request: ``emb_out`` checked (the kernels write B x D values into it), or a new tensor."""
+        torch = self._torch
+        if emb_dtype not in ("float32", "int8"):
+            raise ValueError(f"emb_dtype must be 'float32' or 'int8', not {emb_dtype!r}")
+        D = self.embedding_info()["dim"]
+        code = _hip.EMB_I8 if emb_dtype == "int8" else _hip.EMB_F32
+        want = torch.int8 if code == _hip.EMB_I8 else torch.float32
+        if emb_out is None:
+            return torch.empty((B, D), dtype=want, device=self.device), code
+        if not (isinstance(emb_out, torch.Tensor) and emb_out.device == self.device and emb_out.dtype == want and emb_out.is_contiguous()
+                and tuple(emb_out.shape) == (B, D)):
+            raise ValueError(f"emb_out must be a contiguous {want} tensor of shape ({B}, {D}) on {self.device}")
+        return emb_out, code
+
     # -- device-resident interface --------------------------------------------------------------
-    def predict_device(self, x, minmax=None, return_logits: bool = False):
-        """``x``: CUDA float32 ``[B, input_elems]`` (any trailing shape with that many elements)."""
+    def predict_device(self, x, minmax=None, return_logits: bool = False, return_embeddings: bool = False, emb_dtype: str = "float32",
+                       emb_out=None):
+        """``x``: CUDA float32 ``[B, input_elems]`` (any trailing shape with that many elements).
+
+        ``return_embeddings``: also return the ``[B, D]`` embeddings (``emb_dtype`` "float32", or "int8" on INT8 models; written into
+        ``emb_out`` when given) as the last element of a tuple: ``(scores, emb)`` or ``(scores, logits, emb)``."""
         torch = self._torch
         self._check_dev(x, "x")
         B = x.shape[0]
@@ -89,9 +130,17 @@ class HipRunner:
         logits = torch.empty_like(scores) if return_logits else None
         if minmax is not None:
             self._check_dev(minmax, "minmax")
+        emb, code = (None, 0)
+        if return_embeddings:
+            emb, code = self._emb_buffer(B, emb_dtype, emb_out)
         with torch.cuda.device(self.device):
             for b0 in range(0, B, self.max_batch):
                 nb = min(self.max_batch, B - b0)
+                if emb is not None:
+                    _hip.check(self.lib.bn_forward_embed(self.model.handle, x[b0:].data_ptr(), minmax[b0:].data_ptr() if minmax is not None else None, nb,
+                                                         scores[b0:].data_ptr(), logits[b0:].data_ptr() if logits is not None else None,
+                                                         emb[b0:].data_ptr(), code, self._stream()))
+                    continue
                 _hip.check(
                     self.lib.bn_forward(
                         self.model.handle,
@@ -103,6 +152,8 @@ class HipRunner:
                         self._stream(),
                     )
                 )
+        if emb is not None:
+            return (scores, logits, emb) if return_logits else (scores, emb)
         return (scores, logits) if return_logits else scores
 
     def configure_precomputed(self, audio_frontend: str, sample_rate: int, mag_scale: str = "none", n_fft: int = 512,
@@ -125,10 +176,15 @@ class HipRunner:
         self._precomputed = {"mode": {"librosa": "mel", "log_mel": "log_mel", "mfcc": "mfcc"}[name], "sample_rate": int(sample_rate),
                              "mag_scale": mag_scale if name == "librosa" else "none", "n_fft": int(n_fft), "mel_bins": mels, "n_mfcc": int(n_mfcc)}
 
-    def infer_audio_device(self, audio, hop: int | None = None, return_logits: bool = False, out=None):
-        """``audio``: CUDA float32 ``[B, T]`` chunks -> scores ``[B, C]`` (STFT + frontend + network on the GPU)."""
+    def infer_audio_device(self, audio, hop: int | None = None, return_logits: bool = False, out=None, return_embeddings: bool = False,
+                           emb_dtype: str = "float32", emb_out=None):
+        """``audio``: CUDA float32 ``[B, T]`` chunks -> scores ``[B, C]`` (STFT + frontend + network on the GPU).
+
+        ``return_embeddings``: as in :meth:`predict_device` — the result is ``(scores, emb)`` or ``(scores, logits, emb)``; ``emb_out``
+        (``[B, D]`` CUDA tensor of ``emb_dtype``) receives the embeddings in place when given."""
         torch = self._torch
         self._check_dev(audio, "audio")
+        kw = dict(return_embeddings=True, emb_dtype=emb_dtype, emb_out=emb_out) if return_embeddings else {}
         if self.input_kind == pk.INPUT_MEL:
             if self._precomputed is None:
                 raise ValueError("precomputed-frontend model: call configure_precomputed(audio_frontend, sample_rate, mag_scale, ...) first")
@@ -137,9 +193,9 @@ class HipRunner:
             c = self._precomputed
             spec = mel_spectrograms_device(self.ctx, audio, c["sample_rate"], c["n_fft"], c["mel_bins"], self.spec_width, c["mag_scale"],
                                            c["mode"], c["n_mfcc"])
-            res = self.predict_device(spec.view(spec.shape[0], -1), return_logits=return_logits)
+            res = self.predict_device(spec.view(spec.shape[0], -1), return_logits=return_logits, **kw)
             if out is not None:
-                out.copy_(res[0] if return_logits else res)
+                out.copy_(res[0] if isinstance(res, tuple) else res)
             return res
         if self.input_kind == pk.INPUT_WAVEFORM:
             # raw frontend: the model input is the chunk divided by (its peak + 1e-6) (reference: evaluation/metrics.py:62-69)
@@ -149,23 +205,33 @@ class HipRunner:
             with torch.cuda.device(self.device):
                 _hip.check(self.lib.bn_chunk_peak_normalize(self.ctx.handle, audio.data_ptr(), audio.shape[0], audio.shape[1], 1e-6,
                                                             x.data_ptr(), self._stream()))
-            res = self.predict_device(x, return_logits=return_logits)
+            res = self.predict_device(x, return_logits=return_logits, **kw)
             if out is not None:
-                out.copy_(res[0] if return_logits else res)
+                out.copy_(res[0] if isinstance(res, tuple) else res)
             return res
         B, T = audio.shape
         hop = int(hop) if hop is not None else T // self.spec_width
         scores = out if out is not None else torch.empty((B, self.num_classes), dtype=torch.float32, device=self.device)
         logits = torch.empty_like(scores) if return_logits else None
+        emb, code = (None, 0)
+        if return_embeddings:
+            emb, code = self._emb_buffer(B, emb_dtype, emb_out)
         with torch.cuda.device(self.device):
             for b0 in range(0, B, self.max_batch):
                 nb = min(self.max_batch, B - b0)
+                if emb is not None:
+                    _hip.check(self.lib.bn_infer_audio_embed(self.model.handle, audio[b0:].data_ptr(), nb, T, hop, scores[b0:].data_ptr(),
+                                                             logits[b0:].data_ptr() if logits is not None else None, emb[b0:].data_ptr(), code,
+                                                             self._stream()))
+                    continue
                 _hip.check(
                     self.lib.bn_infer_audio(
                         self.model.handle, audio[b0:].data_ptr(), nb, T, hop, scores[b0:].data_ptr(),
                         logits[b0:].data_ptr() if logits is not None else None, self._stream(),
                     )
                 )  # fmt: skip
+        if emb is not None:
+            return (scores, logits, emb) if return_logits else (scores, emb)
         return (scores, logits) if return_logits else scores
 
     def stft_device(self, audio, n_fft: int = 512, hop: int | None = None, spec_width: int | None = None, normalize: bool = True,

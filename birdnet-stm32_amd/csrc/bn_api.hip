@@ -132,6 +132,9 @@ struct bn_model {
     int32_t* d_pool8 = nullptr;          // [max_batch][pool8_C] int32 channel sums from i8_dw_stream_kernel for the squeeze-excite gate behind it (zero between uses)
     size_t pool8_C = 0;
     size_t workspace_bytes = 0;
+    int emb_dim = 0;                     // the plan's embedding (operators tagged BN_EMB_OP): width, int8 quantisation; 0 = none marked
+    float emb_scale = 1.0f;
+    int emb_zp = 0;
     // per-operator HIP-event timing (bn_profile_*): one (start, stop) pair per launch group
     bool profiling = false;
     int prof_only = -1;                  // >= 0: bracket only this operator (index n_ops = the STFT stage)
@@ -232,7 +235,8 @@ bn::StftGuard guard_slice(const bn_model* m, size_t b0) {
 // Executes the plan for a batch slice.
 // `op_begin..op_end` restricts the run to a range of operators, `slot_b0` is the chunk index the slice starts at inside the
 // workspace slots (bn_infer_audio runs the first operator per sub-batch, the rest over the whole batch).
-int run_plan(bn_model* m, const float* d_input, const float* d_minmax, int B, float* d_scores, float* d_logits,
+// `d_emb` (or null): where the embedding of the slice goes, in the form `emb_dtype` (BN_EMB_*); the caller offsets it like d_scores.
+int run_plan(bn_model* m, const float* d_input, const float* d_minmax, int B, float* d_scores, float* d_logits, void* d_emb, int emb_dtype,
              hipStream_t s, const float* d_audio = nullptr, int T = 0, int hop = 0, size_t op_begin = 0, size_t op_end = (size_t)-1,
              size_t slot_b0 = 0) {
     const int mode = d_audio ? BN_PATH_AUDIO : BN_PATH_INPUT;
@@ -325,6 +329,8 @@ int run_plan(bn_model* m, const float* d_input, const float* d_minmax, int B, fl
         a.add_tab = (q[18] && !q[29] && d.t[10] >= 0) ? (const int8_t*)m->tensor(d.t[10]) : nullptr;
         return a;
     };
+    int emb_written = 0;   // marked operators that stored the embedding in this call (exactly one runs per path)
+    auto emb_for = [&](const OpRec& o) -> void* { return (d_emb && o.p[BN_OP_EMB_TAG] == BN_EMB_OP) ? d_emb : nullptr; };
     m->out_valid.resize(m->ops.size());
     for (size_t oi = op_begin; oi < op_end; ++oi) m->out_valid[oi] = 0;
     if (op_begin == 0) m->slot_valid.assign(m->d_slots.size(), 0);
@@ -482,7 +488,8 @@ int run_plan(bn_model* m, const float* d_input, const float* d_minmax, int B, fl
                 break;
             case BN_OP_F32_GAPDENSE:
                 bn::launch_f32_gap_dense((const float*)in0, (float*)out, d_logits, B, p[0], p[1], p[2], p[3],
-                                         (const float*)m->tensor(o.t[0]), (const float*)m->tensor(o.t[1]), s);
+                                         (const float*)m->tensor(o.t[0]), (const float*)m->tensor(o.t[1]), s, (float*)emb_for(o));
+                emb_written += emb_for(o) != nullptr;
                 break;
             case BN_OP_F32_SEGATE:
                 bn::launch_f32_segate((const float*)in0, (float*)out, B, p[0], p[1], p[2], (const float*)m->tensor(o.t[0]), (const float*)m->tensor(o.t[1]),
@@ -636,6 +643,7 @@ int run_plan(bn_model* m, const float* d_input, const float* d_minmax, int B, fl
                 break;
             }
             case BN_OP_I8_TAIL: {
+                const bn::EmbOut eo{d_emb, emb_dtype == BN_EMB_F32, p[BN_OP_EMB_ZP], o.f[BN_OP_EMB_SCALE]};
                 if (bn::g_opt.i8_tail_mfdw && m->tail2_ok[oi]) {
                     bn::Tail2Args t2 = m->tails2[oi];
                     t2.x = (const int8_t*)in0;
@@ -643,7 +651,8 @@ int run_plan(bn_model* m, const float* d_input, const float* d_minmax, int B, fl
                     t2.logits = d_logits;
                     t2.cst = (const int32_t*)m->tensor(o.t[2]);
                     t2.B = B;
-                    if (!bn::launch_i8_tail2(t2, s)) return fail(BN_ERR_DEVICE, "could not raise the LDS limit of the fused tail kernel");
+                    emb_written += emb_for(o) != nullptr;
+                    if (!bn::launch_i8_tail2(t2, s, emb_for(o) ? &eo : nullptr)) return fail(BN_ERR_DEVICE, "could not raise the LDS limit of the fused tail kernel");
                     break;
                 }
                 bn::Tail8Args ta = m->tails[oi];
@@ -652,7 +661,8 @@ int run_plan(bn_model* m, const float* d_input, const float* d_minmax, int B, fl
                 ta.logits = d_logits;
                 ta.cst = (const int32_t*)m->tensor(o.t[0]);
                 ta.B = B;
-                if (!bn::launch_i8_tail(ta, s)) return fail(BN_ERR_DEVICE, "could not raise the LDS limit of the fused tail kernel");
+                emb_written += emb_for(o) != nullptr;
+                if (!bn::launch_i8_tail(ta, s, emb_for(o) ? &eo : nullptr)) return fail(BN_ERR_DEVICE, "could not raise the LDS limit of the fused tail kernel");
                 break;
             }
             case BN_OP_I8_MEAN:
@@ -721,8 +731,16 @@ int run_plan(bn_model* m, const float* d_input, const float* d_minmax, int B, fl
             default:
                 return fail(BN_ERR_UNSUPPORTED, "plan operator %zu has unknown kind %d", oi, o.kind);
         }
+        // unfused pooling in front of the head: its output slot holds the embedding — copy / dequantise it behind the operator
+        if (emb_for(o) && m->out_valid[oi] && (o.kind == BN_OP_I8_MEAN || o.kind == BN_OP_I8_ATTNPOOL || o.kind == BN_OP_F32_GAP || o.kind == BN_OP_F32_ATTNPOOL)) {
+            const bool src_i8 = o.kind == BN_OP_I8_MEAN || o.kind == BN_OP_I8_ATTNPOOL;
+            bn::launch_emb_store(out, src_i8, d_emb, emb_dtype == BN_EMB_F32, B, m->emb_dim, m->emb_scale, m->emb_zp, s);
+            ++emb_written;
+        }
     }
     HIP_TRY(hipGetLastError());
+    if (d_emb && op_end == m->ops.size() && emb_written != 1)
+        return fail(BN_ERR_UNSUPPORTED, "%d marked operators stored the embedding on this path (expected exactly one)", emb_written);
     return BN_OK;
 }
 
@@ -886,6 +904,26 @@ int bn_model_load(bn_ctx* ctx, const void* blob, size_t nbytes, bn_model** out) 
     if (int rc = parse_blob(blob, nbytes, m->hdr, m->slots, m->tensors, m->ops)) {
         delete m;
         return rc;
+    }
+    // the embedding mark: only on the pooling operators in front of a head (and the fused kernels that pool on chip), all of one width / quantisation
+    for (size_t oi = 0; oi < m->ops.size(); ++oi) {
+        const OpRec& o = m->ops[oi];
+        if (o.p[BN_OP_EMB_TAG] != BN_EMB_OP) continue;
+        const int* p = o.p;
+        const int width = o.kind == BN_OP_I8_TAIL ? p[10] : (o.kind == BN_OP_I8_MEAN || o.kind == BN_OP_I8_ATTNPOOL || o.kind == BN_OP_F32_GAP ||
+                                                             o.kind == BN_OP_F32_ATTNPOOL || o.kind == BN_OP_F32_GAPDENSE) ? p[1] : -1;
+        const bool i8 = o.kind == BN_OP_I8_TAIL || o.kind == BN_OP_I8_MEAN || o.kind == BN_OP_I8_ATTNPOOL;
+        const float sc = i8 ? o.f[BN_OP_EMB_SCALE] : 1.0f;
+        const int zp = i8 ? p[BN_OP_EMB_ZP] : 0;
+        const bool same = m->emb_dim == 0 || (m->emb_dim == width && m->emb_scale == sc && m->emb_zp == zp);
+        if (width <= 0 || width % 4 || width != p[BN_OP_EMB_DIM] || i8 != (m->hdr.dtype == BN_DTYPE_I8) || !same || (i8 && !(sc > 0.0f)) ||
+            zp < -128 || zp > 127 || (o.kind != BN_OP_I8_TAIL && o.kind != BN_OP_F32_GAPDENSE && o.out < 0)) {
+            delete m;
+            return fail(BN_ERR_FORMAT, "operator %zu (kind %d): malformed embedding mark", oi, o.kind);
+        }
+        m->emb_dim = width;
+        m->emb_scale = sc;
+        m->emb_zp = zp;
     }
     const BlobHeader& h = m->hdr;
     const char* base = (const char*)blob;
@@ -1187,9 +1225,61 @@ int bn_mel_spectrogram(bn_ctx* ctx, const float* d_audio, int B, int T, int n_ff
     return BN_OK;
 }
 
+// the checks of an embedding request; *esize = bytes per embedding value
+static int emb_check(const bn_model* m, const void* d_emb, int emb_dtype, size_t* esize) {
+    *esize = 0;
+    if (!d_emb) return BN_OK;
+    if (m->emb_dim <= 0) return fail(BN_ERR_UNSUPPORTED, "this model's plan marks no embedding operator (lower it with this build)");
+    if (emb_dtype != BN_EMB_F32 && emb_dtype != BN_EMB_I8) return fail(BN_ERR_ARG, "unknown embedding dtype %d", emb_dtype);
+    if (emb_dtype == BN_EMB_I8 && m->hdr.dtype != BN_DTYPE_I8) return fail(BN_ERR_ARG, "BN_EMB_I8 needs an INT8 plan; float32 plans give BN_EMB_F32");
+    if ((uintptr_t)d_emb % (emb_dtype == BN_EMB_I8 ? 4 : 16)) return fail(BN_ERR_ARG, "d_emb must be 16-byte (float32) / 4-byte (int8) aligned");
+    *esize = emb_dtype == BN_EMB_I8 ? 1 : 4;
+    return BN_OK;
+}
+
+static int forward_impl(bn_model* m, const float* d_input, const float* d_minmax, int B, float* d_scores, float* d_logits, void* d_emb,
+                        int emb_dtype, void* stream);
+static int infer_audio_impl(bn_model* m, const float* d_audio, int B, int T, int hop, float* d_scores, float* d_logits, void* d_emb,
+                            int emb_dtype, void* stream);
+
 int bn_forward(bn_model* m, const float* d_input, const float* d_minmax, int B, float* d_scores, float* d_logits,
                void* stream) {
+    return forward_impl(m, d_input, d_minmax, B, d_scores, d_logits, nullptr, BN_EMB_F32, stream);
+}
+
+int bn_forward_embed(bn_model* m, const float* d_input, const float* d_minmax, int B, float* d_scores, float* d_logits, void* d_emb,
+                     int emb_dtype, void* stream) {
+    return forward_impl(m, d_input, d_minmax, B, d_scores, d_logits, d_emb, emb_dtype, stream);
+}
+
+int bn_infer_audio(bn_model* m, const float* d_audio, int B, int T, int hop, float* d_scores, float* d_logits,
+                   void* stream) {
+    return infer_audio_impl(m, d_audio, B, T, hop, d_scores, d_logits, nullptr, BN_EMB_F32, stream);
+}
+
+int bn_infer_audio_embed(bn_model* m, const float* d_audio, int B, int T, int hop, float* d_scores, float* d_logits, void* d_emb,
+                         int emb_dtype, void* stream) {
+    return infer_audio_impl(m, d_audio, B, T, hop, d_scores, d_logits, d_emb, emb_dtype, stream);
+}
+
+int bn_model_get_embedding_info(const bn_model* m, int* dim, int* dtype, float* scale, int* zero_point) {
     if (!m) return fail(BN_ERR_ARG, "null model");
+    if (m->emb_dim <= 0) return fail(BN_ERR_UNSUPPORTED, "this model's plan marks no embedding operator (lower it with this build)");
+    if (dim) *dim = m->emb_dim;
+    if (dtype) *dtype = m->hdr.dtype == BN_DTYPE_I8 ? BN_EMB_I8 : BN_EMB_F32;
+    if (scale) *scale = m->emb_scale;
+    if (zero_point) *zero_point = m->emb_zp;
+    return BN_OK;
+}
+
+}  // extern "C"
+
+static int forward_impl(bn_model* m, const float* d_input, const float* d_minmax, int B, float* d_scores, float* d_logits, void* d_emb,
+                        int emb_dtype, void* stream) {
+    if (!m) return fail(BN_ERR_ARG, "null model");
+    size_t esize = 0;
+    if (int rc = emb_check(m, d_emb, emb_dtype, &esize)) return rc;
+    const size_t D = (size_t)m->emb_dim;
     if (int rc = check_device(m->ctx)) return rc;
     if (!d_input || !d_scores) return fail(BN_ERR_ARG, "null device pointer");
     if (B < 0 || B > m->ctx->max_batch)
@@ -1200,15 +1290,19 @@ int bn_forward(bn_model* m, const float* d_input, const float* d_minmax, int B, 
     for (int b0 = 0; b0 < B; b0 += kMaxGridBatch) {
         const int nb = B - b0 < kMaxGridBatch ? B - b0 : kMaxGridBatch;
         if (int rc = run_plan(m, d_input + b0 * in_stride, d_minmax ? d_minmax + 2 * (size_t)b0 : nullptr, nb,
-                              d_scores + b0 * C, d_logits ? d_logits + b0 * C : nullptr, s))
+                              d_scores + b0 * C, d_logits ? d_logits + b0 * C : nullptr, d_emb ? (char*)d_emb + b0 * D * esize : nullptr,
+                              emb_dtype, s))
             return rc;
     }
     return BN_OK;
 }
 
-int bn_infer_audio(bn_model* m, const float* d_audio, int B, int T, int hop, float* d_scores, float* d_logits,
-                   void* stream) {
+static int infer_audio_impl(bn_model* m, const float* d_audio, int B, int T, int hop, float* d_scores, float* d_logits, void* d_emb,
+                            int emb_dtype, void* stream) {
     if (!m) return fail(BN_ERR_ARG, "null model");
+    size_t esize = 0;
+    if (int rc = emb_check(m, d_emb, emb_dtype, &esize)) return rc;
+    const size_t D = (size_t)m->emb_dim;
     if (m->hdr.input_kind != BN_INPUT_SPECTROGRAM)
         return fail(BN_ERR_UNSUPPORTED, "bn_infer_audio needs a hybrid-frontend model; feed waveforms to bn_forward");
     if (B < 0 || B > m->ctx->max_batch)
@@ -1227,7 +1321,7 @@ int bn_infer_audio(bn_model* m, const float* d_audio, int B, int T, int hop, flo
         for (int b0 = 0; b0 < B; b0 += kMaxGridBatch) {
             const int nb = B - b0 < kMaxGridBatch ? B - b0 : kMaxGridBatch;
             if (int rc = run_plan(m, nullptr, nullptr, nb, d_scores + b0 * C, d_logits ? d_logits + b0 * C : nullptr,
-                                  (hipStream_t)stream, d_audio + (size_t)b0 * T, T, hop))
+                                  d_emb ? (char*)d_emb + b0 * D * esize : nullptr, emb_dtype, (hipStream_t)stream, d_audio + (size_t)b0 * T, T, hop))
                 return rc;
         }
         return BN_OK;
@@ -1276,8 +1370,8 @@ int bn_infer_audio(bn_model* m, const float* d_audio, int B, int T, int hop, flo
             m->guard_audio = d_audio + (size_t)b0 * T;
             m->guard_T = T;
             m->guard_hop = hop;
-            rc = run_plan(m, m->d_spec + b0 * in_stride, m->d_minmax + 2 * (size_t)b0, nb, d_scores + b0 * C, d_logits ? d_logits + b0 * C : nullptr, s,
-                          nullptr, 0, 0, 0, (size_t)-1, (size_t)b0);
+            rc = run_plan(m, m->d_spec + b0 * in_stride, m->d_minmax + 2 * (size_t)b0, nb, d_scores + b0 * C, d_logits ? d_logits + b0 * C : nullptr,
+                          d_emb ? (char*)d_emb + b0 * D * esize : nullptr, emb_dtype, s, nullptr, 0, 0, 0, (size_t)-1, (size_t)b0);
             if (rc != BN_OK) break;
         }
     }
@@ -1287,6 +1381,8 @@ int bn_infer_audio(bn_model* m, const float* d_audio, int B, int T, int hop, flo
     m->last_B = rc == BN_OK ? B : 0;
     return rc;
 }
+
+extern "C" {
 
 int bn_debug_tail_form(const bn_model* m, int* form, int* lds_bytes) {
     if (!m || !form || !lds_bytes) return fail(BN_ERR_ARG, "null argument");
@@ -1628,9 +1724,9 @@ int bn_get_option(const char* name, int* value) {
 
 const char* bn_kernel_names(void) {
     return "ingest_resample_kernel\ningest_decimate_kernel\ningest_peak_kernel\ningest_chunks_kernel\nchunk_peaknorm_kernel\npool_scores_kernel\nstft512_mag_kernel\nspec_normalize_kernel\nmelspec_finish_kernel\nf32_mel_kernel\nf32_melfin_kernel\nf32_mag_kernel\nf32_rawfe_kernel\nf32_stem_kernel\nf32_dw_kernel\n"
-           "f32_pw_kernel\nf32_pw_ws_kernel\nf32_dwpw_kernel\nf32_dwpw_wave_kernel\nf32_strip_kernel\nf32_front_strip_kernel\nf32_front2_kernel\nf32_pwdw_kernel\nf32_dw_stream_kernel\nf32_front_kernel\nf32_gap_kernel\nf32_gap_dense_kernel\nf32_dense_kernel\nf32_segate_kernel\nf32_scale_kernel\nf32_attnpool_kernel\n"
-           "i8_quant_kernel\ni8_mel_kernel\ni8_stem_kernel\ni8_dw_kernel\ni8_pw_kernel\ni8_dwpw_kernel\ni8_mel_mfma_kernel\ni8_strip_kernel\ni8_strip_mf_kernel\ni8_front_strip_kernel\ni8_front_kernel\ni8_tail_kernel\ni8_tail2_kernel\ni8_mid2_kernel\ni8_mean_kernel\ni8_fc_kernel\ni8_scale_kernel\ni8_maxnorm_kernel\ni8_rawfe_kernel\ni8_pwdw_kernel\ni8_dw_stream_kernel\ni8_stem_stream_kernel\ni8_segate_kernel\ni8_pw_wave_kernel\ni8_pw_lds_kernel\ni8_attnpool_kernel\n"
-           "i8_head_kernel\ni8_head_softmax_kernel";
+           "f32_pw_kernel\nf32_pw_ws_kernel\nf32_dwpw_kernel\nf32_dwpw_wave_kernel\nf32_strip_kernel\nf32_front_strip_kernel\nf32_front2_kernel\nf32_pwdw_kernel\nf32_dw_stream_kernel\nf32_front_kernel\nf32_gap_kernel\nf32_gap_dense_kernel\nf32_gap_dense_emb_kernel\nf32_dense_kernel\nf32_segate_kernel\nf32_scale_kernel\nf32_attnpool_kernel\n"
+           "i8_quant_kernel\ni8_mel_kernel\ni8_stem_kernel\ni8_dw_kernel\ni8_pw_kernel\ni8_dwpw_kernel\ni8_mel_mfma_kernel\ni8_strip_kernel\ni8_strip_mf_kernel\ni8_front_strip_kernel\ni8_front_kernel\ni8_tail_kernel\ni8_tail_emb_kernel\ni8_tail2_kernel\ni8_tail2_emb_kernel\ni8_mid2_kernel\ni8_mean_kernel\ni8_fc_kernel\ni8_scale_kernel\ni8_maxnorm_kernel\ni8_rawfe_kernel\ni8_pwdw_kernel\ni8_dw_stream_kernel\ni8_stem_stream_kernel\ni8_segate_kernel\ni8_pw_wave_kernel\ni8_pw_lds_kernel\ni8_attnpool_kernel\n"
+           "i8_head_kernel\ni8_head_softmax_kernel\nemb_store_kernel";
 }
 
 }  // extern "C"

@@ -90,6 +90,16 @@ struct TensorRec {
 #define BN_MID_COVERED 0x7A11000E
 #define BN_MID_OP 0x7A11000F
 
+// OpRec.p[BN_OP_EMB_TAG] = BN_EMB_OP: the operator's result is the model's embedding, the pooled vector that feeds the classifier head
+// (INT8 MEAN / attention pooling, float32 GAP / attention pooling) — or, on a fused operator (BN_OP_I8_TAIL, BN_OP_F32_GAPDENSE), the
+// vector it pools on chip.  p[BN_OP_EMB_DIM] = its width D; INT8 plans: p[BN_OP_EMB_ZP] = its zero point, f[BN_OP_EMB_SCALE] = its scale.
+// Only the kinds above carry the tag, so the three p slots and the f slot are free on them.  Squeeze-excite MEANs are never tagged.
+#define BN_OP_EMB_TAG 36
+#define BN_OP_EMB_DIM 35
+#define BN_OP_EMB_ZP 34
+#define BN_OP_EMB_SCALE 7
+#define BN_EMB_OP 0x7A110010
+
 #define BN_OP_NP 40
 #define BN_OP_NT 16
 #define BN_OP_NF 8

@@ -471,9 +471,11 @@ __global__ void f32_dense_kernel(const float* __restrict__ x, float* __restrict_
 // contraction for up to 64 x 4 outputs and the partial sums meet in LDS (reference: birdnet_stm32/models/dscnn.py:256-261).
 // Per chunk the operations and their order are those of the separate GAP and Dense kernels.
 constexpr int kGdChunks = 4;
-__global__ __launch_bounds__(256) void f32_gap_dense_kernel(const float* __restrict__ x, float* __restrict__ scores,
-                                                            float* __restrict__ logits, int B, int P, int Cin, int Cout, int act,
-                                                            const float* __restrict__ w, const float* __restrict__ bias) {
+// EMB: the pooled vectors also go to emb [B][Cin] (f32_gap_dense_emb_kernel); the scores-only kernel is the instantiation without the store.
+template <bool EMB>
+__device__ __forceinline__ void f32_gap_dense_body(const float* __restrict__ x, float* __restrict__ scores, float* __restrict__ logits, int B, int P,
+                                                   int Cin, int Cout, int act, const float* __restrict__ w, const float* __restrict__ bias,
+                                                   float* __restrict__ emb) {
     extern __shared__ float sm[];  // [NC][Cin] pooled, [NC][4][Cout] partial sums, [NC][Cout] logits
     float* pooled = sm;
     float* part = sm + kGdChunks * Cin;
@@ -487,6 +489,7 @@ __global__ __launch_bounds__(256) void f32_gap_dense_kernel(const float* __restr
 #pragma unroll 16
         for (int i = 0; i < P; ++i) s += p[(size_t)i * Cin];  // summed in position order; sixteen loads in flight
         pooled[cb * Cin + c] = s / (float)P;
+        if constexpr (EMB) emb[(size_t)(b0 + cb) * Cin + c] = s / (float)P;
     }
     for (int item = nc * Cin + tid; item < kGdChunks * Cin; item += 256) pooled[item] = 0.0f;  // chunks past the batch end
     __syncthreads();
@@ -530,6 +533,17 @@ __global__ __launch_bounds__(256) void f32_gap_dense_kernel(const float* __restr
         }
         scores[(size_t)(b0 + cb) * Cout + n] = out;
     }
+}
+
+__global__ __launch_bounds__(256) void f32_gap_dense_kernel(const float* __restrict__ x, float* __restrict__ scores,
+                                                            float* __restrict__ logits, int B, int P, int Cin, int Cout, int act,
+                                                            const float* __restrict__ w, const float* __restrict__ bias) {
+    f32_gap_dense_body<false>(x, scores, logits, B, P, Cin, Cout, act, w, bias, nullptr);
+}
+__global__ __launch_bounds__(256) void f32_gap_dense_emb_kernel(const float* __restrict__ x, float* __restrict__ scores,
+                                                                float* __restrict__ logits, int B, int P, int Cin, int Cout, int act,
+                                                                const float* __restrict__ w, const float* __restrict__ bias, float* __restrict__ emb) {
+    f32_gap_dense_body<true>(x, scores, logits, B, P, Cin, Cout, act, w, bias, emb);
 }
 
 inline dim3 grid1d(long total, int block) { return dim3((unsigned)((total + block - 1) / block)); }
@@ -606,9 +620,13 @@ void launch_f32_dense(const float* x, float* scores, float* logits, int B, int C
 }
 
 void launch_f32_gap_dense(const float* x, float* scores, float* logits, int B, int P, int Cin, int Cout, int act, const float* w,
-                          const float* bias, hipStream_t s) {
-    hipLaunchKernelGGL(f32_gap_dense_kernel, dim3((B + kGdChunks - 1) / kGdChunks), dim3(256),
-                       kGdChunks * (Cin + 5 * Cout) * sizeof(float), s, x, scores, logits, B, P, Cin, Cout, act, w, bias);
+                          const float* bias, hipStream_t s, float* emb) {
+    if (emb)
+        hipLaunchKernelGGL(f32_gap_dense_emb_kernel, dim3((B + kGdChunks - 1) / kGdChunks), dim3(256),
+                           kGdChunks * (Cin + 5 * Cout) * sizeof(float), s, x, scores, logits, B, P, Cin, Cout, act, w, bias, emb);
+    else
+        hipLaunchKernelGGL(f32_gap_dense_kernel, dim3((B + kGdChunks - 1) / kGdChunks), dim3(256),
+                           kGdChunks * (Cin + 5 * Cout) * sizeof(float), s, x, scores, logits, B, P, Cin, Cout, act, w, bias);
 }
 
 void launch_f32_attnpool(const float* x, float* y, int B, int P, int C, const float* score, hipStream_t s) {

@@ -309,7 +309,8 @@ __device__ __forceinline__ void tail_block(const Tail8Layer& L, const Tail8Args&
 #endif
 }
 
-__global__ __launch_bounds__(kTailThreads) void i8_tail_kernel(Tail8Args a) {
+template <bool EMB>
+__device__ __forceinline__ void tail_main(const Tail8Args& a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int ngroups = (a.B + kTailG - 1) / kTailG;
     for (int grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
@@ -326,10 +327,14 @@ __global__ __launch_bounds__(kTailThreads) void i8_tail_kernel(Tail8Args a) {
             else if (L.Cin == 128) tail_block<128, 256, 2, 8, 16, false, false>(L, a, lds, chunk0, slot);
             else tail_block<256, 256, 1, 4, 8, true, false>(L, a, lds, chunk0, slot);
         }
-        tail_head<kTailThreads, 4>(a, lds, chunk0);
+        tail_head<kTailThreads, 4, Tail8Args, EMB>(a, lds, chunk0);
         __syncthreads();  // the next group overwrites the maps
     }
 }
+
+__global__ __launch_bounds__(kTailThreads) void i8_tail_kernel(Tail8Args a) { tail_main<false>(a); }
+// the same with the embedding output (a.emb non-null)
+__global__ __launch_bounds__(kTailThreads) void i8_tail_emb_kernel(WithEmb<Tail8Args> w) { tail_main<true>(w.a); }
 
 // first-fit allocator over the workgroup's LDS: `used` holds [begin, end) intervals that must stay intact
 struct Span {
@@ -448,13 +453,17 @@ extern "C" __attribute__((visibility("default"))) int bn_debug_tail_stamps(long 
 }
 #endif
 
-bool launch_i8_tail(Tail8Args a, hipStream_t s) {
+bool launch_i8_tail(Tail8Args a, hipStream_t s, const EmbOut* emb) {
     if (!g_opt.i8_tail_fclds) a.fcw_off = -1;
-    if (!ensure_dynamic_lds(reinterpret_cast<const void*>(i8_tail_kernel), 160 * 1024)) return false;
+    const void* k = emb ? reinterpret_cast<const void*>(i8_tail_emb_kernel) : reinterpret_cast<const void*>(i8_tail_kernel);
+    if (!ensure_dynamic_lds(k, 160 * 1024)) return false;
     const int ngroups = (a.B + kTailG - 1) / kTailG;
     int cus = 256;
     const int grid = ngroups < cus ? ngroups : cus;  // one workgroup per CU (its LDS), each walks over its share of the chunk groups
-    hipLaunchKernelGGL(i8_tail_kernel, dim3(grid), dim3(kTailThreads), (size_t)a.lds_bytes, s, a);
+    if (emb)
+        hipLaunchKernelGGL(i8_tail_emb_kernel, dim3(grid), dim3(kTailThreads), (size_t)a.lds_bytes, s, WithEmb<Tail8Args>{a, *emb});
+    else
+        hipLaunchKernelGGL(i8_tail_kernel, dim3(grid), dim3(kTailThreads), (size_t)a.lds_bytes, s, a);
     return true;
 }
 

@@ -100,6 +100,9 @@ __device__ __forceinline__ int rq_signed(int x, int m2, long c, int e_packed, in
 //   MEAN: thread (chunk slot, channel quad) walks the positions with one dword read each (waves 0-3);
 //   FULLY_CONNECTED on the matrix cores: wave w owns the class tile 16 w .., its A fragments come straight from memory (requested before the
 //   MEAN, 1 KB per k-step, contiguous), B = the pooled vectors from LDS (column n = chunk slot n & 3: columns 4..15 repeat, lanes n < 4 store).
+// EMB: the pooled vectors also go to the embedding output of the WithEmb<Tail2Args> argument (i8_tail2_emb_kernel); the scores-only kernel is
+// the instantiation without the store.
+template <bool EMB>
 __device__ __forceinline__ void tail2_head(const Tail2Args& a_, unsigned char* lds, int chunk0, int stamp_slot = -1) {
 #ifdef BN_TAIL_STAMPS
     long long st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -142,6 +145,19 @@ __device__ __forceinline__ void tail2_head(const Tail2Args& a_, unsigned char* l
         const int q[4] = {mean_q(s0, a.P, a.mean_zp_in, a.mean_mult, a.mean_shift, a.mean_zp_out), mean_q(s1, a.P, a.mean_zp_in, a.mean_mult, a.mean_shift, a.mean_zp_out),
                           mean_q(s2, a.P, a.mean_zp_in, a.mean_mult, a.mean_shift, a.mean_zp_out), mean_q(s3, a.P, a.mean_zp_in, a.mean_mult, a.mean_shift, a.mean_zp_out)};
         reinterpret_cast<int*>(lds + a.mean_off)[i] = pack4(q);
+        if constexpr (EMB) {   // (the output, its form and dequantisation come through the kernarg pointer as well: WithEmb<Tail2Args>)
+            const EmbOut& eo = reinterpret_cast<const WithEmb<Tail2Args>*>(ap)->e;
+            const int chunk = chunk0 + gq;
+            if (chunk < a.B) {
+                const size_t e = (size_t)chunk * C + 4 * cq;
+                if (eo.f32)
+                    *reinterpret_cast<float4*>(reinterpret_cast<float*>(eo.emb) + e) =
+                        make_float4((float)(q[0] - eo.zp) * eo.scale, (float)(q[1] - eo.zp) * eo.scale, (float)(q[2] - eo.zp) * eo.scale,
+                                    (float)(q[3] - eo.zp) * eo.scale);
+                else
+                    *reinterpret_cast<int*>(reinterpret_cast<int8_t*>(eo.emb) + e) = pack4(q);
+            }
+        }
     }
     __syncthreads();
 #ifdef BN_TAIL_STAMPS
@@ -416,7 +432,8 @@ __device__ __forceinline__ void tail2_block(const Tail2Layer& L, const Tail2Args
 #endif
 }
 
-__global__ __launch_bounds__(kTail2Threads) void i8_tail2_kernel(Tail2Args a) {
+template <bool EMB>
+__device__ __forceinline__ void tail2_main(const Tail2Args& a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int ngroups = (a.B + kTailG - 1) / kTailG;
     {   // the first block's depthwise part, once; afterwards every block finds its own staged by its predecessor
@@ -447,13 +464,17 @@ __global__ __launch_bounds__(kTail2Threads) void i8_tail2_kernel(Tail2Args a) {
         const int gi = (grp - (int)blockIdx.x) / (int)gridDim.x;
         if ((int)blockIdx.x < 8 && gi < 4 && g_tail2_stamps) hslot = ((int)blockIdx.x * 4 + gi) * 8 + 6;
 #endif
-        tail2_head(a, lds, chunk0, hslot);
+        tail2_head<EMB>(a, lds, chunk0, hslot);
         __syncthreads();  // the next group overwrites the maps
 #ifdef BN_TAIL_STAMPS
         if (hslot >= 0 && (threadIdx.x & 63) == 0) g_tail2_stamps[((size_t)hslot * kTail2Waves + (threadIdx.x >> 6)) * 8 + 6] = (long long)__builtin_amdgcn_s_memrealtime();
 #endif
     }
 }
+
+__global__ __launch_bounds__(kTail2Threads) void i8_tail2_kernel(Tail2Args a) { tail2_main<false>(a); }
+// the same with the embedding output: the pooled vectors are stored where they are packed for the classifier
+__global__ __launch_bounds__(kTail2Threads) void i8_tail2_emb_kernel(WithEmb<Tail2Args> w) { tail2_main<true>(w.a); }
 
 // Stage 2 of the shipped graph with the same blocks: kMidG = 2 chunks per workgroup (a 16 x 32 map of 64 channels is 40 KB in LDS), the first
 // block's taps from memory, the last map written back for the tail kernel (coalesced 16-byte pieces).
@@ -635,11 +656,15 @@ long tail2_const_words(const Tail2Args& a, bool mid) {
     return need;
 }
 
-bool launch_i8_tail2(Tail2Args a, hipStream_t s) {
-    if (!ensure_dynamic_lds(reinterpret_cast<const void*>(i8_tail2_kernel), 160 * 1024)) return false;
+bool launch_i8_tail2(Tail2Args a, hipStream_t s, const EmbOut* emb) {
+    const void* k = emb ? reinterpret_cast<const void*>(i8_tail2_emb_kernel) : reinterpret_cast<const void*>(i8_tail2_kernel);
+    if (!ensure_dynamic_lds(k, 160 * 1024)) return false;
     const int ngroups = (a.B + kTailG - 1) / kTailG;
     const int grid = ngroups < 256 ? ngroups : 256;  // one workgroup per CU (its LDS), each walks over its share of the chunk groups
-    hipLaunchKernelGGL(i8_tail2_kernel, dim3(grid), dim3(kTail2Threads), (size_t)a.lds_bytes, s, a);
+    if (emb)
+        hipLaunchKernelGGL(i8_tail2_emb_kernel, dim3(grid), dim3(kTail2Threads), (size_t)a.lds_bytes, s, WithEmb<Tail2Args>{a, *emb});
+    else
+        hipLaunchKernelGGL(i8_tail2_kernel, dim3(grid), dim3(kTail2Threads), (size_t)a.lds_bytes, s, a);
     return true;
 }
 

@@ -222,7 +222,10 @@ void launch_f32_front(const float* fe, float* y, int B, int H0, int W0, int C, i
                       const float* pw_w, const float* pw_b, const float* minmax, const float* wsum, const float* magp, int mag,
                       hipStream_t s);
 void launch_f32_gap_dense(const float* x, float* scores, float* logits, int B, int P, int Cin, int Cout, int act, const float* w,
-                          const float* bias, hipStream_t s);
+                          const float* bias, hipStream_t s, float* emb = nullptr);   // emb: [B][Cin] pooled vectors as well (f32_gap_dense_emb_kernel)
+// the embedding of an operator whose output slot holds it ([B][D], unfused plans): an int8 copy, a float32 dequantisation (q - zp) * scale
+// or a float32 copy (bn_embed.hip).  src_i8: the slot holds int8 bytes; dst_f32: write float32.  D % 4 == 0; dst 16-byte aligned (float32) / 4-byte (int8).
+void launch_emb_store(const void* src, bool src_i8, void* dst, bool dst_f32, int B, int D, float scale, int zp, hipStream_t s);
 void launch_f32_dwpw(const DwPwArgs& a, hipStream_t s);
 // persistent two-role kernel for plain 1x1 convolutions with Cin > 128 (bn_f32_pw.hip); false: not its shape
 bool launch_f32_pw_ws(const DwPwArgs& a, hipStream_t s);
@@ -396,11 +399,22 @@ struct Tail8Args {
     float s_fc, s_head;
     int lds_bytes;
     int fcw_off;          // LDS copy of the classifier matrix for the head, rows of C / 4 + 1 dwords (-1: read it from memory); overlays the last block's weights
-    Tail8Layer L[8];
+    Tail8Layer L[8];};
+// The embedding output of the fused tail kernels: the pooled vector the head reads, stored by the kernels' embedding instantiations
+// (i8_tail_emb_kernel, i8_tail2_emb_kernel), whose kernel argument is WithEmb<Args> — the scores-only kernels keep their argument layout.
+struct EmbOut {
+    void* emb;            // [B][C] int8 bytes (f32 = 0; 4-byte aligned) or float32 (q - zp) * scale (f32 = 1; 16-byte aligned)
+    int f32, zp;
+    float scale;
+};
+template <class Args>
+struct WithEmb {
+    Args a;               // (first: the kernel-argument pointer addresses both)
+    EmbOut e;
 };
 bool tail_plan(const int32_t* desc, int n_words, int n_layers, Tail8Args& a);  // a.NC must be set; false = not a topology / size the kernel takes
 long tail_const_words(const Tail8Args& a);
-bool launch_i8_tail(Tail8Args a, hipStream_t s);
+bool launch_i8_tail(Tail8Args a, hipStream_t s, const EmbOut* emb = nullptr);   // emb: also store the pooled vectors
 
 // The same back half with the DEPTHWISE stage on the matrix cores too (bn_i8_tail2.hip): 8 waves per workgroup, maps in place.
 constexpr int kTail2Waves = 8;
@@ -427,11 +441,10 @@ struct Tail2Args {
     float s_fc, s_head;
     int lds_bytes;
     int fcw_off;
-    Tail2Layer L[8];
-};
+    Tail2Layer L[8];};
 bool tail2_plan(const int32_t* desc, int n_words, int n_layers, Tail2Args& a, bool mid = false);  // a.NC must be set (tail); mid: the stage-2 chain, no head
 long tail2_const_words(const Tail2Args& a, bool mid = false);
-bool launch_i8_tail2(Tail2Args a, hipStream_t s);
+bool launch_i8_tail2(Tail2Args a, hipStream_t s, const EmbOut* emb = nullptr);
 bool launch_i8_mid2(Tail2Args a, hipStream_t s);
 
 // INT8 stem 3x3 + depthwise 3x3 stride 2 + pointwise in one kernel (bn_i8_fused.hip)

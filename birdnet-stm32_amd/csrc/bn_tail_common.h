@@ -51,7 +51,8 @@ __device__ __forceinline__ long pair(int lo, int hi) { return __builtin_bit_cast
 
 // MEAN + FULLY_CONNECTED + head for the workgroup's chunks.  (As a real function call it costs a stack copy of the arguments: 1168 B of
 // scratch per lane — it stays inlined.)
-template <int NTHREADS, int PAD, class Args>
+// EMB: the pooled bytes also go to the embedding output of the WithEmb<Args> kernel argument (int8 or dequantised float32; i8_tail_emb_kernel).
+template <int NTHREADS, int PAD, class Args, bool EMB = false>
 __device__ __forceinline__ void tail_head(const Args& a, unsigned char* lds, int chunk0) {
     int tid = threadIdx.x;
     asm volatile("" : "+v"(tid));  // keeps this part's index arithmetic from being hoisted to the top of the kernel and held in registers across
@@ -94,6 +95,28 @@ __device__ __forceinline__ void tail_head(const Args& a, unsigned char* lds, int
         }
     }
     __syncthreads();
+    if constexpr (EMB) {
+        // the pooled bytes of the group ([slot][C] in LDS) to a.emb, four per thread: a dword or a float4 store.  The arguments come through
+        // the kernel-argument pointer (held in registers from the top of the kernel they cost this kernel, at its register cap, scratch)
+        const WithEmb<Args>* ap = (const WithEmb<Args>*)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(ap));
+        const int c4 = ap->a.C / 4;
+        for (int i = tid; i < kTailG * c4; i += NTHREADS) {
+            const int g = i / c4;
+            if (chunk0 + g >= ap->a.B) break;
+            const int q = reinterpret_cast<const int*>(lds + ap->a.mean_off)[i];
+            const size_t e = (size_t)chunk0 * ap->a.C + 4 * (size_t)i;   // (slots are consecutive chunks: [slot][C] is [chunk][C])
+            if (ap->e.f32) {
+                const int zp = ap->e.zp;
+                const float sc = ap->e.scale;
+                *reinterpret_cast<float4*>(reinterpret_cast<float*>(ap->e.emb) + e) =
+                    make_float4((float)((int)(int8_t)q - zp) * sc, (float)((int)(int8_t)(q >> 8) - zp) * sc, (float)((int)(int8_t)(q >> 16) - zp) * sc,
+                                (float)((q >> 24) - zp) * sc);
+            } else {
+                *reinterpret_cast<int*>(reinterpret_cast<int8_t*>(ap->e.emb) + e) = q;
+            }
+        }
+    }
     // ---- FULLY_CONNECTED + head: one thread per (chunk slot, class) ----------------------------------------------------------
     for (int i = tid; i < kTailG * a.NC; i += NTHREADS) {
         const int g = i / a.NC, j = i - g * a.NC;

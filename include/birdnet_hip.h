@@ -139,6 +139,26 @@ BN_API int bn_forward(bn_model* model, const float* d_input, const float* d_minm
 BN_API int bn_infer_audio(bn_model* model, const float* d_audio, int B, int T, int hop,
                    float* d_scores, float* d_logits, void* stream);
 
+/* ---- embeddings: the pooled feature vector in front of the classifier head ------------------------------
+ * The output of the plan operator whose result feeds the classifier: GAP / int8 MEAN or attention pooling (after the optional
+ * embedding convolution), D values per chunk.  Squeeze-excite pools are not embeddings.  The fused kernels store it from where they
+ * pool it; requesting it changes no score.  Forms of d_emb ([B, D]; 16-byte aligned for float32, 4-byte for int8):
+ *   BN_EMB_F32  float32; INT8 plans: the bytes dequantised as (float)(q - zero_point) * scale (float32 arithmetic)
+ *   BN_EMB_I8   the int8 bytes themselves (INT8 plans only: BN_ERR_ARG on a float32 plan)
+ * A plan without a marked embedding operator (older blobs) answers BN_ERR_UNSUPPORTED. */
+#define BN_EMB_F32 0
+#define BN_EMB_I8 1
+
+/* *dim = D, *dtype = BN_EMB_I8 (INT8 plan) or BN_EMB_F32, *scale / *zero_point = the int8 tensor's quantisation (1 / 0 on float32
+ * plans).  Any output pointer may be NULL. */
+BN_API int bn_model_get_embedding_info(const bn_model* model, int* dim, int* dtype, float* scale, int* zero_point);
+
+/* bn_forward / bn_infer_audio that also write the embedding of every chunk to d_emb (NULL: exactly the call without it) */
+BN_API int bn_forward_embed(bn_model* model, const float* d_input, const float* d_minmax, int B, float* d_scores,
+               float* d_logits, void* d_emb, int emb_dtype, void* stream);
+BN_API int bn_infer_audio_embed(bn_model* model, const float* d_audio, int B, int T, int hop, float* d_scores,
+               float* d_logits, void* d_emb, int emb_dtype, void* stream);
+
 /* ---- the steps either side of the path ------------------------- */
 
 /* sample formats of bn_ingest_resample's interleaved PCM (libsndfile's float scaling: /2^15, /2^23, /2^31) */
