@@ -29,7 +29,7 @@ EXPORTS = (
     "bn_kernel_names", "bn_profile_enable", "bn_profile_collect", "bn_ingest_resample", "bn_ingest_chunks",
     "bn_pool_scores", "bn_mel_spectrogram", "bn_profile_only", "bn_chunk_peak_normalize", "bn_set_option", "bn_get_option", "bn_ctx_set_option", "bn_ctx_get_option", "bn_ctx_reset_options", "bn_preload_kernels", "bn_host_alloc_pinned", "bn_host_free_pinned", "bn_rank_orders",
     "bn_blob_check", "bn_debug_requant", "bn_stft_mag_exact", "bn_debug_input_bytes", "bn_debug_guard_stats", "bn_debug_tail_form", "bn_debug_mid_form",
-    "bn_forward_embed", "bn_infer_audio_embed", "bn_model_get_embedding_info",
+    "bn_forward_embed", "bn_infer_audio_embed", "bn_model_get_embedding_info", "bn_ingest_resample_span",
 )  # fmt: skip
 
 EMB_F32, EMB_I8 = 0, 1  # BN_EMB_* (include/birdnet_hip.h)
@@ -100,6 +100,8 @@ def load_library(path: str | None = None):
     lib.bn_profile_collect.argtypes = [c_void_p, POINTER(ctypes.c_double), POINTER(c_int64), c_int]
     lib.bn_ingest_resample.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int64, c_int64,
                                        c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
+    lib.bn_ingest_resample_span.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p,
+                                            c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
     lib.bn_ingest_chunks.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                      c_void_p]
     lib.bn_pool_scores.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p]

@@ -17,6 +17,12 @@ stages that overlap:
 Nothing synchronises the host inside the loop except the ring hand-overs (events).  The chunk scores of all files stay on the GPU;
 the caller pools them (``bn_pool_scores``) once at the end.
 
+**Long files** (``stream_long=True``, opt-in): a file whose read window does not fit one slab, or is longer than one
+``bn_ingest_resample`` launch can index, is cut into *segments* (``plan_segments``): an output range of its window plus the input
+frames those outputs touch.  Segments take the same ring as groups (pinned slab -> copy stream -> device slab); each one is one
+``bn_ingest_resample_span`` launch into a device buffer that holds the file's resampled samples.  Behind its last segment the file's
+chunks are cut and scored in slices of ``group_chunks``.  Device memory: one file's mono samples plus one slice of chunks.
+
 There is no CPU fallback: the module needs ``libbirdnet_hip.so`` and a GPU.  Files that are not plain PCM / float32 WAV (FLAC,
 8-bit, float64, containers only ``soundfile`` reads) are decoded on the host by ``audio.ingest.read_pcm_window`` inside the read
 stage and copied into the slab; their arithmetic still happens on the device.
@@ -43,6 +49,66 @@ from birdnet_stm32.audio.ingest import PCM_F32, PCM_S16, PCM_S24, PCM_S32, _BYTE
 _RAW_FORMATS = {(1, 16): PCM_S16, (1, 24): PCM_S24, (1, 32): PCM_S32, (3, 32): PCM_F32}
 _ALIGN = 256
 MAX_WINDOWS_PER_GROUP = 65535  # bn_ingest_resample's limit per launch
+SPAN_MAX_OUT = 1 << 26         # outputs per bn_ingest_resample_span launch of a streamed file (its block-peak scratch stays <= 256 KiB)
+MONO_BUDGET_BYTES = 16 << 30   # device bytes of one streamed file's resampled samples (~50 h at 22.05 kHz)
+_READ_PIECE = 8 << 20          # a segment is read (or copied) as pieces of this many bytes, in parallel
+
+
+def filter_geometry(sr0: int, sample_rate: int) -> tuple[int, int, int, int]:
+    """``(up, down, taps per phase, leading outputs dropped)`` of ``resample_poly`` from ``sr0`` to ``sample_rate`` (1, 1, 0, 0: same rate)."""
+    if sr0 == sample_rate:
+        return 1, 1, 0, 0
+    g = gcd(int(sr0), int(sample_rate))
+    up, down = int(sample_rate) // g, int(sr0) // g
+    _taps, per_phase, pre = polyphase_filter(up, down)
+    return up, down, int(per_phase), int(pre)
+
+
+def span_inputs(o0: int, o1: int, n_in: int, up: int, down: int, hpp: int, pre: int) -> tuple[int, int]:
+    """Input frames ``[s0, s1)`` that outputs ``[o0, o1)`` of a window of ``n_in`` frames touch, clipped to the window.  Output n reads
+    the ``hpp`` frames ending at ``floor((n + pre) * down / up)`` (the same rate: frame n).  Python integers: exact at any length."""
+    if hpp == 0:
+        lo, hi = o0, o1
+    else:
+        lo = (o0 + pre) * down // up - (hpp - 1)
+        hi = (o1 - 1 + pre) * down // up + 1
+    lo, hi = max(lo, 0), min(hi, n_in)
+    return (lo, hi) if lo < hi else (lo, lo) if lo < n_in else (n_in, n_in)
+
+
+def plan_segments(n_in: int, n_out: int, up: int, down: int, hpp: int, pre: int, frame_bytes: int, budget_bytes: int,
+                  max_out: int = SPAN_MAX_OUT) -> list[tuple[int, int, int, int]]:
+    """Cut the outputs ``[0, n_out)`` of one window into segments ``(o0, o1, s0, s1)``: consecutive output ranges, each as long as its
+    staged input frames ``[s0, s1)`` (``span_inputs``, the filter's halo of ``hpp - 1`` frames included) fit ``budget_bytes`` and at most
+    ``max_out`` outputs.  The segments tile ``[0, n_out)`` without gaps or overlap."""
+    n_in, n_out, up, down, hpp, pre = int(n_in), int(n_out), int(up), int(down), int(hpp), int(pre)
+    frames_budget = int(budget_bytes) // int(frame_bytes)
+    segs, o0 = [], 0
+    while o0 < n_out:
+        lo = span_inputs(o0, o0 + 1, n_in, up, down, hpp, pre)[0]
+        if n_in - lo <= frames_budget:
+            o1 = n_out
+        else:
+            last = lo + frames_budget - 1   # newest frame the budget can stage
+            o1 = last + 1 if hpp == 0 else (last * up + up - 1) // down - pre + 1
+        o1 = min(o1, n_out, o0 + int(max_out))
+        if o1 <= o0:
+            raise ValueError(f"a staging budget of {budget_bytes} bytes cannot hold the {hpp} input frames of one output")
+        s0, s1 = span_inputs(o0, o1, n_in, up, down, hpp, pre)
+        segs.append((o0, o1, s0, s1))
+        o0 = o1
+    return segs
+
+
+def long_files(tab: "FileTable", sample_rate: int, slab_bytes: int) -> np.ndarray:
+    """Files the pipeline streams in ``stream_long`` mode: the read window exceeds one slab, or its positions exceed what one
+    ``bn_ingest_resample`` launch indexes (``(n_out + pre + 4096) * down`` or ``frames * up`` reach 2^32)."""
+    out = np.zeros(len(tab.paths), bool)
+    for i in np.flatnonzero(tab.kind >= 0):
+        up, down, _hpp, pre = filter_geometry(int(tab.sr0[i]), sample_rate)
+        too_far = (int(tab.n_out[i]) + pre + 4096) * down >= 1 << 32 or int(tab.frames[i]) * up >= 1 << 32
+        out[i] = int(tab.nbytes[i]) > slab_bytes or too_far
+    return out
 
 
 def window_counts(total_frames: np.ndarray, sr0: np.ndarray, max_duration) -> np.ndarray:
@@ -111,6 +177,11 @@ class FileTable:
     n_out: np.ndarray       # samples after resampling
     n_chunks: np.ndarray
     decoded: dict = field(default_factory=dict)  # kind 1 windows that had to be decoded to learn their length
+
+    def sub(self, lo: int, hi: int) -> "FileTable":
+        """Files ``[lo, hi)`` as a table of their own."""
+        arrays = ("kind", "fmt", "channels", "sr0", "frames", "file_off", "nbytes", "n_out", "n_chunks")
+        return FileTable(self.paths[lo:hi], *(getattr(self, a)[lo:hi] for a in arrays), {i - lo: w for i, w in self.decoded.items() if lo <= i < hi})
 
 
 def plan_files(paths: list[str], sample_rate: int, chunk_duration: float, chunk_overlap: float, max_duration=60,
@@ -322,6 +393,21 @@ class _Staged:
     read_s: float
 
 
+@dataclass
+class _Segment:
+    """One segment of a streamed file on its way to the GPU."""
+
+    file: int                 # index into the run's file table
+    seg: tuple                # (o0, o1, s0, s1)
+    first: bool
+    last: bool
+    slot: int
+    copied: object
+    h2d_events: tuple
+    read_s: float
+    nbytes: int
+
+
 # Page-locked slabs no pipeline holds at the moment: (address, bytes).  A process keeps them (page-locking costs ~65 us per MiB; every `evaluate`
 # call builds its own EvaluatePipeline) until release_pinned_slabs().
 _SLAB_POOL: list = []
@@ -418,7 +504,8 @@ class EvaluatePipeline:
 
     def __init__(self, runner, sample_rate: int, chunk_duration: float, chunk_overlap: float = 0.0, max_duration=60,
                  slab_bytes: int = 256 << 20, group_chunks: int | None = None, readers: int | None = None, pinned_slabs: int = 3,
-                 ramp: tuple = (8, 4, 2), numa_pin: bool | None = None, read_mode: str | None = None):
+                 ramp: tuple = (8, 4, 2), numa_pin: bool | None = None, read_mode: str | None = None, stream_long: bool = False,
+                 mono_budget_bytes: int = MONO_BUDGET_BYTES):
         import torch
 
         self.torch = torch
@@ -462,6 +549,11 @@ class EvaluatePipeline:
         self.emb_dtype: str | None = None
         self.embeddings = None
         self._emb = None
+        # long files (module docstring): off = every file goes through the grouped path and must fit one slab
+        self.stream_long = bool(stream_long)
+        self.mono_budget_bytes = int(mono_budget_bytes)
+        self._long_mono = self._long_peak = None
+        self._long_payload: dict = {}   # streamed host-decoded file -> its decoded window (producer thread)
 
     def _mark(self, name: str) -> None:
         """Timeline of one run (``BN_PIPELINE_TRACE=1``: ``stats["trace"]`` = [(what, seconds since run() started, thread)]) — where a COLD call's
@@ -609,6 +701,59 @@ class EvaluatePipeline:
         self._mark(f"group {seq}: H2D queued")
         return _Staged(lay, slot, e1, (e0, e1), read_s)
 
+    def _stage_segment(self, tab: FileTable, i: int, seg: tuple, first: bool, last: bool, seq: int) -> _Segment:
+        """Read input frames ``[s0, s1)`` of streamed file ``i`` into the next pinned slab and queue their H2D copy (the ring of
+        ``_stage_group``; no offset table)."""
+        torch = self.torch
+        t0 = time.perf_counter()
+        k = seq % self._n_ring
+        prev = self._pinned_free[k]
+        if prev is not None:
+            prev.synchronize()
+        self._pinned_ready[k].wait()
+        self._wait_s = getattr(self, "_wait_s", 0.0) + (time.perf_counter() - t0)
+        if self._pinned_error is not None:
+            raise self._pinned_error
+        pinned = self._pinned[k]
+        _o0, _o1, s0, s1 = seg
+        fb = _BYTES[int(tab.fmt[i])] * int(tab.channels[i])
+        nbytes = (s1 - s0) * fb
+        pieces = np.arange(0, nbytes, _READ_PIECE, dtype=np.int64)
+        sizes = np.minimum(nbytes - pieces, _READ_PIECE)
+        if int(tab.kind[i]) == 0:
+            status = _pcmio.read_windows([tab.paths[i]] * pieces.shape[0], int(tab.file_off[i]) + s0 * fb + pieces, sizes, pinned.data_ptr(), pieces,
+                                         self.readers)
+            if np.any(status != 0):
+                raise RuntimeError(f"{tab.paths[i]}: reading input frames [{s0}, {s1}) failed")
+        else:
+            payload = self._long_payload.get(i)
+            if payload is None:
+                win = tab.decoded.pop(i, None) or read_pcm_window(tab.paths[i], self.max_duration, self.cd, False)
+                if win is None or win.fmt != tab.fmt[i] or win.channels != tab.channels[i] or win.frames != tab.frames[i]:
+                    raise RuntimeError(f"{tab.paths[i]}: decoding its window again gave a different stream")
+                payload = self._long_payload[i] = np.ascontiguousarray(win.payload)
+            part = payload[s0 * fb : s1 * fb]
+            _pcmio.copy_into([part[a : a + b] for a, b in zip(pieces.tolist(), sizes.tolist())], pinned.data_ptr(), pieces, self.readers)
+            if last:
+                del self._long_payload[i]
+        read_s = time.perf_counter() - t0
+        slot = seq % 2
+        while not self._slot_ready[slot].acquire(timeout=0.1):
+            if self._stop.is_set():
+                raise RuntimeError("evaluate pipeline stopped")
+        with torch.cuda.device(self.dev), torch.cuda.stream(self.copy_stream):
+            free = self._dslab_free[slot]
+            if free is not None:
+                self.copy_stream.wait_event(free)
+            e0 = torch.cuda.Event(enable_timing=True)
+            e1 = torch.cuda.Event(enable_timing=True)
+            e0.record(self.copy_stream)
+            if nbytes:
+                self._dslab[slot][:nbytes].copy_(pinned[:nbytes], non_blocking=True)
+            e1.record(self.copy_stream)
+        self._pinned_free[k] = e1
+        return _Segment(i, seg, first, last, slot, e1, (e0, e1), read_s, nbytes)
+
     # -- stage 3: consumer (caller's thread and stream) -----------------------------------------------------------------------
     def _compute_group(self, st: _Staged, scores, row0: int, batch: int, lat_events: list | None, stats: dict) -> None:
         torch = self.torch
@@ -666,6 +811,87 @@ class EvaluatePipeline:
         self._mark("compute: inference launched")
         stats["_events"].append((st.h2d_events, ev, g.used + 8 * g.tab_len))
 
+    def _compute_segment(self, sg: _Segment, tab: FileTable, stats: dict) -> None:
+        """One ``bn_ingest_resample_span`` launch: outputs ``[o0, o1)`` of the streamed file into its mono buffer, its peak folded in."""
+        torch = self.torch
+        cur = torch.cuda.current_stream(self.dev)
+        i = sg.file
+        if sg.first:
+            n_out = int(tab.n_out[i])
+            if self._long_mono is None or self._long_mono.numel() < n_out:
+                self._long_mono = None
+                self._long_mono = torch.empty(n_out, dtype=torch.float32, device=self.dev)
+            if self._long_peak is None:
+                self._long_peak = torch.empty(1, dtype=torch.float32, device=self.dev)
+            self._long_peak.zero_()
+        cur.wait_event(sg.copied)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        ev[0].record(cur)
+        d_taps, up, down, per_phase, pre = self._filter(int(tab.sr0[i]))
+        o0, o1, s0, s1 = sg.seg
+        _hip.check(self.ctx.lib.bn_ingest_resample_span(
+            self.ctx.handle, self._dslab[sg.slot].data_ptr(), int(tab.fmt[i]), int(tab.channels[i]), s0, s1 - s0, int(tab.frames[i]), o0, o1,
+            d_taps.data_ptr() if d_taps is not None else None, up, down, per_phase, pre, self._long_mono.data_ptr(), self._long_peak.data_ptr(),
+            ctypes.c_void_p(cur.cuda_stream)))
+        done = torch.cuda.Event()
+        done.record(cur)
+        self._dslab_free[sg.slot] = done
+        self._slot_ready[sg.slot].release()
+        ev[1].record(cur)
+        ev[2].record(cur)
+        stats["_events"].append((sg.h2d_events, ev, sg.nbytes))
+
+    def _finish_stream(self, tab: FileTable, i: int, scores, row0: int, stats: dict) -> int:
+        """Chunks of streamed file ``i`` (its resampled samples are complete on the stream) scored in slices of ``group_chunks``."""
+        torch = self.torch
+        lib = self.ctx.lib
+        cur = torch.cuda.current_stream(self.dev)
+        stream = ctypes.c_void_p(cur.cuda_stream)
+        start, valid, _owner, counts, _size = chunk_table_arrays(np.array([int(tab.n_out[i])], np.int64), self.sr, self.cd, self.ov)
+        n = int(counts[0])
+        if not n:
+            return 0
+        d_src = torch.from_numpy(start.astype(np.int64)).to(self.dev)
+        d_valid = torch.from_numpy(valid.astype(np.int32)).to(self.dev)
+        d_owner = torch.zeros(n, dtype=torch.int32, device=self.dev)
+        if self._chunks is None or self._chunks.shape[0] < self.group_chunks:
+            self._chunks = None
+            self._chunks = torch.empty((self.group_chunks, self.size), dtype=torch.float32, device=self.dev)
+        for c0 in range(0, n, self.group_chunks):
+            nc = min(self.group_chunks, n - c0)
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+            ev[0].record(cur)
+            _hip.check(lib.bn_ingest_chunks(self.ctx.handle, self._long_mono.data_ptr(), self._long_peak.data_ptr(), d_src.data_ptr() + 8 * c0,
+                                            d_valid.data_ptr() + 4 * c0, d_owner.data_ptr(), nc, self.size, self._chunks.data_ptr(), stream))
+            ev[1].record(cur)
+            kw = {} if self._emb is None else dict(return_embeddings=True, emb_dtype=self.emb_dtype, emb_out=self._emb[row0 + c0 : row0 + c0 + nc])
+            self.runner.infer_audio_device(self._chunks[:nc], out=scores[row0 + c0 : row0 + c0 + nc], **kw)
+            ev[2].record(cur)
+            stats["_events"].append((None, ev, 0))
+        stats.setdefault("_keep", []).append((d_src, d_valid, d_owner))   # (the launches read them asynchronously)
+        return n
+
+    def _plan_items(self, tab: FileTable, streamed: np.ndarray) -> list:
+        """Work in file order: ``("group", lo, hi)`` for runs of grouped files and ``("stream", i, segments)`` for each streamed file.
+        Refuses, before anything is read, a streamed file whose resampled samples exceed ``mono_budget_bytes``."""
+        items, a, n = [], 0, len(tab.paths)
+        for i in np.flatnonzero(streamed):
+            need = 4 * int(tab.n_out[i])
+            if need > self.mono_budget_bytes:
+                raise ValueError(f"{tab.paths[i]}: its {int(tab.n_out[i])} resampled samples need {need / 2**30:.1f} GiB of device memory, more than "
+                                 f"the budget of {self.mono_budget_bytes / 2**30:.1f} GiB (mono_budget_bytes); lower max_duration")
+        for b in list(np.flatnonzero(streamed)) + [n]:
+            b = int(b)
+            if b > a:
+                ramp = self.ramp if not items else ()
+                items += [("group", a + lo, a + hi) for lo, hi in cut_groups(tab.nbytes[a:b], tab.n_chunks[a:b], self.slab_bytes, self.group_chunks, ramp)]
+            if b < n:
+                up, down, hpp, pre = filter_geometry(int(tab.sr0[b]), self.sr)
+                fb = _BYTES[int(tab.fmt[b])] * int(tab.channels[b])
+                items.append(("stream", b, plan_segments(int(tab.frames[b]), int(tab.n_out[b]), up, down, hpp, pre, fb, self.slab_bytes)))
+            a = b + 1
+        return items
+
     def run(self, paths: list[str], batch_size: int | None = None, measure_latency: bool = False, table: FileTable | None = None):
         """Score every chunk of ``paths``: ``(scores [N, C] CUDA, chunks per file (list), stats dict, per-chunk latencies in ms)``.
 
@@ -692,7 +918,13 @@ class EvaluatePipeline:
                     self.copy_stream = _COPY_STREAMS[key]
             tab = table if table is not None else plan_files(paths, self.sr, self.cd, self.ov, self.max_duration, self.readers)
             stats["probe_s"] = time.perf_counter() - t_start
-            groups = cut_groups(tab.nbytes, tab.n_chunks, self.slab_bytes, self.group_chunks, self.ramp)
+            streamed = long_files(tab, self.sr, self.slab_bytes) if self.stream_long else np.zeros(len(tab.paths), bool)
+            if streamed.any():
+                items = self._plan_items(tab, streamed)
+                groups = [(it[1], it[2]) for it in items if it[0] == "group"]
+            else:
+                groups = cut_groups(tab.nbytes, tab.n_chunks, self.slab_bytes, self.group_chunks, self.ramp)
+                items = [("group", lo, hi) for lo, hi in groups]
             planned = int(tab.n_chunks.sum())
             # size the rings for the largest group once, before the producer starts (nothing is reallocated while copies are in flight)
             cb = np.concatenate([[0], np.cumsum(tab.nbytes + _ALIGN)])
@@ -717,10 +949,20 @@ class EvaluatePipeline:
             def producer():
                 try:
                     torch.cuda.set_device(self.dev)
-                    for seq, (lo, hi) in enumerate(groups):
+                    seq = 0
+                    for it in items:
                         if stop.is_set():
                             break
-                        q.put(self._stage_group(tab, lo, hi, seq))
+                        if it[0] == "group":
+                            q.put(self._stage_group(tab, it[1], it[2], seq))
+                            seq += 1
+                            continue
+                        _, i, segs = it
+                        for j, seg in enumerate(segs):
+                            if stop.is_set():
+                                break
+                            q.put(self._stage_segment(tab, i, seg, j == 0, j == len(segs) - 1, seq))
+                            seq += 1
                     q.put(None)
                 except BaseException as exc:  # noqa: BLE001 - handed to the consumer
                     q.put(exc)
@@ -747,6 +989,13 @@ class EvaluatePipeline:
                         break
                     if isinstance(g, BaseException):
                         raise g
+                    if isinstance(g, _Segment):
+                        self._compute_segment(g, tab, stats)
+                        read_s += g.read_s
+                        if g.last:
+                            counts[g.file] = self._finish_stream(tab, g.file, scores, row, stats)
+                            row += int(counts[g.file])
+                        continue
                     self._compute_group(g, scores, row, int(batch_size or self.runner.max_batch), lat_events, stats)
                     counts[g.lay.lo : g.lay.hi] = g.lay.counts
                     row += g.lay.n_chunks
@@ -764,8 +1013,10 @@ class EvaluatePipeline:
             self._mark("stream drained")
             h2d_ms = ingest_ms = infer_ms = 0.0
             moved = 0
-            for (c0, c1), ev, nbytes in stats.pop("_events"):
-                h2d_ms += c0.elapsed_time(c1)
+            stats.pop("_keep", None)
+            for h2d, ev, nbytes in stats.pop("_events"):
+                if h2d is not None:
+                    h2d_ms += h2d[0].elapsed_time(h2d[1])
                 ingest_ms += ev[0].elapsed_time(ev[1])
                 infer_ms += ev[1].elapsed_time(ev[2])
                 moved += nbytes
@@ -773,7 +1024,7 @@ class EvaluatePipeline:
             if lat_events:
                 for a, b, nb in lat_events:
                     lat.extend([a.elapsed_time(b) / nb] * nb)
-        stats.update(files=len(paths), readable=int((tab.kind >= 0).sum()), chunks=row, groups=len(groups), read_s=read_s, h2d_s=h2d_ms / 1e3,
+        stats.update(files=len(paths), readable=int((tab.kind >= 0).sum()), chunks=row, groups=len(groups), streamed=int(streamed.sum()), read_s=read_s, h2d_s=h2d_ms / 1e3,
                      h2d_bytes=moved, h2d_gbps=(moved / 1e9) / (h2d_ms / 1e3) if h2d_ms > 0 else 0.0, ingest_s=ingest_ms / 1e3,
                      infer_s=infer_ms / 1e3, wall_s=time.perf_counter() - t_start, readers=self.readers, slab_bytes=self.slab_bytes,
                      group_chunks=self.group_chunks, local_world=_pcmio.local_world_size(), numa=dict(self.numa), read_mode=_pcmio.set_read_mode(None), slab_wait_s=round(self._wait_s, 4),

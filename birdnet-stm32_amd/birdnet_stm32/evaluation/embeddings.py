@@ -68,13 +68,6 @@ def _to_host(t) -> np.ndarray:
     return view.numpy().copy()
 
 
-def _sub_table(tab, lo: int, hi: int):
-    from birdnet_stm32.audio.pipeline import FileTable
-
-    arrays = ("kind", "fmt", "channels", "sr0", "frames", "file_off", "nbytes", "n_out", "n_chunks")
-    return FileTable(tab.paths[lo:hi], *(getattr(tab, a)[lo:hi] for a in arrays), {i - lo: w for i, w in tab.decoded.items() if lo <= i < hi})
-
-
 def embedding_blocks(n_chunks: np.ndarray, row_bytes: int, budget_bytes: int) -> list[tuple[int, int]]:
     """Contiguous file ranges ``[lo, hi)`` whose embeddings (``n_chunks`` rows of ``row_bytes`` each) fit ``budget_bytes``; a single
     file larger than the budget forms a block of its own."""
@@ -131,7 +124,7 @@ def embed_files(runner, paths: list[str], chunk_overlap: float = 0.0, max_durati
         for lo, hi in embedding_blocks(counts, row_bytes, budget_bytes):
             if int(counts[lo:hi].sum()) == 0:
                 continue
-            _scores, got, _stats, _lat = pipe.run(list(paths[lo:hi]), table=_sub_table(tab, lo, hi))
+            _scores, got, _stats, _lat = pipe.run(list(paths[lo:hi]), table=tab.sub(lo, hi))
             if list(got) != counts[lo:hi].tolist():
                 raise RuntimeError("the pipeline cut a different number of chunks than it planned")
             emb = pipe.embeddings

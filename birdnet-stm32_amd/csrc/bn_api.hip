@@ -1492,6 +1492,61 @@ int bn_ingest_resample(bn_ctx* ctx, const void* d_pcm, int sample_format, int ch
     return BN_OK;
 }
 
+int bn_ingest_resample_span(bn_ctx* ctx, const void* d_pcm, int sample_format, int channels, int64_t s0, int64_t n_staged, int64_t n_in,
+                            int64_t o0, int64_t o1, const float* d_taps, int up, int down, int taps_per_phase, int n_pre_remove,
+                            float* d_mono_window, float* d_peak, void* stream) {
+    if (int rc = check_device(ctx)) return rc;
+    if (!d_mono_window || !d_peak) return fail(BN_ERR_ARG, "null device pointer");
+    if (sample_format < BN_PCM_S16 || sample_format > BN_PCM_F32) return fail(BN_ERR_ARG, "unknown sample format %d", sample_format);
+    if (channels < 1 || channels > 8)
+        return fail(BN_ERR_UNSUPPORTED, "%d channels: the channel mean is implemented for 1..8 channels", channels);
+    if (s0 < 0 || n_staged < 0 || n_in < 0 || o0 < 0 || o1 < o0 || up < 1 || down < 1 || taps_per_phase < 0 || n_pre_remove < 0)
+        return fail(BN_ERR_ARG, "bad span geometry");
+    if (taps_per_phase > 0 && !d_taps) return fail(BN_ERR_ARG, "null filter");
+    if (taps_per_phase == 0 && up != down) return fail(BN_ERR_ARG, "up=%d down=%d needs a filter", up, down);
+    // 64-bit positions: (n + pre) * down and n_in * up stay far below 2^63 for windows of up to 2^40 frames (years of audio)
+    if (n_in >= ((int64_t)1 << 40) || up >= (1 << 20) || down >= (1 << 20))
+        return fail(BN_ERR_UNSUPPORTED, "window of %lld frames at up=%d down=%d is beyond the resampler's 64-bit positions", (long long)n_in, up, down);
+    const int64_t n_out = taps_per_phase == 0 ? n_in : (n_in * up + down - 1) / down;
+    if (o1 > n_out) return fail(BN_ERR_ARG, "outputs [%lld, %lld) lie beyond the window's %lld outputs", (long long)o0, (long long)o1, (long long)n_out);
+    if (o0 == o1) return BN_OK;
+    const int blk = bn::ingest_resample_block(up, down, taps_per_phase);
+    if ((uint64_t)blk * (uint64_t)down + (uint64_t)up >= ((uint64_t)1 << 32))
+        return fail(BN_ERR_UNSUPPORTED, "down=%d: a workgroup's %d outputs overflow the 32-bit in-workgroup phase index", down, blk);
+    if ((o1 - o0 + blk - 1) / blk >= ((int64_t)1 << 31)) return fail(BN_ERR_UNSUPPORTED, "span of %lld outputs is too long for one launch", (long long)(o1 - o0));
+    // the input frames outputs [o0, o1) touch, clipped to the window, must all be staged
+    int64_t need_lo, need_hi;
+    if (taps_per_phase == 0) {
+        need_lo = o0;
+        need_hi = o1;
+    } else {
+        need_lo = (o0 + n_pre_remove) * (int64_t)down / up - (taps_per_phase - 1);
+        need_hi = (o1 - 1 + n_pre_remove) * (int64_t)down / up + 1;
+    }
+    need_lo = need_lo < 0 ? 0 : need_lo;
+    need_hi = need_hi > n_in ? n_in : need_hi;
+    if (need_lo < need_hi && (need_lo < s0 || need_hi > s0 + n_staged))
+        return fail(BN_ERR_ARG, "outputs [%lld, %lld) need input frames [%lld, %lld); staged are [%lld, %lld)", (long long)o0, (long long)o1,
+                    (long long)need_lo, (long long)need_hi, (long long)s0, (long long)(s0 + n_staged));
+    if (need_lo < need_hi && !d_pcm) return fail(BN_ERR_ARG, "null device pointer");
+    const size_t lds = bn::ingest_resample_lds_bytes(up, down, taps_per_phase, blk);
+    const bool fast_kernel = (up == 1 && (down == 2 || down == 4)) || (up > 1 && up <= 256 && (taps_per_phase == 21 || taps_per_phase == 29 || taps_per_phase == 39));
+    if (lds > (fast_kernel ? 64 : 156) * 1024)
+        return fail(BN_ERR_UNSUPPORTED, "resampling ratio %d/%d needs %zu bytes of LDS per workgroup (limit %d)", up, down, lds, (fast_kernel ? 64 : 156) * 1024);
+    const size_t need = (size_t)((o1 - o0 + blk - 1) / blk);
+    if (need > ctx->block_peaks_elems) {  // growing frees the old buffer, which waits for launches still using it
+        if (ctx->d_block_peaks) HIP_TRY(hipFree(ctx->d_block_peaks));
+        ctx->d_block_peaks = nullptr;
+        ctx->block_peaks_elems = 0;
+        HIP_TRY(hipMalloc(&ctx->d_block_peaks, need * sizeof(float)));
+        ctx->block_peaks_elems = need;
+    }
+    bn::launch_ingest_resample_span(d_pcm, sample_format, channels, (long)s0, (long)n_staged, (long)n_in, (long)o0, (long)o1, d_taps, up, down,
+                                    taps_per_phase, n_pre_remove, d_mono_window, ctx->d_block_peaks, d_peak, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return BN_OK;
+}
+
 int bn_ingest_chunks(bn_ctx* ctx, const float* d_mono, const float* d_peak, const int64_t* d_chunk_src,
                      const int32_t* d_chunk_valid, const int32_t* d_chunk_window, int n_chunks, int chunk_len,
                      float* d_chunks, void* stream) {

@@ -1,7 +1,8 @@
 // bn_ingest.hip — audio ingest in front of the hot path, and score pooling behind it (gfx950).
 //
 //   ingest_resample_kernel : interleaved PCM window(s) -> channel mean -> polyphase FIR resampling -> mono float32,
-//                            plus the absolute peak of every window (atomic max on the float's bit pattern)
+//                            plus the absolute peak of every window (per-workgroup maxima folded by ingest_peak_kernel);
+//                            whole windows, or an output span [o0, o1) of one window whose input is only partly staged
 //   ingest_chunks_kernel   : peak-normalised fixed-length chunks gathered from the resampled windows
 //   pool_scores_kernel     : per-file mean / max / log-mean-exp over the file's rows of the score matrix
 //
@@ -115,22 +116,23 @@ __device__ __forceinline__ bool quad_layout(int ch) {
     return (FMT == 0 || FMT == 3) && ch <= 2;
 }
 
-// Four consecutive mono samples of a window starting at frame k (window-relative; may hang over either end, where the
-// window reads as zeros).
+// Four consecutive mono samples of a window starting at frame k (window-relative; pcm frame in0 + k).  Only frames in
+// [lo, hi) are read: the staged frames within the window.  Everything else reads as zero — outside the window that is the
+// zero padding of upfirdn; inside it the caller guarantees no output needs such a frame (bn_ingest_resample_span checks).
 template <int FMT>
-__device__ __forceinline__ void mono_quad(const void* __restrict__ pcm, long in0, long k, long n_in, int ch, float out[4]) {
-    if (quad_layout<FMT>(ch) && k >= 0 && k + 3 < n_in) {
+__device__ __forceinline__ void mono_quad(const void* __restrict__ pcm, long in0, long k, long lo, long hi, int ch, float out[4]) {
+    if (quad_layout<FMT>(ch) && k >= lo && k + 3 < hi) {
         if (ch == 2) mono_quad_wide<FMT, 2>(pcm, in0 + k, out);
         else mono_quad_wide<FMT, 1>(pcm, in0 + k, out);
         return;
     }
 #pragma unroll
-    for (int e = 0; e < 4; ++e) out[e] = (k + e >= 0 && k + e < n_in) ? mono_frame<FMT>(pcm, in0 + k + e, ch) : 0.0f;
+    for (int e = 0; e < 4; ++e) out[e] = (k + e >= lo && k + e < hi) ? mono_frame<FMT>(pcm, in0 + k + e, ch) : 0.0f;
 }
 
-// Input tile [k_lo, k_lo + tile) of a window -> LDS as mono float32.  A tile that lies inside the window in a wide-load
-// layout is filled by a branch-free loop whose loads the compiler batches (many bytes in flight per thread); a tile
-// touching a window end, or any other layout, goes quad by quad with bounds checks.
+// Input tile [k_lo, k_lo + tile) of a window -> LDS as mono float32.  A tile whose quads (tile rounded up to 4 frames) all lie
+// in the readable frames [lo, hi) in a wide-load layout is filled by a branch-free loop whose loads the compiler batches (many
+// bytes in flight per thread); a tile touching either bound, or any other layout, goes quad by quad with bounds checks.
 template <int FMT, int CH>
 __device__ __forceinline__ void fill_tile_wide(const void* __restrict__ pcm, long frame0, int tile, float* xs, int tid) {
 #pragma unroll 4
@@ -142,9 +144,9 @@ __device__ __forceinline__ void fill_tile_wide(const void* __restrict__ pcm, lon
 }
 
 template <int FMT>
-__device__ __forceinline__ void fill_tile(const void* __restrict__ pcm, long in0, long k_lo, int tile, long n_in, int ch, float* xs,
+__device__ __forceinline__ void fill_tile(const void* __restrict__ pcm, long in0, long k_lo, int tile, long lo, long hi, int ch, float* xs,
                                           int tid) {
-    const bool interior = k_lo >= 0 && k_lo + ((tile + 3) & ~3) <= n_in;
+    const bool interior = k_lo >= lo && k_lo + ((tile + 3) & ~3) <= hi;
     if (interior && quad_layout<FMT>(ch)) {
         if (ch == 2) fill_tile_wide<(FMT == 0 || FMT == 3) ? FMT : 0, 2>(pcm, in0 + k_lo, tile, xs, tid);
         else fill_tile_wide<(FMT == 0 || FMT == 3) ? FMT : 0, 1>(pcm, in0 + k_lo, tile, xs, tid);
@@ -152,7 +154,7 @@ __device__ __forceinline__ void fill_tile(const void* __restrict__ pcm, long in0
     }
     for (int i0 = 4 * tid; i0 < tile; i0 += 1024) {
         float v[4];
-        mono_quad<FMT>(pcm, in0, k_lo + i0, n_in, ch, v);
+        mono_quad<FMT>(pcm, in0, k_lo + i0, lo, hi, ch, v);
         *reinterpret_cast<f32x4*>(xs + i0) = (f32x4){v[0], v[1], v[2], v[3]};
     }
 }
@@ -170,30 +172,63 @@ __device__ __forceinline__ void store_block_peak(float* partial, float vmax, int
 
 struct ResampleArgs {
     const void* __restrict__ pcm;
-    const long* __restrict__ in_off;
-    const long* __restrict__ out_off;
+    const long* __restrict__ in_off;   // [n_windows + 1] frame offsets; nullptr: one window, described by the span fields
+    const long* __restrict__ out_off;  // [n_windows + 1] sample offsets in mono
     const float* __restrict__ taps;  // [up][hpp], phase-major, oldest input sample first
     float* __restrict__ mono;
     float* __restrict__ partial;  // [n_windows][gridDim.x] block maxima
     int ch, up, down, hpp, n_pre_remove;
     int blk;  // outputs per workgroup (a multiple of 1024)
+    // span of one window (in_off == nullptr): pcm holds window frames [s0, s0 + n_staged) of a window of n_win frames; the launch
+    // computes outputs [o0, o1) into mono + n
+    long s0, n_staged, n_win, o0, o1;
 };
+
+// What window blockIdx.y of a launch reads and writes: pcm frame in0 + k holds window frame k, frames [lo, hi) are readable,
+// output n goes to mono[out0 + n], the launch computes outputs [o0, o1).
+struct WinSpan {
+    long in0, lo, hi, out0, o0, o1;
+};
+
+__device__ __forceinline__ WinSpan window_span(const ResampleArgs& a, int f) {
+    if (a.in_off) {
+        const long in0 = a.in_off[f], out0 = a.out_off[f];
+        return {in0, 0, a.in_off[f + 1] - in0, out0, 0, a.out_off[f + 1] - out0};
+    }
+    const long end = a.s0 + a.n_staged;
+    return {-a.s0, a.s0 > 0 ? a.s0 : 0, end < a.n_win ? end : a.n_win, 0, a.o0, a.o1};
+}
+
+// Polyphase position of a workgroup's first output n0: t = (n0 + pre) down in 64 bits, split once into the newest input
+// kbase = t / up and the phase pbase = t % up.  Output n0 + j then has newest input kbase + r / up and phase r % up with
+// r = pbase + j down, which stays in 32 bits within a workgroup (the host checks blk * down + up < 2^32) — the same kmax
+// and phase as (n0 + j + pre) down / up taken whole, so windows of any length index exactly.
+struct Pos {
+    long k_lo;        // first input of the workgroup's tile: kbase - (hpp - 1)
+    unsigned pbase;
+};
+
+__device__ __forceinline__ Pos position(long n_pre, int up, int down, int hpp) {
+    const long t = n_pre * (long)down;
+    const long kbase = t / up;
+    return {kbase - (hpp - 1), (unsigned)(t - kbase * up)};
+}
 
 template <int FMT>
 __global__ __launch_bounds__(256) void ingest_resample_kernel(ResampleArgs a) {
     extern __shared__ float lds[];
     const int f = blockIdx.y, tid = threadIdx.x;
-    const long in0 = a.in_off[f], n_in = a.in_off[f + 1] - in0;
-    const long out0 = a.out_off[f], n_out = a.out_off[f + 1] - out0;
-    const long n0 = (long)blockIdx.x * a.blk;
-    if (n0 >= n_out) return;
-    const int cnt = n_out - n0 < a.blk ? (int)(n_out - n0) : a.blk;
+    const WinSpan w = window_span(a, f);
+    const long in0 = w.in0, out0 = w.out0;
+    const long n0 = w.o0 + (long)blockIdx.x * a.blk;
+    if (n0 >= w.o1) return;
+    const int cnt = w.o1 - n0 < a.blk ? (int)(w.o1 - n0) : a.blk;
     float vmax = 0.0f;
     if (a.hpp == 0) {  // same rate: decode + channel mean only; four loads in flight per thread
         const bool vec_store = ((out0 + n0) & 3) == 0;
         for (int j0 = 4 * tid; j0 < cnt; j0 += 1024) {
             float v[4];
-            mono_quad<FMT>(a.pcm, in0, n0 + j0, n_in, a.ch, v);
+            mono_quad<FMT>(a.pcm, in0, n0 + j0, w.lo, w.hi, a.ch, v);
             float* dst = a.mono + out0 + n0 + j0;
             if (vec_store && j0 + 3 < cnt) {
                 *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
@@ -212,18 +247,16 @@ __global__ __launch_bounds__(256) void ingest_resample_kernel(ResampleArgs a) {
         float* xs = lds + ((up * hpp + 3) & ~3);  // 16-byte aligned for the 128-bit tile stores
         for (int i = tid; i < up * hpp; i += 256) ht[i] = a.taps[i];
         // input samples the outputs [n0, n0 + cnt) touch: newest = floor((n + pre) down / up), hpp samples back from there
-        const unsigned t_first = (unsigned)(n0 + a.n_pre_remove) * (unsigned)down;
-        const unsigned t_last = (unsigned)(n0 + cnt - 1 + a.n_pre_remove) * (unsigned)down;
-        const long k_lo = (long)(t_first / (unsigned)up) - (hpp - 1);
-        const int tile = (int)((long)(t_last / (unsigned)up) - k_lo) + 1;
-        fill_tile<FMT>(a.pcm, in0, k_lo, tile, n_in, a.ch, xs, tid);
+        const Pos p = position(n0 + a.n_pre_remove, up, down, hpp);
+        const int tile = (int)((p.pbase + (unsigned)(cnt - 1) * (unsigned)down) / (unsigned)up) + hpp;
+        fill_tile<FMT>(a.pcm, in0, p.k_lo, tile, w.lo, w.hi, a.ch, xs, tid);
         __syncthreads();
         for (int j = tid; j < cnt; j += 256) {
-            const unsigned t = t_first + (unsigned)j * (unsigned)down;
-            const unsigned kmax = t / (unsigned)up;
-            const unsigned phase = t - kmax * (unsigned)up;
+            const unsigned r = p.pbase + (unsigned)j * (unsigned)down;
+            const unsigned kq = r / (unsigned)up;  // newest input = kbase + kq = tile position hpp - 1 + kq
+            const unsigned phase = r - kq * (unsigned)up;
             const float* hp = ht + phase * hpp;
-            const float* xp = xs + ((long)kmax - (hpp - 1) - k_lo);
+            const float* xp = xs + kq;
             float acc = 0.0f;
             for (int q = 0; q < hpp; ++q) acc = f_add(acc, f_mul(xp[q], hp[q]));
             a.mono[out0 + n0 + j] = acc;
@@ -242,14 +275,14 @@ __global__ __launch_bounds__(256) void ingest_decimate_kernel(ResampleArgs a, co
     constexpr int NX = (HPP + 3 * DOWN + 3) & ~3;
     extern __shared__ float lds[];
     const int f = blockIdx.y, tid = threadIdx.x;
-    const long in0 = a.in_off[f], n_in = a.in_off[f + 1] - in0;
-    const long out0 = a.out_off[f], n_out = a.out_off[f + 1] - out0;
-    const long n0 = (long)blockIdx.x * a.blk;
-    if (n0 >= n_out) return;
-    const int cnt = n_out - n0 < a.blk ? (int)(n_out - n0) : a.blk;
+    const WinSpan w = window_span(a, f);
+    const long in0 = w.in0, out0 = w.out0;
+    const long n0 = w.o0 + (long)blockIdx.x * a.blk;
+    if (n0 >= w.o1) return;
+    const int cnt = w.o1 - n0 < a.blk ? (int)(w.o1 - n0) : a.blk;
     const long k_lo = (n0 + a.n_pre_remove) * DOWN - (HPP - 1);
     const int tile = (cnt - 1) * DOWN + HPP;
-    fill_tile<FMT>(a.pcm, in0, k_lo, tile, n_in, a.ch, lds, tid);
+    fill_tile<FMT>(a.pcm, in0, k_lo, tile, w.lo, w.hi, a.ch, lds, tid);
     __syncthreads();
     float vmax = 0.0f;
     const bool vec_store = ((out0 + n0) & 3) == 0;
@@ -295,31 +328,29 @@ template <int FMT, int HPP>
 __global__ __launch_bounds__(256) void ingest_resample_phase_kernel(ResampleArgs a, const float* __restrict__ taps, float* __restrict__ mono) {
     extern __shared__ float lds[];
     const int f = blockIdx.y, tid = threadIdx.x;
-    const long in0 = a.in_off[f], n_in = a.in_off[f + 1] - in0;
-    const long out0 = a.out_off[f], n_out = a.out_off[f + 1] - out0;
-    const long n0 = (long)blockIdx.x * a.blk;
-    if (n0 >= n_out) return;
-    const int cnt = n_out - n0 < a.blk ? (int)(n_out - n0) : a.blk;
+    const WinSpan w = window_span(a, f);
+    const long in0 = w.in0, out0 = w.out0;
+    const long n0 = w.o0 + (long)blockIdx.x * a.blk;
+    if (n0 >= w.o1) return;
+    const int cnt = w.o1 - n0 < a.blk ? (int)(w.o1 - n0) : a.blk;
     const int up = a.up, down = a.down;
-    const unsigned t_first = (unsigned)(n0 + a.n_pre_remove) * (unsigned)down;
-    const unsigned t_last = (unsigned)(n0 + cnt - 1 + a.n_pre_remove) * (unsigned)down;
-    const long k_lo = (long)(t_first / (unsigned)up) - (HPP - 1);
-    const int tile = (int)((long)(t_last / (unsigned)up) - k_lo) + 1;
-    fill_tile<FMT>(a.pcm, in0, k_lo, tile, n_in, a.ch, lds, tid);
+    const Pos p = position(n0 + a.n_pre_remove, up, down, HPP);
+    const int tile = (int)((p.pbase + (unsigned)(cnt - 1) * (unsigned)down) / (unsigned)up) + HPP;
+    fill_tile<FMT>(a.pcm, in0, p.k_lo, tile, w.lo, w.hi, a.ch, lds, tid);
     const int streams = 256 / up;           // output streams per phase slot that fit the workgroup
     const int slot = tid % up, stream = tid / up;
     const bool active = stream < streams;
     const int j0 = slot + stream * up;
-    const unsigned t0 = t_first + (unsigned)j0 * (unsigned)down;
-    const unsigned kmax0 = t0 / (unsigned)up;
-    const unsigned phase = t0 - kmax0 * (unsigned)up;
+    const unsigned r0 = p.pbase + (unsigned)j0 * (unsigned)down;
+    const unsigned kq0 = r0 / (unsigned)up;
+    const unsigned phase = r0 - kq0 * (unsigned)up;
     float h[HPP];
 #pragma unroll
     for (int q = 0; q < HPP; ++q) h[q] = taps[phase * HPP + q];
     __syncthreads();
     float vmax = 0.0f;
     if (active) {
-        const float* xp = lds + ((long)kmax0 - (HPP - 1) - k_lo);
+        const float* xp = lds + kq0;
         const int xstep = streams * down, jstep = streams * up;
         for (int j = j0; j < cnt; j += jstep, xp += xstep) {
             float acc = 0.0f;
@@ -332,11 +363,13 @@ __global__ __launch_bounds__(256) void ingest_resample_phase_kernel(ResampleArgs
     store_block_peak(a.partial + (size_t)f * gridDim.x + blockIdx.x, vmax, tid);
 }
 
+// Folds the block maxima of window f into peak[f]: overwrites it, or with `accumulate` takes the maximum with what it holds (the
+// spans of one window, launched one after another on a stream, fold into one peak; maximum is exact, so the order does not matter).
+// out_off == nullptr: a span launch, every one of its `stride` blocks wrote a maximum.
 __global__ __launch_bounds__(256) void ingest_peak_kernel(const float* __restrict__ partial, const long* __restrict__ out_off,
-                                                          int stride, int blk, float* __restrict__ peak) {
+                                                          int stride, int blk, int accumulate, float* __restrict__ peak) {
     const int f = blockIdx.x, tid = threadIdx.x;
-    const long n_out = out_off[f + 1] - out_off[f];
-    const int nblk = (int)((n_out + blk - 1) / blk);  // blocks past the window's end returned without writing
+    const int nblk = out_off ? (int)((out_off[f + 1] - out_off[f] + blk - 1) / blk) : stride;  // blocks past the window's end returned without writing
     float m = 0.0f;
     for (int i = tid; i < nblk; i += 256) m = fmaxf(m, partial[(size_t)f * stride + i]);
 #pragma unroll
@@ -344,7 +377,10 @@ __global__ __launch_bounds__(256) void ingest_peak_kernel(const float* __restric
     __shared__ float wmax[4];
     if ((tid & 63) == 0) wmax[tid >> 6] = m;
     __syncthreads();
-    if (tid == 0) peak[f] = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
+    if (tid == 0) {
+        const float v = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
+        peak[f] = accumulate ? fmaxf(peak[f], v) : v;
+    }
 }
 
 __global__ __launch_bounds__(256) void ingest_chunks_kernel(const float* __restrict__ mono, const float* __restrict__ peak,
@@ -465,6 +501,7 @@ int ingest_resample_block(int up, int down, int hpp) {
     return 1024;
 }
 
+// max_out: outputs per window of the launch (its longest window, or the span's o1 - o0)
 static void launch_resample_kernels(const ResampleArgs& a, int fmt, int n_files, long max_out, const float* taps, float* mono,
                                     hipStream_t s) {
     const int blk = a.blk, up = a.up, down = a.down, hpp = a.hpp;
@@ -522,9 +559,17 @@ void launch_ingest_resample(const void* pcm, int fmt, int ch, const long* in_off
                             long max_out, const float* taps, int up, int down, int hpp, int n_pre_remove, float* mono,
                             float* partial, float* peak, hipStream_t s) {
     const int blk = ingest_resample_block(up, down, hpp);
-    ResampleArgs a{pcm, in_off, out_off, taps, mono, partial, ch, up, down, hpp, n_pre_remove, blk};
+    ResampleArgs a{pcm, in_off, out_off, taps, mono, partial, ch, up, down, hpp, n_pre_remove, blk, 0, 0, 0, 0, 0};
     launch_resample_kernels(a, fmt, n_files, max_out, taps, mono, s);
-    hipLaunchKernelGGL(ingest_peak_kernel, dim3(n_files), dim3(256), 0, s, partial, out_off, (int)((max_out + blk - 1) / blk), blk, peak);
+    hipLaunchKernelGGL(ingest_peak_kernel, dim3(n_files), dim3(256), 0, s, partial, out_off, (int)((max_out + blk - 1) / blk), blk, 0, peak);
+}
+
+void launch_ingest_resample_span(const void* pcm, int fmt, int ch, long s0, long n_staged, long n_win, long o0, long o1, const float* taps,
+                                 int up, int down, int hpp, int n_pre_remove, float* mono, float* partial, float* peak, hipStream_t s) {
+    const int blk = ingest_resample_block(up, down, hpp);
+    ResampleArgs a{pcm, nullptr, nullptr, taps, mono, partial, ch, up, down, hpp, n_pre_remove, blk, s0, n_staged, n_win, o0, o1};
+    launch_resample_kernels(a, fmt, 1, o1 - o0, taps, mono, s);
+    hipLaunchKernelGGL(ingest_peak_kernel, dim3(1), dim3(256), 0, s, partial, (const long*)nullptr, (int)((o1 - o0 + blk - 1) / blk), blk, 1, peak);
 }
 
 void launch_ingest_chunks(const float* mono, const float* peak, const long* src, const int* valid, const int* file,

@@ -172,6 +172,9 @@ size_t ingest_partial_elems(int n_files, long max_out, int up, int down, int hpp
 void launch_ingest_resample(const void* pcm, int fmt, int ch, const long* in_off, const long* out_off, int n_files,
                             long max_out, const float* taps, int up, int down, int hpp, int n_pre_remove, float* mono,
                             float* partial, float* peak, hipStream_t s);
+// outputs [o0, o1) of one window of n_win frames whose frames [s0, s0 + n_staged) lie at pcm; output n -> mono[n]; peak = max(peak, ...)
+void launch_ingest_resample_span(const void* pcm, int fmt, int ch, long s0, long n_staged, long n_win, long o0, long o1, const float* taps,
+                                 int up, int down, int hpp, int n_pre_remove, float* mono, float* partial, float* peak, hipStream_t s);
 void launch_ingest_chunks(const float* mono, const float* peak, const long* src, const int* valid, const int* file,
                           int n_chunks, int T, float* out, hipStream_t s);
 void launch_chunk_peaknorm(const float* x, float* y, int B, int T, float eps, hipStream_t s);

@@ -187,6 +187,22 @@ BN_API int bn_ingest_resample(bn_ctx* ctx, const void* d_pcm, int sample_format,
                        int64_t max_out_len, const float* d_taps, int up, int down, int taps_per_phase,
                        int n_pre_remove, float* d_mono, float* d_peak, void* stream);
 
+/* bn_ingest_resample for a SPAN of ONE window: outputs [o0, o1) of a window of n_in frames whose input frames are only partly
+ * staged — long recordings are resampled span by span through a staging buffer.  Same kernels, same bits: a window resampled as
+ * any sequence of spans equals the window resampled at once (and scipy's resample_poly).  Positions are 64-bit: no length limit
+ * below 2^40 frames.
+ *   d_pcm          interleaved frames [s0, s0 + n_staged) of the window (frame s0 first)
+ *   o0, o1         outputs to compute, 0 <= o0 <= o1 <= ceil(n_in * up / down) (n_in without resampling)
+ *   d_mono_window  output sample 0 of the window: output n is written to d_mono_window[n]
+ *   d_peak         ONE float, the window's max |y|: the spans' maxima are folded into it with fmax, in stream order — zero it
+ *                  before the first span
+ * The staged frames must cover every input that outputs [o0, o1) touch (for output n the taps_per_phase frames ending at
+ * floor((n + n_pre_remove) * down / up)), clipped to [0, n_in); BN_ERR_ARG names the missing range otherwise.  Frames outside
+ * [0, n_in) read as zeros.  The filter arguments are those of bn_ingest_resample. */
+BN_API int bn_ingest_resample_span(bn_ctx* ctx, const void* d_pcm, int sample_format, int channels, int64_t s0, int64_t n_staged,
+                       int64_t n_in, int64_t o0, int64_t o1, const float* d_taps, int up, int down, int taps_per_phase,
+                       int n_pre_remove, float* d_mono_window, float* d_peak, void* stream);
+
 /* Fixed-length chunks of peak-normalised audio (reference: audio/io.py:122-124 `y / peak` when peak > 0, then
  * split_audio_into_chunks :133-174; the host computes the start positions, which depend only on lengths).
  *   d_chunk_src    [n_chunks] absolute sample offset of the chunk's first sample in d_mono
