@@ -3,7 +3,8 @@
 ``--input`` takes files and directories (walked recursively, as in ``embed``).  Files are analysed whole by default
 (``--max_duration 0``); recordings longer than one staging slab are streamed through the device path segment by segment
 (``evaluation/detections.py``).  The chunking follows the model's ``<model>_model_config.json``; class names come from its
-``class_names`` ("Scientific name_Common name").
+``class_names`` ("Scientific name_Common name").  With ``--head`` (a head trained by ``probe``) the detections are of the head's classes:
+it is applied on the device to the model's embeddings.
 
 Outputs (``--format``, one or more):
 
@@ -28,6 +29,7 @@ def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="Detect the model's classes in audio files, per chunk, and write them as CSV, Raven tables or npz.")
     p.add_argument("--model_path", type=str, required=True, help="Path to .keras or .tflite model")
     p.add_argument("--model_config", type=str, default="", help="Path to model config JSON (default: <model>_model_config.json)")
+    p.add_argument("--head", type=str, default="", help="A head trained by `probe` (<output>.npz): report its classes instead of the model's")
     p.add_argument("--input", type=str, nargs="+", required=True, help="Audio files and/or directories (walked recursively)")
     p.add_argument("--output", type=str, required=True, help="Output file (csv, npz), directory (raven, or several formats)")
     p.add_argument("--format", type=str, nargs="+", default=["csv"], choices=FORMATS, help="Output format(s)")
@@ -76,6 +78,14 @@ def main(argv=None, runner=None):
     args = build_parser().parse_args(argv)
     cfg = ModelConfig.load(resolve_config_path(args.model_path, args.model_config)).to_dict()
     class_names = list(cfg.get("class_names") or [])
+    head = None
+    if args.head:
+        from birdnet_stm32.training.linear_probe import ProbeHead
+
+        if not os.path.isfile(args.head):
+            raise SystemExit(f"error: head not found: {args.head}")
+        head = ProbeHead.load(args.head)
+        class_names = list(head.class_names)
     if not class_names:
         raise SystemExit("error: class_names missing in model config")
     thresholds = load_thresholds(args.thresholds)
@@ -97,7 +107,7 @@ def main(argv=None, runner=None):
         from birdnet_stm32.models.runners import load_model_runner
 
         runner = load_model_runner(args.model_path, device=args.device, max_batch=args.max_batch, prepare_pipeline=True)
-    if int(runner.num_classes) != len(class_names):
+    if head is None and int(runner.num_classes) != len(class_names):
         raise SystemExit(f"error: the model scores {runner.num_classes} classes, its config names {len(class_names)}")
     frontend = normalize_frontend_name(cfg["audio_frontend"])
     if frontend not in ("hybrid", "raw"):
@@ -108,7 +118,7 @@ def main(argv=None, runner=None):
     try:
         det = detect_files(runner, files, min_conf=args.min_conf, top_k=args.top_k, class_thresholds=thresholds, chunk_overlap=overlap,
                            max_duration=args.max_duration, merge_consecutive=args.merge_consecutive, sample_rate=int(cfg["sample_rate"]),
-                           chunk_duration=float(cfg["chunk_duration"]), return_scores="npz" in outs, class_names=class_names)
+                           chunk_duration=float(cfg["chunk_duration"]), return_scores="npz" in outs, class_names=class_names, head=head)
     except ValueError as exc:
         raise SystemExit(f"error: {exc}") from None
     if "csv" in outs:

@@ -1,0 +1,49 @@
+"""``birdnet-stm32 probe`` — train a new classifier head for your own classes on the frozen backbone (reference: ``train --linear_probe``).
+
+``--data_path_train`` holds one folder per class (``<class>/*.wav``); folders named noise / silence / background / other are negatives.
+The backbone runs once over all files (``embed``'s device path), the head is trained on the embeddings on the GPU
+(``training/linear_probe.py``) and written as ``<output>.npz`` with ``<output>_labels.txt``, ``<output>_model_config.json`` and
+``<output>_history.csv``.  ``analyze --head <output>.npz`` then reports those classes in recordings.
+"""
+
+from __future__ import annotations
+
+import argparse
+
+
+def build_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(description="Train a classifier head for new classes on the embeddings of a pretrained model.")
+    p.add_argument("--model_path", type=str, required=True, help="Path to the pretrained .keras or .tflite model")
+    p.add_argument("--model_config", type=str, default="", help="Path to model config JSON (default: <model>_model_config.json)")
+    p.add_argument("--data_path_train", type=str, required=True, help="Directory with one folder of audio files per class")
+    p.add_argument("--output", type=str, required=True, help="Output stem: writes <output>.npz, _labels.txt, _model_config.json, _history.csv")
+    p.add_argument("--activation", type=str, default="sigmoid", choices=["sigmoid", "softmax"], help="sigmoid: multi-label, noise folders are negatives")
+    p.add_argument("--epochs", type=int, default=50, help="Number of epochs")
+    p.add_argument("--batch_size", type=int, default=32, help="Batch size (embedding rows)")
+    p.add_argument("--learning_rate", type=float, default=0.001, help="Initial learning rate of the cosine schedule")
+    p.add_argument("--optimizer", type=str, default="adam", choices=["adam", "adamw", "sgd"], help="Optimizer")
+    p.add_argument("--weight_decay", type=float, default=0.0, help="Weight decay (adamw only)")
+    p.add_argument("--grad_clip", type=float, default=1.0, help="Gradient clipping by global norm (0 to disable)")
+    p.add_argument("--dropout", type=float, default=0.5, help="Dropout rate in front of the head")
+    p.add_argument("--val_split", type=float, default=0.2, help="Validation split ratio (by file)")
+    p.add_argument("--patience", type=int, default=10, help="Early stopping: epochs without a better validation loss")
+    p.add_argument("--max_duration", type=float, default=30, help="Seconds read from the start of each file")
+    p.add_argument("--overlap", type=float, default=0.0, help="Chunk overlap (seconds)")
+    p.add_argument("--seed", type=int, default=42, help="Seed of the file shuffle, the initial weights, the batches and the dropout mask")
+    p.add_argument("--max_batch", type=int, default=4096, help="Workspace size in chunks = inference slice of the device pipeline")
+    p.add_argument("--device", type=int, default=0, help="MI355X index")
+    return p
+
+
+def main(argv=None, runner=None):
+    from birdnet_stm32.training.linear_probe import run_linear_probe
+
+    args = build_parser().parse_args(argv)
+    try:
+        return run_linear_probe(args, runner=runner)
+    except (ValueError, FileNotFoundError) as exc:
+        raise SystemExit(f"error: {exc}") from None
+
+
+if __name__ == "__main__":
+    main()

@@ -171,30 +171,43 @@ def detections_from_scores(scores: np.ndarray, n_out, paths: list, sample_rate: 
 def detect_files(runner, paths: list[str], min_conf: float = 0.25, top_k: int | None = None, class_thresholds: dict | None = None,
                  chunk_overlap: float = 0.0, max_duration=0, merge_consecutive: bool = False, sample_rate: int = 22050,
                  chunk_duration: float = 3.0, pipeline_options: dict | None = None, return_scores: bool = False, class_names=None,
-                 budget_bytes: int = 256 << 20) -> Detections:
+                 budget_bytes: int = 256 << 20, head=None) -> Detections:
     """Detections in every file of ``paths`` (see the module docstring).  ``class_names`` (needed for ``class_thresholds``): the model's
     classes in score order.  ``pipeline_options``: keyword arguments of ``EvaluatePipeline`` (``slab_bytes``, ``readers``, ...);
-    long files are streamed.  Score rows come to the host in blocks of files whose scores fit ``budget_bytes``."""
+    long files are streamed.  Score rows come to the host in blocks of files whose scores fit ``budget_bytes``.
+
+    ``head`` (a ``training.linear_probe.ProbeHead``): the pipeline also writes its float32 embeddings, the head is applied to them on the
+    device per block, and its ``[N, C_head]`` scores take the place of the model's — ``class_names`` and thresholds are then the head's."""
     from birdnet_stm32.audio.pipeline import EvaluatePipeline, plan_files
     from birdnet_stm32.evaluation.embeddings import _to_host, embedding_blocks
 
     sr, cd, ov = int(sample_rate), float(chunk_duration), float(chunk_overlap)
     C = int(runner.num_classes)
+    if head is not None:
+        head.check_embedding_dim(runner.embedding_info()["dim"])   # (refused before any audio is read)
+        C = int(head.num_classes)
     class_thresholds_vector(C, min_conf, class_thresholds, class_names)   # (an unknown class name fails before any audio is read)
     opts = dict(pipeline_options or {})
     opts.setdefault("stream_long", True)
     pipe = EvaluatePipeline(runner, sr, cd, ov, max_duration=max_duration, **opts)
+    row_bytes = C * 4
+    if head is not None:
+        pipe.emb_dtype = "float32"
+        row_bytes = (C + head.embedding_dim + int(runner.num_classes)) * 4
     paths = list(paths)
     try:
         tab = plan_files(paths, sr, cd, ov, max_duration, pipe.readers)
         counts = tab.n_chunks.astype(np.int64)
         parts = []
-        for lo, hi in embedding_blocks(counts, C * 4, budget_bytes):
+        for lo, hi in embedding_blocks(counts, row_bytes, budget_bytes):
             if int(counts[lo:hi].sum()) == 0:
                 continue
             scores, got, _stats, _lat = pipe.run(paths[lo:hi], table=tab.sub(lo, hi))
             if list(got) != counts[lo:hi].tolist():
                 raise RuntimeError("the pipeline cut a different number of chunks than it planned")
+            if head is not None:
+                scores = head.predict_device(pipe.embeddings.contiguous(), runner.ctx)
+                pipe.embeddings = None
             parts.append(_to_host(scores.contiguous()))
     finally:
         pipe.close()

@@ -1,0 +1,507 @@
+"""Linear probe: train a new classifier head on frozen embeddings (reference: birdnet_stm32/training/linear_probe.py).
+
+The reference freezes the backbone, puts ``Dropout -> Dense(len(classes))`` behind the pooled vector and lets Keras train that, running
+the backbone on every batch of every epoch.  Here the backbone runs once (``evaluation.embeddings.embed_files``) and the head is trained
+on the ``[N, D]`` matrix, which stays on the device for the whole fit (``csrc/bn_probe.hip``, C ABI ``bn_probe_*``).
+
+* ``fit_probe``            the device fit,
+* ``fit_probe_reference``  the same procedure in numpy: the specification the device code is tested against,
+* ``ProbeHead``            the result: ``W [D, C]``, ``b [C]``, activation, class names; ``save`` / ``load`` (plain ``.npz``), ``predict``,
+* ``run_linear_probe``     class folders -> embeddings -> head -> files on disk (the ``probe`` command).
+
+The procedure (both implementations): Glorot-uniform ``W`` from ``default_rng(seed)``, zero ``b``; per epoch a permutation from
+``default_rng([seed, epoch])`` cut into batches (the last one short); per step dropout by a counter-based hash, logits, sigmoid + binary
+cross-entropy or softmax + categorical cross-entropy (Keras definitions, probabilities clipped to ``[1e-7, 1 - 1e-7]`` in the loss only),
+clip by global norm, Adam / AdamW / SGD-with-momentum (Keras definitions) under a cosine schedule to zero; validation loss per epoch,
+early stopping with the best weights restored (Keras ``EarlyStopping(patience, restore_best_weights=True)``).
+"""
+
+from __future__ import annotations
+
+import csv
+import json
+import math
+import os
+from dataclasses import dataclass, field
+
+import numpy as np
+
+ACTIVATIONS = ("sigmoid", "softmax")
+OPTIMIZERS = ("adam", "adamw", "sgd")
+NOISE_CLASSES = ("noise", "silence", "background", "other")
+BETA_1, BETA_2, ADAM_EPS, MOMENTUM, LOSS_EPS = 0.9, 0.999, 1e-7, 0.9, 1e-7
+
+
+# -- the dropout mask ---------------------------------------------------------------------------------------------------------------
+def _fmix(h: np.ndarray) -> np.ndarray:
+    """The murmur3 finaliser on uint32 arrays (multiplications wrap)."""
+    h = h ^ (h >> np.uint32(16))
+    h = h * np.uint32(0x85EBCA6B)
+    h = h ^ (h >> np.uint32(13))
+    h = h * np.uint32(0xC2B2AE35)
+    return h ^ (h >> np.uint32(16))
+
+
+def dropout_hash(seed: int, step: int, n_rows: int, n_cols: int) -> np.ndarray:
+    """The 24-bit draw of every (row in batch, column) of global step ``step``: ``[n_rows, n_cols]`` uint32 in ``[0, 2^24)``.
+    Stateless; ``probe_drop_hash`` of ``csrc/bn_probe.hip`` is the same function."""
+    with np.errstate(over="ignore"):
+        h0 = _fmix(np.array([(int(seed) ^ (int(step) * 0x9E3779B1)) & 0xFFFFFFFF], np.uint32))
+        rows = _fmix(h0 ^ (np.arange(n_rows, dtype=np.uint32) * np.uint32(0x85EBCA77)))
+        h = _fmix(rows[:, None] ^ (np.arange(n_cols, dtype=np.uint32) * np.uint32(0xC2B2AE3D))[None, :])
+    return h >> np.uint32(8)
+
+
+def dropout_threshold(p: float) -> int:
+    """An element is kept iff its draw is >= this (``p`` as the float32 the C ABI takes)."""
+    return int(math.ceil(float(np.float32(p)) * 16777216.0)) if p > 0 else 0
+
+
+def dropout_mask(seed: int, step: int, n_rows: int, n_cols: int, p: float, dtype=np.float32) -> np.ndarray:
+    """``keep / (1 - p)`` of one step."""
+    if not p > 0:
+        return np.ones((n_rows, n_cols), dtype)
+    scale = np.float32(1.0 / (1.0 - float(np.float32(p))))
+    return (dropout_hash(seed, step, n_rows, n_cols) >= dropout_threshold(p)).astype(dtype) * np.asarray(scale, dtype)
+
+
+# -- pieces of the procedure --------------------------------------------------------------------------------------------------------
+def init_head(D: int, C: int, seed: int) -> tuple[np.ndarray, np.ndarray]:
+    """Glorot-uniform ``W [D, C]`` (Keras' Dense default) and zero ``b``, float32."""
+    limit = math.sqrt(6.0 / (D + C))
+    W = np.random.default_rng(seed).uniform(-limit, limit, (D, C)).astype(np.float32)
+    return W, np.zeros(C, np.float32)
+
+
+def epoch_permutation(seed: int, epoch: int, n: int) -> np.ndarray:
+    return np.random.default_rng([int(seed), int(epoch)]).permutation(n).astype(np.int32)
+
+
+def step_sizes(learning_rate: float, t: int, total_steps: int) -> tuple[float, float]:
+    """``(lr_t, alpha_t)`` of global step ``t`` (0-based): cosine decay to zero over ``total_steps`` (Keras ``CosineDecay(alpha=0)``) and
+    Adam's step size with the bias correction folded in.  Computed in float64 (the device code does the same on the host)."""
+    lr_t = float(np.float32(learning_rate)) * 0.5 * (1.0 + math.cos(math.pi * min(t, total_steps) / total_steps))
+    return lr_t, lr_t * math.sqrt(1.0 - BETA_2 ** (t + 1)) / (1.0 - BETA_1 ** (t + 1))
+
+
+def head_scores(X: np.ndarray, W: np.ndarray, b: np.ndarray, activation: str) -> np.ndarray:
+    z = X @ W + b
+    if activation == "softmax":
+        e = np.exp(z - z.max(axis=1, keepdims=True))
+        return e / e.sum(axis=1, keepdims=True)
+    with np.errstate(over="ignore"):
+        return 1.0 / (1.0 + np.exp(-z))
+
+
+def probe_loss(P: np.ndarray, Y: np.ndarray, activation: str):
+    """Keras' loss on probabilities: mean binary cross-entropy over rows x classes, or mean categorical cross-entropy over rows."""
+    one = P.dtype.type(1.0)
+    Pc = np.clip(P, P.dtype.type(LOSS_EPS), one - P.dtype.type(LOSS_EPS))
+    if activation == "softmax":
+        return -(Y * np.log(Pc)).sum() / P.dtype.type(P.shape[0])
+    return -(Y * np.log(Pc) + (one - Y) * np.log(one - Pc)).sum() / P.dtype.type(P.size)
+
+
+def optimizer_step(params: np.ndarray, g: np.ndarray, state: dict, optimizer: str, lr_t, alpha_t, weight_decay=0.0, eps=ADAM_EPS) -> np.ndarray:
+    """One update of ``params`` (any shape) in their dtype; ``state`` holds ``m`` / ``v`` (zeros at the start)."""
+    dt = params.dtype.type
+    if optimizer == "sgd":
+        state["m"] = dt(MOMENTUM) * state["m"] - dt(lr_t) * g
+        return params + state["m"]
+    if optimizer == "adamw":
+        params = params - dt(lr_t) * dt(weight_decay) * params
+    # 1 - beta is formed in float64 and then cast (0.1, 0.001 to the nearest value of the dtype, as the kernel's constants are):
+    # 1 - 0.999 formed in float32 would be 1.3e-5 off, a bias that is no rounding of the procedure
+    state["m"] = state["m"] + (g - state["m"]) * dt(1.0 - BETA_1)
+    state["v"] = state["v"] + (g * g - state["v"]) * dt(1.0 - BETA_2)
+    return params - state["m"] * dt(alpha_t) / (np.sqrt(state["v"]) + dt(eps))
+
+
+def clip_by_global_norm(g: np.ndarray, clipnorm: float) -> np.ndarray:
+    if not clipnorm > 0:
+        return g
+    norm = np.sqrt((g * g).sum())
+    return g * (g.dtype.type(clipnorm) / norm) if norm > g.dtype.type(clipnorm) else g
+
+
+def _check_fit_args(X, Y, activation, optimizer, batch_size, dropout, epochs):
+    if activation not in ACTIVATIONS:
+        raise ValueError(f"activation must be one of {ACTIVATIONS}, not {activation!r}")
+    if optimizer not in OPTIMIZERS:
+        raise ValueError(f"optimizer must be one of {OPTIMIZERS}, not {optimizer!r}")
+    if len(X.shape) != 2 or len(Y.shape) != 2 or X.shape[0] != Y.shape[0] or X.shape[0] < 1:
+        raise ValueError(f"X must be [N, D] and Y [N, C] with the same N >= 1, got {tuple(X.shape)} and {tuple(Y.shape)}")
+    if not 1 <= int(batch_size):
+        raise ValueError("batch_size must be >= 1")
+    if not 0.0 <= float(dropout) < 1.0:
+        raise ValueError("dropout must be in [0, 1)")
+    if int(epochs) < 1:
+        raise ValueError("epochs must be >= 1")
+
+
+def _fit_loop(backend, n: int, epochs: int, batch: int, seed: int, patience: int, has_val: bool) -> dict:
+    """Epochs, validation and early stopping, shared by the device and the numpy fit.  ``backend``: ``epoch(perm) -> step losses``,
+    ``val_loss()``, ``get() -> (W, b)``, ``set(W, b)``."""
+    history = {"loss": [], "val_loss": [], "step_loss": [], "best_epoch": None, "stopped_epoch": None}
+    best, best_weights, wait = math.inf, None, 0
+    for epoch in range(epochs):
+        losses = np.asarray(backend.epoch(epoch_permutation(seed, epoch, n)), np.float64)
+        history["step_loss"].append(losses)
+        history["loss"].append(float(losses.mean()))
+        if not has_val:
+            continue
+        val = float(backend.val_loss())
+        history["val_loss"].append(val)
+        if val < best:
+            best, best_weights, wait, history["best_epoch"] = val, backend.get(), 0, epoch
+        else:
+            wait += 1
+            if wait >= patience and epoch > 0:
+                history["stopped_epoch"] = epoch
+                break
+    if best_weights is not None:
+        backend.set(*best_weights)
+    history["step_loss"] = np.concatenate(history["step_loss"])
+    return history
+
+
+# -- the result -----------------------------------------------------------------------------------------------------------------------
+@dataclass
+class ProbeHead:
+    """A trained head: ``scores = act(x W + b)`` over embedding rows of width ``embedding_dim``."""
+
+    W: np.ndarray
+    b: np.ndarray
+    activation: str = "sigmoid"
+    class_names: list = field(default_factory=list)
+    history: dict = field(default_factory=dict)
+
+    def __post_init__(self):
+        self.W = np.ascontiguousarray(self.W, np.float32)
+        self.b = np.ascontiguousarray(self.b, np.float32)
+        if self.W.ndim != 2 or self.b.shape != (self.W.shape[1],):
+            raise ValueError(f"W must be [D, C] and b [C], got {self.W.shape} and {self.b.shape}")
+        if self.activation not in ACTIVATIONS:
+            raise ValueError(f"activation must be one of {ACTIVATIONS}, not {self.activation!r}")
+        self.class_names = [str(c) for c in self.class_names]
+        if self.class_names and len(self.class_names) != self.W.shape[1]:
+            raise ValueError(f"{len(self.class_names)} class names for {self.W.shape[1]} classes")
+        self._device = {}   # per device index: [own context or None, W, b on the device]; W and b are fixed once the head exists
+
+    @property
+    def embedding_dim(self) -> int:
+        return int(self.W.shape[0])
+
+    @property
+    def num_classes(self) -> int:
+        return int(self.W.shape[1])
+
+    def check_embedding_dim(self, dim: int) -> None:
+        if int(dim) != self.embedding_dim:
+            raise ValueError(f"the head was trained on embeddings of width {self.embedding_dim}, the model's are {int(dim)} wide")
+
+    def save(self, path: str) -> None:
+        """A plain ``.npz`` (``np.load(path)`` reads it without this package)."""
+        hist = {k: np.asarray(v, np.float64) for k, v in self.history.items() if k in ("loss", "val_loss")}
+        np.savez(path, W=self.W, b=self.b, activation=np.str_(self.activation), class_names=np.asarray(self.class_names, dtype=np.str_),
+                 embedding_dim=np.int64(self.embedding_dim), **{f"history_{k}": v for k, v in hist.items()})
+
+    @classmethod
+    def load(cls, path: str) -> "ProbeHead":
+        with np.load(path, allow_pickle=False) as z:
+            hist = {k[len("history_"):]: z[k].tolist() for k in z.files if k.startswith("history_")}
+            head = cls(z["W"], z["b"], str(z["activation"]), [str(c) for c in z["class_names"]], hist)
+            if "embedding_dim" in z.files and int(z["embedding_dim"]) != head.embedding_dim:
+                raise ValueError(f"{path}: embedding_dim {int(z['embedding_dim'])} does not match W {head.W.shape}")
+        return head
+
+    def close(self) -> None:
+        """Drop the device copies of ``W`` / ``b`` and close the contexts ``predict`` opened for itself (none when it was given one)."""
+        for own_ctx, _w, _b in self._device.values():
+            if own_ctx is not None:
+                own_ctx.close()
+        self._device = {}
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def predict_device(self, emb, ctx=None):
+        """Scores ``[N, C]`` of a contiguous float32 CUDA tensor ``[N, D]`` (``bn_head_forward``), as a CUDA tensor.  ``ctx``: the
+        caller's ``_hip.Context`` (a runner's ``ctx``); without one the head opens its own per device and keeps it until ``close()``."""
+        import ctypes
+
+        import torch
+
+        from birdnet_stm32 import _hip
+
+        if not (emb.is_cuda and emb.dtype == torch.float32 and emb.dim() == 2 and emb.is_contiguous()):
+            raise ValueError("embeddings must be a contiguous float32 CUDA tensor [N, D]")
+        self.check_embedding_dim(emb.shape[1])
+        dev = emb.device.index or 0
+        if dev not in self._device:
+            self._device[dev] = [None, torch.from_numpy(self.W).to(emb.device), torch.from_numpy(self.b).to(emb.device)]
+        slot = self._device[dev]
+        if ctx is None:
+            ctx = slot[0] = slot[0] or _hip.Context(dev, 1)
+        out = torch.empty((emb.shape[0], self.num_classes), dtype=torch.float32, device=emb.device)
+        with torch.cuda.device(emb.device):
+            stream = ctypes.c_void_p(torch.cuda.current_stream(emb.device).cuda_stream)
+            _hip.check(ctx.lib.bn_head_forward(ctx.handle, emb.data_ptr(), emb.shape[0], self.embedding_dim, slot[1].data_ptr(), slot[2].data_ptr(),
+                                               self.num_classes, _hip.PROBE_ACTIVATIONS[self.activation], out.data_ptr(), stream))
+        return out
+
+    def predict(self, embeddings, ctx=None, device: int = 0):
+        """Scores of embedding rows: a numpy array in gives a numpy array, a CUDA tensor a CUDA tensor.  Always on the device."""
+        import torch
+
+        if isinstance(embeddings, np.ndarray):
+            emb = torch.from_numpy(np.ascontiguousarray(embeddings, np.float32)).to(f"cuda:{getattr(ctx, 'device', device)}")
+            return self.predict_device(emb, ctx).cpu().numpy()
+        return self.predict_device(embeddings, ctx)
+
+
+# -- the specification ----------------------------------------------------------------------------------------------------------------
+class _NumpyBackend:
+    def __init__(self, X, Y, Xv, Yv, W, b, cfg, dtype):
+        self.X, self.Y, self.Xv, self.Yv, self.cfg, self.dt = X, Y, Xv, Yv, cfg, dtype
+        self.P = np.concatenate([W, b[None, :]]).astype(dtype)   # the bias is row D, as on the device
+        self.state = {"m": np.zeros_like(self.P), "v": np.zeros_like(self.P)}
+        self.t = 0
+
+    def epoch(self, perm):
+        c, dt, D = self.cfg, self.dt, self.X.shape[1]
+        losses = []
+        for s in range(0, len(perm), c["batch"]):
+            idx = perm[s : s + c["batch"]]
+            B = len(idx)
+            xd = np.concatenate([self.X[idx] * dropout_mask(c["seed"], self.t, B, D, c["dropout"], dt), np.ones((B, 1), dt)], axis=1)
+            P = head_scores(xd[:, :D], self.P[:D], self.P[D], c["activation"])
+            y = self.Y[idx]
+            losses.append(float(probe_loss(P, y, c["activation"])))
+            G = (P - y) / dt(B if c["activation"] == "softmax" else B * y.shape[1])
+            g = clip_by_global_norm(xd.T @ G, c["clipnorm"])
+            lr_t, alpha_t = step_sizes(c["lr"], self.t, c["total"])
+            self.P = optimizer_step(self.P, g, self.state, c["optimizer"], np.float32(lr_t), np.float32(alpha_t), np.float32(c["weight_decay"]))
+            self.t += 1
+        return losses
+
+    def val_loss(self):
+        D = self.X.shape[1]
+        return probe_loss(head_scores(self.Xv, self.P[:D], self.P[D], self.cfg["activation"]), self.Yv, self.cfg["activation"])
+
+    def get(self):
+        return self.P[:-1].copy(), self.P[-1].copy()
+
+    def set(self, W, b):
+        self.P = np.concatenate([W, b[None, :]]).astype(self.dt)
+
+
+def fit_probe_reference(X, Y, X_val=None, Y_val=None, *, activation="sigmoid", epochs=50, batch_size=32, learning_rate=1e-3, optimizer="adam",
+                        weight_decay=0.0, clipnorm=1.0, dropout=0.5, patience=10, seed=42, dtype=np.float64, class_names=None) -> ProbeHead:
+    """The procedure of ``fit_probe`` in numpy, all arithmetic in ``dtype``.  ``history["W"]`` / ``["b"]`` keep the result in ``dtype``."""
+    X, Y = np.asarray(X), np.asarray(Y)
+    _check_fit_args(X, Y, activation, optimizer, batch_size, dropout, epochs)
+    n, D = X.shape
+    batch = min(int(batch_size), n)
+    has_val = X_val is not None and len(X_val) > 0
+    W0, b0 = init_head(D, Y.shape[1], seed)
+    cfg = dict(activation=activation, optimizer=optimizer, batch=batch, seed=int(seed), dropout=float(dropout), clipnorm=float(np.float32(clipnorm)),
+               lr=float(learning_rate), weight_decay=float(weight_decay), total=int(epochs) * math.ceil(n / batch))
+    be = _NumpyBackend(X.astype(dtype), Y.astype(dtype), np.asarray(X_val).astype(dtype) if has_val else None,
+                       np.asarray(Y_val).astype(dtype) if has_val else None, W0, b0, cfg, np.dtype(dtype).type)
+    history = _fit_loop(be, n, int(epochs), batch, int(seed), int(patience), has_val)
+    W, b = be.get()
+    history["W"], history["b"] = W, b
+    return ProbeHead(W, b, activation, list(class_names or []), history)
+
+
+# -- the device fit -------------------------------------------------------------------------------------------------------------------
+class _DeviceBackend:
+    def __init__(self, ctx, X, Y, Xv, Yv, W, b, cfg):
+        import ctypes
+
+        import torch
+
+        from birdnet_stm32 import _hip
+
+        self.torch, self.hip, self.ctx, self.cfg = torch, _hip, ctx, cfg
+        self.dev = torch.device(f"cuda:{ctx.device}")
+        self.X, self.Y, self.Xv, self.Yv = (self._dev(a) for a in (X, Y, Xv, Yv))
+        self.W, self.b = self._dev(W), self._dev(b)
+        self.n, self.D = self.X.shape
+        self.C = self.Y.shape[1]
+        self.steps = math.ceil(self.n / cfg["batch"])
+        self.step_loss = torch.empty(self.steps, dtype=torch.float32, device=self.dev)
+        self.val = torch.empty(1, dtype=torch.float32, device=self.dev)
+        h = ctypes.c_void_p()
+        with torch.cuda.device(self.dev):
+            _hip.check(ctx.lib.bn_probe_create(ctx.handle, self.D, self.C, _hip.PROBE_ACTIVATIONS[cfg["activation"]], _hip.PROBE_OPTIMIZERS[cfg["optimizer"]],
+                                               cfg["lr"], cfg["weight_decay"], cfg["clipnorm"], cfg["dropout"], cfg["seed"] & 0xFFFFFFFF, cfg["total"],
+                                               self.W.data_ptr(), self.b.data_ptr(), ctypes.byref(h), self._stream()))
+        self.handle = h
+
+    def _dev(self, a):
+        if a is None:
+            return None
+        if isinstance(a, np.ndarray):
+            a = self.torch.from_numpy(np.ascontiguousarray(a, np.float32))
+        return a.to(self.dev, self.torch.float32).contiguous()
+
+    def _stream(self):
+        import ctypes
+
+        return ctypes.c_void_p(self.torch.cuda.current_stream(self.dev).cuda_stream)
+
+    def epoch(self, perm):
+        with self.torch.cuda.device(self.dev):
+            d_perm = self.torch.from_numpy(perm).to(self.dev)
+            self.hip.check(self.ctx.lib.bn_probe_epoch(self.handle, self.X.data_ptr(), self.Y.data_ptr(), d_perm.data_ptr(), self.n, self.cfg["batch"],
+                                                       self.step_loss.data_ptr(), self._stream()))
+            return self.step_loss.cpu().numpy()   # (synchronises: d_perm outlives the epoch)
+
+    def val_loss(self):
+        with self.torch.cuda.device(self.dev):
+            self.hip.check(self.ctx.lib.bn_probe_loss(self.handle, self.Xv.data_ptr(), self.Yv.data_ptr(), self.Xv.shape[0], self.val.data_ptr(), self._stream()))
+            return float(self.val.item())
+
+    def get(self):
+        W, b = self.torch.empty_like(self.W), self.torch.empty_like(self.b)
+        with self.torch.cuda.device(self.dev):
+            self.hip.check(self.ctx.lib.bn_probe_get(self.handle, W.data_ptr(), b.data_ptr(), self._stream()))
+        return W, b
+
+    def set(self, W, b):
+        with self.torch.cuda.device(self.dev):
+            self.hip.check(self.ctx.lib.bn_probe_set(self.handle, W.data_ptr(), b.data_ptr(), self._stream()))
+            self.torch.cuda.current_stream(self.dev).synchronize()
+
+    def close(self):
+        if self.handle:
+            self.torch.cuda.synchronize(self.dev)
+            self.ctx.lib.bn_probe_destroy(self.handle)
+            self.handle = None
+
+
+def fit_probe(ctx_or_runner, X, Y, X_val=None, Y_val=None, *, activation="sigmoid", epochs=50, batch_size=32, learning_rate=1e-3, optimizer="adam",
+              weight_decay=0.0, clipnorm=1.0, dropout=0.5, patience=10, seed=42, class_names=None) -> ProbeHead:
+    """Train ``scores = act(dropout(x) W + b)`` on embedding rows ``X [N, D]`` with targets ``Y [N, C]`` (float: one-hot, multi-hot or
+    all-zero rows) on the device.  ``X`` / ``Y`` may be numpy arrays or CUDA tensors; they stay on the device for the whole fit, per epoch
+    the host uploads one permutation and reads back the per-step losses.  The defaults are the reference CLI's.  The same inputs and seed
+    give the same bits on every run."""
+    from birdnet_stm32 import _hip
+
+    _check_fit_args(X, Y, activation, optimizer, batch_size, dropout, epochs)
+    n, D = int(X.shape[0]), int(X.shape[1])
+    C = int(Y.shape[1])
+    if not (1 <= D <= _hip.PROBE_MAX_D and 1 <= C <= _hip.PROBE_MAX_C):
+        raise ValueError(f"the device path takes 1 <= D <= {_hip.PROBE_MAX_D} and 1 <= C <= {_hip.PROBE_MAX_C}, got D={D} C={C}")
+    ctx = getattr(ctx_or_runner, "ctx", ctx_or_runner)
+    batch = min(int(batch_size), n)
+    has_val = X_val is not None and len(X_val) > 0
+    W0, b0 = init_head(D, C, seed)
+    cfg = dict(activation=activation, optimizer=optimizer, batch=batch, seed=int(seed), dropout=float(dropout), clipnorm=float(clipnorm),
+               lr=float(learning_rate), weight_decay=float(weight_decay), total=int(epochs) * math.ceil(n / batch))
+    be = _DeviceBackend(ctx, X, Y, X_val if has_val else None, Y_val if has_val else None, W0, b0, cfg)
+    try:
+        history = _fit_loop(be, n, int(epochs), batch, int(seed), int(patience), has_val)
+        W, b = be.get()
+        W, b = W.cpu().numpy(), b.cpu().numpy()
+    finally:
+        be.close()
+    return ProbeHead(W, b, activation, list(class_names or []), history)
+
+
+# -- from class folders to a head on disk ---------------------------------------------------------------------------------------------
+def split_train_val(paths: list, val_split: float) -> tuple[list, list]:
+    """The first ``1 - val_split`` of the (already shuffled) list trains, the rest validates (reference: linear_probe.py, cli/train.py)."""
+    k = int(len(paths) * (1 - float(val_split)))
+    return list(paths[:k]), list(paths[k:])
+
+
+def targets_from_paths(paths: list, classes: list, file_index: np.ndarray, activation: str = "sigmoid") -> tuple[np.ndarray, np.ndarray]:
+    """One-hot targets ``[rows, len(classes)]`` of embedding rows from the parent folder of each row's file, and the mask of rows to
+    keep: files of folders that are not classes (the noise-like ones) give all-zero rows under sigmoid and are dropped under softmax."""
+    col = {c: i for i, c in enumerate(classes)}
+    label = np.array([col.get(os.path.basename(os.path.dirname(p)), -1) for p in paths], np.int64)
+    row_label = label[np.asarray(file_index, np.int64)] if len(paths) else np.zeros(0, np.int64)
+    Y = np.zeros((row_label.shape[0], len(classes)), np.float32)
+    known = row_label >= 0
+    Y[np.flatnonzero(known), row_label[known]] = 1.0
+    keep = known if activation == "softmax" else np.ones_like(known)
+    return Y, keep
+
+
+def probe_output_paths(output: str) -> dict:
+    stem = output[:-4] if output.endswith(".npz") else output
+    return {"head": stem + ".npz", "labels": stem + "_labels.txt", "config": stem + "_model_config.json", "history": stem + "_history.csv"}
+
+
+def write_history_csv(path: str, history: dict) -> None:
+    with open(path, "w", newline="") as fh:
+        w = csv.writer(fh)
+        w.writerow(["epoch", "loss", "val_loss"])
+        val = history.get("val_loss") or []
+        for i, loss in enumerate(history.get("loss", [])):
+            w.writerow([i + 1, f"{loss:.8g}", f"{val[i]:.8g}" if i < len(val) else ""])
+
+
+def run_linear_probe(args, runner=None) -> ProbeHead:
+    """The ``probe`` command: ``args.data_path_train/<class>/*`` -> embeddings (the backbone runs once) -> ``fit_probe`` ->
+    ``<output>.npz``, ``<output>_labels.txt``, ``<output>_model_config.json`` and ``<output>_history.csv``."""
+    import time
+    from dataclasses import replace
+
+    from birdnet_stm32.cli.evaluate import resolve_config_path
+    from birdnet_stm32.data.dataset import load_file_paths_from_directory
+    from birdnet_stm32.evaluation.embeddings import embed_files
+    from birdnet_stm32.training.config import ModelConfig
+
+    if not os.path.isfile(args.model_path):
+        raise FileNotFoundError(f"Pretrained model not found: {args.model_path}")
+    cfg = ModelConfig.load(resolve_config_path(args.model_path, getattr(args, "model_config", "")))
+    np.random.seed(int(args.seed))   # load_file_paths_from_directory shuffles with numpy.random
+    paths, classes = load_file_paths_from_directory(args.data_path_train)
+    if not classes:
+        raise ValueError("No classes found in the training data.")
+    if not 1 <= len(classes) <= 4096:
+        raise ValueError(f"{len(classes)} classes: the device path takes at most 4096")
+    train_paths, val_paths = split_train_val(paths, args.val_split)
+    print(f"[probe] {len(classes)} target classes, {len(train_paths)} training and {len(val_paths)} validation files")
+    if runner is None:
+        from birdnet_stm32.models.runners import load_model_runner
+
+        runner = load_model_runner(args.model_path, device=getattr(args, "device", 0), max_batch=getattr(args, "max_batch", 4096), prepare_pipeline=True)
+    overlap = max(0.0, min(float(cfg.chunk_duration) - 0.1, float(args.overlap)))
+    t0 = time.perf_counter()
+    emb = embed_files(runner, train_paths + val_paths, chunk_overlap=overlap, max_duration=args.max_duration, pooling="none", dtype="float32",
+                      sample_rate=int(cfg.sample_rate), chunk_duration=float(cfg.chunk_duration))
+    t_embed = time.perf_counter() - t0
+    Y, keep = targets_from_paths(emb.paths, classes, emb.file_index, args.activation)
+    is_train = np.asarray(emb.file_index) < len(train_paths)
+    tr, va = keep & is_train, keep & ~is_train
+    if not tr.any():
+        raise ValueError("no training rows: every training file was unreadable, empty or of a noise folder")
+    t0 = time.perf_counter()
+    head = fit_probe(runner, emb.embeddings[tr], Y[tr], emb.embeddings[va] if va.any() else None, Y[va] if va.any() else None,
+                     activation=args.activation, epochs=args.epochs, batch_size=args.batch_size, learning_rate=args.learning_rate,
+                     optimizer=args.optimizer, weight_decay=args.weight_decay, clipnorm=args.grad_clip, dropout=args.dropout,
+                     patience=getattr(args, "patience", 10), seed=args.seed, class_names=classes)
+    t_fit = time.perf_counter() - t0
+    out = probe_output_paths(args.output)
+    os.makedirs(os.path.dirname(os.path.abspath(out["head"])), exist_ok=True)
+    head.save(out["head"])
+    with open(out["labels"], "w") as fh:
+        fh.write("\n".join(classes) + "\n")
+    replace(cfg, num_classes=len(classes), class_names=list(classes), dropout_rate=float(args.dropout)).save(out["config"])
+    write_history_csv(out["history"], head.history)
+    head.history["seconds"] = {"embed": t_embed, "fit": t_fit}
+    val = head.history["val_loss"]
+    print(f"[probe] {int(tr.sum())} training rows x {head.embedding_dim}: embeddings {t_embed:.2f} s, fit {t_fit:.2f} s ({len(head.history['loss'])} epochs, "
+          f"loss {head.history['loss'][-1]:.4f}" + (f", best val_loss {min(val):.4f}" if val else "") + f") -> {out['head']}")
+    if emb.skipped:
+        print(f"[probe] skipped {len(emb.skipped)} unreadable or empty files")
+    return head

@@ -3,6 +3,7 @@
 // bn_forward()/bn_infer_audio() call into a sequence of kernel launches on the caller's stream.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cctype>
 #include <cmath>
 #include <cstdarg>
@@ -1762,7 +1763,7 @@ int bn_preload_kernels(bn_ctx* ctx) {
     // copies wait meanwhile).  A caller with idle time before its first batch — the evaluate pipeline while the first files are read — asks here.
     bn::preload_ingest(); bn::preload_stft(); bn::preload_stft_exact(); bn::preload_i8_fused(); bn::preload_i8_strip(); bn::preload_i8_tail2();
     bn::preload_i8_tail(); bn::preload_i8(); bn::preload_i8_pw(); bn::preload_f32(); bn::preload_f32_fused(); bn::preload_f32_strip();
-    bn::preload_f32_pw(); bn::preload_melspec(); bn::preload_sort();
+    bn::preload_f32_pw(); bn::preload_melspec(); bn::preload_sort(); bn::preload_probe();
     return BN_OK;
 }
 
@@ -1781,7 +1782,216 @@ const char* bn_kernel_names(void) {
     return "ingest_resample_kernel\ningest_decimate_kernel\ningest_peak_kernel\ningest_chunks_kernel\nchunk_peaknorm_kernel\npool_scores_kernel\nstft512_mag_kernel\nspec_normalize_kernel\nmelspec_finish_kernel\nf32_mel_kernel\nf32_melfin_kernel\nf32_mag_kernel\nf32_rawfe_kernel\nf32_stem_kernel\nf32_dw_kernel\n"
            "f32_pw_kernel\nf32_pw_ws_kernel\nf32_dwpw_kernel\nf32_dwpw_wave_kernel\nf32_strip_kernel\nf32_front_strip_kernel\nf32_front2_kernel\nf32_pwdw_kernel\nf32_dw_stream_kernel\nf32_front_kernel\nf32_gap_kernel\nf32_gap_dense_kernel\nf32_gap_dense_emb_kernel\nf32_dense_kernel\nf32_segate_kernel\nf32_scale_kernel\nf32_attnpool_kernel\n"
            "i8_quant_kernel\ni8_mel_kernel\ni8_stem_kernel\ni8_dw_kernel\ni8_pw_kernel\ni8_dwpw_kernel\ni8_mel_mfma_kernel\ni8_strip_kernel\ni8_strip_mf_kernel\ni8_front_strip_kernel\ni8_front_kernel\ni8_tail_kernel\ni8_tail_emb_kernel\ni8_tail2_kernel\ni8_tail2_emb_kernel\ni8_mid2_kernel\ni8_mean_kernel\ni8_fc_kernel\ni8_scale_kernel\ni8_maxnorm_kernel\ni8_rawfe_kernel\ni8_pwdw_kernel\ni8_dw_stream_kernel\ni8_stem_stream_kernel\ni8_segate_kernel\ni8_pw_wave_kernel\ni8_pw_lds_kernel\ni8_attnpool_kernel\n"
-           "i8_head_kernel\ni8_head_softmax_kernel\nemb_store_kernel";
+           "i8_head_kernel\ni8_head_softmax_kernel\nemb_store_kernel\nprobe_fwd_kernel\nprobe_dw_kernel\nprobe_reduce_kernel\nprobe_update_kernel\nprobe_loss_sum_kernel";
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------- probe (bn_probe.hip)
+struct bn_probe {
+    bn_ctx* ctx = nullptr;
+    int D = 0, C = 0, act = 0, opt = 0;
+    float lr = 0, wd = 0, clip = 0, drop = 0;
+    uint32_t seed = 0;
+    int64_t total = 1, t = 0;                       // steps of the cosine schedule, steps taken
+    float *d_params = nullptr, *d_m = nullptr, *d_v = nullptr;   // [(D + 1) * C] each: W, then the bias as row D
+    float* d_G = nullptr;         size_t G_elems = 0;       // [batch, C] dLoss/dlogits of one step
+    float* d_partial = nullptr;   size_t partial_elems = 0; // [row groups][(D + 1) * C]
+    float* d_loss_part = nullptr; size_t loss_elems = 0;    // one per 16 rows
+    float* d_ss = nullptr;                                   // sums of squares per workgroup of the gradient / reduce kernel
+};
+
+namespace {
+
+int probe_shape_check(int D, int C, int activation) {
+    if (D < 1 || D > BN_PROBE_MAX_D) return fail(BN_ERR_ARG, "embedding width D=%d outside 1..%d", D, BN_PROBE_MAX_D);
+    if (C < 1 || C > BN_PROBE_MAX_C) return fail(BN_ERR_ARG, "class count C=%d outside 1..%d", C, BN_PROBE_MAX_C);
+    if (activation != BN_PROBE_ACT_SIGMOID && activation != BN_PROBE_ACT_SOFTMAX) return fail(BN_ERR_ARG, "unknown activation %d", activation);
+    return BN_OK;
+}
+
+// Most row groups the gradient kernel uses for any batch of up to B rows: enough workgroups for two per CU, at least 16 rows per
+// group, and the partials inside BN_PROBE_WORKSPACE_BYTES.  Monotone in B.
+int64_t probe_group_cap(int B, int D, int C) {
+    const size_t E = (size_t)(D + 1) * C;
+    const int tiles = ((D + 1 + 63) / 64) * ((C + 63) / 64);
+    int64_t g = std::max<int64_t>(1, 512 / tiles);
+    g = std::min<int64_t>(g, std::max<int64_t>(1, (int64_t)(BN_PROBE_WORKSPACE_BYTES / (E * sizeof(float)))));
+    return std::min<int64_t>(g, (B + 15) / 16);
+}
+
+// Row groups of the gradient kernel for a batch of B rows: from the shapes only.  The rows per group are a multiple of 4 (one MFMA
+// k-step), so groups <= probe_group_cap(B) — but NOT monotone in B: a short last batch can have more groups than the full one,
+// which is why the workspace is sized by the cap of the full batch.
+void probe_groups(int B, int D, int C, int* groups, int* rows_per_group) {
+    const int64_t g = probe_group_cap(B, D, C);
+    const int rpg = (int)((((B + g - 1) / g) + 3) & ~(int64_t)3);
+    *rows_per_group = rpg;
+    *groups = (B + rpg - 1) / rpg;
+}
+
+int probe_grow(float** p, size_t* have, size_t need, hipStream_t s) {
+    if (need <= *have) return BN_OK;
+    HIP_TRY(hipStreamSynchronize(s));
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+    *have = 0;
+    if (hipMalloc(p, need * sizeof(float)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(BN_ERR_NOMEM, "hipMalloc of %zu bytes for the probe workspace failed", need * sizeof(float));
+    }
+    *have = need;
+    return BN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bn_head_forward(bn_ctx* ctx, const float* d_emb, int64_t n, int D, const float* d_W, const float* d_b, int C, int activation,
+                    float* d_scores, void* stream) {
+    if (int rc = check_device(ctx)) return rc;
+    if (int rc = probe_shape_check(D, C, activation)) return rc;
+    if (n < 0 || n > 0x7fffffffLL) return fail(BN_ERR_ARG, "bad row count %lld", (long long)n);
+    if (n == 0) return BN_OK;
+    if (!d_emb || !d_W || !d_b || !d_scores) return fail(BN_ERR_ARG, "null device pointer");
+    bn::ProbeFwdArgs a{};
+    a.X = d_emb; a.W = d_W; a.b = d_b; a.out = d_scores; a.n = n; a.D = D; a.C = C; a.softmax = activation == BN_PROBE_ACT_SOFTMAX;
+    if (!bn::launch_probe_fwd(a, 2, (hipStream_t)stream)) return fail(BN_ERR_DEVICE, "the head kernel's LDS request was refused");
+    HIP_TRY(hipGetLastError());
+    return BN_OK;
+}
+
+int bn_probe_create(bn_ctx* ctx, int D, int C, int activation, int optimizer, float lr, float weight_decay, float clipnorm, float dropout,
+                    uint32_t seed, int64_t total_steps, const float* d_W, const float* d_b, bn_probe** out, void* stream) {
+    if (!out) return fail(BN_ERR_ARG, "out is null");
+    *out = nullptr;
+    if (int rc = check_device(ctx)) return rc;
+    if (int rc = probe_shape_check(D, C, activation)) return rc;
+    if (optimizer < BN_PROBE_OPT_ADAM || optimizer > BN_PROBE_OPT_SGD) return fail(BN_ERR_ARG, "unknown optimizer %d", optimizer);
+    if (!(lr >= 0.0f) || !(weight_decay >= 0.0f) || !(clipnorm >= 0.0f)) return fail(BN_ERR_ARG, "lr, weight_decay and clipnorm must be >= 0");
+    if (!(dropout >= 0.0f && dropout < 1.0f)) return fail(BN_ERR_ARG, "dropout %g outside [0, 1)", (double)dropout);
+    if (total_steps < 1) return fail(BN_ERR_ARG, "total_steps must be >= 1");
+    if (!d_W || !d_b) return fail(BN_ERR_ARG, "null device pointer");
+    hipStream_t s = (hipStream_t)stream;
+    bn_probe* p = new bn_probe();
+    p->ctx = ctx; p->D = D; p->C = C; p->act = activation; p->opt = optimizer; p->lr = lr; p->wd = weight_decay; p->clip = clipnorm;
+    p->drop = dropout; p->seed = seed; p->total = total_steps;
+    const size_t E = (size_t)(D + 1) * C;
+    const size_t n_ss = std::max<size_t>((size_t)((D + 1 + 63) / 64) * ((C + 63) / 64), (E + 1023) / 1024);
+    if (hipMalloc(&p->d_params, 3 * E * sizeof(float)) != hipSuccess || hipMalloc(&p->d_ss, n_ss * sizeof(float)) != hipSuccess) {
+        (void)hipGetLastError();
+        bn_probe_destroy(p);
+        return fail(BN_ERR_NOMEM, "hipMalloc of the probe's parameters failed");
+    }
+    p->d_m = p->d_params + E;
+    p->d_v = p->d_m + E;
+    hipError_t e = hipMemsetAsync(p->d_m, 0, 2 * E * sizeof(float), s);
+    if (e == hipSuccess) e = hipMemcpyAsync(p->d_params, d_W, (size_t)D * C * sizeof(float), hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(p->d_params + (size_t)D * C, d_b, (size_t)C * sizeof(float), hipMemcpyDeviceToDevice, s);
+    if (e != hipSuccess) {
+        bn_probe_destroy(p);
+        return fail(BN_ERR_DEVICE, "copying the initial weights failed: %s", hipGetErrorString(e));
+    }
+    *out = p;
+    return BN_OK;
+}
+
+void bn_probe_destroy(bn_probe* p) {
+    if (!p) return;
+    if (p->ctx) (void)hipSetDevice(p->ctx->device);
+    (void)hipDeviceSynchronize();   // steps still in flight read and write the buffers freed below
+    for (float* q : {p->d_params, p->d_G, p->d_partial, p->d_loss_part, p->d_ss})
+        if (q) (void)hipFree(q);
+    delete p;
+}
+
+int bn_probe_epoch(bn_probe* p, const float* d_X, const float* d_Y, const int32_t* d_perm, int64_t n, int batch, float* d_step_loss,
+                   void* stream) {
+    if (!p) return fail(BN_ERR_ARG, "null probe");
+    if (int rc = check_device(p->ctx)) return rc;
+    if (!d_X || !d_Y || !d_perm || !d_step_loss) return fail(BN_ERR_ARG, "null device pointer");
+    if (n < 1 || n > 0x7fffffffLL) return fail(BN_ERR_ARG, "bad row count %lld", (long long)n);
+    if (batch < 1 || batch > n) return fail(BN_ERR_ARG, "batch %d outside 1..%lld", batch, (long long)n);
+    hipStream_t s = (hipStream_t)stream;
+    const int D = p->D, C = p->C, E = (D + 1) * C;
+    int groups, rpg;
+    if (int rc = probe_grow(&p->d_G, &p->G_elems, (size_t)batch * C, s)) return rc;
+    if (int rc = probe_grow(&p->d_partial, &p->partial_elems, (size_t)probe_group_cap(batch, D, C) * E, s)) return rc;
+    if (int rc = probe_grow(&p->d_loss_part, &p->loss_elems, (size_t)(batch + 15) / 16, s)) return rc;
+    const uint32_t thresh = p->drop > 0.0f ? (uint32_t)std::ceil((double)p->drop * 16777216.0) : 0u;
+    const float drop_scale = (float)(1.0 / (1.0 - (double)p->drop));
+    const int64_t steps = (n + batch - 1) / batch;
+    for (int64_t st = 0; st < steps; ++st, ++p->t) {
+        const int B = (int)std::min<int64_t>(batch, n - st * batch);
+        const int32_t* idx = d_perm + st * batch;
+        const double frac = (double)std::min<int64_t>(p->t, p->total) / (double)p->total;
+        const double lr_t = (double)p->lr * 0.5 * (1.0 + std::cos(M_PI * frac));
+        const double t1 = (double)(p->t + 1);
+        const double alpha = lr_t * std::sqrt(1.0 - std::pow(0.999, t1)) / (1.0 - std::pow(0.9, t1));
+        bn::ProbeFwdArgs f{};
+        f.X = d_X; f.Y = d_Y; f.idx = idx; f.W = p->d_params; f.b = p->d_params + (size_t)D * C; f.out = p->d_G; f.loss_part = p->d_loss_part;
+        f.n = B; f.D = D; f.C = C; f.softmax = p->act == BN_PROBE_ACT_SOFTMAX; f.drop_thresh = thresh; f.drop_scale = drop_scale;
+        f.seed = p->seed; f.step = (uint32_t)p->t;
+        f.g_scale = p->act == BN_PROBE_ACT_SOFTMAX ? (float)(1.0 / B) : (float)(1.0 / ((double)B * C));
+        if (!bn::launch_probe_fwd(f, 0, s)) return fail(BN_ERR_DEVICE, "the probe forward kernel's LDS request was refused");
+        probe_groups(B, D, C, &groups, &rpg);
+        if ((size_t)groups * E > p->partial_elems) return fail(BN_ERR_UNSUPPORTED, "%d row groups exceed the gradient workspace", groups);
+        bn::ProbeDwArgs g{};
+        g.X = d_X; g.idx = idx; g.G = p->d_G; g.partial = p->d_partial; g.ss_part = p->d_ss; g.B = B; g.D = D; g.C = C; g.E = E;
+        g.rows_per_group = rpg; g.drop_thresh = thresh; g.drop_scale = drop_scale; g.seed = p->seed; g.step = (uint32_t)p->t;
+        bn::launch_probe_dw(g, groups, s);
+        int n_ss = ((D + 1 + 63) / 64) * ((C + 63) / 64);
+        if (groups > 1) {
+            bn::launch_probe_reduce(p->d_partial, E, groups, p->d_ss, s);
+            n_ss = (E + 1023) / 1024;
+        }
+        bn::ProbeUpdateArgs u{};
+        u.params = p->d_params; u.m = p->d_m; u.v = p->d_v; u.grad = p->d_partial; u.ss_part = p->d_ss; u.n_ss = n_ss;
+        u.loss_part = p->d_loss_part; u.n_loss = (B + 15) / 16; u.loss_scale = f.g_scale; u.step_loss = d_step_loss + st;
+        u.E = E; u.optimizer = p->opt; u.lr = (float)lr_t; u.alpha = (float)alpha; u.weight_decay = p->wd; u.clip = p->clip;
+        bn::launch_probe_update(u, s);
+    }
+    HIP_TRY(hipGetLastError());
+    return BN_OK;
+}
+
+int bn_probe_loss(bn_probe* p, const float* d_X, const float* d_Y, int64_t n, float* d_out, void* stream) {
+    if (!p) return fail(BN_ERR_ARG, "null probe");
+    if (int rc = check_device(p->ctx)) return rc;
+    if (!d_X || !d_Y || !d_out) return fail(BN_ERR_ARG, "null device pointer");
+    if (n < 1 || n > 0x7fffffffLL) return fail(BN_ERR_ARG, "bad row count %lld", (long long)n);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t parts = (size_t)(n + 15) / 16;
+    if (int rc = probe_grow(&p->d_loss_part, &p->loss_elems, parts, s)) return rc;
+    bn::ProbeFwdArgs f{};
+    f.X = d_X; f.Y = d_Y; f.W = p->d_params; f.b = p->d_params + (size_t)p->D * p->C; f.loss_part = p->d_loss_part;
+    f.n = n; f.D = p->D; f.C = p->C; f.softmax = p->act == BN_PROBE_ACT_SOFTMAX;
+    if (!bn::launch_probe_fwd(f, 1, s)) return fail(BN_ERR_DEVICE, "the probe forward kernel's LDS request was refused");
+    const float scale = p->act == BN_PROBE_ACT_SOFTMAX ? (float)(1.0 / (double)n) : (float)(1.0 / ((double)n * p->C));
+    bn::launch_probe_loss_sum(p->d_loss_part, (long)parts, scale, d_out, s);
+    HIP_TRY(hipGetLastError());
+    return BN_OK;
+}
+
+int bn_probe_get(bn_probe* p, float* d_W, float* d_b, void* stream) {
+    if (!p) return fail(BN_ERR_ARG, "null probe");
+    if (int rc = check_device(p->ctx)) return rc;
+    if (!d_W || !d_b) return fail(BN_ERR_ARG, "null device pointer");
+    const size_t nw = (size_t)p->D * p->C;
+    HIP_TRY(hipMemcpyAsync(d_W, p->d_params, nw * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    HIP_TRY(hipMemcpyAsync(d_b, p->d_params + nw, (size_t)p->C * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return BN_OK;
+}
+
+int bn_probe_set(bn_probe* p, const float* d_W, const float* d_b, void* stream) {
+    if (!p) return fail(BN_ERR_ARG, "null probe");
+    if (int rc = check_device(p->ctx)) return rc;
+    if (!d_W || !d_b) return fail(BN_ERR_ARG, "null device pointer");
+    const size_t nw = (size_t)p->D * p->C;
+    HIP_TRY(hipMemcpyAsync(p->d_params, d_W, nw * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    HIP_TRY(hipMemcpyAsync(p->d_params + nw, d_b, (size_t)p->C * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return BN_OK;
 }
 
 }  // extern "C"

@@ -466,7 +466,43 @@ void launch_i8_dwpw(const DwPw8Args& a, hipStream_t s);
 // One per source file with kernels: load that file's device code object now (bn_preload_kernels)
 void preload_f32(); void preload_f32_fused(); void preload_f32_pw(); void preload_f32_strip(); void preload_i8(); void preload_i8_fused();
 void preload_i8_pw(); void preload_i8_strip(); void preload_i8_tail(); void preload_i8_tail2(); void preload_ingest(); void preload_melspec();
-void preload_stft(); void preload_stft_exact(); void preload_sort();
+void preload_stft(); void preload_stft_exact(); void preload_sort(); void preload_probe();
+
+// bn_probe.hip: a classifier head on embeddings (bn_head_forward) and its training step (bn_probe_*)
+struct ProbeFwdArgs {
+    const float* X;        // [*, D] embedding rows
+    const float* Y;        // [*, C] targets (modes 0 and 1)
+    const int* idx;        // [n] row of X / Y behind batch row i, or null: row i itself
+    const float* W;        // [D, C]
+    const float* b;        // [C]
+    float* out;            // mode 0: G [n, C] = dLoss/dlogits, mode 2: scores [n, C]
+    float* loss_part;      // [ceil(n / 16)] modes 0 and 1
+    long n;
+    int D, C, softmax;
+    uint32_t drop_thresh;  // keep iff draw >= drop_thresh (0: no dropout)
+    float drop_scale;      // 1 / (1 - p)
+    uint32_t seed, step;
+    float g_scale;         // 1 / (n C) (sigmoid) or 1 / n (softmax)
+};
+struct ProbeDwArgs {
+    const float* X; const int* idx; const float* G;
+    float* partial;        // [row groups][(D + 1) * C]
+    float* ss_part;        // [tiles] sums of squares (written with one row group only)
+    int B, D, C, E, rows_per_group;
+    uint32_t drop_thresh; float drop_scale; uint32_t seed, step;
+};
+struct ProbeUpdateArgs {
+    float* params; float* m; float* v; const float* grad;   // [(D + 1) * C] each, the bias is row D
+    const float* ss_part; int n_ss;
+    const float* loss_part; int n_loss; float loss_scale; float* step_loss;
+    int E, optimizer;      // BN_PROBE_OPT_* (include/birdnet_hip.h)
+    float lr, alpha, weight_decay, clip;
+};
+bool launch_probe_fwd(const ProbeFwdArgs& a, int mode, hipStream_t s);   // false: the runtime refused the LDS request
+void launch_probe_dw(const ProbeDwArgs& a, int row_groups, hipStream_t s);
+void launch_probe_reduce(float* partial, int E, int groups, float* ss_part, hipStream_t s);
+void launch_probe_update(const ProbeUpdateArgs& a, hipStream_t s);
+void launch_probe_loss_sum(const float* part, long n, float scale, float* out, hipStream_t s);
 
 // bn_sort.hip: descending orders of the score matrix for the ranking metrics (per class [C][N] row indices, flattened [N*C] flat indices)
 size_t rank_orders_workspace(int N, int C);

@@ -340,6 +340,49 @@ BN_API int bn_ctx_reset_options(bn_ctx* ctx);
 BN_API void* bn_host_alloc_pinned(bn_ctx* ctx, size_t bytes);
 BN_API int bn_host_free_pinned(void* p);
 
+/* ---- A classifier head on frozen embeddings: scores = act(dropout(x) W + b) (csrc/bn_probe.hip) --------------------------------
+ * (Reference counterpart: birdnet_stm32/training/linear_probe.py — Dropout -> Dense(len(classes)) behind the pooled vector, trained by
+ * Keras with the backbone frozen.  Here the backbone has already run: the rows of X are embeddings, bn_forward_embed's output.)
+ * All arithmetic is float32; the products run on the f32-input matrix instruction (exact f32).  W is [D, C] row-major, b is [C],
+ * 1 <= D <= BN_PROBE_MAX_D, 1 <= C <= BN_PROBE_MAX_C. */
+#define BN_PROBE_MAX_D 2048
+#define BN_PROBE_MAX_C 4096
+#define BN_PROBE_ACT_SIGMOID 0 /* loss: binary cross-entropy, mean over rows x classes (Keras: p clipped to [1e-7, 1 - 1e-7]) */
+#define BN_PROBE_ACT_SOFTMAX 1 /* loss: categorical cross-entropy, mean over rows */
+#define BN_PROBE_OPT_ADAM 0    /* Keras defaults: beta 0.9 / 0.999, eps 1e-7 added to sqrt(v), bias correction folded into the step size */
+#define BN_PROBE_OPT_ADAMW 1   /* ... and w -= lr_t * weight_decay * w in front of the step (weights and bias) */
+#define BN_PROBE_OPT_SGD 2     /* momentum 0.9, Keras form: v = 0.9 v - lr_t g; w += v */
+/* Bound on the gradient workspace of one bn_probe: the batch is split into row groups whose partial gradients ((D + 1) * C floats each,
+ * 32 MiB for the largest head) are added in a fixed order, and the number of groups is chosen from the shapes so that they fit. */
+#define BN_PROBE_WORKSPACE_BYTES (256u << 20)
+
+typedef struct bn_probe bn_probe;
+
+/* d_scores[n, C] = act(d_emb[n, D] d_W + d_b): the scores of a head over n embedding rows (the forward tiles of the training step). */
+BN_API int bn_head_forward(bn_ctx* ctx, const float* d_emb, int64_t n, int D, const float* d_W, const float* d_b, int C, int activation,
+                    float* d_scores, void* stream);
+
+/* A head in training.  d_W / d_b: the initial values (copied; the optimiser state starts at zero).  Learning rate of global step t
+ * (0-based, counted over all bn_probe_epoch calls): lr * 0.5 * (1 + cos(pi * min(t, total_steps) / total_steps)).  clipnorm > 0: the
+ * gradient of W and b together is scaled by clipnorm / norm when its norm exceeds clipnorm.  dropout in [0, 1): element (row i of the
+ * batch, column j) of step t is kept (and scaled by 1 / (1 - dropout)) iff a 24-bit hash of (seed, t, i, j) is >= ceil(dropout * 2^24)
+ * (DESIGN.md 5d gives the function; it is stateless). */
+BN_API int bn_probe_create(bn_ctx* ctx, int D, int C, int activation, int optimizer, float lr, float weight_decay, float clipnorm,
+                    float dropout, uint32_t seed, int64_t total_steps, const float* d_W, const float* d_b, bn_probe** out, void* stream);
+/* Waits for the device to finish (steps still enqueued use the probe's buffers), then frees the probe. */
+BN_API void bn_probe_destroy(bn_probe* probe);
+/* Enqueues the ceil(n / batch) steps of one epoch: step s trains on rows d_perm[s * batch ...] (int32 row numbers into d_X [*, D] and
+ * d_Y [*, C]; the last batch may be short, means are over its real rows) and writes its loss to d_step_loss[s].  Nothing synchronises
+ * with the host inside the call; the same inputs give the same bits on every run (no floating-point atomics).  On an error the steps
+ * enqueued before it still run and count as taken. */
+BN_API int bn_probe_epoch(bn_probe* probe, const float* d_X, const float* d_Y, const int32_t* d_perm, int64_t n, int batch,
+                   float* d_step_loss, void* stream);
+/* *d_out = the mean loss of the current weights over rows 0 .. n-1 of d_X / d_Y, without dropout (validation). */
+BN_API int bn_probe_loss(bn_probe* probe, const float* d_X, const float* d_Y, int64_t n, float* d_out, void* stream);
+/* Copy the weights [D, C] and bias [C] out of / into the probe (device pointers; the optimiser state is left alone). */
+BN_API int bn_probe_get(bn_probe* probe, float* d_W, float* d_b, void* stream);
+BN_API int bn_probe_set(bn_probe* probe, const float* d_W, const float* d_b, void* stream);
+
 /* Loads every device code object of the library now.  The HIP runtime loads one at the first launch of any of its kernels (a few ms each; launches
  * and copies of OTHER threads wait meanwhile), which a first batch otherwise pays one file after the other on its critical path; a caller with idle
  * time before that batch (the evaluate pipeline while the first files are being read) calls this instead.  Idempotent.  (Reference counterpart:

@@ -1,0 +1,95 @@
+"""Steps per second and seconds per epoch of ``fit_probe`` against the same training step written with PyTorch ops on the same GPU.
+
+    python tools/probe_bench.py [--rows 262144] [--epochs 2]
+
+D = 256, C in {12, 100, 1000}, batch in {32, 512, 4096}, random rows.  The PyTorch side is what a user would write without the device
+fit: gather, dropout, ``torch.nn.functional.linear``, sigmoid + binary cross-entropy, backward, ``clip_grad_norm_``, ``torch.optim.Adam``
+with a cosine schedule.  Both sides are timed over whole epochs (first epoch discarded as warm-up), synchronised at the epoch's end only.
+Prints one JSON line per cell and a markdown table.
+"""
+
+import argparse
+import json
+import math
+import os
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [REPO, os.path.join(REPO, "birdnet-stm32_amd")]
+
+
+def torch_epoch_fn(torch, X, Y, C, batch, total_steps):
+    lin = torch.nn.Linear(X.shape[1], C, device=X.device)
+    opt = torch.optim.Adam(lin.parameters(), lr=1e-3, eps=1e-7)
+    sched = torch.optim.lr_scheduler.CosineAnnealingLR(opt, total_steps)
+    drop = torch.nn.Dropout(0.5)
+
+    def epoch(perm):
+        for s in range(0, X.shape[0], batch):
+            idx = perm[s : s + batch]
+            loss = torch.nn.functional.binary_cross_entropy(torch.sigmoid(torch.nn.functional.linear(drop(X[idx]), lin.weight, lin.bias)), Y[idx])
+            opt.zero_grad(set_to_none=True)
+            loss.backward()
+            torch.nn.utils.clip_grad_norm_(lin.parameters(), 1.0)
+            opt.step()
+            sched.step()
+        torch.cuda.synchronize()
+
+    return epoch
+
+
+def main():
+    import numpy as np
+    import torch
+
+    from birdnet_stm32 import _hip
+    from birdnet_stm32.training import linear_probe as lp
+
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, default=262144)
+    ap.add_argument("--epochs", type=int, default=2, help="timed epochs per cell (one more runs first as warm-up)")
+    args = ap.parse_args()
+    n, D = args.rows, 256
+    ctx = _hip.Context(0, 1)
+    g = torch.Generator(device="cuda").manual_seed(1)
+    X = torch.rand((n, D), device="cuda", generator=g)
+    rows = []
+    for C in (12, 100, 1000):
+        Y = torch.zeros((n, C), device="cuda")
+        Y[torch.arange(n, device="cuda"), torch.randint(0, C, (n,), device="cuda", generator=g)] = 1.0
+        for batch in (32, 512, 4096):
+            steps = math.ceil(n / batch)
+            total = steps * (args.epochs + 1)
+            W0, b0 = lp.init_head(D, C, 1)
+            cfg = dict(activation="sigmoid", optimizer="adam", batch=batch, seed=1, dropout=0.5, clipnorm=1.0, lr=1e-3, weight_decay=0.0, total=total)
+            be = lp._DeviceBackend(ctx, X, Y, None, None, W0, b0, cfg)
+            ours = []
+            for e in range(args.epochs + 1):
+                perm = lp.epoch_permutation(1, e, n)
+                t0 = time.perf_counter()
+                be.epoch(perm)   # (uploads the permutation, reads the step losses back: synchronises)
+                ours.append(time.perf_counter() - t0)
+            be.close()
+            ep = torch_epoch_fn(torch, X, Y, C, batch, total)
+            theirs = []
+            for e in range(args.epochs + 1):
+                perm = torch.from_numpy(lp.epoch_permutation(1, e, n).astype(np.int64)).cuda()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                ep(perm)
+                theirs.append(time.perf_counter() - t0)
+            a, b = min(ours[1:]), min(theirs[1:])
+            row = dict(D=D, C=C, batch=batch, steps_per_epoch=steps, fit_probe_s_per_epoch=a, fit_probe_steps_per_s=steps / a, torch_s_per_epoch=b,
+                       torch_steps_per_s=steps / b, speedup=b / a)
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+    print("\n| C | batch | fit_probe steps/s | s/epoch | PyTorch steps/s | s/epoch | ratio |\n|---|---|---|---|---|---|---|")
+    for r in rows:
+        print(f"| {r['C']} | {r['batch']} | {r['fit_probe_steps_per_s']:.0f} | {r['fit_probe_s_per_epoch']:.3f} | {r['torch_steps_per_s']:.0f} | "
+              f"{r['torch_s_per_epoch']:.3f} | {r['speedup']:.2f} |")
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
