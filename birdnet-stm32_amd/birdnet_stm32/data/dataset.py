@@ -20,11 +20,12 @@ _NOISE = {"noise", "silence", "background", "other"}
 def load_file_paths_from_directory(directory: str, classes: list[str] | None = None, max_samples: int | None = None,
                                    exts: tuple = SUPPORTED_AUDIO_EXTS) -> tuple[list[str], list[str]]:
     by_class: dict[str, list[str]] = {}
-    for root, _dirs, names in os.walk(directory):
+    for root, dirs, names in os.walk(directory):
+        dirs.sort()   # (directory order is the file system's: sorted, a seed gives the same shuffle, split and trained head on every machine)
         label = os.path.basename(root)
         if classes is not None and label not in classes:
             continue
-        for name in names:
+        for name in sorted(names):
             if name.lower().endswith(exts):
                 by_class.setdefault(label, []).append(os.path.join(root, name))
     paths: list[str] = []

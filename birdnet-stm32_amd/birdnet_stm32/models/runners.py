@@ -282,6 +282,22 @@ class HipRunner:
         _hip.check(self.lib.bn_debug_mid_form(self.model.handle, ctypes.byref(form), ctypes.byref(lds)))
         return form.value, lds.value
 
+    def mid_plan(self) -> dict | None:
+        """Test hook: the resident LDS placement of the fused stage-2 chain (option ``i8_mid_split``), ``None`` where the plan has none.
+        ``parts`` = (offset, bytes) of every block's depthwise part, pointwise part and zero-point row."""
+        out = (ctypes.c_int * 64)()
+        _hip.check(self.lib.bn_debug_mid_plan(self.model.handle, out, 64))
+        if not out[0]:
+            return None
+        parts = [(out[5 + 6 * i + 2 * k], out[6 + 6 * i + 2 * k]) for i in range(out[4]) for k in range(3) if out[6 + 6 * i + 2 * k]]
+        return {"lds_bytes": out[1], "map_bytes": out[2], "bar_off": out[3], "blocks": out[4], "parts": parts}
+
+    def mid_split_giveups(self) -> int:
+        """Test hook: chunk barriers of ``i8_mid2_kernel`` whose bounded wait ran out since the library was loaded (0 in a working build)."""
+        n = ctypes.c_int64(0)
+        _hip.check(self.lib.bn_debug_mid_split_giveups(self.ctx.handle, ctypes.byref(n)))
+        return int(n.value)
+
     # -- per-operator timing (HIP events on the launch stream) ------------------------------------
     def profile(self, enable: bool) -> None:
         _hip.check(self.lib.bn_profile_enable(self.model.handle, int(bool(enable))))

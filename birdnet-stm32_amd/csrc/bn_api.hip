@@ -50,7 +50,7 @@ const OptName kOptions[] = {
     {"f32_strip", &bn::Options::f32_strip},       {"f32_strip_th", &bn::Options::f32_strip_th},
     {"f32_front_staged", &bn::Options::f32_front_staged}, {"f32_front2", &bn::Options::f32_front2}, {"f32_pwdw", &bn::Options::f32_pwdw}, {"f32_tile_slice", &bn::Options::f32_tile_slice}, {"f32_pw_ws", &bn::Options::f32_pw_ws}, {"i8_pwdw", &bn::Options::i8_pwdw}, {"i8_pw_lds", &bn::Options::i8_pw_lds}, {"i8_pw_forms", &bn::Options::i8_pw_forms}, {"i8_add_tab", &bn::Options::i8_add_tab}, {"front_tpw", &bn::Options::front_tpw},
     {"wave_dwpw", &bn::Options::wave_dwpw},       {"i8_strip", &bn::Options::i8_strip},
-    {"i8_strip_th", &bn::Options::i8_strip_th}, {"i8_dw_pool", &bn::Options::i8_dw_pool}, {"i8_tail_fclds", &bn::Options::i8_tail_fclds},   {"i8_tail", &bn::Options::i8_tail}, {"i8_tail_mfdw", &bn::Options::i8_tail_mfdw}, {"i8_mid", &bn::Options::i8_mid},
+    {"i8_strip_th", &bn::Options::i8_strip_th}, {"i8_dw_pool", &bn::Options::i8_dw_pool}, {"i8_tail_fclds", &bn::Options::i8_tail_fclds},   {"i8_tail", &bn::Options::i8_tail}, {"i8_tail_mfdw", &bn::Options::i8_tail_mfdw}, {"i8_mid", &bn::Options::i8_mid}, {"i8_mid_split", &bn::Options::i8_mid_split},
     {"i8_mel_generic", &bn::Options::i8_mel_generic}, {"stft_rowmajor", &bn::Options::stft_rowmajor},
     {"i8_strip_mfdw", &bn::Options::i8_strip_mfdw}, {"stft_exact", &bn::Options::stft_exact}, {"stft_flagcap", &bn::Options::stft_flagcap}, {"stft_guard", &bn::Options::stft_guard}, {"stft_audit", &bn::Options::stft_audit}, {"stft_minint", &bn::Options::stft_minint},
     {"ingest_blk", &bn::Options::ingest_blk},
@@ -108,6 +108,8 @@ struct bn_model {
     std::vector<uint8_t> tail2_ok;
     std::vector<bn::Tail2Args> mids;     // per operator: arguments of the fused stage-2 chain (BN_OP_I8_MID operators only)
     std::vector<uint8_t> mid_ok;
+    std::vector<bn::Tail2Args> mids_res;   // the same chains with the resident LDS placement (option i8_mid_split) ...
+    std::vector<uint8_t> mid_res_ok;       // ... where it fits
     bool has_mid = false;
     std::vector<uint8_t> out_valid;      // per operator: it wrote its output slot in the last forward call (not when a fused kernel covered it)
     std::vector<uint8_t> slot_valid;     // per slot: some operator wrote it in the last forward call
@@ -635,7 +637,7 @@ int run_plan(bn_model* m, const float* d_input, const float* d_minmax, int B, fl
                 break;
             }
             case BN_OP_I8_MID: {
-                bn::Tail2Args ma = m->mids[oi];
+                bn::Tail2Args ma = bn::g_opt.i8_mid_split && m->mid_res_ok[oi] ? m->mids_res[oi] : m->mids[oi];
                 ma.x = (const int8_t*)in0;
                 ma.y = (int8_t*)out;
                 ma.cst = (const int32_t*)m->tensor(o.t[0]);
@@ -941,6 +943,8 @@ int bn_model_load(bn_ctx* ctx, const void* blob, size_t nbytes, bn_model** out) 
     m->tail2_ok.assign(h.n_ops, 0);
     m->mids.resize(h.n_ops);
     m->mid_ok.assign(h.n_ops, 0);
+    m->mids_res.resize(h.n_ops);
+    m->mid_res_ok.assign(h.n_ops, 0);
     for (size_t oi = 0; oi < m->ops.size(); ++oi) {
         const OpRec& o = m->ops[oi];
         if (o.kind != BN_OP_I8_MID) continue;
@@ -952,6 +956,8 @@ int bn_model_load(bn_ctx* ctx, const void* blob, size_t nbytes, bn_model** out) 
                         ma.L[0].H == o.p[6] && ma.L[0].W == o.p[7] && ma.L[0].Cin == o.p[8] && bn::tail2_const_words(ma, true) * 4 <= (long)tc.nbytes &&
                         ma.L[o.p[5] - 1].OH * ma.L[o.p[5] - 1].OW == o.p[9] && ma.L[o.p[5] - 1].Cout == o.p[10];
         m->mid_ok[oi] = ok;
+        m->mids_res[oi] = ma;
+        m->mid_res_ok[oi] = ok && bn::tail2_plan_resident(m->mids_res[oi]);
         m->has_mid = m->has_mid || ok;
     }
     for (size_t oi = 0; oi < m->ops.size(); ++oi) {
@@ -1406,6 +1412,26 @@ int bn_debug_mid_form(const bn_model* m, int* form, int* lds_bytes) {
             *form = 1;
             *lds_bytes = m->mids[oi].lds_bytes;
         }
+    return BN_OK;
+}
+
+int bn_debug_mid_plan(const bn_model* m, int* out, int n) {
+    if (!m || !out || n < 1) return fail(BN_ERR_ARG, "null argument");
+    out[0] = 0;
+    for (size_t oi = 0; oi < m->ops.size(); ++oi)
+        if (m->ops[oi].kind == BN_OP_I8_MID && m->mid_ok[oi] && m->mid_res_ok[oi]) {
+            if (!bn::tail2_plan_dump(m->mids_res[oi], out, n)) return fail(BN_ERR_ARG, "n=%d is too small for the plan", n);
+            break;
+        }
+    return BN_OK;
+}
+
+int bn_debug_mid_split_giveups(bn_ctx* ctx, int64_t* count) {
+    if (!ctx || !count) return fail(BN_ERR_ARG, "null argument");
+    if (int rc = check_device(ctx)) return rc;
+    const long n = bn::tail2_giveups();
+    if (n < 0) return fail(BN_ERR_DEVICE, "could not read the chunk barriers' give-up counter");
+    *count = n;
     return BN_OK;
 }
 

@@ -37,11 +37,14 @@
 // Constants never make a wave wait for memory: a block's depthwise part (expanded weights + constants) is requested while the PREVIOUS
 // block's pointwise phase runs and written to LDS behind it, its pointwise part (weights + constants) is requested before the block's
 // own depthwise phase and written behind that — two barriers per block, none of them behind a load (tail2_plan places the parts so that
-// nothing live is overwritten).
+// nothing live is overwritten).  i8_mid2_kernel's constants fit beside its maps all at once: there they are staged once per launch and the
+// barriers shrink to the waves of one chunk (mid2_main, chunk_barrier; option i8_mid_split).
 //
 // The first block streams its taps from global memory (range-checked 16-byte buffer loads: a tap outside the map reads 0; what the
 // folded bias assumed for it — the zero point — is taken back through per-border variants of the bias).
 #include "bn_tail_common.h"
+
+#include <algorithm>
 
 namespace bn {
 namespace {
@@ -51,9 +54,12 @@ namespace {
 // barrier (s_memrealtime: 100 MHz) — tools/tail2_stamps.py.
 #ifdef BN_TAIL_STAMPS
 __device__ long long* g_tail2_stamps = nullptr;   // [workgroup < 8][group < 4][block < 8][wave 8][8]
+__device__ long long* g_mid2_stamps = nullptr;    // the same for i8_mid2_kernel (block < 3)
 // (only the stamps right behind a barrier are taken — 0, 4, 6: a stamp in the middle of a phase needs a scheduling fence and changes what it measures;
-// the stamped launch is within 2 % of the production one)
-#define BN_T2STAMP(i) do { if ((i) == 0 || (i) == 4 || (i) == 6) st[i] = (long long)__builtin_amdgcn_s_memrealtime(); } while (0)
+// the stamped launch is within 2 % of the production one.  1 and 2 are a wave's ARRIVAL at the middle / end barrier, taken behind the last
+// scheduling fence of the phase in front of it; 3 and 5 are taken behind a chunk barrier the stamped build puts in front of the workgroup's
+// barrier: when the last wave of the wave's OWN chunk arrived — tools/tail2_stamps.py splits a wave's wait with them.)
+#define BN_T2STAMP(i) do { if ((i) != 7) st[i] = (long long)__builtin_amdgcn_s_memrealtime(); } while (0)
 #else
 #define BN_T2STAMP(i) do {} while (0)
 #endif
@@ -74,9 +80,54 @@ __device__ __forceinline__ void part_request(const int32_t* src, unsigned char* 
                                              (__attribute__((address_space(3))) void*)(dst + (i * kTail2Threads + wave * 64) * 16), 16, 0, 0);
     }
 }
+// A barrier over the WPC waves that share ONE chunk slot's map (tail2_block gives every wave tiles of one chunk), for the form of
+// i8_mid2_kernel whose constants stay in LDS: nothing but a chunk's own map is ever overwritten there, so nothing orders the waves of
+// different chunks.  One monotonic LDS counter per chunk slot (zeroed once at the top of the kernel, in front of a __syncthreads):
+//   arrive  the wave drains its own LDS operations (s_waitcnt lgkmcnt(0): its reads of the map have returned, its writes are in the
+//           array), a workgroup-scope release fence keeps the compiler's LDS accesses in front, one lane adds 1;
+//   wait    every lane reads the counter (one broadcast read, made wave-uniform with readfirstlane) until it has reached `target`, with
+//           s_sleep between the polls so that the SIMD's issue slots go to the waves that still work; then an acquire fence.
+// Counter arithmetic: a wave counts the barriers it has passed in `seq` (a scalar register it carries through the kernel); all WPC
+// waves of a slot run the same sequence of barriers — the group loop's bounds depend on blockIdx only, and in a ragged last group the
+// spare slot repeats the last chunk and ARRIVES like any other (it only stores nothing) — so barrier number seq completes when the
+// counter reads WPC seq: target = WPC * seq, compared as a signed difference (wrap-around after 2^32 / WPC barriers is harmless).  A wave
+// that runs ahead cannot pass barrier seq + 1 before every wave has arrived at it, hence has left barrier seq: one counter suffices.
+// No wave can starve the one it waits for: a workgroup's waves are all resident from its launch to its end (a workgroup is dispatched
+// whole), each has its own program counter, and s_sleep yields the issue slot; the spin needs no other workgroup to make progress.
+// The spin is bounded all the same (~0.1 s): a wave that gives up counts it in g_tail2_giveups and goes on — wrong bytes that the
+// tests catch (bn_debug_mid_split_giveups) instead of a kernel that never ends.  The counters stay consistent: it HAS arrived.
+__device__ unsigned g_tail2_giveups = 0;
+#ifdef BN_TAIL_STAMPS
+constexpr bool kStamped = true;
+#else
+constexpr bool kStamped = false;
+#endif
+template <int WPC>
+__device__ __forceinline__ void chunk_barrier(unsigned char* lds, int bar_off, int slot, unsigned& seq) {
+    unsigned* ctr = reinterpret_cast<unsigned*>(lds + bar_off) + slot;
+    seq += 1;
+    const unsigned target = (unsigned)WPC * seq;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+    if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    bool done = false;
+#pragma unroll 1
+    for (int spins = 0; spins < (1 << 20); ++spins) {
+        const unsigned v = (unsigned)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+        if ((int)(v - target) >= 0) {
+            done = true;
+            break;
+        }
+        __builtin_amdgcn_s_sleep(1);
+    }
+    if (!done && (threadIdx.x & 63) == 0) atomicAdd(&g_tail2_giveups, 1u);
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
+
 constexpr int kTail2MaxDw16 = 7 * kTail2Threads;   // sixteen-byte pieces of the largest depthwise part a block may prefetch (256 channels: 3392)
 
 __device__ __forceinline__ int tail2_dw_bytes(const Tail2Layer& L, bool first) { return (L.Cin / 16) * (3 * 1024 + (first ? 8 : 5) * 64); }
+__device__ __forceinline__ int tail2_pw_bytes(const Tail2Layer& L) { return (L.Cin + 63) / 64 * 64 * L.Cout + (L.Cout / 16) * 5 * 64; }
 
 // MultiplyByQuantizedMultiplier for either sign in four instructions (the block's own term of a residual ADD: no activation, no clamp):
 //   hi = (x M' + C) >> 32 with M' = the dword 2 m read as signed (= 2 m - 2^32) and C = (2^(e-1) << 32) + 2^31
@@ -201,8 +252,10 @@ __device__ __forceinline__ void tail2_head(const Tail2Args& a_, unsigned char* l
 // One block for the G chunks of the workgroup; maps are [chunk][position][C + 16 bytes], input and output at the same place.
 // A wave owns TPW tiles of 16 positions stacked vertically in ONE column strip of ONE chunk (a 32-wide map has two strips; a tile of an
 // 8-wide map is two rows) and walks them in passes of at most four.
-template <int G, int CIN, int COUT, int S, int H, int W, bool ADD, bool SRCG>
-__device__ __forceinline__ void tail2_block(const Tail2Layer& L, const Tail2Args& a, unsigned char* lds, int chunk0, int nxi, int stamp_slot = -1) {
+// RES (i8_mid2_kernel with every block's constants resident in LDS, tail2_plan_resident): nothing is staged here, and the two barriers
+// order the WPC waves of the wave's chunk slot only (chunk_barrier; `seq` = the barriers the wave has passed).
+template <int G, int CIN, int COUT, int S, int H, int W, bool ADD, bool SRCG, bool RES = false>
+__device__ __forceinline__ void tail2_block(const Tail2Layer& L, const Tail2Args& a, unsigned char* lds, int chunk0, int nxi, unsigned& seq, int stamp_slot = -1) {
 #ifdef BN_TAIL_STAMPS
     long long st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #endif
@@ -233,9 +286,7 @@ __device__ __forceinline__ void tail2_block(const Tail2Layer& L, const Tail2Args
     const int n = lane & 15, g = lane >> 4;
 
     // ---- request the block's pointwise part (its depthwise part and zero-point row are in LDS already) ------------------------------
-    part_request<PWP>(a.cst + L.g_cst + (DWA_BYTES + DWC_BYTES) / 4, lds + L.pw_off, PW16, tid);
-    BN_T2STAMP(1);
-    BN_T2STAMP(2);
+    if constexpr (!RES) part_request<PWP>(a.cst + L.g_cst + (DWA_BYTES + DWC_BYTES) / 4, lds + L.pw_off, PW16, tid);
 
     const v4i* wl = reinterpret_cast<const v4i*>(lds + L.pw_off) + lane;
     const v4i* dwa = reinterpret_cast<const v4i*>(lds + L.dw_off) + lane;
@@ -340,13 +391,25 @@ __device__ __forceinline__ void tail2_block(const Tail2Layer& L, const Tail2Args
         __builtin_amdgcn_sched_barrier(0);
     }
     }  // pass
-    BN_T2STAMP(3);
-    __syncthreads();   // the pointwise part has landed, and every wave has read its taps: the map may be overwritten
+    BN_T2STAMP(1);
+    if constexpr (RES) {
+        // the chunk's waves have read their taps: its map may be overwritten.  (A block with its taps from memory has read no map: none of its
+        // waves waits.  What a wave overwrites there was last READ by itself — residual bytes and write-back are a wave's own positions.)
+        if constexpr (!SRCG) chunk_barrier<WPC>(lds, a.bar_off, gch, seq);
+    } else {
+#ifdef BN_TAIL_STAMPS
+        if (a.bar_off >= 0) chunk_barrier<WPC>(lds, a.bar_off, gch, seq);
+        BN_T2STAMP(3);
+#endif
+        __syncthreads();   // the pointwise part has landed, and every wave has read its taps: the map may be overwritten
+    }
     BN_T2STAMP(4);
     // the successor's depthwise part (block 0 of the next group behind the last block): requested now, complete at the end barrier
     const Tail2Layer& N = a.L[nxi < 0 ? 0 : nxi];
-    const int nx_n16 = nxi < 0 ? 0 : tail2_dw_bytes(N, nxi == 0) / 16;
-    part_request<kTail2MaxDw16 / kTail2Threads>(a.cst + N.g_cst, lds + N.dw_off, nx_n16, tid);
+    if constexpr (!RES) {
+        const int nx_n16 = nxi < 0 ? 0 : tail2_dw_bytes(N, nxi == 0) / 16;
+        part_request<kTail2MaxDw16 / kTail2Threads>(a.cst + N.g_cst, lds + N.dw_off, nx_n16, tid);
+    }
 
     // ---- pointwise 1x1 on the matrix cores, requantise, [ADD], store into the map -------------------------------------------------
     const int add_m = L.add_m, add_e1 = L.add_e - 1;
@@ -420,13 +483,25 @@ __device__ __forceinline__ void tail2_block(const Tail2Layer& L, const Tail2Args
         __builtin_amdgcn_sched_barrier(0);
     }
     }  // pass
-    BN_T2STAMP(5);
-    if (nxi > 0 && tid < (N.Cin + 16) / 4) reinterpret_cast<int*>(lds + N.zp_off)[tid] = (N.zp_in & 0xff) * 0x01010101;   // (block 0 has no zero-point row)
-    __syncthreads();
+    BN_T2STAMP(2);
+    if constexpr (RES) {
+        (void)N;
+        // the chunk's pointwise results are in its map for the NEXT block's taps; behind the last block nobody reads another wave's results
+        // (mid2_main writes the map back wave by wave), so nobody waits
+        if (nxi > 0) chunk_barrier<WPC>(lds, a.bar_off, gch, seq);
+    } else {
+        if (nxi > 0 && tid < (N.Cin + 16) / 4) reinterpret_cast<int*>(lds + N.zp_off)[tid] = (N.zp_in & 0xff) * 0x01010101;   // (block 0 has no zero-point row)
+#ifdef BN_TAIL_STAMPS
+        if (a.bar_off >= 0) chunk_barrier<WPC>(lds, a.bar_off, gch, seq);
+        BN_T2STAMP(5);
+#endif
+        __syncthreads();
+    }
     BN_T2STAMP(6);
 #ifdef BN_TAIL_STAMPS
-    if (stamp_slot >= 0 && g_tail2_stamps && (threadIdx.x & 63) == 0) {
-        long long* o = g_tail2_stamps + ((size_t)stamp_slot * kTail2Waves + (threadIdx.x >> 6)) * 8;
+    long long* const sbuf = G == kMidG ? g_mid2_stamps : g_tail2_stamps;
+    if (stamp_slot >= 0 && sbuf && (threadIdx.x & 63) == 0) {
+        long long* o = sbuf + ((size_t)stamp_slot * kTail2Waves + (threadIdx.x >> 6)) * 8;
         for (int i = 0; i < 7; ++i) o[i] = st[i];
     }
 #endif
@@ -436,6 +511,10 @@ template <bool EMB>
 __device__ __forceinline__ void tail2_main(const Tail2Args& a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int ngroups = (a.B + kTailG - 1) / kTailG;
+    unsigned seq = 0;   // (chunk barriers exist in the stamped build only)
+#ifdef BN_TAIL_STAMPS
+    if (threadIdx.x < 4 && a.bar_off >= 0) reinterpret_cast<unsigned*>(lds + a.bar_off)[threadIdx.x] = 0;
+#endif
     {   // the first block's depthwise part, once; afterwards every block finds its own staged by its predecessor
         part_request<kTail2MaxDw16 / kTail2Threads>(a.cst + a.L[0].g_cst, lds + a.L[0].dw_off, tail2_dw_bytes(a.L[0], true) / 16, (int)threadIdx.x);
         __syncthreads();
@@ -454,10 +533,10 @@ __device__ __forceinline__ void tail2_main(const Tail2Args& a) {
             const int gi = (grp - (int)blockIdx.x) / (int)gridDim.x;
             if ((int)blockIdx.x < 8 && gi < 4 && li < 8 && g_tail2_stamps) slot = ((int)blockIdx.x * 4 + gi) * 8 + li;
 #endif
-            if (L.Cin == 64) tail2_block<kTailG, 64, 128, 2, 16, 32, false, true>(L, a, lds, chunk0, nx, slot);
-            else if (L.Cin == 128 && L.Cout == 128) tail2_block<kTailG, 128, 128, 1, 8, 16, true, false>(L, a, lds, chunk0, nx, slot);
-            else if (L.Cin == 128) tail2_block<kTailG, 128, 256, 2, 8, 16, false, false>(L, a, lds, chunk0, nx, slot);
-            else tail2_block<kTailG, 256, 256, 1, 4, 8, true, false>(L, a, lds, chunk0, nx, slot);
+            if (L.Cin == 64) tail2_block<kTailG, 64, 128, 2, 16, 32, false, true>(L, a, lds, chunk0, nx, seq, slot);
+            else if (L.Cin == 128 && L.Cout == 128) tail2_block<kTailG, 128, 128, 1, 8, 16, true, false>(L, a, lds, chunk0, nx, seq, slot);
+            else if (L.Cin == 128) tail2_block<kTailG, 128, 256, 2, 8, 16, false, false>(L, a, lds, chunk0, nx, seq, slot);
+            else tail2_block<kTailG, 256, 256, 1, 4, 8, true, false>(L, a, lds, chunk0, nx, seq, slot);
         }
         int hslot = -1;
 #ifdef BN_TAIL_STAMPS
@@ -478,10 +557,38 @@ __global__ __launch_bounds__(kTail2Threads) void i8_tail2_emb_kernel(WithEmb<Tai
 
 // Stage 2 of the shipped graph with the same blocks: kMidG = 2 chunks per workgroup (a 16 x 32 map of 64 channels is 40 KB in LDS), the first
 // block's taps from memory, the last map written back for the tail kernel (coalesced 16-byte pieces).
-__global__ __launch_bounds__(kTail2Threads) void i8_mid2_kernel(Tail2Args a) {
+//
+// Two forms.  RES (the plan of tail2_plan_resident, option i8_mid_split): the depthwise part, pointwise part and zero-point row of EVERY
+// block have LDS of their own beside the two maps (~130 KB of 160) and are staged ONCE, in front of the group loop.  Nothing but a chunk's
+// own map is overwritten afterwards, so no workgroup-wide order is left inside the loop: the WPC = 4 waves of a chunk slot synchronise
+// among themselves (chunk_barrier) and the two halves of the workgroup are independent streams over the same read-only constants — when
+// one half waits for its slowest wave, the other half's wave on the same SIMD keeps issuing.  A half takes chunk kMidG grp + slot
+// exactly as in the staged form, so every byte is the same.  Only a depthwise phase reads what ANOTHER wave stored (its taps), so only the
+// two residual blocks are fenced: a chunk barrier in front of each (the end barrier of the block before: the results are in the map) and one
+// behind its depthwise phase (the taps are read: the map may be overwritten) — four per group.  The first block reads its taps from
+// memory and overwrites positions whose last readers were the same wave (the last block's residual bytes, the write-back, which goes
+// wave by wave over the wave's own tiles): a wave's LDS operations complete in order, no barrier is needed there.
+// !RES: parts staged block by block into re-used LDS behind workgroup barriers (i8_tail2_kernel's way; the plan when the resident one
+// does not fit, and option i8_mid_split = 0).
+template <bool RES>
+__device__ __forceinline__ void mid2_main(const Tail2Args& a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int ngroups = (a.B + kMidG - 1) / kMidG;
-    part_request<kTail2MaxDw16 / kTail2Threads>(a.cst + a.L[0].g_cst, lds + a.L[0].dw_off, tail2_dw_bytes(a.L[0], true) / 16, (int)threadIdx.x);
+    unsigned seq = 0;
+    if (RES || kStamped) {
+        if (threadIdx.x < 4 && a.bar_off >= 0) reinterpret_cast<unsigned*>(lds + a.bar_off)[threadIdx.x] = 0;
+    }
+    if constexpr (RES) {
+        for (int li = 0; li < a.n_layers; ++li) {
+            const Tail2Layer& L = a.L[li];
+            const int dw16 = tail2_dw_bytes(L, li == 0) / 16;
+            part_request<kTail2MaxDw16 / kTail2Threads>(a.cst + L.g_cst, lds + L.dw_off, dw16, (int)threadIdx.x);
+            part_request<kTail2MaxDw16 / kTail2Threads>(a.cst + L.g_cst + 4 * dw16, lds + L.pw_off, tail2_pw_bytes(L) / 16, (int)threadIdx.x);
+            if (li > 0 && (int)threadIdx.x < (L.Cin + 16) / 4) reinterpret_cast<int*>(lds + L.zp_off)[threadIdx.x] = (L.zp_in & 0xff) * 0x01010101;
+        }
+    } else {
+        part_request<kTail2MaxDw16 / kTail2Threads>(a.cst + a.L[0].g_cst, lds + a.L[0].dw_off, tail2_dw_bytes(a.L[0], true) / 16, (int)threadIdx.x);
+    }
     __syncthreads();
     for (int grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
         const int chunk0 = grp * kMidG;
@@ -490,20 +597,47 @@ __global__ __launch_bounds__(kTail2Threads) void i8_mid2_kernel(Tail2Args a) {
             const Tail2Layer& L = a.L[li];
             const bool last = li == a.n_layers - 1;
             const int nx = last ? (more ? 0 : -1) : li + 1;
-            if (li == 0) tail2_block<kMidG, 32, 64, 2, 32, 64, false, true>(L, a, lds, chunk0, nx);
-            else tail2_block<kMidG, 64, 64, 1, 16, 32, true, false>(L, a, lds, chunk0, nx);
+            int slot = -1;
+#ifdef BN_TAIL_STAMPS
+            const int gi = (grp - (int)blockIdx.x) / (int)gridDim.x;
+            if ((int)blockIdx.x < 8 && gi < 4 && li < 8 && g_mid2_stamps) slot = ((int)blockIdx.x * 4 + gi) * 8 + li;
+#endif
+            if (li == 0) tail2_block<kMidG, 32, 64, 2, 32, 64, false, true, RES>(L, a, lds, chunk0, nx, seq, slot);
+            else tail2_block<kMidG, 64, 64, 1, 16, 32, true, false, RES>(L, a, lds, chunk0, nx, seq, slot);
         }
         // the last map: [chunk slot][position][C + 16] in LDS -> [chunk][position][C] in memory
         const Tail2Layer& L = a.L[a.n_layers - 1];
         const int c16 = L.Cout / 16, per = a.P * c16;
-        for (int i = threadIdx.x; i < kMidG * per; i += kTail2Threads) {
-            const int gq = i / per, r = i - gq * per, pos = r / c16, c = r - pos * c16;
-            if (chunk0 + gq < a.B)
-                reinterpret_cast<v4i*>(a.y + ((size_t)(chunk0 + gq) * a.P + pos) * L.Cout)[c] =
-                    *reinterpret_cast<const v4i*>(lds + L.y_off + (gq * a.P + pos) * (L.Cout + 16) + 16 * c);
+        if constexpr (RES) {
+            // a wave writes back the positions it stored itself (tail2_block's tile ownership on the 16 x 32 map of 64 channels, which
+            // tail2_plan_resident insists on: 8 rows of one 16-column strip; a row of a strip is 1 KB of consecutive memory, 16 bytes per lane)
+            constexpr int WPC = kTail2Waves / kMidG, OW = 32, C = 64;
+            const int lane = (int)threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+            const int gq = wave / WPC, wi = wave % WPC, cx0 = (wi % 2) * 16, oy0 = (wi / 2) * 8;
+            if (chunk0 + gq < a.B) {
+#pragma unroll
+                for (int r = 0; r < 8; ++r) {
+                    const int pos = (oy0 + r) * OW + cx0 + (lane >> 2);
+                    reinterpret_cast<v4i*>(a.y + ((size_t)(chunk0 + gq) * (16 * OW) + pos) * C)[lane & 3] =
+                        *reinterpret_cast<const v4i*>(lds + L.y_off + (gq * (16 * OW) + pos) * (C + 16) + 16 * (lane & 3));
+                }
+            }
+        } else {
+            for (int i = threadIdx.x; i < kMidG * per; i += kTail2Threads) {
+                const int gq = i / per, r = i - gq * per, pos = r / c16, c = r - pos * c16;
+                if (chunk0 + gq < a.B)
+                    reinterpret_cast<v4i*>(a.y + ((size_t)(chunk0 + gq) * a.P + pos) * L.Cout)[c] =
+                        *reinterpret_cast<const v4i*>(lds + L.y_off + (gq * a.P + pos) * (L.Cout + 16) + 16 * c);
+            }
+            __syncthreads();  // the next group overwrites the map
         }
-        __syncthreads();  // the next group overwrites the map
     }
+}
+
+// (one kernel, a workgroup-uniform choice of the form: the name the profiles and the benchmark key on stays whatever the option says)
+__global__ __launch_bounds__(kTail2Threads) void i8_mid2_kernel(Tail2Args a) {
+    if (a.resident) mid2_main<true>(a);
+    else mid2_main<false>(a);
 }
 
 int tail2_dw_part(const Tail2Layer& L, bool first) { return (L.Cin / 16) * (3 * 1024 + (first ? 8 : 5) * 64); }
@@ -527,6 +661,13 @@ int first_fit2(const std::vector<Span2>& used, int bytes, int cap) {
     return pos + bytes > cap ? -1 : pos;
 }
 bool overlap2(int b0, int e0, int b1, int e1) { return b0 < e1 && b1 < e0; }
+// the chunk barriers' counters (one dword per chunk slot) above everything else; the staged forms use them in the stamped measurement build
+// only, so a staged plan that fills the LDS to the last byte stays valid without them (bar_off = -1: that build then stamps no chunk barrier)
+void tail2_place_counters(Tail2Args& a, int cap) {
+    a.bar_off = (a.lds_bytes + 15) & ~15;
+    if (a.bar_off + 16 > cap) a.bar_off = -1;
+    else a.lds_bytes = a.bar_off + 16;
+}
 
 }  // namespace
 
@@ -537,7 +678,8 @@ bool overlap2(int b0, int e0, int b1, int e1) { return b0 < e1 && b1 < e0; }
 // the last block of the previous group and stays through the head: it avoids the last map, the last pointwise part, the pooled vector and
 // the head's copy of the classifier matrix.  false = not a topology / size the kernel takes (the plan keeps i8_tail_kernel).
 bool tail2_plan(const int32_t* desc, int n_words, int n_layers, Tail2Args& a, bool mid) {
-    constexpr int LW = kTail2LayerWords, CAP = 160 * 1024;
+    // (the stamped measurement build keeps the top 16 bytes free for the chunk barriers' counters: its staged plans get them too)
+    constexpr int LW = kTail2LayerWords, CAP = 160 * 1024 - (kStamped ? 16 : 0);
     const int HW = mid ? 0 : 16, G = mid ? kMidG : kTailG;
     if (n_layers < 1 || n_layers > 8 || n_words != LW * n_layers + HW) return false;
     a.n_layers = n_layers;
@@ -610,11 +752,14 @@ bool tail2_plan(const int32_t* desc, int n_words, int n_layers, Tail2Args& a, bo
     const Span2 dw0{a.L[0].dw_off, a.L[0].dw_off + tail2_dw_part(a.L[0], true)};
     const Span2 map_last{0, G * last.OH * last.OW * (last.Cout + 16)};
     if (overlap2(dw0.b, dw0.e, map_last.b, map_last.e) || overlap2(dw0.b, dw0.e, prev_pw.b, prev_pw.e)) return false;
+    a.resident = 0;
+    a.bar_off = -1;
     if (mid) {
         a.P = last.OH * last.OW;
         a.C = last.Cout;
         a.fcw_off = -1;
         a.lds_bytes = lds_need;
+        tail2_place_counters(a, 160 * 1024);
         return a.C % 16 == 0;
     }
     const int32_t* h = desc + LW * n_layers;
@@ -631,7 +776,49 @@ bool tail2_plan(const int32_t* desc, int n_words, int n_layers, Tail2Args& a, bo
     grow(a.mean_off + kTailG * last.Cout);
     a.fcw_off = -1;   // (the classifier's fragments come straight from memory)
     a.lds_bytes = lds_need;
+    tail2_place_counters(a, 160 * 1024);
     return true;
+}
+
+// The resident placement of a stage-2 plan (i8_mid2_kernel, option i8_mid_split): from a plan tail2_plan(..., mid = true) accepted, the same
+// blocks with LDS of its own for every block's depthwise part, pointwise part and zero-point row, laid out one behind the other above the
+// maps (the largest map of the chain times kMidG: input and output in place at offset 0), then the chunk barriers' counters.  Nothing
+// overlaps anything, so nothing is staged twice and nothing orders the two chunk slots.  false = it does not fit the 160 KB of a CU (or a
+// part is larger than the one-time staging copies): the caller keeps the staged plan and the kernel its staged form.
+bool tail2_plan_resident(Tail2Args& a) {
+    constexpr int CAP = 160 * 1024;
+    if (a.n_layers < 1 || a.n_layers > 8) return false;
+    int map_bytes = 0;
+    for (int i = 0; i < a.n_layers; ++i) {
+        const Tail2Layer& L = a.L[i];
+        const int in_bytes = i == 0 ? 0 : kMidG * L.H * L.W * (L.Cin + 16), out_bytes = kMidG * L.OH * L.OW * (L.Cout + 16);
+        map_bytes = std::max(map_bytes, std::max(in_bytes, out_bytes));
+    }
+    std::vector<Span2> used{{0, map_bytes}};
+    auto place = [&](int bytes) {
+        const int off = first_fit2(used, bytes, CAP);
+        if (off >= 0) used.push_back({off, off + bytes});
+        return off;
+    };
+    for (int i = 0; i < a.n_layers; ++i) {
+        Tail2Layer& L = a.L[i];
+        if (tail2_dw_part(L, i == 0) / 16 > kTail2MaxDw16 || tail2_pw_part(L) / 16 > kTail2MaxDw16) return false;
+        if ((L.dw_off = place(tail2_dw_part(L, i == 0))) < 0) return false;
+        if ((L.pw_off = place(tail2_pw_part(L))) < 0) return false;
+        L.zp_off = 0;
+        if (i > 0 && (L.zp_off = place(L.Cin + 16)) < 0) return false;
+    }
+    if ((a.bar_off = place(16)) < 0) return false;
+    for (size_t i = 0; i < used.size(); ++i)   // (first fit cannot produce an overlap; a cheap proof at load beats a wrong byte later)
+        for (size_t j = i + 1; j < used.size(); ++j)
+            if (overlap2(used[i].b, used[i].e, used[j].b, used[j].e)) return false;
+    const Tail2Layer& last = a.L[a.n_layers - 1];
+    if (last.OH != 16 || last.OW != 32 || last.Cout != 64 || a.P != 16 * 32 || a.C != 64) return false;   // (the wave-by-wave write-back's geometry)
+    int end = 0;
+    for (const Span2& u : used) end = std::max(end, u.e);
+    a.lds_bytes = end;
+    a.resident = 1;
+    return end <= CAP;
 }
 
 namespace {
@@ -642,7 +829,30 @@ int tail2_cst_bytes(const Tail2Layer& L, bool first) { return tail2_dw_part(L, f
 extern "C" __attribute__((visibility("default"))) int bn_debug_tail2_stamps(long long* d_buf) {
     return hipMemcpyToSymbol(HIP_SYMBOL(g_tail2_stamps), &d_buf, sizeof d_buf) == hipSuccess ? 0 : -1;
 }
+extern "C" __attribute__((visibility("default"))) int bn_debug_mid2_stamps(long long* d_buf) {
+    return hipMemcpyToSymbol(HIP_SYMBOL(g_mid2_stamps), &d_buf, sizeof d_buf) == hipSuccess ? 0 : -1;
+}
 #endif
+
+bool tail2_plan_dump(const Tail2Args& a, int* out, int n) {
+    if (n < 5 + 6 * a.n_layers) return false;
+    int map_bytes = 0;
+    for (int i = 0; i < a.n_layers; ++i) {
+        const Tail2Layer& L = a.L[i];
+        map_bytes = std::max(map_bytes, std::max(i == 0 ? 0 : kMidG * L.H * L.W * (L.Cin + 16), kMidG * L.OH * L.OW * (L.Cout + 16)));
+        int* o = out + 5 + 6 * i;
+        o[0] = L.dw_off; o[1] = tail2_dw_part(L, i == 0); o[2] = L.pw_off; o[3] = tail2_pw_part(L); o[4] = L.zp_off; o[5] = i == 0 ? 0 : L.Cin + 16;
+    }
+    out[0] = a.resident; out[1] = a.lds_bytes; out[2] = map_bytes; out[3] = a.bar_off; out[4] = a.n_layers;
+    return true;
+}
+
+// chunk barriers whose bounded spin ran out since the library was loaded (0 unless the kernel is broken: tests assert it); -1: the copy failed
+long tail2_giveups() {
+    unsigned n = 0;
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpyFromSymbol(&n, HIP_SYMBOL(g_tail2_giveups), sizeof n) != hipSuccess) return -1;
+    return (long)n;
+}
 
 long tail2_const_words(const Tail2Args& a, bool mid) {
     long need = 0;

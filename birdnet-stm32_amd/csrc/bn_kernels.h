@@ -47,6 +47,8 @@ struct Options {
     int i8_tail_mfdw = 1;      // ... with the depthwise stage on the matrix cores (i8_tail2_kernel) where the plan carries its constants; 0: i8_tail_kernel
     int i8_mel_generic = 0;    // run the mel mixer through the generic fused block
     int stft_rowmajor = 0;     // keep the reference spectrogram layout inside bn_infer_audio (default: tile-major)
+    int i8_mid_split = 1;      // i8_mid2_kernel with every block's constants resident in LDS (staged once) and barriers over the 4 waves of a chunk slot instead of the
+                               // workgroup: its two halves run as independent streams; 0 (or a plan whose resident placement does not fit): parts staged per block
     int i8_strip_mfdw = 1;     // stage1_ds2-shaped blocks (32 -> 32 channels, stride 1, residual ADD): depthwise 3x3 on the matrix cores (i8_strip_mf_kernel); 0: i8_strip_kernel
     int stft_exact = 2;        // INT8 plans from audio: 2 = float32 STFT + float64 pass over the doubtful elements (bit-exact input bytes,
                                // bn_stft_exact.hip; plans / options the guarded kernels do not cover take 1), 1 = every bin as a float64
@@ -444,8 +446,13 @@ struct Tail2Args {
     float s_fc, s_head;
     int lds_bytes;
     int fcw_off;
+    int bar_off;          // LDS byte offset of the chunk barriers' counters (one dword per chunk slot)
+    int resident;         // i8_mid2_kernel: every block's constants have LDS of their own (tail2_plan_resident) — staged once, chunk-local barriers
     Tail2Layer L[8];};
 bool tail2_plan(const int32_t* desc, int n_words, int n_layers, Tail2Args& a, bool mid = false);  // a.NC must be set (tail); mid: the stage-2 chain, no head
+bool tail2_plan_resident(Tail2Args& a);   // a stage-2 plan tail2_plan accepted -> its resident placement; false (a unspecified): it does not fit, keep the staged one
+bool tail2_plan_dump(const Tail2Args& a, int* out, int n);   // bn_debug_mid_plan (include/birdnet_hip.h has the layout)
+long tail2_giveups();                     // chunk barriers that gave up waiting (0 in a working build)
 long tail2_const_words(const Tail2Args& a, bool mid = false);
 bool launch_i8_tail2(Tail2Args a, hipStream_t s, const EmbOut* emb = nullptr);
 bool launch_i8_mid2(Tail2Args a, hipStream_t s);

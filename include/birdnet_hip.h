@@ -301,6 +301,14 @@ BN_API int bn_debug_tail_form(const bn_model* model, int* form, int* lds_bytes);
 /* Test hook: *form = 1 when the plan's fused stage-2 chain (BN_OP_I8_MID: three blocks of the shipped graph as i8_mid2_kernel; option i8_mid)
  * passed the library's LDS plan and runs by default, else 0 (its three strip kernels run instead). */
 BN_API int bn_debug_mid_form(const bn_model* model, int* form, int* lds_bytes);
+/* Test hook: the RESIDENT LDS placement of the fused stage-2 chain (option i8_mid_split: every block's constants staged once, barriers over the
+ * waves of one chunk only).  out[0] = 1 when the model has the chain and the placement fits (what i8_mid2_kernel then runs by default), else 0
+ * and nothing more is written; out[1] = LDS bytes, out[2] = bytes of the maps at offset 0, out[3] = offset of the barrier counters (16 bytes),
+ * out[4] = blocks; then per block: offset and bytes of its depthwise part, its pointwise part and its zero-point row (bytes 0: none).
+ * n >= 5 + 6 * blocks.  bn_debug_mid_split_giveups: *count = chunk barriers whose bounded wait ran out since the library was loaded (waits
+ * for the device; 0 in a working build). */
+BN_API int bn_debug_mid_plan(const bn_model* model, int* out, int n);
+BN_API int bn_debug_mid_split_giveups(bn_ctx* ctx, int64_t* count);
 
 BN_API int bn_debug_requant(bn_ctx* ctx, const int32_t* d_x, const int32_t* d_mult, const int32_t* d_shift, int n, int mode,
                      int zero_point, int32_t* d_out, void* stream);
@@ -319,7 +327,7 @@ BN_API int bn_profile_collect(bn_model* model, double* total_ms, int64_t* launch
 
 /* Run-time switches of the kernel launchers, for A/B measurements and tests (process-wide; the defaults are the production
  * choices).  Names: "f32_strip", "f32_strip_th", "f32_front_staged", "f32_front2", "f32_pwdw", "f32_tile_slice", "f32_pw_ws", "i8_pwdw", "i8_pw_lds", "i8_pw_forms", "i8_add_tab", "front_tpw", "wave_dwpw", "i8_strip", "i8_strip_mfdw", "i8_strip_th",
- * "i8_dw_pool", "i8_tail_fclds", "i8_tail", "i8_tail_mfdw", "i8_mid", "i8_mel_generic", "stft_rowmajor", "stft_exact", "stft_flagcap", "stft_guard", "stft_audit", "stft_minint", "ingest_blk", "ingest_generic" (csrc/bn_kernels.h: Options says
+ * "i8_dw_pool", "i8_tail_fclds", "i8_tail", "i8_tail_mfdw", "i8_mid", "i8_mid_split", "i8_mel_generic", "stft_rowmajor", "stft_exact", "stft_flagcap", "stft_guard", "stft_audit", "stft_minint", "ingest_blk", "ingest_generic" (csrc/bn_kernels.h: Options says
  * what each selects).  An environment variable BN_<NAME IN CAPITALS> seeds the value once when the library is loaded; no
  * launch reads the environment.  The reference has no counterpart (tf.lite.Interpreter's delegates / num_threads arguments,
  * birdnet_stm32/models/runners.py:57, are the closest thing).  Unknown name: BN_ERR_ARG. */

@@ -3,6 +3,11 @@
 
     make -C birdnet-stm32_amd/csrc stamps        # lib/libbirdnet_hip_stamps.so (-DBN_TAIL_STAMPS), in the build container
     python tools/tail2_stamps.py > profiles/r05_i8_tail2_attribution.md      # on the GPU box
+    python tools/tail2_stamps.py split > profiles/r06_mid2_tail2_barrier_split.md
+
+``split``: both fused kernels in their STAGED forms (``i8_mid_split`` = 0 for ``i8_mid2_kernel``); a wave's wait at the middle and at the end
+barrier of every block is divided into (a) until the last wave of its OWN chunk slot arrived and (b) from then until the last wave of the
+workgroup arrived.  The stamped build puts a chunk barrier in front of each workgroup barrier and stamps between the two.
 """
 import ctypes
 import os
@@ -31,6 +36,38 @@ torch.cuda.synchronize()
 WG, GRP, BLK, WAVES = 8, 4, 8, 8
 buf = torch.zeros(WG * GRP * BLK * WAVES * 8, dtype=torch.int64, device=dev)
 assert lib.bn_debug_tail2_stamps(buf.data_ptr()) == 0
+SPLIT = len(sys.argv) > 1 and sys.argv[1] == "split"
+if SPLIT:
+    lib.bn_debug_mid2_stamps.argtypes = [ctypes.c_void_p]
+    mbuf = torch.zeros(WG * GRP * BLK * WAVES * 8, dtype=torch.int64, device=dev)
+    assert lib.bn_debug_mid2_stamps(mbuf.data_ptr()) == 0
+    r.profile(True)
+    with _hip.options(i8_mid_split=0):
+        r.infer_audio_device(x, hop=bench.HOP, out=out)
+    torch.cuda.synchronize()
+    ms = {q["kind"]: q["ms"] for q in r.profile_collect() if q["launches"]}
+    print("# Barrier waits of `i8_mid2_kernel` and `i8_tail2_kernel`, staged forms: own chunk against the rest of the workgroup\n")
+    print(f"INT8 B = {B}, stamped build (`make stamps`, `tools/tail2_stamps.py split`), `i8_mid_split` = 0; launches: stage 2 {ms.get('i8_mid', 0):.3f} ms, tail {ms.get('i8_tail', 0):.3f} ms.")
+    print("Means over 8 workgroups x 4 chunk groups x 8 waves, microseconds per wave and block.  wait = arrival at the barrier -> behind it;")
+    print("(a) = arrival -> the last wave of the wave's own chunk slot has arrived; (b) = from then -> the last wave of the workgroup has arrived.\n")
+    for title, b_, nblk, wpc in (("i8_mid2_kernel (2 chunk slots x 4 waves)", mbuf, 3, 4), ("i8_tail2_kernel (4 chunk slots x 2 waves)", buf, 6, 2)):
+        t = b_.cpu().numpy().reshape(WG, GRP, BLK, WAVES, 8).astype(np.float64) * 0.01
+        print(f"## {title}\n")
+        print("| block | phase before (depthwise) | middle wait | (a) | (b) | phase before (pointwise) | end wait | (a) | (b) |")
+        print("|---|---|---|---|---|---|---|---|---|")
+        tot = np.zeros(8)
+        for li in range(nblk):
+            q = t[:, :, li]
+            row = np.array([(q[..., 1] - q[..., 0]).mean(), (q[..., 4] - q[..., 1]).mean(), (q[..., 3] - q[..., 1]).mean(), (q[..., 4] - q[..., 3]).mean(),
+                            (q[..., 2] - q[..., 4]).mean(), (q[..., 6] - q[..., 2]).mean(), (q[..., 5] - q[..., 2]).mean(), (q[..., 6] - q[..., 5]).mean()])
+            tot += row
+            print(f"| {li} | " + " | ".join(f"{v:.2f}" for v in row) + " |")
+        print("| all | " + " | ".join(f"{v:.2f}" for v in tot) + " |")
+        wait, a_, b__ = tot[1] + tot[5], tot[2] + tot[6], tot[3] + tot[7]
+        print(f"\nPer chunk group: busy {tot[0] + tot[4]:.2f} us, waiting at barriers {wait:.2f} us = (a) {a_:.2f} + (b) {b__:.2f}; "
+              f"(b) is {100 * b__ / max(wait, 1e-9):.0f} % of the wait.\n")
+    r.close()
+    sys.exit(0)
 r.profile(True)
 r.infer_audio_device(x, hop=bench.HOP, out=out)
 torch.cuda.synchronize()
