@@ -197,8 +197,8 @@ def lower_f32(spec: ns.NetSpec, keep_all: bool = False, fuse: bool = True) -> pk
             fbias = (ly.weights["fb_beta"].astype(np.float64) - ly.weights["fb_mean"].astype(np.float64) * g_).astype(np.float32)
             mag = pk.MAG_CODES[fa.get("mag_scale", "none")]
             v = pb.value(M * W * 4)
-            pb.op(pk.F32_RAWFE, val[ly.inputs[0]], v, p=[T, W, M, stride, pad_total // 2, mag],
-                  t=[pb.tensor(fb, np.float32), pb.tensor(fbias, np.float32), pb.tensor(mag_params(ly), np.float32)], name=ly.name,
+            pb.op(pk.F32_RAWFE, val[ly.inputs[0]], v, p=dict(T=T, W=W, M=M, stride=stride, pad_left=pad_total // 2, mag=mag),
+                  t=dict(fb=pb.tensor(fb, np.float32), bias=pb.tensor(fbias, np.float32), magp=pb.tensor(mag_params(ly), np.float32)), name=ly.name,
                   out_shape=(M, W, 1))
             val[ly.name], shape[ly.name] = v, (M, W, 1)
         elif k == ns.FRONTEND:
@@ -209,15 +209,15 @@ def lower_f32(spec: ns.NetSpec, keep_all: bool = False, fuse: bool = True) -> pk
             mag, norm = pk.MAG_CODES[fa.get("mag_scale", "none")], int(bool(fa.get("norm", False)))
             v = pb.value(M * W * 4)
             both = pk.PATH_BOTH if not fuse else pk.PATH_INPUT
-            pb.op(pk.F32_MEL, val[ly.inputs[0]], v, p=[F, W, M, mag, norm], t=[t_w, t_b, t_m],
+            pb.op(pk.F32_MEL, val[ly.inputs[0]], v, p=dict(F=F, W=W, M=M, mag=mag, norm=norm), t=dict(wvals=t_w, bands=t_b, magp=t_m),
                   name=ly.name if not norm else ly.name + ":mel", out_shape=(M, W, 1), path=both)
             if norm:
-                pb.op(pk.F32_MAG, v, v, p=[M, W, mag], t=[-1, -1, t_m], name=ly.name, out_shape=(M, W, 1), path=both)
+                pb.op(pk.F32_MAG, v, v, p=dict(M=M, W=W, mag=mag), t=dict(magp=t_m), name=ly.name, out_shape=(M, W, 1), path=both)
             if fuse and F == 257:
                 # audio entry point: STFT with the mixer fused (no spectrogram in HBM), then normalise + scale
                 wsum = ly.weights["mel"][:F].astype(np.float64).sum(axis=0).astype(np.float32)
                 raw = pb.value(M * W * 4)
-                pb.op(pk.F32_STFTMEL, pk.SLOT_AUDIO, raw, p=[0, W, M], t=[t_w, t_b], name=ly.name + ":melraw", out_shape=(M, W, 1),
+                pb.op(pk.F32_STFTMEL, pk.SLOT_AUDIO, raw, p=dict(T=0, W=W, M=M), t=dict(wvals=t_w, bands=t_b), name=ly.name + ":melraw", out_shape=(M, W, 1),
                       path=pk.PATH_AUDIO)
                 t_ws = pb.tensor(wsum, np.float32)
                 nxt_i = only_consumer(ly.name)
@@ -226,7 +226,7 @@ def lower_f32(spec: ns.NetSpec, keep_all: bool = False, fuse: bool = True) -> pk
                 if front_next:
                     audio_raw[ly.name] = {"value": raw, "wsum": t_ws, "magp": t_m, "mag": mag}  # the front block finalises while loading
                 else:
-                    pb.op(pk.F32_MELFIN, raw, v, p=[M, W, mag, norm], t=[t_ws, -1, t_m], name=ly.name, out_shape=(M, W, 1), path=pk.PATH_AUDIO)
+                    pb.op(pk.F32_MELFIN, raw, v, p=dict(M=M, W=W, mag=mag, norm=norm), t=dict(wsum=t_ws, magp=t_m), name=ly.name, out_shape=(M, W, 1), path=pk.PATH_AUDIO)
             val[ly.name], shape[ly.name] = v, (M, W, 1)
         elif k in (ns.CONV, ns.DWCONV):
             src = ly.inputs[0]
@@ -236,6 +236,7 @@ def lower_f32(spec: ns.NetSpec, keep_all: bool = False, fuse: bool = True) -> pk
             bn, res, act, last = chain_after(i, ly.name)
             OH, pt, _ = ns.same_pad(H, kh, sh)
             OW, pl, _ = ns.same_pad(Wd, kw, sw)
+            geom = dict(H=H, W=Wd, sh=sh, sw=sw, OH=OH, OW=OW, pt=pt, pl=pl)
             if k == ns.DWCONV:
                 if (kh, kw) != (3, 3) or res is not None:
                     raise NotImplementedError(f"{ly.name}: only 3x3 depthwise convolutions without residual")
@@ -254,17 +255,18 @@ def lower_f32(spec: ns.NetSpec, keep_all: bool = False, fuse: bool = True) -> pk
                     w2, b2 = fold_bn(nxt.weights["kernel"], bn2)
                     Cout = w2.shape[-1]
                     v = pb.value(OH * OW * Cout * 4)
-                    p = [H, Wd, C, sh, sw, pk.ACT_CODES[act], OH, OW, pt, pl, Cout, pk.ACT_CODES[act2], int(res2 is not None), 0, 0, 1, *tile]
+                    p = dict(geom, Cin=C, dw_act=pk.ACT_CODES[act], Cout=Cout, pw_act=pk.ACT_CODES[act2], has_res=int(res2 is not None), has_dw=1,
+                             TH=tile[0], TW=tile[1], NB=tile[2])
                     pb.op(pk.F32_DWPW, val[src], v, p=p,
-                          t=[pb.tensor(w, np.float32), pb.tensor(b, np.float32), pb.tensor(pack_pw_fragments(w2[0, 0]), np.float32),
-                             pb.tensor(b2, np.float32)],
+                          t=dict(dw_w=pb.tensor(w, np.float32), dw_b=pb.tensor(b, np.float32), pw_w=pb.tensor(pack_pw_fragments(w2[0, 0]), np.float32),
+                                 pw_b=pb.tensor(b2, np.float32)),
                           in1=val[res2] if res2 is not None else pk.SLOT_NONE, name=last2, out_shape=(OH, OW, Cout))
                     out_shape = (OH, OW, Cout)
                     last = last2
                 else:
                     v = pb.value(OH * OW * C * 4)
-                    pb.op(pk.F32_DW, val[src], v, p=[H, Wd, C, sh, sw, pk.ACT_CODES[act], OH, OW, pt, pl],
-                          t=[pb.tensor(w, np.float32), pb.tensor(b, np.float32)], name=last, out_shape=(OH, OW, C))
+                    pb.op(pk.F32_DW, val[src], v, p=dict(geom, C=C, act=pk.ACT_CODES[act]),
+                          t=dict(w=pb.tensor(w, np.float32), bias=pb.tensor(b, np.float32)), name=last, out_shape=(OH, OW, C))
                     out_shape = (OH, OW, C)
             elif (kh, kw) == (3, 3):
                 if Cin != 1 or res is not None:
@@ -291,28 +293,28 @@ def lower_f32(spec: ns.NetSpec, keep_all: bool = False, fuse: bool = True) -> pk
                     wp_, bp = fold_bn(pwl.weights["kernel"], bn_p)
                     N = wp_.shape[-1]
                     v = pb.value(BH * BW * N * 4)
-                    tens = [pb.tensor(w[:, :, 0, :], np.float32), pb.tensor(b, np.float32), pb.tensor(wd, np.float32), pb.tensor(bd, np.float32),
-                            pb.tensor(pack_pw_fragments(wp_[0, 0]), np.float32), pb.tensor(bp, np.float32)]
-                    base_p = [H, Wd, Cout, N, BH, BW, pk.ACT_CODES[act], pk.ACT_CODES[act_d], pk.ACT_CODES[act_p]]
+                    tens = dict(stem_w=pb.tensor(w[:, :, 0, :], np.float32), stem_b=pb.tensor(b, np.float32), dw_w=pb.tensor(wd, np.float32),
+                                dw_b=pb.tensor(bd, np.float32), pw_w=pb.tensor(pack_pw_fragments(wp_[0, 0]), np.float32), pw_b=pb.tensor(bp, np.float32))
+                    base_p = dict(H0=H, W0=Wd, C=Cout, N=N, OH=BH, OW=BW, stem_act=pk.ACT_CODES[act], dw_act=pk.ACT_CODES[act_d], pw_act=pk.ACT_CODES[act_p])
                     raw = audio_raw.get(src)
                     if raw is not None:
                         # audio entry point: read the un-normalised mel energies and finalise them while loading the patch
-                        pb.op(pk.F32_FRONT, val[src], v, p=base_p + [0, 0], t=tens, name=last_p, out_shape=(BH, BW, N), path=pk.PATH_INPUT)
-                        pb.op(pk.F32_FRONT, raw["value"], v, p=base_p + [1, raw["mag"]], t=tens + [raw["wsum"], raw["magp"]], name=last_p,
+                        pb.op(pk.F32_FRONT, val[src], v, p=base_p, t=tens, name=last_p, out_shape=(BH, BW, N), path=pk.PATH_INPUT)
+                        pb.op(pk.F32_FRONT, raw["value"], v, p=dict(base_p, raw_mel=1, mag=raw["mag"]), t=dict(tens, wsum=raw["wsum"], magp=raw["magp"]), name=last_p,
                               out_shape=(BH, BW, N), path=pk.PATH_AUDIO)
                     else:
-                        pb.op(pk.F32_FRONT, val[src], v, p=base_p + [0, 0], t=tens, name=last_p, out_shape=(BH, BW, N))
+                        pb.op(pk.F32_FRONT, val[src], v, p=base_p, t=tens, name=last_p, out_shape=(BH, BW, N))
                     out_shape = (BH, BW, N)
                     last = last_p
                 else:
                     raw = audio_raw.pop(src, None)
                     if raw is not None:  # no front block after all: finalise the mel energies in their own pass
                         Ms, Ws, _ = shape[src]
-                        pb.op(pk.F32_MELFIN, raw["value"], val[src], p=[Ms, Ws, raw["mag"], 0], t=[raw["wsum"], -1, raw["magp"]], name=src,
+                        pb.op(pk.F32_MELFIN, raw["value"], val[src], p=dict(M=Ms, W=Ws, mag=raw["mag"], norm=0), t=dict(wsum=raw["wsum"], magp=raw["magp"]), name=src,
                               out_shape=(Ms, Ws, 1), path=pk.PATH_AUDIO)
                     v = pb.value(OH * OW * Cout * 4)
-                    pb.op(pk.F32_STEM, val[src], v, p=[H, Wd, Cout, sh, sw, pk.ACT_CODES[act], OH, OW, pt, pl],
-                          t=[pb.tensor(w[:, :, 0, :], np.float32), pb.tensor(b, np.float32)], name=last, out_shape=(OH, OW, Cout))
+                    pb.op(pk.F32_STEM, val[src], v, p=dict(geom, Cout=Cout, act=pk.ACT_CODES[act]),
+                          t=dict(w=pb.tensor(w[:, :, 0, :], np.float32), bias=pb.tensor(b, np.float32)), name=last, out_shape=(OH, OW, Cout))
                     out_shape = (OH, OW, Cout)
             elif (kh, kw) == (1, 1) and (sh, sw) == (1, 1):
                 w, b = fold_bn(ly.weights["kernel"], bn)  # [1,1,Cin,Cout]
@@ -325,18 +327,19 @@ def lower_f32(spec: ns.NetSpec, keep_all: bool = False, fuse: bool = True) -> pk
                 v = pb.value(P * Cout * 4)
                 tile = pick_tile(H, Wd)
                 if fuse and tile is not None and Cin % 4 == 0 and Cout % 16 == 0:
-                    p = [H, Wd, Cin, 1, 1, 0, H, Wd, 0, 0, Cout, pk.ACT_CODES[act], int(res is not None), int(gate_val is not None),
-                         gate_val if gate_val is not None else 0, 0, *tile]
+                    p = dict(H=H, W=Wd, Cin=Cin, sh=1, sw=1, OH=H, OW=Wd, Cout=Cout, pw_act=pk.ACT_CODES[act], has_res=int(res is not None),
+                             has_gate=int(gate_val is not None), gate_slot=gate_val if gate_val is not None else 0, TH=tile[0], TW=tile[1], NB=tile[2])
                     zero = pb.tensor(np.zeros(4, np.float32), np.float32)
-                    pb.op(pk.F32_DWPW, x_val, v, p=p, t=[zero, zero, pb.tensor(pack_pw_fragments(w[0, 0]), np.float32), pb.tensor(b, np.float32)],
+                    pb.op(pk.F32_DWPW, x_val, v, p=p,
+                          t=dict(dw_w=zero, dw_b=zero, pw_w=pb.tensor(pack_pw_fragments(w[0, 0]), np.float32), pw_b=pb.tensor(b, np.float32)),
                           in1=val[res] if res is not None else pk.SLOT_NONE, name=last, out_shape=(H, Wd, Cout),
-                          value_params=(14,) if gate_val is not None else ())
+                          value_params=("gate_slot",) if gate_val is not None else ())
                 else:
-                    p = [P, Cin, Cout, pk.ACT_CODES[act], int(res is not None), int(gate_val is not None),
-                         gate_val if gate_val is not None else 0]
-                    pb.op(pk.F32_PW, x_val, v, p=p, t=[pb.tensor(w[0, 0], np.float32), pb.tensor(b, np.float32)],
+                    p = dict(P=P, Cin=Cin, Cout=Cout, act=pk.ACT_CODES[act], has_res=int(res is not None), has_gate=int(gate_val is not None),
+                             gate_slot=gate_val if gate_val is not None else 0)
+                    pb.op(pk.F32_PW, x_val, v, p=p, t=dict(w=pb.tensor(w[0, 0], np.float32), bias=pb.tensor(b, np.float32)),
                           in1=val[res] if res is not None else pk.SLOT_NONE, name=last, out_shape=(H, Wd, Cout),
-                          value_params=(6,) if gate_val is not None else ())
+                          value_params=("gate_slot",) if gate_val is not None else ())
                 out_shape = (H, Wd, Cout)
             else:
                 raise NotImplementedError(f"{ly.name}: kernel {kh}x{kw} stride {sh}x{sw}")
@@ -363,8 +366,8 @@ def lower_f32(spec: ns.NetSpec, keep_all: bool = False, fuse: bool = True) -> pk
             H, Wd, C = shape[x]
             Cr = int(d1.attrs["units"])
             g = pb.value(C * 4)
-            pb.op(pk.F32_SEGATE, val[x], g, p=[H * Wd, C, Cr],
-                  t=[pb.tensor(d1.weights["kernel"], np.float32), pb.tensor(d2.weights["kernel"], np.float32)],
+            pb.op(pk.F32_SEGATE, val[x], g, p=dict(P=H * Wd, C=C, Cr=Cr),
+                  t=dict(w1=pb.tensor(d1.weights["kernel"], np.float32), w2=pb.tensor(d2.weights["kernel"], np.float32)),
                   name=d2.name, out_shape=(C,))
             done.update({index_of[d1.name], index_of[d2.name], mul_i})
             nxt = only_consumer(mul.name)
@@ -373,7 +376,7 @@ def lower_f32(spec: ns.NetSpec, keep_all: bool = False, fuse: bool = True) -> pk
                 shape[mul.name] = shape[x]
             else:
                 v = pb.value(H * Wd * C * 4)
-                pb.op(pk.F32_SCALE, val[x], v, p=[H * Wd, C], in1=g, name=mul.name, out_shape=(H, Wd, C))
+                pb.op(pk.F32_SCALE, val[x], v, p=dict(P=H * Wd, C=C), in1=g, name=mul.name, out_shape=(H, Wd, C))
                 val[mul.name], shape[mul.name] = v, shape[x]
         elif k == ns.GAP and fuse and _gap_dense_tail(layers, i, only_consumer) is not None:
             head_i = _gap_dense_tail(layers, i, only_consumer)
@@ -382,19 +385,19 @@ def lower_f32(spec: ns.NetSpec, keep_all: bool = False, fuse: bool = True) -> pk
             cout = int(head.attrs["units"])
             act = {"linear": 0, "sigmoid": 1, "softmax": 2}[head.attrs.get("activation", "linear")]
             bias = head.weights.get("bias", np.zeros(cout, np.float32))
-            o = pb.op(pk.F32_GAPDENSE, val[ly.inputs[0]], pk.SLOT_SCORES, p=[H * Wd, C, cout, act],
-                      t=[pb.tensor(head.weights["kernel"], np.float32), pb.tensor(bias, np.float32)], name=head.name, out_shape=(cout,))
+            o = pb.op(pk.F32_GAPDENSE, val[ly.inputs[0]], pk.SLOT_SCORES, p=dict(P=H * Wd, Cin=C, Cout=cout, act=act),
+                      t=dict(w=pb.tensor(head.weights["kernel"], np.float32), bias=pb.tensor(bias, np.float32)), name=head.name, out_shape=(cout,))
             pk.mark_embedding(o, C)  # the kernel pools the embedding on chip
             done.update(range(i + 1, head_i + 1))
         elif k == ns.GAP:
             H, Wd, C = shape[ly.inputs[0]]
             v = pb.value(C * 4)
-            pb.op(pk.F32_GAP, val[ly.inputs[0]], v, p=[H * Wd, C], name=ly.name, out_shape=(C,))
+            pb.op(pk.F32_GAP, val[ly.inputs[0]], v, p=dict(P=H * Wd, C=C), name=ly.name, out_shape=(C,))
             val[ly.name], shape[ly.name] = v, (C,)
         elif k == ns.ATTNPOOL:
             H, Wd, C = shape[ly.inputs[0]]
             v = pb.value(C * 4)
-            pb.op(pk.F32_ATTNPOOL, val[ly.inputs[0]], v, p=[H * Wd, C], t=[pb.tensor(ly.weights["score"], np.float32)],
+            pb.op(pk.F32_ATTNPOOL, val[ly.inputs[0]], v, p=dict(P=H * Wd, C=C), t=dict(score=pb.tensor(ly.weights["score"], np.float32)),
                   name=ly.name, out_shape=(C,))
             val[ly.name], shape[ly.name] = v, (C,)
         elif k == ns.IDENTITY:
@@ -409,8 +412,8 @@ def lower_f32(spec: ns.NetSpec, keep_all: bool = False, fuse: bool = True) -> pk
             cout = int(ly.attrs["units"])
             act = {"linear": 0, "sigmoid": 1, "softmax": 2}[ly.attrs.get("activation", "linear")]
             bias = ly.weights.get("bias", np.zeros(cout, np.float32))
-            pb.op(pk.F32_DENSE, val[ly.inputs[0]], pk.SLOT_SCORES, p=[cin, cout, act],
-                  t=[pb.tensor(ly.weights["kernel"], np.float32), pb.tensor(bias, np.float32)], name=ly.name, out_shape=(cout,))
+            pb.op(pk.F32_DENSE, val[ly.inputs[0]], pk.SLOT_SCORES, p=dict(Cin=cin, Cout=cout, act=act),
+                  t=dict(w=pb.tensor(ly.weights["kernel"], np.float32), bias=pb.tensor(bias, np.float32)), name=ly.name, out_shape=(cout,))
         else:
             raise NotImplementedError(f"layer {ly.name} of kind {k} cannot be lowered on its own")
     if fuse and not keep_all:
@@ -427,14 +430,14 @@ def _tag_pwdw(pb: pk.PlanBuilder) -> None:
     gate_slots = {ops[oi].p[pi] for oi, pi in pb._gate_refs}
     for i in range(len(ops) - 1):
         e, d = ops[i], ops[i + 1]
-        if not (e.kind == pk.F32_DWPW and e.p[15] == 0 and e.p[12] == 0 and e.p[13] == 0 and d.kind == pk.F32_DW and d.in0 == e.out and e.out >= 0):
+        if not (e.kind == pk.F32_DWPW and not e.get("has_dw") and not e.get("has_res") and not e.get("has_gate") and d.kind == pk.F32_DW and d.in0 == e.out and e.out >= 0):
             continue
         if e.p[pk.TAIL_TAG] or d.p[pk.TAIL_TAG] or e.p[pk.OP_PATH] != d.p[pk.OP_PATH]:
             continue
         v = e.out
         readers = [k for k, r in enumerate(ops) if k != i + 1 and (r.in0 == v or r.in1 == v)]
         writers = [k for k, r in enumerate(ops) if r.out == v]
-        if readers or writers != [i] or v in gate_slots or d.p[2] != e.p[10] or (d.p[0], d.p[1]) != (e.p[6], e.p[7]):
+        if readers or writers != [i] or v in gate_slots or d.get("C") != e.get("Cout") or (d.get("H"), d.get("W")) != (e.get("OH"), e.get("OW")):
             continue
         e.p[pk.TAIL_TAG] = pk.PWDW_HEAD
         d.p[pk.TAIL_TAG] = pk.PWDW_COVERED
@@ -445,7 +448,7 @@ def _tag_pwdw(pb: pk.PlanBuilder) -> None:
             st = ops[i - 1]
             others = [k for k, r in enumerate(ops) if k != i and (r.in0 == e.in0 or r.in1 == e.in0)]
             if not others and [k for k, r in enumerate(ops) if r.out == e.in0] == [i - 1] and e.in0 not in gate_slots \
-                    and (st.p[6], st.p[7], st.p[2]) == (e.p[0], e.p[1], e.p[2]) and st.p[pk.OP_PATH] == e.p[pk.OP_PATH]:
+                    and (st.get("OH"), st.get("OW"), st.get("Cout")) == (e.get("H"), e.get("W"), e.get("Cin")) and st.p[pk.OP_PATH] == e.p[pk.OP_PATH]:
                 st.p[pk.TAIL_TAG] = pk.PWDW_STEM
                 if st.in0 >= 0:
                     pb._extra_uses.append((i + 1, st.in0))
@@ -461,9 +464,8 @@ def _tag_front2(pb: pk.PlanBuilder) -> None:
     ops = pb.plan.ops
     gate_slots = {ops[oi].p[pi] for oi, pi in pb._gate_refs}
     for i, o in enumerate(ops):
-        q = o.p
-        if not (o.kind == pk.F32_DWPW and q[15] == 1 and q[2] == 32 and q[10] == 32 and q[3] == 1 and q[4] == 1 and q[12] == 1
-                and q[13] == 0 and o.in0 == o.in1 and o.in0 >= 0):
+        if not (o.kind == pk.F32_DWPW and [o.get(k) for k in ("has_dw", "Cin", "Cout", "sh", "sw", "has_res", "has_gate")] == [1, 32, 32, 1, 1, 1, 0]
+                and o.in0 == o.in1 and o.in0 >= 0):
             continue
         v = o.in0
         fronts = [j for j in range(i) if ops[j].kind == pk.F32_FRONT and ops[j].out == v]
@@ -471,12 +473,12 @@ def _tag_front2(pb: pk.PlanBuilder) -> None:
         writers = [k for k, r in enumerate(ops) if r.out == v]
         if not fronts or readers or writers != fronts or v in gate_slots:
             continue
-        if any(ops[j].p[2] != 16 or ops[j].p[3] != 32 or ops[j].p[4] != q[0] or ops[j].p[5] != q[1] or q[1] % 16 or q[1] // 16 > 4
-               or i - j >= 8 for j in fronts):
+        if any((ops[j].get("C"), ops[j].get("N"), ops[j].get("OH"), ops[j].get("OW")) != (16, 32, o.get("H"), o.get("W")) or o.get("W") % 16
+               or o.get("W") // 16 > 4 or i - j >= 8 for j in fronts):
             continue
         for j in fronts:
             ops[j].p[pk.TAIL_TAG] = pk.FRONT2_HEAD
             ops[j].p[pk.FRONT2_DIST] = i - j
             if ops[j].in0 >= 0:  # the fused kernel reads the front block's input while it writes this block's output: no slot sharing
                 pb._extra_uses.append((i, ops[j].in0))
-        q[pk.TAIL_TAG] = pk.FRONT2_COVERED
+        o.p[pk.TAIL_TAG] = pk.FRONT2_COVERED

@@ -671,11 +671,12 @@ def lower_i8(model, keep_all: bool = False, fuse: bool = True, softmax_form: str
         F = 0
         plan = pk.Plan(pk.DTYPE_I8, pk.INPUT_WAVEFORM, T, 0, W, int(t[model.outputs[0]].shape[-1]), meta={"tflite_ops": len(ops)})
         pb = pk.PlanBuilder(plan)
-        tt = [pb.tensor(w_fb, np.int8), pb.tensor(bias, np.int32), pb.tensor(mult, np.int32), pb.tensor(shift, np.int32)]
+        tt = dict(w=pb.tensor(w_fb, np.int8), bias=pb.tensor(bias, np.int32), mult=pb.tensor(mult, np.int32), shift=pb.tensor(shift, np.int32))
         if lut is not None:
-            tt.append(pb.tensor(lut, np.int8))
+            tt["lut"] = pb.tensor(lut, np.int8)
         v = pb.value(M * W)
-        pb.op(pk.I8_RAWFE, pk.SLOT_INPUT, v, p=[T, W, M, stride, pad_left, q_zp, z_fb, lo, hi, int(lut is not None)], t=tt, f=[q_scale], name=f"t{cur}",
+        pb.op(pk.I8_RAWFE, pk.SLOT_INPUT, v, p=dict(T=T, W=W, M=M, stride=stride, pad_left=pad_left, q_zp=q_zp, zp_out=z_fb, act_min=lo, act_max=hi,
+                                                    has_lut=int(lut is not None)), t=tt, f=dict(q_scale=q_scale), name=f"t{cur}",
               out_shape=(M, W, 1), out_dtype="int8")
     else:
         _expect(len(in_shape) == 4 and in_shape[3] == 1, "input must be [B, F, W, 1]")
@@ -773,12 +774,12 @@ def lower_i8(model, keep_all: bool = False, fuse: bool = True, softmax_form: str
 
         plan = pk.Plan(pk.DTYPE_I8, pk.INPUT_SPECTROGRAM, F * W, F, W, int(t[model.outputs[0]].shape[-1]), meta={"tflite_ops": len(ops)})
         pb = pk.PlanBuilder(plan)
-        tens = [pb.tensor(w_mel, np.int8), pb.tensor(bias, np.int32), pb.tensor(mult, np.int32), pb.tensor(shift, np.int32)]
+        tens = dict(w=pb.tensor(w_mel, np.int8), bias=pb.tensor(bias, np.int32), mult=pb.tensor(mult, np.int32), shift=pb.tensor(shift, np.int32))
         norm_lut = lut if maxnorm is not None else None  # with the max normalisation the per-channel table sits behind the DIV, not behind the mixer
         if maxnorm is not None:
             lut = None
         if lut is not None:
-            tens.append(pb.tensor(lut, np.int8))
+            tens["lut"] = pb.tensor(lut, np.int8)
         mel_tile = pick_tile(1, W)
         mfma_mel = fuse and mel_tile is not None and M % 16 == 0
         # production plans quantise inside the mel mixer's load (i8_mel_mfma_kernel<QIN>: one pass over the float32 spectrogram, no int8
@@ -787,26 +788,29 @@ def lower_i8(model, keep_all: bool = False, fuse: bool = True, softmax_form: str
         v_q = pk.SLOT_INPUT
         if not quant_in_mel:
             v_q = pb.value(W * Kp)
-            pb.op(pk.I8_QUANT, pk.SLOT_INPUT, v_q, p=[F, W, Kp, q_zp, fill_value], f=[q_scale], name=f"t{mel.inputs[0]}",
+            pb.op(pk.I8_QUANT, pk.SLOT_INPUT, v_q, p=dict(F=F, W=W, Kp=Kp, zp=q_zp, fill=fill_value), f=dict(scale=q_scale), name=f"t{mel.inputs[0]}",
                   out_shape=(W, Kp), out_dtype="int8")
         v = pb.value(M * W)
         if mfma_mel:
             zero = pb.tensor(np.zeros(4, np.int32), np.int32)
-            p = [1, W, Kp, 1, 1, F if quant_in_mel else 0, 1, W, 0, 0, 0, 0, 0, 0, M, z_mel, lo, hi, *([0] * 11), 0, 1, *mel_tile, int(lut is not None),
-                 0, int(quant_in_mel), q_zp, fill_value]
-            tt = [zero, zero, zero, zero, pb.tensor(pack_i8_fragments(w_mel), np.int8), tens[1], tens[2], tens[3]]
+            p = dict(H=1, W=W, Cin=Kp, sh=1, sw=1, qF=F if quant_in_mel else 0, OH=1, OW=W, Cout=M, pw_zp_out=z_mel, pw_amin=lo, pw_amax=hi, transposed=1,
+                     TH=mel_tile[0], TW=mel_tile[1], NB=mel_tile[2], has_lut=int(lut is not None), q_at_load=int(quant_in_mel), qzp=q_zp, qfill=fill_value)
+            tt = dict(dw_w=zero, dw_b=zero, dw_mult=zero, dw_shift=zero, pw_w=pb.tensor(pack_i8_fragments(w_mel), np.int8), pw_b=tens["bias"],
+                      pw_mult=tens["mult"], pw_shift=tens["shift"])
             if lut is not None:
-                tt.append(tens[4])
-            pb.op(pk.I8_DWPW, v_q, v, p=p, t=tt, f=[q_scale], name=f"t{cur}", out_shape=(M, W, 1), out_dtype="int8")
+                tt["lut"] = tens["lut"]
+            pb.op(pk.I8_DWPW, v_q, v, p=p, t=tt, f=dict(qscale=q_scale), name=f"t{cur}", out_shape=(M, W, 1), out_dtype="int8")
         else:
-            pb.op(pk.I8_MEL, v_q, v, p=[W, Kp, M, z_mel, lo, hi, int(lut is not None)], t=tens, name=f"t{cur}",
+            pb.op(pk.I8_MEL, v_q, v, p=dict(W=W, Kp=Kp, M=M, zp_out=z_mel, act_min=lo, act_max=hi, has_lut=int(lut is not None)), t=tens, name=f"t{cur}",
                   out_shape=(M, W, 1), out_dtype="int8")
         if maxnorm is not None:
             _expect(W % 4 == 0, "max normalisation kernel: map width must be a multiple of 4")
             pb.plan.ops[-1].name = "mel_mixer"  # (its [W][M] graph tensor is not compared by name: the plan keeps [M][W])
             v_n = pb.value(M * W)
-            tt = [pb.tensor(maxnorm[0], np.int8), pb.tensor(maxnorm[1], np.int8)] + ([pb.tensor(norm_lut, np.int8)] if norm_lut is not None else [])
-            pb.op(pk.I8_MAXNORM, v, v_n, p=[M, W, int(norm_lut is not None)], t=tt, name=f"t{cur}", out_shape=(M, W, 1), out_dtype="int8")
+            tt = dict(denom=pb.tensor(maxnorm[0], np.int8), div=pb.tensor(maxnorm[1], np.int8))
+            if norm_lut is not None:
+                tt["lut"] = pb.tensor(norm_lut, np.int8)
+            pb.op(pk.I8_MAXNORM, v, v_n, p=dict(C=M, W=W, has_lut=int(norm_lut is not None)), t=tt, name=f"t{cur}", out_shape=(M, W, 1), out_dtype="int8")
             v = v_n
     val = {cur: v}
     shape = {cur: (M, W, 1)}
@@ -859,18 +863,19 @@ def lower_i8(model, keep_all: bool = False, fuse: bool = True, softmax_form: str
                     # (the strip kernels drop the sign term of the rounding shift where a negative result clamps to the zero point anyway)
                     relu_ok = a_lo >= z_o and dlo >= zdo and plo >= zpo
                     cst = front_strip_constants(w, b, mu, sh, z_i, z_o, wtd.data[0], bd, mud, shd, zdo, wpw, bp, mup, shp, zpo) if BW % 16 == 0 and relu_ok else None
-                    pb.op(pk.I8_FRONT, val[src], v, p=[H, Wd, Cout, N, BH, BW, z_i, z_o, a_lo, a_hi, zdo, dlo, dhi, zpo, plo, phi, int(cst is not None)],
-                          t=[pb.tensor(w, np.int8), pb.tensor(b, np.int32), pb.tensor(mu, np.int32), pb.tensor(sh, np.int32),
-                             pb.tensor(wtd.data[0], np.int8), pb.tensor(bd, np.int32), pb.tensor(mud, np.int32), pb.tensor(shd, np.int32),
-                             pb.tensor(pack_i8_fragments(wpw), np.int8), pb.tensor(bp, np.int32), pb.tensor(mup, np.int32), pb.tensor(shp, np.int32),
-                             pb.tensor(cst, np.int32) if cst is not None else -1],
+                    pb.op(pk.I8_FRONT, val[src], v, p=dict(H0=H, W0=Wd, C=Cout, N=N, OH=BH, OW=BW, stem_zp_in=z_i, stem_zp_out=z_o, stem_amin=a_lo, stem_amax=a_hi, dw_zp_out=zdo, dw_amin=dlo,
+                                 dw_amax=dhi, pw_zp_out=zpo, pw_amin=plo, pw_amax=phi, strip=int(cst is not None)),
+                          t=dict(stem_w=pb.tensor(w, np.int8), stem_b=pb.tensor(b, np.int32), stem_mult=pb.tensor(mu, np.int32), stem_shift=pb.tensor(sh, np.int32),
+                                 dw_w=pb.tensor(wtd.data[0], np.int8), dw_b=pb.tensor(bd, np.int32), dw_mult=pb.tensor(mud, np.int32), dw_shift=pb.tensor(shd, np.int32),
+                                 pw_w=pb.tensor(pack_i8_fragments(wpw), np.int8), pw_b=pb.tensor(bp, np.int32), pw_mult=pb.tensor(mup, np.int32),
+                                 pw_shift=pb.tensor(shp, np.int32), strip_cst=pb.tensor(cst, np.int32) if cst is not None else -1),
                           name=f"t{p_op.outputs[0]}", out_shape=(BH, BW, N), out_dtype="int8")
                     val[p_op.outputs[0]], shape[p_op.outputs[0]] = v, (BH, BW, N)
                     i += 3
                     continue
             v = pb.value(OH * OW * Cout)
-            pb.op(pk.I8_STEM, val[src], v, p=[H, Wd, Cout, sh_, sw_, 0, OH, OW, pt, pl, z_i, z_o, a_lo, a_hi],
-                  t=[pb.tensor(w, np.int8), pb.tensor(b, np.int32), pb.tensor(mu, np.int32), pb.tensor(sh, np.int32)],
+            pb.op(pk.I8_STEM, val[src], v, p=dict(H=H, W=Wd, Cout=Cout, sh=sh_, sw=sw_, OH=OH, OW=OW, pt=pt, pl=pl, zp_in=z_i, zp_out=z_o, act_min=a_lo, act_max=a_hi),
+                  t=dict(w=pb.tensor(w, np.int8), bias=pb.tensor(b, np.int32), mult=pb.tensor(mu, np.int32), shift=pb.tensor(sh, np.int32)),
                   name=f"t{op.outputs[0]}", out_shape=(OH, OW, Cout), out_dtype="int8")
             val[op.outputs[0]], shape[op.outputs[0]] = v, (OH, OW, Cout)
             i += 1
@@ -923,15 +928,17 @@ def lower_i8(model, keep_all: bool = False, fuse: bool = True, softmax_form: str
                 if (nw and relu_ok and (not add_p[0] or res_val == val[src])
                         and ((ow_ * sw_ - pl + 1 >= 0) & (ow_ * sw_ - pl + 1 < Wd)).all()):
                     cst = strip_constants(wt_.data[0], bdw, mu, sh, z_o, w2, b2, mu2, sh2, zo2, bool(add_p[0]), nw)
-                p = [H, Wd, C, sh_, sw_, 0, OH, OW, pt, pl, z_i, z_o, a_lo, a_hi, Cout, zo2, lo2, hi2, *add_p, 1, 0, *tile, 0, int(cst is not None)]
+                p = dict(H=H, W=Wd, Cin=C, sh=sh_, sw=sw_, OH=OH, OW=OW, pt=pt, pl=pl, dw_zp_in=z_i, dw_zp_out=z_o, dw_amin=a_lo, dw_amax=a_hi, Cout=Cout,
+                         pw_zp_out=zo2, pw_amin=lo2, pw_amax=hi2, **dict(zip(pk.ADD_FIELDS, add_p)), has_dw=1, TH=tile[0], TW=tile[1], NB=tile[2],
+                         strip=int(cst is not None))
                 tail_blocks.append(dict(op=len(plan.ops), src=val[src], res_is_input=(not add_p[0]) or res_val == val[src], H=H, W=Wd, C=C, N=Cout, sh=sh_, sw=sw_,
                                         OH=OH, OW=OW, pt=pt, pl=pl, z_in=z_i, z_dw=z_o, dw_lo=a_lo, dw_hi=a_hi, z_pw=zo2, pw_lo=lo2, pw_hi=hi2, add=list(add_p),
                                         wd=wt_.data[0], bdw=bdw, mu=mu, sh_dw=sh, w2=w2, b2=b2, mu2=mu2, sh2=sh2, macs=(OH * OW * C * 9, OH * OW * C * Cout)))
                 pb.op(pk.I8_DWPW, val[src], v, p=p, in1=res_val,
-                      t=[pb.tensor(wt_.data[0], np.int8), pb.tensor(bdw, np.int32), pb.tensor(mu, np.int32), pb.tensor(sh, np.int32),
-                         pb.tensor(pack_i8_fragments(w2), np.int8), pb.tensor(b2, np.int32), pb.tensor(mu2, np.int32), pb.tensor(sh2, np.int32),
-                         -1, pb.tensor(cst, np.int32) if cst is not None else -1,
-                         pb.tensor(add_table(add_p, zo2), np.int8) if cst is not None and add_p[0] else -1],
+                      t=dict(dw_w=pb.tensor(wt_.data[0], np.int8), dw_b=pb.tensor(bdw, np.int32), dw_mult=pb.tensor(mu, np.int32), dw_shift=pb.tensor(sh, np.int32),
+                             pw_w=pb.tensor(pack_i8_fragments(w2), np.int8), pw_b=pb.tensor(b2, np.int32), pw_mult=pb.tensor(mu2, np.int32),
+                             pw_shift=pb.tensor(sh2, np.int32), strip_cst=pb.tensor(cst, np.int32) if cst is not None else -1,
+                             add_tab=pb.tensor(add_table(add_p, zo2), np.int8) if cst is not None and add_p[0] else -1),
                       name=f"t{out_t}", out_shape=(OH, OW, Cout), out_dtype="int8")
                 val[out_t], shape[out_t] = v, (OH, OW, Cout)
                 i += 2
@@ -940,8 +947,8 @@ def lower_i8(model, keep_all: bool = False, fuse: bool = True, softmax_form: str
             else:
                 _expect_acc_range(wt_.data[0], b - z_i * wt_.data[0].astype(np.int64).sum(axis=(0, 1)), (0, 1), f"depthwise conv of operator #{op.index}", mu, sh)
                 v = pb.value(OH * OW * C)
-                pb.op(pk.I8_DW, val[src], v, p=[H, Wd, C, sh_, sw_, 0, OH, OW, pt, pl, z_i, z_o, a_lo, a_hi],
-                      t=[pb.tensor(wt_.data[0], np.int8), pb.tensor(b, np.int32), pb.tensor(mu, np.int32), pb.tensor(sh, np.int32)],
+                pb.op(pk.I8_DW, val[src], v, p=dict(H=H, W=Wd, C=C, sh=sh_, sw=sw_, OH=OH, OW=OW, pt=pt, pl=pl, zp_in=z_i, zp_out=z_o, act_min=a_lo, act_max=a_hi),
+                      t=dict(w=pb.tensor(wt_.data[0], np.int8), bias=pb.tensor(b, np.int32), mult=pb.tensor(mu, np.int32), shift=pb.tensor(sh, np.int32)),
                       name=f"t{op.outputs[0]}", out_shape=(OH, OW, C), out_dtype="int8")
                 val[op.outputs[0]], shape[op.outputs[0]] = v, (OH, OW, C)
                 i += 1
@@ -978,14 +985,16 @@ def lower_i8(model, keep_all: bool = False, fuse: bool = True, softmax_form: str
                 # plain 1x1 convolution (inverted-residual expand / project, embedding conv) on the int8 matrix cores: the fused block kernel
                 # without its depthwise stage
                 zero = pb.tensor(np.zeros(4, np.int32), np.int32)
-                pp = [H, Wd, Cin, 1, 1, 0, H, Wd, 0, 0, 0, 0, 0, 0, Cout, z_o, a_lo, a_hi, *add_p, 0, 0, *tile, 0, 0]
+                pp = dict(H=H, W=Wd, Cin=Cin, sh=1, sw=1, OH=H, OW=Wd, Cout=Cout, pw_zp_out=z_o, pw_amin=a_lo, pw_amax=a_hi, **dict(zip(pk.ADD_FIELDS, add_p)),
+                          TH=tile[0], TW=tile[1], NB=tile[2])
                 pb.op(pk.I8_DWPW, val[src], v, p=pp, in1=res_val,
-                      t=[zero, zero, zero, zero, pb.tensor(pack_i8_fragments(w), np.int8), pb.tensor(b, np.int32), pb.tensor(mu, np.int32), pb.tensor(sh, np.int32),
-                         -1, -1, pb.tensor(add_table(add_p, z_o), np.int8) if add_p[0] else -1],  # the whole ADD as a 64 KB table (i8_pw_wave / i8_pw_lds kernels)
+                      t=dict(dw_w=zero, dw_b=zero, dw_mult=zero, dw_shift=zero, pw_w=pb.tensor(pack_i8_fragments(w), np.int8), pw_b=pb.tensor(b, np.int32),
+                             pw_mult=pb.tensor(mu, np.int32), pw_shift=pb.tensor(sh, np.int32),
+                             add_tab=pb.tensor(add_table(add_p, z_o), np.int8) if add_p[0] else -1),  # the whole ADD as a 64 KB table (i8_pw_wave / i8_pw_lds kernels)
                       name=f"t{out_t}", out_shape=(H, Wd, Cout), out_dtype="int8")
             else:
-                pb.op(pk.I8_PW, val[src], v, p=[H * Wd, Cin, Cout, z_o, a_lo, a_hi, *add_p], in1=res_val,
-                      t=[pb.tensor(w, np.int8), pb.tensor(b, np.int32), pb.tensor(mu, np.int32), pb.tensor(sh, np.int32)],
+                pb.op(pk.I8_PW, val[src], v, p=dict(P=H * Wd, Cin=Cin, Cout=Cout, zp_out=z_o, act_min=a_lo, act_max=a_hi, **dict(zip(pk.ADD_FIELDS, add_p))), in1=res_val,
+                      t=dict(w=pb.tensor(w, np.int8), bias=pb.tensor(b, np.int32), mult=pb.tensor(mu, np.int32), shift=pb.tensor(sh, np.int32)),
                       name=f"t{out_t}", out_shape=(H, Wd, Cout), out_dtype="int8")
             val[out_t], shape[out_t] = v, (H, Wd, Cout)
             i += 1
@@ -1023,8 +1032,9 @@ def lower_i8(model, keep_all: bool = False, fuse: bool = True, softmax_form: str
             o_mu, o_sh = qz.quantize_multiplier(float(np.float32(s_m)) / float(np.float32(s_o)))
             form = {"fixed": 0, "lut": 1}[softmax_form]
             v = pb.value(C)
-            pb.op(pk.I8_ATTNPOOL, val[src], v, p=[P, C, int(b), int(mu[0]), int(sh[0]), z_s, form, z_x, z_a, m_mu, m_sh, z_m, m_lo, m_hi, o_mu, o_sh, z_o],
-                  t=[pb.tensor(w.astype(np.int8), np.int8), pb.tensor(qz.softmax_tables(s_s, beta, softmax_form), np.int32)],
+            pb.op(pk.I8_ATTNPOOL, val[src], v, p=dict(P=P, C=C, fc_bias=int(b), fc_mult=int(mu[0]), fc_shift=int(sh[0]), fc_zo=z_s, form=form, zx=z_x, za=z_a, mul_mult=m_mu, mul_shift=m_sh,
+                         mul_zo=z_m, mul_lo=m_lo, mul_hi=m_hi, sum_mult=o_mu, sum_shift=o_sh, sum_zo=z_o),
+                  t=dict(score=pb.tensor(w.astype(np.int8), np.int8), tables=pb.tensor(qz.softmax_tables(s_s, beta, softmax_form), np.int32)),
                   name=f"t{sm_sum.outputs[0]}", out_shape=(C,), out_dtype="int8")
             val[sm_sum.outputs[0]], shape[sm_sum.outputs[0]] = v, (C,)
             i += 7
@@ -1037,7 +1047,7 @@ def lower_i8(model, keep_all: bool = False, fuse: bool = True, softmax_form: str
             mu, sh = qz.mean_multiplier(s_i, s_o, H * Wd) if mean_form == "int" else qz.mean_float_params(s_i, s_o)
             v = pb.value(C)
             tail_head.update(mean_op=len(plan.ops), mean_src=val[src], P=H * Wd, C=C, mean_zp_in=z_i, mean_mult=mu, mean_shift=sh, mean_zp_out=z_o)
-            pb.op(pk.I8_MEAN, val[src], v, p=[H * Wd, C, z_i, mu, sh, z_o], name=f"t{op.outputs[0]}", out_shape=(C,), out_dtype="int8")
+            pb.op(pk.I8_MEAN, val[src], v, p=dict(P=H * Wd, C=C, zp_in=z_i, mult=mu, shift=sh, zp_out=z_o), name=f"t{op.outputs[0]}", out_shape=(C,), out_dtype="int8")
             val[op.outputs[0]], shape[op.outputs[0]] = v, (C,)
             i += 1
         elif op.name == "FULLY_CONNECTED":
@@ -1061,16 +1071,16 @@ def lower_i8(model, keep_all: bool = False, fuse: bool = True, softmax_form: str
             nxt = ops[i + 1] if i + 1 < len(ops) else None
             fold_lut = (nxt is not None and nxt.name == "LOGISTIC" and nxt.inputs[0] == op.outputs[0] and g.consumers.get(op.outputs[0], []) == [nxt.index]
                         and i + 2 < len(ops) and ops[i + 2].name != "DEQUANTIZE")
-            tt = [pb.tensor(w_pad, np.int8), pb.tensor(b, np.int32), pb.tensor(mu, np.int32), pb.tensor(sh, np.int32)]
+            tt = dict(w=pb.tensor(w_pad, np.int8), bias=pb.tensor(b, np.int32), mult=pb.tensor(mu, np.int32), shift=pb.tensor(sh, np.int32))
             out_t = op.outputs[0]
             if fold_lut:
                 s_h, z_h = g.q(nxt.outputs[0])
-                tt.append(pb.tensor(qz.logistic_table(s_o, z_o, s_h, z_h), np.int8))
+                tt["lut"] = pb.tensor(qz.logistic_table(s_o, z_o, s_h, z_h), np.int8)
                 out_t = nxt.outputs[0]
             v = pb.value(Cout)
             if not fold_lut:
                 tail_head.update(fc_op=len(plan.ops), fc_cin=Cin, NC=Cout, fc_zp_out=z_o, fc_lo=a_lo, fc_hi=a_hi, fc_w=wt_.data, fc_b=b, fc_m=mu, fc_s=sh)
-            pb.op(pk.I8_FC, val[src], v, p=[Cin, Cout, z_o, a_lo, a_hi, int(fold_lut)], t=tt, name=f"t{out_t}", out_shape=(Cout,), out_dtype="int8")
+            pb.op(pk.I8_FC, val[src], v, p=dict(Cin=Cin, Cout=Cout, zp_out=z_o, act_min=a_lo, act_max=a_hi, has_lut=int(fold_lut)), t=tt, name=f"t{out_t}", out_shape=(Cout,), out_dtype="int8")
             val[out_t], shape[out_t] = v, (Cout,)
             i += 2 if fold_lut else 1
         elif op.name == "MUL":
@@ -1086,7 +1096,8 @@ def lower_i8(model, keep_all: bool = False, fuse: bool = True, softmax_form: str
             mu, sh = qz.quantize_multiplier(float(np.float32(s1)) * float(np.float32(s2)) / float(np.float32(so)))
             lo_, hi_ = qz.activation_bounds(op.options["activation"], so, zo)
             v = pb.value(H * Wd * C)
-            pb.op(pk.I8_SCALE, val[a_t], v, in1=val[b_t], p=[H * Wd, C, z1, z2, mu, sh, zo, lo_, hi_], name=f"t{op.outputs[0]}", out_shape=(H, Wd, C), out_dtype="int8")
+            pb.op(pk.I8_SCALE, val[a_t], v, in1=val[b_t], p=dict(P=H * Wd, C=C, zp_x=z1, zp_gate=z2, mult=mu, shift=sh, zp_out=zo, act_min=lo_, act_max=hi_),
+                  name=f"t{op.outputs[0]}", out_shape=(H, Wd, C), out_dtype="int8")
             val[op.outputs[0]], shape[op.outputs[0]] = v, (H, Wd, C)
             i += 1
         elif op.name in ("LOGISTIC", "DEQUANTIZE"):
@@ -1111,7 +1122,8 @@ def lower_i8(model, keep_all: bool = False, fuse: bool = True, softmax_form: str
                 i += 1
             if not softmax:
                 tail_head.update(head_op=len(plan.ops), lut=qz.logistic_table(s_fc, z_fc, s_h, z_h) if has else None, zp_fc=z_fc, zp_head=z_h, s_fc=s_fc, s_head=s_h)
-            pb.op(pk.I8_HEAD, val[fc_out], pk.SLOT_SCORES, p=[Cout, z_fc, z_h, has, softmax], f=[s_fc, s_h, beta], t=[lut_t], name=f"t{ops[i].outputs[0]}",
+            pb.op(pk.I8_HEAD, val[fc_out], pk.SLOT_SCORES, p=dict(C=Cout, zp_fc=z_fc, zp_out=z_h, has_lut=has, softmax=softmax),
+                  f=dict(s_fc=s_fc, s_out=s_h, beta=beta), t=dict(lut=lut_t), name=f"t{ops[i].outputs[0]}",
                   out_shape=(Cout,))
             i += 1
             _expect(i == len(ops), "operators after the head")
@@ -1143,7 +1155,7 @@ def _mark_embedding(g: _Graph, plan: pk.Plan) -> None:
     if pool.kind not in (pk.I8_MEAN, pk.I8_ATTNPOOL) or not pool.name.startswith("t"):
         return
     s, z = g.q(int(pool.name[1:]))
-    pk.mark_embedding(pool, pool.p[1], float(np.float32(s)), z)
+    pk.mark_embedding(pool, pool.get("C"), float(np.float32(s)), z)
 
 
 def _tag_se_gates(pb: pk.PlanBuilder) -> None:
@@ -1154,7 +1166,8 @@ def _tag_se_gates(pb: pk.PlanBuilder) -> None:
         a, f1, f2 = ops[i], ops[i + 1], ops[i + 2]
         if a.kind != pk.I8_MEAN or f1.kind != pk.I8_FC or f2.kind != pk.I8_FC or f1.in0 != a.out or f2.in0 != f1.out:
             continue
-        if f1.p[0] != a.p[1] or f2.p[0] != f1.p[1] or f1.p[1] > 256 or a.p[1] > 1024 or a.p[1] % 4:
+        C, Cr = a.get("C"), f1.get("Cout")
+        if f1.get("Cin") != C or f2.get("Cin") != Cr or Cr > 256 or C > 1024 or C % 4:
             continue
         others = [k for k, o in enumerate(ops) if (k != i + 1 and a.out in (o.in0, o.in1)) or (k != i + 2 and f1.out in (o.in0, o.in1))]
         if others or a.out < 0 or f1.out < 0 or f2.out < 0:
@@ -1171,11 +1184,11 @@ def _tag_pwdw_pairs(pb: pk.PlanBuilder) -> None:
     ops = pb.plan.ops
     for i in range(len(ops) - 1):
         e, d = ops[i], ops[i + 1]
-        if e.kind != pk.I8_DWPW or d.kind != pk.I8_DW or e.p[29] or e.p[30] or e.p[18] or e.p[34] or e.p[36] or d.in0 != e.out or e.out < 0:
+        if e.kind != pk.I8_DWPW or d.kind != pk.I8_DW or any(e.get(k) for k in ("has_dw", "transposed", "has_add", "has_lut", "q_at_load")) or d.in0 != e.out or e.out < 0:
             continue
         if e.p[pk.TAIL_TAG] or d.p[pk.TAIL_TAG] or e.p[pk.OP_PATH] != d.p[pk.OP_PATH]:
             continue
-        if d.p[2] != e.p[14] or (d.p[0], d.p[1]) != (e.p[6], e.p[7]) or d.p[10] != e.p[15]:
+        if d.get("C") != e.get("Cout") or (d.get("H"), d.get("W")) != (e.get("OH"), e.get("OW")) or d.get("zp_in") != e.get("pw_zp_out"):
             continue
         readers = [k for k, o in enumerate(ops) if k != i + 1 and e.out in (o.in0, o.in1)]
         writers = [k for k, o in enumerate(ops) if o.out == e.out]
@@ -1194,9 +1207,9 @@ def _tag_scale_pairs(pb: pk.PlanBuilder) -> None:
     ops = pb.plan.ops
     for i in range(len(ops) - 1):
         a, b = ops[i], ops[i + 1]
-        if a.kind != pk.I8_SCALE or b.kind != pk.I8_DWPW or b.p[29] or b.p[30] or b.p[34] or b.p[36] or b.in0 != a.out:
+        if a.kind != pk.I8_SCALE or b.kind != pk.I8_DWPW or any(b.get(k) for k in ("has_dw", "transposed", "has_lut", "q_at_load")) or b.in0 != a.out:
             continue
-        if b.p[2] != a.p[1] or b.p[0] * b.p[1] != a.p[0] or b.p[2] > 768 or (b.p[3], b.p[4]) != (1, 1):
+        if b.get("Cin") != a.get("C") or b.get("H") * b.get("W") != a.get("P") or b.get("Cin") > 768 or (b.get("sh"), b.get("sw")) != (1, 1):
             continue
         readers = [k for k, o in enumerate(ops) if k != i + 1 and a.out in (o.in0, o.in1)]
         if readers or b.in1 == a.out:
@@ -1238,9 +1251,9 @@ def _add_mid_op(pb, plan, blocks: list[dict]) -> None:
         plan.ops[k].p[pk.TAIL_TAG] = pk.MID_COVERED
     last = plan.ops[ops_idx[-1]]
     pb.op(pk.I8_MID, a["src"], last.out,
-          p=[a["H"] * a["W"] * a["C"], sum(blk["macs"][1] for blk in chain), sum(blk["macs"][0] for blk in chain), 0, 0, 3,
-             a["H"], a["W"], a["C"], c["OH"] * c["OW"], c["N"], *([0] * (pk.TAIL_TAG - 11)), pk.MID_OP],
-          t=[pb.tensor(cst, np.int32), pb.tensor(desc, np.int32)], name=last.name, out_shape=last.out_shape, out_dtype="int8")
+          p=dict(in_bytes=a["H"] * a["W"] * a["C"], pw_macs=sum(blk["macs"][1] for blk in chain), dw_macs=sum(blk["macs"][0] for blk in chain), n_layers=3,
+                 H0=a["H"], W0=a["W"], C0=a["C"], P_last=c["OH"] * c["OW"], C_last=c["N"]), tag=pk.MID_OP,
+          t=dict(cst=pb.tensor(cst, np.int32), desc=pb.tensor(desc, np.int32)), name=last.name, out_shape=last.out_shape, out_dtype="int8")
 
 
 def _add_tail_op(pb, plan, blocks: list[dict], head: dict) -> None:
@@ -1274,10 +1287,11 @@ def _add_tail_op(pb, plan, blocks: list[dict], head: dict) -> None:
     for k in ops_idx:
         plan.ops[k].p[pk.TAIL_TAG] = pk.TAIL_COVERED
     pb.op(pk.I8_TAIL, first["src"], pk.SLOT_SCORES,
-          p=[first["H"] * first["W"] * first["C"], pw_macs, dw_macs, head["P"] * head["C"] + head["C"] * head["NC"], head["NC"], len(chain),
-             first["H"], first["W"], first["C"], head["P"], head["C"], *([0] * (pk.TAIL_TAG - 11)), pk.TAIL_OP],
-          t=[pb.tensor(cst, np.int32), pb.tensor(desc, np.int32)] + ([pb.tensor(packed2[0], np.int32), pb.tensor(packed2[1], np.int32)] if packed2 is not None else []),
-          f=[head["s_fc"], head["s_head"]], name="tail", out_shape=(head["NC"],))
+          p=dict(in_bytes=first["H"] * first["W"] * first["C"], pw_macs=pw_macs, dw_macs=dw_macs, other_macs=head["P"] * head["C"] + head["C"] * head["NC"],
+                 n_classes=head["NC"], n_layers=len(chain), H0=first["H"], W0=first["W"], C0=first["C"], P_last=head["P"], C_last=head["C"]), tag=pk.TAIL_OP,
+          t=dict(cst=pb.tensor(cst, np.int32), desc=pb.tensor(desc, np.int32),
+                 **(dict(cst2=pb.tensor(packed2[0], np.int32), desc2=pb.tensor(packed2[1], np.int32)) if packed2 is not None else {})),
+          f=dict(s_fc=head["s_fc"], s_head=head["s_head"]), name="tail", out_shape=(head["NC"],))
     mean = plan.ops[head["mean_op"]]
     if mean.p[pk.EMB_TAG] == pk.EMB_OP:  # the fused operator pools the same vector on chip: it carries the mark as well
         pk.mark_embedding(plan.ops[-1], mean.p[pk.EMB_DIM], mean.f[pk.EMB_SCALE], mean.p[pk.EMB_ZP])

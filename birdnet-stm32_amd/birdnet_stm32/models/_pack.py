@@ -51,6 +51,66 @@ KIND_NAMES = {
     I8_PW: "i8_pw", I8_DWPW: "i8_dwpw", I8_FRONT: "i8_front", I8_MEAN: "i8_mean", I8_FC: "i8_fc", I8_HEAD: "i8_head", I8_TAIL: "i8_tail", I8_SCALE: "i8_scale", I8_MAXNORM: "i8_maxnorm", I8_RAWFE: "i8_rawfe", I8_ATTNPOOL: "i8_attnpool", I8_MID: "i8_mid",
 }  # fmt: skip
 
+# ---- operator-record fields: the Python mirror of csrc/bn_ops.h ---------------------------------------------------------------------
+# OP_FIELDS[kind] = (names of p[0..], names of t[0..], names of f[0..]) in index order; tests/test_lowering_and_abi.py compares the table
+# with the enumerators of bn_ops.h.  A kind's names are unique across its three arrays, so one name addresses one entry.  rsvN: an entry
+# the kind leaves at its default.  The cross-kind entries (OP_PATH, TAIL_TAG, FRONT2_DIST, EMB_*) keep the fixed indices above.
+
+
+def _geom(c: str, p5: str) -> tuple:
+    """The ten conv-geometry fields STEM / DW / DWPW of both plans start with (bn_ops.h: BN_OP_GEOM)."""
+    return ("H", "W", c, "sh", "sw", p5, "OH", "OW", "pt", "pl")
+
+
+ADD_FIELDS = ("has_add", "add_z1", "add_m1", "add_s1", "add_m2", "add_s2", "add_mo", "add_so", "add_zo", "add_amin", "add_amax")  # bn_ops.h: BN_OP_ADD
+_RQ = ("w", "bias", "mult", "shift")
+_FRONT_T = ("stem_w", "stem_b", "dw_w", "dw_b", "pw_w", "pw_b")
+_FRONT8_T = ("stem_w", "stem_b", "stem_mult", "stem_shift", "dw_w", "dw_b", "dw_mult", "dw_shift", "pw_w", "pw_b", "pw_mult", "pw_shift")
+_CHAIN = ("n_layers", "H0", "W0", "C0", "P_last", "C_last")
+
+OP_FIELDS = {
+    F32_MEL: (("F", "W", "M", "mag", "norm"), ("wvals", "bands", "magp"), ()),
+    F32_MAG: (("M", "W", "mag"), ("rsv0", "rsv1", "magp"), ()),
+    F32_RAWFE: (("T", "W", "M", "stride", "pad_left", "mag"), ("fb", "bias", "magp"), ()),
+    F32_STEM: (_geom("Cout", "act"), ("w", "bias"), ()),
+    F32_DW: (_geom("C", "act"), ("w", "bias"), ()),
+    F32_PW: (("P", "Cin", "Cout", "act", "has_res", "has_gate", "gate_slot"), ("w", "bias"), ()),
+    F32_SEGATE: (("P", "C", "Cr"), ("w1", "w2"), ()),
+    F32_SCALE: (("P", "C"), (), ()),
+    F32_GAP: (("P", "C"), (), ()),
+    F32_DENSE: (("Cin", "Cout", "act"), ("w", "bias"), ()),
+    F32_ATTNPOOL: (("P", "C"), ("score",), ()),
+    F32_DWPW: (_geom("Cin", "dw_act") + ("Cout", "pw_act", "has_res", "has_gate", "gate_slot", "has_dw", "TH", "TW", "NB"),
+               ("dw_w", "dw_b", "pw_w", "pw_b"), ()),
+    F32_STFTMEL: (("T", "W", "M"), ("wvals", "bands"), ()),
+    F32_MELFIN: (("M", "W", "mag", "norm"), ("wsum", "rsv1", "magp"), ()),
+    F32_FRONT: (("H0", "W0", "C", "N", "OH", "OW", "stem_act", "dw_act", "pw_act", "raw_mel", "mag"), _FRONT_T + ("wsum", "magp"), ()),
+    F32_GAPDENSE: (("P", "Cin", "Cout", "act"), ("w", "bias"), ()),
+    I8_QUANT: (("F", "W", "Kp", "zp", "fill"), (), ("scale",)),
+    I8_MEL: (("W", "Kp", "M", "zp_out", "act_min", "act_max", "has_lut"), _RQ + ("lut",), ()),
+    I8_STEM: (_geom("Cout", "rsv5") + ("zp_in", "zp_out", "act_min", "act_max"), _RQ, ()),
+    I8_DW: (_geom("C", "rsv5") + ("zp_in", "zp_out", "act_min", "act_max"), _RQ, ()),
+    I8_PW: (("P", "Cin", "Cout", "zp_out", "act_min", "act_max") + ADD_FIELDS, _RQ, ()),
+    I8_MEAN: (("P", "C", "zp_in", "mult", "shift", "zp_out"), (), ()),
+    I8_FC: (("Cin", "Cout", "zp_out", "act_min", "act_max", "has_lut"), _RQ + ("lut",), ()),
+    I8_HEAD: (("C", "zp_fc", "zp_out", "has_lut", "softmax"), ("lut",), ("s_fc", "s_out", "beta")),
+    I8_DWPW: (_geom("Cin", "qF") + ("dw_zp_in", "dw_zp_out", "dw_amin", "dw_amax", "Cout", "pw_zp_out", "pw_amin", "pw_amax") + ADD_FIELDS
+              + ("has_dw", "transposed", "TH", "TW", "NB", "has_lut", "strip", "q_at_load", "qzp", "qfill"),
+              ("dw_w", "dw_b", "dw_mult", "dw_shift", "pw_w", "pw_b", "pw_mult", "pw_shift", "lut", "strip_cst", "add_tab"), ("qscale",)),
+    I8_FRONT: (("H0", "W0", "C", "N", "OH", "OW", "stem_zp_in", "stem_zp_out", "stem_amin", "stem_amax", "dw_zp_out", "dw_amin", "dw_amax",
+                "pw_zp_out", "pw_amin", "pw_amax", "strip"), _FRONT8_T + ("strip_cst",), ()),
+    I8_TAIL: (("in_bytes", "pw_macs", "dw_macs", "other_macs", "n_classes") + _CHAIN, ("cst", "desc", "cst2", "desc2"), ("s_fc", "s_head")),
+    I8_SCALE: (("P", "C", "zp_x", "zp_gate", "mult", "shift", "zp_out", "act_min", "act_max"), (), ()),
+    I8_MAXNORM: (("C", "W", "has_lut"), ("denom", "div", "lut"), ()),
+    I8_RAWFE: (("T", "W", "M", "stride", "pad_left", "q_zp", "zp_out", "act_min", "act_max", "has_lut"), _RQ + ("lut",), ("q_scale",)),
+    I8_ATTNPOOL: (("P", "C", "fc_bias", "fc_mult", "fc_shift", "fc_zo", "form", "zx", "za", "mul_mult", "mul_shift", "mul_zo", "mul_lo", "mul_hi",
+                   "sum_mult", "sum_shift", "sum_zo"), ("score", "tables"), ()),
+    I8_MID: (("in_bytes", "pw_macs", "dw_macs", "rsv3", "rsv4") + _CHAIN, ("cst", "desc"), ()),
+}
+for _k, _pf in OP_FIELDS.items():
+    _all = _pf[0] + _pf[1] + _pf[2]
+    assert len(set(_all)) == len(_all) and len(_pf[0]) <= OP_PATH and len(_pf[1]) <= OP_NT and len(_pf[2]) <= OP_NF, KIND_NAMES[_k]
+
 ACT_CODES = {"none": 0, "linear": 0, "relu": 1, "relu6": 2}
 MAG_CODES = {"none": 0, "pwl": 1, "pcen": 2, "db": 3}
 
@@ -87,6 +147,21 @@ class PlanOp:
     name: str = ""  # reference layer / tflite tensor this output corresponds to
     out_shape: tuple = ()  # per chunk
     out_dtype: str = "float32"
+
+    def _entry(self, name: str) -> tuple[list, int]:
+        for arr, names in zip((self.p, self.t, self.f), OP_FIELDS[self.kind]):
+            if name in names:
+                return arr, names.index(name)
+        raise KeyError(f"{KIND_NAMES[self.kind]} has no field '{name}'")
+
+    def get(self, name: str):
+        """The entry of p / t / f that ``OP_FIELDS`` names ``name`` for this operator's kind."""
+        arr, i = self._entry(name)
+        return arr[i]
+
+    def set(self, name: str, value) -> None:
+        arr, i = self._entry(name)
+        arr[i] = value
 
 
 @dataclass
@@ -151,17 +226,27 @@ class PlanBuilder:
         self._value_bytes.append(_align(int(nbytes), 256))
         return len(self._value_bytes) - 1
 
-    def op(self, kind, in0, out, p=(), t=(), f=(), in1=SLOT_NONE, name="", out_shape=(), out_dtype="float32",
-           value_params=(), path=PATH_BOTH) -> PlanOp:
-        pp = [int(v) for v in p] + [0] * (OP_NP - len(p))
+    def op(self, kind, in0, out, p=None, t=None, f=None, in1=SLOT_NONE, name="", out_shape=(), out_dtype="float32",
+           value_params=(), path=PATH_BOTH, tag=0) -> PlanOp:
+        """Append an operator.  ``p`` / ``t`` / ``f`` map field names of ``OP_FIELDS[kind]`` to values (entries left out keep 0 / -1 / 0.0);
+        a name the kind does not have in that array raises.  ``value_params``: names of p entries that hold a value id; ``tag``: p[TAIL_TAG]."""
+        names = OP_FIELDS[kind]
+
+        def fill(given, which, n, default, conv):
+            arr = [default] * n
+            for k, v in (given or {}).items():
+                if k not in names[which]:
+                    raise ValueError(f"{KIND_NAMES[kind]}: '{k}' is not a field of {'ptf'[which]}")
+                arr[names[which].index(k)] = conv(v)
+            return arr
+
+        pp, tt, ff = fill(p, 0, OP_NP, 0, int), fill(t, 1, OP_NT, -1, int), fill(f, 2, OP_NF, 0.0, float)
         pp[OP_PATH] = int(path)
-        tt = [int(v) for v in t] + [-1] * (OP_NT - len(t))
-        ff = [float(v) for v in f] + [0.0] * (OP_NF - len(f))
-        if len(pp) != OP_NP or len(tt) != OP_NT or len(ff) != OP_NF:
-            raise ValueError("operator record overflow")
+        if tag:  # (I8_DWPW's qfill shares the index: see the stated exception in bn_ops.h)
+            pp[TAIL_TAG] = int(tag)
         o = PlanOp(kind, int(in0), int(in1), int(out), pp, tt, ff, name, tuple(out_shape), out_dtype)
-        for pi in value_params:
-            self._gate_refs.append((len(self.plan.ops), pi))
+        for pn in value_params:
+            self._gate_refs.append((len(self.plan.ops), names[0].index(pn)))
         self.plan.ops.append(o)
         return o
 

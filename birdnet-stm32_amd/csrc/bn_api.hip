@@ -1,6 +1,6 @@
 // bn_api.hip — the C ABI of libbirdnet_hip.so (include/birdnet_hip.h): context and model
-// lifetime, packed-blob parsing, workspace planning and the device-plan executor that turns one
-// bn_forward()/bn_infer_audio() call into a sequence of kernel launches on the caller's stream.
+// lifetime, packed-blob parsing, workspace allocation and the entry points that split a
+// bn_forward()/bn_infer_audio() call into launch groups for the plan executor (bn_plan_run.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -13,34 +13,13 @@
 #include <string>
 #include <vector>
 
-#include "../../include/birdnet_hip.h"
-#include "bn_blob.h"
-#include "bn_kernels.h"
-#include "bn_quant_in.h"
+#include "bn_model.h"
 
 namespace {
 
 thread_local std::string g_err;
 
-int fail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                             \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess)                                                                     \
-            return fail(BN_ERR_DEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
 constexpr int kFft = 512;
-constexpr int kMaxGridBatch = 32768;  // chunks per launch group (gridDim.y/z limit is 65535)
 
 struct OptName {
     const char* name;
@@ -72,98 +51,23 @@ bn::Options options_from_env() {
 
 namespace bn {
 thread_local Options g_opt;
+
+int fail(int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    g_err = buf;
+    return code;
 }
+}  // namespace bn
+using bn::fail;
+using bn::kMaxGridBatch;
+using bn::ProfScope;
 
 bn::Options g_opt_default = options_from_env();   // the process default (bn_set_option); copied into bn::g_opt per API call
 std::mutex g_opt_mu;
-
-struct bn_ctx {
-    std::vector<std::pair<int bn::Options::*, int>> opt_override;   // switches this context sets for itself (bn_ctx_set_option)
-    int device = 0;
-    int max_batch = 0;
-    float* d_window = nullptr;
-    float4* d_tw256 = nullptr;
-    float4* d_tw512 = nullptr;
-    double* d_f64tab = nullptr;      // hann64[512], cs64[512] (bn_stft_exact.hip)
-    bn::StftTables tables{};
-    float* d_block_peaks = nullptr;  // bn_ingest_resample: per-workgroup maxima, grown on demand
-    size_t block_peaks_elems = 0;
-    void* d_rank_work = nullptr;     // bn_rank_orders: transposed keys, index arrays, rocPRIM storage; grown on demand
-    size_t rank_work_bytes = 0;
-};
-
-struct bn_model {
-    bn_ctx* ctx = nullptr;
-    BlobHeader hdr{};
-    std::vector<OpRec> ops;
-    std::vector<TensorRec> tensors;
-    std::vector<SlotRec> slots;
-    char* d_consts = nullptr;            // one allocation, tensors at their blob offsets
-    size_t consts_base = 0;              // blob offset of the first payload byte
-    size_t consts_bytes = 0;
-    std::vector<uint8_t> rq_right;       // per operator: all requantisation multipliers >= 0 and shifts < 0
-    std::vector<bn::Tail8Args> tails;    // per operator: arguments of the fused tail kernel (BN_OP_I8_TAIL operators only)
-    std::vector<uint8_t> tail_ok;        // per operator: BN_OP_I8_TAIL whose maps fit the kernel's LDS plan
-    std::vector<bn::Tail2Args> tails2;   // per operator: the same for i8_tail2_kernel (depthwise stage on the matrix cores), when the plan carries its constants
-    std::vector<uint8_t> tail2_ok;
-    std::vector<bn::Tail2Args> mids;     // per operator: arguments of the fused stage-2 chain (BN_OP_I8_MID operators only)
-    std::vector<uint8_t> mid_ok;
-    std::vector<bn::Tail2Args> mids_res;   // the same chains with the resident LDS placement (option i8_mid_split) ...
-    std::vector<uint8_t> mid_res_ok;       // ... where it fits
-    bool has_mid = false;
-    std::vector<uint8_t> out_valid;      // per operator: it wrote its output slot in the last forward call (not when a fused kernel covered it)
-    std::vector<uint8_t> slot_valid;     // per slot: some operator wrote it in the last forward call
-    bool has_tail = false;               // the plan holds a usable fused tail operator
-    bool guard_form_ok = false;          // ... and its QUANTIZE has zero point -128 (the only form the guarded mixer is built for)
-    bool spec_tiled_ok = false;          // the plan's first operator reads the spectrogram through i8_mel_mfma_kernel<QIN>: bn_infer_audio
-                                         // may hand it the tile-major layout the STFT writes fastest
-    bool spec_tiled_now = false;         // set by bn_infer_audio around its bn_forward call
-    std::vector<char*> d_slots;          // max_batch * bytes_per_chunk each
-    float* d_spec = nullptr;             // [max_batch][F][W] for bn_infer_audio
-    float* d_minmax = nullptr;           // [max_batch][2]
-    char* d_guard = nullptr;             // buffers of the exactness pass (INT8 plans whose first operator quantises the spectrogram)
-    bn::StftGuard guard{};
-    bool last_tiled = false;             // layout of d_spec after the last bn_infer_audio call (bn_debug_input_bytes)
-    int last_B = 0;
-    bool guard_now = false;              // set by bn_infer_audio: the first operator lists doubtful bytes, the float64 pass follows it
-    const float* guard_audio = nullptr;
-    int* d_audit = nullptr;              // [2] exactness audit: elements audited, violations (option stft_audit; zeroed per bn_infer_audio call)
-    int guard_T = 0, guard_hop = 0;
-    float* d_smax = nullptr;             // [max_batch] per-sample maxima of the frontend
-    float* d_gap_part = nullptr;         // [max_batch][gap_part_elems] channel sums per row block from f32_pwdw_kernel for the squeeze-excite gate behind it
-    size_t gap_part_elems = 0;
-    int32_t* d_pool8 = nullptr;          // [max_batch][pool8_C] int32 channel sums from i8_dw_stream_kernel for the squeeze-excite gate behind it (zero between uses)
-    size_t pool8_C = 0;
-    size_t workspace_bytes = 0;
-    int emb_dim = 0;                     // the plan's embedding (operators tagged BN_EMB_OP): width, int8 quantisation; 0 = none marked
-    float emb_scale = 1.0f;
-    int emb_zp = 0;
-    // per-operator HIP-event timing (bn_profile_*): one (start, stop) pair per launch group
-    bool profiling = false;
-    int prof_only = -1;                  // >= 0: bracket only this operator (index n_ops = the STFT stage)
-    struct EvRec {
-        int op;
-        hipEvent_t start, stop;
-    };
-    std::vector<EvRec> ev_used;
-    std::vector<hipEvent_t> ev_free;
-
-    hipEvent_t take_event() {
-        if (!ev_free.empty()) {
-            hipEvent_t e = ev_free.back();
-            ev_free.pop_back();
-            return e;
-        }
-        hipEvent_t e = nullptr;
-        (void)hipEventCreate(&e);
-        return e;
-    }
-
-    const void* tensor(int id) const {
-        if (id < 0) return nullptr;
-        return d_consts + (tensors[id].offset - consts_base);
-    }
-};
 
 namespace {
 
@@ -175,575 +79,6 @@ int check_device(bn_ctx* ctx) {
         bn::g_opt = g_opt_default;
         for (const auto& ov : ctx->opt_override) bn::g_opt.*(ov.first) = ov.second;
     }
-    return BN_OK;
-}
-
-// Brackets the launches of one plan operator with HIP events on the launch stream when profiling.
-struct ProfScope {
-    bn_model* m;
-    hipStream_t s;
-    hipEvent_t stop = nullptr;
-    ProfScope(bn_model* m_, int op, hipStream_t s_) : m(m_), s(s_) {
-        if (!m->profiling || (m->prof_only >= 0 && m->prof_only != op)) return;
-        hipEvent_t start = m->take_event();
-        stop = m->take_event();
-        (void)hipEventRecord(start, s);
-        m->ev_used.push_back({op, start, stop});
-    }
-    void end() {
-        if (stop) (void)hipEventRecord(stop, s);
-        stop = nullptr;
-    }
-    ~ProfScope() { end(); }
-};
-
-// A fused kernel runs its head operator and the partner(s) the packer tagged as ONE launch: only when the partner runs wherever the head
-// does — it belongs to both entry paths (the usual case: one head per path in front of a shared block) or to the head's own.  A partner of
-// the OTHER path would not run at all in this mode: separate launches then.
-inline bool same_path(const OpRec& head, const OpRec& partner) {
-    return partner.p[BN_OP_PATH] == BN_PATH_BOTH || partner.p[BN_OP_PATH] == head.p[BN_OP_PATH];
-}
-
-// The exactness pass's buffers for the chunks from b0 on (the work list is shared: one launch group at a time uses it).
-bn::StftGuard guard_slice(const bn_model* m, size_t b0) {
-    bn::StftGuard g = m->guard;
-    const size_t W = m->hdr.spec_width;
-    g.eps += b0 * W;
-    g.rec += b0 * ((W + 15) / 16) * bn::kGuardRec;
-    g.count += b0;
-    g.dirty += b0;
-    g.mn_lo += b0;
-    g.min_interval = bn::g_opt.stft_minint;
-    // every launch group has its own lists and counters (a batch beyond kMaxGridBatch runs the STFT stage of all groups before the plan of the first)
-    const size_t group = b0 / kMaxGridBatch;
-    g.work += b0 * ((W + 63) / 64);
-    g.n_work += group;
-    g.hard += b0;
-    g.n_hard += 2 * group;
-    g.audio = m->guard_audio;  // (already offset to the launch group's first chunk by bn_infer_audio)
-    g.T = m->guard_T;
-    g.hop = m->guard_hop;
-    g.tabs = m->ctx->tables;
-    g.flag_cap = bn::g_opt.stft_flagcap;
-    // the frame part of the bound (bn_quant_in.h): empirical, proven, or — tests only — far too small
-    const int gm = bn::g_opt.stft_guard;
-    g.k_l2 = gm == 1 ? bn::kGuardL2Proven : gm == 2 ? bn::kGuardL2 / 1024.0f : bn::kGuardL2;
-    g.k_peak = gm == 1 ? 0.0f : gm == 2 ? bn::kGuardPeak / 1024.0f : bn::kGuardPeak;
-    g.audit_scale = gm == 2 ? 1024.0f : 1.0f;
-    g.slack_scale = gm == 2 ? 0.0f : 1.0f;
-    g.audit = bn::g_opt.stft_audit ? m->d_audit : nullptr;
-    return g;
-}
-
-// Executes the plan for a batch slice.
-// `op_begin..op_end` restricts the run to a range of operators, `slot_b0` is the chunk index the slice starts at inside the
-// workspace slots (bn_infer_audio runs the first operator per sub-batch, the rest over the whole batch).
-// `d_emb` (or null): where the embedding of the slice goes, in the form `emb_dtype` (BN_EMB_*); the caller offsets it like d_scores.
-int run_plan(bn_model* m, const float* d_input, const float* d_minmax, int B, float* d_scores, float* d_logits, void* d_emb, int emb_dtype,
-             hipStream_t s, const float* d_audio = nullptr, int T = 0, int hop = 0, size_t op_begin = 0, size_t op_end = (size_t)-1,
-             size_t slot_b0 = 0) {
-    const int mode = d_audio ? BN_PATH_AUDIO : BN_PATH_INPUT;
-    auto slot_ptr = [&](int id) -> char* {
-        if (id == BN_SLOT_INPUT) return (char*)d_input;
-        if (id == BN_SLOT_AUDIO) return (char*)d_audio;
-        if (id == BN_SLOT_SCORES) return (char*)d_scores;
-        if (id == BN_SLOT_LOGITS) return (char*)d_logits;
-        if (id < 0 || id >= (int)m->d_slots.size()) return nullptr;
-        return m->d_slots[id] + slot_b0 * m->slots[id].bytes_per_chunk;
-    };
-    const bool tail_on = m->has_tail && bn::g_opt.i8_tail;
-    const bool mid_on = m->has_mid && bn::g_opt.i8_mid && bn::g_opt.i8_strip;
-    if (op_end > m->ops.size()) op_end = m->ops.size();
-    // the pooling scratch is zero between uses (i8_segate_kernel clears what it reads); cleared here as well, so that a call that failed half-way
-    // cannot leave sums behind for the next one
-    if (m->d_pool8 && op_begin == 0 && bn::g_opt.i8_dw_pool) HIP_TRY(hipMemsetAsync(m->d_pool8, 0, (size_t)B * m->pool8_C * sizeof(int32_t), s));
-    size_t gap_for = (size_t)-1;      // squeeze-excite gate whose pooling comes as row-block sums from the fused kernel in front of it
-    int gap_R = 0, cand_R = 0;
-    size_t cand_for = (size_t)-1;     // (candidate: becomes gap_for once the fused kernel has been launched)
-    // the gate right behind a fused (expand, depthwise) pair pools the depthwise map: the fused kernel hands it per-row-block channel sums
-    auto gap_target = [&](size_t di) -> float* {
-        const OpRec& d = m->ops[di];
-        cand_for = (size_t)-1;
-        if (bn::g_opt.f32_pwdw < 2 || !m->d_gap_part || di + 1 >= op_end) return nullptr;
-        const OpRec& g = m->ops[di + 1];
-        const int rb = bn::f32_pwdw_rows(d.p[6]);
-        const int R = (d.p[6] + rb - 1) / rb;
-        if (g.kind != BN_OP_F32_SEGATE || g.in0 != d.out || g.p[1] != d.p[2] || g.p[0] != d.p[6] * d.p[7] || (size_t)R * d.p[2] > m->gap_part_elems ||
-            (g.p[BN_OP_PATH] != BN_PATH_BOTH && g.p[BN_OP_PATH] != mode))
-            return nullptr;
-        cand_for = di + 1;
-        cand_R = R;
-        return m->d_gap_part;
-    };
-    size_t pwdw_head_done = (size_t)-1;  // expand convolution that ran inside the fused kernel of the stem operator in front of it
-    size_t pwdw_done = (size_t)-1;    // depthwise stage that ran inside the expand convolution in front of it
-    size_t front2_done = (size_t)-1;  // operator that the fused front kernel of this run has already covered
-    auto dwpw_args = [&](const OpRec& d) {
-        bn::DwPwArgs a{};
-        const int* q = d.p;
-        a.x = (const float*)slot_ptr(d.in0);
-        a.res = q[12] ? (const float*)slot_ptr(d.in1) : nullptr;
-        a.gate = q[13] ? (const float*)slot_ptr(q[14]) : nullptr;
-        a.y = (float*)slot_ptr(d.out);
-        a.dw_w = (const float*)m->tensor(d.t[0]);
-        a.dw_b = (const float*)m->tensor(d.t[1]);
-        a.pw_w = (const float*)m->tensor(d.t[2]);
-        a.pw_b = (const float*)m->tensor(d.t[3]);
-        a.B = B; a.H = q[0]; a.W = q[1]; a.Cin = q[2]; a.sh = q[3]; a.sw = q[4]; a.dw_act = q[5];
-        a.OH = q[6]; a.OW = q[7]; a.pt = q[8]; a.pl = q[9]; a.Cout = q[10]; a.pw_act = q[11];
-        a.has_dw = q[15]; a.TH = q[16]; a.TW = q[17]; a.NB = q[18];
-        return a;
-    };
-    size_t segate_done[2] = {(size_t)-1, (size_t)-1};  // the two dense layers of a squeeze-excite gate that ran inside the pooling kernel
-    size_t pool8_for = (size_t)-1;  // MEAN operator whose channel sums the depthwise kernel in front of it has already put into d_pool8
-    // does the MEAN operator `mi` run as i8_segate_kernel (MEAN -> FC -> FC in one launch)?
-    auto segate_fused = [&](size_t mi) {
-        if (mi + 2 >= op_end) return false;
-        const OpRec& o = m->ops[mi];
-        const OpRec& f1 = m->ops[mi + 1];
-        const OpRec& f2 = m->ops[mi + 2];
-        const int* p = o.p;
-        return o.kind == BN_OP_I8_MEAN && p[BN_OP_TAIL_TAG] == BN_SEGATE_HEAD && bn::g_opt.i8_strip && same_path(o, f1) && same_path(o, f2) &&
-               f1.kind == BN_OP_I8_FC && f2.kind == BN_OP_I8_FC && f1.p[BN_OP_TAIL_TAG] == BN_SEGATE_COVERED && f2.p[BN_OP_TAIL_TAG] == BN_SEGATE_COVERED &&
-               f1.in0 == o.out && f2.in0 == f1.out && f1.p[0] == p[1] && f2.p[0] == f1.p[1] && f2.p[1] == p[1] && p[1] % 4 == 0 && f2.out != o.in0;
-    };
-    size_t scale_done = (size_t)-1;  // 1x1 convolution that already ran with the squeeze-excite MUL in front of it applied on load
-    auto dwpw8_args = [&](const OpRec& d, size_t di) {
-        bn::DwPw8Args a{};
-        const int* q = d.p;
-        a.x = (const int8_t*)slot_ptr(d.in0);
-        a.res = q[18] ? (const int8_t*)slot_ptr(d.in1) : nullptr;
-        a.y = (int8_t*)slot_ptr(d.out);
-        a.dw_w = (const int8_t*)m->tensor(d.t[0]);
-        a.dw_b = (const int32_t*)m->tensor(d.t[1]);
-        a.dw_mult = (const int32_t*)m->tensor(d.t[2]);
-        a.dw_shift = (const int32_t*)m->tensor(d.t[3]);
-        a.pw_w = (const int8_t*)m->tensor(d.t[4]);
-        a.pw_b = (const int32_t*)m->tensor(d.t[5]);
-        a.pw_mult = (const int32_t*)m->tensor(d.t[6]);
-        a.pw_shift = (const int32_t*)m->tensor(d.t[7]);
-        a.lut = q[34] ? (const int8_t*)m->tensor(d.t[8]) : nullptr;
-        a.B = B; a.H = q[0]; a.W = q[1]; a.Cin = q[2]; a.sh = q[3]; a.sw = q[4]; a.OH = q[6]; a.OW = q[7];
-        a.pt = q[8]; a.pl = q[9]; a.dw_zp_in = q[10]; a.dw_zp_out = q[11]; a.dw_amin = q[12]; a.dw_amax = q[13];
-        a.Cout = q[14]; a.pw_zp_out = q[15]; a.pw_amin = q[16]; a.pw_amax = q[17];
-        a.add = bn::I8AddParams{q[18], q[19], q[20], q[21], q[22], q[23], q[24], q[25], q[26], q[27], q[28]};
-        a.has_dw = q[29]; a.transposed = q[30]; a.TH = q[31]; a.TW = q[32]; a.NB = q[33];
-        a.rq_right = m->rq_right[di];
-        a.add_tab = (q[18] && !q[29] && d.t[10] >= 0) ? (const int8_t*)m->tensor(d.t[10]) : nullptr;
-        return a;
-    };
-    int emb_written = 0;   // marked operators that stored the embedding in this call (exactly one runs per path)
-    auto emb_for = [&](const OpRec& o) -> void* { return (d_emb && o.p[BN_OP_EMB_TAG] == BN_EMB_OP) ? d_emb : nullptr; };
-    m->out_valid.resize(m->ops.size());
-    for (size_t oi = op_begin; oi < op_end; ++oi) m->out_valid[oi] = 0;
-    if (op_begin == 0) m->slot_valid.assign(m->d_slots.size(), 0);
-    for (size_t oi = op_begin; oi < op_end; ++oi) {
-        const OpRec& o = m->ops[oi];
-        const int* p = o.p;
-        if (p[BN_OP_PATH] != BN_PATH_BOTH && p[BN_OP_PATH] != mode) continue;
-        if (oi == front2_done || oi == pwdw_done || oi == pwdw_head_done || oi == scale_done || oi == segate_done[0] || oi == segate_done[1]) continue;  // ran inside a preceding operator's kernel
-        if (p[BN_OP_TAIL_TAG] == BN_MID_COVERED && mid_on) continue;    // the fused stage-2 chain runs these blocks
-        if (p[BN_OP_TAIL_TAG] == BN_MID_OP && !(mid_on && m->mid_ok[oi])) continue;
-        if (p[BN_OP_TAIL_TAG] == BN_TAIL_COVERED && tail_on) continue;  // the fused tail operator runs these blocks
-        if (p[BN_OP_TAIL_TAG] == BN_TAIL_OP && !(tail_on && m->tail_ok[oi])) continue;
-        ProfScope prof(m, (int)oi, s);
-        m->out_valid[oi] = 1;  // (a fused kernel that keeps this operator's map on chip clears it again and marks the partner it wrote)
-        auto mark_slot = [&](int sid, int v) {
-            if (sid >= 0 && (size_t)sid < m->slot_valid.size()) m->slot_valid[sid] = (uint8_t)v;
-        };
-        mark_slot(o.out, 1);
-        auto fused_into = [&](size_t partner) {
-            m->out_valid[oi] = 0;
-            mark_slot(o.out, 0);
-            m->out_valid[partner] = 1;
-            mark_slot(m->ops[partner].out, 1);
-        };
-        char* in0 = slot_ptr(o.in0);
-        char* in1 = slot_ptr(o.in1);
-        char* out = slot_ptr(o.out);
-        const float* mm = (o.in0 == BN_SLOT_INPUT) ? d_minmax : nullptr;
-        switch (o.kind) {
-            case BN_OP_F32_MEL: {
-                if (p[4]) bn::launch_u32_fill((uint32_t*)m->d_smax, 0u, B, s);
-                bn::launch_f32_mel((const float*)in0, mm, (float*)out, m->d_smax, B, p[0], p[1], p[2],
-                                   (const float*)m->tensor(o.t[0]), (const int*)m->tensor(o.t[1]),
-                                   (const float*)m->tensor(o.t[2]), p[3], p[4], s);
-                break;
-            }
-            case BN_OP_F32_STFTMEL: {
-                bn::launch_minmax_init(m->d_minmax, B, s);
-                if (!bn::launch_stft512_mel(m->ctx->tables, d_audio, B, T, hop, p[1], (float*)out, p[2],
-                                            (const float*)m->tensor(o.t[0]), (const int*)m->tensor(o.t[1]), m->d_minmax, s))
-                    return fail(BN_ERR_UNSUPPORTED, "the fused STFT+mel kernel takes at most 128 mel bins (got %d)", p[2]);
-                break;
-            }
-            case BN_OP_F32_MELFIN:
-                bn::launch_f32_melfin((const float*)in0, m->d_minmax, (float*)out, B, p[0], p[1], (const float*)m->tensor(o.t[0]),
-                                      (const float*)m->tensor(o.t[2]), p[2], p[3], s);
-                break;
-            case BN_OP_F32_RAWFE:
-                bn::launch_f32_rawfe((const float*)in0, (float*)out, B, p[0], p[1], p[2], p[3], p[4], (const float*)m->tensor(o.t[0]),
-                                     (const float*)m->tensor(o.t[1]), (const float*)m->tensor(o.t[2]), p[5], s);
-                break;
-            case BN_OP_F32_MAG:
-                bn::launch_f32_mag((float*)out, m->d_smax, B, p[0], p[1], (const float*)m->tensor(o.t[2]), p[2], s);
-                break;
-            case BN_OP_F32_STEM:
-                if (p[BN_OP_TAIL_TAG] == BN_PWDW_STEM && bn::g_opt.f32_pwdw && bn::g_opt.f32_strip && oi + 2 < op_end) {
-                    // stem -> expand 1x1 -> depthwise 3x3 as ONE kernel: neither the stem map nor the expanded map is written
-                    const OpRec& e = m->ops[oi + 1];
-                    const OpRec& d = m->ops[oi + 2];
-                    const int* q = d.p;
-                    if (same_path(o, e) && same_path(o, d) &&
-                        e.kind == BN_OP_F32_DWPW && e.p[BN_OP_TAIL_TAG] == BN_PWDW_HEAD && d.kind == BN_OP_F32_DW && q[BN_OP_TAIL_TAG] == BN_PWDW_COVERED &&
-                        e.in0 == o.out && d.in0 == e.out && d.out != o.in0 && d.out != o.out && d.out != e.out && e.p[0] == p[6] && e.p[1] == p[7] &&
-                        e.p[2] == p[2]) {
-                        const bn::DwPwArgs ea = dwpw_args(e);
-                        const bn::F32StemIn st{(const float*)in0, (const float*)m->tensor(o.t[0]), (const float*)m->tensor(o.t[1]), p[0], p[1], p[3], p[4],
-                                               p[8], p[9], p[5]};
-                        if (ea.Cin <= 32 && bn::f32_pwdw_supported(ea, q[0], q[1], q[2], q[3], q[4], q[6], q[7]) &&  // (the stem on the matrix cores feeds at most two channel tiles)
-                            bn::launch_f32_pwdw(ea, (const float*)m->tensor(d.t[0]), (const float*)m->tensor(d.t[1]), (float*)slot_ptr(d.out), q[3], q[6], q[7],
-                                                q[8], q[9], q[5], &st, gap_target(oi + 2), s)) {
-                            pwdw_head_done = oi + 1;
-                            pwdw_done = oi + 2;
-                            fused_into(oi + 2);
-                            gap_for = cand_for;
-                            gap_R = cand_R;
-                            break;
-                        }
-                    }
-                }
-                bn::launch_f32_stem((const float*)in0, (float*)out, B, p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7],
-                                    p[8], p[9], (const float*)m->tensor(o.t[0]), (const float*)m->tensor(o.t[1]), s);
-                break;
-            case BN_OP_F32_DW: {
-                // a squeeze-excite gate right behind the stage pools per-strip channel sums written by the depthwise kernel (as behind fused pairs)
-                float* gp = nullptr;
-                int R = 0;
-                if (bn::g_opt.f32_pwdw >= 2 && m->d_gap_part && oi + 1 < op_end) {
-                    const OpRec& g = m->ops[oi + 1];
-                    R = bn::f32_dw_stream_strips(B, p[2], p[6], p[7]);
-                    if (g.kind == BN_OP_F32_SEGATE && g.in0 == o.out && g.p[1] == p[2] && g.p[0] == p[6] * p[7] && (size_t)R * p[2] <= m->gap_part_elems &&
-                        (g.p[BN_OP_PATH] == BN_PATH_BOTH || g.p[BN_OP_PATH] == mode))
-                        gp = m->d_gap_part;
-                }
-                if (bn::launch_f32_dw((const float*)in0, (float*)out, B, p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], p[9],
-                                      (const float*)m->tensor(o.t[0]), (const float*)m->tensor(o.t[1]), gp, s) && gp) {
-                    gap_for = oi + 1;
-                    gap_R = R;
-                }
-                break;
-            }
-            case BN_OP_F32_PW:
-                bn::launch_f32_pw((const float*)in0, p[4] ? (const float*)in1 : nullptr,
-                                  p[5] ? (const float*)slot_ptr(p[6]) : nullptr, (float*)out, B, p[0], p[1], p[2], p[3],
-                                  (const float*)m->tensor(o.t[0]), (const float*)m->tensor(o.t[1]), s);
-                break;
-            case BN_OP_F32_DWPW: {
-                const bn::DwPwArgs a = dwpw_args(o);
-                if (p[BN_OP_TAIL_TAG] == BN_PWDW_HEAD && bn::g_opt.f32_pwdw && bn::g_opt.f32_strip && oi + 1 < op_end) {
-                    // inverted-residual block: the expand convolution runs inside the depthwise kernel behind it (the expanded map stays in LDS)
-                    const OpRec& d = m->ops[oi + 1];
-                    const int* q = d.p;
-                    if (same_path(o, d) && d.kind == BN_OP_F32_DW && q[BN_OP_TAIL_TAG] == BN_PWDW_COVERED && d.in0 == o.out && d.out != o.in0 && d.out != o.out &&
-                        bn::f32_pwdw_supported(a, q[0], q[1], q[2], q[3], q[4], q[6], q[7]) &&
-                        bn::launch_f32_pwdw(a, (const float*)m->tensor(d.t[0]), (const float*)m->tensor(d.t[1]), (float*)slot_ptr(d.out), q[3], q[6], q[7], q[8],
-                                            q[9], q[5], nullptr, gap_target(oi + 1), s)) {
-                        pwdw_done = oi + 1;
-                        fused_into(oi + 1);
-                        gap_for = cand_for;
-                        gap_R = cand_R;
-                        break;
-                    }
-                }
-                if (!bn::f32_dwpw_supported(a.Cin, a.Cout) || (a.has_dw && a.Cin % 16) || a.TH * a.TW * a.NB != 64 || a.OH % a.TH || a.OW % a.TW)
-                    return fail(BN_ERR_FORMAT, "operator %zu: unsupported fused block geometry", oi);
-                bn::launch_f32_dwpw(a, s);
-                break;
-            }
-            case BN_OP_F32_FRONT:
-                if (!bn::f32_front_supported(p[0], p[1], p[2], p[3], p[4], p[5]))
-                    return fail(BN_ERR_FORMAT, "operator %zu: unsupported front-block geometry", oi);
-                if (p[BN_OP_TAIL_TAG] == BN_FRONT2_HEAD && bn::g_opt.f32_front2 && bn::g_opt.f32_strip && bn::g_opt.f32_front_staged &&
-                    p[BN_OP_FRONT2_DIST] > 0 && oi + (size_t)p[BN_OP_FRONT2_DIST] < op_end) {
-                    // front block + the residual block behind it as one kernel: the 32-channel map between them stays in LDS
-                    const OpRec& d = m->ops[oi + (size_t)p[BN_OP_FRONT2_DIST]];
-                    if (same_path(o, d) && d.kind == BN_OP_F32_DWPW && d.p[BN_OP_TAIL_TAG] == BN_FRONT2_COVERED && d.in0 == o.out && d.out != o.in0) {  // (never in place)
-                        const bn::F32FrontStripArgs f{(const float*)in0, nullptr,
-                                                      (const float*)m->tensor(o.t[0]), (const float*)m->tensor(o.t[1]),
-                                                      (const float*)m->tensor(o.t[2]), (const float*)m->tensor(o.t[3]),
-                                                      (const float*)m->tensor(o.t[4]), (const float*)m->tensor(o.t[5]),
-                                                      p[9] ? m->d_minmax : nullptr, (const float*)m->tensor(o.t[6]),
-                                                      (const float*)m->tensor(o.t[7]), B, p[0], p[1], p[4], p[5], 0, p[6], p[7], p[8], p[10]};
-                        const bn::DwPwArgs da = dwpw_args(d);
-                        if (p[2] == 16 && p[3] == 32 && bn::f32_front2_supported(f, da) && bn::launch_f32_front2(f, da, s)) {
-                            front2_done = oi + (size_t)p[BN_OP_FRONT2_DIST];
-                            fused_into(front2_done);
-                            break;
-                        }
-                    }
-                }
-                bn::launch_f32_front((const float*)in0, (float*)out, B, p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8],
-                                     (const float*)m->tensor(o.t[0]), (const float*)m->tensor(o.t[1]),
-                                     (const float*)m->tensor(o.t[2]), (const float*)m->tensor(o.t[3]),
-                                     (const float*)m->tensor(o.t[4]), (const float*)m->tensor(o.t[5]), p[9] ? m->d_minmax : nullptr,
-                                     (const float*)m->tensor(o.t[6]), (const float*)m->tensor(o.t[7]), p[10], s);
-                break;
-            case BN_OP_F32_GAPDENSE:
-                bn::launch_f32_gap_dense((const float*)in0, (float*)out, d_logits, B, p[0], p[1], p[2], p[3],
-                                         (const float*)m->tensor(o.t[0]), (const float*)m->tensor(o.t[1]), s, (float*)emb_for(o));
-                emb_written += emb_for(o) != nullptr;
-                break;
-            case BN_OP_F32_SEGATE:
-                bn::launch_f32_segate((const float*)in0, (float*)out, B, p[0], p[1], p[2], (const float*)m->tensor(o.t[0]), (const float*)m->tensor(o.t[1]),
-                                      oi == gap_for ? m->d_gap_part : nullptr, gap_R, s);
-                break;
-            case BN_OP_F32_SCALE:
-                bn::launch_f32_scale((const float*)in0, (const float*)in1, (float*)out, B, p[0], p[1], s);
-                break;
-            case BN_OP_F32_GAP:
-                bn::launch_f32_gap((const float*)in0, (float*)out, B, p[0], p[1], s);
-                break;
-            case BN_OP_F32_ATTNPOOL:
-                bn::launch_f32_attnpool((const float*)in0, (float*)out, B, p[0], p[1], (const float*)m->tensor(o.t[0]),
-                                        s);
-                break;
-            case BN_OP_F32_DENSE:
-                bn::launch_f32_dense((const float*)in0, (float*)out, d_logits, B, p[0], p[1], p[2],
-                                     (const float*)m->tensor(o.t[0]), (const float*)m->tensor(o.t[1]), s);
-                break;
-            case BN_OP_I8_QUANT:
-                bn::launch_i8_quant((const float*)in0, mm, (int8_t*)out, B, p[0], p[1], p[2], p[3], p[4], o.f[0], s);
-                break;
-            case BN_OP_I8_MEL:
-                bn::launch_i8_mel((const int8_t*)in0, (int8_t*)out, B, p[0], p[1], p[2], p[3], p[4], p[5],
-                                  (const int8_t*)m->tensor(o.t[0]), (const int32_t*)m->tensor(o.t[1]),
-                                  (const int32_t*)m->tensor(o.t[2]), (const int32_t*)m->tensor(o.t[3]),
-                                  p[6] ? (const int8_t*)m->tensor(o.t[4]) : nullptr, s);
-                break;
-            case BN_OP_I8_STEM:
-            case BN_OP_I8_DW: {
-                bn::I8ConvGeom g{p[0], p[1], p[2], p[3], p[4], p[6], p[7], p[8], p[9], p[10], p[11], p[12], p[13]};
-                g.rq_right = m->rq_right[oi];
-                if (o.kind == BN_OP_I8_DW) {  // row-streaming form (three loads per input row instead of nine per output) where the shape allows
-                    // ... which also adds up what it stores when the squeeze-excite gate's MEAN is the next operator (integer sums: bit-identical)
-                    int32_t* pool = nullptr;
-                    if (bn::g_opt.i8_dw_pool && m->d_pool8 && oi + 1 < op_end && segate_fused(oi + 1)) {
-                        const OpRec& mo = m->ops[oi + 1];
-                        if (same_path(o, mo) && mo.in0 == o.out && mo.p[1] == p[2] && mo.p[0] == p[6] * p[7] && (size_t)p[2] <= m->pool8_C) pool = m->d_pool8;
-                    }
-                    if (bn::launch_i8_dw_stream((const int8_t*)in0, (int8_t*)out, B, g, (const int8_t*)m->tensor(o.t[0]), (const int32_t*)m->tensor(o.t[1]),
-                                                (const int32_t*)m->tensor(o.t[2]), (const int32_t*)m->tensor(o.t[3]), s, pool)) {
-                        if (pool) pool8_for = oi + 1;
-                        break;
-                    }
-                }
-                if (o.kind == BN_OP_I8_STEM &&
-                    bn::launch_i8_stem_stream((const int8_t*)in0, (int8_t*)out, B, g, (const int8_t*)m->tensor(o.t[0]), (const int32_t*)m->tensor(o.t[1]),
-                                              (const int32_t*)m->tensor(o.t[2]), (const int32_t*)m->tensor(o.t[3]), s))
-                    break;
-                auto fn = o.kind == BN_OP_I8_STEM ? bn::launch_i8_stem : bn::launch_i8_dw;
-                fn((const int8_t*)in0, (int8_t*)out, B, g, (const int8_t*)m->tensor(o.t[0]),
-                   (const int32_t*)m->tensor(o.t[1]), (const int32_t*)m->tensor(o.t[2]),
-                   (const int32_t*)m->tensor(o.t[3]), s);
-                break;
-            }
-            case BN_OP_I8_PW: {
-                bn::I8AddParams add{p[6], p[7], p[8], p[9], p[10], p[11], p[12], p[13], p[14], p[15], p[16]};
-                bn::launch_i8_pw((const int8_t*)in0, (const int8_t*)in1, (int8_t*)out, B, p[0], p[1], p[2], p[3], p[4],
-                                 p[5], add, (const int8_t*)m->tensor(o.t[0]), (const int32_t*)m->tensor(o.t[1]),
-                                 (const int32_t*)m->tensor(o.t[2]), (const int32_t*)m->tensor(o.t[3]), s);
-                break;
-            }
-            case BN_OP_I8_DWPW: {
-                bn::DwPw8Args a = dwpw8_args(o, oi);
-                if (p[BN_OP_TAIL_TAG] == BN_PWDW8_HEAD && bn::g_opt.i8_pwdw && bn::g_opt.i8_strip && oi + 1 < op_end) {
-                    // inverted-residual block of an exported graph: expand convolution + depthwise stage as one kernel (the expanded map stays in LDS)
-                    const OpRec& d = m->ops[oi + 1];
-                    const int* q = d.p;
-                    if (same_path(o, d) && d.kind == BN_OP_I8_DW && q[BN_OP_TAIL_TAG] == BN_PWDW8_COVERED && d.in0 == o.out && d.out != o.in0 && d.out != o.out) {
-                        const bn::I8ConvGeom g{q[0], q[1], q[2], q[3], q[4], q[6], q[7], q[8], q[9], q[10], q[11], q[12], q[13]};
-                        if (bn::i8_pwdw_supported(a, g) &&
-                            bn::launch_i8_pwdw(a, g, (const int8_t*)m->tensor(d.t[0]), (const int32_t*)m->tensor(d.t[1]), (const int32_t*)m->tensor(d.t[2]),
-                                               (const int32_t*)m->tensor(d.t[3]), (int8_t*)slot_ptr(d.out), s)) {
-                            pwdw_done = oi + 1;
-                            fused_into(oi + 1);
-                            break;
-                        }
-                    }
-                }
-                if (a.transposed && p[36]) {  // QUANTIZE fused into the mel mixer: the input slot holds the float32 spectrogram
-                    a.qx = (const float*)in0;
-                    a.qminmax = mm;
-                    a.qscale = o.f[0];
-                    a.qzp = p[37];
-                    a.qfill = p[38];
-                    a.qF = p[5];
-                    a.qtiled = (m->spec_tiled_now && o.in0 == BN_SLOT_INPUT) ? 1 : 0;
-                    a.x = nullptr;
-                    if (!bn::i8_mel_mfma_supported(a)) return fail(BN_ERR_FORMAT, "operator %zu: fused QUANTIZE needs the mel-mixer kernel's geometry", oi);
-                    if (m->guard_now && a.qtiled && mm) {
-                        // audio path: list the bytes the float32 STFT leaves in doubt, recompute those elements in float64, run the
-                        // blocks whose bytes changed once more (bn_stft_exact.hip)
-                        a.qguard = guard_slice(m, slot_b0);
-                        a.qmode = 1;
-                        bn::launch_i8_dwpw(a, s);
-                        prof.end();  // (the operator's own launch; the float64 pass has its own profiling entry)
-                        ProfScope fix(m, (int)m->ops.size() + 2, s);
-                        bn::launch_stft_fix(m->ctx->tables, m->guard_audio, B, m->guard_T, m->guard_hop, a.W, (float*)in0, true, a.qguard, mm, a.qscale,
-                                            a.qzp, s);
-                        a.qmode = 2;
-                        bn::launch_i8_dwpw(a, s);
-                        break;
-                    }
-                }
-                // wide early layers: wave-autonomous strip kernel when the packer prepared its constant block
-                if (p[35] && o.t[9] >= 0 && bn::g_opt.i8_strip && a.has_dw && !a.transposed && a.sh == a.sw &&
-                    bn::i8_strip_supported(a.Cin, a.Cout, a.sh, a.OW, a.add.enabled != 0) &&
-                    (!a.add.enabled || (a.res == a.x && o.t[10] >= 0))) {
-                    const int off = a.add.enabled ? 128 : 0;
-                    bn::Strip8Args q{a.x, a.y, (const int32_t*)m->tensor(o.t[9]), B, a.H, a.W, a.OH, a.OW, 0, a.pt, a.pl,
-                                     a.dw_zp_in, a.dw_amin, a.dw_amax, a.pw_amin + off, a.pw_amax + off, a.pw_zp_out, a.add,
-                                     a.add.enabled ? (const int8_t*)m->tensor(o.t[10]) : nullptr};
-                    bn::launch_i8_strip(q, a.Cin, a.Cout, a.sh, s);
-                    break;
-                }
-                if (!bn::i8_dwpw_supported(a.Cin, a.Cout) || a.TH * a.TW * a.NB != 64 || a.OH % a.TH || a.OW % a.TW)
-                    return fail(BN_ERR_FORMAT, "operator %zu: unsupported fused INT8 block geometry", oi);
-                bn::launch_i8_dwpw(a, s);
-                break;
-            }
-            case BN_OP_I8_FRONT: {
-                bn::I8FrontParams q{};
-                q.stem_w = (const int8_t*)m->tensor(o.t[0]); q.stem_b = (const int32_t*)m->tensor(o.t[1]);
-                q.stem_mult = (const int32_t*)m->tensor(o.t[2]); q.stem_shift = (const int32_t*)m->tensor(o.t[3]);
-                q.dw_w = (const int8_t*)m->tensor(o.t[4]); q.dw_b = (const int32_t*)m->tensor(o.t[5]);
-                q.dw_mult = (const int32_t*)m->tensor(o.t[6]); q.dw_shift = (const int32_t*)m->tensor(o.t[7]);
-                q.pw_w = (const int8_t*)m->tensor(o.t[8]); q.pw_b = (const int32_t*)m->tensor(o.t[9]);
-                q.pw_mult = (const int32_t*)m->tensor(o.t[10]); q.pw_shift = (const int32_t*)m->tensor(o.t[11]);
-                q.H0 = p[0]; q.W0 = p[1]; q.C = p[2]; q.N = p[3]; q.OH = p[4]; q.OW = p[5];
-                q.stem_zp_in = p[6]; q.stem_zp_out = p[7]; q.stem_amin = p[8]; q.stem_amax = p[9];
-                q.dw_zp_out = p[10]; q.dw_amin = p[11]; q.dw_amax = p[12]; q.pw_zp_out = p[13]; q.pw_amin = p[14]; q.pw_amax = p[15];
-                q.rq_right = m->rq_right[oi];
-                if (p[16] && o.t[12] >= 0 && bn::g_opt.i8_strip && bn::i8_front_strip_supported(q.H0, q.W0, q.C, q.N, q.OH, q.OW)) {
-                    bn::FrontStrip8Args fa{(const int8_t*)in0, (int8_t*)out, (const int32_t*)m->tensor(o.t[12]), B, q.H0, q.W0, q.OH, q.OW, 0,
-                                           q.stem_zp_in, q.stem_amin, q.stem_amax, q.stem_zp_out, q.dw_amin, q.dw_amax, q.pw_amin, q.pw_amax};
-                    bn::launch_i8_front_strip(fa, s);
-                    break;
-                }
-                if (!bn::i8_front_supported(q.H0, q.W0, q.C, q.N, q.OH, q.OW))
-                    return fail(BN_ERR_FORMAT, "operator %zu: unsupported INT8 front-block geometry", oi);
-                bn::launch_i8_front(q, (const int8_t*)in0, (int8_t*)out, B, s);
-                break;
-            }
-            case BN_OP_I8_MID: {
-                bn::Tail2Args ma = bn::g_opt.i8_mid_split && m->mid_res_ok[oi] ? m->mids_res[oi] : m->mids[oi];
-                ma.x = (const int8_t*)in0;
-                ma.y = (int8_t*)out;
-                ma.cst = (const int32_t*)m->tensor(o.t[0]);
-                ma.B = B;
-                if (!bn::launch_i8_mid2(ma, s)) return fail(BN_ERR_DEVICE, "could not raise the LDS limit of the fused stage-2 kernel");
-                break;
-            }
-            case BN_OP_I8_TAIL: {
-                const bn::EmbOut eo{d_emb, emb_dtype == BN_EMB_F32, p[BN_OP_EMB_ZP], o.f[BN_OP_EMB_SCALE]};
-                if (bn::g_opt.i8_tail_mfdw && m->tail2_ok[oi]) {
-                    bn::Tail2Args t2 = m->tails2[oi];
-                    t2.x = (const int8_t*)in0;
-                    t2.scores = d_scores;
-                    t2.logits = d_logits;
-                    t2.cst = (const int32_t*)m->tensor(o.t[2]);
-                    t2.B = B;
-                    emb_written += emb_for(o) != nullptr;
-                    if (!bn::launch_i8_tail2(t2, s, emb_for(o) ? &eo : nullptr)) return fail(BN_ERR_DEVICE, "could not raise the LDS limit of the fused tail kernel");
-                    break;
-                }
-                bn::Tail8Args ta = m->tails[oi];
-                ta.x = (const int8_t*)in0;
-                ta.scores = d_scores;
-                ta.logits = d_logits;
-                ta.cst = (const int32_t*)m->tensor(o.t[0]);
-                ta.B = B;
-                emb_written += emb_for(o) != nullptr;
-                if (!bn::launch_i8_tail(ta, s, emb_for(o) ? &eo : nullptr)) return fail(BN_ERR_DEVICE, "could not raise the LDS limit of the fused tail kernel");
-                break;
-            }
-            case BN_OP_I8_MEAN:
-                if (segate_fused(oi)) {
-                    const OpRec& f1 = m->ops[oi + 1];
-                    const OpRec& f2 = m->ops[oi + 2];
-                    bn::launch_i8_segate((const int8_t*)in0, (int8_t*)slot_ptr(f2.out), B, p[0], p[1], p[2], p[3], p[4], p[5], f1.p[1], f1.p[2], f1.p[3], f1.p[4],
-                                         (const int8_t*)m->tensor(f1.t[0]), (const int32_t*)m->tensor(f1.t[1]), (const int32_t*)m->tensor(f1.t[2]),
-                                         (const int32_t*)m->tensor(f1.t[3]), f1.p[5] ? (const int8_t*)m->tensor(f1.t[4]) : nullptr, f2.p[2], f2.p[3], f2.p[4],
-                                         (const int8_t*)m->tensor(f2.t[0]), (const int32_t*)m->tensor(f2.t[1]), (const int32_t*)m->tensor(f2.t[2]),
-                                         (const int32_t*)m->tensor(f2.t[3]), f2.p[5] ? (const int8_t*)m->tensor(f2.t[4]) : nullptr, s,
-                                         oi == pool8_for ? m->d_pool8 : nullptr);
-                    segate_done[0] = oi + 1;
-                    segate_done[1] = oi + 2;
-                    fused_into(oi + 2);
-                    break;
-                }
-                bn::launch_i8_mean((const int8_t*)in0, (int8_t*)out, B, p[0], p[1], p[2], p[3], p[4], p[5], s);
-                break;
-            case BN_OP_I8_FC:
-                bn::launch_i8_fc((const int8_t*)in0, (int8_t*)out, B, p[0], p[1], p[2], p[3], p[4],
-                                 (const int8_t*)m->tensor(o.t[0]), (const int32_t*)m->tensor(o.t[1]),
-                                 (const int32_t*)m->tensor(o.t[2]), (const int32_t*)m->tensor(o.t[3]),
-                                 p[5] ? (const int8_t*)m->tensor(o.t[4]) : nullptr, s);
-                break;
-            case BN_OP_I8_ATTNPOOL:
-                if (!bn::launch_i8_attnpool((const int8_t*)in0, (int8_t*)out, B, p, (const int8_t*)m->tensor(o.t[0]), (const int32_t*)m->tensor(o.t[1]), s))
-                    return fail(BN_ERR_FORMAT, "operator %zu: attention pooling geometry", oi);
-                break;
-            case BN_OP_I8_SCALE:
-                if (p[BN_OP_TAIL_TAG] == BN_SCALE_HEAD && bn::g_opt.i8_strip && oi + 1 < op_end) {
-                    // the projection convolution behind the gate applies it while loading (the scaled map is never written)
-                    const OpRec& d = m->ops[oi + 1];
-                    if (same_path(o, d) && d.kind == BN_OP_I8_DWPW && d.p[BN_OP_TAIL_TAG] == BN_SCALE_COVERED && d.in0 == o.out && d.out != o.in0 && d.out != o.in1 &&
-                        d.p[2] == p[1] && d.p[6] * d.p[7] == p[0]) {
-                        bn::DwPw8Args a2 = dwpw8_args(d, oi + 1);
-                        a2.x = (const int8_t*)in0;
-                        a2.gate = (const int8_t*)in1;
-                        a2.g_zx = p[2]; a2.g_zg = p[3]; a2.g_mult = p[4]; a2.g_shift = p[5]; a2.g_zo = p[6]; a2.g_amin = p[7]; a2.g_amax = p[8];
-                        if (!a2.has_dw && !a2.transposed && bn::i8_pw_wave_takes(a2)) {
-                            bn::launch_i8_dwpw(a2, s);
-                            scale_done = oi + 1;
-                            fused_into(oi + 1);
-                            break;
-                        }
-                    }
-                }
-                bn::launch_i8_scale((const int8_t*)in0, (const int8_t*)in1, (int8_t*)out, B, p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], s);
-                break;
-            case BN_OP_I8_MAXNORM:
-                bn::launch_i8_maxnorm((const int8_t*)in0, (int8_t*)out, B, p[0], p[1], (const int8_t*)m->tensor(o.t[0]), (const int8_t*)m->tensor(o.t[1]),
-                                      p[2] ? (const int8_t*)m->tensor(o.t[2]) : nullptr, s);
-                break;
-            case BN_OP_I8_RAWFE:
-                bn::launch_i8_rawfe((const float*)in0, (int8_t*)out, B, p[0], p[1], p[2], p[3], p[4], o.f[0], p[5], p[6], p[7], p[8],
-                                    (const int8_t*)m->tensor(o.t[0]), (const int32_t*)m->tensor(o.t[1]), (const int32_t*)m->tensor(o.t[2]),
-                                    (const int32_t*)m->tensor(o.t[3]), p[9] ? (const int8_t*)m->tensor(o.t[4]) : nullptr, s);
-                break;
-            case BN_OP_I8_HEAD:
-                if (p[4])  // float32 softmax behind DEQUANTIZE
-                    bn::launch_i8_head_softmax((const int8_t*)in0, d_scores, d_logits, B, p[0], p[1], o.f[0], o.f[2], s);
-                else
-                    bn::launch_i8_head((const int8_t*)in0, d_scores, d_logits, B, p[0], p[1], p[2], o.f[0], o.f[1],
-                                       p[3] ? (const int8_t*)m->tensor(o.t[0]) : nullptr, s);
-                break;
-            default:
-                return fail(BN_ERR_UNSUPPORTED, "plan operator %zu has unknown kind %d", oi, o.kind);
-        }
-        // unfused pooling in front of the head: its output slot holds the embedding — copy / dequantise it behind the operator
-        if (emb_for(o) && m->out_valid[oi] && (o.kind == BN_OP_I8_MEAN || o.kind == BN_OP_I8_ATTNPOOL || o.kind == BN_OP_F32_GAP || o.kind == BN_OP_F32_ATTNPOOL)) {
-            const bool src_i8 = o.kind == BN_OP_I8_MEAN || o.kind == BN_OP_I8_ATTNPOOL;
-            bn::launch_emb_store(out, src_i8, d_emb, emb_dtype == BN_EMB_F32, B, m->emb_dim, m->emb_scale, m->emb_zp, s);
-            ++emb_written;
-        }
-    }
-    HIP_TRY(hipGetLastError());
-    if (d_emb && op_end == m->ops.size() && emb_written != 1)
-        return fail(BN_ERR_UNSUPPORTED, "%d marked operators stored the embedding on this path (expected exactly one)", emb_written);
     return BN_OK;
 }
 
@@ -908,25 +243,9 @@ int bn_model_load(bn_ctx* ctx, const void* blob, size_t nbytes, bn_model** out) 
         delete m;
         return rc;
     }
-    // the embedding mark: only on the pooling operators in front of a head (and the fused kernels that pool on chip), all of one width / quantisation
-    for (size_t oi = 0; oi < m->ops.size(); ++oi) {
-        const OpRec& o = m->ops[oi];
-        if (o.p[BN_OP_EMB_TAG] != BN_EMB_OP) continue;
-        const int* p = o.p;
-        const int width = o.kind == BN_OP_I8_TAIL ? p[10] : (o.kind == BN_OP_I8_MEAN || o.kind == BN_OP_I8_ATTNPOOL || o.kind == BN_OP_F32_GAP ||
-                                                             o.kind == BN_OP_F32_ATTNPOOL || o.kind == BN_OP_F32_GAPDENSE) ? p[1] : -1;
-        const bool i8 = o.kind == BN_OP_I8_TAIL || o.kind == BN_OP_I8_MEAN || o.kind == BN_OP_I8_ATTNPOOL;
-        const float sc = i8 ? o.f[BN_OP_EMB_SCALE] : 1.0f;
-        const int zp = i8 ? p[BN_OP_EMB_ZP] : 0;
-        const bool same = m->emb_dim == 0 || (m->emb_dim == width && m->emb_scale == sc && m->emb_zp == zp);
-        if (width <= 0 || width % 4 || width != p[BN_OP_EMB_DIM] || i8 != (m->hdr.dtype == BN_DTYPE_I8) || !same || (i8 && !(sc > 0.0f)) ||
-            zp < -128 || zp > 127 || (o.kind != BN_OP_I8_TAIL && o.kind != BN_OP_F32_GAPDENSE && o.out < 0)) {
-            delete m;
-            return fail(BN_ERR_FORMAT, "operator %zu (kind %d): malformed embedding mark", oi, o.kind);
-        }
-        m->emb_dim = width;
-        m->emb_scale = sc;
-        m->emb_zp = zp;
+    if (int rc = bn::prepare_plan(m, blob)) {  // embedding mark, per-operator records, scratch sizes (bn_plan_run.hip)
+        delete m;
+        return rc;
     }
     const BlobHeader& h = m->hdr;
     const char* base = (const char*)blob;
@@ -936,105 +255,6 @@ int bn_model_load(bn_ctx* ctx, const void* blob, size_t nbytes, bn_model** out) 
             lo = t.offset < lo ? (size_t)t.offset : lo;
             hi = t.offset + t.nbytes > hi ? (size_t)(t.offset + t.nbytes) : hi;
         }
-    // fused tail operators: build the kernel arguments and the LDS plan from the descriptor table
-    m->tails.resize(h.n_ops);
-    m->tail_ok.assign(h.n_ops, 0);
-    m->tails2.resize(h.n_ops);
-    m->tail2_ok.assign(h.n_ops, 0);
-    m->mids.resize(h.n_ops);
-    m->mid_ok.assign(h.n_ops, 0);
-    m->mids_res.resize(h.n_ops);
-    m->mid_res_ok.assign(h.n_ops, 0);
-    for (size_t oi = 0; oi < m->ops.size(); ++oi) {
-        const OpRec& o = m->ops[oi];
-        if (o.kind != BN_OP_I8_MID) continue;
-        bn::Tail2Args& ma = m->mids[oi];
-        ma = bn::Tail2Args{};
-        const TensorRec& td = m->tensors[o.t[1]];
-        const TensorRec& tc = m->tensors[o.t[0]];
-        const bool ok = (td.nbytes & 3) == 0 && bn::tail2_plan((const int32_t*)(base + td.offset), (int)(td.nbytes / 4), o.p[5], ma, true) &&
-                        ma.L[0].H == o.p[6] && ma.L[0].W == o.p[7] && ma.L[0].Cin == o.p[8] && bn::tail2_const_words(ma, true) * 4 <= (long)tc.nbytes &&
-                        ma.L[o.p[5] - 1].OH * ma.L[o.p[5] - 1].OW == o.p[9] && ma.L[o.p[5] - 1].Cout == o.p[10];
-        m->mid_ok[oi] = ok;
-        m->mids_res[oi] = ma;
-        m->mid_res_ok[oi] = ok && bn::tail2_plan_resident(m->mids_res[oi]);
-        m->has_mid = m->has_mid || ok;
-    }
-    for (size_t oi = 0; oi < m->ops.size(); ++oi) {
-        const OpRec& o = m->ops[oi];
-        if (o.kind != BN_OP_I8_TAIL) continue;
-        bn::Tail8Args& ta = m->tails[oi];
-        ta = bn::Tail8Args{};
-        ta.NC = o.p[4];
-        ta.s_fc = o.f[0];
-        ta.s_head = o.f[1];
-        const TensorRec& td = m->tensors[o.t[1]];
-        const TensorRec& tc = m->tensors[o.t[0]];
-        const bool ok = (td.nbytes & 3) == 0 && bn::tail_plan((const int32_t*)(base + td.offset), (int)(td.nbytes / 4), o.p[5], ta) &&
-                        ta.L[0].H == o.p[6] && ta.L[0].W == o.p[7] && ta.L[0].Cin == o.p[8] && bn::tail_const_words(ta) * 4 <= (long)tc.nbytes;
-        m->tail_ok[oi] = ok;
-        m->has_tail = m->has_tail || ok;
-        // the second form's constants (t[2], t[3]) are optional; it only ever runs where the first form could (same coverage, same fallback)
-        if (ok && o.t[2] >= 0 && o.t[3] >= 0 && (size_t)o.t[2] < m->tensors.size() && (size_t)o.t[3] < m->tensors.size()) {
-            bn::Tail2Args& t2 = m->tails2[oi];
-            t2 = bn::Tail2Args{};
-            t2.NC = o.p[4];
-            t2.s_fc = o.f[0];
-            t2.s_head = o.f[1];
-            const TensorRec& td2 = m->tensors[o.t[3]];
-            const TensorRec& tc2 = m->tensors[o.t[2]];
-            m->tail2_ok[oi] = (td2.nbytes & 3) == 0 && bn::tail2_plan((const int32_t*)(base + td2.offset), (int)(td2.nbytes / 4), o.p[5], t2) &&
-                              t2.L[0].H == o.p[6] && t2.L[0].W == o.p[7] && t2.L[0].Cin == o.p[8] && bn::tail2_const_words(t2) * 4 <= (long)tc2.nbytes;
-        }
-    }
-    // INT8 blocks: can every requantisation of the operator take the branch-free right-shift form?
-    m->rq_right.assign(h.n_ops, 0);
-    for (const OpRec& o : m->ops)
-        if (o.in0 == BN_SLOT_INPUT) {
-            m->spec_tiled_ok = o.kind == BN_OP_I8_DWPW && o.p[36] && o.p[30] && o.p[1] % 64 == 0;
-            m->guard_form_ok = m->spec_tiled_ok && o.p[37] == -128;
-        }
-    for (size_t oi = 0; oi < m->ops.size(); ++oi) {
-        const OpRec& o = m->ops[oi];
-        auto all_right = [&](int t_mult, int t_shift) {
-            if (t_mult < 0 || t_shift < 0) return false;
-            const TensorRec& tm = m->tensors[t_mult];
-            const TensorRec& ts = m->tensors[t_shift];
-            const int32_t* pm = (const int32_t*)(base + tm.offset);
-            const int32_t* ps = (const int32_t*)(base + ts.offset);
-            if ((tm.nbytes | ts.nbytes) & 3) return false;
-            for (size_t i = 0; i < tm.nbytes / 4; ++i)
-                if (pm[i] < 0) return false;
-            for (size_t i = 0; i < ts.nbytes / 4; ++i)
-                if (ps[i] >= 0) return false;
-            return true;
-        };
-        if (o.kind == BN_OP_I8_DWPW) {
-            const int* p = o.p;
-            const bool pw_ok = all_right(o.t[6], o.t[7]);  // (bit 2: the pointwise stage alone, whatever the ADD behind it looks like)
-            bool ok = pw_ok && (!p[29] || all_right(o.t[2], o.t[3]));
-            if (p[18]) ok = ok && p[20] >= 0 && p[21] < 0 && p[22] >= 0 && p[23] < 0 && p[24] >= 0 && p[25] < 0;  // ADD: m1 s1 m2 s2 mo so
-            // bit 1: every pointwise shift lies in [-20, -1] — the 64-bit addend of the one-multiply-add requantisation (i8_pw_lds_kernel) cannot overflow
-            bool narrow = pw_ok && o.t[7] >= 0;
-            if (narrow) {
-                const TensorRec& ts = m->tensors[o.t[7]];
-                const int32_t* ps = (const int32_t*)(base + ts.offset);
-                for (size_t i = 0; i < ts.nbytes / 4; ++i) narrow = narrow && ps[i] >= -20;
-            }
-            m->rq_right[oi] = (ok ? 1 : 0) | (narrow ? 2 : 0) | (pw_ok ? 4 : 0);
-        } else if (o.kind == BN_OP_I8_DW || o.kind == BN_OP_I8_STEM) {
-            // bit 0: multipliers >= 0, right shifts; bit 1: every shift >= -20 (the 64-bit addend of the one-multiply-add form cannot overflow)
-            bool narrow = o.t[3] >= 0;
-            if (narrow) {
-                const TensorRec& ts = m->tensors[o.t[3]];
-                const int32_t* ps = (const int32_t*)(base + ts.offset);
-                for (size_t i = 0; i < ts.nbytes / 4; ++i) narrow = narrow && ps[i] >= -20;
-            }
-            m->rq_right[oi] = (all_right(o.t[2], o.t[3]) ? 1 : 0) | (narrow ? 2 : 0);
-        } else if (o.kind == BN_OP_I8_FRONT) {
-            m->rq_right[oi] = all_right(o.t[2], o.t[3]) && all_right(o.t[6], o.t[7]) && all_right(o.t[10], o.t[11]);
-        }
-    }
     auto cleanup_fail = [&](int code) {
         bn_model_free(m);
         return code;
@@ -1086,25 +306,6 @@ int bn_model_load(bn_ctx* ctx, const void* blob, size_t nbytes, bn_model** out) 
         hipMalloc(&m->d_smax, mb * sizeof(float)) != hipSuccess)
         return cleanup_fail(fail(BN_ERR_NOMEM, "hipMalloc of reduction scratch failed"));
     m->workspace_bytes += mb * 3 * sizeof(float);
-    for (size_t i = 0; i + 1 < m->ops.size(); ++i)  // row-block channel sums of fused inverted-residual pairs (largest pair decides)
-        if (m->ops[i].kind == BN_OP_F32_DWPW && m->ops[i].p[BN_OP_TAIL_TAG] == BN_PWDW_HEAD && m->ops[i + 1].kind == BN_OP_F32_DW) {
-            const int* q = m->ops[i + 1].p;
-            const int rb = bn::f32_pwdw_rows(q[6]);
-            const size_t need = (size_t)((q[6] + rb - 1) / rb) * (size_t)q[2];
-            if (need > m->gap_part_elems) m->gap_part_elems = need;
-        }
-    for (size_t i = 0; i + 1 < m->ops.size(); ++i)  // stand-alone depthwise stage -> gate: one partial sum per strip (at most OH / 4 row blocks)
-        if (m->ops[i].kind == BN_OP_F32_DW && m->ops[i + 1].kind == BN_OP_F32_SEGATE && m->ops[i + 1].in0 == m->ops[i].out) {
-            const int* q = m->ops[i].p;
-            int cq = 16;
-            while ((q[2] / 4) % cq) cq >>= 1;
-            const int ncol = 64 / cq;
-            const size_t need = (size_t)((q[7] + ncol - 1) / ncol) * (size_t)((q[6] + 3) / 4) * (size_t)q[2];
-            if (need > m->gap_part_elems) m->gap_part_elems = need;
-        }
-    for (size_t i = 0; i + 1 < m->ops.size(); ++i)  // INT8 depthwise stage -> MEAN of a squeeze-excite gate: channel sums taken on the way out
-        if (m->ops[i].kind == BN_OP_I8_DW && m->ops[i + 1].kind == BN_OP_I8_MEAN && m->ops[i + 1].in0 == m->ops[i].out && m->ops[i + 1].p[1] == m->ops[i].p[2])
-            if ((size_t)m->ops[i].p[2] > m->pool8_C) m->pool8_C = (size_t)m->ops[i].p[2];
     if (m->pool8_C) {
         if (hipMalloc(&m->d_pool8, mb * m->pool8_C * sizeof(int32_t)) != hipSuccess)
             return cleanup_fail(fail(BN_ERR_NOMEM, "hipMalloc of pooling scratch failed"));
@@ -1296,10 +497,9 @@ static int forward_impl(bn_model* m, const float* d_input, const float* d_minmax
     const size_t in_stride = m->hdr.input_elems, C = m->hdr.num_classes;
     for (int b0 = 0; b0 < B; b0 += kMaxGridBatch) {
         const int nb = B - b0 < kMaxGridBatch ? B - b0 : kMaxGridBatch;
-        if (int rc = run_plan(m, d_input + b0 * in_stride, d_minmax ? d_minmax + 2 * (size_t)b0 : nullptr, nb,
-                              d_scores + b0 * C, d_logits ? d_logits + b0 * C : nullptr, d_emb ? (char*)d_emb + b0 * D * esize : nullptr,
-                              emb_dtype, s))
-            return rc;
+        const bn::RunArgs ra{d_input + b0 * in_stride, d_minmax ? d_minmax + 2 * (size_t)b0 : nullptr, nb, d_scores + b0 * C,
+                             d_logits ? d_logits + b0 * C : nullptr, d_emb ? (char*)d_emb + b0 * D * esize : nullptr, emb_dtype, s};
+        if (int rc = bn::run_plan(m, ra)) return rc;
     }
     return BN_OK;
 }
@@ -1327,9 +527,9 @@ static int infer_audio_impl(bn_model* m, const float* d_audio, int B, int T, int
         const size_t C = m->hdr.num_classes;
         for (int b0 = 0; b0 < B; b0 += kMaxGridBatch) {
             const int nb = B - b0 < kMaxGridBatch ? B - b0 : kMaxGridBatch;
-            if (int rc = run_plan(m, nullptr, nullptr, nb, d_scores + b0 * C, d_logits ? d_logits + b0 * C : nullptr,
-                                  d_emb ? (char*)d_emb + b0 * D * esize : nullptr, emb_dtype, (hipStream_t)stream, d_audio + (size_t)b0 * T, T, hop))
-                return rc;
+            const bn::RunArgs ra{nullptr, nullptr, nb, d_scores + b0 * C, d_logits ? d_logits + b0 * C : nullptr,
+                                 d_emb ? (char*)d_emb + b0 * D * esize : nullptr, emb_dtype, (hipStream_t)stream, d_audio + (size_t)b0 * T, T, hop};
+            if (int rc = bn::run_plan(m, ra)) return rc;
         }
         return BN_OK;
     }
@@ -1348,7 +548,6 @@ static int infer_audio_impl(bn_model* m, const float* d_audio, int B, int T, int
     const bool guarded = exact_opt == 2 && tiled && m->d_guard && !bn::g_opt.i8_mel_generic && W % 16 == 0 && W <= 1024;
     // (Sub-batching the STFT -> first operator pair for the Infinity Cache and a two-stream skewed schedule were measured and removed:
     // slower / no gain)
-    m->spec_tiled_now = tiled;
     int rc = BN_OK;
     if (guarded) {
         // profiling entries: n_ops = the float32 STFT kernel, n_ops + 1 = exact min / max, n_ops + 2 = the float64 pass behind the first operator
@@ -1356,7 +555,7 @@ static int infer_audio_impl(bn_model* m, const float* d_audio, int B, int T, int
         if (m->d_audit) HIP_TRY(hipMemsetAsync(m->d_audit, 0, 2 * sizeof(int), s));
         for (int b0 = 0; rc == BN_OK && b0 < B; b0 += kMaxGridBatch) {
             const int nb = B - b0 < kMaxGridBatch ? B - b0 : kMaxGridBatch;
-            bn::StftGuard g = guard_slice(m, (size_t)b0);
+            bn::StftGuard g = bn::guard_slice(m, (size_t)b0, bn::SpecStage{tiled, true, d_audio + (size_t)b0 * T, T, hop});
             {
                 ProfScope prof(m, (int)m->ops.size(), s);
                 bn::launch_stft512(m->ctx->tables, d_audio + (size_t)b0 * T, nb, T, hop, W, m->d_spec + b0 * in_stride, m->d_minmax + 2 * (size_t)b0, s,
@@ -1373,17 +572,14 @@ static int infer_audio_impl(bn_model* m, const float* d_audio, int B, int T, int
     if (rc == BN_OK) {
         for (int b0 = 0; b0 < B; b0 += kMaxGridBatch) {
             const int nb = B - b0 < kMaxGridBatch ? B - b0 : kMaxGridBatch;
-            m->guard_now = guarded;
-            m->guard_audio = d_audio + (size_t)b0 * T;
-            m->guard_T = T;
-            m->guard_hop = hop;
-            rc = run_plan(m, m->d_spec + b0 * in_stride, m->d_minmax + 2 * (size_t)b0, nb, d_scores + b0 * C, d_logits ? d_logits + b0 * C : nullptr,
-                          d_emb ? (char*)d_emb + b0 * D * esize : nullptr, emb_dtype, s, nullptr, 0, 0, 0, (size_t)-1, (size_t)b0);
+            bn::RunArgs ra{m->d_spec + b0 * in_stride, m->d_minmax + 2 * (size_t)b0, nb, d_scores + b0 * C, d_logits ? d_logits + b0 * C : nullptr,
+                           d_emb ? (char*)d_emb + b0 * D * esize : nullptr, emb_dtype, s};
+            ra.slot_b0 = (size_t)b0;
+            ra.spec = bn::SpecStage{tiled, guarded, d_audio + (size_t)b0 * T, T, hop};
+            rc = bn::run_plan(m, ra);
             if (rc != BN_OK) break;
         }
     }
-    m->guard_now = false;
-    m->spec_tiled_now = false;
     m->last_tiled = tiled;
     m->last_B = rc == BN_OK ? B : 0;
     return rc;
@@ -1396,9 +592,10 @@ int bn_debug_tail_form(const bn_model* m, int* form, int* lds_bytes) {
     *form = 0;
     *lds_bytes = 0;
     for (size_t oi = 0; oi < m->ops.size(); ++oi) {
-        if (m->ops[oi].kind != BN_OP_I8_TAIL || !m->tail_ok[oi]) continue;
-        *form = m->tail2_ok[oi] ? 2 : 1;
-        *lds_bytes = m->tail2_ok[oi] ? m->tails2[oi].lds_bytes : m->tails[oi].lds_bytes;
+        if (m->ops[oi].kind != BN_OP_I8_TAIL || !m->prep[oi]->ok) continue;
+        const bn::OpPrep& pr = *m->prep[oi];
+        *form = pr.alt_ok ? 2 : 1;
+        *lds_bytes = pr.alt_ok ? pr.chain.lds_bytes : pr.tail.lds_bytes;
     }
     return BN_OK;
 }
@@ -1408,9 +605,9 @@ int bn_debug_mid_form(const bn_model* m, int* form, int* lds_bytes) {
     *form = 0;
     *lds_bytes = 0;
     for (size_t oi = 0; oi < m->ops.size(); ++oi)
-        if (m->ops[oi].kind == BN_OP_I8_MID && m->mid_ok[oi]) {
+        if (m->ops[oi].kind == BN_OP_I8_MID && m->prep[oi]->ok) {
             *form = 1;
-            *lds_bytes = m->mids[oi].lds_bytes;
+            *lds_bytes = m->prep[oi]->chain.lds_bytes;
         }
     return BN_OK;
 }
@@ -1419,8 +616,8 @@ int bn_debug_mid_plan(const bn_model* m, int* out, int n) {
     if (!m || !out || n < 1) return fail(BN_ERR_ARG, "null argument");
     out[0] = 0;
     for (size_t oi = 0; oi < m->ops.size(); ++oi)
-        if (m->ops[oi].kind == BN_OP_I8_MID && m->mid_ok[oi] && m->mid_res_ok[oi]) {
-            if (!bn::tail2_plan_dump(m->mids_res[oi], out, n)) return fail(BN_ERR_ARG, "n=%d is too small for the plan", n);
+        if (m->ops[oi].kind == BN_OP_I8_MID && m->prep[oi]->ok && m->prep[oi]->alt_ok) {
+            if (!bn::tail2_plan_dump(m->prep[oi]->resident, out, n)) return fail(BN_ERR_ARG, "n=%d is too small for the plan", n);
             break;
         }
     return BN_OK;
@@ -1472,12 +669,13 @@ int bn_debug_guard_stats(bn_model* m, int B, int64_t* out) {
 int bn_debug_input_bytes(bn_model* m, int B, int8_t* d_out, void* stream) {
     if (!m || !d_out) return fail(BN_ERR_ARG, "null argument");
     if (int rc = check_device(m->ctx)) return rc;
+    namespace k = bn::op::i8_dwpw;
     const OpRec* first = nullptr;
     for (const OpRec& o : m->ops)
-        if (o.in0 == BN_SLOT_INPUT && o.kind == BN_OP_I8_DWPW && o.p[36] && o.p[30]) first = &o;
+        if (o.in0 == BN_SLOT_INPUT && o.kind == BN_OP_I8_DWPW && o.p[k::q_at_load] && o.p[k::transposed]) first = &o;
     if (!first || !m->d_spec) return fail(BN_ERR_UNSUPPORTED, "the plan's first operator is not the mel mixer with QUANTIZE fused into its load");
     if (B <= 0 || B > m->last_B || B > kMaxGridBatch) return fail(BN_ERR_ARG, "B=%d: the last bn_infer_audio call left %d spectrograms", B, m->last_B);
-    bn::launch_spec_bytes(m->d_spec, m->d_minmax, B, (int)m->hdr.spec_width, m->last_tiled, first->f[0], first->p[37], d_out, (hipStream_t)stream);
+    bn::launch_spec_bytes(m->d_spec, m->d_minmax, B, (int)m->hdr.spec_width, m->last_tiled, first->f[k::qscale], first->p[k::qzp], d_out, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return BN_OK;
 }

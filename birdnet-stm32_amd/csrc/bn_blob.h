@@ -117,98 +117,43 @@ static_assert(sizeof(OpRec) == 16 + 4 * BN_OP_NP + 4 * BN_OP_NT + 4 * BN_OP_NF, 
 
 // ---------------------------------------------------------------------------------------
 // Operator kinds.  Activations are NHWC per chunk (C innermost); P = H*W positions.
-// act codes: 0 none, 1 relu, 2 relu6.   mag codes: 0 none, 1 pwl, 2 pcen, 3 db.
+// What p[], t[] and f[] hold for each kind — names, order, shapes and meaning — is defined in bn_ops.h (namespace bn::op::<kind>)
+// and nowhere else; the entries above (BN_OP_PATH, BN_OP_TAIL_TAG, BN_OP_FRONT2_DIST, BN_OP_EMB_*) are the same for every kind.
 // ---------------------------------------------------------------------------------------
 enum BnOpKind : int32_t {
     // ---- float32 plan --------------------------------------------------------------
-    // spec [F][W] -> mel [M][W]   p: F W M mag norm   t: wvals(f32) bands(i32 [3][M]: start,len,off) magp(f32 [NP][M])
-    BN_OP_F32_MEL = 1,
-    // in place [M][W]: x/(max+1e-6) then magnitude scaling   p: M W mag   t: - - magp
-    BN_OP_F32_MAG = 2,
-    // wave [T] -> [M][W]  p: T W M stride pad_left mag   t: fb(f32 [16][M] BN-folded) bias magp
-    BN_OP_F32_RAWFE = 3,
-    // [H][W] (C=1) -> [OH][OW][Cout]  p: H W Cout sh sw act OH OW pad_top pad_left   t: w[3][3][Cout] bias[Cout]
-    BN_OP_F32_STEM = 4,
-    // [H][W][C] -> [OH][OW][C]        p: H W C sh sw act OH OW pad_top pad_left      t: w[3][3][C] bias[C]
-    BN_OP_F32_DW = 5,
-    // [P][Cin] -> [P][Cout]  p: P Cin Cout act has_res has_gate   in1: residual slot, p6: gate slot   t: w[Cin][Cout] bias
-    BN_OP_F32_PW = 6,
-    // [P][C] -> gate [C]  p: P C Cr   t: w1[C][Cr] w2[Cr][C]
-    BN_OP_F32_SEGATE = 7,
-    // [P][C] * gate(in1)[C] -> [P][C]  p: P C
-    BN_OP_F32_SCALE = 8,
-    // [P][C] -> [C]   p: P C
-    BN_OP_F32_GAP = 9,
-    // [Cin] -> scores [Cout] (+ logits)  p: Cin Cout act(0 linear,1 sigmoid,2 softmax)   t: w[Cin][Cout] bias
-    BN_OP_F32_DENSE = 10,
-    // [P][C] -> [C]  p: P C   t: score[C]
-    BN_OP_F32_ATTNPOOL = 11,
-    // fused [depthwise 3x3 ->] pointwise 1x1 on the matrix cores; has_dw = 0: plain 1x1 conv of in0
-    // p: H W Cin sh sw dw_act OH OW pad_top pad_left | Cout pw_act has_res has_gate gate_slot has_dw TH TW NB
-    // in1: residual slot   t: dw_w[3][3][Cin] dw_b[Cin] pw_w(fragment order [Cin/16][Cout/16][64][4]) pw_b[Cout]
-    BN_OP_F32_DWPW = 12,
-    // audio [T] -> un-normalised mel energies [M][W] (+ min/max of the magnitudes): STFT with the band-sparse mixer fused
-    // p: T(0 = runtime) W M   t: wvals bands
-    BN_OP_F32_STFTMEL = 13,
-    // un-normalised mel energies -> frontend output [M][W]   p: M W mag norm   t: wsum[M] - magp
-    BN_OP_F32_MELFIN = 14,
-    // frontend output [H0][W0] -> stem 3x3 s(1,2) -> depthwise 3x3 s2 -> pointwise, one kernel
-    // p: H0 W0 C N OH OW stem_act dw_act pw_act raw_mel mag   t: stem_w stem_b dw_w dw_b pw_w(fragment order) pw_b wsum magp
-    // raw_mel = 1 (audio path): in0 holds un-normalised mel energies, finalised while the patch is loaded
-    BN_OP_F32_FRONT = 15,
-    // global average pool + Dense + sigmoid/softmax in one kernel: [P][Cin] -> scores [Cout] (+ logits)
-    // p: P Cin Cout act   t: w[Cin][Cout] bias
-    BN_OP_F32_GAPDENSE = 16,
+    BN_OP_F32_MEL = 1,        // spectrogram -> mel map (band-sparse mixer)
+    BN_OP_F32_MAG = 2,        // in place: max normalisation + magnitude scaling
+    BN_OP_F32_RAWFE = 3,      // waveform -> raw-frontend map
+    BN_OP_F32_STEM = 4,       // 3x3 stem convolution (one input channel)
+    BN_OP_F32_DW = 5,         // depthwise 3x3
+    BN_OP_F32_PW = 6,         // pointwise 1x1 (+ residual, + squeeze-excite gate)
+    BN_OP_F32_SEGATE = 7,     // squeeze-excite gate: pool + two dense layers
+    BN_OP_F32_SCALE = 8,      // map * gate
+    BN_OP_F32_GAP = 9,        // global average pool
+    BN_OP_F32_DENSE = 10,     // classifier head
+    BN_OP_F32_ATTNPOOL = 11,  // attention pooling
+    BN_OP_F32_DWPW = 12,      // fused [depthwise 3x3 ->] pointwise 1x1 on the matrix cores
+    BN_OP_F32_STFTMEL = 13,   // audio -> un-normalised mel energies (STFT with the mixer fused)
+    BN_OP_F32_MELFIN = 14,    // un-normalised mel energies -> frontend output
+    BN_OP_F32_FRONT = 15,     // stem -> depthwise stride 2 -> pointwise, one kernel
+    BN_OP_F32_GAPDENSE = 16,  // global average pool + classifier head, one kernel
 
     // ---- INT8 plan -----------------------------------------------------------------
-    // spec f32 [F][W] -> q int8 [W][Kp]   p: F W Kp zp fill   f: scale
-    BN_OP_I8_QUANT = 20,
-    // [W][Kp] -> [M][W]  p: W Kp M zp_out act_min act_max has_lut   t: w[M][Kp] bias(zp-folded) mult shift lut[M][256]
-    BN_OP_I8_MEL = 21,
-    // [H][W] -> [OH][OW][Cout]  p: H W Cout sh sw - OH OW pad_top pad_left zp_in zp_out act_min act_max   t: w[3][3][Cout] bias mult shift
-    BN_OP_I8_STEM = 22,
-    // [H][W][C] -> [OH][OW][C]  p: as STEM with C                                     t: w[3][3][C] bias mult shift
-    BN_OP_I8_DW = 23,
-    // [P][Cin] -> [P][Cout]  p: P Cin Cout zp_out act_min act_max has_add | z1 m1 s1 m2 s2 mo so zo amin amax   t: w[Cout][Cin] bias(zp-folded) mult shift
-    BN_OP_I8_PW = 24,
-    // [P][C] -> [C]  p: P C zp_in mult shift zp_out
-    BN_OP_I8_MEAN = 25,
-    // [Cin] -> [Cout]  p: Cin Cout zp_out act_min act_max has_lut   t: w[Cout][Cin rounded up to 4, zero padded] bias(zp-folded) mult shift lut[256]
-    // (lut: the int8 LOGISTIC behind the layer, squeeze-excite gates)
-    BN_OP_I8_FC = 26,
-    // [C] int8 -> scores f32 (+ logits f32)  p: C zp_fc zp_out has_lut softmax   f: s_fc s_out beta   t: lut[256]
-    // softmax = 1: scores = float32 softmax of the dequantised input (DEQUANTIZE -> SOFTMAX graphs of conversion/export.py)
-    BN_OP_I8_HEAD = 27,
-    // fused [depthwise 3x3 ->] pointwise 1x1 on the int8 matrix cores (has_dw = 0: plain 1x1; transposed = 1: mel mixer)
-    // p: H W Cin sh sw - OH OW pad_top pad_left | dw_zp_in dw_zp_out dw_amin dw_amax | Cout pw_zp_out pw_amin pw_amax
-    //    | has_add z1 m1 s1 m2 s2 mo so zo amin amax | has_dw transposed TH TW NB has_lut
-    // in1: residual slot   t: dw_w dw_b(zp folded) dw_mult dw_shift pw_w(fragment order) pw_b(zp folded) pw_mult pw_shift lut
-    BN_OP_I8_DWPW = 28,
-    // frontend output [H0][W0] int8 -> stem 3x3 s(1,2) -> depthwise 3x3 s2 -> pointwise, one kernel
-    // p: H0 W0 C N OH OW | stem_zp_in stem_zp_out stem_amin stem_amax | dw_zp_out dw_amin dw_amax | pw_zp_out pw_amin pw_amax
-    // t: stem_w stem_b stem_mult stem_shift dw_w dw_b(zp folded) dw_mult dw_shift pw_w(fragment order) pw_b(zp folded) pw_mult pw_shift
-    BN_OP_I8_FRONT = 29,
-    // the back half of the INT8 graph in one kernel: n_layers blocks [DW 3x3 -> PW 1x1 (-> ADD)] with the maps in LDS, then MEAN,
-    // FULLY_CONNECTED and the head (bn_i8_tail.hip)
-    // p: in_bytes pw_macs dw_macs other_macs n_classes n_layers H0 W0 C0 P_last C_last   f: s_fc s_head
-    // t: constant block (int32 words), descriptor table (24 words per block + 16 head words; models/_lower_i8.py: tail_constants)
-    BN_OP_I8_TAIL = 30,
-    // int8 MUL of a map with a per-chunk gate vector (squeeze-excite): [P][C] * gate(in1)[C] -> [P][C]
-    // p: P C zp_x zp_gate mult shift zp_out act_min act_max
-    BN_OP_I8_SCALE = 31,
-    // per-chunk max normalisation of an int8 map (REDUCE_MAX over the whole map -> ADD epsilon -> DIV by that scalar) followed by an
-    // optional per-channel 256-entry table (the PWL behind it): [C][W] -> [C][W].  Everything after the max is a function of bytes:
-    // p: C W has_lut   t: denominator byte per max byte (256), DIV table [256 denominators][256 values] (row/column = byte + 128),
-    //    per-channel table [C][256] (has_lut)
-    BN_OP_I8_MAXNORM = 32,
-    // raw frontend of an exported INT8 graph: QUANTIZE of the float32 waveform [T] -> [PAD] -> CONV_2D 1x16 stride s VALID (ReLU6 clamp)
-    // -> optional per-channel table (magnitude scaling) -> [M][W] int8
-    // p: T W M stride pad_left q_zp zp_out act_min act_max has_lut   f: q_scale
-    // t: weights [M][16] int8, bias (zero point of the input folded), multipliers, shifts, table [M][256] (has_lut)
-    BN_OP_I8_RAWFE = 33,
-    // the three blocks of stage 2 of the shipped INT8 graph in one kernel (a stride-2 block from memory, two residual blocks in LDS, the last
-    // map back to memory): bn_i8_tail2.hip, i8_mid2_kernel.  p: in_bytes pw_macs dw_macs 0 0 n_layers H0 W0 C0 P_last C_last
-    // t: constant block (int32 words), descriptor table (32 words per block; models/_lower_i8.py: tail2_constants without head)
-    BN_OP_I8_MID = 35,
-    BN_OP_I8_ATTNPOOL = 34,  // attention pooling of an exported graph: score FC + int8 SOFTMAX over the positions + MUL + SUM (bn_i8.hip)
+    BN_OP_I8_QUANT = 20,     // float32 spectrogram -> int8
+    BN_OP_I8_MEL = 21,       // mel mixer (generic kernel)
+    BN_OP_I8_STEM = 22,      // 3x3 stem convolution
+    BN_OP_I8_DW = 23,        // depthwise 3x3
+    BN_OP_I8_PW = 24,        // pointwise 1x1 (+ residual ADD)
+    BN_OP_I8_MEAN = 25,      // MEAN over the positions
+    BN_OP_I8_FC = 26,        // FULLY_CONNECTED (+ LOGISTIC table)
+    BN_OP_I8_HEAD = 27,      // int8 classifier output -> float32 scores (+ logits)
+    BN_OP_I8_DWPW = 28,      // fused [depthwise 3x3 ->] pointwise 1x1 on the int8 matrix cores; also the mel mixer
+    BN_OP_I8_FRONT = 29,     // stem -> depthwise stride 2 -> pointwise, one kernel
+    BN_OP_I8_TAIL = 30,      // the back half of the graph in one kernel (bn_i8_tail.hip, bn_i8_tail2.hip)
+    BN_OP_I8_SCALE = 31,     // squeeze-excite MUL: map * gate
+    BN_OP_I8_MAXNORM = 32,   // per-chunk max normalisation (+ per-channel table)
+    BN_OP_I8_RAWFE = 33,     // raw frontend of an exported graph
+    BN_OP_I8_ATTNPOOL = 34,  // attention pooling of an exported graph
+    BN_OP_I8_MID = 35,       // the three blocks of stage 2 in one kernel (bn_i8_tail2.hip: i8_mid2_kernel)
 };

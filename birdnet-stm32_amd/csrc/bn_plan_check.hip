@@ -5,7 +5,7 @@
 // BN_ERR_FORMAT, instead of becoming an out-of-bounds device access: per operator kind this pass derives the bytes per
 // chunk the operator reads from and writes to each slot and the bytes it reads from each constant tensor, and compares
 // them with SlotRec.bytes_per_chunk / TensorRec.nbytes.  Slot ids stored in p[] (squeeze-excite gates) are checked like
-// in0 / in1 / out.  The reference's counterpart is the flatbuffer verifier inside tf.lite.Interpreter
+// in0 / in1 / out.  Fields are addressed by the names of bn_ops.h.  The reference's counterpart is the flatbuffer verifier inside tf.lite.Interpreter
 // (reference: birdnet_stm32/models/runners.py:57).
 #include <cstdarg>
 #include <cstdio>
@@ -13,8 +13,8 @@
 #include <vector>
 
 #include "../../include/birdnet_hip.h"
-#include "bn_blob.h"
 #include "bn_kernels.h"
+#include "bn_ops.h"
 
 namespace bn {
 
@@ -106,189 +106,260 @@ bool check_plan(const BlobHeader& h, const std::vector<SlotRec>& slots, const st
         c.o = &o;
         if (p[BN_OP_PATH] < BN_PATH_BOTH || p[BN_OP_PATH] > BN_PATH_AUDIO) c.bad("path tag %d", p[BN_OP_PATH]);
         switch (o.kind) {
-            case BN_OP_F32_MEL:  // F W M mag norm
-                c.dims({p[0], p[1], p[2]}, "mel") && c.slot(o.in0, 4LL * p[0] * p[1], "input") && c.slot(o.out, 4LL * p[2] * p[1], "output") &&
-                    c.tensor(0, 4, "band weights") && c.tensor(1, 12LL * p[2], "band table") && (p[3] == 0 || c.tensor(2, 4LL * p[2], "magnitude parameters"));
+            case BN_OP_F32_MEL: {
+                namespace k = op::f32_mel;
+                c.dims({p[k::F], p[k::W], p[k::M]}, "mel") && c.slot(o.in0, 4LL * p[k::F] * p[k::W], "input") && c.slot(o.out, 4LL * p[k::M] * p[k::W], "output") &&
+                    c.tensor(k::wvals, 4, "band weights") && c.tensor(k::bands, 12LL * p[k::M], "band table") &&
+                    (p[k::mag] == 0 || c.tensor(k::magp, 4LL * p[k::M], "magnitude parameters"));
                 break;
-            case BN_OP_F32_MAG:  // M W mag
-                c.dims({p[0], p[1]}, "mag") && c.slot(o.out, 4LL * p[0] * p[1], "map") && (p[2] == 0 || c.tensor(2, 4LL * p[0], "magnitude parameters"));
+            }
+            case BN_OP_F32_MAG: {
+                namespace k = op::f32_mag;
+                c.dims({p[k::M], p[k::W]}, "mag") && c.slot(o.out, 4LL * p[k::M] * p[k::W], "map") && (p[k::mag] == 0 || c.tensor(k::magp, 4LL * p[k::M], "magnitude parameters"));
                 break;
-            case BN_OP_F32_RAWFE:  // T W M stride pad_left mag
-                c.dims({p[0], p[1], p[2], p[3]}, "raw frontend") && c.slot(o.in0, 4LL * p[0], "waveform") && c.slot(o.out, 4LL * p[2] * p[1], "output") &&
-                    c.tensor(0, 64LL * p[2], "filterbank") && c.tensor(1, 4LL * p[2], "bias") && (p[5] == 0 || c.tensor(2, 4LL * p[2], "magnitude parameters"));
-                if (c.ok && p[4] < 0) c.bad("negative left padding");
-                if (c.ok && p[9]) c.clamp8(p[7], p[8], "raw frontend");
-                if (c.ok && p[1] % 4) c.bad("raw frontend width %d is not a multiple of 4 (the kernel stores dwords of one filter)", p[1]);
+            }
+            case BN_OP_F32_RAWFE: {
+                namespace k = op::f32_rawfe;
+                c.dims({p[k::T], p[k::W], p[k::M], p[k::stride]}, "raw frontend") && c.slot(o.in0, 4LL * p[k::T], "waveform") && c.slot(o.out, 4LL * p[k::M] * p[k::W], "output") &&
+                    c.tensor(k::fb, 64LL * p[k::M], "filterbank") && c.tensor(k::bias, 4LL * p[k::M], "bias") &&
+                    (p[k::mag] == 0 || c.tensor(k::magp, 4LL * p[k::M], "magnitude parameters"));
+                if (c.ok && p[k::pad_left] < 0) c.bad("negative left padding");
+                if (c.ok && p[k::W] % 4) c.bad("raw frontend width %d is not a multiple of 4 (the kernel stores dwords of one filter)", p[k::W]);
                 break;
+            }
             case BN_OP_F32_STEM:
-            case BN_OP_F32_DW: {  // H W C sh sw act OH OW pt pl
-                const long long cin = o.kind == BN_OP_F32_STEM ? 1 : p[2];
-                c.dims({p[0], p[1], p[2], p[6], p[7]}, "conv") && c.conv_geom(p[0], p[1], p[3], p[4], p[6], p[7], p[8], p[9]) &&
-                    c.slot(o.in0, 4LL * p[0] * p[1] * cin, "input") && c.slot(o.out, 4LL * p[6] * p[7] * p[2], "output") &&
-                    c.tensor(0, 36LL * p[2], "weights") && c.tensor(1, 4LL * p[2], "bias");
+            case BN_OP_F32_DW: {
+                namespace k = op::f32_dw;  // (F32_STEM: the same layout, C = Cout)
+                const long long cin = o.kind == BN_OP_F32_STEM ? 1 : p[k::C];
+                c.dims({p[k::H], p[k::W], p[k::C], p[k::OH], p[k::OW]}, "conv") && c.conv_geom(p[k::H], p[k::W], p[k::sh], p[k::sw], p[k::OH], p[k::OW], p[k::pt], p[k::pl]) &&
+                    c.slot(o.in0, 4LL * p[k::H] * p[k::W] * cin, "input") && c.slot(o.out, 4LL * p[k::OH] * p[k::OW] * p[k::C], "output") &&
+                    c.tensor(k::w, 36LL * p[k::C], "weights") && c.tensor(k::bias, 4LL * p[k::C], "bias");
                 break;
             }
-            case BN_OP_F32_PW:  // P Cin Cout act has_res has_gate gate_slot
-                c.dims({p[0], p[1], p[2]}, "pointwise") && c.slot(o.in0, 4LL * p[0] * p[1], "input") && c.slot(o.out, 4LL * p[0] * p[2], "output") &&
-                    (!p[4] || c.slot(o.in1, 4LL * p[0] * p[2], "residual")) && (!p[5] || c.slot(p[6], 4LL * p[1], "gate")) &&
-                    c.tensor(0, 4LL * p[1] * p[2], "weights") && c.tensor(1, 4LL * p[2], "bias");
+            case BN_OP_F32_PW: {
+                namespace k = op::f32_pw;
+                c.dims({p[k::P], p[k::Cin], p[k::Cout]}, "pointwise") && c.slot(o.in0, 4LL * p[k::P] * p[k::Cin], "input") && c.slot(o.out, 4LL * p[k::P] * p[k::Cout], "output") &&
+                    (!p[k::has_res] || c.slot(o.in1, 4LL * p[k::P] * p[k::Cout], "residual")) && (!p[k::has_gate] || c.slot(p[k::gate_slot], 4LL * p[k::Cin], "gate")) &&
+                    c.tensor(k::w, 4LL * p[k::Cin] * p[k::Cout], "weights") && c.tensor(k::bias, 4LL * p[k::Cout], "bias");
                 break;
-            case BN_OP_F32_SEGATE:  // P C Cr
-                c.dims({p[0], p[1], p[2]}, "squeeze-excite") && c.slot(o.in0, 4LL * p[0] * p[1], "input") && c.slot(o.out, 4LL * p[1], "gate") &&
-                    c.tensor(0, 4LL * p[1] * p[2], "reduce weights") && c.tensor(1, 4LL * p[1] * p[2], "expand weights");
+            }
+            case BN_OP_F32_SEGATE: {
+                namespace k = op::f32_segate;
+                c.dims({p[k::P], p[k::C], p[k::Cr]}, "squeeze-excite") && c.slot(o.in0, 4LL * p[k::P] * p[k::C], "input") && c.slot(o.out, 4LL * p[k::C], "gate") &&
+                    c.tensor(k::w1, 4LL * p[k::C] * p[k::Cr], "reduce weights") && c.tensor(k::w2, 4LL * p[k::C] * p[k::Cr], "expand weights");
                 break;
-            case BN_OP_F32_SCALE:  // P C
-                c.dims({p[0], p[1]}, "scale") && c.slot(o.in0, 4LL * p[0] * p[1], "input") && c.slot(o.in1, 4LL * p[1], "gate") && c.slot(o.out, 4LL * p[0] * p[1], "output");
+            }
+            case BN_OP_F32_SCALE: {
+                namespace k = op::f32_scale;
+                c.dims({p[k::P], p[k::C]}, "scale") && c.slot(o.in0, 4LL * p[k::P] * p[k::C], "input") && c.slot(o.in1, 4LL * p[k::C], "gate") &&
+                    c.slot(o.out, 4LL * p[k::P] * p[k::C], "output");
                 break;
+            }
             case BN_OP_F32_GAP:
-            case BN_OP_F32_ATTNPOOL:  // P C
-                c.dims({p[0], p[1]}, "pool") && c.slot(o.in0, 4LL * p[0] * p[1], "input") && c.slot(o.out, 4LL * p[1], "output") &&
-                    (o.kind == BN_OP_F32_GAP || c.tensor(0, 4LL * p[1], "score vector"));
-                break;
-            case BN_OP_F32_DENSE:  // Cin Cout act
-                c.dims({p[0], p[1]}, "dense") && c.slot(o.in0, 4LL * p[0], "input") && c.slot(o.out, 4LL * p[1], "scores") &&
-                    c.tensor(0, 4LL * p[0] * p[1], "weights") && c.tensor(1, 4LL * p[1], "bias");
-                if (c.ok && p[1] != (int)h.num_classes) c.bad("classifier width %d, header says %u classes", p[1], h.num_classes);
-                break;
-            case BN_OP_F32_GAPDENSE:  // P Cin Cout act
-                c.dims({p[0], p[1], p[2]}, "pool+dense") && c.slot(o.in0, 4LL * p[0] * p[1], "input") && c.slot(o.out, 4LL * p[2], "scores") &&
-                    c.tensor(0, 4LL * p[1] * p[2], "weights") && c.tensor(1, 4LL * p[2], "bias");
-                if (c.ok && p[2] != (int)h.num_classes) c.bad("classifier width %d, header says %u classes", p[2], h.num_classes);
-                break;
-            case BN_OP_F32_DWPW: {  // H W Cin sh sw dw_act OH OW pt pl | Cout pw_act has_res has_gate gate_slot has_dw TH TW NB
-                const long long out_b = 4LL * p[6] * p[7] * p[10];
-                c.dims({p[0], p[1], p[2], p[6], p[7], p[10]}, "fused block") && c.slot(o.in0, 4LL * p[0] * p[1] * p[2], "input") && c.slot(o.out, out_b, "output") &&
-                    (!p[12] || c.slot(o.in1, out_b, "residual")) && (!p[13] || c.slot(p[14], 4LL * p[2], "gate")) &&
-                    c.tensor(2, 4LL * up(p[2], 16) * p[10], "pointwise weights") && c.tensor(3, 4LL * p[10], "pointwise bias");
-                if (c.ok && p[15]) c.conv_geom(p[0], p[1], p[3], p[4], p[6], p[7], p[8], p[9]) && c.tensor(0, 36LL * p[2], "depthwise weights") && c.tensor(1, 4LL * p[2], "depthwise bias");
-                if (c.ok && !p[15] && (p[0] != p[6] || p[1] != p[7])) c.bad("plain 1x1 convolution must keep the map size");
-                if (c.ok && (p[16] < 1 || p[17] < 1 || p[18] < 1)) c.bad("tile %dx%dx%d", p[16], p[17], p[18]);
+            case BN_OP_F32_ATTNPOOL: {
+                namespace k = op::f32_attnpool;  // (F32_GAP: the same P, C; no tensor)
+                c.dims({p[k::P], p[k::C]}, "pool") && c.slot(o.in0, 4LL * p[k::P] * p[k::C], "input") && c.slot(o.out, 4LL * p[k::C], "output") &&
+                    (o.kind == BN_OP_F32_GAP || c.tensor(k::score, 4LL * p[k::C], "score vector"));
                 break;
             }
-            case BN_OP_F32_STFTMEL:  // T W M
-                c.dims({p[1], p[2]}, "stft+mel") && c.slot(o.out, 4LL * p[2] * p[1], "mel energies") && c.tensor(0, 4, "band weights") && c.tensor(1, 12LL * p[2], "band table");
+            case BN_OP_F32_DENSE: {
+                namespace k = op::f32_dense;
+                c.dims({p[k::Cin], p[k::Cout]}, "dense") && c.slot(o.in0, 4LL * p[k::Cin], "input") && c.slot(o.out, 4LL * p[k::Cout], "scores") &&
+                    c.tensor(k::w, 4LL * p[k::Cin] * p[k::Cout], "weights") && c.tensor(k::bias, 4LL * p[k::Cout], "bias");
+                if (c.ok && p[k::Cout] != (int)h.num_classes) c.bad("classifier width %d, header says %u classes", p[k::Cout], h.num_classes);
                 break;
-            case BN_OP_F32_MELFIN:  // M W mag norm
-                c.dims({p[0], p[1]}, "mel finish") && c.slot(o.in0, 4LL * p[0] * p[1], "input") && c.slot(o.out, 4LL * p[0] * p[1], "output") &&
-                    c.tensor(0, 4LL * p[0], "band sums") && (p[2] == 0 || c.tensor(2, 4LL * p[0], "magnitude parameters"));
+            }
+            case BN_OP_F32_GAPDENSE: {
+                namespace k = op::f32_gapdense;
+                c.dims({p[k::P], p[k::Cin], p[k::Cout]}, "pool+dense") && c.slot(o.in0, 4LL * p[k::P] * p[k::Cin], "input") && c.slot(o.out, 4LL * p[k::Cout], "scores") &&
+                    c.tensor(k::w, 4LL * p[k::Cin] * p[k::Cout], "weights") && c.tensor(k::bias, 4LL * p[k::Cout], "bias");
+                if (c.ok && p[k::Cout] != (int)h.num_classes) c.bad("classifier width %d, header says %u classes", p[k::Cout], h.num_classes);
                 break;
-            case BN_OP_F32_FRONT:  // H0 W0 C N OH OW stem_act dw_act pw_act raw_mel mag
-                c.dims({p[0], p[1], p[2], p[3], p[4], p[5]}, "front block") && c.slot(o.in0, 4LL * p[0] * p[1], "frontend map") && c.slot(o.out, 4LL * p[4] * p[5] * p[3], "output") &&
-                    c.tensor(0, 36LL * p[2], "stem weights") && c.tensor(1, 4LL * p[2], "stem bias") && c.tensor(2, 36LL * p[2], "depthwise weights") &&
-                    c.tensor(3, 4LL * p[2], "depthwise bias") && c.tensor(4, 4LL * up(p[2], 16) * p[3], "pointwise weights") && c.tensor(5, 4LL * p[3], "pointwise bias") &&
-                    (!p[9] || (c.tensor(6, 4LL * p[0], "band sums") && (p[10] == 0 || c.tensor(7, 4LL * p[0], "magnitude parameters"))));
-                if (c.ok && (p[4] != (p[0] + 1) / 2 || p[5] != ((p[1] + 1) / 2 + 1) / 2)) c.bad("front block output %dx%d does not follow from %dx%d", p[4], p[5], p[0], p[1]);
+            }
+            case BN_OP_F32_DWPW: {
+                namespace k = op::f32_dwpw;
+                const long long out_b = 4LL * p[k::OH] * p[k::OW] * p[k::Cout];
+                c.dims({p[k::H], p[k::W], p[k::Cin], p[k::OH], p[k::OW], p[k::Cout]}, "fused block") && c.slot(o.in0, 4LL * p[k::H] * p[k::W] * p[k::Cin], "input") &&
+                    c.slot(o.out, out_b, "output") && (!p[k::has_res] || c.slot(o.in1, out_b, "residual")) &&
+                    (!p[k::has_gate] || c.slot(p[k::gate_slot], 4LL * p[k::Cin], "gate")) && c.tensor(k::pw_w, 4LL * up(p[k::Cin], 16) * p[k::Cout], "pointwise weights") &&
+                    c.tensor(k::pw_b, 4LL * p[k::Cout], "pointwise bias");
+                if (c.ok && p[k::has_dw])
+                    c.conv_geom(p[k::H], p[k::W], p[k::sh], p[k::sw], p[k::OH], p[k::OW], p[k::pt], p[k::pl]) && c.tensor(k::dw_w, 36LL * p[k::Cin], "depthwise weights") &&
+                        c.tensor(k::dw_b, 4LL * p[k::Cin], "depthwise bias");
+                if (c.ok && !p[k::has_dw] && (p[k::H] != p[k::OH] || p[k::W] != p[k::OW])) c.bad("plain 1x1 convolution must keep the map size");
+                if (c.ok && (p[k::TH] < 1 || p[k::TW] < 1 || p[k::NB] < 1)) c.bad("tile %dx%dx%d", p[k::TH], p[k::TW], p[k::NB]);
                 break;
-            case BN_OP_I8_QUANT:  // F W Kp zp fill
-                c.dims({p[0], p[1], p[2]}, "quantise") && c.slot(o.in0, 4LL * p[0] * p[1], "spectrogram") && c.slot(o.out, 1LL * p[1] * p[2], "output");
-                if (c.ok && p[2] < p[0]) c.bad("padded bin count %d below %d bins", p[2], p[0]);
+            }
+            case BN_OP_F32_STFTMEL: {
+                namespace k = op::f32_stftmel;
+                c.dims({p[k::W], p[k::M]}, "stft+mel") && c.slot(o.out, 4LL * p[k::M] * p[k::W], "mel energies") && c.tensor(k::wvals, 4, "band weights") &&
+                    c.tensor(k::bands, 12LL * p[k::M], "band table");
                 break;
-            case BN_OP_I8_MEL:  // W Kp M zp_out act_min act_max has_lut
-                c.dims({p[0], p[1], p[2]}, "mel") && c.slot(o.in0, 1LL * p[0] * p[1], "input") && c.slot(o.out, 1LL * p[2] * p[0], "output") &&
-                    c.tensor(0, 1LL * p[2] * p[1], "weights") && c.tensor(1, 4LL * p[2], "bias") && c.tensor(2, 4LL * p[2], "multipliers") &&
-                    c.tensor(3, 4LL * p[2], "shifts") && (!p[6] || c.tensor(4, 256LL * p[2], "table"));
-                if (c.ok && p[6]) c.clamp8(p[4], p[5], "mel");  // the clamped value + 128 indexes the 256-entry table
+            }
+            case BN_OP_F32_MELFIN: {
+                namespace k = op::f32_melfin;
+                c.dims({p[k::M], p[k::W]}, "mel finish") && c.slot(o.in0, 4LL * p[k::M] * p[k::W], "input") && c.slot(o.out, 4LL * p[k::M] * p[k::W], "output") &&
+                    c.tensor(k::wsum, 4LL * p[k::M], "band sums") && (p[k::mag] == 0 || c.tensor(k::magp, 4LL * p[k::M], "magnitude parameters"));
                 break;
+            }
+            case BN_OP_F32_FRONT: {
+                namespace k = op::f32_front;
+                c.dims({p[k::H0], p[k::W0], p[k::C], p[k::N], p[k::OH], p[k::OW]}, "front block") && c.slot(o.in0, 4LL * p[k::H0] * p[k::W0], "frontend map") &&
+                    c.slot(o.out, 4LL * p[k::OH] * p[k::OW] * p[k::N], "output") && c.tensor(k::stem_w, 36LL * p[k::C], "stem weights") &&
+                    c.tensor(k::stem_b, 4LL * p[k::C], "stem bias") && c.tensor(k::dw_w, 36LL * p[k::C], "depthwise weights") &&
+                    c.tensor(k::dw_b, 4LL * p[k::C], "depthwise bias") && c.tensor(k::pw_w, 4LL * up(p[k::C], 16) * p[k::N], "pointwise weights") &&
+                    c.tensor(k::pw_b, 4LL * p[k::N], "pointwise bias") &&
+                    (!p[k::raw_mel] || (c.tensor(k::wsum, 4LL * p[k::H0], "band sums") && (p[k::mag] == 0 || c.tensor(k::magp, 4LL * p[k::H0], "magnitude parameters"))));
+                if (c.ok && (p[k::OH] != (p[k::H0] + 1) / 2 || p[k::OW] != ((p[k::W0] + 1) / 2 + 1) / 2))
+                    c.bad("front block output %dx%d does not follow from %dx%d", p[k::OH], p[k::OW], p[k::H0], p[k::W0]);
+                break;
+            }
+            case BN_OP_I8_QUANT: {
+                namespace k = op::i8_quant;
+                c.dims({p[k::F], p[k::W], p[k::Kp]}, "quantise") && c.slot(o.in0, 4LL * p[k::F] * p[k::W], "spectrogram") && c.slot(o.out, 1LL * p[k::W] * p[k::Kp], "output");
+                if (c.ok && p[k::Kp] < p[k::F]) c.bad("padded bin count %d below %d bins", p[k::Kp], p[k::F]);
+                break;
+            }
+            case BN_OP_I8_MEL: {
+                namespace k = op::i8_mel;
+                c.dims({p[k::W], p[k::Kp], p[k::M]}, "mel") && c.slot(o.in0, 1LL * p[k::W] * p[k::Kp], "input") && c.slot(o.out, 1LL * p[k::M] * p[k::W], "output") &&
+                    c.tensor(k::w, 1LL * p[k::M] * p[k::Kp], "weights") && c.tensor(k::bias, 4LL * p[k::M], "bias") && c.tensor(k::mult, 4LL * p[k::M], "multipliers") &&
+                    c.tensor(k::shift, 4LL * p[k::M], "shifts") && (!p[k::has_lut] || c.tensor(k::lut, 256LL * p[k::M], "table"));
+                if (c.ok && p[k::has_lut]) c.clamp8(p[k::act_min], p[k::act_max], "mel");  // the clamped value + 128 indexes the 256-entry table
+                break;
+            }
             case BN_OP_I8_STEM:
-            case BN_OP_I8_DW: {  // H W C sh sw - OH OW pt pl ...
-                const long long cin = o.kind == BN_OP_I8_STEM ? 1 : p[2];
-                c.dims({p[0], p[1], p[2], p[6], p[7]}, "conv") && c.conv_geom(p[0], p[1], p[3], p[4], p[6], p[7], p[8], p[9]) &&
-                    c.slot(o.in0, 1LL * p[0] * p[1] * cin, "input") && c.slot(o.out, 1LL * p[6] * p[7] * p[2], "output") && c.tensor(0, 9LL * p[2], "weights") &&
-                    c.tensor(1, 4LL * p[2], "bias") && c.tensor(2, 4LL * p[2], "multipliers") && c.tensor(3, 4LL * p[2], "shifts");
+            case BN_OP_I8_DW: {
+                namespace k = op::i8_dw;  // (I8_STEM: the same layout, C = Cout)
+                const long long cin = o.kind == BN_OP_I8_STEM ? 1 : p[k::C];
+                c.dims({p[k::H], p[k::W], p[k::C], p[k::OH], p[k::OW]}, "conv") && c.conv_geom(p[k::H], p[k::W], p[k::sh], p[k::sw], p[k::OH], p[k::OW], p[k::pt], p[k::pl]) &&
+                    c.slot(o.in0, 1LL * p[k::H] * p[k::W] * cin, "input") && c.slot(o.out, 1LL * p[k::OH] * p[k::OW] * p[k::C], "output") && c.tensor(k::w, 9LL * p[k::C], "weights") &&
+                    c.tensor(k::bias, 4LL * p[k::C], "bias") && c.tensor(k::mult, 4LL * p[k::C], "multipliers") && c.tensor(k::shift, 4LL * p[k::C], "shifts");
                 break;
             }
-            case BN_OP_I8_PW:  // P Cin Cout zp_out amin amax has_add ...
-                c.dims({p[0], p[1], p[2]}, "pointwise") && c.slot(o.in0, 1LL * p[0] * p[1], "input") && c.slot(o.out, 1LL * p[0] * p[2], "output") &&
-                    (!p[6] || c.slot(o.in1, 1LL * p[0] * p[2], "residual")) && c.tensor(0, 1LL * p[1] * p[2], "weights") && c.tensor(1, 4LL * p[2], "bias") &&
-                    c.tensor(2, 4LL * p[2], "multipliers") && c.tensor(3, 4LL * p[2], "shifts");
+            case BN_OP_I8_PW: {
+                namespace k = op::i8_pw;
+                c.dims({p[k::P], p[k::Cin], p[k::Cout]}, "pointwise") && c.slot(o.in0, 1LL * p[k::P] * p[k::Cin], "input") && c.slot(o.out, 1LL * p[k::P] * p[k::Cout], "output") &&
+                    (!p[k::has_add] || c.slot(o.in1, 1LL * p[k::P] * p[k::Cout], "residual")) && c.tensor(k::w, 1LL * p[k::Cin] * p[k::Cout], "weights") &&
+                    c.tensor(k::bias, 4LL * p[k::Cout], "bias") && c.tensor(k::mult, 4LL * p[k::Cout], "multipliers") && c.tensor(k::shift, 4LL * p[k::Cout], "shifts");
                 break;
-            case BN_OP_I8_MEAN:  // P C ...
-                c.dims({p[0], p[1]}, "mean") && c.slot(o.in0, 1LL * p[0] * p[1], "input") && c.slot(o.out, 1LL * p[1], "output");
+            }
+            case BN_OP_I8_MEAN: {
+                namespace k = op::i8_mean;
+                c.dims({p[k::P], p[k::C]}, "mean") && c.slot(o.in0, 1LL * p[k::P] * p[k::C], "input") && c.slot(o.out, 1LL * p[k::C], "output");
                 break;
-            case BN_OP_I8_FC:  // Cin Cout ...
-                c.dims({p[0], p[1]}, "fully connected") && c.slot(o.in0, 1LL * p[0], "input") && c.slot(o.out, 1LL * p[1], "output") &&
-                    c.tensor(0, up(p[0], 4) * p[1], "weights") && c.tensor(1, 4LL * p[1], "bias") && c.tensor(2, 4LL * p[1], "multipliers") &&
-                    c.tensor(3, 4LL * p[1], "shifts") && (!p[5] || c.tensor(4, 256, "table"));
-                if (c.ok && p[5]) c.clamp8(p[3], p[4], "fully connected");
+            }
+            case BN_OP_I8_FC: {
+                namespace k = op::i8_fc;
+                c.dims({p[k::Cin], p[k::Cout]}, "fully connected") && c.slot(o.in0, 1LL * p[k::Cin], "input") && c.slot(o.out, 1LL * p[k::Cout], "output") &&
+                    c.tensor(k::w, up(p[k::Cin], 4) * p[k::Cout], "weights") && c.tensor(k::bias, 4LL * p[k::Cout], "bias") && c.tensor(k::mult, 4LL * p[k::Cout], "multipliers") &&
+                    c.tensor(k::shift, 4LL * p[k::Cout], "shifts") && (!p[k::has_lut] || c.tensor(k::lut, 256, "table"));
+                if (c.ok && p[k::has_lut]) c.clamp8(p[k::act_min], p[k::act_max], "fully connected");
                 break;
-            case BN_OP_I8_SCALE:  // P C zp_x zp_gate mult shift zp_out act_min act_max
-                c.dims({p[0], p[1]}, "scale") && c.slot(o.in0, 1LL * p[0] * p[1], "input") && c.slot(o.in1, 1LL * p[1], "gate") && c.slot(o.out, 1LL * p[0] * p[1], "output");
-                if (c.ok && p[1] % 4) c.bad("channel count %d is not a multiple of 4", p[1]);
+            }
+            case BN_OP_I8_SCALE: {
+                namespace k = op::i8_scale;
+                c.dims({p[k::P], p[k::C]}, "scale") && c.slot(o.in0, 1LL * p[k::P] * p[k::C], "input") && c.slot(o.in1, 1LL * p[k::C], "gate") &&
+                    c.slot(o.out, 1LL * p[k::P] * p[k::C], "output");
+                if (c.ok && p[k::C] % 4) c.bad("channel count %d is not a multiple of 4", p[k::C]);
                 break;
-            case BN_OP_I8_MAXNORM:  // C W has_lut
-                c.dims({p[0], p[1]}, "max normalisation") && c.slot(o.in0, 1LL * p[0] * p[1], "input") && c.slot(o.out, 1LL * p[0] * p[1], "output") &&
-                    c.tensor(0, 256, "denominator table") && c.tensor(1, 65536, "division table") && (!p[2] || c.tensor(2, 256LL * p[0], "channel table"));
-                if (c.ok && p[1] % 4) c.bad("map width %d is not a multiple of 4 (the kernel reads dwords of one channel)", p[1]);
+            }
+            case BN_OP_I8_MAXNORM: {
+                namespace k = op::i8_maxnorm;
+                c.dims({p[k::C], p[k::W]}, "max normalisation") && c.slot(o.in0, 1LL * p[k::C] * p[k::W], "input") && c.slot(o.out, 1LL * p[k::C] * p[k::W], "output") &&
+                    c.tensor(k::denom, 256, "denominator table") && c.tensor(k::div, 65536, "division table") && (!p[k::has_lut] || c.tensor(k::lut, 256LL * p[k::C], "channel table"));
+                if (c.ok && p[k::W] % 4) c.bad("map width %d is not a multiple of 4 (the kernel reads dwords of one channel)", p[k::W]);
                 break;
-            case BN_OP_I8_RAWFE:  // T W M stride pad_left q_zp zp_out act_min act_max has_lut
-                c.dims({p[0], p[1], p[2], p[3]}, "raw frontend") && c.slot(o.in0, 4LL * p[0], "waveform") && c.slot(o.out, 1LL * p[2] * p[1], "output") &&
-                    c.tensor(0, 16LL * p[2], "filterbank") && c.tensor(1, 4LL * p[2], "bias") && c.tensor(2, 4LL * p[2], "multipliers") &&
-                    c.tensor(3, 4LL * p[2], "shifts") && (!p[9] || c.tensor(4, 256LL * p[2], "table"));
-                if (c.ok && p[4] < 0) c.bad("negative left padding");
-                if (c.ok && p[9]) c.clamp8(p[7], p[8], "raw frontend");
-                if (c.ok && p[1] % 4) c.bad("raw frontend width %d is not a multiple of 4 (the kernel stores dwords of one filter)", p[1]);
+            }
+            case BN_OP_I8_RAWFE: {
+                namespace k = op::i8_rawfe;
+                c.dims({p[k::T], p[k::W], p[k::M], p[k::stride]}, "raw frontend") && c.slot(o.in0, 4LL * p[k::T], "waveform") && c.slot(o.out, 1LL * p[k::M] * p[k::W], "output") &&
+                    c.tensor(k::w, 16LL * p[k::M], "filterbank") && c.tensor(k::bias, 4LL * p[k::M], "bias") && c.tensor(k::mult, 4LL * p[k::M], "multipliers") &&
+                    c.tensor(k::shift, 4LL * p[k::M], "shifts") && (!p[k::has_lut] || c.tensor(k::lut, 256LL * p[k::M], "table"));
+                if (c.ok && p[k::pad_left] < 0) c.bad("negative left padding");
+                if (c.ok && p[k::has_lut]) c.clamp8(p[k::act_min], p[k::act_max], "raw frontend");
+                if (c.ok && p[k::W] % 4) c.bad("raw frontend width %d is not a multiple of 4 (the kernel stores dwords of one filter)", p[k::W]);
                 break;
-            case BN_OP_I8_ATTNPOOL:  // P C fc_bias fc_mult fc_shift fc_zo form zx za mul_mult mul_shift mul_zo mul_lo mul_hi sum_mult sum_shift sum_zo
-                c.dims({p[0], p[1]}, "attention pooling") && c.slot(o.in0, 1LL * p[0] * p[1], "input map") && c.slot(o.out, 1LL * p[1], "output") &&
-                    c.tensor(0, 1LL * p[1], "score vector") && c.tensor(1, p[6] == 0 ? 2048 : 1024, "softmax tables");
-                if (c.ok && (p[1] % 4 || p[0] > 4096 || 1LL * p[0] * p[1] + 2LL * p[0] + 32 > 64 * 1024))  // (P <= 4096: the int32 sum of the exponentials)
-                    c.bad("attention pooling map %d x %d does not fit the kernel", p[0], p[1]);
-                if (c.ok && (p[6] < 0 || p[6] > 1)) c.bad("softmax form %d", p[6]);
-                if (c.ok) c.clamp8(p[12], p[13], "attention pooling MUL");
+            }
+            case BN_OP_I8_ATTNPOOL: {
+                namespace k = op::i8_attnpool;
+                c.dims({p[k::P], p[k::C]}, "attention pooling") && c.slot(o.in0, 1LL * p[k::P] * p[k::C], "input map") && c.slot(o.out, 1LL * p[k::C], "output") &&
+                    c.tensor(k::score, 1LL * p[k::C], "score vector") && c.tensor(k::tables, p[k::form] == 0 ? 2048 : 1024, "softmax tables");
+                if (c.ok && (p[k::C] % 4 || p[k::P] > 4096 || 1LL * p[k::P] * p[k::C] + 2LL * p[k::P] + 32 > 64 * 1024))  // (P <= 4096: the int32 sum of the exponentials)
+                    c.bad("attention pooling map %d x %d does not fit the kernel", p[k::P], p[k::C]);
+                if (c.ok && (p[k::form] < 0 || p[k::form] > 1)) c.bad("softmax form %d", p[k::form]);
+                if (c.ok) c.clamp8(p[k::mul_lo], p[k::mul_hi], "attention pooling MUL");
                 break;
-            case BN_OP_I8_HEAD:  // C zp_fc zp_out has_lut
-                c.dims({p[0]}, "head") && c.slot(o.in0, 1LL * p[0], "input") && c.slot(o.out, 4LL * p[0], "scores") && (!p[3] || c.tensor(0, 256, "table"));
-                if (c.ok && p[0] != (int)h.num_classes) c.bad("classifier width %d, header says %u classes", p[0], h.num_classes);
+            }
+            case BN_OP_I8_HEAD: {
+                namespace k = op::i8_head;
+                c.dims({p[k::C]}, "head") && c.slot(o.in0, 1LL * p[k::C], "input") && c.slot(o.out, 4LL * p[k::C], "scores") && (!p[k::has_lut] || c.tensor(k::lut, 256, "table"));
+                if (c.ok && p[k::C] != (int)h.num_classes) c.bad("classifier width %d, header says %u classes", p[k::C], h.num_classes);
                 break;
+            }
             case BN_OP_I8_DWPW: {
-                // H W Cin sh sw F OH OW pt pl | dw q (10..13) | Cout(14) pw q (15..17) | add (18..28) | has_dw(29) transposed(30) TH TW NB has_lut(34)
-                // strip(35) quantise_at_load(36) qzp qfill
-                const long long out_b = 1LL * p[6] * p[7] * p[14];
-                c.dims({p[0], p[1], p[2], p[6], p[7], p[14]}, "fused block");
-                if (c.ok && p[36]) c.dims({p[5]}, "spectrogram bins") && c.slot(o.in0, 4LL * p[5] * p[1], "spectrogram");
-                else c.slot(o.in0, 1LL * p[0] * p[1] * p[2], "input");
-                c.slot(o.out, out_b, "output") && (!p[18] || c.slot(o.in1, out_b, "residual")) && c.tensor(4, up(p[2], 64) * p[14], "pointwise weights") &&
-                    c.tensor(5, 4LL * p[14], "pointwise bias") && c.tensor(6, 4LL * p[14], "pointwise multipliers") && c.tensor(7, 4LL * p[14], "pointwise shifts") &&
-                    (!p[34] || c.tensor(8, 256LL * p[14], "table"));
-                if (c.ok && p[29])
-                    c.conv_geom(p[0], p[1], p[3], p[4], p[6], p[7], p[8], p[9]) && c.tensor(0, 9LL * p[2], "depthwise weights") && c.tensor(1, 4LL * p[2], "depthwise bias") &&
-                        c.tensor(2, 4LL * p[2], "depthwise multipliers") && c.tensor(3, 4LL * p[2], "depthwise shifts");
-                if (c.ok && !p[29] && (p[0] != p[6] || p[1] != p[7])) c.bad("plain 1x1 convolution must keep the map size");
-                if (c.ok && !p[29] && p[18] && o.t[10] >= 0) c.tensor(10, 65536, "ADD table");
-                if (c.ok && (p[31] < 1 || p[32] < 1 || p[33] < 1)) c.bad("tile %dx%dx%d", p[31], p[32], p[33]);
+                namespace k = op::i8_dwpw;
+                const long long out_b = 1LL * p[k::OH] * p[k::OW] * p[k::Cout];
+                c.dims({p[k::H], p[k::W], p[k::Cin], p[k::OH], p[k::OW], p[k::Cout]}, "fused block");
+                if (c.ok && p[k::q_at_load]) c.dims({p[k::qF]}, "spectrogram bins") && c.slot(o.in0, 4LL * p[k::qF] * p[k::W], "spectrogram");
+                else c.slot(o.in0, 1LL * p[k::H] * p[k::W] * p[k::Cin], "input");
+                c.slot(o.out, out_b, "output") && (!p[k::has_add] || c.slot(o.in1, out_b, "residual")) && c.tensor(k::pw_w, up(p[k::Cin], 64) * p[k::Cout], "pointwise weights") &&
+                    c.tensor(k::pw_b, 4LL * p[k::Cout], "pointwise bias") && c.tensor(k::pw_mult, 4LL * p[k::Cout], "pointwise multipliers") &&
+                    c.tensor(k::pw_shift, 4LL * p[k::Cout], "pointwise shifts") && (!p[k::has_lut] || c.tensor(k::lut, 256LL * p[k::Cout], "table"));
+                if (c.ok && p[k::has_dw])
+                    c.conv_geom(p[k::H], p[k::W], p[k::sh], p[k::sw], p[k::OH], p[k::OW], p[k::pt], p[k::pl]) && c.tensor(k::dw_w, 9LL * p[k::Cin], "depthwise weights") &&
+                        c.tensor(k::dw_b, 4LL * p[k::Cin], "depthwise bias") && c.tensor(k::dw_mult, 4LL * p[k::Cin], "depthwise multipliers") &&
+                        c.tensor(k::dw_shift, 4LL * p[k::Cin], "depthwise shifts");
+                if (c.ok && !p[k::has_dw] && (p[k::H] != p[k::OH] || p[k::W] != p[k::OW])) c.bad("plain 1x1 convolution must keep the map size");
+                if (c.ok && !p[k::has_dw] && p[k::has_add] && o.t[k::add_tab] >= 0) c.tensor(k::add_tab, 65536, "ADD table");
+                if (c.ok && (p[k::TH] < 1 || p[k::TW] < 1 || p[k::NB] < 1)) c.bad("tile %dx%dx%d", p[k::TH], p[k::TW], p[k::NB]);
                 // the transposed form is the mel mixer: a plain 1x1 over the frames of one chunk, no residual; only it takes a table or float32 input
-                if (c.ok && p[30] && (p[29] || p[18] || p[0] != 1 || p[6] != 1 || p[33] != 1)) c.bad("transposed output on a block that is not a mel mixer");
-                if (c.ok && !p[30] && (p[34] || p[36])) c.bad("table / fused QUANTIZE on a block without transposed output");
-                if (c.ok && p[34]) c.clamp8(p[16], p[17], "mel mixer");
-                if (c.ok && p[18]) c.clamp8(p[16], p[17], "block with ADD") && c.clamp8(p[27], p[28], "ADD");  // both index the 256-entry rescale tables
-                if (c.ok && p[35] && o.t[9] >= 0) {  // constant block of the strip kernel (bn_i8_strip.hip: kPWC + NW * nPWC words)
-                    const int nw = p[3] == p[4] ? i8_strip_waves(p[2], p[14], p[3], p[7], p[18] != 0) : 0;
+                if (c.ok && p[k::transposed] && (p[k::has_dw] || p[k::has_add] || p[k::H] != 1 || p[k::OH] != 1 || p[k::NB] != 1))
+                    c.bad("transposed output on a block that is not a mel mixer");
+                if (c.ok && !p[k::transposed] && (p[k::has_lut] || p[k::q_at_load])) c.bad("table / fused QUANTIZE on a block without transposed output");
+                if (c.ok && p[k::has_lut]) c.clamp8(p[k::pw_amin], p[k::pw_amax], "mel mixer");
+                if (c.ok && p[k::has_add])  // both index the 256-entry rescale tables
+                    c.clamp8(p[k::pw_amin], p[k::pw_amax], "block with ADD") && c.clamp8(p[k::add_amin], p[k::add_amax], "ADD");
+                if (c.ok && p[k::strip] && o.t[k::strip_cst] >= 0) {  // constant block of the strip kernel (bn_i8_strip.hip: kPWC + NW * nPWC words)
+                    const int nw = p[k::sh] == p[k::sw] ? i8_strip_waves(p[k::Cin], p[k::Cout], p[k::sh], p[k::OW], p[k::has_add] != 0) : 0;
                     if (nw) {
-                        const long long ql = p[2] / nw / 16, nt = p[14] / nw / 16;
+                        const long long ql = p[k::Cin] / nw / 16, nt = p[k::Cout] / nw / 16;
                         const long long words = nw * (4 * ql * 12 + 4 * ql * 4 + 4 * ql * 12 + nt * nw * 64 * ql + 4 * nt * 4 + 4 * nt * 12);
-                        c.tensor(9, 4 * words, "strip constants") && (!p[18] || o.t[10] < 0 || c.tensor(10, 65536, "ADD table"));
+                        c.tensor(k::strip_cst, 4 * words, "strip constants") && (!p[k::has_add] || o.t[k::add_tab] < 0 || c.tensor(k::add_tab, 65536, "ADD table"));
                     }
                 }
                 break;
             }
-            case BN_OP_I8_FRONT:  // H0 W0 C N OH OW ... strip(16)
-                c.dims({p[0], p[1], p[2], p[3], p[4], p[5]}, "front block") && c.slot(o.in0, 1LL * p[0] * p[1], "frontend map") && c.slot(o.out, 1LL * p[4] * p[5] * p[3], "output") &&
-                    c.tensor(0, 9LL * p[2], "stem weights") && c.tensor(1, 4LL * p[2], "stem bias") && c.tensor(2, 4LL * p[2], "stem multipliers") && c.tensor(3, 4LL * p[2], "stem shifts") &&
-                    c.tensor(4, 9LL * p[2], "depthwise weights") && c.tensor(5, 4LL * p[2], "depthwise bias") && c.tensor(6, 4LL * p[2], "depthwise multipliers") &&
-                    c.tensor(7, 4LL * p[2], "depthwise shifts") && c.tensor(8, up(p[2], 64) * p[3], "pointwise weights") && c.tensor(9, 4LL * p[3], "pointwise bias") &&
-                    c.tensor(10, 4LL * p[3], "pointwise multipliers") && c.tensor(11, 4LL * p[3], "pointwise shifts") && (!p[16] || o.t[12] < 0 || c.tensor(12, 496 * 4, "strip constants"));
-                if (c.ok && (p[4] != (p[0] + 1) / 2 || p[5] != ((p[1] + 1) / 2 + 1) / 2)) c.bad("front block output %dx%d does not follow from %dx%d", p[4], p[5], p[0], p[1]);
+            case BN_OP_I8_FRONT: {
+                namespace k = op::i8_front;
+                c.dims({p[k::H0], p[k::W0], p[k::C], p[k::N], p[k::OH], p[k::OW]}, "front block") && c.slot(o.in0, 1LL * p[k::H0] * p[k::W0], "frontend map") &&
+                    c.slot(o.out, 1LL * p[k::OH] * p[k::OW] * p[k::N], "output") && c.tensor(k::stem_w, 9LL * p[k::C], "stem weights") &&
+                    c.tensor(k::stem_b, 4LL * p[k::C], "stem bias") && c.tensor(k::stem_mult, 4LL * p[k::C], "stem multipliers") &&
+                    c.tensor(k::stem_shift, 4LL * p[k::C], "stem shifts") && c.tensor(k::dw_w, 9LL * p[k::C], "depthwise weights") &&
+                    c.tensor(k::dw_b, 4LL * p[k::C], "depthwise bias") && c.tensor(k::dw_mult, 4LL * p[k::C], "depthwise multipliers") &&
+                    c.tensor(k::dw_shift, 4LL * p[k::C], "depthwise shifts") && c.tensor(k::pw_w, up(p[k::C], 64) * p[k::N], "pointwise weights") &&
+                    c.tensor(k::pw_b, 4LL * p[k::N], "pointwise bias") && c.tensor(k::pw_mult, 4LL * p[k::N], "pointwise multipliers") &&
+                    c.tensor(k::pw_shift, 4LL * p[k::N], "pointwise shifts") && (!p[k::strip] || o.t[k::strip_cst] < 0 || c.tensor(k::strip_cst, 496 * 4, "strip constants"));
+                if (c.ok && (p[k::OH] != (p[k::H0] + 1) / 2 || p[k::OW] != ((p[k::W0] + 1) / 2 + 1) / 2))
+                    c.bad("front block output %dx%d does not follow from %dx%d", p[k::OH], p[k::OW], p[k::H0], p[k::W0]);
                 break;
-            case BN_OP_I8_TAIL:  // in_bytes pw_macs dw_macs other_macs n_classes n_layers H0 W0 C0 P_last C_last
-                c.dims({p[0], p[4], p[5], p[6], p[7], p[8]}, "fused tail") && c.slot(o.in0, 1LL * p[6] * p[7] * p[8], "input map") && c.slot(o.out, 4LL * p[4], "scores") &&
-                    c.tensor(0, 16, "constant block") && c.tensor(1, 4LL * (24 * p[5] + 16), "descriptor table");
-                if (c.ok && (p[4] != (int)h.num_classes || p[5] > 8 || p[BN_OP_TAIL_TAG] != BN_TAIL_OP)) c.bad("fused tail header");
-                break;  // the descriptor table itself is validated by bn::tail_plan at load (bn_api.hip)
-            case BN_OP_I8_MID:  // in_bytes pw_macs dw_macs 0 0 n_layers H0 W0 C0 P_last C_last
-                c.dims({p[0], p[5], p[6], p[7], p[8], p[9], p[10]}, "fused stage-2 chain") && c.slot(o.in0, 1LL * p[6] * p[7] * p[8], "input map") &&
-                    c.slot(o.out, 1LL * p[9] * p[10], "output map") && c.tensor(0, 16, "constant block") && c.tensor(1, 4LL * 32 * p[5], "descriptor table");
-                if (c.ok && (p[5] > 8 || p[BN_OP_TAIL_TAG] != BN_MID_OP)) c.bad("fused stage-2 chain header");
+            }
+            case BN_OP_I8_TAIL: {
+                namespace k = op::i8_tail;
+                c.dims({p[k::in_bytes], p[k::n_classes], p[k::n_layers], p[k::H0], p[k::W0], p[k::C0]}, "fused tail") &&
+                    c.slot(o.in0, 1LL * p[k::H0] * p[k::W0] * p[k::C0], "input map") && c.slot(o.out, 4LL * p[k::n_classes], "scores") &&
+                    c.tensor(k::cst, 16, "constant block") && c.tensor(k::desc, 4LL * (24 * p[k::n_layers] + 16), "descriptor table");
+                if (c.ok && (p[k::n_classes] != (int)h.num_classes || p[k::n_layers] > 8 || p[BN_OP_TAIL_TAG] != BN_TAIL_OP)) c.bad("fused tail header");
+                break;  // the descriptor table itself is validated by bn::tail_plan at load (bn_plan_run.hip: prepare_plan)
+            }
+            case BN_OP_I8_MID: {
+                namespace k = op::i8_mid;
+                c.dims({p[k::in_bytes], p[k::n_layers], p[k::H0], p[k::W0], p[k::C0], p[k::P_last], p[k::C_last]}, "fused stage-2 chain") &&
+                    c.slot(o.in0, 1LL * p[k::H0] * p[k::W0] * p[k::C0], "input map") && c.slot(o.out, 1LL * p[k::P_last] * p[k::C_last], "output map") &&
+                    c.tensor(k::cst, 16, "constant block") && c.tensor(k::desc, 4LL * 32 * p[k::n_layers], "descriptor table");
+                if (c.ok && (p[k::n_layers] > 8 || p[BN_OP_TAIL_TAG] != BN_MID_OP)) c.bad("fused stage-2 chain header");
                 break;  // (descriptor table: bn::tail2_plan at load)
+            }
             default:
                 c.bad("unknown operator kind");
                 break;

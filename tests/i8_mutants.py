@@ -426,10 +426,10 @@ def plan_forms(plan) -> dict:
     ops = plan.ops
     tail = [o for o in ops if o.kind == pk.I8_TAIL]
     front = [o for o in ops if o.kind == pk.I8_FRONT]
-    strips = [o for o in ops if o.kind == pk.I8_DWPW and o.p[29] == 1 and not o.p[pk.TAIL_TAG]]
+    strips = [o for o in ops if o.kind == pk.I8_DWPW and o.get("has_dw") == 1 and not o.p[pk.TAIL_TAG]]
     return dict(mid=sum(o.kind == pk.I8_MID for o in ops), tail=len(tail),
-                tail2=bool(tail and tail[0].t[2] >= 0 and tail[0].t[3] >= 0),
-                front_strip=bool(front and front[0].t[12] >= 0), strip=[bool(o.t[9] >= 0) for o in strips])
+                tail2=bool(tail and tail[0].get("cst2") >= 0 and tail[0].get("desc2") >= 0),
+                front_strip=bool(front and front[0].get("strip_cst") >= 0), strip=[bool(o.get("strip_cst") >= 0) for o in strips])
 
 
 def ledger(model, S: np.ndarray) -> dict:

@@ -223,7 +223,7 @@ def _perturbations(plan, case, n: int) -> dict:
 
     model = case["model"]
     op = next(o for o in plan.ops if o.kind == pk.I8_MID)
-    cst, desc = plan.tensors[op.t[0]].reshape(-1), plan.tensors[op.t[1]].reshape(-1)
+    cst, desc = plan.tensors[op.get("cst")].reshape(-1), plan.tensors[op.get("desc")].reshape(-1)
     _, blocks = im.backbone(model)
     mid = [b for b in blocks if b["stage"] == "stage2"]
     out = {}
@@ -276,10 +276,10 @@ def test_a_perturbed_constant_is_reported_as_a_mismatch(torch_mod, which):
 
     def run(words: dict) -> dict:
         bad = copy.deepcopy(plan)
-        cst = bad.tensors[op.t[0]].copy()
+        cst = bad.tensors[op.get("cst")].copy()
         for w, v in words.items():
             cst.reshape(-1)[w] = v
-        bad.tensors[op.t[0]] = cst
+        bad.tensors[op.get("cst")] = cst
         blob = bad.to_blob()
         assert _hip.load_library().bn_blob_check(blob, len(blob)) == 0
         runner, mid_op = _production(case, 37, plan=bad)

@@ -148,9 +148,9 @@ def test_a_perturbed_classifier_weight_shows_in_its_column_under_the_form_that_r
 
     plan = lower_i8(c["model"])
     tail = next(o for o in plan.ops if o.kind == pk.I8_TAIL)
-    n_layers = tail.p[5]
-    g_w1 = int(plan.tensors[tail.t[1]].reshape(-1)[24 * n_layers + 7])
-    g_w2 = int(plan.tensors[tail.t[3]].reshape(-1)[32 * n_layers + 7])
+    n_layers = tail.get("n_layers")
+    g_w1 = int(plan.tensors[tail.get("desc")].reshape(-1)[24 * n_layers + 7])
+    g_w2 = int(plan.tensors[tail.get("desc2")].reshape(-1)[32 * n_layers + 7])
     ks, g, j = k // 64, (k % 64) // 16, k % 16    # fragments [class tile][ks][lane = 16 g + m][16 bytes]: byte j = W[16 ct + m][64 ks + 16 g + j]
 
     def frag_byte(row: int) -> int:

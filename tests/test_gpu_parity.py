@@ -149,7 +149,7 @@ def test_f32_strip_kernel_matches_tile_kernels(torch_mod, oracle_specs):
     x = np.tile(oracle_specs[..., None], (9, 1, 1, 1))[:130]
     B = x.shape[0]
     runner = load_model_runner(KERAS_PATH, max_batch=B, keep_all=True)
-    ops = [oi for oi, op in enumerate(runner.plan.ops) if op.kind == pk.F32_DWPW and op.p[2] <= 128 and op.p[10] <= 128 and op.p[7] % 16 == 0]
+    ops = [oi for oi, op in enumerate(runner.plan.ops) if op.kind == pk.F32_DWPW and op.get("Cin") <= 128 and op.get("Cout") <= 128 and op.get("OW") % 16 == 0]
     ops += [oi for oi, op in enumerate(runner.plan.ops) if op.kind == pk.F32_FRONT and op.p[pk.OP_PATH] == pk.PATH_INPUT]  # front block
     assert len(ops) == 9
     from birdnet_stm32 import _hip
@@ -220,7 +220,7 @@ def test_i8_strip_kernel_matches_generic_block(torch_mod, oracle_specs):
     from birdnet_stm32 import _hip
 
     runner = load_model_runner(TFLITE_PATH, max_batch=B, keep_all=True)
-    strip_ops = [oi for oi, op in enumerate(runner.plan.ops) if (op.kind == pk.I8_DWPW and op.p[35]) or (op.kind == pk.I8_FRONT and op.p[16])]
+    strip_ops = [oi for oi, op in enumerate(runner.plan.ops) if op.kind in (pk.I8_DWPW, pk.I8_FRONT) and op.get("strip")]
     assert len(strip_ops) == 11
     with _hip.options(i8_strip=0):
         want_scores = runner.predict(x)
@@ -240,7 +240,7 @@ def test_i8_strip_kernel_matches_generic_block(torch_mod, oracle_specs):
     # the production plan (slots recycled, QUANTIZE fused into the mel mixer's load with the three-instruction exact division) gives
     # the same scores bit for bit, on the test spectrograms and on random ones that exercise the rounding of the quantiser
     prod = load_model_runner(TFLITE_PATH, max_batch=B)
-    assert prod.plan.ops[0].kind == pk.I8_DWPW and prod.plan.ops[0].p[36] == 1
+    assert prod.plan.ops[0].kind == pk.I8_DWPW and prod.plan.ops[0].get("q_at_load") == 1
     assert np.array_equal(prod.predict(x), want_scores)
     dbg = load_model_runner(TFLITE_PATH, max_batch=B, keep_all=True)
     xr = np.random.default_rng(11).random((64, 257, 256, 1), dtype=np.float32)

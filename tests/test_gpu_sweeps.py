@@ -288,7 +288,7 @@ def test_f32_dw_stream_matches_baseline_kernel(torch_mod):
     for B, ths in ((130, (0, 1, 3, 5, 7, 64) * 8), (1024, (0, 3, 64))):
         runner = HipRunner(lower_f32(spec, keep_all=True), max_batch=B)
         dw_ops = [oi for oi, op in enumerate(runner.plan.ops) if op.kind == pk.F32_DW]
-        assert len(dw_ops) >= 8 and {runner.plan.ops[oi].p[3] for oi in dw_ops} == {1, 2}
+        assert len(dw_ops) >= 8 and {runner.plan.ops[oi].get("sh") for oi in dw_ops} == {1, 2}
         x = torch.from_numpy(rng.random((B, 257 * 256), dtype=np.float32)).cuda()
         with _hip.options(f32_strip=0):
             want_scores = runner.predict_device(x).clone()
@@ -423,7 +423,7 @@ def test_i8_fused_tail_matches_per_block_kernels_and_oracle(torch_mod):
     assert rows.get("i8_tail") == 1 and "i8_mean" not in rows
     # both forms of the fused kernel: depthwise stage on the matrix cores (i8_tail2_kernel, the default where the plan carries its
     # constants) and on the vector ALU (i8_tail_kernel)
-    assert tail[0].t[2] >= 0 and tail[0].t[3] >= 0, "the shipped graph must take the matrix-core depthwise form"
+    assert tail[0].get("cst2") >= 0 and tail[0].get("desc2") >= 0, "the shipped graph must take the matrix-core depthwise form"
     assert runner.tail_form()[0] == 2, "the library refused the matrix-core form's LDS plan: the default path would silently be i8_tail_kernel"
     with _hip.options(i8_tail_mfdw=0):
         for nb in (261, 1, 3, 37):
@@ -776,7 +776,7 @@ def test_f32_pw_ws_kernel_matches_the_tile_kernel(torch_mod, alpha):
     runner = HipRunner(lower_f32(spec), max_batch=B)
     from birdnet_stm32.models import _pack as pk
 
-    wide = [o for o in runner.plan.ops if o.kind == pk.F32_DWPW and o.p[2] > 128 and o.p[2] % 64 == 0 and o.p[10] % 128 in (0, 64)]
+    wide = [o for o in runner.plan.ops if o.kind == pk.F32_DWPW and o.get("Cin") > 128 and o.get("Cin") % 64 == 0 and o.get("Cout") % 128 in (0, 64)]
     assert len(wide) >= 6, len(wide)  # (the shapes the kernel takes: Cin > 128, Cout a multiple of 192 or 128)
     rng = np.random.default_rng(9)
     x = rng.standard_normal((B, 48000)).astype(np.float32)
@@ -815,7 +815,7 @@ def test_i8_dw_stream_kernel_matches_the_baseline_kernel(torch_mod):
         B = x.shape[0]
         runner = HipRunner(lower_i8(model, keep_all=True), max_batch=B)
         dw_ops = [oi for oi, op in enumerate(runner.plan.ops) if op.kind in (pk.I8_DW, pk.I8_STEM)]  # the stem streams its rows the same way
-        assert len(dw_ops) >= 5 and {runner.plan.ops[oi].p[3] for oi in dw_ops} == {1, 2} and pk.I8_STEM in {runner.plan.ops[oi].kind for oi in dw_ops}
+        assert len(dw_ops) >= 5 and {runner.plan.ops[oi].get("sh") for oi in dw_ops} == {1, 2} and pk.I8_STEM in {runner.plan.ops[oi].kind for oi in dw_ops}
         with _hip.options(i8_strip=0):
             want_scores = runner.predict(x)
             want = {oi: runner.op_output(oi, B) for oi in dw_ops}
@@ -849,7 +849,7 @@ def test_i8_strip_mf_kernel_matches_the_strip_kernel_and_the_oracle(torch_mod):
     B = 21
     x = rng.random((B, 257, 256, 1), dtype=np.float32)
     runner = HipRunner(lower_i8(model, keep_all=True), max_batch=B)
-    ops = [oi for oi, op in enumerate(runner.plan.ops) if op.kind == pk.I8_DWPW and op.p[35] and op.p[2] == 32 and op.p[14] == 32 and op.p[3] == 1 and op.p[18]]
+    ops = [oi for oi, op in enumerate(runner.plan.ops) if op.kind == pk.I8_DWPW and op.get("strip") and op.get("Cin") == 32 and op.get("Cout") == 32 and op.get("sh") == 1 and op.get("has_add")]
     assert len(ops) == 1, ops
     oi = ops[0]
     _, env = Int8Interpreter(model).invoke(x, return_all=True)
@@ -1082,9 +1082,9 @@ def test_hostile_tail_descriptor_falls_back_to_the_block_kernels(torch_mod):
     good.close()
     for word, value in ((21, -4), (13, -300), (24 + 19, 400), (24 * 6 + 7, -8)):  # g_dwc / pw_lo of block 0, add_hi of block 1 (the first with an ADD), g_fcw of the head
         bad = copy.deepcopy(plan)
-        desc = bad.tensors[bad.ops[ti].t[1]].copy()
+        desc = bad.tensors[bad.ops[ti].get("desc")].copy()
         desc.reshape(-1)[word] = value
-        bad.tensors[bad.ops[ti].t[1]] = desc
+        bad.tensors[bad.ops[ti].get("desc")] = desc
         r = HipRunner(bad, max_batch=8)
         r.profile(True)
         got = r.predict(S)

@@ -30,10 +30,10 @@ def test_variant_lowers_to_the_expected_forms_and_is_not_flat(name):
     # -- the forms
     forms = im.plan_forms(plan)
     tail = [o for o in plan.ops if o.kind == pk.I8_TAIL]
-    got = dict(mid=forms["mid"], tail=forms["tail"], tail2=forms["tail2"], layers=tail[0].p[5] if tail else None, nc=tail[0].p[4] if tail else None)
+    got = dict(mid=forms["mid"], tail=forms["tail"], tail2=forms["tail2"], layers=tail[0].get("n_layers") if tail else None, nc=tail[0].get("n_classes") if tail else None)
     assert got == dict(mid=1, tail=want["tail"], tail2=want["tail2"], layers=want["layers"] if want["tail"] else None, nc=want["nc"] if want["tail"] else None), got
     if want["tail"]:
-        desc = plan.tensors[tail[0].t[1]].reshape(-1)
+        desc = plan.tensors[tail[0].get("desc")].reshape(-1)
         assert (desc[24 * want["layers"] + 11] >= 0) == want["table"], "head word g_hlut: -1 exactly where no table follows the classifier"
     else:   # the per-block operators run: none of them may be left tagged as covered
         assert not any(o.p[pk.TAIL_TAG] in (pk.TAIL_COVERED, pk.TAIL_OP) for o in plan.ops)

@@ -29,48 +29,48 @@ def test_fused_plan_structure():
     assert f32.ops[1].in0 == pk.SLOT_AUDIO and f32.ops[0].in0 == pk.SLOT_INPUT
     # runner boundary: mel -> front block; audio: STFT+mel -> front block that finalises the raw mel energies while loading
     assert f32.ops[2].in0 == f32.ops[0].out and f32.ops[3].in0 == f32.ops[1].out and f32.ops[2].out == f32.ops[3].out
-    assert (f32.ops[2].p[9], f32.ops[3].p[9]) == (0, 1)
-    assert sum(1 for o in f32.ops if o.kind == pk.F32_DWPW and o.p[12]) == 7  # residual blocks
+    assert (f32.ops[2].get("raw_mel"), f32.ops[3].get("raw_mel")) == (0, 1)
+    assert sum(1 for o in f32.ops if o.kind == pk.F32_DWPW and o.get("has_res")) == 7  # residual blocks
     kinds = [pk.KIND_NAMES[o.kind] for o in i8.ops]
     assert kinds == ["i8_dwpw", "i8_front"] + ["i8_dwpw"] * 4 + ["i8_mid"] + ["i8_dwpw"] * 6 + ["i8_mean", "i8_fc", "i8_head", "i8_tail"]
     # the fused stage-2 chain covers stage2_ds1..ds3 (three operators, kept in the plan for the i8_mid = 0 path) and sits right behind them
     mid = i8.ops[6]
     assert mid.p[pk.TAIL_TAG] == pk.MID_OP and [o.p[pk.TAIL_TAG] == pk.MID_COVERED for o in i8.ops[:6]] == [False] * 3 + [True] * 3
-    assert mid.in0 == i8.ops[3].in0 and mid.out == i8.ops[5].out and mid.p[5:11] == [3, 32, 64, 32, 512, 64]
-    assert i8.tensors[mid.t[1]].size == 32 * 3
+    assert mid.in0 == i8.ops[3].in0 and mid.out == i8.ops[5].out and [mid.get(k) for k in ("n_layers", "H0", "W0", "C0", "P_last", "C_last")] == [3, 32, 64, 32, 512, 64]
+    assert i8.tensors[mid.get("desc")].size == 32 * 3
     # the fused tail operator covers stage 3-4 + MEAN + FC + head (9 operators, kept in the plan for the i8_tail = 0 path)
     tail = i8.ops[-1]
     assert tail.p[pk.TAIL_TAG] == pk.TAIL_OP and [o.p[pk.TAIL_TAG] == pk.TAIL_COVERED for o in i8.ops[:-1]] == [False] * 7 + [True] * 9
-    assert tail.in0 == i8.ops[7].in0 and tail.out == pk.SLOT_SCORES and tail.p[:11] == [16 * 32 * 64, 10485760, 626688, 32 * 256 + 256 * 100, 100, 6, 16, 32, 64, 32, 256]
-    desc = i8.tensors[tail.t[1]]
+    assert tail.in0 == i8.ops[7].in0 and tail.out == pk.SLOT_SCORES and [tail.get(k) for k in pk.OP_FIELDS[pk.I8_TAIL][0]] == [16 * 32 * 64, 10485760, 626688, 32 * 256 + 256 * 100, 100, 6, 16, 32, 64, 32, 256]
+    desc = i8.tensors[tail.get("desc")]
     assert desc.size == 24 * 6 + 16 and desc[:10].tolist() == [16, 32, 64, 128, 2, 8, 16, 0, 0, 0] and desc[24 * 5 : 24 * 5 + 10].tolist() == [4, 8, 256, 256, 1, 4, 8, 1, 1, 1]
     # pointwise A fragments of a tail block: lane (m, kq), byte b of k-step ks = W[16 nt + m][4 (base[kq] + 4 ks + (b >> 2)) + (b & 3)]
     from birdnet_stm32.models._lower_i8 import _tail_quad_base
 
     blk = i8.ops[8]  # stage3_ds2: 128 -> 128
     w2 = np.zeros((128, 128), np.int8)
-    fr_old = i8.tensors[blk.t[4]].reshape(2, 8, 64, 16)  # generic fragment order [K/64][N/16][lane][16]: lane (q, c) -> W[16 ct + c][64 s + 16 q ..]
+    fr_old = i8.tensors[blk.get("pw_w")].reshape(2, 8, 64, 16)  # generic fragment order [K/64][N/16][lane][16]: lane (q, c) -> W[16 ct + c][64 s + 16 q ..]
     for s_ in range(2):
         for ct in range(8):
             for lane in range(64):
                 w2[16 * ct + (lane & 15), 64 * s_ + 16 * (lane >> 4) : 64 * s_ + 16 * (lane >> 4) + 16] = fr_old[s_, ct, lane]
     g_w = int(desc[24 * 1 + 20])
-    frag = i8.tensors[tail.t[0]][g_w : g_w + 128 * 128 // 4].view(np.int8).reshape(8, 2, 64, 16)
+    frag = i8.tensors[tail.get("cst")][g_w : g_w + 128 * 128 // 4].view(np.int8).reshape(8, 2, 64, 16)
     base = _tail_quad_base(128)
     for nt, ks, lane, b in ((0, 0, 0, 0), (3, 1, 37, 9), (7, 1, 63, 15), (5, 0, 18, 6)):
         assert frag[nt, ks, lane, b] == w2[16 * nt + (lane & 15), 4 * (base[lane >> 4] + 4 * ks + (b >> 2)) + (b & 3)]
     _, i8_dbg2 = _plans(keep_all=True, fuse=True)
     assert all(o.kind != pk.I8_TAIL for o in i8_dbg2.ops)  # keep_all plans keep every tensor visible: no fused tail
     mel = i8.ops[0]  # the mel mixer: QUANTIZE fused into its load (float32 spectrogram in), transposed output + PWL table
-    assert mel.in0 == pk.SLOT_INPUT and mel.p[36] == 1 and mel.p[5] == 257 and mel.p[30] == 1 and mel.p[34] == 1 and mel.f[0] > 0
+    assert mel.in0 == pk.SLOT_INPUT and mel.get("q_at_load") == 1 and mel.get("qF") == 257 and mel.get("transposed") == 1 and mel.get("has_lut") == 1 and mel.get("qscale") > 0
     _, i8_dbg = _plans(keep_all=True, fuse=True)  # debug plans keep QUANTIZE as its own operator (its tensor can be compared)
-    assert [pk.KIND_NAMES[o.kind] for o in i8_dbg.ops][:2] == ["i8_quant", "i8_dwpw"] and i8_dbg.ops[1].p[36] == 0
-    assert sum(1 for o in i8.ops if o.kind == pk.I8_DWPW and o.p[18]) == 7
+    assert [pk.KIND_NAMES[o.kind] for o in i8_dbg.ops][:2] == ["i8_quant", "i8_dwpw"] and i8_dbg.ops[1].get("q_at_load") == 0
+    assert sum(1 for o in i8.ops if o.kind == pk.I8_DWPW and o.get("has_add")) == 7
     for plan in (f32, i8):
         for o in plan.ops:
             if o.kind in (pk.F32_DWPW, pk.I8_DWPW):
-                th, tw, nb = (o.p[16], o.p[17], o.p[18]) if o.kind == pk.F32_DWPW else (o.p[31], o.p[32], o.p[33])
-                assert th * tw * nb == 64 and o.p[6] % th == 0 and o.p[7] % tw == 0
+                th, tw, nb = o.get("TH"), o.get("TW"), o.get("NB")
+                assert th * tw * nb == 64 and o.get("OH") % th == 0 and o.get("OW") % tw == 0
     # fragment-ordered pointwise weights: [K/16][N/16][64][4] floats hold exactly the folded [K][N] matrix
     from birdnet_stm32.models._lower_f32 import pack_pw_fragments
     from birdnet_stm32.models._lower_i8 import pack_i8_fragments
@@ -95,11 +95,11 @@ def test_plan_structure():
     kinds = [pk.KIND_NAMES[o.kind] for o in f32.ops]
     assert kinds[:2] == ["f32_mel", "f32_stem"] and kinds[-2:] == ["f32_gap", "f32_dense"]
     assert kinds.count("f32_dw") == 11 and kinds.count("f32_pw") == 11 and len(f32.ops) == 26
-    assert sum(1 for o in f32.ops if o.kind == pk.F32_PW and o.p[4]) == 7  # residual blocks
+    assert sum(1 for o in f32.ops if o.kind == pk.F32_PW and o.get("has_res")) == 7  # residual blocks
     kinds = [pk.KIND_NAMES[o.kind] for o in i8.ops]
     assert kinds[:3] == ["i8_quant", "i8_mel", "i8_stem"] and kinds[-3:] == ["i8_mean", "i8_fc", "i8_head"]
     assert kinds.count("i8_dw") == 11 and kinds.count("i8_pw") == 11 and len(i8.ops) == 28  # 56 TFLite ops -> 28 launches
-    assert sum(1 for o in i8.ops if o.kind == pk.I8_PW and o.p[6]) == 7
+    assert sum(1 for o in i8.ops if o.kind == pk.I8_PW and o.get("has_add")) == 7
     assert (f32.dtype, i8.dtype) == (pk.DTYPE_F32, pk.DTYPE_I8)
     assert f32.input_elems == i8.input_elems == 257 * 256 and f32.num_classes == i8.num_classes == 100
     # shapes of the SURVEY §8d per-layer table
@@ -107,9 +107,9 @@ def test_plan_structure():
     assert shapes[0] == (64, 128, 16) and shapes[1] == (32, 64, 32) and shapes[-1] == (4, 8, 256)
     # TensorFlow SAME padding is asymmetric for stride 2: stem pads W 0/1, stride-2 depthwise pads 0/1 on both axes
     stem = f32.ops[1]
-    assert (stem.p[8], stem.p[9]) == (1, 0)
+    assert (stem.get("pt"), stem.get("pl")) == (1, 0)
     dws = [o for o in f32.ops if o.kind == pk.F32_DW]
-    assert all((o.p[8], o.p[9]) == ((0, 0) if o.p[3] == 2 else (1, 1)) for o in dws)
+    assert all((o.get("pt"), o.get("pl")) == ((0, 0) if o.get("sh") == 2 else (1, 1)) for o in dws)
 
 
 def test_slots_never_alias_live_values():
@@ -153,7 +153,7 @@ def test_residual_source_survives_until_the_add():
 
     for f32 in (_plans()[0], _plans(fuse=True)[0]):
       for i, o in enumerate(f32.ops):
-        if (o.kind == pk.F32_PW and o.p[4]) or (o.kind == pk.F32_DWPW and o.p[12]):
+        if o.kind in (pk.F32_PW, pk.F32_DWPW) and o.get("has_res"):
             res = o.in1
             # the producer of `res` is the last writer of that slot before op i
             writers = [j for j in range(i) if f32.ops[j].out == res]
@@ -184,6 +184,17 @@ def test_blob_layout_roundtrip():
     assert f"BN_OP_NP {pk.OP_NP}" in hdr and f"BN_OP_NT {pk.OP_NT}" in hdr and f"BN_OP_NF {pk.OP_NF}" in hdr
     for name, val in pk.KIND_NAMES.items():
         assert re.search(rf"BN_OP_{val.upper()} = {name}\b", hdr), val
+    # the field names of every kind mirror csrc/bn_ops.h: same enumerators in the same order, for p, t and f
+    ops_h = open(os.path.join(REPO, "birdnet-stm32_amd", "csrc", "bn_ops.h")).read()
+    geom = re.search(r"#define BN_FIELDS_GEOM\(c, p5\) (.*)", ops_h).group(1)
+    ops_h = re.sub(r"BN_FIELDS_GEOM\((\w+), (\w+)\)", lambda m: re.sub(r"\bp5\b", m.group(2), re.sub(r"\bc\b", m.group(1), geom)), ops_h)
+    ops_h = re.sub(r"\bBN_FIELDS_ADD\b(?! has_add)", re.search(r"#define BN_FIELDS_ADD (.*)", ops_h).group(1), ops_h)
+    seen = {}
+    for kind, body in re.findall(r"^namespace (\w+) \{\n((?:enum .*\n)+)\}", ops_h, re.M):
+        enums = {e: tuple(n.strip() for n in names.split(",") if not n.strip().endswith("_END")) for e, names in re.findall(r"enum (\w+) \{(.*?)\};", body)}
+        seen[kind] = (enums.get("Pi", ()), enums.get("Ti", ()), enums.get("Fi", ()))
+    assert seen == {pk.KIND_NAMES[k]: v for k, v in pk.OP_FIELDS.items()}
+    assert pk.ADD_FIELDS == tuple(re.search(r"#define BN_FIELDS_ADD (.*)", ops_h).group(1).split(", "))
 
 
 def test_band_sparse_mel_equals_dense():
@@ -213,9 +224,9 @@ def test_pwl_table_and_folded_biases_match_the_oracle():
     model = load_tflite(TFLITE_PATH)
     _, i8f = _plans(fuse=True)
     _, i8 = _plans()
-    assert np.array_equal(i8f.tensors[i8f.ops[0].t[8]], i8.tensors[i8.ops[1].t[4]])  # same PWL table in both plans (fused: mel mixer first)
+    assert np.array_equal(i8f.tensors[i8f.ops[0].get("lut")], i8.tensors[i8.ops[1].get("lut")])  # same PWL table in both plans (fused: mel mixer first)
     mel = i8.ops[1]
-    lut = i8.tensors[mel.t[4]]  # [64][256]
+    lut = i8.tensors[mel.get("lut")]  # [64][256]
     interp = og.Int8Interpreter(model)
     q = np.repeat(np.arange(-128, 128, dtype=np.int8)[None, None, :, None], 64, axis=3)  # [1,1,256,64]: every value in every channel
     env = {83: q}
@@ -232,13 +243,13 @@ def test_pwl_table_and_folded_biases_match_the_oracle():
         for sc, zp in ((0.0235294, -128), (0.20542, -34), (1.23353e-3, -128)):
             assert qz.activation_bounds(act, sc, zp) == og.activation_range(act, sc, zp)
     head = i8.ops[-1]
-    assert np.array_equal(i8.tensors[head.t[0]], interp.logistic_lut(model.ops[54]))
+    assert np.array_equal(i8.tensors[head.get("lut")], interp.logistic_lut(model.ops[54]))
     # zero-point folding: bias' = bias - zp_in * sum_k w
     pw = next(o for o in i8.ops if o.kind == pk.I8_PW)
     op = model.ops[24]
     w = model.tensors[op.inputs[1]].data.reshape(32, 16).astype(np.int64)
     zp_in = int(model.tensors[op.inputs[0]].zero_point[0])
-    assert np.array_equal(i8.tensors[pw.t[1]], (model.tensors[op.inputs[2]].data - zp_in * w.sum(axis=1)).astype(np.int32))
+    assert np.array_equal(i8.tensors[pw.get("bias")], (model.tensors[op.inputs[2]].data - zp_in * w.sum(axis=1)).astype(np.int32))
 
 
 def test_unsupported_graphs_are_rejected():
@@ -344,8 +355,8 @@ def test_inverted_residual_pairs_are_tagged_and_never_run_in_place():
     assert len(heads) == 11
     for i in heads:
         e, d = plan.ops[i], plan.ops[i + 1]
-        assert e.kind == pk.F32_DWPW and e.p[15] == 0 and e.p[12] == 0 and e.p[13] == 0 and d.kind == pk.F32_DW and d.p[pk.TAIL_TAG] == pk.PWDW_COVERED
-        assert d.in0 == e.out and d.out != e.in0 and d.out != e.out and d.p[2] == e.p[10]
+        assert e.kind == pk.F32_DWPW and e.get("has_dw") == 0 and e.get("has_res") == 0 and e.get("has_gate") == 0 and d.kind == pk.F32_DW and d.p[pk.TAIL_TAG] == pk.PWDW_COVERED
+        assert d.in0 == e.out and d.out != e.in0 and d.out != e.out and d.get("C") == e.get("Cout")
     stems = [i for i, o in enumerate(plan.ops) if o.p[pk.TAIL_TAG] == pk.PWDW_STEM]  # the stem in front of the first pair: computed inside the fused kernel
     assert len(stems) == 1 and plan.ops[stems[0]].kind == pk.F32_STEM and stems[0] + 1 == heads[0] and plan.ops[stems[0] + 2].out != plan.ops[stems[0]].in0
     for kw in (dict(keep_all=True), dict(fuse=False)):
@@ -377,15 +388,15 @@ def test_blob_check_accepts_every_lowered_plan_and_refuses_damaged_ones():
     f32 = next(p for n, p in plans.items() if n.startswith("dscnn {} fuse=True"))
     # 1) an output slot smaller than what the operator writes
     bad = copy.deepcopy(i8)
-    oi = next(i for i, o in enumerate(bad.ops) if o.kind == pk.I8_DWPW and o.p[29])
+    oi = next(i for i, o in enumerate(bad.ops) if o.kind == pk.I8_DWPW and o.get("has_dw"))
     bad.slot_bytes[bad.ops[oi].out] = 256
     refused(bad, "needs .* bytes per chunk")
     # 2) a gate slot id stored in p[] that is not a slot of the plan (squeeze-excite)
     bad = copy.deepcopy(f32)
-    gated = [i for i, o in enumerate(bad.ops) if (o.kind == pk.F32_DWPW and o.p[13]) or (o.kind == pk.F32_PW and o.p[5])]
+    gated = [i for i, o in enumerate(bad.ops) if o.kind in (pk.F32_DWPW, pk.F32_PW) and o.get("has_gate")]
     assert gated
     o = bad.ops[gated[0]]
-    o.p[14 if o.kind == pk.F32_DWPW else 6] = 10_000
+    o.set("gate_slot", 10_000)
     refused(bad, "slot id 10000 is not a slot")
     # 3) a referenced slot without storage
     bad = copy.deepcopy(i8)
@@ -394,31 +405,31 @@ def test_blob_check_accepts_every_lowered_plan_and_refuses_damaged_ones():
     # 4) a constant tensor shorter than the operator reads
     bad = copy.deepcopy(i8)
     o = bad.ops[oi]
-    bad.tensors[o.t[4]] = bad.tensors[o.t[4]].reshape(-1)[:64].copy()
+    bad.tensors[o.get("pw_w")] = bad.tensors[o.get("pw_w")].reshape(-1)[:64].copy()
     refused(bad, "holds 64 bytes, the operator reads")
     # 5) geometry that does not follow from the input size
     bad = copy.deepcopy(i8)
-    bad.ops[oi].p[6] -= 1
+    bad.ops[oi].set("OH", bad.ops[oi].get("OH") - 1)
     refused(bad, "does not follow from input")
     # 6) residual slot missing
     bad = copy.deepcopy(i8)
-    oj = next(i for i, o in enumerate(bad.ops) if o.kind == pk.I8_DWPW and o.p[18])
+    oj = next(i for i, o in enumerate(bad.ops) if o.kind == pk.I8_DWPW and o.get("has_add"))
     bad.ops[oj].in1 = pk.SLOT_NONE
     refused(bad, "residual")
     # 6b) flags that select a kernel form the block's other fields do not describe
     bad = copy.deepcopy(i8)
-    bad.ops[oi].p[30] = 1  # transposed output on a depthwise + pointwise block
+    bad.ops[oi].set("transposed", 1)  # transposed output on a depthwise + pointwise block
     refused(bad, "not a mel mixer")
     bad = copy.deepcopy(i8)
-    bad.ops[oi].p[34] = 1  # per-channel table on a block whose kernel has none
+    bad.ops[oi].set("has_lut", 1)  # per-channel table on a block whose kernel has none
     refused(bad, "table")
     # 6c) a clamp that is not an int8 range on a value that indexes a 256-entry table (residual ADD tables, the mel mixer's PWL table)
     bad = copy.deepcopy(i8)
-    bad.ops[oj].p[28] = 300
+    bad.ops[oj].set("add_amax", 300)
     refused(bad, "not an int8 range")
     bad = copy.deepcopy(i8)
-    om = next(i for i, o in enumerate(bad.ops) if o.kind == pk.I8_DWPW and o.p[34])
-    bad.ops[om].p[16] = -129
+    om = next(i for i, o in enumerate(bad.ops) if o.kind == pk.I8_DWPW and o.get("has_lut"))
+    bad.ops[om].set("pw_amin", -129)
     refused(bad, "not an int8 range")
     # 7) truncated blob, bad magic
     blob = i8.to_blob()
@@ -443,14 +454,16 @@ def test_context_creation_fails_loudly_without_device():
 
 
 # ------------------------------------------------------------------ strip-kernel constant block (bn_i8_strip.hip)
-def _emulate_strip(cst, x, p, nw, tab=None):
+def _emulate_strip(cst, x, o, nw, tab=None):
     """numpy restatement of ``i8_strip_kernel``'s lane arithmetic (csrc/bn_i8_strip.hip) from the packer's constant block:
     wave w / lane (n, kq) owns channels CW w + CL kq .. of column n, row-transposed depthwise weights, folded requantisation
     addends, A fragments with permuted rows per channel slice, own value + 128 as the table index of the ADD.
     x: int8 [B][H][W][C]."""
-    H, W, C, S, OH, OW, pt, pl = p[0], p[1], p[2], p[3], p[6], p[7], p[8], p[9]
-    z_in, dw_lo, dw_hi, N, pw_zp, pw_lo, pw_hi = p[10], p[12], p[13], p[14], p[15], p[16], p[17]
-    add = p[18:29]
+    from birdnet_stm32.models._pack import ADD_FIELDS
+
+    H, W, C, S, OH, OW, pt, pl = (o.get(k) for k in ("H", "W", "Cin", "sh", "OH", "OW", "pt", "pl"))
+    z_in, dw_lo, dw_hi, N, pw_zp, pw_lo, pw_hi = (o.get(k) for k in ("dw_zp_in", "dw_amin", "dw_amax", "Cout", "pw_zp_out", "pw_amin", "pw_amax"))
+    add = [o.get(k) for k in ADD_FIELDS]
     CW, CWO = C // nw, N // nw
     CL, COL = CW // 4, CWO // 4
     QL, NT = CL // 4, CWO // 16
@@ -519,31 +532,32 @@ def test_strip_constant_block_reproduces_the_oracle():
     from conftest import synth_chunks
 
     plan = lower_model_file(TFLITE_PATH, keep_all=True, fuse=True)
-    strip_ops = [o for o in plan.ops if o.kind == pk.I8_DWPW and o.p[35]]
+    strip_ops = [o for o in plan.ops if o.kind == pk.I8_DWPW and o.get("strip")]
     assert [o.name for o in strip_ops] == ["t102", "t104", "t107", "t110", "t112", "t115", "t118", "t121", "t123", "t126"]
     S = np.stack([stft.hybrid_spectrogram(a) for a in synth_chunks(2)])[..., None]
     _, env = Int8Interpreter(load_tflite(TFLITE_PATH)).invoke(S, return_all=True)
     by_val = {o.out: o for o in plan.ops}
     for o in strip_ops:
         src = by_val[o.in0]
-        x = env[int(src.name[1:])].reshape(2, o.p[0], o.p[1], o.p[2])
-        want = env[int(o.name[1:])].reshape(2, o.p[6], o.p[7], o.p[14])
-        if o.p[18]:
+        x = env[int(src.name[1:])].reshape(2, o.get("H"), o.get("W"), o.get("Cin"))
+        want = env[int(o.name[1:])].reshape(2, o.get("OH"), o.get("OW"), o.get("Cout"))
+        if o.get("has_add"):
             assert o.in1 == o.in0  # the residual is the block input
         from birdnet_stm32.models._lower_i8 import strip_waves
 
-        nw = strip_waves(o.p[2], o.p[14], o.p[3], o.p[7], bool(o.p[18]))
-        assert nw == {32: 1, 64: 2, 128: 4, 256: 8}[o.p[2]]
-        tab = np.asarray(plan.tensors[o.t[10]], np.int8).reshape(256, 256) if o.p[18] else None
-        got = _emulate_strip(np.asarray(plan.tensors[o.t[9]], np.int32), x, o.p, nw, tab)
+        nw = strip_waves(o.get("Cin"), o.get("Cout"), o.get("sh"), o.get("OW"), bool(o.get("has_add")))
+        assert nw == {32: 1, 64: 2, 128: 4, 256: 8}[o.get("Cin")]
+        tab = np.asarray(plan.tensors[o.get("add_tab")], np.int8).reshape(256, 256) if o.get("has_add") else None
+        got = _emulate_strip(np.asarray(plan.tensors[o.get("strip_cst")], np.int32), x, o, nw, tab)
         assert np.array_equal(got, want), f"{o.name}: {(got != want).sum()} of {got.size} values differ"
 
 
-def _emulate_front_strip(cst, fe, p):
+def _emulate_front_strip(cst, fe, o):
     """numpy restatement of ``i8_front_strip_kernel`` from its constant block: the stem as a matrix product with contraction
     index 8 * (window row) + column, lane (n, kq) reading input row (stem row - 1 + kq).  fe: int8 [B][H0][W0]."""
-    H0, W0, OH, OW = p[0], p[1], p[4], p[5]
-    z_fe, z_st, st_lo, st_hi, dw_lo, dw_hi, pw_lo, pw_hi = p[6], p[7], p[8], p[9], p[11], p[12], p[14], p[15]
+    H0, W0, OH, OW = (o.get(k) for k in ("H0", "W0", "OH", "OW"))
+    z_fe, z_st, st_lo, st_hi, dw_lo, dw_hi, pw_lo, pw_hi = (o.get(k) for k in ("stem_zp_in", "stem_zp_out", "stem_amin", "stem_amax", "dw_amin", "dw_amax",
+                                                                               "pw_amin", "pw_amax"))
     sta = cst[0:64].view(np.int8).reshape(64, 4).astype(np.int64)
     stb = cst[64:80].reshape(4, 4).astype(np.int64)
     stc = cst[80:128].reshape(4, 3, 4).astype(np.int64)
@@ -623,8 +637,8 @@ def test_add_table_is_the_oracles_add_on_every_byte_pair():
 
     _, model, _, _ = _export(next(v for k, v in EXPORT_TOPOLOGIES.items() if "ir" in k))
     plan = lower_i8(model)
-    with_add = [o for o in plan.ops if o.kind == pk.I8_DWPW and o.p[18] and not o.p[29]]
-    assert with_add and all(o.t[10] >= 0 and plan.tensors[o.t[10]].nbytes == 65536 for o in with_add)
+    with_add = [o for o in plan.ops if o.kind == pk.I8_DWPW and o.get("has_add") and not o.get("has_dw")]
+    assert with_add and all(o.get("add_tab") >= 0 and plan.tensors[o.get("add_tab")].nbytes == 65536 for o in with_add)
 
 
 def test_front_strip_constant_block_reproduces_the_oracle():
@@ -640,11 +654,11 @@ def test_front_strip_constant_block_reproduces_the_oracle():
 
     plan = lower_model_file(TFLITE_PATH, keep_all=True, fuse=True)
     (o,) = [o for o in plan.ops if o.kind == pk.I8_FRONT]
-    assert o.p[16] == 1 and o.t[12] >= 0
+    assert o.get("strip") == 1 and o.get("strip_cst") >= 0
     S = np.stack([stft.hybrid_spectrogram(a) for a in synth_chunks(2)])[..., None]
     _, env = Int8Interpreter(load_tflite(TFLITE_PATH)).invoke(S, return_all=True)
     src = {q.out: q for q in plan.ops}[o.in0]
-    fe = env[int(src.name[1:])].reshape(2, o.p[0], o.p[1])
-    want = env[int(o.name[1:])].reshape(2, o.p[4], o.p[5], o.p[3])
-    got = _emulate_front_strip(np.asarray(plan.tensors[o.t[12]], np.int32), fe, o.p)
+    fe = env[int(src.name[1:])].reshape(2, o.get("H0"), o.get("W0"))
+    want = env[int(o.name[1:])].reshape(2, o.get("OH"), o.get("OW"), o.get("N"))
+    got = _emulate_front_strip(np.asarray(plan.tensors[o.get("strip_cst")], np.int32), fe, o)
     assert np.array_equal(got, want), f"{(got != want).sum()} of {got.size} values differ"

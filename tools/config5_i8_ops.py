@@ -32,17 +32,18 @@ torch.cuda.synchronize()
 for q in r.profile_collect():
     if not q["launches"]:
         continue
-    p = q["p"]
+    g = r.plan.ops[q["op"]].get if q["p"] else None  # field of the operator's record by name (the STFT stages have none)
     ms = q["ms"] / q["launches"]
     if q["kind"] == "i8_dwpw":
-        desc = f"H{p[0]} W{p[1]} Cin{p[2]} s{p[3]} -> OH{p[6]} OW{p[7]} Cout{p[14]} dw{p[29]} add{p[18]} strip{p[35]}"
-        gb = B * (p[0] * p[1] * p[2] + p[6] * p[7] * p[14]) / ms / 1e6
+        desc = f"H{g('H')} W{g('W')} Cin{g('Cin')} s{g('sh')} -> OH{g('OH')} OW{g('OW')} Cout{g('Cout')} dw{g('has_dw')} add{g('has_add')} strip{g('strip')}"
+        gb = B * (g("H") * g("W") * g("Cin") + g("OH") * g("OW") * g("Cout")) / ms / 1e6
     elif q["kind"] in ("i8_dw", "i8_stem"):
-        desc = f"H{p[0]} W{p[1]} C{p[2]} s{p[3]} -> OH{p[6]} OW{p[7]}"
-        gb = B * (p[0] * p[1] * (p[2] if q["kind"] == "i8_dw" else 1) + p[6] * p[7] * p[2]) / ms / 1e6
+        C = g("C" if q["kind"] == "i8_dw" else "Cout")
+        desc = f"H{g('H')} W{g('W')} C{C} s{g('sh')} -> OH{g('OH')} OW{g('OW')}"
+        gb = B * (g("H") * g("W") * (C if q["kind"] == "i8_dw" else 1) + g("OH") * g("OW") * C) / ms / 1e6
     elif q["kind"] == "i8_scale":
-        desc = f"P{p[0]} C{p[1]}"
-        gb = B * 2 * p[0] * p[1] / ms / 1e6
+        desc = f"P{g('P')} C{g('C')}"
+        gb = B * 2 * g("P") * g("C") / ms / 1e6
     else:
-        desc, gb = str(p[:4]), 0.0
+        desc, gb = str(q["p"][:4]), 0.0
     print(f"{q['kind']:10s} {q['name']:6s} {ms:7.3f} ms  {gb:8.1f} GB/s  {desc}")

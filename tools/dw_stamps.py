@@ -54,7 +54,7 @@ print("|---|---|---|---|---|---|---|---|---|")
 seen = set()
 ms_by_name = {q["name"]: q["ms"] for q in rows}
 for op in ops:
-    H, Wd, C, sh = op.p[0], op.p[1], op.p[2], op.p[3]
+    H, Wd, C, sh = (op.get(k) for k in ("H", "W", "C", "sh"))
     if (C, H) in seen:
         continue
     seen.add((C, H))
