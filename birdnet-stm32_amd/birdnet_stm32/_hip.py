@@ -31,6 +31,7 @@ EXPORTS = (
     "bn_blob_check", "bn_debug_requant", "bn_stft_mag_exact", "bn_debug_input_bytes", "bn_debug_guard_stats", "bn_debug_tail_form", "bn_debug_mid_form", "bn_debug_mid_plan", "bn_debug_mid_split_giveups",
     "bn_forward_embed", "bn_infer_audio_embed", "bn_model_get_embedding_info", "bn_ingest_resample_span",
     "bn_head_forward", "bn_probe_create", "bn_probe_destroy", "bn_probe_epoch", "bn_probe_loss", "bn_probe_get", "bn_probe_set",
+    "bn_short_time_energy", "bn_activity_counts",
 )  # fmt: skip
 
 EMB_F32, EMB_I8 = 0, 1  # BN_EMB_* (include/birdnet_hip.h)
@@ -124,6 +125,8 @@ def load_library(path: str | None = None):
     lib.bn_ctx_reset_options.argtypes = [c_void_p]
     lib.bn_preload_kernels.argtypes = [c_void_p]
     lib.bn_rank_orders.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]
+    lib.bn_short_time_energy.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
+    lib.bn_activity_counts.argtypes = [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p]
     lib.bn_host_alloc_pinned.argtypes = [c_void_p, ctypes.c_size_t]
     lib.bn_host_alloc_pinned.restype = c_void_p
     lib.bn_host_free_pinned.argtypes = [c_void_p]

@@ -23,6 +23,13 @@ frames those outputs touch.  Segments take the same ring as groups (pinned slab 
 ``bn_ingest_resample_span`` launch into a device buffer that holds the file's resampled samples.  Behind its last segment the file's
 chunks are cut and scored in slices of ``group_chunks``.  Device memory: one file's mono samples plus one slice of chunks.
 
+**Selection** (``select=ChunkSelection(...)``, opt-in): instead of every grid chunk, each file contributes its few most active chunks, chosen
+as the reference's training loader chooses them (data/generator.py ``_process_file``; ``audio/activity.py``).  Per group, behind the resampler:
+files with more grid chunks than ``candidate_chunks`` get their short-time energy from ``bn_short_time_energy`` (one launch per group), the host
+turns the energies into smart-crop starts, one ``bn_ingest_chunks`` cuts the candidates, ``bn_stft_mag(normalize=1)`` + ``bn_activity_counts``
+give every candidate's active-element count, the host ranks and thresholds per file, a second ``bn_ingest_chunks`` cuts the selected rows and only
+those are scored.  Two host round trips per group; reader and copy threads keep running beside them.  Needs ``chunk_overlap = 0``.
+
 There is no CPU fallback: the module needs ``libbirdnet_hip.so`` and a GPU.  Files that are not plain PCM / float32 WAV (FLAC,
 8-bit, float64, containers only ``soundfile`` reads) are decoded on the host by ``audio.ingest.read_pcm_window`` inside the read
 stage and copied into the slab; their arithmetic still happens on the device.
@@ -273,6 +280,116 @@ def cut_groups(nbytes: np.ndarray, n_chunks: np.ndarray, slab_bytes: int, group_
 
 
 @dataclass
+class ChunkSelection:
+    """Which chunks of a file the pipeline keeps (the reference loader's ``max_chunks_per_file`` / ``snr_threshold`` /
+    ``candidate_chunks_per_file``, data/generator.py:87-157; the remaining fields are the defaults of ``audio/activity.py``).
+
+    A file with more grid chunks than ``candidate_chunks`` is cropped around its loudest stretches (``smart_crop``), any other keeps its
+    grid; candidates are ranked by activity ratio, those under ``activity_threshold`` dropped (one is always kept), the first
+    ``max_chunks_per_file`` taken.  ``exact_stft``: rank the bytes of ``bn_stft_mag_exact`` instead of the fast float32 STFT."""
+
+    max_chunks_per_file: int
+    activity_threshold: float = 0.1
+    candidate_chunks: int | None = None
+    k: float = 2.0
+    max_active: float = 0.8
+    subsample: int = 512
+    energy_percentile: float = 75.0
+    exact_stft: bool = False
+
+    def __post_init__(self):
+        if int(self.max_chunks_per_file) < 1:
+            raise ValueError(f"max_chunks_per_file must be at least 1, got {self.max_chunks_per_file}")
+        self.max_chunks_per_file = int(self.max_chunks_per_file)
+        if self.candidate_chunks is None:
+            self.candidate_chunks = min(8, max(4, 2 * self.max_chunks_per_file))
+        self.candidate_chunks = int(self.candidate_chunks)
+        if self.candidate_chunks < 1:
+            raise ValueError(f"candidate_chunks must be at least 1, got {self.candidate_chunks}")
+        if not 1 <= int(self.subsample) <= 512:
+            raise ValueError(f"subsample={self.subsample}: bn_activity_counts takes the median over 1..512 elements")
+
+    def crops(self, n_chunks) -> np.ndarray:
+        """Per file: does it go through the smart crop (more grid chunks than candidates) or keep its grid?"""
+        return np.asarray(n_chunks, np.int64) > self.candidate_chunks
+
+    def candidate_counts(self, n_chunks) -> np.ndarray:
+        """Upper bound of candidate rows per file (a crop may find fewer salient stretches than ``candidate_chunks``)."""
+        return np.minimum(np.asarray(n_chunks, np.int64), self.candidate_chunks)
+
+    def max_counts(self, n_chunks) -> np.ndarray:
+        """Upper bound of selected rows per file."""
+        return np.minimum(np.asarray(n_chunks, np.int64), self.max_chunks_per_file)
+
+
+def selection_from_args(args, activity_threshold: float | None = None) -> ChunkSelection | None:
+    """The selection the ``--max_chunks_per_file`` / ``--activity_threshold`` / ``--candidate_chunks`` flags of ``probe`` and ``embed`` ask for
+    (``None`` when the first is 0 or absent)."""
+    n = int(getattr(args, "max_chunks_per_file", 0) or 0)
+    if n < 0:
+        raise ValueError(f"--max_chunks_per_file must be >= 0, got {n}")
+    if n == 0:
+        return None
+    cand = int(getattr(args, "candidate_chunks", 0) or 0)
+    if cand < 0:
+        raise ValueError(f"--candidate_chunks must be >= 0 (0 = the default min(8, max(4, 2 N))), got {cand}")
+    thr = float(getattr(args, "activity_threshold", 0.1)) if activity_threshold is None else float(activity_threshold)
+    return ChunkSelection(n, activity_threshold=thr, candidate_chunks=cand if cand > 0 else None)
+
+
+STE_FRAME, STE_HOP = 1024, 512   # what bn_short_time_energy implements; smart_crop derives them for every chunk of >= 4096 samples
+
+
+def ste_frame_counts(n_out, crop) -> np.ndarray:
+    """Energy frames per window: ``1 + (n - 1024) // 512`` for the windows that are cropped, 0 for the others."""
+    n = np.asarray(n_out, np.int64)
+    return np.where(np.asarray(crop, bool) & (n >= STE_FRAME), 1 + (n - STE_FRAME) // STE_HOP, 0).astype(np.int64)
+
+
+def candidate_table(n_out: np.ndarray, profiles: list, sel: ChunkSelection, sample_rate: int, chunk_duration: float):
+    """Candidate chunks of a group's files, in file order: ``(start within the window, valid samples, owner file)`` arrays.
+
+    ``profiles[j]`` is file j's short-time-energy profile when the file is cropped (its starts are then ``smart_crop``'s, off the grid), else
+    ``None`` (it keeps the chunk grid without overlap, the reference's ``split_audio_into_chunks`` as its loader calls it).  Host only."""
+    from birdnet_stm32.audio import activity
+
+    size = int(sample_rate * chunk_duration)
+    n_out = np.asarray(n_out, np.int64)
+    start, valid, _owner, counts, _ = chunk_table_arrays(n_out, sample_rate, chunk_duration, 0.0)
+    first = np.cumsum(counts) - counts
+    starts, valids, owners = [], [], []
+    for j, prof in enumerate(profiles):
+        if prof is not None:
+            st = np.asarray(activity._crop_starts(prof, int(n_out[j]), size, STE_HOP, sel.candidate_chunks, sel.energy_percentile), np.int64)
+            va = np.full(st.shape[0], size, np.int32)
+        else:
+            st, va = start[first[j] : first[j] + counts[j]], valid[first[j] : first[j] + counts[j]]
+        starts.append(st)
+        valids.append(va)
+        owners.append(np.full(st.shape[0], j, np.int64))
+    if not starts:
+        return np.zeros(0, np.int64), np.zeros(0, np.int32), np.zeros(0, np.int64)
+    return np.concatenate(starts).astype(np.int64), np.concatenate(valids).astype(np.int32), np.concatenate(owners)
+
+
+def rank_rows(active: np.ndarray, n_feat: int, owner: np.ndarray, n_files: int, sel: ChunkSelection):
+    """From the candidates' active-element counts to the rows that stay: ``(candidate indices per file in rank order, rows kept per file)``.
+    Ratio, ``max_active``, ``np.argsort(r)[::-1]`` and the threshold in float64, as ``audio/activity.py`` does them.  Host only."""
+    from birdnet_stm32.audio import activity
+
+    ratios = np.array([activity.ratio_from_count(int(a), n_feat, sel.max_active) for a in active], np.float64)
+    first = np.concatenate([[0], np.cumsum(np.bincount(np.asarray(owner, np.int64), minlength=n_files))]) if n_files else np.zeros(1, np.int64)
+    rows, kept_per_file = [], np.zeros(n_files, np.int64)
+    for j in range(n_files):
+        a, b = int(first[j]), int(first[j + 1])
+        if b > a:
+            kept = activity.rank_by_activity(ratios[a:b], sel.activity_threshold)[: sel.max_chunks_per_file]
+            rows.extend(a + r for r in kept)
+            kept_per_file[j] = len(kept)
+    return np.asarray(rows, np.int64), kept_per_file
+
+
+@dataclass
 class GroupLayout:
     """Where one group's windows lie in its slab and what its offset table holds (pure host data; see ``layout_group``)."""
 
@@ -290,6 +407,7 @@ class GroupLayout:
     off_src: int              # chunk source positions [n_chunks] (int64),
     off_valid: int            # chunk valid lengths [n_chunks] (int32, two per word),
     off_owner: int            # chunk window indices [n_chunks] (int32)
+    win_of_file: np.ndarray | None = None   # window index of files[j] (selection builds its own chunk tables from it)
 
 
 def layout_group(tab: FileTable, lo: int, hi: int, base_ptr: int, capacity: int, table: np.ndarray, sample_rate: int, chunk_duration: float,
@@ -379,7 +497,7 @@ def layout_group(tab: FileTable, lo: int, hi: int, base_ptr: int, capacity: int,
     cur += half
     counts = np.zeros(hi - lo, np.int64)
     counts[alive - lo] = counts_f
-    return GroupLayout(lo, hi, alive, counts, subs, n_windows, n_chunks, int(out_off[-1]), used, cur, off_out, off_src, off_valid, off_owner)
+    return GroupLayout(lo, hi, alive, counts, subs, n_windows, n_chunks, int(out_off[-1]), used, cur, off_out, off_src, off_valid, off_owner, win_of_file)
 
 
 @dataclass
@@ -505,7 +623,7 @@ class EvaluatePipeline:
     def __init__(self, runner, sample_rate: int, chunk_duration: float, chunk_overlap: float = 0.0, max_duration=60,
                  slab_bytes: int = 256 << 20, group_chunks: int | None = None, readers: int | None = None, pinned_slabs: int = 3,
                  ramp: tuple = (8, 4, 2), numa_pin: bool | None = None, read_mode: str | None = None, stream_long: bool = False,
-                 mono_budget_bytes: int = MONO_BUDGET_BYTES):
+                 mono_budget_bytes: int = MONO_BUDGET_BYTES, select: ChunkSelection | None = None):
         import torch
 
         self.torch = torch
@@ -554,6 +672,25 @@ class EvaluatePipeline:
         self.mono_budget_bytes = int(mono_budget_bytes)
         self._long_mono = self._long_peak = None
         self._long_payload: dict = {}   # streamed host-decoded file -> its decoded window (producer thread)
+        # chunk selection (module docstring): None = every grid chunk, the path every earlier caller takes
+        self.select = select
+        self.selected_rows: list = []   # per run(): (file index into paths, start sample within its window) of every output row, in row order
+        self.select_stats: dict = {}
+        if select is not None:
+            from birdnet_stm32.models import _pack as pk
+
+            if self.stream_long:
+                raise ValueError("chunk selection and stream_long cannot be combined: a streamed file's samples are never on the device at once "
+                                 "in the grouped form the selection works on; lower max_duration or drop one of the two")
+            if runner.input_kind == pk.INPUT_MEL:
+                raise ValueError("chunk selection ranks the hybrid frontend's spectrograms or the raw frontend's waveforms; models with a "
+                                 "precomputed frontend (librosa / log_mel / mfcc) are not supported")
+            if self.ov > 0.0:
+                raise ValueError("chunk selection works on chunks without overlap, as the reference's loader cuts them (cropped files take their "
+                                 f"chunks off the grid anyway); chunk_overlap={self.ov} given")
+            if self.size < 4 * STE_FRAME:
+                raise ValueError(f"chunk selection needs chunks of at least {4 * STE_FRAME} samples (bn_short_time_energy implements frames of "
+                                 f"{STE_FRAME} at hops of {STE_HOP}); {self.size} given")
 
     def _mark(self, name: str) -> None:
         """Timeline of one run (``BN_PIPELINE_TRACE=1``: ``stats["trace"]`` = [(what, seconds since run() started, thread)]) — where a COLD call's
@@ -755,7 +892,7 @@ class EvaluatePipeline:
         return _Segment(i, seg, first, last, slot, e1, (e0, e1), read_s, nbytes)
 
     # -- stage 3: consumer (caller's thread and stream) -----------------------------------------------------------------------
-    def _compute_group(self, st: _Staged, scores, row0: int, batch: int, lat_events: list | None, stats: dict) -> None:
+    def _compute_group(self, st: _Staged, scores, row0: int, batch: int, lat_events: list | None, stats: dict, ftab: FileTable | None = None) -> None:
         torch = self.torch
         lib = self.ctx.lib
         cur = torch.cuda.current_stream(self.dev)
@@ -781,7 +918,10 @@ class EvaluatePipeline:
             _hip.check(lib.bn_ingest_resample(self.ctx.handle, slab + pos, fmt, ch, tab + 8 * in_off, tab + 8 * (g.off_out + w0), nw, max_in, max_out,
                                               d_taps.data_ptr() if d_taps is not None else None, up, down, per_phase, pre,
                                               self._mono.data_ptr(), self._peak.data_ptr() + 4 * w0, stream))
-        if g.n_chunks:
+        keep = None
+        if self.select is not None:
+            keep = self._select_rows(g, ftab, tab_dev=tab, stream=stream)   # (rewrites g.counts / g.n_chunks)
+        elif g.n_chunks:
             _hip.check(lib.bn_ingest_chunks(self.ctx.handle, self._mono.data_ptr(), self._peak.data_ptr(), tab + 8 * g.off_src, tab + 8 * g.off_valid,
                                             tab + 8 * g.off_owner, g.n_chunks, self.size, self._chunks.data_ptr(), stream))
         done = torch.cuda.Event()
@@ -810,6 +950,129 @@ class EvaluatePipeline:
         ev[2].record(cur)
         self._mark("compute: inference launched")
         stats["_events"].append((st.h2d_events, ev, g.used + 8 * g.tab_len))
+        if keep is not None:
+            stats.setdefault("_keep", []).append(keep)   # (the second bn_ingest_chunks reads its tables asynchronously)
+
+    def _select_rows(self, g: GroupLayout, tab: FileTable, tab_dev: int, stream) -> tuple:
+        """Selection for one group whose windows are resampled on the stream (module docstring).  On return ``self._chunks[: g.n_chunks]`` holds the
+        selected rows, per file in rank order, and ``g.counts`` / ``g.n_chunks`` describe them.  Two host synchronisations: the energies
+        (``_energies``) and the counts (``_count_candidates``); the decisions between them are ``candidate_table`` and ``rank_rows``."""
+        torch, lib, sel, dev = self.torch, self.ctx.lib, self.select, self.dev
+        files, wof = g.files, g.win_of_file
+        n_out = tab.n_out[files].astype(np.int64)
+        by_window = np.zeros(g.n_windows, np.int64)
+        by_window[wof] = n_out
+        out_off = np.concatenate([[0], np.cumsum(by_window)])
+        crop = sel.crops(tab.n_chunks[files])
+        times = {}
+        t0 = time.perf_counter()
+        ste, frame_off = self._energies(g, by_window, crop, tab_dev, stream, times)
+        t1 = time.perf_counter()
+        profiles = [ste[frame_off[w] : frame_off[w + 1]] if c else None for w, c in zip(wof.tolist(), crop.tolist())]
+        c_start, c_valid, c_owner = candidate_table(n_out, profiles, sel, self.sr, self.cd)
+        n_cand = int(c_start.shape[0])
+        if n_cand > self._chunks.shape[0]:
+            raise RuntimeError("chunk selection: more candidates than the group's planned chunks")
+        c_src = c_start + out_off[wof[c_owner]]
+        c_win = wof[c_owner].astype(np.int32)
+        t2 = time.perf_counter()
+        active, n_feat = self._count_candidates(c_src, c_valid, c_win, stream, times)
+        t3 = time.perf_counter()
+        keep_rows, new_counts = rank_rows(active, n_feat, c_owner, files.shape[0], sel)
+        n_sel = int(keep_rows.shape[0])
+        keep = None
+        if n_sel:   # the selected rows, cut again from the resampled windows in their final order (the bytes bn_ingest_chunks gave the candidates)
+            keep = tuple(torch.from_numpy(np.ascontiguousarray(a[keep_rows])).to(dev) for a in (c_src, c_valid, c_win))
+            _hip.check(lib.bn_ingest_chunks(self.ctx.handle, self._mono.data_ptr(), self._peak.data_ptr(), keep[0].data_ptr(), keep[1].data_ptr(),
+                                            keep[2].data_ptr(), n_sel, self.size, self._chunks.data_ptr(), stream))
+            self.selected_rows.extend(zip(files[c_owner[keep_rows]].tolist(), c_start[keep_rows].tolist()))
+        t4 = time.perf_counter()
+        counts_all = np.zeros(g.hi - g.lo, np.int64)
+        counts_all[files - g.lo] = new_counts
+        g.counts, g.n_chunks = counts_all, n_sel
+        # wall seconds of the four steps, and inside the two device steps the kernels' own time from events: what is left of a step is its
+        # launches, table uploads and the round trip to the host
+        times.update(candidates=n_cand, selected=n_sel, cropped_files=int(crop.sum()), ste_s=t1 - t0, host_crop_s=t2 - t1, features_s=t3 - t2,
+                     host_rank_s=t4 - t3)
+        times["round_trip1_s"] = times["ste_s"] - times.get("ste_kernel_s", 0.0)
+        times["round_trip2_s"] = times["features_s"] - times.get("cut_kernel_s", 0.0) - times.get("stft_kernel_s", 0.0) - times.get("count_kernel_s", 0.0)
+        for key, v in times.items():
+            self.select_stats[key] = self.select_stats.get(key, 0) + v
+        return keep
+
+    def _timed(self, what: str, pairs: list):
+        """Bracket a launch with two events on the current stream; ``_elapsed`` adds them up once the stream has been synchronised."""
+        torch = self.torch
+        cur = torch.cuda.current_stream(self.dev)
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        pairs.append((what, a, b))
+        a.record(cur)
+        return lambda: b.record(cur)
+
+    @staticmethod
+    def _elapsed(pairs: list, times: dict) -> None:
+        for what, a, b in pairs:
+            times[what] = times.get(what, 0.0) + a.elapsed_time(b) / 1e3
+
+    def _energies(self, g: GroupLayout, by_window: np.ndarray, crop: np.ndarray, tab_dev: int, stream, times: dict):
+        """Short-time energies of the cropped files: one ``bn_short_time_energy`` launch over the group's windows (the others get an empty slice of
+        the output) and round trip 1, 4 bytes per 512 samples.  Returns ``(energies, frame offsets per window)``."""
+        torch, dev = self.torch, self.dev
+        frame_off = np.zeros(g.n_windows + 1, np.int64)
+        if not crop.any():
+            return np.zeros(0, np.float32), frame_off
+        crop_w = np.zeros(g.n_windows, bool)
+        crop_w[g.win_of_file] = crop
+        np.cumsum(ste_frame_counts(by_window, crop_w), out=frame_off[1:])
+        d_frame_off = torch.from_numpy(frame_off).to(dev)
+        d_index = torch.arange(g.n_windows, dtype=torch.int32, device=dev)
+        d_ste = torch.empty(max(int(frame_off[-1]), 1), dtype=torch.float32, device=dev)
+        pairs: list = []
+        done = self._timed("ste_kernel_s", pairs)
+        _hip.check(self.ctx.lib.bn_short_time_energy(self.ctx.handle, self._mono.data_ptr(), self._peak.data_ptr(), tab_dev + 8 * g.off_out,
+                                                     d_index.data_ptr(), d_frame_off.data_ptr(), g.n_windows, STE_FRAME, STE_HOP, d_ste.data_ptr(), stream))
+        done()
+        ste = d_ste.cpu().numpy()   # (synchronises)
+        self._elapsed(pairs, times)
+        return ste, frame_off
+
+    def _count_candidates(self, c_src: np.ndarray, c_valid: np.ndarray, c_win: np.ndarray, stream, times: dict):
+        """Cut the candidates into ``self._chunks``, compute their features (hybrid frontend: ``bn_stft_mag(normalize=1)`` in slices of ``max_batch``;
+        raw frontend: the chunks themselves) and count the active elements per candidate; round trip 2, 4 bytes per candidate.
+        Returns ``(counts, elements per feature map)``."""
+        from birdnet_stm32.audio import activity
+        from birdnet_stm32.models import _pack as pk
+        from birdnet_stm32.models.runners import stft_device
+
+        torch, lib, sel, dev = self.torch, self.ctx.lib, self.select, self.dev
+        n_cand = int(c_src.shape[0])
+        raw = self.runner.input_kind == pk.INPUT_WAVEFORM
+        n_feat = self.size if raw else 257 * self.runner.spec_width
+        if not n_cand:
+            return np.zeros(0, np.int32), n_feat
+        pairs: list = []
+        d_src, d_valid, d_win = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (c_src, c_valid, c_win))
+        done = self._timed("cut_kernel_s", pairs)
+        _hip.check(lib.bn_ingest_chunks(self.ctx.handle, self._mono.data_ptr(), self._peak.data_ptr(), d_src.data_ptr(), d_valid.data_ptr(),
+                                        d_win.data_ptr(), n_cand, self.size, self._chunks.data_ptr(), stream))
+        done()
+        d_active = torch.empty(n_cand, dtype=torch.int32, device=dev)
+        d_idx = torch.from_numpy(activity.subsample_indices(n_feat, sel.subsample).astype(np.int32)).to(dev)
+        step = n_cand if raw else self.runner.max_batch
+        for b0 in range(0, n_cand, step):
+            nb = min(step, n_cand - b0)
+            feat = self._chunks[b0 : b0 + nb]
+            if not raw:
+                done = self._timed("stft_kernel_s", pairs)
+                feat = stft_device(self.ctx, feat, 512, None, self.runner.spec_width, True, exact=sel.exact_stft)
+                done()
+            done = self._timed("count_kernel_s", pairs)
+            _hip.check(lib.bn_activity_counts(self.ctx.handle, feat.data_ptr(), nb, n_feat, d_idx.data_ptr(), d_idx.numel(), float(sel.k),
+                                              d_active.data_ptr() + 4 * b0, None, stream))
+            done()
+        active = d_active.cpu().numpy()   # (synchronises)
+        self._elapsed(pairs, times)
+        return active, n_feat
 
     def _compute_segment(self, sg: _Segment, tab: FileTable, stats: dict) -> None:
         """One ``bn_ingest_resample_span`` launch: outputs ``[o0, o1)`` of the streamed file into its mono buffer, its peak folded in."""
@@ -919,6 +1182,9 @@ class EvaluatePipeline:
             tab = table if table is not None else plan_files(paths, self.sr, self.cd, self.ov, self.max_duration, self.readers)
             stats["probe_s"] = time.perf_counter() - t_start
             streamed = long_files(tab, self.sr, self.slab_bytes) if self.stream_long else np.zeros(len(tab.paths), bool)
+            self.selected_rows, self.select_stats = [], {}
+            if self.select is not None and measure_latency:
+                raise ValueError("chunk selection synchronises with the host inside a group: per-chunk latencies are not measured with it")
             if streamed.any():
                 items = self._plan_items(tab, streamed)
                 groups = [(it[1], it[2]) for it in items if it[0] == "group"]
@@ -996,7 +1262,7 @@ class EvaluatePipeline:
                             counts[g.file] = self._finish_stream(tab, g.file, scores, row, stats)
                             row += int(counts[g.file])
                         continue
-                    self._compute_group(g, scores, row, int(batch_size or self.runner.max_batch), lat_events, stats)
+                    self._compute_group(g, scores, row, int(batch_size or self.runner.max_batch), lat_events, stats, tab)
                     counts[g.lay.lo : g.lay.hi] = g.lay.counts
                     row += g.lay.n_chunks
                     read_s += g.read_s
@@ -1029,6 +1295,8 @@ class EvaluatePipeline:
                      infer_s=infer_ms / 1e3, wall_s=time.perf_counter() - t_start, readers=self.readers, slab_bytes=self.slab_bytes,
                      group_chunks=self.group_chunks, local_world=_pcmio.local_world_size(), numa=dict(self.numa), read_mode=_pcmio.set_read_mode(None), slab_wait_s=round(self._wait_s, 4),
                      read_s_per_group=read_groups[:32])
+        if self.select is not None:
+            stats["select"] = dict(self.select_stats)
         if self._trace is not None:
             stats["trace"] = list(self._trace)
         if self._emb is not None:

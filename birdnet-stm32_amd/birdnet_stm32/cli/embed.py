@@ -24,6 +24,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--dtype", type=str, default="float32", choices=["float32", "int8"], help="int8: the raw bytes of an INT8 model")
     p.add_argument("--overlap", type=float, default=0.0, help="Chunk overlap (seconds)")
     p.add_argument("--max_duration", type=float, default=60, help="Seconds read from the start of each file")
+    p.add_argument("--max_chunks_per_file", type=int, default=0,
+                   help="Keep only each file's N most active chunks (long files are cropped around their loudest stretches first); 0 = off, every "
+                        "chunk is used.  Needs --overlap 0.  The reference's `train` defaults to 3")
+    p.add_argument("--activity_threshold", type=float, default=0.1, help="With --max_chunks_per_file: drop chunks whose activity ratio is lower (one per file is always kept)")
+    p.add_argument("--candidate_chunks", type=int, default=0, help="With --max_chunks_per_file: chunks ranked per file (0 = min(8, max(4, 2 N)), as the reference)")
     p.add_argument("--max_batch", type=int, default=4096, help="Workspace size in chunks = inference slice of the device pipeline")
     p.add_argument("--device", type=int, default=0, help="MI355X index")
     p.add_argument("--skip_undecodable", action="store_true", default=False,
@@ -52,11 +57,16 @@ def collect_inputs(inputs: list[str]) -> list[str]:
 def main(argv=None, runner=None):
     from birdnet_stm32.audio.io import have_soundfile
     from birdnet_stm32.cli.evaluate import resolve_config_path
+    from birdnet_stm32.audio.pipeline import selection_from_args
     from birdnet_stm32.evaluation.embeddings import embed_files, save_embeddings_npz
     from birdnet_stm32.models.frontend import normalize_frontend_name
     from birdnet_stm32.training.config import ModelConfig
 
     args = build_parser().parse_args(argv)
+    try:
+        select = selection_from_args(args)
+    except ValueError as exc:
+        raise SystemExit(f"error: {exc}") from None
     cfg = ModelConfig.load(resolve_config_path(args.model_path, args.model_config)).to_dict()
     files = collect_inputs(args.input)
     if not files:
@@ -82,10 +92,17 @@ def main(argv=None, runner=None):
         runner.configure_precomputed(frontend, int(cfg["sample_rate"]), cfg.get("mag_scale", "none"), int(cfg["fft_length"]), int(cfg["num_mels"]),
                                      int(cfg.get("n_mfcc", 20)))
     overlap = max(0.0, min(float(cfg["chunk_duration"]) - 0.1, args.overlap))
-    res = embed_files(runner, files, chunk_overlap=overlap, max_duration=args.max_duration, pooling=args.pooling, dtype=args.dtype,
-                      sample_rate=int(cfg["sample_rate"]), chunk_duration=float(cfg["chunk_duration"]))
+    try:
+        res = embed_files(runner, files, chunk_overlap=overlap, max_duration=args.max_duration, pooling=args.pooling, dtype=args.dtype,
+                          sample_rate=int(cfg["sample_rate"]), chunk_duration=float(cfg["chunk_duration"]), select=select)
+    except ValueError as exc:
+        if select is None:
+            raise
+        raise SystemExit(f"error: {exc}") from None
     save_embeddings_npz(args.output, res)
     print(f"Embedded {len(files) - len(res.skipped)} files: {res.embeddings.shape[0]} rows x {res.embeddings.shape[1]} ({res.dtype}, pooling {res.pooling}) -> {args.output}")
+    if select is not None:
+        print(f"Selection kept {res.embeddings.shape[0] if res.pooling == 'none' else int(res.chunks_per_file.sum())} of {res.candidate_rows} candidate chunks")
     if res.skipped:
         print(f"Skipped {len(res.skipped)} unreadable or empty files:")
         for p in res.skipped:

@@ -29,6 +29,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--patience", type=int, default=10, help="Early stopping: epochs without a better validation loss")
     p.add_argument("--max_duration", type=float, default=30, help="Seconds read from the start of each file")
     p.add_argument("--overlap", type=float, default=0.0, help="Chunk overlap (seconds)")
+    p.add_argument("--max_chunks_per_file", type=int, default=0,
+                   help="Keep only each file's N most active chunks (long files are cropped around their loudest stretches first); 0 = off, every "
+                        "chunk is used.  Needs --overlap 0.  The reference's `train` defaults to 3")
+    p.add_argument("--activity_threshold", type=float, default=0.1, help="With --max_chunks_per_file: drop chunks whose activity ratio is lower (one per file is always kept); validation files use 0.5, as the reference's linear probe does")
+    p.add_argument("--candidate_chunks", type=int, default=0, help="With --max_chunks_per_file: chunks ranked per file (0 = min(8, max(4, 2 N)), as the reference)")
     p.add_argument("--seed", type=int, default=42, help="Seed of the file shuffle, the initial weights, the batches and the dropout mask")
     p.add_argument("--max_batch", type=int, default=4096, help="Workspace size in chunks = inference slice of the device pipeline")
     p.add_argument("--device", type=int, default=0, help="MI355X index")
@@ -40,6 +45,9 @@ def main(argv=None, runner=None):
 
     args = build_parser().parse_args(argv)
     try:
+        from birdnet_stm32.audio.pipeline import selection_from_args
+
+        selection_from_args(args)   # (bad selection flags are refused before anything is loaded, as `embed` does)
         return run_linear_probe(args, runner=runner)
     except (ValueError, FileNotFoundError) as exc:
         raise SystemExit(f"error: {exc}") from None

@@ -26,7 +26,8 @@ class FileEmbeddings:
 
     ``embeddings``: ``[N, D]`` per chunk (rows in file order) or ``[F, D]`` per file (``pooling`` != "none": one row per file with
     chunks, in file order); ``file_index`` / ``start_s``: owner file (index into ``paths``) and start of each chunk in seconds within its
-    file's read window; ``chunks_per_file``: per path (0 = unreadable or empty, see ``skipped``)."""
+    file's read window; ``chunks_per_file``: per path (0 = unreadable or empty, see ``skipped``).  With a selection the rows of a file are
+    its selected chunks, most active first, and ``start_s`` need not lie on the chunk grid."""
 
     embeddings: np.ndarray
     file_index: np.ndarray
@@ -38,6 +39,7 @@ class FileEmbeddings:
     scale: float
     zero_point: int
     skipped: list = field(default_factory=list)
+    candidate_rows: int = 0   # with a selection: rows that were ranked (``embeddings`` holds the ones that were kept)
 
 
 def chunk_starts(n_out: np.ndarray, sample_rate: int, chunk_duration: float, chunk_overlap: float) -> tuple[np.ndarray, np.ndarray]:
@@ -85,12 +87,15 @@ def embedding_blocks(n_chunks: np.ndarray, row_bytes: int, budget_bytes: int) ->
 
 def embed_files(runner, paths: list[str], chunk_overlap: float = 0.0, max_duration=60, pooling: str = "none", dtype: str | None = None,
                 sample_rate: int = 22050, chunk_duration: float = 3.0, budget_bytes: int = 256 << 20,
-                pipeline_options: dict | None = None) -> FileEmbeddings:
+                pipeline_options: dict | None = None, select=None) -> FileEmbeddings:
     """Embeddings of every chunk of ``paths`` (the chunks ``evaluate`` scores: first ``max_duration`` seconds, ``chunk_duration`` chunks
     with ``chunk_overlap`` seconds of overlap at ``sample_rate``).
 
     ``dtype``: "float32" (default) or "int8" (INT8 models: the MEAN / attention-pool bytes themselves; dequantise with the result's
-    ``scale`` / ``zero_point``).  ``pooling``: "none" (per chunk), "avg" or "max" (per file, float32 only)."""
+    ``scale`` / ``zero_point``).  ``pooling``: "none" (per chunk), "avg" or "max" (per file, float32 only).
+
+    ``select``: an ``audio.pipeline.ChunkSelection`` — only each file's most active chunks are embedded (long files are cropped around
+    their loudest stretches first, as the reference's training loader does); ``None`` embeds every grid chunk."""
     from birdnet_stm32.audio.ingest import pool_scores_device
     from birdnet_stm32.audio.pipeline import EvaluatePipeline, plan_files
 
@@ -110,7 +115,11 @@ def embed_files(runner, paths: list[str], chunk_overlap: float = 0.0, max_durati
     D = int(info["dim"])
     row_bytes = D * (1 if dtype == "int8" else 4)
     sr, cd, ov = int(sample_rate), float(chunk_duration), float(chunk_overlap)
-    pipe = EvaluatePipeline(runner, sr, cd, ov, max_duration=max_duration, **(pipeline_options or {}))
+    opts = dict(pipeline_options or {})
+    if select is not None:
+        opts["select"] = select
+    pipe = EvaluatePipeline(runner, sr, cd, ov, max_duration=max_duration, **opts)
+    sel_file, sel_start, candidates = [], [], 0
     pipe.emb_dtype = dtype
     try:
         tab = plan_files(list(paths), sr, cd, ov, max_duration, pipe.readers)
@@ -120,12 +129,20 @@ def embed_files(runner, paths: list[str], chunk_overlap: float = 0.0, max_durati
             raise ValueError(f"{paths[i]}: its read window of {int(tab.nbytes[i])} bytes exceeds one staging slab ({pipe.slab_bytes} bytes = "
                              f"{pipe.slab_bytes >> 20} MiB); lower max_duration (streaming longer recordings is not supported)")
         counts = tab.n_chunks.astype(np.int64)
+        selected = np.zeros_like(counts)
         parts = []
         for lo, hi in embedding_blocks(counts, row_bytes, budget_bytes):
             if int(counts[lo:hi].sum()) == 0:
                 continue
             _scores, got, _stats, _lat = pipe.run(list(paths[lo:hi]), table=tab.sub(lo, hi))
-            if list(got) != counts[lo:hi].tolist():
+            if select is not None:   # the planned grid count is an upper bound; the pipeline reports what it kept
+                if np.any(np.asarray(got) > select.max_counts(counts[lo:hi])):
+                    raise RuntimeError("the pipeline selected more chunks than the selection allows")
+                sel_file += [lo + f for f, _ in pipe.selected_rows]
+                sel_start += [s0 for _, s0 in pipe.selected_rows]
+                candidates += int(pipe.select_stats.get("candidates", 0))
+                selected[lo:hi] = got
+            elif list(got) != counts[lo:hi].tolist():
                 raise RuntimeError("the pipeline cut a different number of chunks than it planned")
             emb = pipe.embeddings
             if pooling != "none":
@@ -137,11 +154,14 @@ def embed_files(runner, paths: list[str], chunk_overlap: float = 0.0, max_durati
         pipe.close()
     out = np.concatenate(parts) if parts else np.zeros((0, D), np.int8 if dtype == "int8" else np.float32)
     file_index, start_s = chunk_starts(tab.n_out, sr, cd, ov)
+    if select is not None:
+        counts = selected
+        file_index, start_s = np.asarray(sel_file, np.int64), np.asarray(sel_start, np.float64) / float(sr)
     if pooling != "none":
         file_index = np.flatnonzero(counts > 0).astype(np.int64)
         start_s = np.zeros(file_index.shape[0], np.float64)
     skipped = [p for p, k in zip(paths, tab.kind) if k < 0]
-    return FileEmbeddings(out, file_index, start_s, list(paths), counts, pooling, dtype, float(info["scale"]), int(info["zero_point"]), skipped)
+    return FileEmbeddings(out, file_index, start_s, list(paths), counts, pooling, dtype, float(info["scale"]), int(info["zero_point"]), skipped, candidates)
 
 
 def save_embeddings_npz(path: str, res: FileEmbeddings) -> None:

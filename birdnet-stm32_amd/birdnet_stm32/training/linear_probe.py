@@ -449,6 +449,16 @@ def write_history_csv(path: str, history: dict) -> None:
             w.writerow([i + 1, f"{loss:.8g}", f"{val[i]:.8g}" if i < len(val) else ""])
 
 
+def _join_embeddings(a, b):
+    """Two ``FileEmbeddings`` (per chunk) as one over ``a.paths + b.paths``."""
+    from dataclasses import replace
+
+    return replace(a, embeddings=np.concatenate([a.embeddings, b.embeddings]), file_index=np.concatenate([a.file_index, b.file_index + len(a.paths)]),
+                   start_s=np.concatenate([a.start_s, b.start_s]), paths=list(a.paths) + list(b.paths),
+                   chunks_per_file=np.concatenate([a.chunks_per_file, b.chunks_per_file]), skipped=list(a.skipped) + list(b.skipped),
+                   candidate_rows=a.candidate_rows + b.candidate_rows)
+
+
 def run_linear_probe(args, runner=None) -> ProbeHead:
     """The ``probe`` command: ``args.data_path_train/<class>/*`` -> embeddings (the backbone runs once) -> ``fit_probe`` ->
     ``<output>.npz``, ``<output>_labels.txt``, ``<output>_model_config.json`` and ``<output>_history.csv``."""
@@ -477,8 +487,21 @@ def run_linear_probe(args, runner=None) -> ProbeHead:
         runner = load_model_runner(args.model_path, device=getattr(args, "device", 0), max_batch=getattr(args, "max_batch", 4096), prepare_pipeline=True)
     overlap = max(0.0, min(float(cfg.chunk_duration) - 0.1, float(args.overlap)))
     t0 = time.perf_counter()
-    emb = embed_files(runner, train_paths + val_paths, chunk_overlap=overlap, max_duration=args.max_duration, pooling="none", dtype="float32",
-                      sample_rate=int(cfg.sample_rate), chunk_duration=float(cfg.chunk_duration))
+    from birdnet_stm32.audio.pipeline import selection_from_args
+
+    kw = dict(chunk_overlap=overlap, max_duration=args.max_duration, pooling="none", dtype="float32", sample_rate=int(cfg.sample_rate),
+              chunk_duration=float(cfg.chunk_duration))
+    select = selection_from_args(args)
+    if select is None:
+        emb = embed_files(runner, train_paths + val_paths, **kw)
+    else:
+        # the reference's loader (data/generator.py:87-157): training files at --activity_threshold, validation files at 0.5 (its linear probe's
+        # validation generator, training/linear_probe.py), hence one pass per split
+        emb = embed_files(runner, train_paths, select=select, **kw)
+        if val_paths:
+            emb = _join_embeddings(emb, embed_files(runner, val_paths, select=selection_from_args(args, 0.5), **kw))
+        print(f"[probe] selection: {emb.candidate_rows} candidate rows -> {emb.embeddings.shape[0]} rows (at most {select.max_chunks_per_file} per file, "
+              f"{select.candidate_chunks} candidates)")
     t_embed = time.perf_counter() - t0
     Y, keep = targets_from_paths(emb.paths, classes, emb.file_index, args.activation)
     is_train = np.asarray(emb.file_index) < len(train_paths)

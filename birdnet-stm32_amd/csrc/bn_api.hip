@@ -817,6 +817,34 @@ int bn_pool_scores(bn_ctx* ctx, const float* d_scores, const int64_t* d_file_off
     return BN_OK;
 }
 
+int bn_short_time_energy(bn_ctx* ctx, const float* d_mono, const float* d_peak, const int64_t* d_win_off, const int32_t* d_win_index,
+                         const int64_t* d_frame_off, int n_windows, int frame_len, int hop, float* d_ste, void* stream) {
+    if (int rc = check_device(ctx)) return rc;
+    if (n_windows < 0 || frame_len <= 0 || hop <= 0) return fail(BN_ERR_ARG, "bad energy geometry windows=%d frame_len=%d hop=%d", n_windows, frame_len, hop);
+    if (frame_len != 1024 || hop != 512)
+        return fail(BN_ERR_UNSUPPORTED, "frame_len=%d hop=%d: only frames of 1024 at hops of 512 are implemented", frame_len, hop);
+    if (n_windows == 0) return BN_OK;
+    if (n_windows > 65535) return fail(BN_ERR_ARG, "at most 65535 windows per call");
+    if (!d_mono || !d_peak || !d_win_off || !d_win_index || !d_frame_off || !d_ste) return fail(BN_ERR_ARG, "null device pointer");
+    bn::launch_short_time_energy(d_mono, d_peak, (const long*)d_win_off, d_win_index, (const long*)d_frame_off, n_windows, d_ste, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return BN_OK;
+}
+
+int bn_activity_counts(bn_ctx* ctx, const float* d_x, int B, int64_t n, const int32_t* d_idx, int m, float k, int32_t* d_active, float* d_stats,
+                       void* stream) {
+    if (int rc = check_device(ctx)) return rc;
+    if (B < 0 || n < 1 || n > 0x7fffffffLL) return fail(BN_ERR_ARG, "bad feature matrix %d x %lld", B, (long long)n);
+    if (m < 1 || m > 512) return fail(BN_ERR_ARG, "m=%d: the median is taken over 1..512 elements", m);
+    if (!(k == k)) return fail(BN_ERR_ARG, "k is not a number");
+    if (B == 0) return BN_OK;
+    if (!d_x || !d_idx || !d_active) return fail(BN_ERR_ARG, "null device pointer");
+    if ((uintptr_t)d_x % 4 || (uintptr_t)d_idx % 4) return fail(BN_ERR_ARG, "d_x and d_idx must be 4-byte aligned");
+    bn::launch_activity_counts(d_x, B, (long)n, d_idx, m, k, d_active, d_stats, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return BN_OK;
+}
+
 int bn_rank_orders(bn_ctx* ctx, const float* d_scores, int n_rows, int n_classes, int32_t* d_cols, int32_t* d_flat, void* stream) {
     if (int rc = check_device(ctx)) return rc;
     if (n_rows < 0 || n_classes <= 0) return fail(BN_ERR_ARG, "bad score matrix %d x %d", n_rows, n_classes);
@@ -987,7 +1015,7 @@ int bn_preload_kernels(bn_ctx* ctx) {
     // copies wait meanwhile).  A caller with idle time before its first batch — the evaluate pipeline while the first files are read — asks here.
     bn::preload_ingest(); bn::preload_stft(); bn::preload_stft_exact(); bn::preload_i8_fused(); bn::preload_i8_strip(); bn::preload_i8_tail2();
     bn::preload_i8_tail(); bn::preload_i8(); bn::preload_i8_pw(); bn::preload_f32(); bn::preload_f32_fused(); bn::preload_f32_strip();
-    bn::preload_f32_pw(); bn::preload_melspec(); bn::preload_sort(); bn::preload_probe();
+    bn::preload_f32_pw(); bn::preload_melspec(); bn::preload_sort(); bn::preload_probe(); bn::preload_activity();
     return BN_OK;
 }
 
@@ -1006,7 +1034,7 @@ const char* bn_kernel_names(void) {
     return "ingest_resample_kernel\ningest_decimate_kernel\ningest_peak_kernel\ningest_chunks_kernel\nchunk_peaknorm_kernel\npool_scores_kernel\nstft512_mag_kernel\nspec_normalize_kernel\nmelspec_finish_kernel\nf32_mel_kernel\nf32_melfin_kernel\nf32_mag_kernel\nf32_rawfe_kernel\nf32_stem_kernel\nf32_dw_kernel\n"
            "f32_pw_kernel\nf32_pw_ws_kernel\nf32_dwpw_kernel\nf32_dwpw_wave_kernel\nf32_strip_kernel\nf32_front_strip_kernel\nf32_front2_kernel\nf32_pwdw_kernel\nf32_dw_stream_kernel\nf32_front_kernel\nf32_gap_kernel\nf32_gap_dense_kernel\nf32_gap_dense_emb_kernel\nf32_dense_kernel\nf32_segate_kernel\nf32_scale_kernel\nf32_attnpool_kernel\n"
            "i8_quant_kernel\ni8_mel_kernel\ni8_stem_kernel\ni8_dw_kernel\ni8_pw_kernel\ni8_dwpw_kernel\ni8_mel_mfma_kernel\ni8_strip_kernel\ni8_strip_mf_kernel\ni8_front_strip_kernel\ni8_front_kernel\ni8_tail_kernel\ni8_tail_emb_kernel\ni8_tail2_kernel\ni8_tail2_emb_kernel\ni8_mid2_kernel\ni8_mean_kernel\ni8_fc_kernel\ni8_scale_kernel\ni8_maxnorm_kernel\ni8_rawfe_kernel\ni8_pwdw_kernel\ni8_dw_stream_kernel\ni8_stem_stream_kernel\ni8_segate_kernel\ni8_pw_wave_kernel\ni8_pw_lds_kernel\ni8_attnpool_kernel\n"
-           "i8_head_kernel\ni8_head_softmax_kernel\nemb_store_kernel\nprobe_fwd_kernel\nprobe_dw_kernel\nprobe_reduce_kernel\nprobe_update_kernel\nprobe_loss_sum_kernel";
+           "i8_head_kernel\ni8_head_softmax_kernel\nemb_store_kernel\nprobe_fwd_kernel\nprobe_dw_kernel\nprobe_reduce_kernel\nprobe_update_kernel\nprobe_loss_sum_kernel\nste_kernel\nactivity_count_kernel";
 }
 
 }  // extern "C"

@@ -473,7 +473,7 @@ void launch_i8_dwpw(const DwPw8Args& a, hipStream_t s);
 // One per source file with kernels: load that file's device code object now (bn_preload_kernels)
 void preload_f32(); void preload_f32_fused(); void preload_f32_pw(); void preload_f32_strip(); void preload_i8(); void preload_i8_fused();
 void preload_i8_pw(); void preload_i8_strip(); void preload_i8_tail(); void preload_i8_tail2(); void preload_ingest(); void preload_melspec();
-void preload_stft(); void preload_stft_exact(); void preload_sort(); void preload_probe();
+void preload_stft(); void preload_stft_exact(); void preload_sort(); void preload_probe(); void preload_activity();
 
 // bn_probe.hip: a classifier head on embeddings (bn_head_forward) and its training step (bn_probe_*)
 struct ProbeFwdArgs {
@@ -510,6 +510,13 @@ void launch_probe_dw(const ProbeDwArgs& a, int row_groups, hipStream_t s);
 void launch_probe_reduce(float* partial, int E, int groups, float* ss_part, hipStream_t s);
 void launch_probe_update(const ProbeUpdateArgs& a, hipStream_t s);
 void launch_probe_loss_sum(const float* part, long n, float scale, float* out, hipStream_t s);
+
+// bn_activity.hip: the reductions behind chunk selection.  Short-time energy (frames of 1024 at hops of 512) of windows [win_off[w], win_off[w+1])
+// of the resampled mono buffer, divided by peak[win_index[w]] first, written to ste[frame_off[w] ...]; and per row of x [B][n] the median / MAD /
+// threshold over |x[idx[0..m)]| (m <= 512) with the number of elements above the threshold (stats [B][3] may be null).
+void launch_short_time_energy(const float* mono, const float* peak, const long* win_off, const int* win_index, const long* frame_off, int n_windows,
+                              float* ste, hipStream_t s);
+void launch_activity_counts(const float* x, int B, long n, const int* idx, int m, float k, int* active, float* stats, hipStream_t s);
 
 // bn_sort.hip: descending orders of the score matrix for the ranking metrics (per class [C][N] row indices, flattened [N*C] flat indices)
 size_t rank_orders_workspace(int N, int C);

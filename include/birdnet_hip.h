@@ -213,6 +213,28 @@ BN_API int bn_ingest_chunks(bn_ctx* ctx, const float* d_mono, const float* d_pea
                      const int32_t* d_chunk_valid, const int32_t* d_chunk_window, int n_chunks, int chunk_len,
                      float* d_chunks, void* stream);
 
+/* ---- chunk selection: the two per-sample reductions of the reference's audio/activity.py -----------------------------------
+ * Both repeat, operation for operation, the float32 order that birdnet_stm32/audio/activity.py documents (short_time_energy,
+ * activity_stats), so their outputs equal that module's bit for bit.  Percentile, regions, ratios and ranking stay on the host.
+ *
+ * Short-time energy (reference: audio/activity.py:12-30 `_short_time_energy`, called by smart_crop :75-77 with 1024 / 512 for every
+ * chunk of at least 4096 samples): for window w = d_mono[d_win_off[w] : d_win_off[w+1]] of the un-normalised buffer bn_ingest_resample
+ * wrote, d_ste[d_frame_off[w] + f] = mean((y / peak)[512 f : 512 f + 1024]^2), peak = d_peak[d_win_index[w]] (divided only when
+ * peak > 0, as bn_ingest_chunks does).  Only full frames: window w gives min(1 + (len - 1024) / 512, d_frame_off[w+1] - d_frame_off[w])
+ * frames, none when len < 1024 -- a window the caller wants skipped gets an empty slice of d_ste.
+ *   d_win_off [n_windows + 1] int64, d_win_index [n_windows] int32, d_frame_off [n_windows + 1] int64
+ * frame_len / hop other than 1024 / 512 answer BN_ERR_UNSUPPORTED; at most 65535 windows per call. */
+BN_API int bn_short_time_energy(bn_ctx* ctx, const float* d_mono, const float* d_peak, const int64_t* d_win_off, const int32_t* d_win_index,
+                         const int64_t* d_frame_off, int n_windows, int frame_len, int hop, float* d_ste, void* stream);
+
+/* Activity counts (reference: audio/activity.py:188-209 `get_activity_ratio` up to np.count_nonzero): for every row of d_x [B, n]
+ * (finite float32; rows need only 4-byte alignment) sort |x[d_idx[0..m)]| (1 <= m <= 512; the host passes
+ * np.linspace(0, n - 1, 512, dtype=int), or the identity with m = n when n <= 512), median = mean of the two middle values, mad = the same of
+ * |v - median| plus 1e-10, thresh = median + k * mad (two roundings), and count the row's elements with |x| > thresh.
+ *   d_active [B] int32 counts; d_stats [B, 3] float32 (median, mad, thresh), may be NULL.  Indices outside [0, n) are clamped. */
+BN_API int bn_activity_counts(bn_ctx* ctx, const float* d_x, int B, int64_t n, const int32_t* d_idx, int m, float k, int32_t* d_active,
+                       float* d_stats, void* stream);
+
 /* The sorts behind the ranking metrics (reference: sklearn roc_auc_score / average_precision_score, birdnet_stm32/evaluation/metrics.py:155-190,
  * each of which argsorts on the host): descending, stable orders of the [n_rows, n_classes] float32 score matrix, on the device it lives on.
  *   d_cols [n_classes, n_rows] int32 — for class c the row indices by descending score of column c
