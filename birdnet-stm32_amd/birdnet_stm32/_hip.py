@@ -31,13 +31,17 @@ EXPORTS = (
     "bn_blob_check", "bn_debug_requant", "bn_stft_mag_exact", "bn_debug_input_bytes", "bn_debug_guard_stats", "bn_debug_tail_form", "bn_debug_mid_form", "bn_debug_mid_plan", "bn_debug_mid_split_giveups",
     "bn_forward_embed", "bn_infer_audio_embed", "bn_model_get_embedding_info", "bn_ingest_resample_span",
     "bn_head_forward", "bn_probe_create", "bn_probe_destroy", "bn_probe_epoch", "bn_probe_loss", "bn_probe_get", "bn_probe_set",
-    "bn_short_time_energy", "bn_activity_counts",
+    "bn_short_time_energy", "bn_activity_counts", "bn_search_inv_norms", "bn_search_topk",
 )  # fmt: skip
 
 EMB_F32, EMB_I8 = 0, 1  # BN_EMB_* (include/birdnet_hip.h)
 PROBE_ACTIVATIONS = {"sigmoid": 0, "softmax": 1}  # BN_PROBE_ACT_*
 PROBE_OPTIMIZERS = {"adam": 0, "adamw": 1, "sgd": 2}  # BN_PROBE_OPT_*
 PROBE_MAX_D, PROBE_MAX_C = 2048, 4096
+DTYPE_F32, DTYPE_I8 = 0, 1  # BN_DTYPE_*
+SEARCH_METRICS = {"cosine": 0, "dot": 1}  # BN_SEARCH_*
+SEARCH_MAX_K, SEARCH_MAX_D = 128, 2048
+SEARCH_STEP_ROWS, SEARCH_MIN_WG_STEPS, SEARCH_MAX_WGS = 64, 8, 1024  # how bn_search_topk deals rows to workgroups (include/birdnet_hip.h)
 
 # launcher switches of bn_set_option (include/birdnet_hip.h); the production defaults are what a fresh process has
 OPTION_NAMES = ("f32_strip", "f32_strip_th", "f32_front_staged", "f32_front2", "f32_pwdw", "f32_tile_slice", "f32_pw_ws", "i8_pwdw", "i8_pw_lds", "i8_pw_forms", "i8_add_tab", "front_tpw", "wave_dwpw", "i8_strip", "i8_strip_mfdw", "i8_strip_th", "i8_dw_pool", "i8_tail_fclds", "i8_tail", "i8_tail_mfdw", "i8_mid",
@@ -127,6 +131,9 @@ def load_library(path: str | None = None):
     lib.bn_rank_orders.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]
     lib.bn_short_time_energy.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
     lib.bn_activity_counts.argtypes = [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p]
+    lib.bn_search_inv_norms.argtypes = [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p]
+    lib.bn_search_topk.argtypes = [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p,
+                                   c_int, c_void_p, c_void_p, c_void_p]
     lib.bn_host_alloc_pinned.argtypes = [c_void_p, ctypes.c_size_t]
     lib.bn_host_alloc_pinned.restype = c_void_p
     lib.bn_host_free_pinned.argtypes = [c_void_p]

@@ -184,6 +184,7 @@ void bn_ctx_destroy(bn_ctx* c) {
     (void)hipFree(c->d_f64tab);
     (void)hipFree(c->d_block_peaks);
     if (c->d_rank_work) (void)hipFree(c->d_rank_work);
+    if (c->d_search_work) (void)hipFree(c->d_search_work);
     delete c;
 }
 
@@ -1015,7 +1016,7 @@ int bn_preload_kernels(bn_ctx* ctx) {
     // copies wait meanwhile).  A caller with idle time before its first batch — the evaluate pipeline while the first files are read — asks here.
     bn::preload_ingest(); bn::preload_stft(); bn::preload_stft_exact(); bn::preload_i8_fused(); bn::preload_i8_strip(); bn::preload_i8_tail2();
     bn::preload_i8_tail(); bn::preload_i8(); bn::preload_i8_pw(); bn::preload_f32(); bn::preload_f32_fused(); bn::preload_f32_strip();
-    bn::preload_f32_pw(); bn::preload_melspec(); bn::preload_sort(); bn::preload_probe(); bn::preload_activity();
+    bn::preload_f32_pw(); bn::preload_melspec(); bn::preload_sort(); bn::preload_probe(); bn::preload_activity(); bn::preload_search();
     return BN_OK;
 }
 
@@ -1034,7 +1035,7 @@ const char* bn_kernel_names(void) {
     return "ingest_resample_kernel\ningest_decimate_kernel\ningest_peak_kernel\ningest_chunks_kernel\nchunk_peaknorm_kernel\npool_scores_kernel\nstft512_mag_kernel\nspec_normalize_kernel\nmelspec_finish_kernel\nf32_mel_kernel\nf32_melfin_kernel\nf32_mag_kernel\nf32_rawfe_kernel\nf32_stem_kernel\nf32_dw_kernel\n"
            "f32_pw_kernel\nf32_pw_ws_kernel\nf32_dwpw_kernel\nf32_dwpw_wave_kernel\nf32_strip_kernel\nf32_front_strip_kernel\nf32_front2_kernel\nf32_pwdw_kernel\nf32_dw_stream_kernel\nf32_front_kernel\nf32_gap_kernel\nf32_gap_dense_kernel\nf32_gap_dense_emb_kernel\nf32_dense_kernel\nf32_segate_kernel\nf32_scale_kernel\nf32_attnpool_kernel\n"
            "i8_quant_kernel\ni8_mel_kernel\ni8_stem_kernel\ni8_dw_kernel\ni8_pw_kernel\ni8_dwpw_kernel\ni8_mel_mfma_kernel\ni8_strip_kernel\ni8_strip_mf_kernel\ni8_front_strip_kernel\ni8_front_kernel\ni8_tail_kernel\ni8_tail_emb_kernel\ni8_tail2_kernel\ni8_tail2_emb_kernel\ni8_mid2_kernel\ni8_mean_kernel\ni8_fc_kernel\ni8_scale_kernel\ni8_maxnorm_kernel\ni8_rawfe_kernel\ni8_pwdw_kernel\ni8_dw_stream_kernel\ni8_stem_stream_kernel\ni8_segate_kernel\ni8_pw_wave_kernel\ni8_pw_lds_kernel\ni8_attnpool_kernel\n"
-           "i8_head_kernel\ni8_head_softmax_kernel\nemb_store_kernel\nprobe_fwd_kernel\nprobe_dw_kernel\nprobe_reduce_kernel\nprobe_update_kernel\nprobe_loss_sum_kernel\nste_kernel\nactivity_count_kernel";
+           "i8_head_kernel\ni8_head_softmax_kernel\nemb_store_kernel\nprobe_fwd_kernel\nprobe_dw_kernel\nprobe_reduce_kernel\nprobe_update_kernel\nprobe_loss_sum_kernel\nste_kernel\nactivity_count_kernel\nsearch_inv_norms_kernel\nsearch_score_kernel\nsearch_merge_kernel";
 }
 
 }  // extern "C"
@@ -1243,6 +1244,89 @@ int bn_probe_set(bn_probe* p, const float* d_W, const float* d_b, void* stream) 
     const size_t nw = (size_t)p->D * p->C;
     HIP_TRY(hipMemcpyAsync(p->d_params, d_W, nw * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     HIP_TRY(hipMemcpyAsync(p->d_params + nw, d_b, (size_t)p->C * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return BN_OK;
+}
+
+}  // extern "C"
+
+// --------------------------------------------------------------------------------------------------------------- search (bn_search.hip)
+namespace {
+
+int search_shape_check(int dtype, int64_t n, int D) {
+    if (dtype != BN_DTYPE_F32 && dtype != BN_DTYPE_I8) return fail(BN_ERR_ARG, "unknown dtype %d", dtype);
+    if (D < 1 || D > BN_SEARCH_MAX_D) return fail(BN_ERR_ARG, "embedding width D=%d outside 1..%d", D, BN_SEARCH_MAX_D);
+    if (n < 0 || n > 0x7fffffffLL) return fail(BN_ERR_ARG, "bad row count %lld", (long long)n);
+    return BN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bn_search_inv_norms(bn_ctx* ctx, const void* d_rows, int dtype, int64_t n, int D, int zero_point, float* d_inv, void* stream) {
+    if (int rc = check_device(ctx)) return rc;
+    if (int rc = search_shape_check(dtype, n, D)) return rc;
+    if (dtype == BN_DTYPE_I8 && (zero_point < -128 || zero_point > 127)) return fail(BN_ERR_ARG, "zero point %d outside -128..127", zero_point);
+    if (!d_rows || !d_inv) return fail(BN_ERR_ARG, "null device pointer");
+    if (dtype == BN_DTYPE_F32 && (uintptr_t)d_rows % 4) return fail(BN_ERR_ARG, "float32 rows must be 4-byte aligned");
+    if (n == 0) return BN_OK;
+    bn::launch_search_inv_norms(d_rows, dtype == BN_DTYPE_I8, (long)n, D, zero_point, d_inv, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return BN_OK;
+}
+
+int bn_search_topk(bn_ctx* ctx, const void* d_db, int dtype, int64_t n, int D, int zero_point, const float* d_db_inv, const void* d_queries,
+                   int64_t Q, const float* d_q_inv, int metric, const int32_t* d_db_group, const int32_t* d_q_group, int k, int32_t* d_idx,
+                   float* d_score, void* stream) {
+    if (int rc = check_device(ctx)) return rc;
+    if (int rc = search_shape_check(dtype, n, D)) return rc;
+    if (k < 1 || k > BN_SEARCH_MAX_K) return fail(BN_ERR_ARG, "k=%d outside 1..%d", k, BN_SEARCH_MAX_K);
+    if (Q < 0 || Q > 0x7fffffffLL) return fail(BN_ERR_ARG, "bad query count %lld", (long long)Q);
+    if (metric != BN_SEARCH_COSINE && metric != BN_SEARCH_DOT) return fail(BN_ERR_ARG, "unknown metric %d", metric);
+    if (dtype == BN_DTYPE_I8 && (zero_point < -128 || zero_point > 127)) return fail(BN_ERR_ARG, "zero point %d outside -128..127", zero_point);
+    if (!d_db || !d_queries || !d_idx || !d_score) return fail(BN_ERR_ARG, "null device pointer");
+    if (metric == BN_SEARCH_COSINE && (!d_db_inv || !d_q_inv)) return fail(BN_ERR_ARG, "the cosine metric needs both inverse-norm arrays");
+    if ((d_db_group == nullptr) != (d_q_group == nullptr)) return fail(BN_ERR_ARG, "d_db_group and d_q_group go together");
+    if (dtype == BN_DTYPE_F32 && ((uintptr_t)d_db % 4 || (uintptr_t)d_queries % 4)) return fail(BN_ERR_ARG, "float32 rows must be 4-byte aligned");
+    if (Q == 0) return BN_OK;
+    const bool i8 = dtype == BN_DTYPE_I8;
+    hipStream_t s = (hipStream_t)stream;
+    bn::SearchGeom g{};
+    if (!bn::search_geometry((long)n, D, (int)Q, k, i8, &g)) return fail(BN_ERR_ARG, "D=%d k=%d: no query tile fits the LDS", D, k);
+    // queries per launch: whole passes whose partial lists fit the workspace bound
+    const size_t per_query = (size_t)g.nwg * k * (sizeof(float) + sizeof(int32_t));
+    const int pass_q = 16 * g.nt;
+    int64_t group = (int64_t)(BN_SEARCH_WORKSPACE_BYTES / per_query) / pass_q * pass_q;
+    if (group < pass_q) group = pass_q;
+    if (group > Q) group = Q;
+    const size_t need = (size_t)group * per_query;
+    if (need > ctx->search_work_bytes) {   // (grown outside any capture, as bn_rank_orders grows its own)
+        HIP_TRY(hipStreamSynchronize(s));
+        if (ctx->d_search_work) (void)hipFree(ctx->d_search_work);
+        ctx->d_search_work = nullptr;
+        ctx->search_work_bytes = 0;
+        if (hipMalloc(&ctx->d_search_work, need) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(BN_ERR_NOMEM, "hipMalloc of %zu bytes for the search workspace failed", need);
+        }
+        ctx->search_work_bytes = need;
+    }
+    float* part_score = (float*)ctx->d_search_work;
+    int* part_idx = (int*)(part_score + (size_t)group * g.nwg * k);
+    const size_t row_bytes = (size_t)D * (i8 ? 1 : 4);
+    for (int64_t q0 = 0; q0 < Q; q0 += group) {
+        const int nq = (int)std::min<int64_t>(group, Q - q0);
+        bn::SearchArgs a{};
+        a.db = d_db; a.q = (const char*)d_queries + (size_t)q0 * row_bytes;
+        a.db_inv = d_db_inv; a.q_inv = d_q_inv ? d_q_inv + q0 : nullptr;
+        a.db_group = d_db_group; a.q_group = d_q_group ? d_q_group + q0 : nullptr;
+        a.part_score = part_score; a.part_idx = part_idx;
+        a.n = (int)n; a.D = D; a.Q = nq; a.k = k; a.zp = i8 ? zero_point : 0; a.cosine = metric == BN_SEARCH_COSINE;
+        a.steps_per_wg = g.steps_per_wg;
+        if (!bn::launch_search_scores(a, g, i8, s)) return fail(BN_ERR_DEVICE, "the search kernel's LDS request was refused");
+        bn::launch_search_merge(part_score, part_idx, g.nwg, nq, k, d_idx + (size_t)q0 * k, d_score + (size_t)q0 * k, s);
+        HIP_TRY(hipGetLastError());
+    }
     return BN_OK;
 }
 

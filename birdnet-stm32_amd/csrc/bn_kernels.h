@@ -473,7 +473,7 @@ void launch_i8_dwpw(const DwPw8Args& a, hipStream_t s);
 // One per source file with kernels: load that file's device code object now (bn_preload_kernels)
 void preload_f32(); void preload_f32_fused(); void preload_f32_pw(); void preload_f32_strip(); void preload_i8(); void preload_i8_fused();
 void preload_i8_pw(); void preload_i8_strip(); void preload_i8_tail(); void preload_i8_tail2(); void preload_ingest(); void preload_melspec();
-void preload_stft(); void preload_stft_exact(); void preload_sort(); void preload_probe(); void preload_activity();
+void preload_stft(); void preload_stft_exact(); void preload_sort(); void preload_probe(); void preload_activity(); void preload_search();
 
 // bn_probe.hip: a classifier head on embeddings (bn_head_forward) and its training step (bn_probe_*)
 struct ProbeFwdArgs {
@@ -521,5 +521,29 @@ void launch_activity_counts(const float* x, int B, long n, const int* idx, int m
 // bn_sort.hip: descending orders of the score matrix for the ranking metrics (per class [C][N] row indices, flattened [N*C] flat indices)
 size_t rank_orders_workspace(int N, int C);
 bool launch_rank_orders(const float* d_scores, int N, int C, int* d_cols, int* d_flat, void* d_work, size_t work_bytes, hipStream_t s);
+
+// bn_search.hip: the k best rows per query by cosine or dot score (bn_search_*)
+struct SearchArgs {
+    const void* db;          // [n, D] float32 or int8 rows
+    const void* q;           // [Q, D] queries of the same type
+    const float* db_inv;     // [n] inverse norms (cosine)
+    const float* q_inv;      // [Q]
+    const int* db_group;     // [n] or null
+    const int* q_group;      // [Q] (with db_group)
+    float* part_score;       // [Q][workgroups][k] partial lists
+    int* part_idx;
+    int n, D, Q, k, zp, cosine;
+    long steps_per_wg;       // steps of BN_SEARCH_STEP_ROWS rows a workgroup streams
+};
+struct SearchGeom {
+    int nt;                  // query tiles of 16 per pass
+    int nwg;                 // workgroups along the rows
+    long steps_per_wg;
+    size_t lds;
+};
+bool search_geometry(long n, int D, int Q, int k, bool i8, SearchGeom* g);   // from the shapes only; false: no tile fits the LDS
+void launch_search_inv_norms(const void* rows, bool i8, long n, int D, int zp, float* inv, hipStream_t s);
+bool launch_search_scores(const SearchArgs& a, const SearchGeom& g, bool i8, hipStream_t s);   // false: the runtime refused the LDS request
+void launch_search_merge(const float* part_score, const int* part_idx, int nwg, int Q, int k, int* out_idx, float* out_score, hipStream_t s);
 
 }  // namespace bn

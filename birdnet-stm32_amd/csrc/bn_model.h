@@ -62,6 +62,8 @@ struct bn_ctx {
     size_t block_peaks_elems = 0;
     void* d_rank_work = nullptr;     // bn_rank_orders: transposed keys, index arrays, rocPRIM storage; grown on demand
     size_t rank_work_bytes = 0;
+    void* d_search_work = nullptr;   // bn_search_topk: the workgroups' partial lists; grown on demand
+    size_t search_work_bytes = 0;
 };
 
 struct bn_model {

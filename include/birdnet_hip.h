@@ -413,6 +413,37 @@ BN_API int bn_probe_loss(bn_probe* probe, const float* d_X, const float* d_Y, in
 BN_API int bn_probe_get(bn_probe* probe, float* d_W, float* d_b, void* stream);
 BN_API int bn_probe_set(bn_probe* probe, const float* d_W, const float* d_b, void* stream);
 
+/* ---- Query by example: the k best rows of an embedding matrix per query (csrc/bn_search.hip; no reference counterpart) -------------
+ * Rows and queries are BN_DTYPE_F32 values or the BN_DTYPE_I8 bytes of bn_forward_embed with their zero point; both sides have the same
+ * type.  dot is the float32 inner product (its summation order is the implementation's) or, for int8, the exact int32 inner product of
+ * (byte - zero_point) rounded once to float32.  inv = 1 / sqrt(sum of squares), both correctly rounded, 0 for a zero row.  Scores:
+ * BN_SEARCH_DOT dot, BN_SEARCH_COSINE fl(fl(dot * inv_query) * inv_row).  Results per query are ordered by score descending and, among
+ * equal scores, by row index ascending; when fewer than k rows qualify the remaining slots hold index -1 and score -inf.  With both
+ * group arrays given, a row whose group equals the query's does not qualify.  Inputs must be finite.
+ * 1 <= D <= BN_SEARCH_MAX_D, 1 <= k <= BN_SEARCH_MAX_K, 0 <= n < 2^31, Q >= 0.  float32 rows need 4-byte alignment (16 with D % 4 == 0
+ * takes the wide loads; int8: 16 with D % 16 == 0).  The same inputs give the same bits on every run. */
+#define BN_SEARCH_COSINE 0
+#define BN_SEARCH_DOT 1
+#define BN_SEARCH_MAX_K 128
+#define BN_SEARCH_MAX_D 2048
+/* How the rows are dealt to workgroups — from (n, D, Q, k) alone: steps of BN_SEARCH_STEP_ROWS rows, at least BN_SEARCH_MIN_WG_STEPS
+ * steps per workgroup, at most BN_SEARCH_MAX_WGS workgroups per pass over the rows; a pass holds 16, 32 or 64 queries in
+ * BN_SEARCH_LDS_BYTES of LDS.  The partial lists of a call take at most BN_SEARCH_WORKSPACE_BYTES (more queries run as further launches). */
+#define BN_SEARCH_STEP_ROWS 64
+#define BN_SEARCH_MIN_WG_STEPS 8
+#define BN_SEARCH_MAX_WGS 1024
+#define BN_SEARCH_LDS_BYTES (160 * 1024)
+#define BN_SEARCH_WORKSPACE_BYTES (128u << 20)
+
+/* d_inv[n] = inverse norms of the rows of d_rows [n, D] (zero_point is read for BN_DTYPE_I8 only). */
+BN_API int bn_search_inv_norms(bn_ctx* ctx, const void* d_rows, int dtype, int64_t n, int D, int zero_point, float* d_inv, void* stream);
+/* d_idx [Q, k] int32 and d_score [Q, k] float32: the k best rows of d_db [n, D] for each row of d_queries [Q, D].  d_db_inv [n] and
+ * d_q_inv [Q] come from bn_search_inv_norms and may be NULL for BN_SEARCH_DOT; d_db_group [n] / d_q_group [Q] int32, both or neither.
+ * Nothing synchronises with the host inside the call unless the context's workspace has to grow. */
+BN_API int bn_search_topk(bn_ctx* ctx, const void* d_db, int dtype, int64_t n, int D, int zero_point, const float* d_db_inv, const void* d_queries,
+                   int64_t Q, const float* d_q_inv, int metric, const int32_t* d_db_group, const int32_t* d_q_group, int k, int32_t* d_idx,
+                   float* d_score, void* stream);
+
 /* Loads every device code object of the library now.  The HIP runtime loads one at the first launch of any of its kernels (a few ms each; launches
  * and copies of OTHER threads wait meanwhile), which a first batch otherwise pays one file after the other on its critical path; a caller with idle
  * time before that batch (the evaluate pipeline while the first files are being read) calls this instead.  Idempotent.  (Reference counterpart:
