@@ -31,7 +31,7 @@ EXPORTS = (
     "bn_blob_check", "bn_debug_requant", "bn_stft_mag_exact", "bn_debug_input_bytes", "bn_debug_guard_stats", "bn_debug_tail_form", "bn_debug_mid_form", "bn_debug_mid_plan", "bn_debug_mid_split_giveups",
     "bn_forward_embed", "bn_infer_audio_embed", "bn_model_get_embedding_info", "bn_ingest_resample_span",
     "bn_head_forward", "bn_probe_create", "bn_probe_destroy", "bn_probe_epoch", "bn_probe_loss", "bn_probe_get", "bn_probe_set",
-    "bn_short_time_energy", "bn_activity_counts", "bn_search_inv_norms", "bn_search_topk",
+    "bn_short_time_energy", "bn_activity_counts", "bn_search_inv_norms", "bn_search_topk", "bn_augment_inputs",
 )  # fmt: skip
 
 EMB_F32, EMB_I8 = 0, 1  # BN_EMB_* (include/birdnet_hip.h)
@@ -41,6 +41,7 @@ PROBE_MAX_D, PROBE_MAX_C = 2048, 4096
 DTYPE_F32, DTYPE_I8 = 0, 1  # BN_DTYPE_*
 SEARCH_METRICS = {"cosine": 0, "dot": 1}  # BN_SEARCH_*
 SEARCH_MAX_K, SEARCH_MAX_D = 128, 2048
+AUGMENT_MAX_MASKS = 4  # BN_AUGMENT_MAX_MASKS
 SEARCH_STEP_ROWS, SEARCH_MIN_WG_STEPS, SEARCH_MAX_WGS = 64, 8, 1024  # how bn_search_topk deals rows to workgroups (include/birdnet_hip.h)
 
 # launcher switches of bn_set_option (include/birdnet_hip.h); the production defaults are what a fresh process has
@@ -134,6 +135,8 @@ def load_library(path: str | None = None):
     lib.bn_search_inv_norms.argtypes = [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p]
     lib.bn_search_topk.argtypes = [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p,
                                    c_int, c_void_p, c_void_p, c_void_p]
+    lib.bn_augment_inputs.argtypes = [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int64,
+                                      c_void_p, c_void_p]
     lib.bn_host_alloc_pinned.argtypes = [c_void_p, ctypes.c_size_t]
     lib.bn_host_alloc_pinned.restype = c_void_p
     lib.bn_host_free_pinned.argtypes = [c_void_p]

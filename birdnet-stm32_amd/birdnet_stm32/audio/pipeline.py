@@ -666,6 +666,12 @@ class EvaluatePipeline:
         # embedding output (evaluation/embeddings.py): None = scores only; "float32" / "int8" = run() also fills self.embeddings [N, D]
         self.emb_dtype: str | None = None
         self.embeddings = None
+        # model inputs kept on the device (the augmented probe fit): run() also fills self.inputs [N, input_elems], the rows predict_device takes
+        self.keep_inputs = False
+        self.inputs = None
+        self.inputs_into = None   # a caller's [>= rows, input_elems] CUDA tensor that run() fills instead of allocating (embed_files: one buffer for all blocks)
+        self._inp = None
+        self.inputs_budget_bytes = 32 << 30
         self._emb = None
         # long files (module docstring): off = every file goes through the grouped path and must fit one slab
         self.stream_long = bool(stream_long)
@@ -948,6 +954,10 @@ class EvaluatePipeline:
                     b.record(cur)
                     lat_events.append((a, b, nb))
         ev[2].record(cur)
+        if n and self._inp is not None:   # (after the events: the inference time stays the inference's)
+            mb = int(self.runner.max_batch)
+            for b0 in range(0, n, mb):
+                self._inp[row0 + b0 : row0 + min(b0 + mb, n)].copy_(self.runner.model_inputs_device(self._chunks[b0 : min(b0 + mb, n)]))
         self._mark("compute: inference launched")
         stats["_events"].append((st.h2d_events, ev, g.used + 8 * g.tab_len))
         if keep is not None:
@@ -1163,7 +1173,8 @@ class EvaluatePipeline:
         evaluation/metrics.py:130-136) — without a host synchronisation per slice.  Otherwise slices are the runner's ``max_batch``.
 
         ``table``: the ``plan_files`` result for ``paths`` when the caller has it already.  With ``emb_dtype`` set, ``self.embeddings``
-        holds the ``[N, D]`` CUDA embeddings of the same rows afterwards.
+        holds the ``[N, D]`` CUDA embeddings of the same rows afterwards; with ``keep_inputs`` set, ``self.inputs`` holds their model
+        inputs ``[N, input_elems]`` (``runner.model_inputs_device`` of every chunk; with a selection the selected rows in their final order).
         """
         torch = self.torch
         t_start = time.perf_counter()
@@ -1192,6 +1203,10 @@ class EvaluatePipeline:
                 groups = cut_groups(tab.nbytes, tab.n_chunks, self.slab_bytes, self.group_chunks, self.ramp)
                 items = [("group", lo, hi) for lo, hi in groups]
             planned = int(tab.n_chunks.sum())
+            self.inputs = self._inp = None
+            inp_rows = int(self.select.max_counts(tab.n_chunks).sum()) if self.select is not None else planned   # (a selection keeps at most that many)
+            if self.keep_inputs:
+                check_inputs_budget(inp_rows, int(self.runner.input_elems), self.inputs_budget_bytes, self.stream_long, measure_latency)
             # size the rings for the largest group once, before the producer starts (nothing is reallocated while copies are in flight)
             cb = np.concatenate([[0], np.cumsum(tab.nbytes + _ALIGN)])
             cc = np.concatenate([[0], np.cumsum(tab.n_chunks)])
@@ -1209,6 +1224,12 @@ class EvaluatePipeline:
             if self.emb_dtype is not None:
                 D = self.runner.embedding_info()["dim"]
                 self._emb = torch.empty((max(planned, 1), D), dtype=torch.int8 if self.emb_dtype == "int8" else torch.float32, device=self.dev)
+            if self.keep_inputs and self.inputs_into is not None:
+                if self.inputs_into.shape[0] < inp_rows or self.inputs_into.shape[1] != int(self.runner.input_elems) or not self.inputs_into.is_contiguous():
+                    raise ValueError(f"inputs_into must be a contiguous [>= {inp_rows}, {int(self.runner.input_elems)}] tensor")
+                self._inp = self.inputs_into
+            elif self.keep_inputs:
+                self._inp = torch.empty((max(inp_rows, 1), int(self.runner.input_elems)), dtype=torch.float32, device=self.dev)
             q: queue.Queue = queue.Queue(maxsize=max(1, self._n_ring - 1))
             stop = self._stop
 
@@ -1301,7 +1322,23 @@ class EvaluatePipeline:
             stats["trace"] = list(self._trace)
         if self._emb is not None:
             self.embeddings, self._emb = self._emb[:row], None
+        if self._inp is not None:
+            self.inputs, self._inp = self._inp[:row], None
         return scores[:row], counts.tolist(), stats, lat
+
+
+def check_inputs_budget(rows: int, input_elems: int, budget_bytes: int, stream_long: bool = False, measure_latency: bool = False) -> None:
+    """The refusals of ``keep_inputs``, from the plan alone (nothing has been read yet): ``rows`` model-input rows of ``input_elems`` float32
+    must fit ``budget_bytes`` of device memory, and neither streaming nor latency slices go with it."""
+    if stream_long:
+        raise ValueError("keep_inputs and stream_long cannot be combined: a streamed file's chunks are cut slice by slice into one buffer")
+    if measure_latency:
+        raise ValueError("keep_inputs and measure_latency cannot be combined: keeping the inputs adds work between the timed slices")
+    row_bytes = 4 * int(input_elems)
+    if int(rows) * row_bytes > int(budget_bytes):
+        raise ValueError(f"keeping the model inputs of {int(rows)} rows needs {int(rows) * row_bytes / 2**30:.1f} GiB of device memory, more than the "
+                         f"budget of {int(budget_bytes) / 2**30:.1f} GiB (inputs_budget_bytes): {int(budget_bytes) // row_bytes} rows would fit; "
+                         "pass fewer files or a selection (max_chunks_per_file)")
 
 
 def balanced_bounds(weights, world: int) -> list[int]:

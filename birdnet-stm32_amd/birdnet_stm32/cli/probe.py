@@ -3,7 +3,9 @@
 ``--data_path_train`` holds one folder per class (``<class>/*.wav``); folders named noise / silence / background / other are negatives.
 The backbone runs once over all files (``embed``'s device path), the head is trained on the embeddings on the GPU
 (``training/linear_probe.py``) and written as ``<output>.npz`` with ``<output>_labels.txt``, ``<output>_model_config.json`` and
-``<output>_history.csv``.  ``analyze --head <output>.npz`` then reports those classes in recordings.
+``<output>_history.csv``.  ``analyze --head <output>.npz`` then reports those classes in recordings.  With ``--mixup_probability`` or
+``--spec_augment`` the training rows' model inputs stay on the device and every epoch trains on fresh embeddings of augmented rows
+(``training/augment.py``).
 """
 
 from __future__ import annotations
@@ -34,6 +36,15 @@ def build_parser() -> argparse.ArgumentParser:
                         "chunk is used.  Needs --overlap 0.  The reference's `train` defaults to 3")
     p.add_argument("--activity_threshold", type=float, default=0.1, help="With --max_chunks_per_file: drop chunks whose activity ratio is lower (one per file is always kept); validation files use 0.5, as the reference's linear probe does")
     p.add_argument("--candidate_chunks", type=int, default=0, help="With --max_chunks_per_file: chunks ranked per file (0 = min(8, max(4, 2 N)), as the reference)")
+    p.add_argument("--mixup_alpha", type=float, default=0.2, help="Dirichlet concentration of the mixup gains (the reference's default)")
+    p.add_argument("--mixup_probability", type=float, default=0.0,
+                   help="Fraction of the training rows mixed from 2-3 rows each epoch, labels united; 0 = off (the default here; the reference's `train` "
+                        "defaults to 0.25).  Needs --activation sigmoid.  The backbone then runs every epoch")
+    p.add_argument("--spec_augment", action="store_true",
+                   help="Mask two frequency bands and two time spans of every training row, drawn anew each epoch (off by default here; on in the "
+                        "reference unless --no_spec_augment).  Spectrogram frontends only: a raw-frontend model gets no masks")
+    p.add_argument("--freq_mask_max", type=int, default=8, help="With --spec_augment: widest frequency mask in bins (the reference's default)")
+    p.add_argument("--time_mask_max", type=int, default=25, help="With --spec_augment: widest time mask in frames (the reference's default)")
     p.add_argument("--seed", type=int, default=42, help="Seed of the file shuffle, the initial weights, the batches and the dropout mask")
     p.add_argument("--max_batch", type=int, default=4096, help="Workspace size in chunks = inference slice of the device pipeline")
     p.add_argument("--device", type=int, default=0, help="MI355X index")
@@ -48,6 +59,9 @@ def main(argv=None, runner=None):
         from birdnet_stm32.audio.pipeline import selection_from_args
 
         selection_from_args(args)   # (bad selection flags are refused before anything is loaded, as `embed` does)
+        from birdnet_stm32.training.linear_probe import augmentation_from_args
+
+        augmentation_from_args(args)   # (and bad augmentation flags)
         return run_linear_probe(args, runner=runner)
     except (ValueError, FileNotFoundError) as exc:
         raise SystemExit(f"error: {exc}") from None

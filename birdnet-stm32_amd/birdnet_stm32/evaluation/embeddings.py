@@ -40,6 +40,7 @@ class FileEmbeddings:
     zero_point: int
     skipped: list = field(default_factory=list)
     candidate_rows: int = 0   # with a selection: rows that were ranked (``embeddings`` holds the ones that were kept)
+    inputs: object = None     # with ``keep_inputs``: the rows' model inputs, one CUDA float32 tensor ``[N, input_elems]`` (never copied to the host)
 
 
 def chunk_starts(n_out: np.ndarray, sample_rate: int, chunk_duration: float, chunk_overlap: float) -> tuple[np.ndarray, np.ndarray]:
@@ -87,7 +88,7 @@ def embedding_blocks(n_chunks: np.ndarray, row_bytes: int, budget_bytes: int) ->
 
 def embed_files(runner, paths: list[str], chunk_overlap: float = 0.0, max_duration=60, pooling: str = "none", dtype: str | None = None,
                 sample_rate: int = 22050, chunk_duration: float = 3.0, budget_bytes: int = 256 << 20,
-                pipeline_options: dict | None = None, select=None) -> FileEmbeddings:
+                pipeline_options: dict | None = None, select=None, keep_inputs: bool = False, inputs_budget_bytes: int = 32 << 30) -> FileEmbeddings:
     """Embeddings of every chunk of ``paths`` (the chunks ``evaluate`` scores: first ``max_duration`` seconds, ``chunk_duration`` chunks
     with ``chunk_overlap`` seconds of overlap at ``sample_rate``).
 
@@ -95,9 +96,12 @@ def embed_files(runner, paths: list[str], chunk_overlap: float = 0.0, max_durati
     ``scale`` / ``zero_point``).  ``pooling``: "none" (per chunk), "avg" or "max" (per file, float32 only).
 
     ``select``: an ``audio.pipeline.ChunkSelection`` — only each file's most active chunks are embedded (long files are cropped around
-    their loudest stretches first, as the reference's training loader does); ``None`` embeds every grid chunk."""
+    their loudest stretches first, as the reference's training loader does); ``None`` embeds every grid chunk.
+
+    ``keep_inputs``: also keep every row's model inputs (``HipRunner.model_inputs_device`` of its chunk) on the device and return them as
+    one tensor, ``inputs [N, input_elems]`` (per-chunk rows only); refused, before a file is read, when they exceed ``inputs_budget_bytes``."""
     from birdnet_stm32.audio.ingest import pool_scores_device
-    from birdnet_stm32.audio.pipeline import EvaluatePipeline, plan_files
+    from birdnet_stm32.audio.pipeline import EvaluatePipeline, check_inputs_budget, plan_files
 
     pooling = pooling.lower()
     if pooling in ("mean", "average"):
@@ -112,6 +116,8 @@ def embed_files(runner, paths: list[str], chunk_overlap: float = 0.0, max_durati
         raise ValueError("int8 embeddings need an INT8 (.tflite) model; float32 models give float32")
     if dtype == "int8" and pooling != "none":
         raise ValueError("per-file pooling works on float32 embeddings: pass dtype='float32' (the dequantised bytes)")
+    if keep_inputs and pooling != "none":
+        raise ValueError("keep_inputs keeps one row per chunk: pass pooling='none'")
     D = int(info["dim"])
     row_bytes = D * (1 if dtype == "int8" else 4)
     sr, cd, ov = int(sample_rate), float(chunk_duration), float(chunk_overlap)
@@ -121,6 +127,8 @@ def embed_files(runner, paths: list[str], chunk_overlap: float = 0.0, max_durati
     pipe = EvaluatePipeline(runner, sr, cd, ov, max_duration=max_duration, **opts)
     sel_file, sel_start, candidates = [], [], 0
     pipe.emb_dtype = dtype
+    pipe.keep_inputs, pipe.inputs_budget_bytes = bool(keep_inputs), int(inputs_budget_bytes)
+    all_inputs, kept_rows = None, 0
     try:
         tab = plan_files(list(paths), sr, cd, ov, max_duration, pipe.readers)
         big = np.flatnonzero(tab.nbytes > pipe.slab_bytes)
@@ -129,11 +137,20 @@ def embed_files(runner, paths: list[str], chunk_overlap: float = 0.0, max_durati
             raise ValueError(f"{paths[i]}: its read window of {int(tab.nbytes[i])} bytes exceeds one staging slab ({pipe.slab_bytes} bytes = "
                              f"{pipe.slab_bytes >> 20} MiB); lower max_duration (streaming longer recordings is not supported)")
         counts = tab.n_chunks.astype(np.int64)
+        if keep_inputs:   # all blocks together stay resident (with a selection: its upper bound)
+            rows = int((select.max_counts(counts) if select is not None else counts).sum())
+            check_inputs_budget(rows, int(runner.input_elems), inputs_budget_bytes, bool(opts.get("stream_long")))
+            import torch
+
+            # one buffer for all blocks, allocated once: the budget bounds what stays resident (no per-block buffers, no joined copy)
+            all_inputs = torch.empty((max(rows, 1), int(runner.input_elems)), dtype=torch.float32, device=runner.device)
         selected = np.zeros_like(counts)
         parts = []
         for lo, hi in embedding_blocks(counts, row_bytes, budget_bytes):
             if int(counts[lo:hi].sum()) == 0:
                 continue
+            if keep_inputs:
+                pipe.inputs_into = all_inputs[kept_rows:]
             _scores, got, _stats, _lat = pipe.run(list(paths[lo:hi]), table=tab.sub(lo, hi))
             if select is not None:   # the planned grid count is an upper bound; the pipeline reports what it kept
                 if np.any(np.asarray(got) > select.max_counts(counts[lo:hi])):
@@ -150,6 +167,9 @@ def embed_files(runner, paths: list[str], chunk_overlap: float = 0.0, max_durati
                 emb = pool_scores_device(runner.ctx, emb.contiguous(), nz, pooling)
             parts.append(_to_host(emb.contiguous()))
             pipe.embeddings = None
+            if keep_inputs:
+                kept_rows += int(pipe.inputs.shape[0])
+                pipe.inputs = pipe.inputs_into = None
     finally:
         pipe.close()
     out = np.concatenate(parts) if parts else np.zeros((0, D), np.int8 if dtype == "int8" else np.float32)
@@ -161,7 +181,10 @@ def embed_files(runner, paths: list[str], chunk_overlap: float = 0.0, max_durati
         file_index = np.flatnonzero(counts > 0).astype(np.int64)
         start_s = np.zeros(file_index.shape[0], np.float64)
     skipped = [p for p, k in zip(paths, tab.kind) if k < 0]
-    return FileEmbeddings(out, file_index, start_s, list(paths), counts, pooling, dtype, float(info["scale"]), int(info["zero_point"]), skipped, candidates)
+    res = FileEmbeddings(out, file_index, start_s, list(paths), counts, pooling, dtype, float(info["scale"]), int(info["zero_point"]), skipped, candidates)
+    if keep_inputs:
+        res.inputs = all_inputs[:kept_rows]   # (with a selection a view of the buffer sized for its upper bound, which the budget covered)
+    return res
 
 
 def save_embeddings_npz(path: str, res: FileEmbeddings) -> None:

@@ -176,6 +176,40 @@ class HipRunner:
         self._precomputed = {"mode": {"librosa": "mel", "log_mel": "log_mel", "mfcc": "mfcc"}[name], "sample_rate": int(sample_rate),
                              "mag_scale": mag_scale if name == "librosa" else "none", "n_fft": int(n_fft), "mel_bins": mels, "n_mfcc": int(n_mfcc)}
 
+    def model_inputs_device(self, audio, hop: int | None = None):
+        """``audio``: CUDA float32 ``[B, T]`` chunks -> the model inputs ``[B, input_elems]`` that ``predict_device`` takes: what
+        ``infer_audio_device`` computes in front of the network, kept (``evaluation.embeddings.embed_files(keep_inputs=True)``, the
+        augmented probe fit).  Hybrid models: the normalised STFT magnitudes (``stft_device``); the fused audio path of
+        ``infer_audio_device`` forms the same map inside its kernels, rounded its own way on float32 plans."""
+        torch = self._torch
+        self._check_dev(audio, "audio")
+        if self.input_kind == pk.INPUT_MEL:
+            if self._precomputed is None:
+                raise ValueError("precomputed-frontend model: call configure_precomputed(audio_frontend, sample_rate, mag_scale, ...) first")
+            from birdnet_stm32.audio.spectrogram import mel_spectrograms_device
+
+            c = self._precomputed
+            spec = mel_spectrograms_device(self.ctx, audio, c["sample_rate"], c["n_fft"], c["mel_bins"], self.spec_width, c["mag_scale"],
+                                           c["mode"], c["n_mfcc"])
+            return spec.view(spec.shape[0], -1)
+        if self.input_kind == pk.INPUT_WAVEFORM:
+            # raw frontend: the model input is the chunk divided by (its peak + 1e-6) (reference: evaluation/metrics.py:62-69)
+            if audio.shape[1] != self.input_elems:
+                raise ValueError(f"raw-frontend model expects {self.input_elems} samples per chunk, got {audio.shape[1]}")
+            x = torch.empty_like(audio)
+            with torch.cuda.device(self.device):
+                _hip.check(self.lib.bn_chunk_peak_normalize(self.ctx.handle, audio.data_ptr(), audio.shape[0], audio.shape[1], 1e-6,
+                                                            x.data_ptr(), self._stream()))
+            return x
+        spec = self.stft_device(audio, hop=hop, normalize=True)
+        return spec.view(spec.shape[0], -1)
+
+    def input_shape(self) -> tuple[int, int]:
+        """``(F, W)`` of a model-input row as the augmentation sees it: ``(1, T)`` for the raw frontend, else ``(rows, spec_width)``."""
+        if self.input_kind == pk.INPUT_WAVEFORM:
+            return 1, int(self.input_elems)
+        return int(self.input_elems) // int(self.spec_width), int(self.spec_width)
+
     def infer_audio_device(self, audio, hop: int | None = None, return_logits: bool = False, out=None, return_embeddings: bool = False,
                            emb_dtype: str = "float32", emb_out=None):
         """``audio``: CUDA float32 ``[B, T]`` chunks -> scores ``[B, C]`` (STFT + frontend + network on the GPU).
@@ -185,27 +219,8 @@ class HipRunner:
         torch = self._torch
         self._check_dev(audio, "audio")
         kw = dict(return_embeddings=True, emb_dtype=emb_dtype, emb_out=emb_out) if return_embeddings else {}
-        if self.input_kind == pk.INPUT_MEL:
-            if self._precomputed is None:
-                raise ValueError("precomputed-frontend model: call configure_precomputed(audio_frontend, sample_rate, mag_scale, ...) first")
-            from birdnet_stm32.audio.spectrogram import mel_spectrograms_device
-
-            c = self._precomputed
-            spec = mel_spectrograms_device(self.ctx, audio, c["sample_rate"], c["n_fft"], c["mel_bins"], self.spec_width, c["mag_scale"],
-                                           c["mode"], c["n_mfcc"])
-            res = self.predict_device(spec.view(spec.shape[0], -1), return_logits=return_logits, **kw)
-            if out is not None:
-                out.copy_(res[0] if isinstance(res, tuple) else res)
-            return res
-        if self.input_kind == pk.INPUT_WAVEFORM:
-            # raw frontend: the model input is the chunk divided by (its peak + 1e-6) (reference: evaluation/metrics.py:62-69)
-            if audio.shape[1] != self.input_elems:
-                raise ValueError(f"raw-frontend model expects {self.input_elems} samples per chunk, got {audio.shape[1]}")
-            x = torch.empty_like(audio)
-            with torch.cuda.device(self.device):
-                _hip.check(self.lib.bn_chunk_peak_normalize(self.ctx.handle, audio.data_ptr(), audio.shape[0], audio.shape[1], 1e-6,
-                                                            x.data_ptr(), self._stream()))
-            res = self.predict_device(x, return_logits=return_logits, **kw)
+        if self.input_kind in (pk.INPUT_MEL, pk.INPUT_WAVEFORM):
+            res = self.predict_device(self.model_inputs_device(audio), return_logits=return_logits, **kw)
             if out is not None:
                 out.copy_(res[0] if isinstance(res, tuple) else res)
             return res

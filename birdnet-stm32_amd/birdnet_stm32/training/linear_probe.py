@@ -6,6 +6,8 @@ on the ``[N, D]`` matrix, which stays on the device for the whole fit (``csrc/bn
 
 * ``fit_probe``            the device fit,
 * ``fit_probe_reference``  the same procedure in numpy: the specification the device code is tested against,
+* ``fit_probe_augmented``  the device fit on fresh embeddings per epoch: mixup and SpecAugment over resident model inputs
+  (``training/augment.py``, ``csrc/bn_augment.hip``), and ``fit_probe_augmented_reference``, the same loop in numpy,
 * ``ProbeHead``            the result: ``W [D, C]``, ``b [C]``, activation, class names; ``save`` / ``load`` (plain ``.npz``), ``predict``,
 * ``run_linear_probe``     class folders -> embeddings -> head -> files on disk (the ``probe`` command).
 
@@ -415,6 +417,182 @@ def fit_probe(ctx_or_runner, X, Y, X_val=None, Y_val=None, *, activation="sigmoi
     return ProbeHead(W, b, activation, list(class_names or []), history)
 
 
+# -- the fit on augmented inputs ------------------------------------------------------------------------------------------------------
+def _check_augmented_args(augment, activation, input_shape, n_elems):
+    """The refusals of the augmented fit that need no model: raised before anything is loaded or uploaded."""
+    from birdnet_stm32.training.augment import ProbeAugmentation
+
+    if not isinstance(augment, ProbeAugmentation):
+        raise ValueError("augment must be a ProbeAugmentation")
+    if not augment.active:
+        raise ValueError("the augmentation is off (no mixup, no SpecAugment): call fit_probe on the embeddings instead")
+    if augment.mixup and activation == "softmax":
+        raise ValueError("mixup takes the union of its sources' labels, which is no distribution: use activation='sigmoid' "
+                         "(the reference switches to sigmoid whenever mixup is on)")
+    F, W = (int(v) for v in input_shape)
+    if F < 1 or W < 1 or (n_elems is not None and F * W != int(n_elems)):
+        raise ValueError(f"input_shape {F} x {W} does not match rows of {n_elems} elements")
+    return F, W
+
+
+class _Shape:
+    def __init__(self, *shape):
+        self.shape = shape
+
+
+def augmented_embeddings(runner, inputs, plan, out=None, slice_buf=None):
+    """Embeddings ``[plan.rows, D]`` (CUDA float32) of the plan's augmented rows: in slices of ``runner.max_batch``, ``bn_augment_inputs``
+    into one slice buffer and the backbone over it.  ``inputs``: the resident un-augmented model inputs ``[n, F * W]``."""
+    import ctypes
+
+    import torch
+
+    from birdnet_stm32 import _hip
+    from birdnet_stm32.training.augment import check_plan
+
+    n, E = int(inputs.shape[0]), int(inputs.shape[1])
+    if not (inputs.is_cuda and inputs.dtype == torch.float32 and inputs.is_contiguous() and E == int(plan.F) * int(plan.W)):
+        raise ValueError(f"inputs must be a contiguous float32 CUDA tensor [n, {int(plan.F) * int(plan.W)}]")
+    check_plan(plan, n)
+    m, mb = plan.rows, int(runner.max_batch)
+    dev = inputs.device
+    up = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+    d_nsrc, d_src, d_gain, d_f, d_t = (up(a) for a in (plan.nsrc, plan.src, plan.gain, plan.fmask, plan.tmask))
+    nf, nt = (0 if t is None else int(t.shape[1]) for t in (plan.fmask, plan.tmask))
+    D = int(runner.embedding_info()["dim"])
+    if out is None:
+        out = torch.empty((m, D), dtype=torch.float32, device=dev)
+    if slice_buf is None:
+        slice_buf = torch.empty((min(mb, max(m, 1)), E), dtype=torch.float32, device=dev)
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    with torch.cuda.device(dev):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        for b0 in range(0, m, mb):
+            nb = min(mb, m - b0)
+            _hip.check(runner.ctx.lib.bn_augment_inputs(runner.ctx.handle, inputs.data_ptr(), n, int(plan.F), int(plan.W), d_nsrc[b0:].data_ptr(),
+                                                        d_src[b0:].data_ptr(), d_gain[b0:].data_ptr(), ptr(d_f), nf, ptr(d_t), nt, nb,
+                                                        slice_buf.data_ptr(), stream))
+            runner.predict_device(slice_buf[:nb], return_embeddings=True, emb_out=out[b0 : b0 + nb])
+        torch.cuda.current_stream(dev).synchronize()   # (the tables are freed on return)
+    return out
+
+
+class _AugmentedDeviceBackend(_DeviceBackend):
+    """The device fit over rows that change per epoch: ``epoch`` first builds that epoch's ``X`` / ``Y`` in place, then runs the plain epoch."""
+
+    def __init__(self, runner, inputs, Y, Xv, Yv, W, b, cfg, augment, F, W_in):
+        import time
+
+        import torch
+
+        self.runner, self.inputs, self.aug, self.F, self.W_in, self.time = runner, inputs, augment, F, W_in, time
+        self.Y_host = np.ascontiguousarray(Y, np.float32)
+        n, D = int(inputs.shape[0]), int(runner.embedding_info()["dim"])
+        super().__init__(runner.ctx, torch.zeros((n, D), dtype=torch.float32, device=inputs.device), self.Y_host, Xv, Yv, W, b, cfg)
+        self.slice_buf = torch.empty((min(int(runner.max_batch), n), int(inputs.shape[1])), dtype=torch.float32, device=inputs.device)
+        self.epochs_done, self.augment_seconds = 0, []
+
+    def epoch(self, perm):
+        from birdnet_stm32.training.augment import augment_plan, mixed_targets
+
+        t0 = self.time.perf_counter()
+        plan = augment_plan(self.n, self.F, self.W_in, self.aug, self.cfg["seed"], self.epochs_done)
+        augmented_embeddings(self.runner, self.inputs, plan, out=self.X, slice_buf=self.slice_buf)
+        self.Y.copy_(self.torch.from_numpy(mixed_targets(self.Y_host, plan)))
+        self.torch.cuda.current_stream(self.dev).synchronize()
+        self.augment_seconds.append(self.time.perf_counter() - t0)
+        self.epochs_done += 1
+        return super().epoch(perm)
+
+
+def fit_probe_augmented(runner, inputs, Y, X_val=None, Y_val=None, *, augment, input_shape, activation="sigmoid", epochs=50, batch_size=32,
+                        learning_rate=1e-3, optimizer="adam", weight_decay=0.0, clipnorm=1.0, dropout=0.5, patience=10, seed=42,
+                        class_names=None) -> ProbeHead:
+    """``fit_probe`` on fresh embeddings per epoch (reference: training/linear_probe.py:112-125, whose training loader masks and mixes).
+
+    ``inputs [N, F * W]``: the un-augmented model inputs of the training rows (``HipRunner.model_inputs_device``; a CUDA tensor stays
+    where it is, a numpy array is uploaded once), ``input_shape = (F, W)`` (the raw frontend: ``(1, T)``).  Epoch ``e`` builds
+    ``training.augment.augment_plan(N, F, W, augment, seed, e)``, augments on the device (``bn_augment_inputs``), embeds the rows again with
+    the frozen backbone and runs the plain epoch (same permutation, same dropout draws) on them with ``mixed_targets``.  ``X_val`` are
+    embeddings of un-augmented validation rows, computed once by the caller.  ``history["augment_seconds"]`` holds the per-epoch time of
+    plan + augmentation + backbone.  The same inputs and seed give the same bits on every run."""
+    import torch
+
+    from birdnet_stm32 import _hip
+
+    F, W_in = _check_augmented_args(augment, activation, input_shape, inputs.shape[1] if len(inputs.shape) == 2 else None)
+    if not hasattr(runner, "predict_device"):
+        raise ValueError("fit_probe_augmented needs the model's runner: the backbone runs every epoch")
+    if len(inputs.shape) != 2:
+        raise ValueError(f"inputs must be [N, F * W], got {tuple(inputs.shape)}")
+    n, D = int(inputs.shape[0]), int(runner.embedding_info()["dim"])
+    _check_fit_args(_Shape(n, D), Y, activation, optimizer, batch_size, dropout, epochs)
+    C = int(Y.shape[1])
+    if not (1 <= D <= _hip.PROBE_MAX_D and 1 <= C <= _hip.PROBE_MAX_C):
+        raise ValueError(f"the device path takes 1 <= D <= {_hip.PROBE_MAX_D} and 1 <= C <= {_hip.PROBE_MAX_C}, got D={D} C={C}")
+    if int(inputs.shape[1]) != int(runner.input_elems):
+        raise ValueError(f"inputs have {int(inputs.shape[1])} elements per row, the model takes {runner.input_elems}")
+    if isinstance(inputs, np.ndarray):
+        inputs = torch.from_numpy(np.ascontiguousarray(inputs, np.float32)).to(runner.device)
+    if isinstance(Y, torch.Tensor):
+        Y = Y.cpu().numpy()
+    batch = min(int(batch_size), n)
+    has_val = X_val is not None and len(X_val) > 0
+    W0, b0 = init_head(D, C, seed)
+    cfg = dict(activation=activation, optimizer=optimizer, batch=batch, seed=int(seed), dropout=float(dropout), clipnorm=float(clipnorm),
+               lr=float(learning_rate), weight_decay=float(weight_decay), total=int(epochs) * math.ceil(n / batch))
+    be = _AugmentedDeviceBackend(runner, inputs.contiguous(), Y, X_val if has_val else None, Y_val if has_val else None, W0, b0, cfg, augment, F, W_in)
+    try:
+        history = _fit_loop(be, n, int(epochs), batch, int(seed), int(patience), has_val)
+        W, b = be.get()
+        W, b = W.cpu().numpy(), b.cpu().numpy()
+        history["augment_seconds"] = list(be.augment_seconds)
+    finally:
+        be.close()
+    return ProbeHead(W, b, activation, list(class_names or []), history)
+
+
+class _AugmentedNumpyBackend(_NumpyBackend):
+    def __init__(self, embed, inputs, Y, Xv, Yv, W, b, cfg, dtype, augment, F, W_in):
+        self.embed, self.inputs, self.Y_host, self.aug, self.F, self.W_in, self.epochs_done = embed, inputs, Y, augment, F, W_in, 0
+        super().__init__(None, None, Xv, Yv, W, b, cfg, dtype)
+
+    def epoch(self, perm):
+        from birdnet_stm32.training.augment import augment_plan, augment_reference, mixed_targets
+
+        plan = augment_plan(self.inputs.shape[0], self.F, self.W_in, self.aug, self.cfg["seed"], self.epochs_done)
+        self.X = np.asarray(self.embed(augment_reference(self.inputs, plan))).astype(self.dt)
+        self.Y = mixed_targets(self.Y_host, plan).astype(self.dt)
+        self.epochs_done += 1
+        return super().epoch(perm)
+
+    def val_loss(self):
+        D = self.P.shape[0] - 1
+        return probe_loss(head_scores(self.Xv, self.P[:D], self.P[D], self.cfg["activation"]), self.Yv, self.cfg["activation"])
+
+
+def fit_probe_augmented_reference(embed, inputs, Y, X_val=None, Y_val=None, *, augment, input_shape, activation="sigmoid", epochs=50, batch_size=32,
+                                  learning_rate=1e-3, optimizer="adam", weight_decay=0.0, clipnorm=1.0, dropout=0.5, patience=10, seed=42,
+                                  dtype=np.float64, class_names=None) -> ProbeHead:
+    """The procedure of ``fit_probe_augmented`` in numpy over a caller-supplied ``embed(inputs [N, F * W] float32) -> X [N, D]``."""
+    inputs, Y = np.ascontiguousarray(inputs, np.float32), np.asarray(Y)
+    F, W_in = _check_augmented_args(augment, activation, input_shape, inputs.shape[1] if inputs.ndim == 2 else None)
+    n = inputs.shape[0]
+    D = int(np.asarray(embed(inputs[:1])).shape[1])
+    _check_fit_args(_Shape(n, D), Y, activation, optimizer, batch_size, dropout, epochs)
+    batch = min(int(batch_size), n)
+    has_val = X_val is not None and len(X_val) > 0
+    W0, b0 = init_head(D, Y.shape[1], seed)
+    cfg = dict(activation=activation, optimizer=optimizer, batch=batch, seed=int(seed), dropout=float(dropout), clipnorm=float(np.float32(clipnorm)),
+               lr=float(learning_rate), weight_decay=float(weight_decay), total=int(epochs) * math.ceil(n / batch))
+    be = _AugmentedNumpyBackend(embed, inputs, Y, np.asarray(X_val).astype(dtype) if has_val else None,
+                                np.asarray(Y_val).astype(dtype) if has_val else None, W0, b0, cfg, np.dtype(dtype).type, augment, F, W_in)
+    history = _fit_loop(be, n, int(epochs), batch, int(seed), int(patience), has_val)
+    W, b = be.get()
+    history["W"], history["b"] = W, b
+    return ProbeHead(W, b, activation, list(class_names or []), history)
+
+
 # -- from class folders to a head on disk ---------------------------------------------------------------------------------------------
 def split_train_val(paths: list, val_split: float) -> tuple[list, list]:
     """The first ``1 - val_split`` of the (already shuffled) list trains, the rest validates (reference: linear_probe.py, cli/train.py)."""
@@ -459,6 +637,20 @@ def _join_embeddings(a, b):
                    candidate_rows=a.candidate_rows + b.candidate_rows)
 
 
+def augmentation_from_args(args):
+    """The ``ProbeAugmentation`` the ``--mixup_*`` / ``--spec_augment`` / ``--*_mask_max`` flags of ``probe`` ask for, ``None`` when both are
+    off or absent (older namespaces); bad values and mixup with softmax are refused here, before anything is loaded."""
+    from birdnet_stm32.training.augment import ProbeAugmentation
+
+    aug = ProbeAugmentation(mixup_alpha=float(getattr(args, "mixup_alpha", 0.2)), mixup_probability=float(getattr(args, "mixup_probability", 0.0) or 0.0),
+                            spec_augment=bool(getattr(args, "spec_augment", False)), freq_mask_max=int(getattr(args, "freq_mask_max", 8)),
+                            time_mask_max=int(getattr(args, "time_mask_max", 25)))
+    if not aug.active:
+        return None
+    _check_augmented_args(aug, getattr(args, "activation", "sigmoid"), (1, 1), None)
+    return aug
+
+
 def run_linear_probe(args, runner=None) -> ProbeHead:
     """The ``probe`` command: ``args.data_path_train/<class>/*`` -> embeddings (the backbone runs once) -> ``fit_probe`` ->
     ``<output>.npz``, ``<output>_labels.txt``, ``<output>_model_config.json`` and ``<output>_history.csv``."""
@@ -470,6 +662,7 @@ def run_linear_probe(args, runner=None) -> ProbeHead:
     from birdnet_stm32.evaluation.embeddings import embed_files
     from birdnet_stm32.training.config import ModelConfig
 
+    augment = augmentation_from_args(args)
     if not os.path.isfile(args.model_path):
         raise FileNotFoundError(f"Pretrained model not found: {args.model_path}")
     cfg = ModelConfig.load(resolve_config_path(args.model_path, getattr(args, "model_config", "")))
@@ -492,7 +685,14 @@ def run_linear_probe(args, runner=None) -> ProbeHead:
     kw = dict(chunk_overlap=overlap, max_duration=args.max_duration, pooling="none", dtype="float32", sample_rate=int(cfg.sample_rate),
               chunk_duration=float(cfg.chunk_duration))
     select = selection_from_args(args)
-    if select is None:
+    train_inputs = None
+    if augment is not None:
+        # training files keep their model inputs on the device; validation files take the plain path (with a selection at 0.5, as below)
+        emb = embed_files(runner, train_paths, select=select, keep_inputs=True, **kw)
+        train_inputs = emb.inputs
+        if val_paths:
+            emb = _join_embeddings(emb, embed_files(runner, val_paths, select=selection_from_args(args, 0.5), **kw))
+    elif select is None:
         emb = embed_files(runner, train_paths + val_paths, **kw)
     else:
         # the reference's loader (data/generator.py:87-157): training files at --activity_threshold, validation files at 0.5 (its linear probe's
@@ -500,6 +700,7 @@ def run_linear_probe(args, runner=None) -> ProbeHead:
         emb = embed_files(runner, train_paths, select=select, **kw)
         if val_paths:
             emb = _join_embeddings(emb, embed_files(runner, val_paths, select=selection_from_args(args, 0.5), **kw))
+    if select is not None:
         print(f"[probe] selection: {emb.candidate_rows} candidate rows -> {emb.embeddings.shape[0]} rows (at most {select.max_chunks_per_file} per file, "
               f"{select.candidate_chunks} candidates)")
     t_embed = time.perf_counter() - t0
@@ -509,10 +710,22 @@ def run_linear_probe(args, runner=None) -> ProbeHead:
     if not tr.any():
         raise ValueError("no training rows: every training file was unreadable, empty or of a noise folder")
     t0 = time.perf_counter()
-    head = fit_probe(runner, emb.embeddings[tr], Y[tr], emb.embeddings[va] if va.any() else None, Y[va] if va.any() else None,
-                     activation=args.activation, epochs=args.epochs, batch_size=args.batch_size, learning_rate=args.learning_rate,
-                     optimizer=args.optimizer, weight_decay=args.weight_decay, clipnorm=args.grad_clip, dropout=args.dropout,
-                     patience=getattr(args, "patience", 10), seed=args.seed, class_names=classes)
+    fit_kw = dict(activation=args.activation, epochs=args.epochs, batch_size=args.batch_size, learning_rate=args.learning_rate,
+                  optimizer=args.optimizer, weight_decay=args.weight_decay, clipnorm=args.grad_clip, dropout=args.dropout,
+                  patience=getattr(args, "patience", 10), seed=args.seed, class_names=classes)
+    if augment is None:
+        head = fit_probe(runner, emb.embeddings[tr], Y[tr], emb.embeddings[va] if va.any() else None, Y[va] if va.any() else None, **fit_kw)
+    else:
+        import torch
+
+        n_train = int(is_train.sum())   # the kept inputs are the training rows, in row order
+        if train_inputs.shape[0] != n_train:
+            raise RuntimeError("the kept model inputs do not match the training rows")
+        rows = tr[:n_train]
+        inputs = train_inputs if rows.all() else train_inputs[torch.from_numpy(np.flatnonzero(rows)).to(train_inputs.device)]
+        head = fit_probe_augmented(runner, inputs, Y[tr], emb.embeddings[va] if va.any() else None, Y[va] if va.any() else None, augment=augment,
+                                   input_shape=runner.input_shape(), **fit_kw)
+        del train_inputs, inputs
     t_fit = time.perf_counter() - t0
     out = probe_output_paths(args.output)
     os.makedirs(os.path.dirname(os.path.abspath(out["head"])), exist_ok=True)
@@ -523,7 +736,9 @@ def run_linear_probe(args, runner=None) -> ProbeHead:
     write_history_csv(out["history"], head.history)
     head.history["seconds"] = {"embed": t_embed, "fit": t_fit}
     val = head.history["val_loss"]
-    print(f"[probe] {int(tr.sum())} training rows x {head.embedding_dim}: embeddings {t_embed:.2f} s, fit {t_fit:.2f} s ({len(head.history['loss'])} epochs, "
+    aug_s = head.history.get("augment_seconds")
+    aug_note = f" of which augment + re-embed {sum(aug_s):.2f} s = {1e3 * sum(aug_s) / len(aug_s):.1f} ms per epoch" if aug_s else ""
+    print(f"[probe] {int(tr.sum())} training rows x {head.embedding_dim}: embeddings {t_embed:.2f} s, fit {t_fit:.2f} s{aug_note} ({len(head.history['loss'])} epochs, "
           f"loss {head.history['loss'][-1]:.4f}" + (f", best val_loss {min(val):.4f}" if val else "") + f") -> {out['head']}")
     if emb.skipped:
         print(f"[probe] skipped {len(emb.skipped)} unreadable or empty files")

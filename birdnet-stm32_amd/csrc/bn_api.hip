@@ -1016,7 +1016,7 @@ int bn_preload_kernels(bn_ctx* ctx) {
     // copies wait meanwhile).  A caller with idle time before its first batch — the evaluate pipeline while the first files are read — asks here.
     bn::preload_ingest(); bn::preload_stft(); bn::preload_stft_exact(); bn::preload_i8_fused(); bn::preload_i8_strip(); bn::preload_i8_tail2();
     bn::preload_i8_tail(); bn::preload_i8(); bn::preload_i8_pw(); bn::preload_f32(); bn::preload_f32_fused(); bn::preload_f32_strip();
-    bn::preload_f32_pw(); bn::preload_melspec(); bn::preload_sort(); bn::preload_probe(); bn::preload_activity(); bn::preload_search();
+    bn::preload_f32_pw(); bn::preload_melspec(); bn::preload_sort(); bn::preload_probe(); bn::preload_activity(); bn::preload_search(); bn::preload_augment();
     return BN_OK;
 }
 
@@ -1035,7 +1035,7 @@ const char* bn_kernel_names(void) {
     return "ingest_resample_kernel\ningest_decimate_kernel\ningest_peak_kernel\ningest_chunks_kernel\nchunk_peaknorm_kernel\npool_scores_kernel\nstft512_mag_kernel\nspec_normalize_kernel\nmelspec_finish_kernel\nf32_mel_kernel\nf32_melfin_kernel\nf32_mag_kernel\nf32_rawfe_kernel\nf32_stem_kernel\nf32_dw_kernel\n"
            "f32_pw_kernel\nf32_pw_ws_kernel\nf32_dwpw_kernel\nf32_dwpw_wave_kernel\nf32_strip_kernel\nf32_front_strip_kernel\nf32_front2_kernel\nf32_pwdw_kernel\nf32_dw_stream_kernel\nf32_front_kernel\nf32_gap_kernel\nf32_gap_dense_kernel\nf32_gap_dense_emb_kernel\nf32_dense_kernel\nf32_segate_kernel\nf32_scale_kernel\nf32_attnpool_kernel\n"
            "i8_quant_kernel\ni8_mel_kernel\ni8_stem_kernel\ni8_dw_kernel\ni8_pw_kernel\ni8_dwpw_kernel\ni8_mel_mfma_kernel\ni8_strip_kernel\ni8_strip_mf_kernel\ni8_front_strip_kernel\ni8_front_kernel\ni8_tail_kernel\ni8_tail_emb_kernel\ni8_tail2_kernel\ni8_tail2_emb_kernel\ni8_mid2_kernel\ni8_mean_kernel\ni8_fc_kernel\ni8_scale_kernel\ni8_maxnorm_kernel\ni8_rawfe_kernel\ni8_pwdw_kernel\ni8_dw_stream_kernel\ni8_stem_stream_kernel\ni8_segate_kernel\ni8_pw_wave_kernel\ni8_pw_lds_kernel\ni8_attnpool_kernel\n"
-           "i8_head_kernel\ni8_head_softmax_kernel\nemb_store_kernel\nprobe_fwd_kernel\nprobe_dw_kernel\nprobe_reduce_kernel\nprobe_update_kernel\nprobe_loss_sum_kernel\nste_kernel\nactivity_count_kernel\nsearch_inv_norms_kernel\nsearch_score_kernel\nsearch_merge_kernel";
+           "i8_head_kernel\ni8_head_softmax_kernel\nemb_store_kernel\nprobe_fwd_kernel\nprobe_dw_kernel\nprobe_reduce_kernel\nprobe_update_kernel\nprobe_loss_sum_kernel\nste_kernel\nactivity_count_kernel\nsearch_inv_norms_kernel\nsearch_score_kernel\nsearch_merge_kernel\naugment_kernel";
 }
 
 }  // extern "C"
@@ -1327,6 +1327,32 @@ int bn_search_topk(bn_ctx* ctx, const void* d_db, int dtype, int64_t n, int D, i
         bn::launch_search_merge(part_score, part_idx, g.nwg, nq, k, d_idx + (size_t)q0 * k, d_score + (size_t)q0 * k, s);
         HIP_TRY(hipGetLastError());
     }
+    return BN_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------- augmentation (bn_augment.hip)
+extern "C" {
+
+int bn_augment_inputs(bn_ctx* ctx, const float* d_x, int64_t n_rows, int F, int W, const int32_t* d_nsrc, const int32_t* d_src, const float* d_gain,
+                      const int32_t* d_fmask, int nf, const int32_t* d_tmask, int nt, int64_t m, float* d_out, void* stream) {
+    if (int rc = check_device(ctx)) return rc;
+    if (n_rows < 1 || n_rows > 0x7fffffffLL || m < 0 || m > 0x7fffffffLL) return fail(BN_ERR_ARG, "bad row counts n_rows=%lld m=%lld", (long long)n_rows, (long long)m);
+    if (F < 1 || W < 1 || (int64_t)F * W > BN_AUGMENT_MAX_ROW) return fail(BN_ERR_ARG, "bad row shape %d x %d (at most %d elements)", F, W, BN_AUGMENT_MAX_ROW);
+    if (nf < 0 || nf > BN_AUGMENT_MAX_MASKS || nt < 0 || nt > BN_AUGMENT_MAX_MASKS)
+        return fail(BN_ERR_ARG, "nf=%d nt=%d: at most %d masks per axis", nf, nt, BN_AUGMENT_MAX_MASKS);
+    if ((nf > 0) != (d_fmask != nullptr) || (nt > 0) != (d_tmask != nullptr)) return fail(BN_ERR_ARG, "a mask table and its count go together");
+    if (!d_x || !d_nsrc || !d_src || !d_gain || !d_out) return fail(BN_ERR_ARG, "null device pointer");
+    if ((uintptr_t)d_x % 4 || (uintptr_t)d_out % 4 || (uintptr_t)d_nsrc % 4 || (uintptr_t)d_src % 4 || (uintptr_t)d_gain % 4 || (uintptr_t)d_fmask % 4 ||
+        (uintptr_t)d_tmask % 4)
+        return fail(BN_ERR_ARG, "rows and tables must be 4-byte aligned");
+    const size_t E = (size_t)F * W;
+    const uintptr_t x0 = (uintptr_t)d_x, x1 = x0 + (size_t)n_rows * E * 4, o0 = (uintptr_t)d_out, o1 = o0 + (size_t)m * E * 4;
+    if (o0 < x1 && x0 < o1) return fail(BN_ERR_ARG, "d_out overlaps d_x");
+    if (m == 0) return BN_OK;
+    bn::launch_augment(d_x, (long)n_rows, W, (int)E, d_nsrc, d_src, d_gain, d_fmask, nf, d_tmask, nt, (long)m, d_out, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
     return BN_OK;
 }
 

@@ -473,7 +473,7 @@ void launch_i8_dwpw(const DwPw8Args& a, hipStream_t s);
 // One per source file with kernels: load that file's device code object now (bn_preload_kernels)
 void preload_f32(); void preload_f32_fused(); void preload_f32_pw(); void preload_f32_strip(); void preload_i8(); void preload_i8_fused();
 void preload_i8_pw(); void preload_i8_strip(); void preload_i8_tail(); void preload_i8_tail2(); void preload_ingest(); void preload_melspec();
-void preload_stft(); void preload_stft_exact(); void preload_sort(); void preload_probe(); void preload_activity(); void preload_search();
+void preload_stft(); void preload_stft_exact(); void preload_sort(); void preload_probe(); void preload_activity(); void preload_search(); void preload_augment();
 
 // bn_probe.hip: a classifier head on embeddings (bn_head_forward) and its training step (bn_probe_*)
 struct ProbeFwdArgs {
@@ -545,5 +545,9 @@ bool search_geometry(long n, int D, int Q, int k, bool i8, SearchGeom* g);   // 
 void launch_search_inv_norms(const void* rows, bool i8, long n, int D, int zp, float* inv, hipStream_t s);
 bool launch_search_scores(const SearchArgs& a, const SearchGeom& g, bool i8, hipStream_t s);   // false: the runtime refused the LDS request
 void launch_search_merge(const float* part_score, const int* part_idx, int nwg, int Q, int k, int* out_idx, float* out_score, hipStream_t s);
+
+// bn_augment.hip: mixup and SpecAugment over resident model-input rows of E = F * W floats (bn_augment_inputs)
+void launch_augment(const float* x, long n_rows, int W, int E, const int* nsrc, const int* src, const float* gain, const int* fmask, int nf,
+                    const int* tmask, int nt, long m, float* out, hipStream_t s);
 
 }  // namespace bn

@@ -444,6 +444,25 @@ BN_API int bn_search_topk(bn_ctx* ctx, const void* d_db, int dtype, int64_t n, i
                    int64_t Q, const float* d_q_inv, int metric, const int32_t* d_db_group, const int32_t* d_q_group, int k, int32_t* d_idx,
                    float* d_score, void* stream);
 
+/* ---- Probe augmentation: mixup and SpecAugment over resident model inputs (csrc/bn_augment.hip) --------------------------------------
+ * (reference: audio/augmentation.py:10-120 as data/generator.py:169-170 and :406-418 apply them: every sample is masked in the loader, the
+ * batch is mixed afterwards.)  d_x holds n_rows un-augmented rows of E = F * W float32 (the raw frontend: F = 1, W = T).  Output row r:
+ *   masked(x[s])(f, t) = +0.0f where f lies in any [f0, f0 + width) of d_fmask[s] or t in any of d_tmask[s], x[s](f, t) elsewhere -- the
+ *                        masks belong to the SOURCE row s; a mask reaching past F or W is clipped, a width <= 0 masks nothing;
+ *   d_nsrc[r] == 1:  out[r] = masked(x[src0])                       unmasked elements are copied bit for bit (no multiply)
+ *   d_nsrc[r] == 2:  out[r] = fl(fl(g0 * v0) + fl(g1 * v1))         every product and sum rounded to float32, nothing fused,
+ *   d_nsrc[r] == 3:  out[r] = fl(fl(fl(g0 * v0) + fl(g1 * v1)) + fl(g2 * v2))    float32 subnormals kept
+ * which is numpy's np.sum(gains[:, None] * masked[src], axis=0), including its start from +0.0 (products that are all -0.0 sum to +0.0); birdnet_stm32/training/augment.py `augment_reference` is the specification and
+ * the results equal it bit for bit.
+ *   d_nsrc [m] int32, d_src [m, 3] int32, d_gain [m, 3] float32 (slots past nsrc are not read as sources);
+ *   d_fmask [n_rows, nf, 2] / d_tmask [n_rows, nt, 2] int32 (start, width), NULL exactly when the count is 0; counts <= BN_AUGMENT_MAX_MASKS.
+ * The host cannot see the device tables: the kernel clamps nsrc to 1..3 and every source index to [0, n_rows), so a bad plan gives a wrong
+ * row, never a stray read.  Rows and tables need 4-byte alignment only; d_out [m, E] must not overlap d_x.  F * W <= BN_AUGMENT_MAX_ROW. */
+#define BN_AUGMENT_MAX_MASKS 4
+#define BN_AUGMENT_MAX_ROW (1 << 28)
+BN_API int bn_augment_inputs(bn_ctx* ctx, const float* d_x, int64_t n_rows, int F, int W, const int32_t* d_nsrc, const int32_t* d_src,
+                      const float* d_gain, const int32_t* d_fmask, int nf, const int32_t* d_tmask, int nt, int64_t m, float* d_out, void* stream);
+
 /* Loads every device code object of the library now.  The HIP runtime loads one at the first launch of any of its kernels (a few ms each; launches
  * and copies of OTHER threads wait meanwhile), which a first batch otherwise pays one file after the other on its critical path; a caller with idle
  * time before that batch (the evaluate pipeline while the first files are being read) calls this instead.  Idempotent.  (Reference counterpart:
