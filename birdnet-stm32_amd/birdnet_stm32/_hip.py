@@ -32,6 +32,7 @@ EXPORTS = (
     "bn_forward_embed", "bn_infer_audio_embed", "bn_model_get_embedding_info", "bn_ingest_resample_span",
     "bn_head_forward", "bn_probe_create", "bn_probe_destroy", "bn_probe_epoch", "bn_probe_loss", "bn_probe_get", "bn_probe_set",
     "bn_short_time_energy", "bn_activity_counts", "bn_search_inv_norms", "bn_search_topk", "bn_augment_inputs",
+    "bn_kmeans_assign", "bn_kmeans_accumulate", "bn_kmeans_centroids",
 )  # fmt: skip
 
 EMB_F32, EMB_I8 = 0, 1  # BN_EMB_* (include/birdnet_hip.h)
@@ -43,6 +44,21 @@ SEARCH_METRICS = {"cosine": 0, "dot": 1}  # BN_SEARCH_*
 SEARCH_MAX_K, SEARCH_MAX_D = 128, 2048
 AUGMENT_MAX_MASKS = 4  # BN_AUGMENT_MAX_MASKS
 SEARCH_STEP_ROWS, SEARCH_MIN_WG_STEPS, SEARCH_MAX_WGS = 64, 8, 1024  # how bn_search_topk deals rows to workgroups (include/birdnet_hip.h)
+# bn_kmeans_* (include/birdnet_hip.h): limits, and the constants the centroid tiles, the row steps and the update's segments follow from
+KMEANS_MAX_K, KMEANS_MAX_D = 4096, 2048
+KMEANS_LDS_BYTES, KMEANS_MAX_TILE, KMEANS_STEP_ROWS, KMEANS_MIN_WG_STEPS, KMEANS_MAX_WGS, KMEANS_SEGMENT_ROWS = 160 * 1024, 128, 64, 8, 1024, 256
+
+
+def kmeans_tile_centroids(D: int, K: int) -> int:
+    """Centroids per LDS tile of ``bn_kmeans_assign`` (``kmeans_geometry`` of csrc/bn_kmeans.hip)."""
+    pitch_bytes = (-(-int(D) // 64) * 64 + 4) * 4
+    nt = 1
+    while nt < KMEANS_MAX_TILE // 16 and 16 * nt < K:
+        nt *= 2
+    while nt > 1 and 16 * nt * pitch_bytes > KMEANS_LDS_BYTES:
+        nt //= 2
+    return 16 * nt
+
 
 # launcher switches of bn_set_option (include/birdnet_hip.h); the production defaults are what a fresh process has
 OPTION_NAMES = ("f32_strip", "f32_strip_th", "f32_front_staged", "f32_front2", "f32_pwdw", "f32_tile_slice", "f32_pw_ws", "i8_pwdw", "i8_pw_lds", "i8_pw_forms", "i8_add_tab", "front_tpw", "wave_dwpw", "i8_strip", "i8_strip_mfdw", "i8_strip_th", "i8_dw_pool", "i8_tail_fclds", "i8_tail", "i8_tail_mfdw", "i8_mid",
@@ -135,6 +151,10 @@ def load_library(path: str | None = None):
     lib.bn_search_inv_norms.argtypes = [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p]
     lib.bn_search_topk.argtypes = [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p,
                                    c_int, c_void_p, c_void_p, c_void_p]
+    lib.bn_kmeans_assign.argtypes = [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p]
+    lib.bn_kmeans_accumulate.argtypes = [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]
+    lib.bn_kmeans_centroids.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]
     lib.bn_augment_inputs.argtypes = [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int64,
                                       c_void_p, c_void_p]
     lib.bn_host_alloc_pinned.argtypes = [c_void_p, ctypes.c_size_t]

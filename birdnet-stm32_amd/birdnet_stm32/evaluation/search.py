@@ -220,6 +220,35 @@ class EmbeddingIndex:
             self._ctx.close()
             self._ctx = None
 
+    def context(self, ctx=None, device: int = 0):
+        """``ctx`` if one is given, else the index's own context on ``device`` (created on first use, replaced when the device changes)."""
+        from birdnet_stm32 import _hip
+
+        if ctx is not None:
+            return ctx
+        if self._ctx is None or self._ctx.device != int(device):
+            self.close()
+            self._ctx = _hip.Context(int(device), 1)
+        return self._ctx
+
+    def device_block(self, ctx, lo: int, hi: int, stream_ptr):
+        """Rows ``lo .. hi`` of a block of ``block_ranges()`` on ``ctx``'s device with their inverse norms and file groups (tensors; to be
+        called under ``torch.cuda.device``).  The block of an index that fits its budget is kept for the next call."""
+        import torch
+
+        from birdnet_stm32 import _hip
+
+        if self._resident is not None and self._resident[0] == (ctx.device, lo, hi):
+            return self._resident[1:]
+        dev = torch.device("cuda", ctx.device)
+        code = _hip.DTYPE_I8 if self.dtype == "int8" else _hip.DTYPE_F32
+        d_db = torch.from_numpy(self.embeddings[lo:hi]).to(dev)
+        d_inv = torch.empty(hi - lo, dtype=torch.float32, device=dev)
+        d_grp = torch.from_numpy(self.file_group[self.file_index[lo:hi]].astype(np.int32)).to(dev)
+        _hip.check(ctx.lib.bn_search_inv_norms(ctx.handle, d_db.data_ptr(), code, hi - lo, self.dim, self.zero_point, d_inv.data_ptr(), stream_ptr))
+        self._resident = ((ctx.device, lo, hi), d_db, d_inv, d_grp) if (lo, hi) == (0, len(self)) else None
+        return d_db, d_inv, d_grp
+
     def _check_queries(self, queries):
         """Queries as a contiguous CUDA tensor of the index's dtype (numpy arrays are checked on the host, tensors on the device)."""
         import torch
@@ -267,11 +296,7 @@ class EmbeddingIndex:
             if qgrp.shape != (q.shape[0],) or (qgrp.size and qgrp.max() >= len(self.paths)):
                 raise ValueError("query_file_index needs one entry per query, each -1 or an index into paths")
             qgrp = np.where(qgrp >= 0, self.file_group[np.maximum(qgrp, 0)] if len(self.paths) else -1, -1)
-        if ctx is None:
-            if self._ctx is None or self._ctx.device != int(device):
-                self.close()
-                self._ctx = _hip.Context(int(device), 1)
-            ctx = self._ctx
+        ctx = self.context(ctx, device)
         dev = torch.device("cuda", ctx.device)
         Q = int(q.shape[0])
         code = _hip.DTYPE_I8 if self.dtype == "int8" else _hip.DTYPE_F32
@@ -288,14 +313,7 @@ class EmbeddingIndex:
             for lo, hi in blocks:
                 if hi == lo or Q == 0:
                     continue
-                if self._resident is not None and self._resident[0] == (ctx.device, lo, hi):
-                    _, d_db, d_inv, d_grp = self._resident
-                else:
-                    d_db = torch.from_numpy(self.embeddings[lo:hi]).to(dev)
-                    d_inv = torch.empty(hi - lo, dtype=torch.float32, device=dev)
-                    d_grp = torch.from_numpy(self.file_group[self.file_index[lo:hi]].astype(np.int32)).to(dev)
-                    _hip.check(ctx.lib.bn_search_inv_norms(ctx.handle, d_db.data_ptr(), code, hi - lo, self.dim, self.zero_point, d_inv.data_ptr(), sp))
-                    self._resident = ((ctx.device, lo, hi), d_db, d_inv, d_grp) if len(blocks) == 1 else None
+                d_db, d_inv, d_grp = self.device_block(ctx, lo, hi, sp)
                 d_idx = torch.empty((Q, k), dtype=torch.int32, device=dev)
                 d_score = torch.empty((Q, k), dtype=torch.float32, device=dev)
                 _hip.check(ctx.lib.bn_search_topk(ctx.handle, d_db.data_ptr(), code, hi - lo, self.dim, self.zero_point, d_inv.data_ptr(), d_q.data_ptr(), Q,

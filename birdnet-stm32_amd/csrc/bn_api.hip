@@ -185,6 +185,7 @@ void bn_ctx_destroy(bn_ctx* c) {
     (void)hipFree(c->d_block_peaks);
     if (c->d_rank_work) (void)hipFree(c->d_rank_work);
     if (c->d_search_work) (void)hipFree(c->d_search_work);
+    if (c->d_kmeans_work) (void)hipFree(c->d_kmeans_work);
     delete c;
 }
 
@@ -1016,7 +1017,7 @@ int bn_preload_kernels(bn_ctx* ctx) {
     // copies wait meanwhile).  A caller with idle time before its first batch — the evaluate pipeline while the first files are read — asks here.
     bn::preload_ingest(); bn::preload_stft(); bn::preload_stft_exact(); bn::preload_i8_fused(); bn::preload_i8_strip(); bn::preload_i8_tail2();
     bn::preload_i8_tail(); bn::preload_i8(); bn::preload_i8_pw(); bn::preload_f32(); bn::preload_f32_fused(); bn::preload_f32_strip();
-    bn::preload_f32_pw(); bn::preload_melspec(); bn::preload_sort(); bn::preload_probe(); bn::preload_activity(); bn::preload_search(); bn::preload_augment();
+    bn::preload_f32_pw(); bn::preload_melspec(); bn::preload_sort(); bn::preload_probe(); bn::preload_activity(); bn::preload_search(); bn::preload_augment(); bn::preload_kmeans();
     return BN_OK;
 }
 
@@ -1035,7 +1036,7 @@ const char* bn_kernel_names(void) {
     return "ingest_resample_kernel\ningest_decimate_kernel\ningest_peak_kernel\ningest_chunks_kernel\nchunk_peaknorm_kernel\npool_scores_kernel\nstft512_mag_kernel\nspec_normalize_kernel\nmelspec_finish_kernel\nf32_mel_kernel\nf32_melfin_kernel\nf32_mag_kernel\nf32_rawfe_kernel\nf32_stem_kernel\nf32_dw_kernel\n"
            "f32_pw_kernel\nf32_pw_ws_kernel\nf32_dwpw_kernel\nf32_dwpw_wave_kernel\nf32_strip_kernel\nf32_front_strip_kernel\nf32_front2_kernel\nf32_pwdw_kernel\nf32_dw_stream_kernel\nf32_front_kernel\nf32_gap_kernel\nf32_gap_dense_kernel\nf32_gap_dense_emb_kernel\nf32_dense_kernel\nf32_segate_kernel\nf32_scale_kernel\nf32_attnpool_kernel\n"
            "i8_quant_kernel\ni8_mel_kernel\ni8_stem_kernel\ni8_dw_kernel\ni8_pw_kernel\ni8_dwpw_kernel\ni8_mel_mfma_kernel\ni8_strip_kernel\ni8_strip_mf_kernel\ni8_front_strip_kernel\ni8_front_kernel\ni8_tail_kernel\ni8_tail_emb_kernel\ni8_tail2_kernel\ni8_tail2_emb_kernel\ni8_mid2_kernel\ni8_mean_kernel\ni8_fc_kernel\ni8_scale_kernel\ni8_maxnorm_kernel\ni8_rawfe_kernel\ni8_pwdw_kernel\ni8_dw_stream_kernel\ni8_stem_stream_kernel\ni8_segate_kernel\ni8_pw_wave_kernel\ni8_pw_lds_kernel\ni8_attnpool_kernel\n"
-           "i8_head_kernel\ni8_head_softmax_kernel\nemb_store_kernel\nprobe_fwd_kernel\nprobe_dw_kernel\nprobe_reduce_kernel\nprobe_update_kernel\nprobe_loss_sum_kernel\nste_kernel\nactivity_count_kernel\nsearch_inv_norms_kernel\nsearch_score_kernel\nsearch_merge_kernel\naugment_kernel";
+           "i8_head_kernel\ni8_head_softmax_kernel\nemb_store_kernel\nprobe_fwd_kernel\nprobe_dw_kernel\nprobe_reduce_kernel\nprobe_update_kernel\nprobe_loss_sum_kernel\nste_kernel\nactivity_count_kernel\nsearch_inv_norms_kernel\nsearch_score_kernel\nsearch_merge_kernel\naugment_kernel\nkmeans_assign_kernel\nkmeans_keys_kernel\nkmeans_offsets_kernel\nkmeans_segments_kernel\nkmeans_partial_kernel\nkmeans_fold_kernel\nkmeans_scale_kernel";
 }
 
 }  // extern "C"
@@ -1327,6 +1328,95 @@ int bn_search_topk(bn_ctx* ctx, const void* d_db, int dtype, int64_t n, int D, i
         bn::launch_search_merge(part_score, part_idx, g.nwg, nq, k, d_idx + (size_t)q0 * k, d_score + (size_t)q0 * k, s);
         HIP_TRY(hipGetLastError());
     }
+    return BN_OK;
+}
+
+}  // extern "C"
+
+// --------------------------------------------------------------------------------------------------------------- k-means (bn_kmeans.hip)
+namespace {
+
+int kmeans_shape_check(int dtype, int64_t n, int D, int K, int zero_point) {
+    if (dtype != BN_DTYPE_F32 && dtype != BN_DTYPE_I8) return fail(BN_ERR_ARG, "unknown dtype %d", dtype);
+    if (D < 1 || D > BN_KMEANS_MAX_D) return fail(BN_ERR_ARG, "embedding width D=%d outside 1..%d", D, BN_KMEANS_MAX_D);
+    if (K < 1 || K > BN_KMEANS_MAX_K) return fail(BN_ERR_ARG, "K=%d outside 1..%d", K, BN_KMEANS_MAX_K);
+    if (n < 0 || n > 0x7fffffffLL) return fail(BN_ERR_ARG, "bad row count %lld", (long long)n);
+    if (dtype == BN_DTYPE_I8 && (zero_point < -128 || zero_point > 127)) return fail(BN_ERR_ARG, "zero point %d outside -128..127", zero_point);
+    return BN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bn_kmeans_assign(bn_ctx* ctx, const void* d_rows, int dtype, int64_t n, int D, int zero_point, const float* d_row_inv, const float* d_centroids,
+                     const float* d_cent_inv, int K, const int32_t* d_prev_label, int32_t* d_label, float* d_score, int64_t* d_changed, void* stream) {
+    if (int rc = check_device(ctx)) return rc;
+    if (int rc = kmeans_shape_check(dtype, n, D, K, zero_point)) return rc;
+    if (!d_rows || !d_row_inv || !d_centroids || !d_cent_inv || !d_label || !d_score || !d_changed) return fail(BN_ERR_ARG, "null device pointer");
+    if (d_prev_label == d_label) return fail(BN_ERR_ARG, "d_prev_label must not be d_label");
+    if (dtype == BN_DTYPE_F32 && (uintptr_t)d_rows % 4) return fail(BN_ERR_ARG, "float32 rows must be 4-byte aligned");
+    if ((uintptr_t)d_row_inv % 4 || (uintptr_t)d_centroids % 4 || (uintptr_t)d_cent_inv % 4 || (uintptr_t)d_prev_label % 4 || (uintptr_t)d_label % 4 ||
+        (uintptr_t)d_score % 4 || (uintptr_t)d_changed % 8)
+        return fail(BN_ERR_ARG, "float32 / int32 arrays must be 4-byte aligned, d_changed 8-byte aligned");
+    const bool i8 = dtype == BN_DTYPE_I8;
+    hipStream_t s = (hipStream_t)stream;
+    bn::KmeansGeom g{};
+    if (!bn::kmeans_geometry((long)n, D, K, &g)) return fail(BN_ERR_ARG, "D=%d: no centroid tile fits the LDS", D);
+    HIP_TRY(hipMemsetAsync(d_changed, 0, sizeof(int64_t), s));
+    if (n == 0) return BN_OK;
+    bn::KmeansAssignArgs a{};
+    a.rows = d_rows; a.row_inv = d_row_inv; a.cent = d_centroids; a.cent_inv = d_cent_inv; a.prev = d_prev_label; a.label = d_label; a.score = d_score;
+    a.changed = (unsigned long long*)d_changed;
+    a.n = (int)n; a.D = D; a.K = K; a.zp = i8 ? zero_point : 0; a.steps_per_wg = g.steps_per_wg;
+    if (!bn::launch_kmeans_assign(a, g, i8, s)) return fail(BN_ERR_DEVICE, "the assignment kernel's LDS request was refused");
+    HIP_TRY(hipGetLastError());
+    return BN_OK;
+}
+
+int bn_kmeans_accumulate(bn_ctx* ctx, const void* d_rows, int dtype, int64_t n, int D, int zero_point, const float* d_row_inv, const int32_t* d_label, int K,
+                         int accumulate, float* d_sums, int64_t* d_counts, void* stream) {
+    if (int rc = check_device(ctx)) return rc;
+    if (int rc = kmeans_shape_check(dtype, n, D, K, zero_point)) return rc;
+    if (!d_rows || !d_row_inv || !d_label || !d_sums || !d_counts) return fail(BN_ERR_ARG, "null device pointer");
+    if (dtype == BN_DTYPE_F32 && (uintptr_t)d_rows % 4) return fail(BN_ERR_ARG, "float32 rows must be 4-byte aligned");
+    if ((uintptr_t)d_row_inv % 4 || (uintptr_t)d_label % 4 || (uintptr_t)d_sums % 4 || (uintptr_t)d_counts % 8)
+        return fail(BN_ERR_ARG, "float32 / int32 arrays must be 4-byte aligned, d_counts 8-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    if (n == 0) {
+        if (!accumulate) {
+            HIP_TRY(hipMemsetAsync(d_sums, 0, (size_t)K * D * sizeof(float), s));
+            HIP_TRY(hipMemsetAsync(d_counts, 0, (size_t)K * sizeof(int64_t), s));
+        }
+        return BN_OK;
+    }
+    const size_t need = bn::kmeans_accumulate_workspace((long)n, D, K);
+    if (need > ctx->kmeans_work_bytes) {   // (grown outside any capture, as bn_search_topk grows its own)
+        HIP_TRY(hipStreamSynchronize(s));
+        if (ctx->d_kmeans_work) (void)hipFree(ctx->d_kmeans_work);
+        ctx->d_kmeans_work = nullptr;
+        ctx->kmeans_work_bytes = 0;
+        if (hipMalloc(&ctx->d_kmeans_work, need) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(BN_ERR_NOMEM, "hipMalloc of %zu bytes for the k-means workspace failed", need);
+        }
+        ctx->kmeans_work_bytes = need;
+    }
+    if (!bn::launch_kmeans_accumulate(d_rows, dtype == BN_DTYPE_I8, (long)n, D, zero_point, d_row_inv, d_label, K, accumulate != 0, d_sums, (long long*)d_counts,
+                                      ctx->d_kmeans_work, ctx->kmeans_work_bytes, s))
+        return fail(BN_ERR_DEVICE, "the sort of the rows by label failed");
+    HIP_TRY(hipGetLastError());
+    return BN_OK;
+}
+
+int bn_kmeans_centroids(bn_ctx* ctx, const float* d_sums, const int64_t* d_counts, int K, int D, float* d_centroids, float* d_cent_inv, void* stream) {
+    if (int rc = check_device(ctx)) return rc;
+    if (int rc = kmeans_shape_check(BN_DTYPE_F32, 0, D, K, 0)) return rc;
+    if (!d_sums || !d_counts || !d_centroids || !d_cent_inv) return fail(BN_ERR_ARG, "null device pointer");
+    if ((uintptr_t)d_sums % 4 || (uintptr_t)d_centroids % 4 || (uintptr_t)d_cent_inv % 4 || (uintptr_t)d_counts % 8)
+        return fail(BN_ERR_ARG, "float32 arrays must be 4-byte aligned, d_counts 8-byte aligned");
+    bn::launch_kmeans_centroids(d_sums, (const long long*)d_counts, K, D, d_centroids, d_cent_inv, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
     return BN_OK;
 }
 

@@ -473,7 +473,7 @@ void launch_i8_dwpw(const DwPw8Args& a, hipStream_t s);
 // One per source file with kernels: load that file's device code object now (bn_preload_kernels)
 void preload_f32(); void preload_f32_fused(); void preload_f32_pw(); void preload_f32_strip(); void preload_i8(); void preload_i8_fused();
 void preload_i8_pw(); void preload_i8_strip(); void preload_i8_tail(); void preload_i8_tail2(); void preload_ingest(); void preload_melspec();
-void preload_stft(); void preload_stft_exact(); void preload_sort(); void preload_probe(); void preload_activity(); void preload_search(); void preload_augment();
+void preload_stft(); void preload_stft_exact(); void preload_sort(); void preload_probe(); void preload_activity(); void preload_search(); void preload_augment(); void preload_kmeans();
 
 // bn_probe.hip: a classifier head on embeddings (bn_head_forward) and its training step (bn_probe_*)
 struct ProbeFwdArgs {
@@ -545,6 +545,33 @@ bool search_geometry(long n, int D, int Q, int k, bool i8, SearchGeom* g);   // 
 void launch_search_inv_norms(const void* rows, bool i8, long n, int D, int zp, float* inv, hipStream_t s);
 bool launch_search_scores(const SearchArgs& a, const SearchGeom& g, bool i8, hipStream_t s);   // false: the runtime refused the LDS request
 void launch_search_merge(const float* part_score, const int* part_idx, int nwg, int Q, int k, int* out_idx, float* out_score, hipStream_t s);
+
+// bn_kmeans.hip: spherical k-means, one Lloyd iteration = an assignment and an update (bn_kmeans_*)
+struct KmeansAssignArgs {
+    const void* rows;        // [n, D] float32 or int8 rows
+    const float* row_inv;    // [n] inverse norms
+    const float* cent;       // [K, D] float32 centroids
+    const float* cent_inv;   // [K]
+    const int* prev;         // [n] labels of the previous assignment, or null
+    int* label;              // [n] best centroid, -1 for a zero row
+    float* score;            // [n]
+    unsigned long long* changed;   // rows whose label differs from prev (every non-zero row without prev), added to
+    int n, D, K, zp;
+    long steps_per_wg;       // steps of BN_KMEANS_STEP_ROWS rows a workgroup streams
+};
+struct KmeansGeom {
+    int nt;                  // centroid subtiles of 16 per LDS tile
+    int tiles;               // LDS tiles the K centroids take
+    int nwg;                 // workgroups along the rows
+    long steps_per_wg;
+    size_t lds;
+};
+bool kmeans_geometry(long n, int D, int K, KmeansGeom* g);   // from the shapes only; false: no tile fits the LDS
+bool launch_kmeans_assign(const KmeansAssignArgs& a, const KmeansGeom& g, bool i8, hipStream_t s);   // false: the runtime refused the LDS request
+size_t kmeans_accumulate_workspace(long n, int D, int K);
+bool launch_kmeans_accumulate(const void* rows, bool i8, long n, int D, int zp, const float* row_inv, const int* label, int K, int accumulate, float* sums,
+                              long long* counts, void* d_work, size_t work_bytes, hipStream_t s);
+void launch_kmeans_centroids(const float* sums, const long long* counts, int K, int D, float* cent, float* cent_inv, hipStream_t s);
 
 // bn_augment.hip: mixup and SpecAugment over resident model-input rows of E = F * W floats (bn_augment_inputs)
 void launch_augment(const float* x, long n_rows, int W, int E, const int* nsrc, const int* src, const float* gain, const int* fmask, int nf,

@@ -64,6 +64,8 @@ struct bn_ctx {
     size_t rank_work_bytes = 0;
     void* d_search_work = nullptr;   // bn_search_topk: the workgroups' partial lists; grown on demand
     size_t search_work_bytes = 0;
+    void* d_kmeans_work = nullptr;   // bn_kmeans_accumulate: sort keys, row orders, segment partial sums, rocPRIM storage; grown on demand
+    size_t kmeans_work_bytes = 0;
 };
 
 struct bn_model {

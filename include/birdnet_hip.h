@@ -444,6 +444,49 @@ BN_API int bn_search_topk(bn_ctx* ctx, const void* d_db, int dtype, int64_t n, i
                    int64_t Q, const float* d_q_inv, int metric, const int32_t* d_db_group, const int32_t* d_q_group, int k, int32_t* d_idx,
                    float* d_score, void* stream);
 
+/* ---- Clustering: spherical k-means over an embedding matrix (csrc/bn_kmeans.hip; no reference counterpart) ---------------------------
+ * Rows are BN_DTYPE_F32 values or the BN_DTYPE_I8 bytes of bn_forward_embed with their zero point; an int8 row means
+ * float32(byte - zero_point), which is exact, and everything after that is float32.  Centroids are float32 [K, D].  Inverse norms of rows
+ * and centroids come from bn_search_inv_norms.  One Lloyd iteration is bn_kmeans_assign, bn_kmeans_accumulate and bn_kmeans_centroids.
+ *   score[i, c] = fl(fl(dot(x_i, C_c) * inv_row[i]) * inv_cent[c])   (the dot product's summation order is the implementation's)
+ *   label[i]    = the centroid with the highest score, the lowest index among equal scores; a zero row (inv_row == 0) gets label -1 and
+ *                 score 0 and takes no part in sums, counts or the changed count
+ *   S[c]        = sum over the members of c, in ascending row order, of fl(inv_row[i] * x_i): segments of BN_KMEANS_SEGMENT_ROWS members are
+ *                 summed one after the other and folded in segment order, so the order follows from (labels, n, D, K) alone
+ * 1 <= D <= BN_KMEANS_MAX_D, 1 <= K <= BN_KMEANS_MAX_K, 0 <= n < 2^31.  float32 rows need 4-byte alignment (16 with D % 4 == 0 takes the
+ * wide loads; int8: 16 with D % 16 == 0).  No floating-point atomics: the same inputs give the same bits on every run.  A refused call
+ * returns BN_ERR_ARG and writes nothing. */
+#define BN_KMEANS_MAX_K 4096
+#define BN_KMEANS_MAX_D 2048
+/* How the work is dealt — from (n, D, K) alone.  Assignment: the centroids sit in LDS in tiles of 16, 32, 64 or BN_KMEANS_MAX_TILE, the
+ * smallest that holds K or else the largest whose rows of (D rounded up to 64, plus 4) floats fit BN_KMEANS_LDS_BYTES; rows go in steps of
+ * BN_KMEANS_STEP_ROWS, at least BN_KMEANS_MIN_WG_STEPS steps per workgroup, at most BN_KMEANS_MAX_WGS workgroups.  Update: a workgroup
+ * per segment of at most BN_KMEANS_SEGMENT_ROWS members of a cluster. */
+#define BN_KMEANS_LDS_BYTES (160 * 1024)
+#define BN_KMEANS_MAX_TILE 128
+#define BN_KMEANS_STEP_ROWS 64
+#define BN_KMEANS_MIN_WG_STEPS 8
+#define BN_KMEANS_MAX_WGS 1024
+#define BN_KMEANS_SEGMENT_ROWS 256
+
+/* d_label [n] int32 and d_score [n] float32 of the rows of d_rows [n, D] against d_centroids [K, D].  *d_changed (int64, 8-byte aligned)
+ * is set to the number of non-zero rows whose label differs from d_prev_label [n] (NULL: every non-zero row counts).  d_prev_label must
+ * not be d_label.  With more centroids than one LDS tile holds, d_label / d_score carry the best of the tiles seen so far while the call
+ * runs: they hold the result once it has finished, and nothing else may read or write them meanwhile.  Nothing synchronises with the host
+ * inside the call. */
+BN_API int bn_kmeans_assign(bn_ctx* ctx, const void* d_rows, int dtype, int64_t n, int D, int zero_point, const float* d_row_inv,
+                     const float* d_centroids, const float* d_cent_inv, int K, const int32_t* d_prev_label, int32_t* d_label, float* d_score,
+                     int64_t* d_changed, void* stream);
+/* d_sums [K, D] float32 and d_counts [K] int64 from the rows and their labels (a label outside 0 .. K-1 belongs to no cluster).  With
+ * accumulate != 0 the results are added to what d_sums / d_counts hold, the old sum first: an index larger than the device budget is
+ * processed block by block.  Nothing synchronises with the host inside the call unless the context's workspace has to grow. */
+BN_API int bn_kmeans_accumulate(bn_ctx* ctx, const void* d_rows, int dtype, int64_t n, int D, int zero_point, const float* d_row_inv,
+                         const int32_t* d_label, int K, int accumulate, float* d_sums, int64_t* d_counts, void* stream);
+/* d_centroids[c] = fl(d_sums[c] * inv_norm(d_sums[c])) for every cluster with d_counts[c] > 0 (the others keep their centroid), then
+ * d_cent_inv [K] = the inverse norms of the centroids. */
+BN_API int bn_kmeans_centroids(bn_ctx* ctx, const float* d_sums, const int64_t* d_counts, int K, int D, float* d_centroids, float* d_cent_inv,
+                        void* stream);
+
 /* ---- Probe augmentation: mixup and SpecAugment over resident model inputs (csrc/bn_augment.hip) --------------------------------------
  * (reference: audio/augmentation.py:10-120 as data/generator.py:169-170 and :406-418 apply them: every sample is masked in the loader, the
  * batch is mixed afterwards.)  d_x holds n_rows un-augmented rows of E = F * W float32 (the raw frontend: F = 1, W = T).  Output row r:
