@@ -271,7 +271,7 @@ class _DeviceBackend:
 
         self.torch, self.hip, self.index, self.ctx = torch, _hip, index, ctx
         self.dev = torch.device("cuda", ctx.device)
-        self.code = _hip.DTYPE_I8 if index.dtype == "int8" else _hip.DTYPE_F32
+        self.code = index.dtype_code
         self.N, self.D, self.K = len(index), index.dim, int(centroids.shape[0])
         self.blocks = index.block_ranges()
         with torch.cuda.device(self.dev):

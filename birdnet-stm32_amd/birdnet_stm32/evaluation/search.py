@@ -186,6 +186,13 @@ class EmbeddingIndex:
     def __len__(self) -> int:
         return int(self.embeddings.shape[0])
 
+    @property
+    def dtype_code(self) -> int:
+        """``dtype`` as the C ABI's ``BN_DTYPE_*``."""
+        from birdnet_stm32 import _hip
+
+        return _hip.DTYPE_I8 if self.dtype == "int8" else _hip.DTYPE_F32
+
     @classmethod
     def from_npz(cls, *paths: str, budget_bytes: int = 2 << 30) -> "EmbeddingIndex":
         if not paths:
@@ -241,11 +248,10 @@ class EmbeddingIndex:
         if self._resident is not None and self._resident[0] == (ctx.device, lo, hi):
             return self._resident[1:]
         dev = torch.device("cuda", ctx.device)
-        code = _hip.DTYPE_I8 if self.dtype == "int8" else _hip.DTYPE_F32
         d_db = torch.from_numpy(self.embeddings[lo:hi]).to(dev)
         d_inv = torch.empty(hi - lo, dtype=torch.float32, device=dev)
         d_grp = torch.from_numpy(self.file_group[self.file_index[lo:hi]].astype(np.int32)).to(dev)
-        _hip.check(ctx.lib.bn_search_inv_norms(ctx.handle, d_db.data_ptr(), code, hi - lo, self.dim, self.zero_point, d_inv.data_ptr(), stream_ptr))
+        _hip.check(ctx.lib.bn_search_inv_norms(ctx.handle, d_db.data_ptr(), self.dtype_code, hi - lo, self.dim, self.zero_point, d_inv.data_ptr(), stream_ptr))
         self._resident = ((ctx.device, lo, hi), d_db, d_inv, d_grp) if (lo, hi) == (0, len(self)) else None
         return d_db, d_inv, d_grp
 
@@ -299,7 +305,7 @@ class EmbeddingIndex:
         ctx = self.context(ctx, device)
         dev = torch.device("cuda", ctx.device)
         Q = int(q.shape[0])
-        code = _hip.DTYPE_I8 if self.dtype == "int8" else _hip.DTYPE_F32
+        code = self.dtype_code
         idx_parts, score_parts = [], []
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev)

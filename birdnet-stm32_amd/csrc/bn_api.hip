@@ -82,6 +82,32 @@ int check_device(bn_ctx* ctx) {
     return BN_OK;
 }
 
+// Grows a device buffer that a context or a probe owns to at least `need` bytes; `alloc` >= need is what it asks for when it has to.
+// Never inside a capture: it waits for the stream first, whose work in flight may still use the old buffer.  A refused allocation is the
+// caller's `code`, about its `what` workspace.
+int grow_device_buffer(void** p, size_t* have, size_t need, size_t alloc, hipStream_t s, int code, const char* what) {
+    if (need <= *have) return BN_OK;
+    HIP_TRY(hipStreamSynchronize(s));
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+    *have = 0;
+    if (hipMalloc(p, alloc) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(code, "hipMalloc of %zu bytes for the %s workspace failed", alloc, what);
+    }
+    *have = alloc;
+    return BN_OK;
+}
+
+// What every entry point over an [n, D] matrix of embedding rows (bn_search_*, bn_kmeans_*) checks first
+int row_matrix_check(int dtype, int64_t n, int D, int max_D, int zero_point) {
+    if (dtype != BN_DTYPE_F32 && dtype != BN_DTYPE_I8) return fail(BN_ERR_ARG, "unknown dtype %d", dtype);
+    if (D < 1 || D > max_D) return fail(BN_ERR_ARG, "embedding width D=%d outside 1..%d", D, max_D);
+    if (n < 0 || n > 0x7fffffffLL) return fail(BN_ERR_ARG, "bad row count %lld", (long long)n);
+    if (dtype == BN_DTYPE_I8 && (zero_point < -128 || zero_point > 127)) return fail(BN_ERR_ARG, "zero point %d outside -128..127", zero_point);
+    return BN_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -854,17 +880,8 @@ int bn_rank_orders(bn_ctx* ctx, const float* d_scores, int n_rows, int n_classes
     if (!d_scores || !d_cols || !d_flat) return fail(BN_ERR_ARG, "null device pointer");
     if ((int64_t)n_rows * n_classes > 0x3fffffffLL) return fail(BN_ERR_ARG, "rows x classes exceeds 2^30");
     const size_t need = bn::rank_orders_workspace(n_rows, n_classes);
-    if (need > ctx->rank_work_bytes) {   // (grown outside any capture: the call is made once per evaluation, behind the last inference)
-        HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-        if (ctx->d_rank_work) (void)hipFree(ctx->d_rank_work);
-        ctx->d_rank_work = nullptr;
-        ctx->rank_work_bytes = 0;
-        if (hipMalloc(&ctx->d_rank_work, need + need / 4) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(BN_ERR_DEVICE, "hipMalloc of %zu bytes for the sort workspace failed", need + need / 4);
-        }
-        ctx->rank_work_bytes = need + need / 4;
-    }
+    // (grown outside any capture: the call is made once per evaluation, behind the last inference)
+    if (int rc = grow_device_buffer(&ctx->d_rank_work, &ctx->rank_work_bytes, need, need + need / 4, (hipStream_t)stream, BN_ERR_DEVICE, "sort")) return rc;
     if (!bn::launch_rank_orders(d_scores, n_rows, n_classes, d_cols, d_flat, ctx->d_rank_work, ctx->rank_work_bytes, (hipStream_t)stream)) {
         (void)hipGetLastError();
         return fail(BN_ERR_DEVICE, "the device sort failed");
@@ -1049,9 +1066,9 @@ struct bn_probe {
     uint32_t seed = 0;
     int64_t total = 1, t = 0;                       // steps of the cosine schedule, steps taken
     float *d_params = nullptr, *d_m = nullptr, *d_v = nullptr;   // [(D + 1) * C] each: W, then the bias as row D
-    float* d_G = nullptr;         size_t G_elems = 0;       // [batch, C] dLoss/dlogits of one step
-    float* d_partial = nullptr;   size_t partial_elems = 0; // [row groups][(D + 1) * C]
-    float* d_loss_part = nullptr; size_t loss_elems = 0;    // one per 16 rows
+    float* d_G = nullptr;         size_t G_bytes = 0;       // [batch, C] dLoss/dlogits of one step
+    float* d_partial = nullptr;   size_t partial_bytes = 0; // [row groups][(D + 1) * C]
+    float* d_loss_part = nullptr; size_t loss_bytes = 0;    // one per 16 rows
     float* d_ss = nullptr;                                   // sums of squares per workgroup of the gradient / reduce kernel
 };
 
@@ -1084,18 +1101,8 @@ void probe_groups(int B, int D, int C, int* groups, int* rows_per_group) {
     *groups = (B + rpg - 1) / rpg;
 }
 
-int probe_grow(float** p, size_t* have, size_t need, hipStream_t s) {
-    if (need <= *have) return BN_OK;
-    HIP_TRY(hipStreamSynchronize(s));
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *have = 0;
-    if (hipMalloc(p, need * sizeof(float)) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(BN_ERR_NOMEM, "hipMalloc of %zu bytes for the probe workspace failed", need * sizeof(float));
-    }
-    *have = need;
-    return BN_OK;
+int probe_grow(float** p, size_t* bytes, size_t floats, hipStream_t s) {
+    return grow_device_buffer((void**)p, bytes, floats * sizeof(float), floats * sizeof(float), s, BN_ERR_NOMEM, "probe");
 }
 
 }  // namespace
@@ -1170,9 +1177,9 @@ int bn_probe_epoch(bn_probe* p, const float* d_X, const float* d_Y, const int32_
     hipStream_t s = (hipStream_t)stream;
     const int D = p->D, C = p->C, E = (D + 1) * C;
     int groups, rpg;
-    if (int rc = probe_grow(&p->d_G, &p->G_elems, (size_t)batch * C, s)) return rc;
-    if (int rc = probe_grow(&p->d_partial, &p->partial_elems, (size_t)probe_group_cap(batch, D, C) * E, s)) return rc;
-    if (int rc = probe_grow(&p->d_loss_part, &p->loss_elems, (size_t)(batch + 15) / 16, s)) return rc;
+    if (int rc = probe_grow(&p->d_G, &p->G_bytes, (size_t)batch * C, s)) return rc;
+    if (int rc = probe_grow(&p->d_partial, &p->partial_bytes, (size_t)probe_group_cap(batch, D, C) * E, s)) return rc;
+    if (int rc = probe_grow(&p->d_loss_part, &p->loss_bytes, (size_t)(batch + 15) / 16, s)) return rc;
     const uint32_t thresh = p->drop > 0.0f ? (uint32_t)std::ceil((double)p->drop * 16777216.0) : 0u;
     const float drop_scale = (float)(1.0 / (1.0 - (double)p->drop));
     const int64_t steps = (n + batch - 1) / batch;
@@ -1190,7 +1197,7 @@ int bn_probe_epoch(bn_probe* p, const float* d_X, const float* d_Y, const int32_
         f.g_scale = p->act == BN_PROBE_ACT_SOFTMAX ? (float)(1.0 / B) : (float)(1.0 / ((double)B * C));
         if (!bn::launch_probe_fwd(f, 0, s)) return fail(BN_ERR_DEVICE, "the probe forward kernel's LDS request was refused");
         probe_groups(B, D, C, &groups, &rpg);
-        if ((size_t)groups * E > p->partial_elems) return fail(BN_ERR_UNSUPPORTED, "%d row groups exceed the gradient workspace", groups);
+        if ((size_t)groups * E * sizeof(float) > p->partial_bytes) return fail(BN_ERR_UNSUPPORTED, "%d row groups exceed the gradient workspace", groups);
         bn::ProbeDwArgs g{};
         g.X = d_X; g.idx = idx; g.G = p->d_G; g.partial = p->d_partial; g.ss_part = p->d_ss; g.B = B; g.D = D; g.C = C; g.E = E;
         g.rows_per_group = rpg; g.drop_thresh = thresh; g.drop_scale = drop_scale; g.seed = p->seed; g.step = (uint32_t)p->t;
@@ -1217,7 +1224,7 @@ int bn_probe_loss(bn_probe* p, const float* d_X, const float* d_Y, int64_t n, fl
     if (n < 1 || n > 0x7fffffffLL) return fail(BN_ERR_ARG, "bad row count %lld", (long long)n);
     hipStream_t s = (hipStream_t)stream;
     const size_t parts = (size_t)(n + 15) / 16;
-    if (int rc = probe_grow(&p->d_loss_part, &p->loss_elems, parts, s)) return rc;
+    if (int rc = probe_grow(&p->d_loss_part, &p->loss_bytes, parts, s)) return rc;
     bn::ProbeFwdArgs f{};
     f.X = d_X; f.Y = d_Y; f.W = p->d_params; f.b = p->d_params + (size_t)p->D * p->C; f.loss_part = p->d_loss_part;
     f.n = n; f.D = p->D; f.C = p->C; f.softmax = p->act == BN_PROBE_ACT_SOFTMAX;
@@ -1251,23 +1258,11 @@ int bn_probe_set(bn_probe* p, const float* d_W, const float* d_b, void* stream) 
 }  // extern "C"
 
 // --------------------------------------------------------------------------------------------------------------- search (bn_search.hip)
-namespace {
-
-int search_shape_check(int dtype, int64_t n, int D) {
-    if (dtype != BN_DTYPE_F32 && dtype != BN_DTYPE_I8) return fail(BN_ERR_ARG, "unknown dtype %d", dtype);
-    if (D < 1 || D > BN_SEARCH_MAX_D) return fail(BN_ERR_ARG, "embedding width D=%d outside 1..%d", D, BN_SEARCH_MAX_D);
-    if (n < 0 || n > 0x7fffffffLL) return fail(BN_ERR_ARG, "bad row count %lld", (long long)n);
-    return BN_OK;
-}
-
-}  // namespace
-
 extern "C" {
 
 int bn_search_inv_norms(bn_ctx* ctx, const void* d_rows, int dtype, int64_t n, int D, int zero_point, float* d_inv, void* stream) {
     if (int rc = check_device(ctx)) return rc;
-    if (int rc = search_shape_check(dtype, n, D)) return rc;
-    if (dtype == BN_DTYPE_I8 && (zero_point < -128 || zero_point > 127)) return fail(BN_ERR_ARG, "zero point %d outside -128..127", zero_point);
+    if (int rc = row_matrix_check(dtype, n, D, BN_SEARCH_MAX_D, zero_point)) return rc;
     if (!d_rows || !d_inv) return fail(BN_ERR_ARG, "null device pointer");
     if (dtype == BN_DTYPE_F32 && (uintptr_t)d_rows % 4) return fail(BN_ERR_ARG, "float32 rows must be 4-byte aligned");
     if (n == 0) return BN_OK;
@@ -1280,11 +1275,10 @@ int bn_search_topk(bn_ctx* ctx, const void* d_db, int dtype, int64_t n, int D, i
                    int64_t Q, const float* d_q_inv, int metric, const int32_t* d_db_group, const int32_t* d_q_group, int k, int32_t* d_idx,
                    float* d_score, void* stream) {
     if (int rc = check_device(ctx)) return rc;
-    if (int rc = search_shape_check(dtype, n, D)) return rc;
+    if (int rc = row_matrix_check(dtype, n, D, BN_SEARCH_MAX_D, zero_point)) return rc;
     if (k < 1 || k > BN_SEARCH_MAX_K) return fail(BN_ERR_ARG, "k=%d outside 1..%d", k, BN_SEARCH_MAX_K);
     if (Q < 0 || Q > 0x7fffffffLL) return fail(BN_ERR_ARG, "bad query count %lld", (long long)Q);
     if (metric != BN_SEARCH_COSINE && metric != BN_SEARCH_DOT) return fail(BN_ERR_ARG, "unknown metric %d", metric);
-    if (dtype == BN_DTYPE_I8 && (zero_point < -128 || zero_point > 127)) return fail(BN_ERR_ARG, "zero point %d outside -128..127", zero_point);
     if (!d_db || !d_queries || !d_idx || !d_score) return fail(BN_ERR_ARG, "null device pointer");
     if (metric == BN_SEARCH_COSINE && (!d_db_inv || !d_q_inv)) return fail(BN_ERR_ARG, "the cosine metric needs both inverse-norm arrays");
     if ((d_db_group == nullptr) != (d_q_group == nullptr)) return fail(BN_ERR_ARG, "d_db_group and d_q_group go together");
@@ -1301,17 +1295,7 @@ int bn_search_topk(bn_ctx* ctx, const void* d_db, int dtype, int64_t n, int D, i
     if (group < pass_q) group = pass_q;
     if (group > Q) group = Q;
     const size_t need = (size_t)group * per_query;
-    if (need > ctx->search_work_bytes) {   // (grown outside any capture, as bn_rank_orders grows its own)
-        HIP_TRY(hipStreamSynchronize(s));
-        if (ctx->d_search_work) (void)hipFree(ctx->d_search_work);
-        ctx->d_search_work = nullptr;
-        ctx->search_work_bytes = 0;
-        if (hipMalloc(&ctx->d_search_work, need) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(BN_ERR_NOMEM, "hipMalloc of %zu bytes for the search workspace failed", need);
-        }
-        ctx->search_work_bytes = need;
-    }
+    if (int rc = grow_device_buffer(&ctx->d_search_work, &ctx->search_work_bytes, need, need, s, BN_ERR_NOMEM, "search")) return rc;
     float* part_score = (float*)ctx->d_search_work;
     int* part_idx = (int*)(part_score + (size_t)group * g.nwg * k);
     const size_t row_bytes = (size_t)D * (i8 ? 1 : 4);
@@ -1337,11 +1321,8 @@ int bn_search_topk(bn_ctx* ctx, const void* d_db, int dtype, int64_t n, int D, i
 namespace {
 
 int kmeans_shape_check(int dtype, int64_t n, int D, int K, int zero_point) {
-    if (dtype != BN_DTYPE_F32 && dtype != BN_DTYPE_I8) return fail(BN_ERR_ARG, "unknown dtype %d", dtype);
-    if (D < 1 || D > BN_KMEANS_MAX_D) return fail(BN_ERR_ARG, "embedding width D=%d outside 1..%d", D, BN_KMEANS_MAX_D);
+    if (int rc = row_matrix_check(dtype, n, D, BN_KMEANS_MAX_D, zero_point)) return rc;
     if (K < 1 || K > BN_KMEANS_MAX_K) return fail(BN_ERR_ARG, "K=%d outside 1..%d", K, BN_KMEANS_MAX_K);
-    if (n < 0 || n > 0x7fffffffLL) return fail(BN_ERR_ARG, "bad row count %lld", (long long)n);
-    if (dtype == BN_DTYPE_I8 && (zero_point < -128 || zero_point > 127)) return fail(BN_ERR_ARG, "zero point %d outside -128..127", zero_point);
     return BN_OK;
 }
 
@@ -1391,17 +1372,7 @@ int bn_kmeans_accumulate(bn_ctx* ctx, const void* d_rows, int dtype, int64_t n, 
         return BN_OK;
     }
     const size_t need = bn::kmeans_accumulate_workspace((long)n, D, K);
-    if (need > ctx->kmeans_work_bytes) {   // (grown outside any capture, as bn_search_topk grows its own)
-        HIP_TRY(hipStreamSynchronize(s));
-        if (ctx->d_kmeans_work) (void)hipFree(ctx->d_kmeans_work);
-        ctx->d_kmeans_work = nullptr;
-        ctx->kmeans_work_bytes = 0;
-        if (hipMalloc(&ctx->d_kmeans_work, need) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(BN_ERR_NOMEM, "hipMalloc of %zu bytes for the k-means workspace failed", need);
-        }
-        ctx->kmeans_work_bytes = need;
-    }
+    if (int rc = grow_device_buffer(&ctx->d_kmeans_work, &ctx->kmeans_work_bytes, need, need, s, BN_ERR_NOMEM, "k-means")) return rc;
     if (!bn::launch_kmeans_accumulate(d_rows, dtype == BN_DTYPE_I8, (long)n, D, zero_point, d_row_inv, d_label, K, accumulate != 0, d_sums, (long long*)d_counts,
                                       ctx->d_kmeans_work, ctx->kmeans_work_bytes, s))
         return fail(BN_ERR_DEVICE, "the sort of the rows by label failed");

@@ -2,9 +2,9 @@
 //
 //   kmeans_assign_kernel     grid (row ranges).  The centroids sit in LDS as the B operand of the matrix cores, a tile of 16 * NT at a
 //                            time (NT <= 8; the tile follows from D and BN_KMEANS_LDS_BYTES, kmeans_geometry).  A workgroup streams its
-//                            range of rows once per tile: 64 rows per step, 16 per wave, read with 16-byte loads straight into the A
-//                            operand (v_mfma_f32_16x16x4_f32: exact float32 products; int8 bytes become float32(byte - zero_point) on the
-//                            way, which is exact).  Per row it keeps the best (score, centroid) under the total order — score descending,
+//                            range of rows once per tile, straight into the A operand (bn_rowstream.h owns the row layout, the padding
+//                            beyond D and the prefetch depth; v_mfma_f32_16x16x4_f32: exact float32 products; int8 bytes become
+//                            float32(byte - zero_point) on the way, which is exact, and read as the zero point beyond D).  Per row it keeps the best (score, centroid) under the total order — score descending,
 //                            centroid index ascending — which is one value however the centroids are tiled: no list, no merge.  With
 //                            several tiles the best so far is carried in the row's own label / score slot, which only the lane that
 //                            wrote it reads again.  Rows whose label differs from the previous one are counted with integer adds.
@@ -19,7 +19,8 @@
 // No floating-point atomics anywhere: every sum's order is a function of (labels, n, D, K), so the same inputs give the same bits.
 //
 // Rounding: the dot product is an fmaf chain in the matrix cores (the specification leaves its order free); the two factors of the cosine
-// and the terms fl(inv * x) of the sums are single float32 operations, defined under a contraction-off pragma as in bn_search.hip.
+// and the terms fl(inv * x) of the sums are single float32 operations, defined in bn_rowstream.h under a contraction-off pragma that holds
+// for this whole file.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -27,29 +28,16 @@
 
 #include "../../include/birdnet_hip.h"
 #include "bn_kernels.h"
-
-#pragma clang fp contract(off)
+#include "bn_rowstream.h"
 
 namespace bn {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef int v4i __attribute__((ext_vector_type(4)));
-
 namespace {
 
-__device__ __forceinline__ float f_add(float a, float b) { return a + b; }
-__device__ __forceinline__ float f_mul(float a, float b) { return a * b; }
-
-constexpr int kWaves = 4;                       // waves per assignment workgroup, one 16-row tile each per step
-constexpr int kStepRows = BN_KMEANS_STEP_ROWS;  // 64
-constexpr int kGroup = 4;                       // chunks of a row tile whose loads are in flight together
 constexpr int kSeg = BN_KMEANS_SEGMENT_ROWS;
 constexpr int kMaxNT = BN_KMEANS_MAX_TILE / 16;
-static_assert(kStepRows == 16 * kWaves, "a step is one MFMA row tile per wave");
 static_assert(kMaxNT == 8, "the launcher instantiates 1, 2, 4 and 8 centroid subtiles");
 static_assert(BN_KMEANS_MAX_K <= 256 * 16, "kmeans_segments_kernel scans 16 clusters per thread");
 
-__host__ __device__ inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 // LDS pitch of a staged centroid in floats: the row padded to 64 elements (one 16-byte int8 load per lane and chunk) plus 4, so the 16
 // centroids of a B fragment start four banks apart
 __host__ __device__ inline int cent_pitch(int D) { return round_up(D, 64) + 4; }
@@ -62,14 +50,11 @@ bool kmeans_geometry(long n, int D, int K, KmeansGeom* g) {
     while (nt > 1 && (size_t)16 * nt * cent_pitch(D) * 4 > BN_KMEANS_LDS_BYTES) nt >>= 1;
     const size_t lds = (size_t)16 * nt * cent_pitch(D) * 4;
     if (lds > BN_KMEANS_LDS_BYTES) return false;
-    const long steps = (n + kStepRows - 1) / kStepRows;
-    long wgs = (steps + BN_KMEANS_MIN_WG_STEPS - 1) / BN_KMEANS_MIN_WG_STEPS;
-    wgs = wgs < 1 ? 1 : wgs > BN_KMEANS_MAX_WGS ? BN_KMEANS_MAX_WGS : wgs;
-    const long per = steps > 0 ? (steps + wgs - 1) / wgs : 1;
+    const RowSplit split = split_rows(n, BN_KMEANS_MIN_WG_STEPS, BN_KMEANS_MAX_WGS);
     g->nt = nt;
     g->tiles = (K + 16 * nt - 1) / (16 * nt);
-    g->steps_per_wg = per;
-    g->nwg = steps > 0 ? (int)((steps + per - 1) / per) : 1;
+    g->steps_per_wg = split.steps_per_wg;
+    g->nwg = split.nwg;
     g->lds = lds;
     return true;
 }
@@ -83,7 +68,7 @@ __global__ __launch_bounds__(256) void kmeans_assign_kernel(KmeansAssignArgs a) 
     const int D = a.D, K = a.K;
     const int pitch = cent_pitch(D), Dp = pitch - 4;
     float* cs = reinterpret_cast<float*>(smem);
-    const int nc = I8 ? Dp / 64 : round_up(D, 16) / 16;   // chunks of a row: 16 bytes per lane each
+    const int nc = row_chunks<I8>(D);
     const bool aligned = ((uintptr_t)a.rows % 16 == 0) && (I8 ? D % 16 == 0 : D % 4 == 0);
     const size_t row_bytes = (size_t)D * (I8 ? 1 : 4);
     const int pad = I8 ? (int)(0x01010101u * (unsigned)(a.zp & 0xff)) : 0;   // bytes equal to the zero point are 0.0f after the conversion
@@ -113,75 +98,38 @@ __global__ __launch_bounds__(256) void kmeans_assign_kernel(KmeansAssignArgs a) 
         for (long st = s0; st < s1; ++st) {
             const long tile_row = st * kStepRows + wave * 16;
             const long lrow = tile_row + li < a.n ? tile_row + li : (long)a.n - 1;   // rows past the end repeat the last one; nothing is written for them
-            const unsigned char* rp = (const unsigned char*)a.rows + (size_t)lrow * row_bytes;
-
-            // chunk c of this lane's row: 16 bytes at element offset 64 c + 16 lk (int8) / 16 c + 4 lk (float32), zero beyond D
-            auto load_a = [&](int c) -> v4i {
-                v4i v = {pad, pad, pad, pad};
-                if (c >= nc) return v;
-                if constexpr (I8) {
-                    const int d0 = c * 64 + lk * 16;
-                    if (aligned && d0 + 16 <= D) return *reinterpret_cast<const v4i*>(rp + d0);
-                    unsigned w[4] = {(unsigned)pad, (unsigned)pad, (unsigned)pad, (unsigned)pad};
-#pragma unroll
-                    for (int j = 0; j < 16; ++j)
-                        if (d0 + j < D) w[j >> 2] = (w[j >> 2] & ~(0xffu << (8 * (j & 3)))) | ((unsigned)rp[d0 + j] << (8 * (j & 3)));
-                    v = v4i{(int)w[0], (int)w[1], (int)w[2], (int)w[3]};
-                } else {
-                    const int d0 = c * 16 + lk * 4;
-                    if (aligned && d0 + 4 <= D) return *reinterpret_cast<const v4i*>(rp + (size_t)d0 * 4);
-                    int w[4] = {0, 0, 0, 0};
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        if (d0 + j < D) w[j] = reinterpret_cast<const int*>(rp)[d0 + j];
-                    v = v4i{w[0], w[1], w[2], w[3]};
-                }
-                return v;
-            };
+            const RowView<I8> row{(const unsigned char*)a.rows + (size_t)lrow * row_bytes, D, nc, lk, pad, aligned};
 
             f32x4 facc[NT];
 #pragma unroll
             for (int t = 0; t < NT; ++t) facc[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-            v4i cur[kGroup], nxt[kGroup];
+            row_stream(row, [&](int c, v4i av) __attribute__((always_inline)) {
+                if constexpr (I8) {
 #pragma unroll
-            for (int u = 0; u < kGroup; ++u) cur[u] = load_a(u);
-            for (int cb = 0; cb < nc; cb += kGroup) {
+                    for (int g = 0; g < 4; ++g) {
+                        const int w = av[g];
+                        f32x4 af;
 #pragma unroll
-                for (int u = 0; u < kGroup; ++u) nxt[u] = load_a(cb + kGroup + u);
+                        for (int j = 0; j < 4; ++j) af[j] = (float)((int)(int8_t)(w >> (8 * j)) - a.zp);
+                        f32x4 b[NT];
 #pragma unroll
-                for (int u = 0; u < kGroup; ++u) {
-                    const int c = cb + u;
-                    if (c < nc) {   // (wave-uniform)
-                        if constexpr (I8) {
+                        for (int t = 0; t < NT; ++t) b[t] = *reinterpret_cast<const f32x4*>(cs + (t * 16 + li) * pitch + c * 64 + lk * 16 + g * 4);
 #pragma unroll
-                            for (int g = 0; g < 4; ++g) {
-                                const int w = cur[u][g];
-                                f32x4 af;
+                        for (int j = 0; j < 4; ++j)
 #pragma unroll
-                                for (int j = 0; j < 4; ++j) af[j] = (float)((int)(int8_t)(w >> (8 * j)) - a.zp);
-                                f32x4 b[NT];
-#pragma unroll
-                                for (int t = 0; t < NT; ++t) b[t] = *reinterpret_cast<const f32x4*>(cs + (t * 16 + li) * pitch + c * 64 + lk * 16 + g * 4);
-#pragma unroll
-                                for (int j = 0; j < 4; ++j)
-#pragma unroll
-                                    for (int t = 0; t < NT; ++t) facc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[j], b[t][j], facc[t], 0, 0, 0);
-                            }
-                        } else {
-                            const f32x4 af = __builtin_bit_cast(f32x4, cur[u]);
-                            f32x4 b[NT];
-#pragma unroll
-                            for (int t = 0; t < NT; ++t) b[t] = *reinterpret_cast<const f32x4*>(cs + (t * 16 + li) * pitch + c * 16 + lk * 4);
-#pragma unroll
-                            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                                for (int t = 0; t < NT; ++t) facc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[j], b[t][j], facc[t], 0, 0, 0);
-                        }
+                            for (int t = 0; t < NT; ++t) facc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[j], b[t][j], facc[t], 0, 0, 0);
                     }
-                }
+                } else {
+                    const f32x4 af = __builtin_bit_cast(f32x4, av);
+                    f32x4 b[NT];
 #pragma unroll
-                for (int u = 0; u < kGroup; ++u) cur[u] = nxt[u];
-            }
+                    for (int t = 0; t < NT; ++t) b[t] = *reinterpret_cast<const f32x4*>(cs + (t * 16 + li) * pitch + c * 16 + lk * 4);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+#pragma unroll
+                        for (int t = 0; t < NT; ++t) facc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[j], b[t][j], facc[t], 0, 0, 0);
+                }
+            });
 
             // ---- facc[t][r]: row tile_row + 4 lk + r against centroid c0 + 16 t + li.  Best per row: over t in the lane, then over li.
 #pragma unroll
@@ -203,7 +151,7 @@ __global__ __launch_bounds__(256) void kmeans_assign_kernel(KmeansAssignArgs a) 
                 for (int mk = 1; mk < 16; mk <<= 1) {   // (stays inside the 16 lanes of this lk)
                     const float os = __shfl_xor(bs, mk);
                     const int oi = __shfl_xor(bi, mk);
-                    if (os > bs || (os == bs && oi < bi)) {
+                    if (before(os, oi, bs, bi)) {
                         bs = os;
                         bi = oi;
                     }

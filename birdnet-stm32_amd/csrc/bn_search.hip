@@ -3,9 +3,10 @@
 //   search_inv_norms_kernel  1 / sqrt(sum of squares) per row (0 for a zero row), 16 lanes per row.  An index computes it once per block of
 //                            rows and hands it to every search.
 //   search_score_kernel      grid (row ranges, query passes).  A workgroup holds a tile of 16 * NT queries in LDS and streams its range of
-//                            database rows once: 64 rows per step, 16 per wave, read with 16-byte loads straight into the A operand of the
-//                            matrix cores (v_mfma_f32_16x16x4_f32: exact float32; v_mfma_i32_16x16x64_i8 on the raw bytes, the zero point
-//                            taken out afterwards through row and query sums).  Per query it keeps the best k (score, row) pairs it has
+//                            database rows once, straight into the A operand of the matrix cores (bn_rowstream.h owns the row layout,
+//                            the padding beyond D and the prefetch depth; v_mfma_f32_16x16x4_f32: exact float32; v_mfma_i32_16x16x64_i8
+//                            on the raw bytes, zero beyond D, the zero point taken out afterwards through row and query sums).  Per
+//                            query it keeps the best k (score, row) pairs it has
 //                            seen as a sorted list in LDS; the list's last entry is the running threshold, so after the first few hundred
 //                            rows almost no score passes it and the list is rarely touched.  Each workgroup writes one partial list.
 //   search_merge_kernel      one workgroup per query folds the partial lists into the result.
@@ -16,38 +17,19 @@
 //
 // Rounding: the float32 dot product is an fmaf chain in the matrix cores (the specification leaves the summation order free); the norm's
 // square root and division are the correctly rounded ones (the file is built without fast-math) and the two factors of the cosine are
-// applied by f_mul, one rounding each — defined under a contraction-off pragma as in bn_activity.hip and bn_ingest.hip.
+// applied by f_mul, one rounding each — defined in bn_rowstream.h under a contraction-off pragma that holds for this whole file.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/birdnet_hip.h"
 #include "bn_kernels.h"
-
-#pragma clang fp contract(off)
+#include "bn_rowstream.h"
 
 namespace bn {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef int v4i __attribute__((ext_vector_type(4)));
-
 namespace {
 
-// individually rounded float32 operations (defined under the pragma above, so they never fuse)
-__device__ __forceinline__ float f_add(float a, float b) { return a + b; }
-__device__ __forceinline__ float f_mul(float a, float b) { return a * b; }
-__device__ __forceinline__ float f_div(float a, float b) { return a / b; }
-
-constexpr int kWaves = 4;                          // waves per scoring workgroup, one 16-row tile each per step
-constexpr int kStepRows = BN_SEARCH_STEP_ROWS;     // 64
-constexpr int kGroup = 4;                          // chunks of a row tile whose loads are in flight together
-static_assert(kStepRows == 16 * kWaves, "a step is one MFMA row tile per wave");
-
-__host__ __device__ inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 // LDS pitch of a staged query in bytes: the padded row plus 16 bytes, so the 16 queries of a B fragment start four banks apart
 __host__ __device__ inline int query_pitch(int D, bool i8) { return i8 ? round_up(D, 64) + 16 : (round_up(D, 16) + 4) * 4; }
-
-// (s, i) comes before (ts, ti) in the total order
-__device__ __forceinline__ bool before(float s, int i, float ts, int ti) { return s > ts || (s == ts && i < ti); }
 
 // One wave offers up to 64 candidates (one per lane; a NaN score is "none") to a sorted list of k <= 128 entries in LDS that only this
 // wave touches.  Unused entries are (-inf, -1) and sort last.  Lane l owns positions l and l + 64: an insertion is one read of every
@@ -144,13 +126,10 @@ bool search_geometry(long n, int D, int Q, int k, bool i8, SearchGeom* g) {
     int nt = Q <= 16 ? 1 : Q <= 32 ? 2 : 4;
     while (nt > 1 && search_lds_bytes(D, k, i8, nt) > BN_SEARCH_LDS_BYTES) nt >>= 1;
     if (search_lds_bytes(D, k, i8, nt) > BN_SEARCH_LDS_BYTES) return false;
-    const long steps = (n + kStepRows - 1) / kStepRows;
-    long wgs = (steps + BN_SEARCH_MIN_WG_STEPS - 1) / BN_SEARCH_MIN_WG_STEPS;
-    wgs = wgs < 1 ? 1 : wgs > BN_SEARCH_MAX_WGS ? BN_SEARCH_MAX_WGS : wgs;
-    const long per = steps > 0 ? (steps + wgs - 1) / wgs : 1;
+    const RowSplit split = split_rows(n, BN_SEARCH_MIN_WG_STEPS, BN_SEARCH_MAX_WGS);
     g->nt = nt;
-    g->steps_per_wg = per;
-    g->nwg = steps > 0 ? (int)((steps + per - 1) / per) : 1;
+    g->steps_per_wg = split.steps_per_wg;
+    g->nwg = split.nwg;
     g->lds = search_lds_bytes(D, k, i8, nt);
     return true;
 }
@@ -204,7 +183,7 @@ __global__ __launch_bounds__(256) void search_score_kernel(SearchArgs a) {
         qgrp[t] = (a.q_group && qok[t]) ? a.q_group[q] : 0;
         qcorr[t] = 0;
     }
-    const int nc = I8 ? (pitch - 16) / 64 : (pitch / 4 - 4) / 16;   // chunks of a row: 64 bytes each
+    const int nc = row_chunks<I8>(D);
     if constexpr (I8) {   // dot of centred bytes = sum a b - zp (sum a + sum b) + D zp^2: the query's share of it, once
         const v4i ones = {0x01010101, 0x01010101, 0x01010101, 0x01010101};
 #pragma unroll
@@ -225,31 +204,7 @@ __global__ __launch_bounds__(256) void search_score_kernel(SearchArgs a) {
     for (long st = s0; st < s1; ++st) {
         const long tile_row = st * kStepRows + wave * 16;
         const long lrow = tile_row + li < a.n ? tile_row + li : (long)a.n - 1;   // rows past the end repeat the last one; their scores are dropped below
-        const unsigned char* rp = (const unsigned char*)a.db + (size_t)lrow * row_bytes;
-
-        // chunk c of this lane's row: 16 bytes at element offset 64 c + 16 lk (int8) / 16 c + 4 lk (float32), zero beyond D
-        auto load_a = [&](int c) -> v4i {
-            v4i v = {0, 0, 0, 0};
-            if (c >= nc) return v;
-            if constexpr (I8) {
-                const int d0 = c * 64 + lk * 16;
-                if (aligned && d0 + 16 <= D) return *reinterpret_cast<const v4i*>(rp + d0);
-                unsigned w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-                for (int j = 0; j < 16; ++j)
-                    if (d0 + j < D) w[j >> 2] |= (unsigned)rp[d0 + j] << (8 * (j & 3));
-                v = v4i{(int)w[0], (int)w[1], (int)w[2], (int)w[3]};
-            } else {
-                const int d0 = c * 16 + lk * 4;
-                if (aligned && d0 + 4 <= D) return *reinterpret_cast<const v4i*>(rp + (size_t)d0 * 4);
-                int w[4] = {0, 0, 0, 0};
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (d0 + j < D) w[j] = reinterpret_cast<const int*>(rp)[d0 + j];
-                v = v4i{w[0], w[1], w[2], w[3]};
-            }
-            return v;
-        };
+        const RowView<I8> row{(const unsigned char*)a.db + (size_t)lrow * row_bytes, D, nc, lk, 0, aligned};   // zero beyond D
 
         f32x4 facc[NT];
         v4i iacc[NT], rsum = {0, 0, 0, 0};
@@ -258,39 +213,24 @@ __global__ __launch_bounds__(256) void search_score_kernel(SearchArgs a) {
             facc[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
             iacc[t] = v4i{0, 0, 0, 0};
         }
-        v4i cur[kGroup], nxt[kGroup];
+        row_stream(row, [&](int c, v4i av) __attribute__((always_inline)) {
+            if constexpr (I8) {
+                const v4i ones = {0x01010101, 0x01010101, 0x01010101, 0x01010101};
+                rsum = __builtin_amdgcn_mfma_i32_16x16x64_i8(av, ones, rsum, 0, 0, 0);
 #pragma unroll
-        for (int u = 0; u < kGroup; ++u) cur[u] = load_a(u);
-        for (int c0 = 0; c0 < nc; c0 += kGroup) {
+                for (int t = 0; t < NT; ++t)
+                    iacc[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(av, *reinterpret_cast<const v4i*>(qs + (t * 16 + li) * pitch + c * 64 + lk * 16), iacc[t], 0, 0, 0);
+            } else {
+                const f32x4 af = __builtin_bit_cast(f32x4, av);
+                f32x4 b[NT];
 #pragma unroll
-            for (int u = 0; u < kGroup; ++u) nxt[u] = load_a(c0 + kGroup + u);
+                for (int t = 0; t < NT; ++t) b[t] = *reinterpret_cast<const f32x4*>(qs + (t * 16 + li) * pitch + (c * 16 + lk * 4) * 4);
 #pragma unroll
-            for (int u = 0; u < kGroup; ++u) {
-                const int c = c0 + u;
-                if (c < nc) {   // (wave-uniform)
-                    if constexpr (I8) {
-                        const v4i ones = {0x01010101, 0x01010101, 0x01010101, 0x01010101};
-                        rsum = __builtin_amdgcn_mfma_i32_16x16x64_i8(cur[u], ones, rsum, 0, 0, 0);
+                for (int j = 0; j < 4; ++j)
 #pragma unroll
-                        for (int t = 0; t < NT; ++t)
-                            iacc[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(cur[u], *reinterpret_cast<const v4i*>(qs + (t * 16 + li) * pitch + c * 64 + lk * 16),
-                                                                            iacc[t], 0, 0, 0);
-                    } else {
-                        const f32x4 af = __builtin_bit_cast(f32x4, cur[u]);   // (the whole vector: element access inside the cast read element 0 four times)
-                        f32x4 b[NT];
-#pragma unroll
-                        for (int t = 0; t < NT; ++t) b[t] = *reinterpret_cast<const f32x4*>(qs + (t * 16 + li) * pitch + (c * 16 + lk * 4) * 4);
-#pragma unroll
-                        for (int j = 0; j < 4; ++j)
-#pragma unroll
-                            for (int t = 0; t < NT; ++t)
-                                facc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[j], b[t][j], facc[t], 0, 0, 0);
-                    }
-                }
+                    for (int t = 0; t < NT; ++t) facc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[j], b[t][j], facc[t], 0, 0, 0);
             }
-#pragma unroll
-            for (int u = 0; u < kGroup; ++u) cur[u] = nxt[u];
-        }
+        });
 
         // ---- scores of rows tile_row + 4 lk + r against queries t * 16 + li; which of them pass the query's threshold
         int* fl = flags + (int)(st & 1) * (QP + 4);

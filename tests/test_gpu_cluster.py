@@ -40,21 +40,26 @@ def ctx(torch_mod):
     c.close()
 
 
-def _inv_norms(torch, ctx, rows, zp=0):
+def _inv_norms(torch, ctx, rows, zp=0, off=False):
     from birdnet_stm32 import _hip
 
     d = torch.from_numpy(np.ascontiguousarray(rows)).cuda()
+    if off:   # the same rows in a flat buffer one element longer, from its element 1: +4 bytes for float32, +1 byte for int8
+        flat = torch.empty(rows.size + 1, dtype=d.dtype, device="cuda")
+        flat[1:] = d.view(-1)
+        d = flat[1:].view(rows.shape)
+        assert d.data_ptr() % 16 == rows.itemsize
     out = torch.empty(rows.shape[0], dtype=torch.float32, device="cuda")
     code = _hip.DTYPE_I8 if rows.dtype == np.int8 else _hip.DTYPE_F32
     _hip.check(ctx.lib.bn_search_inv_norms(ctx.handle, d.data_ptr(), code, rows.shape[0], rows.shape[1], zp, out.data_ptr(), None))
     return d, out
 
 
-def _assign(torch, ctx, rows, C, zp=0, prev=None):
-    """bn_kmeans_assign through the C ABI: (label int64, score float32, changed) on the host."""
+def _assign(torch, ctx, rows, C, zp=0, prev=None, off=False):
+    """bn_kmeans_assign through the C ABI: (label int64, score float32, changed) on the host.  ``off``: the rows off the 16-byte boundary."""
     from birdnet_stm32 import _hip
 
-    d_rows, d_inv = _inv_norms(torch, ctx, rows, zp)
+    d_rows, d_inv = _inv_norms(torch, ctx, rows, zp, off)
     d_C, d_cinv = _inv_norms(torch, ctx, np.ascontiguousarray(C, np.float32))
     n, K = rows.shape[0], C.shape[0]
     label = torch.full((n,), -7, dtype=torch.int32, device="cuda")
@@ -100,14 +105,20 @@ def _tile_crossing_k():
 
 
 # (N, D, K): every N of {1, 15, 17, 1000, 4099}, every D of {8, 96, 255, 256} and every K of {1, 2, 15, 16, 17, 100} at least once; a K that
-# crosses a centroid tile at D = 256; K = 1024 at D = 8 (eight tiles)
+# crosses a centroid tile at D = 256; K = 1024 at D = 8 (eight tiles).  A fourth entry "off": the rows start one element behind a 16-byte
+# boundary while D is a multiple of 16, so every chunk of every row takes the loader's slow path (one full 16-row tile, one ragged tile,
+# one chunk group)
 SHAPES = [(1, 256, 1), (15, 96, 2), (17, 255, 15), (1000, 8, 16), (4099, 256, 17), (1000, 96, 100), (4099, 255, 16), (17, 8, 100), (1000, 256, "tile"),
-          (1000, 8, 1024)]
+          (1000, 8, 1024), (17, 256, 2, "off")]
 
 
 def _shape(s):
-    N, D, K = s
-    return N, D, (_tile_crossing_k() if K == "tile" else K)
+    N, D, K = s[:3]
+    return N, D, (_tile_crossing_k() if K == "tile" else K), len(s) > 3
+
+
+def _shape_id(s):
+    return "N{}-D{}-K{}".format(*s) + "-off" * (len(s) > 3)
 
 
 def _lattice(N, D, K, seed, int8_zp=None):
@@ -131,31 +142,31 @@ def _lattice(N, D, K, seed, int8_zp=None):
     return X, C
 
 
-def _check_assignment(torch, ctx, X, C, zp, what):
+def _check_assignment(torch, ctx, X, C, zp, what, off=False):
     from birdnet_stm32.evaluation.cluster import assign_reference
 
     wl, ws = assign_reference(X, C, zero_point=zp)
-    gl, gs, changed = _assign(torch, ctx, X, C, zp)
+    gl, gs, changed = _assign(torch, ctx, X, C, zp, off=off)
     assert np.array_equal(gl, wl), f"{what}: labels differ on {int((gl != wl).sum())} of {len(wl)} rows"
     assert np.array_equal(gs.view(np.uint32), ws.view(np.uint32)), f"{what}: scores differ"
     assert changed == int((wl >= 0).sum()), f"{what}: without previous labels every non-zero row counts"
-    assert _assign(torch, ctx, X, C, zp, prev=gl)[2] == 0, f"{what}: the result as the previous labels"
+    assert _assign(torch, ctx, X, C, zp, prev=gl, off=off)[2] == 0, f"{what}: the result as the previous labels"
     live = np.flatnonzero(wl >= 0)
     if live.size and C.shape[0] > 1:
         prev = gl.copy()
         prev[live[live.size // 2]] = (prev[live[live.size // 2]] + 1) % C.shape[0]
-        l2, s2, ch = _assign(torch, ctx, X, C, zp, prev=prev)
+        l2, s2, ch = _assign(torch, ctx, X, C, zp, prev=prev, off=off)
         assert ch == 1 and np.array_equal(l2, gl) and np.array_equal(s2.view(np.uint32), gs.view(np.uint32)), f"{what}: one label altered by hand"
     return gl, gs
 
 
-@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "N{}-D{}-K{}".format(*s))
+@pytest.mark.parametrize("shape", SHAPES, ids=_shape_id)
 def test_assignment_of_lattice_rows_equals_the_reference_bit_for_bit(torch_mod, ctx, shape):
     from birdnet_stm32.evaluation.search import EmbeddingIndex
 
-    N, D, K = _shape(shape)
+    N, D, K, off = _shape(shape)
     X, C = _lattice(N, D, K, 7 + N + D + K)
-    gl, gs = _check_assignment(torch_mod, ctx, X, C, 0, shape)
+    gl, gs = _check_assignment(torch_mod, ctx, X, C, 0, shape, off)
     if N >= 15:
         assert (gl == -1).sum() == 2
     if N >= 1000 and K >= 15:
@@ -168,11 +179,11 @@ def test_assignment_of_lattice_rows_equals_the_reference_bit_for_bit(torch_mod, 
 
 
 @pytest.mark.parametrize("zp", [-128, 0, 5])
-@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "N{}-D{}-K{}".format(*s))
+@pytest.mark.parametrize("shape", SHAPES, ids=_shape_id)
 def test_assignment_of_int8_rows_equals_the_reference_bit_for_bit(torch_mod, ctx, shape, zp):
-    N, D, K = _shape(shape)
+    N, D, K, off = _shape(shape)
     X, C = _lattice(N, D, K, 1000 + N + D + K + zp, int8_zp=zp)
-    _check_assignment(torch_mod, ctx, X, C, zp, (shape, zp))
+    _check_assignment(torch_mod, ctx, X, C, zp, (shape, zp), off)
 
 
 # ----------------------------------------------------------------------------------------------------------------------- update

@@ -53,21 +53,32 @@ def _multi_wg_rows():
     return n
 
 
-# (N, D, Q, k): every N, D, Q and k of the grid at least once, k > N, and the multi-workgroup N at a small D
+# (N, D, Q, k): every N, D, Q and k of the grid at least once, k > N, and the multi-workgroup N at a small D.  A fifth entry "off": the rows
+# start one element behind a 16-byte boundary while D is a multiple of 16, so every chunk of every row takes the loader's slow path (one
+# full 16-row tile, one ragged tile, one chunk group)
 SHAPES = [(1, 256, 1, 1), (1, 8, 16, 10), (15, 96, 17, 10), (15, 255, 1, 128), (17, 256, 16, 10), (17, 8, 100, 128), (1000, 256, 17, 10),
           (1000, 96, 100, 1), (1000, 255, 16, 128), (4099, 256, 100, 10), (4099, 8, 1, 1), (4099, 255, 17, 128), (4099, 96, 16, 10),
-          ("multi", 8, 17, 10), ("multi", 8, 100, 128)]
+          ("multi", 8, 17, 10), ("multi", 8, 100, 128), (17, 256, 16, 10, "off")]
 
 
 def _shape(s):
-    N, D, Q, k = s
-    return (_multi_wg_rows() if N == "multi" else N), D, Q, k
+    N, D, Q, k = s[:4]
+    return (_multi_wg_rows() if N == "multi" else N), D, Q, k, len(s) > 4
 
 
-def _inv_norms(torch, ctx, rows, zp=0):
+def _shape_id(s):
+    return "N{}-D{}-Q{}-k{}".format(*s) + "-off" * (len(s) > 4)
+
+
+def _inv_norms(torch, ctx, rows, zp=0, off=False):
     from birdnet_stm32 import _hip
 
     d = torch.from_numpy(np.ascontiguousarray(rows)).cuda()
+    if off:   # the same rows in a flat buffer one element longer, from its element 1: +4 bytes for float32, +1 byte for int8
+        flat = torch.empty(rows.size + 1, dtype=d.dtype, device="cuda")
+        flat[1:] = d.view(-1)
+        d = flat[1:].view(rows.shape)
+        assert d.data_ptr() % 16 == rows.itemsize
     out = torch.empty(rows.shape[0], dtype=torch.float32, device="cuda")
     code = _hip.DTYPE_I8 if rows.dtype == np.int8 else _hip.DTYPE_F32
     _hip.check(ctx.lib.bn_search_inv_norms(ctx.handle, d.data_ptr(), code, rows.shape[0], rows.shape[1], zp, out.data_ptr(), None))
@@ -75,11 +86,11 @@ def _inv_norms(torch, ctx, rows, zp=0):
     return d, out
 
 
-def _search(torch, ctx, db, q, k, metric, zp=0, db_group=None, q_group=None):
-    """bn_search_topk through the C ABI: (idx int64, score float32) on the host."""
+def _search(torch, ctx, db, q, k, metric, zp=0, db_group=None, q_group=None, off=False):
+    """bn_search_topk through the C ABI: (idx int64, score float32) on the host.  ``off``: the database rows off the 16-byte boundary."""
     from birdnet_stm32 import _hip
 
-    d_db, d_inv = _inv_norms(torch, ctx, db, zp)
+    d_db, d_inv = _inv_norms(torch, ctx, db, zp, off)
     d_q, d_qinv = _inv_norms(torch, ctx, q, zp)
     Q = q.shape[0]
     idx = torch.full((Q, k), -7, dtype=torch.int32, device="cuda")
@@ -117,27 +128,27 @@ def _assert_equal(got, want, what):
     assert np.array_equal(gs.view(np.uint32), ws.view(np.uint32)), f"{what}: scores differ"
 
 
-@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "N{}-D{}-Q{}-k{}".format(*s))
+@pytest.mark.parametrize("shape", SHAPES, ids=_shape_id)
 def test_lattice_rows_equal_the_reference_bit_for_bit(torch_mod, ctx, shape):
     from birdnet_stm32.evaluation.search import search_reference
 
-    N, D, Q, k = _shape(shape)
+    N, D, Q, k, off = _shape(shape)
     db, q = _lattice(N, D, Q, 11 + N + D)
     ties = 0
     for metric in ("cosine", "dot"):
         want = search_reference(db, q, k, metric)
-        _assert_equal(_search(torch_mod, ctx, db, q, k, metric), want, f"{shape} {metric}")
+        _assert_equal(_search(torch_mod, ctx, db, q, k, metric, off=off), want, f"{shape} {metric}")
         ties += int((want[1][:, 1:] == want[1][:, :-1]).sum())
     if N >= 1000 and k >= 10:
         assert ties > 0, "the duplicated rows should tie inside the top k"
 
 
 @pytest.mark.parametrize("zp", [-128, 0, 5])
-@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "N{}-D{}-Q{}-k{}".format(*s))
+@pytest.mark.parametrize("shape", SHAPES, ids=_shape_id)
 def test_int8_rows_equal_the_reference_bit_for_bit(torch_mod, ctx, shape, zp):
     from birdnet_stm32.evaluation.search import search_reference
 
-    N, D, Q, k = _shape(shape)
+    N, D, Q, k, off = _shape(shape)
     rng = np.random.default_rng(1000 + N + D + zp)   # (zp may be -128: the seed must not be negative)
     db = rng.integers(-128, 128, (N, D)).astype(np.int8)
     q = rng.integers(-128, 128, (Q, D)).astype(np.int8)
@@ -146,7 +157,7 @@ def test_int8_rows_equal_the_reference_bit_for_bit(torch_mod, ctx, shape, zp):
         db[N // 2] = zp   # a zero vector
     q[: min(Q, N, 4)] = db[: min(Q, N, 4)]
     for metric in ("cosine", "dot"):
-        _assert_equal(_search(torch_mod, ctx, db, q, k, metric, zp=zp), search_reference(db, q, k, metric, zero_point=zp), f"{shape} zp={zp} {metric}")
+        _assert_equal(_search(torch_mod, ctx, db, q, k, metric, zp=zp, off=off), search_reference(db, q, k, metric, zero_point=zp), f"{shape} zp={zp} {metric}")
 
 
 def _clusters(n, D, C, seed):
