@@ -7,25 +7,18 @@
 //
 // Both repeat a float32 operation order that birdnet_stm32/audio/activity.py spells out (short_time_energy, activity_stats), so their
 // results are compared with that module for equality.  Every addition and multiplication whose rounding is part of that order is written
-// with the f_add / f_mul / f_sub / f_div helpers below, defined under a contraction-off pragma as in bn_ingest.hip: a fused multiply-add
-// rounds once where numpy rounds twice.  (The __fmul_rn / __fadd_rn intrinsics do not prevent it: they are inline functions of a header
-// compiled with contraction allowed, and after inlining the backend fuses their multiply and add; median + k * mad came out one ulp low.)
+// with the f_add / f_mul / f_sub / f_div helpers of bn_device.h (a fused multiply-add rounds once where numpy rounds twice).
 // Percentiles, regions, ratios and every ordering decision stay on the host.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bn_device.h"
 #include "bn_kernels.h"
 
 #pragma clang fp contract(off)
 
 namespace bn {
 namespace {
-
-// individually rounded float32 operations (defined under the pragma above, so they never fuse)
-__device__ __forceinline__ float f_add(float a, float b) { return a + b; }
-__device__ __forceinline__ float f_sub(float a, float b) { return a - b; }
-__device__ __forceinline__ float f_mul(float a, float b) { return a * b; }
-__device__ __forceinline__ float f_div(float a, float b) { return a / b; }
 
 // ------------------------------------------------------------------------------------------------------------ short-time energy
 // numpy sums a contiguous float32 run of 1024 as a binary tree over eight blocks of 128; a block is eight strided accumulators (sixteen

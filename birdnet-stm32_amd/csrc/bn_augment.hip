@@ -4,8 +4,8 @@
 //                    row (reference: audio/augmentation.py:10-71 `apply_mixup` after data/generator.py:169-170 masked every sample).
 //
 // birdnet_stm32/training/augment.py `augment_reference` is the specification and the results are compared with it for equality, so every
-// product and sum whose rounding is part of it goes through the f_add / f_mul helpers under a contraction-off pragma, as in
-// bn_activity.hip (a fused multiply-add rounds once where numpy rounds twice).  A row with one source is copied, not multiplied: -0.0 and
+// product and sum whose rounding is part of it goes through the f_add / f_mul helpers of bn_device.h
+// (a fused multiply-add rounds once where numpy rounds twice).  A row with one source is copied, not multiplied: -0.0 and
 // NaN payloads survive.  Gains go down to 1e-27, products are routinely subnormal; the file is compiled in hipcc's default float32 mode,
 // which keeps them.
 //
@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include "../../include/birdnet_hip.h"
+#include "bn_device.h"
 #include "bn_kernels.h"
 
 #pragma clang fp contract(off)
@@ -25,13 +26,9 @@
 namespace bn {
 namespace {
 
-__device__ __forceinline__ float f_add(float a, float b) { return a + b; }
-__device__ __forceinline__ float f_mul(float a, float b) { return a * b; }
-
 constexpr int kAugThreads = 256, kAugUnroll = 4;
 constexpr int kAugChunk = kAugThreads * kAugUnroll * 4;   // elements of a row per workgroup
 
-typedef float v4f __attribute__((ext_vector_type(4)));
 struct __attribute__((packed, aligned(4))) F4U { float v[4]; };   // four floats at any 4-byte boundary
 
 struct AugMasks {            // the (start, width) tables of a row's sources; width >= 0
@@ -106,8 +103,8 @@ __device__ __forceinline__ void aug_row(const float* const* xs, const float* g, 
             for (int s = 0; s < NS; ++s) v[s] = (masked[u][s] >> e & 1u) ? 0.0f : val[u][s].v[e];
             r[e] = mix<NS>(v, g);
         }
-        v4f q = {r[0], r[1], r[2], r[3]};
-        *reinterpret_cast<v4f*>(o + head + 4 * grp) = q;
+        f32x4 q = {r[0], r[1], r[2], r[3]};
+        *reinterpret_cast<f32x4*>(o + head + 4 * grp) = q;
         asm volatile("s_nop 1" : "+v"(q));   // the data registers of a 16-byte store are not rewritten right behind it (bn_f32_strip.hip: store16)
     }
 }

@@ -9,16 +9,11 @@
 //   head             birdnet_stm32/models/dscnn.py:248-261
 // Layout: NHWC per chunk, C innermost.  TensorFlow SAME padding (pad_top/pad_left come from the
 // packer; the odd cell is after).
+#include "bn_device.h"
 #include "bn_kernels.h"
 
 namespace bn {
 namespace {
-
-__device__ __forceinline__ float apply_act(float v, int act) {
-    if (act == 1) return fmaxf(v, 0.0f);
-    if (act == 2) return fminf(fmaxf(v, 0.0f), 6.0f);
-    return v;
-}
 
 // channel-wise magnitude scaling (reference: magnitude.py:166-192); magp is [NP][M]
 __device__ __forceinline__ float mag_scale(float y, int m, int M, const float* __restrict__ magp, int mag) {
@@ -219,10 +214,10 @@ __global__ void f32_stem_kernel(const float* __restrict__ x, float* __restrict__
             acc.w = fmaf(v, k.w, acc.w);
         }
     }
-    acc.x = apply_act(acc.x, act);
-    acc.y = apply_act(acc.y, act);
-    acc.z = apply_act(acc.z, act);
-    acc.w = apply_act(acc.w, act);
+    acc.x = act_f(acc.x, act);
+    acc.y = act_f(acc.y, act);
+    acc.z = act_f(acc.z, act);
+    acc.w = act_f(acc.w, act);
     *reinterpret_cast<float4*>(y + ((b * OH + oh) * OW + ow) * Cout + 4 * cg) = acc;
 }
 
@@ -257,10 +252,10 @@ __global__ void f32_dw_kernel(const float* __restrict__ x, float* __restrict__ y
             acc.w = fmaf(v.w, k.w, acc.w);
         }
     }
-    acc.x = apply_act(acc.x, act);
-    acc.y = apply_act(acc.y, act);
-    acc.z = apply_act(acc.z, act);
-    acc.w = apply_act(acc.w, act);
+    acc.x = act_f(acc.x, act);
+    acc.y = act_f(acc.y, act);
+    acc.z = act_f(acc.z, act);
+    acc.w = act_f(acc.w, act);
     *reinterpret_cast<float4*>(y + ((b * OH + oh) * OW + ow) * C + 4 * cg) = acc;
 }
 
@@ -303,10 +298,10 @@ __global__ void f32_pw_kernel(const float* __restrict__ x, const float* __restri
         acc.z += rr.z;
         acc.w += rr.w;
     }
-    acc.x = apply_act(acc.x, act);
-    acc.y = apply_act(acc.y, act);
-    acc.z = apply_act(acc.z, act);
-    acc.w = apply_act(acc.w, act);
+    acc.x = act_f(acc.x, act);
+    acc.y = act_f(acc.y, act);
+    acc.z = act_f(acc.z, act);
+    acc.w = act_f(acc.w, act);
     *reinterpret_cast<float4*>(y + row * Cout + 4 * ng) = acc;
 }
 

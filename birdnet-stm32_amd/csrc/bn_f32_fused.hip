@@ -16,18 +16,11 @@
 //           the packer stored in fragment order, so each wave-instruction reads 1 KiB contiguous from L2.
 // The contraction index inside each group of 16 channels is permuted identically for A and B
 // (k = 16 j + 4 (lane >> 4) + e for the e-th MFMA), which only re-orders the float32 summation.
+#include "bn_device.h"
 #include "bn_kernels.h"
 
 namespace bn {
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float act_f(float v, int act) {
-    if (act == 1) return fmaxf(v, 0.0f);
-    if (act == 2) return fminf(fmaxf(v, 0.0f), 6.0f);
-    return v;
-}
 
 constexpr int kKC = 128;  // contraction channels staged in LDS at a time (256: one barrier pair less per 256 channels, but 64 KB tiles — measured slower:
                           // configs[4] 7.04 -> 6.86 ms, shipped float32 net 0.945 -> 0.923 ms per 1024 chunks; the epilogue in two column passes
@@ -355,12 +348,6 @@ __global__ __launch_bounds__(256) void f32_dwpw_kernel(DwPwArgs a) {
 // outputs, its 16-row A fragments, all Cout columns, its epilogue rows.  Nothing is exchanged between waves, so there is
 // no workgroup barrier: the waves drift apart and one wave's HBM round trip overlaps the others' arithmetic (with
 // barriers every wave waited for the slowest four times per tile).  Each wave reads the whole (small) weight matrix.
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 template <int CTA>
 __global__ __launch_bounds__(256) void f32_dwpw_wave_kernel(DwPwArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds_raw[];

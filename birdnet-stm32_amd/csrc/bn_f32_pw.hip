@@ -28,17 +28,11 @@
 // activation): results are bit-identical to it (tests/test_gpu_sweeps.py: test_f32_pw_ws_kernel_matches_the_tile_kernel).
 #include <type_traits>
 
+#include "bn_device.h"
 #include "bn_kernels.h"
 
 namespace bn {
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// The workgroup's barrier orders LDS traffic only (tiles, accumulators): global loads and stores stay in flight across it.  __syncthreads()
-// is a workgroup-scope fence as well: for the waves that store it put `s_waitcnt vmcnt(0)` in front of every barrier — the epilogue waves
-// arrived late by a store round trip at the first barrier behind each tile and the matrix waves waited for them (5.5 us per tile).
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 constexpr int kKC = 128;            // contraction channels per slice
 constexpr int kS4 = kKC / 4 + 1;    // row stride of an activation buffer in float4 (one of padding: conflict-free fragment reads)

@@ -23,24 +23,24 @@
 // taps); no blob change.
 #include <stdlib.h>
 
+#include "bn_device.h"
 #include "bn_kernels.h"
 
 namespace bn {
 namespace {
 
-typedef float v4f __attribute__((ext_vector_type(4)));
 
 // every activation code (none / ReLU / ReLU6) is one v_med3_f32 with run-time bounds: no per-code copies of the row loop
 struct ActBounds { float lo, hi; };
 __device__ __forceinline__ ActBounds act_bounds(int act) {
     return {act == 0 ? -__builtin_inff() : 0.0f, act == 2 ? 6.0f : __builtin_inff()};
 }
-__device__ __forceinline__ v4f act4(v4f v, ActBounds b) {
-    return (v4f){__builtin_amdgcn_fmed3f(v.x, b.lo, b.hi), __builtin_amdgcn_fmed3f(v.y, b.lo, b.hi), __builtin_amdgcn_fmed3f(v.z, b.lo, b.hi),
+__device__ __forceinline__ f32x4 act4(f32x4 v, ActBounds b) {
+    return (f32x4){__builtin_amdgcn_fmed3f(v.x, b.lo, b.hi), __builtin_amdgcn_fmed3f(v.y, b.lo, b.hi), __builtin_amdgcn_fmed3f(v.z, b.lo, b.hi),
                  __builtin_amdgcn_fmed3f(v.w, b.lo, b.hi)};
 }
 
-__device__ __forceinline__ void mfma_acc(v4f& acc, float a, float b) { acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0); }
+__device__ __forceinline__ void mfma_acc(f32x4& acc, float a, float b) { acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0); }
 
 // A 16-byte store must not see its data registers rewritten right behind it.  Measured on MI355X: `buffer_store_dwordx4 v[4:7], ..,
 // s6 offen` followed at once by `v_med3_f32 v4, ..` (the next tile's result re-using the registers) stored the NEW v4 for lanes
@@ -48,20 +48,20 @@ __device__ __forceinline__ void mfma_acc(v4f& acc, float a, float b) { acc = __b
 // was.  The compiler knows this hazard only for stores without an SGPR offset.  Keeping the data an in/out operand of a
 // two-wait-state no-op placed after the store makes the allocator pick other registers for what follows;
 // tools/store_hazard_check.py scans the generated assembly of every kernel file and the Makefile fails the build on a hit.
-__device__ __forceinline__ void store16(__amdgpu_buffer_rsrc_t rs, v4f r, int voff, int soff) {
+__device__ __forceinline__ void store16(__amdgpu_buffer_rsrc_t rs, f32x4 r, int voff, int soff) {
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned, r), rs, voff, soff, 0);
     asm volatile("s_nop 1" : "+v"(r));
 }
 
-struct Row4 { v4f t[3]; };  // the three taps (columns j = 0..2) of one input row, one channel quad
+struct Row4 { f32x4 t[3]; };  // the three taps (columns j = 0..2) of one input row, one channel quad
 
 template <int NW, int COUT, int S, bool RES>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(((NW == 2 && COUT == 32) || NW == 8) ? 4 : 3))) void f32_strip_kernel(DwPwArgs a) {
     constexpr int CIN = 16 * NW, CWO = COUT / NW, NT = CWO / 16;
     static_assert(NT == 1 || NT == 2, "16 or 32 output channels per wave");
     static_assert(!RES || (CIN == COUT && S == 1), "the residual is the block input");
-    __shared__ v4f xchg[2][NW][64];
-    __shared__ v4f dw_lds[9][CIN / 4];  // depthwise taps: re-read every row (9 x 16 B per lane) instead of pinning 36 registers
+    __shared__ f32x4 xchg[2][NW][64];
+    __shared__ f32x4 dw_lds[9][CIN / 4];  // depthwise taps: re-read every row (9 x 16 B per lane) instead of pinning 36 registers
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -80,20 +80,20 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(((NW ==
     const int c0 = 16 * w + 4 * kq;  // first input channel of the lane
     const ActBounds dw_bounds = act_bounds(a.dw_act), pw_bounds = act_bounds(a.pw_act);
 
-    for (int i = tid; i < 9 * (CIN / 4); i += 64 * NW) (&dw_lds[0][0])[i] = reinterpret_cast<const v4f*>(a.dw_w)[i];
+    for (int i = tid; i < 9 * (CIN / 4); i += 64 * NW) (&dw_lds[0][0])[i] = reinterpret_cast<const f32x4*>(a.dw_w)[i];
     __syncthreads();
-    const v4f* dw = &dw_lds[0][c0 >> 2];  // tap t of this lane's quad at dw[t * (CIN / 4)]
-    const v4f dwb = *reinterpret_cast<const v4f*>(a.dw_b + c0);
+    const f32x4* dw = &dw_lds[0][c0 >> 2];  // tap t of this lane's quad at dw[t * (CIN / 4)]
+    const f32x4 dwb = *reinterpret_cast<const f32x4*>(a.dw_b + c0);
     // A operands: pa[t][ks] = W[16 ks + 4 kq + g][ch], g = 0..3, ch = CWO w + 4 NT (m >> 2) + 4 t + (m & 3) for lane (m, kq);
     // the packer's fragment order [K/16][N/16][64][4] holds W[16 j + 4 (l >> 4) + e][16 ct + (l & 15)] at [j][ct][l][e].
-    v4f pa[NT][NW], pb[NT];
+    f32x4 pa[NT][NW], pb[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
         const int ch = CWO * w + 4 * NT * (n >> 2) + 4 * t + (n & 3);
 #pragma unroll
         for (int ks = 0; ks < NW; ++ks)
-            pa[t][ks] = reinterpret_cast<const v4f*>(a.pw_w)[(ks * (COUT / 16) + (ch >> 4)) * 64 + kq * 16 + (ch & 15)];
-        pb[t] = *reinterpret_cast<const v4f*>(a.pw_b + CWO * w + 4 * NT * kq + 4 * t);
+            pa[t][ks] = reinterpret_cast<const f32x4*>(a.pw_w)[(ks * (COUT / 16) + (ch >> 4)) * 64 + kq * 16 + (ch & 15)];
+        pb[t] = *reinterpret_cast<const f32x4*>(a.pw_b + CWO * w + 4 * NT * kq + 4 * t);
     }
 
     const int in_chunk_bytes = a.H * a.W * CIN * 4;
@@ -117,7 +117,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(((NW ==
         if (row_ok(rr)) {
             const int soff = (ir0 + rr) * row_bytes;
 #pragma unroll
-            for (int j = 0; j < 3; ++j) raw[slot].t[j] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rs_in, voff_in[j], soff, 0));
+            for (int j = 0; j < 3; ++j) raw[slot].t[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_in, voff_in[j], soff, 0));
         }
     };
     auto consume = [&](int slot, int rr, int ti) {
@@ -125,12 +125,12 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(((NW ==
             T[ti] = raw[slot];
         } else {
 #pragma unroll
-            for (int j = 0; j < 3; ++j) T[ti].t[j] = (v4f){0.0f, 0.0f, 0.0f, 0.0f};
+            for (int j = 0; j < 3; ++j) T[ti].t[j] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
         }
     };
     auto emit = [&](int i0, int i1, int i2, int oh, int step) {
         asm volatile("" ::: "memory");  // keeps the tap reads inside the row loop
-        v4f acc = dwb;
+        f32x4 acc = dwb;
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
             acc = __builtin_elementwise_fma(T[i0].t[j], dw[(0 + j) * (CIN / 4)], acc);
@@ -138,26 +138,26 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(((NW ==
             acc = __builtin_elementwise_fma(T[i2].t[j], dw[(6 + j) * (CIN / 4)], acc);
         }
         acc = act4(acc, dw_bounds);
-        v4f (*buf)[64] = xchg[step & 1];
+        f32x4 (*buf)[64] = xchg[step & 1];
         buf[w][lane] = acc;
         // LDS only: the prefetched global loads stay in flight across the barrier
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        v4f o[NT];
+        lds_barrier();
+        f32x4 o[NT];
         if constexpr (NW >= 8 && NT == 1) {
             // eight waves per strip: the other waves' fragments two at a time (the eight of them at once are 32 registers: with them the kernel
             // needs ~145 and ONE workgroup of eight waves fits a CU; at <= 128 two fit, and this kernel is bound by the per-row latency chain)
             o[0] = pb[0];
-            v4f fc = buf[0][lane], fn = buf[1][lane];
+            f32x4 fc = buf[0][lane], fn = buf[1][lane];
 #pragma unroll
             for (int ks = 0; ks < NW; ++ks) {
-                const v4f fu = fc;
+                const f32x4 fu = fc;
                 fc = fn;
                 if (ks + 2 < NW) fn = buf[ks + 2][lane];
 #pragma unroll
                 for (int g = 0; g < 4; ++g) mfma_acc(o[0], pa[0][ks][g], fu[g]);
             }
         } else {
-        v4f f[NW];
+        f32x4 f[NW];
 #pragma unroll
         for (int ks = 0; ks < NW; ++ks) f[ks] = buf[ks][lane];
 #pragma unroll
@@ -171,7 +171,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(((NW ==
         }
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
-            v4f r = o[t];
+            f32x4 r = o[t];
             if constexpr (RES) r += T[i1].t[1];  // centre tap = the block input at this position, channels 16 w + 4 q + 0..3
             r = act4(r, pw_bounds);
             store16(rs_out, r, voff_out + 16 * t, oh * a.OW * COUT * 4);
@@ -218,7 +218,7 @@ template <bool STAGED>
 __global__ __launch_bounds__(STAGED ? 1024 : 256) __attribute__((amdgpu_waves_per_eu(STAGED ? 4 : 3))) void f32_front_strip_kernel(F32FrontStripArgs a) {  // (the per-wave A/B form spilled 4 registers at four waves)
     extern __shared__ __attribute__((aligned(16))) float fe_tile[];  // STAGED: [2 TH + 4][W0 + 8], rows sr0 - 1 .., zero outside the map
     __shared__ float rowc[64][12];          // per input row: wsum, then the ten magnitude-scaling rows (finalising mode)
-    __shared__ v4f dw_lds[9][4];            // depthwise taps [tap][quad]
+    __shared__ f32x4 dw_lds[9][4];            // depthwise taps [tap][quad]
     const int tid = threadIdx.x;
     const int nthreads = blockDim.x;
     const bool fin = a.minmax != nullptr;
@@ -227,7 +227,7 @@ __global__ __launch_bounds__(STAGED ? 1024 : 256) __attribute__((amdgpu_waves_pe
             const int rr = i / 12, c = i - rr * 12;
             rowc[rr][c] = c == 0 ? a.wsum[rr] : (c <= 10 ? a.magp[(c - 1) * a.H0 + rr] : 0.0f);
         }
-    if (tid < 36) (&dw_lds[0][0])[tid] = reinterpret_cast<const v4f*>(a.dw_w)[tid];
+    if (tid < 36) (&dw_lds[0][0])[tid] = reinterpret_cast<const f32x4*>(a.dw_w)[tid];
     __syncthreads();
 
     const int lane = tid & 63;
@@ -250,14 +250,14 @@ __global__ __launch_bounds__(STAGED ? 1024 : 256) __attribute__((amdgpu_waves_pe
     float sa[3];
 #pragma unroll
     for (int j = 0; j < 3; ++j) sa[j] = kq < 3 ? a.stem_w[(kq * 3 + j) * 16 + n] : 0.0f;
-    const v4f stb = *reinterpret_cast<const v4f*>(a.stem_b + 4 * kq);
-    const v4f dwb = *reinterpret_cast<const v4f*>(a.dw_b + 4 * kq);
-    v4f pa[2], pb[2];
+    const f32x4 stb = *reinterpret_cast<const f32x4*>(a.stem_b + 4 * kq);
+    const f32x4 dwb = *reinterpret_cast<const f32x4*>(a.dw_b + 4 * kq);
+    f32x4 pa[2], pb[2];
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
         const int ch = 8 * (n >> 2) + 4 * t + (n & 3);
-        pa[t] = reinterpret_cast<const v4f*>(a.pw_w)[(ch >> 4) * 64 + kq * 16 + (ch & 15)];
-        pb[t] = *reinterpret_cast<const v4f*>(a.pw_b + 8 * kq + 4 * t);
+        pa[t] = reinterpret_cast<const f32x4*>(a.pw_w)[(ch >> 4) * 64 + kq * 16 + (ch & 15)];
+        pb[t] = *reinterpret_cast<const f32x4*>(a.pw_b + 8 * kq + 4 * t);
     }
     float mn = 0.0f, inv_rng = 1.0f;
     if (fin) {
@@ -281,12 +281,12 @@ __global__ __launch_bounds__(STAGED ? 1024 : 256) __attribute__((amdgpu_waves_pe
         for (int i = tid; i < nr * (quads + 2); i += nthreads) {
             const int row = i / (quads + 2), c = i - row * (quads + 2);
             const int fr = sr0 - 1 + row;
-            v4f v = {0.0f, 0.0f, 0.0f, 0.0f};
+            f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
             if (c < quads && fr >= 0 && fr < a.H0) {
-                v = *reinterpret_cast<const v4f*>(a.fe + ((size_t)chunk * a.H0 + fr) * a.W0 + 4 * c);
+                v = *reinterpret_cast<const f32x4*>(a.fe + ((size_t)chunk * a.H0 + fr) * a.W0 + 4 * c);
                 if (fin) {
-                    const v4f c0 = *reinterpret_cast<const v4f*>(&rowc[fr][0]), c1 = *reinterpret_cast<const v4f*>(&rowc[fr][4]),
-                              c2 = *reinterpret_cast<const v4f*>(&rowc[fr][8]);
+                    const f32x4 c0 = *reinterpret_cast<const f32x4*>(&rowc[fr][0]), c1 = *reinterpret_cast<const f32x4*>(&rowc[fr][4]),
+                              c2 = *reinterpret_cast<const f32x4*>(&rowc[fr][8]);
                     const float off = mn * c0.x;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
@@ -307,19 +307,19 @@ __global__ __launch_bounds__(STAGED ? 1024 : 256) __attribute__((amdgpu_waves_pe
                     }
                 }
             }
-            *reinterpret_cast<v4f*>(fe_tile + row * tile_w + 4 * c) = v;
+            *reinterpret_cast<f32x4*>(fe_tile + row * tile_w + 4 * c) = v;
         }
         __syncthreads();
     }
-    v4f raw[2][2];
+    f32x4 raw[2][2];
     Row4 T[3];
     auto fe_row = [&](int srel) { return sr0 + srel - 1 + kq; };
     auto issue = [&](int slot, int srel) {
         if (!STAGED && srel < rows_needed) {
             const int fr = fe_row(srel);
             const int base = (fr >= 0 && fr < a.H0) ? (fr * a.W0 + 4 * ow) * 4 : 0x7fff0000;  // padding rows read as 0
-            raw[slot][0] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rs_fe, base, 0, 0));
-            raw[slot][1] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rs_fe, base + 16, 0, 0));  // beyond the row end only for ow = OW - 1
+            raw[slot][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_fe, base, 0, 0));
+            raw[slot][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_fe, base + 16, 0, 0));  // beyond the row end only for ow = OW - 1
         }
     };
     auto stem_row = [&](int slot, int srel, int ti) {
@@ -330,7 +330,7 @@ __global__ __launch_bounds__(STAGED ? 1024 : 256) __attribute__((amdgpu_waves_pe
             float x[7];
             if constexpr (STAGED) {
                 const float* trow = fe_tile + (srel + kq) * tile_w + 4 * ow;  // input row sr - 1 + kq, already finalised / zero-padded
-                const v4f lo = *reinterpret_cast<const v4f*>(trow), hi = *reinterpret_cast<const v4f*>(trow + 4);
+                const f32x4 lo = *reinterpret_cast<const f32x4*>(trow), hi = *reinterpret_cast<const f32x4*>(trow + 4);
                 x[0] = lo.x; x[1] = lo.y; x[2] = lo.z; x[3] = lo.w; x[4] = hi.x; x[5] = hi.y; x[6] = hi.z;
             } else {
                 x[0] = raw[slot][0].x; x[1] = raw[slot][0].y; x[2] = raw[slot][0].z; x[3] = raw[slot][0].w;
@@ -338,8 +338,8 @@ __global__ __launch_bounds__(STAGED ? 1024 : 256) __attribute__((amdgpu_waves_pe
             }
             if (!STAGED && fin) {
                 const int rr = ok ? fr : 0;
-                const v4f c0 = *reinterpret_cast<const v4f*>(&rowc[rr][0]), c1 = *reinterpret_cast<const v4f*>(&rowc[rr][4]),
-                          c2 = *reinterpret_cast<const v4f*>(&rowc[rr][8]);
+                const f32x4 c0 = *reinterpret_cast<const f32x4*>(&rowc[rr][0]), c1 = *reinterpret_cast<const f32x4*>(&rowc[rr][4]),
+                          c2 = *reinterpret_cast<const f32x4*>(&rowc[rr][8]);
                 const float off = mn * c0.x;
 #pragma unroll
                 for (int e = 0; e < 7; ++e) {
@@ -360,7 +360,7 @@ __global__ __launch_bounds__(STAGED ? 1024 : 256) __attribute__((amdgpu_waves_pe
                 }
             }
             if (!STAGED && !has_hi) x[4] = x[5] = x[6] = 0.0f;  // columns beyond the map (the second load wrapped into the next row)
-            v4f st[3];
+            f32x4 st[3];
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 st[c] = stb;
@@ -369,16 +369,16 @@ __global__ __launch_bounds__(STAGED ? 1024 : 256) __attribute__((amdgpu_waves_pe
             }
 #pragma unroll
             for (int c = 0; c < 3; ++c) T[ti].t[c] = act4(st[c], st_bounds);
-            if (right_st) T[ti].t[2] = (v4f){0.0f, 0.0f, 0.0f, 0.0f};
+            if (right_st) T[ti].t[2] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
         } else {
 #pragma unroll
-            for (int c = 0; c < 3; ++c) T[ti].t[c] = (v4f){0.0f, 0.0f, 0.0f, 0.0f};
+            for (int c = 0; c < 3; ++c) T[ti].t[c] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
         }
     };
     auto emit = [&](int i0, int i1, int i2, int oh) {
         asm volatile("" ::: "memory");
-        const v4f* dw = &dw_lds[0][kq];
-        v4f d = dwb;
+        const f32x4* dw = &dw_lds[0][kq];
+        f32x4 d = dwb;
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
             d = __builtin_elementwise_fma(T[i0].t[j], dw[(0 + j) * 4], d);
@@ -386,7 +386,7 @@ __global__ __launch_bounds__(STAGED ? 1024 : 256) __attribute__((amdgpu_waves_pe
             d = __builtin_elementwise_fma(T[i2].t[j], dw[(6 + j) * 4], d);
         }
         d = act4(d, dw_bounds);
-        v4f o[2];
+        f32x4 o[2];
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             o[t] = pb[t];
@@ -441,15 +441,15 @@ __global__ __launch_bounds__(768) void f32_front2_kernel(F32Front2Args A) {
     const F32FrontStripArgs& a = A.f;
     extern __shared__ __attribute__((aligned(16))) float lds2[];
     __shared__ float rowc[64][12];
-    __shared__ v4f dw_lds[9][4];
-    __shared__ v4f dw2_lds[9][8];
+    __shared__ f32x4 dw_lds[9][4];
+    __shared__ f32x4 dw2_lds[9][8];
     const int tid = threadIdx.x, nthreads = blockDim.x;
     const int strips_x = a.OW >> 4;
     const int tile_w = a.W0 + 8, nr = a.H0 + 4;
     constexpr int RP = 36;                              // ring pitch per column (floats): 32 channels + 4
     float* fe_tile = lds2;                              // [H0 + 4][W0 + 8], rows -1 .., zero outside the map
     float* ring = fe_tile + nr * tile_w;                // [2][OW + 2][RP]
-    v4f* xchg = reinterpret_cast<v4f*>(ring + 2 * (a.OW + 2) * RP);  // [strip][2][2][64]
+    f32x4* xchg = reinterpret_cast<f32x4*>(ring + 2 * (a.OW + 2) * RP);  // [strip][2][2][64]
     const bool fin = a.minmax != nullptr;
     const int chunk = xcd_tile(blockIdx.x, gridDim.x);
     if (fin)
@@ -457,8 +457,8 @@ __global__ __launch_bounds__(768) void f32_front2_kernel(F32Front2Args A) {
             const int rr = i / 12, c = i - rr * 12;
             rowc[rr][c] = c == 0 ? a.wsum[rr] : (c <= 10 ? a.magp[(c - 1) * a.H0 + rr] : 0.0f);
         }
-    if (tid < 36) (&dw_lds[0][0])[tid] = reinterpret_cast<const v4f*>(a.dw_w)[tid];
-    if (tid >= 64 && tid < 64 + 72) (&dw2_lds[0][0])[tid - 64] = reinterpret_cast<const v4f*>(A.dw_w)[tid - 64];
+    if (tid < 36) (&dw_lds[0][0])[tid] = reinterpret_cast<const f32x4*>(a.dw_w)[tid];
+    if (tid >= 64 && tid < 64 + 72) (&dw2_lds[0][0])[tid - 64] = reinterpret_cast<const f32x4*>(A.dw_w)[tid - 64];
     for (int i = tid; i < 4 * RP; i += nthreads) {      // the ring's border columns stay zero: SAME padding of the second block
         const int rrow = i / (2 * RP), rest = i - rrow * 2 * RP;
         ring[(rrow * (a.OW + 2) + (rest < RP ? 0 : a.OW + 1)) * RP + (rest % RP)] = 0.0f;
@@ -474,24 +474,24 @@ __global__ __launch_bounds__(768) void f32_front2_kernel(F32Front2Args A) {
         const int quads = a.W0 >> 2, total = nr * (quads + 2);
         constexpr int kInFlight = 6;
         for (int i0 = tid; i0 < total; i0 += kInFlight * nthreads) {
-            v4f vin[kInFlight];
+            f32x4 vin[kInFlight];
 #pragma unroll
             for (int u = 0; u < kInFlight; ++u) {
                 const int i = i0 + u * nthreads;
                 const int row = i / (quads + 2), c = i - row * (quads + 2), fr = row - 1;
-                vin[u] = (v4f){0.0f, 0.0f, 0.0f, 0.0f};
+                vin[u] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
                 if (i < total && c < quads && fr >= 0 && fr < a.H0)
-                    vin[u] = *reinterpret_cast<const v4f*>(a.fe + ((size_t)chunk * a.H0 + fr) * a.W0 + 4 * c);
+                    vin[u] = *reinterpret_cast<const f32x4*>(a.fe + ((size_t)chunk * a.H0 + fr) * a.W0 + 4 * c);
             }
 #pragma unroll
             for (int u = 0; u < kInFlight; ++u) {
                 const int i = i0 + u * nthreads;
                 if (i >= total) break;
                 const int row = i / (quads + 2), c = i - row * (quads + 2), fr = row - 1;
-                v4f v = vin[u];
+                f32x4 v = vin[u];
                 if (fin && c < quads && fr >= 0 && fr < a.H0) {
-                    const v4f c0 = *reinterpret_cast<const v4f*>(&rowc[fr][0]), c1 = *reinterpret_cast<const v4f*>(&rowc[fr][4]),
-                              c2 = *reinterpret_cast<const v4f*>(&rowc[fr][8]);
+                    const f32x4 c0 = *reinterpret_cast<const f32x4*>(&rowc[fr][0]), c1 = *reinterpret_cast<const f32x4*>(&rowc[fr][4]),
+                              c2 = *reinterpret_cast<const f32x4*>(&rowc[fr][8]);
                     const float off = mn * c0.x;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
@@ -511,7 +511,7 @@ __global__ __launch_bounds__(768) void f32_front2_kernel(F32Front2Args A) {
                         v[e] = r;
                     }
                 }
-                *reinterpret_cast<v4f*>(fe_tile + row * tile_w + 4 * c) = v;
+                *reinterpret_cast<f32x4*>(fe_tile + row * tile_w + 4 * c) = v;
             }
         }
     }
@@ -521,7 +521,6 @@ __global__ __launch_bounds__(768) void f32_front2_kernel(F32Front2Args A) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int n = lane & 15, kq = lane >> 4;
     const int OH = a.OH;
-    auto step_barrier = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
 
     if (wave < strips_x) {
         // ---------------------------------------------------------------- producer: front block rows -> ring
@@ -530,14 +529,14 @@ __global__ __launch_bounds__(768) void f32_front2_kernel(F32Front2Args A) {
         float sa[3];
 #pragma unroll
         for (int j = 0; j < 3; ++j) sa[j] = kq < 3 ? a.stem_w[(kq * 3 + j) * 16 + n] : 0.0f;
-        const v4f stb = *reinterpret_cast<const v4f*>(a.stem_b + 4 * kq);
-        const v4f dwb = *reinterpret_cast<const v4f*>(a.dw_b + 4 * kq);
-        v4f pa[2], pb[2];
+        const f32x4 stb = *reinterpret_cast<const f32x4*>(a.stem_b + 4 * kq);
+        const f32x4 dwb = *reinterpret_cast<const f32x4*>(a.dw_b + 4 * kq);
+        f32x4 pa[2], pb[2];
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             const int ch = 8 * (n >> 2) + 4 * t + (n & 3);
-            pa[t] = reinterpret_cast<const v4f*>(a.pw_w)[(ch >> 4) * 64 + kq * 16 + (ch & 15)];
-            pb[t] = *reinterpret_cast<const v4f*>(a.pw_b + 8 * kq + 4 * t);
+            pa[t] = reinterpret_cast<const f32x4*>(a.pw_w)[(ch >> 4) * 64 + kq * 16 + (ch & 15)];
+            pb[t] = *reinterpret_cast<const f32x4*>(a.pw_b + 8 * kq + 4 * t);
         }
         const bool right_st = 2 * ow + 2 >= a.W0 / 2;
         const int rows_needed = 2 * (OH - 1) + 3;
@@ -545,9 +544,9 @@ __global__ __launch_bounds__(768) void f32_front2_kernel(F32Front2Args A) {
         auto stem_row = [&](int srel, int ti) {
             if (srel < rows_needed && srel < a.H0) {
                 const float* trow = fe_tile + (srel + kq) * tile_w + 4 * ow;  // input row srel - 1 + kq
-                const v4f lo = *reinterpret_cast<const v4f*>(trow), hi = *reinterpret_cast<const v4f*>(trow + 4);
+                const f32x4 lo = *reinterpret_cast<const f32x4*>(trow), hi = *reinterpret_cast<const f32x4*>(trow + 4);
                 const float x[7] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z};
-                v4f st[3];
+                f32x4 st[3];
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
                     st[c] = stb;
@@ -556,16 +555,16 @@ __global__ __launch_bounds__(768) void f32_front2_kernel(F32Front2Args A) {
                 }
 #pragma unroll
                 for (int c = 0; c < 3; ++c) T[ti].t[c] = act4(st[c], st_bounds);
-                if (right_st) T[ti].t[2] = (v4f){0.0f, 0.0f, 0.0f, 0.0f};
+                if (right_st) T[ti].t[2] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
             } else {
 #pragma unroll
-                for (int c = 0; c < 3; ++c) T[ti].t[c] = (v4f){0.0f, 0.0f, 0.0f, 0.0f};
+                for (int c = 0; c < 3; ++c) T[ti].t[c] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
             }
         };
         auto emit = [&](int i0, int i1, int i2, int oh) {
             asm volatile("" ::: "memory");
-            const v4f* dw = &dw_lds[0][kq];
-            v4f d = dwb;
+            const f32x4* dw = &dw_lds[0][kq];
+            f32x4 d = dwb;
 #pragma unroll
             for (int j = 0; j < 3; ++j) {
                 d = __builtin_elementwise_fma(T[i0].t[j], dw[(0 + j) * 4], d);
@@ -576,12 +575,12 @@ __global__ __launch_bounds__(768) void f32_front2_kernel(F32Front2Args A) {
             float* dst = ring + (((oh & 1) * (a.OW + 2)) + ow + 1) * RP + 8 * kq;
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
-                v4f o = pb[t];
+                f32x4 o = pb[t];
 #pragma unroll
                 for (int g = 0; g < 4; ++g) mfma_acc(o, pa[t][g], d[g]);
-                *reinterpret_cast<v4f*>(dst + 4 * t) = act4(o, pw_bounds);
+                *reinterpret_cast<f32x4*>(dst + 4 * t) = act4(o, pw_bounds);
             }
-            step_barrier();
+            lds_barrier();
         };
         // (queueing the next row's stem matrix instructions before this row's ring write and barrier changed nothing: 0.198 vs 0.190 ms)
         stem_row(0, 0);
@@ -597,8 +596,8 @@ __global__ __launch_bounds__(768) void f32_front2_kernel(F32Front2Args A) {
                 emit((2 * u) % 3, (2 * u + 1) % 3, (2 * u + 2) % 3, k + u);
             }
         }
-        step_barrier();  // the consumers' two trailing steps
-        step_barrier();
+        lds_barrier();  // the consumers' two trailing steps
+        lds_barrier();
     } else {
         // ---------------------------------------------------------------- consumer: the residual block on 16 of the 32 channels
         const int cw = wave - strips_x;
@@ -606,22 +605,22 @@ __global__ __launch_bounds__(768) void f32_front2_kernel(F32Front2Args A) {
         const int ow = sx * 16 + n;
         const int c0 = 16 * w + 4 * kq;
         const ActBounds dw_bounds = act_bounds(A.dw_act), pw_bounds = act_bounds(A.pw_act);
-        const v4f* dw = &dw2_lds[0][c0 >> 2];
-        const v4f dwb = *reinterpret_cast<const v4f*>(A.dw_b + c0);
-        v4f pa[2];
+        const f32x4* dw = &dw2_lds[0][c0 >> 2];
+        const f32x4 dwb = *reinterpret_cast<const f32x4*>(A.dw_b + c0);
+        f32x4 pa[2];
         {
             const int ch = 16 * w + 4 * (n >> 2) + (n & 3);
 #pragma unroll
-            for (int ks = 0; ks < 2; ++ks) pa[ks] = reinterpret_cast<const v4f*>(A.pw_w)[(ks * 2 + (ch >> 4)) * 64 + kq * 16 + (ch & 15)];
+            for (int ks = 0; ks < 2; ++ks) pa[ks] = reinterpret_cast<const f32x4*>(A.pw_w)[(ks * 2 + (ch >> 4)) * 64 + kq * 16 + (ch & 15)];
         }
-        const v4f pb = *reinterpret_cast<const v4f*>(A.pw_b + 16 * w + 4 * kq);
+        const f32x4 pb = *reinterpret_cast<const f32x4*>(A.pw_b + 16 * w + 4 * kq);
         const __amdgpu_buffer_rsrc_t rs_out =
             __builtin_amdgcn_make_buffer_rsrc(A.y + (size_t)chunk * OH * a.OW * 32, 0, OH * a.OW * 32 * 4, 0x00020000);
         const int voff_out = (ow * 32 + 16 * w + 4 * kq) * 4;
         const float* rcol = ring + ow * RP + c0;          // tap j of row r: rcol[((r & 1) * (OW + 2) + j) * RP]
-        v4f* xs = xchg + sx * 256;                        // [2][2][64]
+        f32x4* xs = xchg + sx * 256;                        // [2][2][64]
         Row4 T[3];
-        v4f pacc = {0.0f, 0.0f, 0.0f, 0.0f}, pcen = pacc;
+        f32x4 pacc = {0.0f, 0.0f, 0.0f, 0.0f}, pcen = pacc;
         const int steps = OH + 2;
         for (int t0 = 0; t0 < steps; t0 += 3) {
 #pragma unroll
@@ -632,15 +631,15 @@ __global__ __launch_bounds__(768) void f32_front2_kernel(F32Front2Args A) {
                 if (t >= 1 && t <= OH) {
                     const float* rp = rcol + (((t - 1) & 1) * (a.OW + 2)) * RP;
 #pragma unroll
-                    for (int j = 0; j < 3; ++j) T[u].t[j] = *reinterpret_cast<const v4f*>(rp + j * RP);
+                    for (int j = 0; j < 3; ++j) T[u].t[j] = *reinterpret_cast<const f32x4*>(rp + j * RP);
                 } else {
 #pragma unroll
-                    for (int j = 0; j < 3; ++j) T[u].t[j] = (v4f){0.0f, 0.0f, 0.0f, 0.0f};
+                    for (int j = 0; j < 3; ++j) T[u].t[j] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
                 }
                 const int i0 = (u + 1) % 3, i1 = (u + 2) % 3, i2 = u;   // rows t - 3, t - 2, t - 1
                 if (t >= 2) {
                     asm volatile("" ::: "memory");
-                    v4f acc = dwb;
+                    f32x4 acc = dwb;
 #pragma unroll
                     for (int j = 0; j < 3; ++j) {
                         acc = __builtin_elementwise_fma(T[i0].t[j], dw[(0 + j) * 8], acc);
@@ -650,9 +649,9 @@ __global__ __launch_bounds__(768) void f32_front2_kernel(F32Front2Args A) {
                     xs[((t & 1) * 2 + w) * 64 + lane] = act4(acc, dw_bounds);
                 }
                 if (t >= 3) store16(rs_out, act4(pacc + pcen, pw_bounds), voff_out, (t - 3) * a.OW * 32 * 4);
-                step_barrier();
+                lds_barrier();
                 if (t >= 2) {
-                    const v4f f0 = xs[((t & 1) * 2 + 0) * 64 + lane], f1 = xs[((t & 1) * 2 + 1) * 64 + lane];
+                    const f32x4 f0 = xs[((t & 1) * 2 + 0) * 64 + lane], f1 = xs[((t & 1) * 2 + 1) * 64 + lane];
                     pacc = pb;
 #pragma unroll
                     for (int g = 0; g < 4; ++g) mfma_acc(pacc, pa[0][g], f0[g]);
@@ -708,12 +707,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(S == 2 ? 3 
     const int c0 = 4 * (g * CQ + cq);
     const ActBounds bounds = act_bounds(a.act);
 
-    v4f wt[3][3];
+    f32x4 wt[3][3];
 #pragma unroll
     for (int i = 0; i < 3; ++i)
 #pragma unroll
-        for (int j = 0; j < 3; ++j) wt[i][j] = *reinterpret_cast<const v4f*>(a.w + (i * 3 + j) * a.C + c0);
-    const v4f b4 = *reinterpret_cast<const v4f*>(a.bias + c0);
+        for (int j = 0; j < 3; ++j) wt[i][j] = *reinterpret_cast<const f32x4*>(a.w + (i * 3 + j) * a.C + c0);
+    const f32x4 b4 = *reinterpret_cast<const f32x4*>(a.bias + c0);
 
     const int in_chunk_bytes = a.H * a.W * a.C * 4;
     const int row_bytes = a.W * a.C * 4;
@@ -735,7 +734,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(S == 2 ? 3 
         if (row_ok(rr)) {
             const int soff = (ir0 + rr) * row_bytes;
 #pragma unroll
-            for (int j = 0; j < 3; ++j) raw[slot].t[j] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rs_in, voff_in[j], soff, 0));
+            for (int j = 0; j < 3; ++j) raw[slot].t[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_in, voff_in[j], soff, 0));
         }
     };
     auto consume = [&](int slot, int rr, int ti) {
@@ -743,19 +742,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(S == 2 ? 3 
             T[ti] = raw[slot];
         } else {
 #pragma unroll
-            for (int j = 0; j < 3; ++j) T[ti].t[j] = (v4f){0.0f, 0.0f, 0.0f, 0.0f};
+            for (int j = 0; j < 3; ++j) T[ti].t[j] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
         }
     };
-    v4f gsum = {0.0f, 0.0f, 0.0f, 0.0f};
+    f32x4 gsum = {0.0f, 0.0f, 0.0f, 0.0f};
     auto emit = [&](int i0, int i1, int i2, int oh) {
-        v4f acc = b4;
+        f32x4 acc = b4;
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
             acc = __builtin_elementwise_fma(T[i0].t[j], wt[0][j], acc);
             acc = __builtin_elementwise_fma(T[i1].t[j], wt[1][j], acc);
             acc = __builtin_elementwise_fma(T[i2].t[j], wt[2][j], acc);
         }
-        const v4f o = act4(acc, bounds);
+        const f32x4 o = act4(acc, bounds);
         if (live) gsum += o;
         store16(rs_out, o, voff_out, oh * a.OW * a.C * 4);
     };
@@ -786,7 +785,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(S == 2 ? 3 
 #pragma unroll
             for (int e = 0; e < 4; ++e) gsum[e] += __shfl_xor(gsum[e], m, 64);
         }
-        if (n == 0) *reinterpret_cast<v4f*>(a.gap_part + ((size_t)chunk * strips_x * rblocks + (size_t)ry * strips_x + sx) * a.C + c0) = gsum;
+        if (n == 0) *reinterpret_cast<f32x4*>(a.gap_part + ((size_t)chunk * strips_x * rblocks + (size_t)ry * strips_x + sx) * a.C + c0) = gsum;
     }
 }
 
@@ -859,12 +858,12 @@ __global__ __launch_bounds__(640) void f32_pwdw_kernel(F32PwDwArgs a) {
         const int pp = w % npp, tc = w / npp;      // positions 32 pp + 16 u + n, hidden channels 16 NCW tc + 16 c + 4 kq + e
         const int nct = a.hid >> 4;
         const ActBounds pw_bounds = act_bounds(a.pw_act);
-        v4f pa[NCW][NJ], pbias[NCW];
+        f32x4 pa[NCW][NJ], pbias[NCW];
 #pragma unroll
         for (int c = 0; c < NCW; ++c) {
 #pragma unroll
-            for (int j = 0; j < NJ; ++j) pa[c][j] = reinterpret_cast<const v4f*>(a.pw_w)[(j * nct + NCW * tc + c) * 64 + lane];
-            pbias[c] = *reinterpret_cast<const v4f*>(a.pw_b + 16 * NCW * tc + 16 * c + 4 * kq);
+            for (int j = 0; j < NJ; ++j) pa[c][j] = reinterpret_cast<const f32x4*>(a.pw_w)[(j * nct + NCW * tc + c) * 64 + lane];
+            pbias[c] = *reinterpret_cast<const f32x4*>(a.pw_b + 16 * NCW * tc + 16 * c + 4 * kq);
         }
         bool chan_ok[NJ];                           // channels beyond Cin: the zero-padded k-step of Cin = 24
 #pragma unroll
@@ -878,7 +877,7 @@ __global__ __launch_bounds__(640) void f32_pwdw_kernel(F32PwDwArgs a) {
         constexpr bool STEM_OK = NJ <= 2;           // (a stem feeds at most 32 channels; the wide instantiations do not carry this code)
         constexpr int NJS = STEM_OK ? NJ : 1;
         float sa[3][NJS], tcur[2][3], tnext[2][3];
-        v4f sbias[NJS];
+        f32x4 sbias[NJS];
         const bool stem = STEM_OK && a.fe != nullptr;
         const ActBounds st_bounds = act_bounds(a.stem_act);
         // taps through a range-checked raw buffer over this chunk's map: a tap outside it (SAME padding, rows the strip does not need, lane
@@ -902,7 +901,7 @@ __global__ __launch_bounds__(640) void f32_pwdw_kernel(F32PwDwArgs a) {
                 const int ch = 16 * j + n;           // A operand row = stem channel
 #pragma unroll
                 for (int i = 0; i < 3; ++i) sa[i][j] = (kq < 3 && ch < a.Cin) ? a.stem_w[(i * 3 + kq) * a.Cin + ch] : 0.0f;
-                sbias[j] = chan_ok[j] ? *reinterpret_cast<const v4f*>(a.stem_b + 16 * j + 4 * kq) : (v4f){0.0f, 0.0f, 0.0f, 0.0f};
+                sbias[j] = chan_ok[j] ? *reinterpret_cast<const f32x4*>(a.stem_b + 16 * j + 4 * kq) : (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
             }
             taps(tcur, 0);
         }
@@ -911,13 +910,13 @@ __global__ __launch_bounds__(640) void f32_pwdw_kernel(F32PwDwArgs a) {
             if (stem) taps(tnext, t + 1);
             if (row_ok(t)) {
                 const float* src = stage + (t % 3) * a.W * PI + src_off;
-                v4f bf[2][NJ];
+                f32x4 bf[2][NJ];
                 if (stem) {
 #pragma unroll
                     for (int u = 0; u < 2; ++u)
 #pragma unroll
                         for (int j = 0; j < NJS; ++j) {
-                            v4f st = sbias[j];
+                            f32x4 st = sbias[j];
 #pragma unroll
                             for (int i = 0; i < 3; ++i) mfma_acc(st, sa[i][j], tcur[u][i]);
                             bf[u][j] = act4(st, st_bounds);
@@ -927,14 +926,14 @@ __global__ __launch_bounds__(640) void f32_pwdw_kernel(F32PwDwArgs a) {
                     for (int u = 0; u < 2; ++u)
 #pragma unroll
                         for (int j = 0; j < NJ; ++j)
-                            bf[u][j] = chan_ok[j] ? *reinterpret_cast<const v4f*>(src + 16 * u * PI + 16 * j) : (v4f){0.0f, 0.0f, 0.0f, 0.0f};
+                            bf[u][j] = chan_ok[j] ? *reinterpret_cast<const f32x4*>(src + 16 * u * PI + 16 * j) : (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
                 }
                 float* dst = ring3 + (((h_lo + t) & 3) * (a.W + 2)) * P + dst_off;
-                v4f acc[2][NCW];  // the tiles' chains interleaved: consecutive matrix instructions never depend on each other
+                f32x4 acc[2][NCW];  // the tiles' chains interleaved: consecutive matrix instructions never depend on each other
 #pragma unroll
                 for (int u = 0; u < 2; ++u)
 #pragma unroll
-                    for (int c = 0; c < NCW; ++c) acc[u][c] = (v4f){0.0f, 0.0f, 0.0f, 0.0f};
+                    for (int c = 0; c < NCW; ++c) acc[u][c] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
                 for (int j = 0; j < NJ; ++j)
 #pragma unroll
@@ -947,7 +946,7 @@ __global__ __launch_bounds__(640) void f32_pwdw_kernel(F32PwDwArgs a) {
                 for (int u = 0; u < 2; ++u)
 #pragma unroll
                     for (int c = 0; c < NCW; ++c)  // bias behind the sum, as the stand-alone 1x1 kernels add it: the pair stays bit-identical to them
-                        *reinterpret_cast<v4f*>(dst + 16 * u * P + 16 * c) = act4(acc[u][c] + pbias[c], pw_bounds);
+                        *reinterpret_cast<f32x4*>(dst + 16 * u * P + 16 * c) = act4(acc[u][c] + pbias[c], pw_bounds);
             }
             if (stem) {
 #pragma unroll
@@ -967,14 +966,14 @@ __global__ __launch_bounds__(640) void f32_pwdw_kernel(F32PwDwArgs a) {
         const int groups = dwn / quads;
         const bool dw_live = dt < dwn;
         const int q = dw_live ? dt % quads : 0, cg = dw_live ? dt / quads : 0;
-        v4f wt[3][3], dwb = {0.0f, 0.0f, 0.0f, 0.0f};
+        f32x4 wt[3][3], dwb = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
         for (int dy = 0; dy < 3; ++dy)
 #pragma unroll
-            for (int dx = 0; dx < 3; ++dx) wt[dy][dx] = dw_live ? *reinterpret_cast<const v4f*>(a.dw_w + (dy * 3 + dx) * a.hid + 4 * q) : dwb;
-        if (dw_live) dwb = *reinterpret_cast<const v4f*>(a.dw_b + 4 * q);
+            for (int dx = 0; dx < 3; ++dx) wt[dy][dx] = dw_live ? *reinterpret_cast<const f32x4*>(a.dw_w + (dy * 3 + dx) * a.hid + 4 * q) : dwb;
+        if (dw_live) dwb = *reinterpret_cast<const f32x4*>(a.dw_b + 4 * q);
         float* ybase = a.y + ((size_t)chunk * a.OH) * a.OW * a.hid + 4 * q;
-        v4f gsum = {0.0f, 0.0f, 0.0f, 0.0f};
+        f32x4 gsum = {0.0f, 0.0f, 0.0f, 0.0f};
         auto depthwise = [&](int oh) {
             if (!dw_live) return;
             const int hr0 = S * oh - a.pt;
@@ -989,13 +988,13 @@ __global__ __launch_bounds__(640) void f32_pwdw_kernel(F32PwDwArgs a) {
             const bool interior = rok[0] && rok[1] && rok[2];
             for (int ox = cg; ox < a.OW; ox += groups) {
                 const int off = S * ox * P;
-                v4f acc = dwb;
+                f32x4 acc = dwb;
                 if (interior) {  // nine loads in flight, then the same summation order as below
-                    v4f v[3][3];
+                    f32x4 v[3][3];
 #pragma unroll
                     for (int dy = 0; dy < 3; ++dy)
 #pragma unroll
-                        for (int dx = 0; dx < 3; ++dx) v[dy][dx] = *reinterpret_cast<const v4f*>(rows[dy] + off + dx * P);
+                        for (int dx = 0; dx < 3; ++dx) v[dy][dx] = *reinterpret_cast<const f32x4*>(rows[dy] + off + dx * P);
 #pragma unroll
                     for (int dx = 0; dx < 3; ++dx)
 #pragma unroll
@@ -1005,11 +1004,11 @@ __global__ __launch_bounds__(640) void f32_pwdw_kernel(F32PwDwArgs a) {
                     for (int dx = 0; dx < 3; ++dx)
 #pragma unroll
                         for (int dy = 0; dy < 3; ++dy)
-                            if (rok[dy]) acc = __builtin_elementwise_fma(*reinterpret_cast<const v4f*>(rows[dy] + off + dx * P), wt[dy][dx], acc);
+                            if (rok[dy]) acc = __builtin_elementwise_fma(*reinterpret_cast<const f32x4*>(rows[dy] + off + dx * P), wt[dy][dx], acc);
                 }
-                const v4f o = act4(acc, dw_bounds);
+                const f32x4 o = act4(acc, dw_bounds);
                 gsum += o;
-                *reinterpret_cast<v4f*>(ybase + ((size_t)oh * a.OW + ox) * a.hid) = o;
+                *reinterpret_cast<f32x4*>(ybase + ((size_t)oh * a.OW + ox) * a.hid) = o;
             }
         };
         __syncthreads();
@@ -1018,12 +1017,12 @@ __global__ __launch_bounds__(640) void f32_pwdw_kernel(F32PwDwArgs a) {
             __syncthreads();
         }
         // channel sums of this workgroup's rows: the column groups' sums meet in LDS (the ring is free now) and are added in a fixed order
-        if (a.gap_part && dw_live) *reinterpret_cast<v4f*>(ring3 + cg * a.hid + 4 * q) = gsum;
+        if (a.gap_part && dw_live) *reinterpret_cast<f32x4*>(ring3 + cg * a.hid + 4 * q) = gsum;
         __syncthreads();
         if (a.gap_part && dt < quads) {
-            v4f tot = {0.0f, 0.0f, 0.0f, 0.0f};
-            for (int g2 = 0; g2 < groups; ++g2) tot += *reinterpret_cast<const v4f*>(ring3 + g2 * a.hid + 4 * dt);
-            *reinterpret_cast<v4f*>(a.gap_part + ((size_t)chunk * rblocks + ry) * a.hid + 4 * dt) = tot;
+            f32x4 tot = {0.0f, 0.0f, 0.0f, 0.0f};
+            for (int g2 = 0; g2 < groups; ++g2) tot += *reinterpret_cast<const f32x4*>(ring3 + g2 * a.hid + 4 * dt);
+            *reinterpret_cast<f32x4*>(a.gap_part + ((size_t)chunk * rblocks + ry) * a.hid + 4 * dt) = tot;
         }
     } else {
         // ------------------------------------------------------------------------------------------------ loaders (two waves)
@@ -1041,19 +1040,19 @@ __global__ __launch_bounds__(640) void f32_pwdw_kernel(F32PwDwArgs a) {
             const int idx = lt + 128 * e, pos = idx / cq4;
             st_off[e] = pos * PI + 4 * (idx - pos * cq4);
         }
-        auto request = [&](v4f (&r)[NLD], int k) {
+        auto request = [&](f32x4 (&r)[NLD], int k) {
             int hr = h_lo + k;
             hr = hr < 0 ? 0 : (hr >= a.H ? a.H - 1 : hr);
             const float* src = xc + (size_t)hr * a.W * a.Cin;
 #pragma unroll
-            for (int e = 0; e < NLD; ++e) r[e] = *reinterpret_cast<const v4f*>(src + 512 * e);
+            for (int e = 0; e < NLD; ++e) r[e] = *reinterpret_cast<const f32x4*>(src + 512 * e);
         };
-        auto deposit = [&](const v4f (&r)[NLD], int k) {
+        auto deposit = [&](const f32x4 (&r)[NLD], int k) {
             float* dst = stage + (k % 3) * a.W * PI;
 #pragma unroll
-            for (int e = 0; e < NLD; ++e) *reinterpret_cast<v4f*>(dst + st_off[e]) = r[e];
+            for (int e = 0; e < NLD; ++e) *reinterpret_cast<f32x4*>(dst + st_off[e]) = r[e];
         };
-        v4f r0[NLD], r1[NLD], r2[NLD];
+        f32x4 r0[NLD], r1[NLD], r2[NLD];
         request(r0, 0);
         request(r1, 1);
         request(r2, 2);

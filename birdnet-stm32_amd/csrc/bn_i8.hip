@@ -15,22 +15,6 @@
 namespace bn {
 namespace {
 
-
-
-
-
-__device__ __forceinline__ int32_t dot4(int32_t a, int32_t b, int32_t c) {
-#if __has_builtin(__builtin_amdgcn_sdot4)
-    return __builtin_amdgcn_sdot4(a, b, c, false);
-#else
-    c += (int32_t)(int8_t)(a) * (int32_t)(int8_t)(b);
-    c += (int32_t)(int8_t)(a >> 8) * (int32_t)(int8_t)(b >> 8);
-    c += (int32_t)(int8_t)(a >> 16) * (int32_t)(int8_t)(b >> 16);
-    c += (int32_t)(int8_t)(a >> 24) * (int32_t)(int8_t)(b >> 24);
-    return c;
-#endif
-}
-
 // TFLite int8 ADD (left_shift = 20); a = first ADD input, b = second
 struct AddQ {
     int z1, m1, s1, z2, m2, s2, mo, so, zo, amin, amax;
@@ -601,7 +585,7 @@ __global__ __launch_bounds__(256) void i8_attnpool_kernel(AttnPool8Args a) {
     __syncthreads();
     for (int p = tid; p < P; p += 256) {
         int acc = a.fc_bias;  // bias - zx * sum(w) folded by the packer
-        for (int k = 0; k < C / 4; ++k) acc = __builtin_amdgcn_sdot4(reinterpret_cast<const int*>(apx + (size_t)p * C)[k], reinterpret_cast<const int*>(a.w)[k], acc, false);
+        for (int k = 0; k < C / 4; ++k) acc = dot4(reinterpret_cast<const int*>(apx + (size_t)p * C)[k], reinterpret_cast<const int*>(a.w)[k], acc);
         sc[p] = (int8_t)clampi(mbqm_ref(acc, a.fc_mult, a.fc_shift) + a.fc_zo, -128, 127);
     }
     __syncthreads();

@@ -28,14 +28,11 @@
 namespace bn {
 namespace {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
-
 __device__ __forceinline__ int32_t sx8(int32_t v, int byte) { return (int32_t)(int8_t)(v >> (8 * byte)); }
 
 // One multiply-accumulate of channel e of a packed 4-channel dword without unpacking: v_dot4_i32_i8 against a weight dword
 // whose other three bytes are zero (the reduction over the four bytes then has a single non-zero term).  Exact int32.
 __device__ __forceinline__ int32_t lane_byte(int32_t w, int e) { return w & (0xff << (8 * e)); }
-__device__ __forceinline__ int32_t dot4(int32_t a, int32_t b, int32_t c) { return __builtin_amdgcn_sdot4(a, b, c, false); }
 
 // 4 x 4 byte transpose: rows r0..r3 hold four channels of one tap each; c[e] gets channel e of the four taps.
 // v_perm_b32 picks bytes out of the 8-byte value {s0 (bytes 4-7), s1 (bytes 0-3)}.
@@ -1034,7 +1031,7 @@ __global__ __launch_bounds__(TAB ? 1024 : 256) void i8_pw_wave_kernel(DwPw8Args 
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
                             const int p = (int)((xu >> (8 * e)) & 0xff) * (int)((gu >> (8 * e)) & 0xff);
-                            gq[e] = med3i((int)(((long long)p * a.g_mult + gC) >> 32) >> gsh, a.g_amin, a.g_amax);
+                            gq[e] = med3((int)(((long long)p * a.g_mult + gC) >> 32) >> gsh, a.g_amin, a.g_amax);
                         }
                         packed = pack4(gq);
                     } else if constexpr (MODE == 0) {
@@ -1113,25 +1110,25 @@ __global__ __launch_bounds__(TAB ? 1024 : 256) void i8_pw_wave_kernel(DwPw8Args 
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const long long C = (long long)(((unsigned long long)(unsigned)chi[e] << 32) | (unsigned)clo[e]);
-                        qv[e] = med3i((int)(((long long)acc[e] * m[e] + C) >> 32) >> sh[e], a.pw_amin, a.pw_amax);
+                        qv[e] = med3((int)(((long long)acc[e] * m[e] + C) >> 32) >> sh[e], a.pw_amin, a.pw_amax);
                     }
                 } else if constexpr (TAB) {
                     // own value + 128 (the table's column), then the ADD as one byte read
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        const int own = med3i(mbqm_right(acc[e], m[e], sh[e]) + (a.pw_zp_out + 128), a.pw_amin + 128, a.pw_amax + 128);
+                        const int own = med3(mbqm_right(acc[e], m[e], sh[e]) + (a.pw_zp_out + 128), a.pw_amin + 128, a.pw_amax + 128);
                         qv[e] = add_tab[__builtin_amdgcn_perm((unsigned)rv, (unsigned)own, 0x0c0c0400u + (e << 8))];
                     }
                 } else {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) qv[e] = med3i(mbqm_right(acc[e], m[e], sh[e]) + a.pw_zp_out, a.pw_amin, a.pw_amax);
+                    for (int e = 0; e < 4; ++e) qv[e] = med3(mbqm_right(acc[e], m[e], sh[e]) + a.pw_zp_out, a.pw_amin, a.pw_amax);
                 }
                 if (ADD && !TAB) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const int sa = add_lut[0][(rv >> (8 * e)) & 0xff];
                         const int sb = add_lut[1][qv[e] & 0xff];
-                        qv[e] = med3i(mbqm_right(sa + sb, a.add.mo, a.add.so) + a.add.zo, a.add.amin, a.add.amax);
+                        qv[e] = med3(mbqm_right(sa + sb, a.add.mo, a.add.so) + a.add.zo, a.add.amin, a.add.amax);
                     }
                 }
                 outw[u] = pack4(qv);

@@ -30,8 +30,6 @@
 namespace bn {
 namespace {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
-
 constexpr int kPwLdsThreads = 1024;  // one workgroup of sixteen waves per CU: the slice's weights are staged once per CU, not twice
 constexpr int kPwLdsWaves = kPwLdsThreads / 64;
 constexpr size_t kPwLdsBudget = 154 * 1024;  // weights + constants of a slice (+ 2 KB of ADD tables) inside a CU's 160 KB
@@ -170,7 +168,7 @@ __global__ __launch_bounds__(kPwLdsThreads) void i8_pw_lds_kernel(DwPw8Args a, P
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
                             const int p = (int)((xu >> (8 * e)) & 0xff) * (int)((gu >> (8 * e)) & 0xff);
-                            gq[e] = med3i((int)(((long long)p * a.g_mult + gC) >> 32) >> gsh, a.g_amin, a.g_amax);
+                            gq[e] = med3((int)(((long long)p * a.g_mult + gC) >> 32) >> gsh, a.g_amin, a.g_amax);
                         }
                         b[d] = pack4(gq);
                         __builtin_amdgcn_sched_barrier(0);  // (one dword at a time: the sixteen requantisations in parallel cost 40 more registers)
@@ -208,17 +206,17 @@ __global__ __launch_bounds__(kPwLdsThreads) void i8_pw_lds_kernel(DwPw8Args a, P
                 for (int e = 0; e < 4; ++e) {
                     if constexpr (HI) {
                         const long long C = (long long)(((unsigned long long)(unsigned)chi[e] << 32) | (unsigned)clo[e]);
-                        qv[e] = med3i((int)(((long long)acc[ct0 + u][e] * m[e] + C) >> 32) >> sh[e], a.pw_amin, a.pw_amax);
+                        qv[e] = med3((int)(((long long)acc[ct0 + u][e] * m[e] + C) >> 32) >> sh[e], a.pw_amin, a.pw_amax);
                     } else if (ADD && g.tab) {  // (uniform) own value + 128 = the table's column; the ADD is one byte read
-                        const int own = med3i(mbqm_right(acc[ct0 + u][e], m[e], sh[e]) + (a.pw_zp_out + 128), a.pw_amin + 128, a.pw_amax + 128);
+                        const int own = med3(mbqm_right(acc[ct0 + u][e], m[e], sh[e]) + (a.pw_zp_out + 128), a.pw_amin + 128, a.pw_amax + 128);
                         qv[e] = tabl[__builtin_amdgcn_perm((unsigned)rv4[u], (unsigned)own, 0x0c0c0400u + (e << 8))];
                     } else {  // every multiplier >= 0 and every shift < 0 (checked at load): the branch-free signed form
-                        qv[e] = med3i(mbqm_right(acc[ct0 + u][e], m[e], sh[e]) + a.pw_zp_out, a.pw_amin, a.pw_amax);
+                        qv[e] = med3(mbqm_right(acc[ct0 + u][e], m[e], sh[e]) + a.pw_zp_out, a.pw_amin, a.pw_amax);
                     }
                     if (ADD && !g.tab) {
                         const int sa = add_lut[0][(rv4[u] >> (8 * e)) & 0xff];
                         const int sb = add_lut[1][qv[e] & 0xff];
-                        qv[e] = med3i(mbqm(sa + sb, a.add.mo, a.add.so) + a.add.zo, a.add.amin, a.add.amax);  // (uniform parameters: the form is chosen once)
+                        qv[e] = med3(mbqm(sa + sb, a.add.mo, a.add.so) + a.add.zo, a.add.amin, a.add.amax);  // (uniform parameters: the form is chosen once)
                     }
                 }
                 outw[u] = pack4(qv);

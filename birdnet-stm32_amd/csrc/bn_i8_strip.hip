@@ -39,51 +39,6 @@
 namespace bn {
 namespace {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v2i __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ int perm(int s0, int s1, uint32_t sel) { return (int)__builtin_amdgcn_perm((uint32_t)s0, (uint32_t)s1, sel); }
-__device__ __forceinline__ int dot4(int a, int b, int c) { return __builtin_amdgcn_sdot4(a, b, c, false); }
-// clamp as ONE instruction; lo <= hi.  (The compiler cannot prove lo <= hi for run-time bounds and emits compare + select + min.)
-__device__ __forceinline__ int med3(int v, int lo, int hi) {
-    int r;
-    asm("v_med3_i32 %0, %1, %2, %3" : "=v"(r) : "v"(v), "v"(lo), "v"(hi));
-    return r;
-}
-// first link of a dot4 chain in the three-address form (no move of the bias into the accumulator)
-__device__ __forceinline__ int dot4_first(int a, int b, int c) {
-    int r;
-    asm("v_dot4_i32_i8 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
-
-// q = ((srdhm(x, m) + c1 + sign) >> e), c1 = 2^(e-1) + (zp << e): RoundingDivideByPOT(SRDHM(x, m), e) + zp (bn_requant.h)
-__device__ __forceinline__ int rq(int x, int m, int c1, int e) {
-    const int v = srdhm_pos(x, m);
-    return (v + c1 + (v >> 31)) >> e;
-}
-
-// Where the clamp's lower bound is at or above the zero point (ReLU / ReLU6 outputs: the packer checks it) a negative v gives a result
-// <= zero point with or without the sign term (v + 2^(e-1) < 2^e) and both clamp to the same bound: (v + c1) >> e,
-// and with the addend folded into the 64-bit multiply-add: ((x*m + 2^30) >> 31 + c1) >> e == (x*m + 2^30 + c1 * 2^31) >> (31 + e)
-// (nested floors) == hi32(x*m + C) >> (e - 1) for e >= 1: v_mad_i64_i32 with a per-channel 64-bit constant C = 2^30 + c1 * 2^31, then ONE
-// arithmetic shift of the high dword — 2 instructions + clamp instead of 5 + clamp.  rq64(c1) builds C; kernels keep (C, e - 1) per channel.
-__device__ __forceinline__ long rq64(int c1) { return ((long)c1 << 31) + 0x40000000L; }
-// The four shifts of a channel quad are packed into the bytes of ONE register (SDWA picks byte `e` as the shift
-// count: no unpacking instruction, three registers less per quad)
-__device__ __forceinline__ int pack_shifts(v4i sh) { return sh.x | (sh.y << 8) | (sh.z << 16) | (sh.w << 24); }
-__device__ __forceinline__ int rq_hi(int x, int m, long c, int e1_packed, int e) {
-    const int hi = (int)(((long)x * (long)m + c) >> 32);
-    int r;
-    switch (e) {  // e is a compile-time constant after unrolling
-        case 0: asm("v_ashrrev_i32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_0 src1_sel:DWORD" : "=v"(r) : "v"(e1_packed), "v"(hi)); break;
-        case 1: asm("v_ashrrev_i32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_1 src1_sel:DWORD" : "=v"(r) : "v"(e1_packed), "v"(hi)); break;
-        case 2: asm("v_ashrrev_i32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_2 src1_sel:DWORD" : "=v"(r) : "v"(e1_packed), "v"(hi)); break;
-        default: asm("v_ashrrev_i32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_3 src1_sel:DWORD" : "=v"(r) : "v"(e1_packed), "v"(hi)); break;
-    }
-    return r;
-}
-
 template <int QL> struct RawRow { int t[3][QL]; };   // three taps (columns j = 0..2) of one input row, QL dwords each
 template <int QL> struct TRow { int c[QL][4]; };     // per channel: bytes (tap0, tap1, tap2, 0)
 
@@ -390,7 +345,7 @@ void i8_strip_kernel(Strip8Args a) {
         if constexpr (NW > 1 && !PIPE) {
             v2i* buf = xchg + ((step & 1) * SPB + wave / NW) * (NW * 64);
             buf[w * 64 + lane] = (v2i){bfrag[0], bfrag[1]};
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            lds_barrier();
             v4i acc[NT];
             mma_part(bfrag, buf, acc);
             epi_part(acc, cen[i1], oh);
@@ -399,7 +354,7 @@ void i8_strip_kernel(Strip8Args a) {
             buf[w * 64 + lane] = (v2i){bfrag[0], bfrag[1]};
             if (step > 0) epi_part(pacc, pcen, poh);
             // LDS only: the prefetched global loads stay in flight across the barrier (a __syncthreads would drain them)
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            lds_barrier();
             mma_part(bfrag, buf, pacc);
 #pragma unroll
             for (int ql = 0; ql < QL; ++ql) pcen[ql] = cen[i1][ql];

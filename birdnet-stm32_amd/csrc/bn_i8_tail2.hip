@@ -137,14 +137,7 @@ __device__ __forceinline__ int tail2_pw_bytes(const Tail2Layer& L) { return (L.C
 __device__ __forceinline__ int rq_signed(int x, int m2, long c, int e_packed, int e) {
     const int hi = (int)(((long)x * (long)m2 + c) >> 32);
     const int s = hi + x + (x >> 31);
-    int r;
-    switch (e) {
-        case 0: asm("v_ashrrev_i32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_0 src1_sel:DWORD" : "=v"(r) : "v"(e_packed), "v"(s)); break;
-        case 1: asm("v_ashrrev_i32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_1 src1_sel:DWORD" : "=v"(r) : "v"(e_packed), "v"(s)); break;
-        case 2: asm("v_ashrrev_i32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_2 src1_sel:DWORD" : "=v"(r) : "v"(e_packed), "v"(s)); break;
-        default: asm("v_ashrrev_i32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_3 src1_sel:DWORD" : "=v"(r) : "v"(e_packed), "v"(s)); break;
-    }
-    return r;
+    return ashr_byte(e_packed, s, e);
 }
 
 // MEAN -> FULLY_CONNECTED -> LOGISTIC / DEQUANTIZE for the workgroup's chunks (reference operators #52-#55).

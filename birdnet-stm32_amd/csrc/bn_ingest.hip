@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 
+#include "bn_device.h"
 #include "bn_kernels.h"
 
 // numpy and scipy round after every multiply and after every add; a fused multiply-add would differ in the last bit
@@ -20,14 +21,6 @@
 
 namespace bn {
 namespace {
-
-
-// individually rounded float32 operations (defined under the pragma above, so they never fuse)
-__device__ __forceinline__ float f_add(float a, float b) { return a + b; }
-__device__ __forceinline__ float f_mul(float a, float b) { return a * b; }
-__device__ __forceinline__ float f_div(float a, float b) { return a / b; }
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 template <int FMT>
 __device__ __forceinline__ float pcm_sample(const void* p, long i) {

@@ -16,11 +16,11 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/birdnet_hip.h"
+#include "bn_device.h"
 #include "bn_kernels.h"
 
 namespace bn {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 

@@ -24,7 +24,7 @@ __device__ __forceinline__ float div_by_const(float a, float b, float y) {
 __device__ __forceinline__ int quantise_i8_zp128(float v) {
     int r;
     asm("v_cvt_rpi_i32_f32 %0, %1" : "=v"(r) : "v"(v));
-    return min(max(r, 0), 255) - 128;  // v_med3_i32
+    return min(max(r, 0), 255) - 128;  // one median-of-three instruction
 }
 __device__ __forceinline__ int quantise_i8_any(float v, int zp) {
     const int r = (int32_t)roundf(v) + zp;

@@ -15,6 +15,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bn_device.h"
+
 namespace bn {
 
 __device__ __forceinline__ int32_t srdhm_ref(int32_t a, int32_t b) {
@@ -64,9 +66,18 @@ __device__ __forceinline__ int32_t mbqm_u(int32_t x, int32_t mult, int shift, bo
 __device__ __forceinline__ int32_t clampi(int32_t v, int32_t lo, int32_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // clamp as ONE instruction; lo <= hi.  (The compiler cannot prove lo <= hi for run-time bounds and emits compare + select + min.)
-__device__ __forceinline__ int med3i(int v, int lo, int hi) {
+__device__ __forceinline__ int med3(int v, int lo, int hi) {
     int r;
     asm("v_med3_i32 %0, %1, %2, %3" : "=v"(r) : "v"(v), "v"(lo), "v"(hi));
+    return r;
+}
+__device__ __forceinline__ int perm(int s0, int s1, uint32_t sel) { return (int)__builtin_amdgcn_perm((uint32_t)s0, (uint32_t)s1, sel); }
+// One multiply-accumulate of four packed int8 channels without unpacking: v_dot4_i32_i8
+__device__ __forceinline__ int dot4(int a, int b, int c) { return __builtin_amdgcn_sdot4(a, b, c, false); }
+// first link of a dot4 chain in the three-address form (no move of the bias into the accumulator)
+__device__ __forceinline__ int dot4_first(int a, int b, int c) {
+    int r;
+    asm("v_dot4_i32_i8 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
     return r;
 }
 // the low bytes of four values as one dword (three v_perm_b32)
@@ -75,6 +86,36 @@ __device__ __forceinline__ int pack4(const int (&q)[4]) {
     return (int)__builtin_amdgcn_perm(hi, lo, 0x05040100u);
 }
 
+// q = ((srdhm(x, m) + c1 + sign) >> e), c1 = 2^(e-1) + (zp << e): RoundingDivideByPOT(SRDHM(x, m), e) + zp with the rounding offset and
+// the zero point in one addend
+__device__ __forceinline__ int rq(int x, int m, int c1, int e) {
+    const int v = srdhm_pos(x, m);
+    return (v + c1 + (v >> 31)) >> e;
+}
+
+// Where the clamp's lower bound is at or above the zero point (ReLU / ReLU6 outputs: the packer checks it) a negative v gives a result
+// <= zero point with or without the sign term (v + 2^(e-1) < 2^e) and both clamp to the same bound: (v + c1) >> e,
+// and with the addend folded into the 64-bit multiply-add: ((x*m + 2^30) >> 31 + c1) >> e == (x*m + 2^30 + c1 * 2^31) >> (31 + e)
+// (nested floors) == hi32(x*m + C) >> (e - 1) for e >= 1: v_mad_i64_i32 with a per-channel 64-bit constant C = 2^30 + c1 * 2^31, then ONE
+// arithmetic shift of the high dword — 2 instructions + clamp instead of 5 + clamp.  rq64(c1) builds C; kernels keep (C, e - 1) per channel.
+__device__ __forceinline__ long rq64(int c1) { return ((long)c1 << 31) + 0x40000000L; }
+// The four shifts of a channel quad are packed into the bytes of ONE register (SDWA picks byte `e` as the shift
+// count: no unpacking instruction, three registers less per quad)
+__device__ __forceinline__ int pack_shifts(v4i sh) { return sh.x | (sh.y << 8) | (sh.z << 16) | (sh.w << 24); }
+// v >> byte `e` of `packed`
+__device__ __forceinline__ int ashr_byte(int packed, int v, int e) {
+    int r;
+    switch (e) {  // e is a compile-time constant after unrolling
+        case 0: asm("v_ashrrev_i32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_0 src1_sel:DWORD" : "=v"(r) : "v"(packed), "v"(v)); break;
+        case 1: asm("v_ashrrev_i32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_1 src1_sel:DWORD" : "=v"(r) : "v"(packed), "v"(v)); break;
+        case 2: asm("v_ashrrev_i32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_2 src1_sel:DWORD" : "=v"(r) : "v"(packed), "v"(v)); break;
+        default: asm("v_ashrrev_i32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_3 src1_sel:DWORD" : "=v"(r) : "v"(packed), "v"(v)); break;
+    }
+    return r;
+}
+__device__ __forceinline__ int rq_hi(int x, int m, long c, int e1_packed, int e) {
+    return ashr_byte(e1_packed, (int)(((long)x * (long)m + c) >> 32), e);
+}
 
 // int8 MEAN of `raw_sum` = sum of the P raw bytes of a channel.  Two published forms (oracle/int8_graph.py has both behind mean_form):
 //   integer (default): MultiplyByQuantizedMultiplier(raw_sum - zp_in P, mult, shift) with 1 / P folded into the multiplier (reduce.h);

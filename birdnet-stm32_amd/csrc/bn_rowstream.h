@@ -8,6 +8,7 @@
 // current kGroup are used.
 #pragma once
 #include "../../include/birdnet_hip.h"
+#include "bn_device.h"
 
 // From here to the end of the including translation unit: every float32 operation is rounded on its own.  Both includers want that for
 // their whole file (the specifications they are tested against count the roundings).
@@ -15,14 +16,6 @@
 
 namespace bn {
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef int v4i __attribute__((ext_vector_type(4)));
-
-// individually rounded float32 operations (defined under the pragma above, so they never fuse)
-__device__ __forceinline__ float f_add(float a, float b) { return a + b; }
-__device__ __forceinline__ float f_mul(float a, float b) { return a * b; }
-__device__ __forceinline__ float f_div(float a, float b) { return a / b; }
 
 __host__ __device__ inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 

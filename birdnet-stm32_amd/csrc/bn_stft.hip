@@ -14,6 +14,7 @@
 // frequency-major rows so that the global stores are 64-byte runs.
 #include <cstdlib>
 
+#include "bn_device.h"
 #include "bn_kernels.h"
 #include "bn_quant_in.h"
 
@@ -24,8 +25,6 @@ namespace {
 constexpr int kFT = 16;    // frames per workgroup
 constexpr int kFS = 274;   // floats reserved per frame in the exchange buffer (one component at a time, see the kernel)
 
-typedef float v2f __attribute__((ext_vector_type(2)));
-typedef float v4f __attribute__((ext_vector_type(4)));
 // Complex values live in 64-bit register pairs end to end so that the compiler emits packed-f32 instructions
 // (v_pk_add/mul/fma_f32) with the swizzles folded into op_sel: a 16-point FFT is ~100 vector instructions.
 #define BN_SWAP(a) __builtin_shufflevector(a, a, 1, 0)
@@ -140,11 +139,7 @@ struct MelOut {
 // The 16 lanes that own a frame sit in ONE wave, and every LDS exchange of the FFT stays inside that frame's slice of
 // `xch`, so no workgroup barrier is needed between the passes: LDS instructions of a wave execute in issue order, the
 // compiler only has to keep that order.  Waves of a workgroup therefore drift apart and overlap loads with arithmetic.
-__device__ __forceinline__ void frame_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
+__device__ __forceinline__ void frame_sync() { wave_sync(); }
 
 // reductions over the 16 lanes of a frame (one DPP row): quad swaps, then rotations by 4 and 8 — vector-ALU only, no LDS traffic
 template <int CTRL>
@@ -157,8 +152,7 @@ __device__ __forceinline__ float dpp_f(float v) {
     v = OP(v, dpp_f<0x4E>(v));  /* quad_perm [2,3,0,1] */ \
     v = OP(v, dpp_f<0x124>(v)); /* row_ror:4 */           \
     v = OP(v, dpp_f<0x128>(v)); /* row_ror:8 */
-__device__ __forceinline__ float addf(float a, float b) { return a + b; }
-__device__ __forceinline__ float row16_sum(float v) { BN_ROW16(addf, v) return v; }
+__device__ __forceinline__ float row16_sum(float v) { BN_ROW16(f_add, v) return v; }
 __device__ __forceinline__ float row16_max(float v) { BN_ROW16(fmaxf, v) return v; }
 __device__ __forceinline__ float row16_min(float v) { BN_ROW16(fminf, v) return v; }
 
@@ -207,9 +201,9 @@ __global__ __launch_bounds__(256) void stft512_mag_kernel(StftTables tb, const f
     // kernel, the extra ~100 packed multiply-adds are free next to it.
     //   w[32 n1 + 2 j + e] = 0.25 - 0.25 cos(theta_je + n1 pi/8)        (0.5 * periodic Hann)
     //   t[j + 16 k2]       = -i exp(-i (alpha_j + k2 pi/16))
-    const v4f wb = reinterpret_cast<const v4f*>(tb.window)[j];  // (-0.25 cos th_j0, -0.25 cos th_j1, 0.25 sin th_j0, 0.25 sin th_j1)
+    const f32x4 wb = reinterpret_cast<const f32x4*>(tb.window)[j];  // (-0.25 cos th_j0, -0.25 cos th_j1, 0.25 sin th_j0, 0.25 sin th_j1)
     const v2f wa = {wb.x, wb.y}, wsn = {wb.z, wb.w};
-    const v4f tbase = reinterpret_cast<const v4f*>(tb.tw512)[j];  // (-sin a_j, -cos a_j, -cos a_j, sin a_j)
+    const f32x4 tbase = reinterpret_cast<const f32x4*>(tb.tw512)[j];  // (-sin a_j, -cos a_j, -cos a_j, sin a_j)
     const v2f tp = {tbase.x, tbase.y}, tq = {tbase.z, tbase.w};
 
     // Raw buffer loads through a descriptor that covers exactly this chunk: samples before the chunk (negative offset = huge
@@ -252,7 +246,7 @@ __global__ __launch_bounds__(256) void stft512_mag_kernel(StftTables tb, const f
         {
             // inter-pass twiddles W256^(j k1), k1 = 0..15: powers of w = W256^j built from one table entry per lane by
             // square-and-multiply (at most four roundings deep) instead of sixteen strided gathers
-            const v4f wl = reinterpret_cast<const v4f*>(tb.tw256)[j];
+            const f32x4 wl = reinterpret_cast<const f32x4*>(tb.tw256)[j];
             v2f p[16];
             p[1] = (v2f){wl.x, wl.y};
 #define BN_CM(u, v) cmul(u, v)

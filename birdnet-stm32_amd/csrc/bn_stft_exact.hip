@@ -24,6 +24,7 @@
 //
 // stft512_f64_kernel computes a WHOLE spectrogram that way (every bin a float64 DFT): the public bn_stft_mag_exact, and
 // bn_infer_audio's INT8 route whenever the guarded fast path does not apply (debug plans, layout / kernel A-B options).
+#include "bn_device.h"
 #include "bn_kernels.h"
 #include "bn_quant_in.h"
 #include "bn_exact_dft.h"
@@ -35,14 +36,6 @@ namespace bn {
 namespace {
 
 constexpr int kFT = 16;  // frames per tile (= stft512_mag_kernel's workgroup)
-
-
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ void wave_lds_sync() { wave_sync(); }  // a wave's LDS writes visible to its own lanes: wave-level, no workgroup barrier
 
 __device__ __forceinline__ size_t spec_offset(int W, bool tile_major, int k, int t) {
     return tile_major ? (size_t)(t / kFT) * 257 * kFT + (size_t)k * kFT + (t % kFT) : (size_t)k * W + t;
@@ -132,7 +125,7 @@ __device__ __forceinline__ void f64_tile(F64Lds& L, const F64Regs& R, const floa
             const double2 wv = L.win[lane + 64 * i];
             A[fslot(lane + 64 * i)] = make_double2((double)xs[i][0] * wv.x, (double)xs[i][1] * wv.y);
         }
-        wave_lds_sync();
+        wave_sync();
         double2* src = A;
         double2* dst = Bf;
 #pragma unroll
@@ -153,7 +146,7 @@ __device__ __forceinline__ void f64_tile(F64Lds& L, const F64Regs& R, const floa
             dst[fslot(j0 + Ns)] = make_double2(a1.x + a3.x, a1.y + a3.y);
             dst[fslot(j0 + 2 * Ns)] = make_double2(a0.x - a2.x, a0.y - a2.y);
             dst[fslot(j0 + 3 * Ns)] = make_double2(a1.x - a3.x, a1.y - a3.y);
-            wave_lds_sync();
+            wave_sync();
             double2* tmp = src;
             src = dst;
             dst = tmp;
@@ -182,7 +175,7 @@ __device__ __forceinline__ void f64_tile(F64Lds& L, const F64Regs& R, const floa
                 }
             }
         }
-        wave_lds_sync();  // the next frame overwrites A
+        wave_sync();  // the next frame overwrites A
         }
         if (fi < 3) {
 #pragma unroll

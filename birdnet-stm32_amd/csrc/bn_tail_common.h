@@ -1,5 +1,5 @@
-// bn_tail_common.h — helpers shared by the two fused-tail kernels (bn_i8_tail.hip, bn_i8_tail2.hip): byte permutes, the requantisation
-// forms, and the MEAN -> FULLY_CONNECTED -> head part behind the last block.
+// bn_tail_common.h — helpers shared by the two fused-tail kernels (bn_i8_tail.hip, bn_i8_tail2.hip): the staging of the high-dword
+// requantisation constants (bn_requant.h: rq_hi), and the MEAN -> FULLY_CONNECTED -> head part behind the last block.
 #pragma once
 #include "bn_kernels.h"
 #include "bn_requant.h"
@@ -7,38 +7,6 @@
 namespace bn {
 namespace {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v2i __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ int perm(int s0, int s1, uint32_t sel) { return (int)__builtin_amdgcn_perm((uint32_t)s0, (uint32_t)s1, sel); }
-__device__ __forceinline__ int dot4(int a, int b, int c) { return __builtin_amdgcn_sdot4(a, b, c, false); }
-__device__ __forceinline__ int med3(int v, int lo, int hi) {
-    int r;
-    asm("v_med3_i32 %0, %1, %2, %3" : "=v"(r) : "v"(v), "v"(lo), "v"(hi));
-    return r;
-}
-// RoundingDivideByPOT(SRDHM(x, m), e) + zp with the rounding offset and the zero point in one addend (bn_i8_strip.hip: rq)
-__device__ __forceinline__ int rq(int x, int m, int c1, int e) {
-    const int v = srdhm_pos(x, m);
-    return (v + c1 + (v >> 31)) >> e;
-}
-
-// where the clamp's lower bound is at or above the zero point the sign term is not needed, the addend folds into the 64-bit
-// multiply-add and the result is the HIGH dword shifted by e - 1 (bn_i8_strip.hip: rq_hi; the packer checks the clamp and e >= 1).
-// The four shifts of a channel quad sit in the bytes of one register, SDWA picks byte `e`.
-__device__ __forceinline__ long rq64(int c1) { return ((long)c1 << 31) + 0x40000000L; }
-__device__ __forceinline__ int pack_shifts(v4i sh) { return sh.x | (sh.y << 8) | (sh.z << 16) | (sh.w << 24); }
-__device__ __forceinline__ int rq_hi(int x, int m, long c, int e1_packed, int e) {
-    const int hi = (int)(((long)x * (long)m + c) >> 32);
-    int r;
-    switch (e) {  // e is a compile-time constant after unrolling
-        case 0: asm("v_ashrrev_i32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_0 src1_sel:DWORD" : "=v"(r) : "v"(e1_packed), "v"(hi)); break;
-        case 1: asm("v_ashrrev_i32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_1 src1_sel:DWORD" : "=v"(r) : "v"(e1_packed), "v"(hi)); break;
-        case 2: asm("v_ashrrev_i32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_2 src1_sel:DWORD" : "=v"(r) : "v"(e1_packed), "v"(hi)); break;
-        default: asm("v_ashrrev_i32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_3 src1_sel:DWORD" : "=v"(r) : "v"(e1_packed), "v"(hi)); break;
-    }
-    return r;
-}
 // (multiplier, c1, shift) of the constant block -> (multiplier, C01, C23, packed shifts - 1) in LDS
 __device__ __forceinline__ void stage_rq(v4i* dst, v4i m, v4i c1, v4i sh) {
     const long c[4] = {rq64(c1.x), rq64(c1.y), rq64(c1.z), rq64(c1.w)};
