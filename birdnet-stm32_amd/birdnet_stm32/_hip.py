@@ -33,6 +33,7 @@ EXPORTS = (
     "bn_head_forward", "bn_probe_create", "bn_probe_destroy", "bn_probe_epoch", "bn_probe_loss", "bn_probe_get", "bn_probe_set",
     "bn_short_time_energy", "bn_activity_counts", "bn_search_inv_norms", "bn_search_topk", "bn_augment_inputs",
     "bn_kmeans_assign", "bn_kmeans_accumulate", "bn_kmeans_centroids",
+    "bn_bootstrap_rejections", "bn_bootstrap_counts", "bn_bootstrap_ap",
 )  # fmt: skip
 
 EMB_F32, EMB_I8 = 0, 1  # BN_EMB_* (include/birdnet_hip.h)
@@ -46,6 +47,7 @@ AUGMENT_MAX_MASKS = 4  # BN_AUGMENT_MAX_MASKS
 SEARCH_STEP_ROWS, SEARCH_MIN_WG_STEPS, SEARCH_MAX_WGS = 64, 8, 1024  # how bn_search_topk deals rows to workgroups (include/birdnet_hip.h)
 # bn_kmeans_* (include/birdnet_hip.h): limits, and the constants the centroid tiles, the row steps and the update's segments follow from
 KMEANS_MAX_K, KMEANS_MAX_D = 4096, 2048
+BOOTSTRAP_MAX_N = 32768  # BN_BOOTSTRAP_MAX_N
 KMEANS_LDS_BYTES, KMEANS_MAX_TILE, KMEANS_STEP_ROWS, KMEANS_MIN_WG_STEPS, KMEANS_MAX_WGS, KMEANS_SEGMENT_ROWS = 160 * 1024, 128, 64, 8, 1024, 256
 
 
@@ -155,6 +157,10 @@ def load_library(path: str | None = None):
                                      c_void_p, c_void_p]
     lib.bn_kmeans_accumulate.argtypes = [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]
     lib.bn_kmeans_centroids.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]
+    u64 = ctypes.c_uint64
+    lib.bn_bootstrap_rejections.argtypes = [c_void_p, u64, u64, u64, u64, ctypes.c_uint32, c_int64, c_int64, c_void_p, c_int64, POINTER(c_int64), c_void_p]
+    lib.bn_bootstrap_counts.argtypes = [c_void_p, u64, u64, u64, u64, c_int, c_int, c_void_p, c_void_p, c_void_p]
+    lib.bn_bootstrap_ap.argtypes = [c_void_p, u64, u64, u64, u64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]
     lib.bn_augment_inputs.argtypes = [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int64,
                                       c_void_p, c_void_p]
     lib.bn_host_alloc_pinned.argtypes = [c_void_p, ctypes.c_size_t]

@@ -5,7 +5,8 @@ given, read ``class_names`` from it, collect the test files under ``--data_path_
 run ``evaluate`` and print the metric summary.  ``--benchmark`` writes the reference's JSON report shape
 (``model_path``, ``num_classes``, ``num_files`` (= total chunks, as in the reference), ``metrics``, ``config``)
 and ``--save_csv`` the per-file scores.  ``--confusion_matrix``, ``--det_curve`` (text forms), ``--species_report`` /
-``--n_bootstrap`` (bootstrap AP intervals) and ``--optimize_thresholds`` work as in the reference.  The plot / HTML
+``--n_bootstrap`` (bootstrap AP intervals) and ``--optimize_thresholds`` work as in the reference; with a device runner the
+bootstrap's resamples run on the GPU (``evaluation/bootstrap.py``; ``--bootstrap_backend host`` keeps scikit-learn).  The plot / HTML
 renderings (``--save_cm_plot``, ``--save_det_plot``, ``--report_html``: matplotlib) are outside the accelerated path:
 the command refuses them with a non-zero exit before doing any work, so a script written for the reference fails
 loudly instead of missing an output file.
@@ -44,6 +45,9 @@ def build_parser() -> argparse.ArgumentParser:
                    help="Measure per-chunk inference latency (mean, median, p95, p99)")
     p.add_argument("--species_report", type=str, default="")
     p.add_argument("--n_bootstrap", type=int, default=1000)
+    p.add_argument("--bootstrap_backend", type=str, default="auto", choices=["auto", "host"],
+                   help="Where the bootstrap's resamples run: auto = on the GPU when the runner has a device context (same draws, intervals within "
+                        "2 n 2^-53 of the host's), host = scikit-learn per resample as in the reference")
     p.add_argument("--det_curve", action="store_true", default=False)
     p.add_argument("--save_det_plot", type=str, default="")
     p.add_argument("--report_html", type=str, default="")
@@ -181,7 +185,18 @@ def main(argv=None, runner=None):
         print_ascii_det_curve(far, frr)
     species = None
     if args.species_report or args.benchmark:
-        species = bootstrap_ap_ci(y_true, y_scores, classes, n_bootstrap=args.n_bootstrap)
+        import time
+
+        t_boot = time.perf_counter()
+        boot_ctx = getattr(runner, "ctx", None) if args.bootstrap_backend == "auto" else None
+        if boot_ctx is not None:
+            from birdnet_stm32.evaluation.bootstrap import bootstrap_ap_ci_device
+
+            species = bootstrap_ap_ci_device(y_true, y_scores, classes, n_bootstrap=args.n_bootstrap, ctx=boot_ctx)
+        else:
+            species = bootstrap_ap_ci(y_true, y_scores, classes, n_bootstrap=args.n_bootstrap)
+        print(f"Bootstrap AP intervals ({args.n_bootstrap} resamples x {len(classes)} classes, {'device' if boot_ctx is not None else 'host'}): "
+              f"{time.perf_counter() - t_boot:.3f} s")
         if args.species_report:
             save_species_report_csv(species, args.species_report)
     if args.save_csv:

@@ -212,6 +212,7 @@ void bn_ctx_destroy(bn_ctx* c) {
     if (c->d_rank_work) (void)hipFree(c->d_rank_work);
     if (c->d_search_work) (void)hipFree(c->d_search_work);
     if (c->d_kmeans_work) (void)hipFree(c->d_kmeans_work);
+    if (c->d_boot_work) (void)hipFree(c->d_boot_work);
     delete c;
 }
 
@@ -1034,7 +1035,7 @@ int bn_preload_kernels(bn_ctx* ctx) {
     // copies wait meanwhile).  A caller with idle time before its first batch — the evaluate pipeline while the first files are read — asks here.
     bn::preload_ingest(); bn::preload_stft(); bn::preload_stft_exact(); bn::preload_i8_fused(); bn::preload_i8_strip(); bn::preload_i8_tail2();
     bn::preload_i8_tail(); bn::preload_i8(); bn::preload_i8_pw(); bn::preload_f32(); bn::preload_f32_fused(); bn::preload_f32_strip();
-    bn::preload_f32_pw(); bn::preload_melspec(); bn::preload_sort(); bn::preload_probe(); bn::preload_activity(); bn::preload_search(); bn::preload_augment(); bn::preload_kmeans();
+    bn::preload_f32_pw(); bn::preload_melspec(); bn::preload_sort(); bn::preload_probe(); bn::preload_activity(); bn::preload_search(); bn::preload_augment(); bn::preload_kmeans(); bn::preload_bootstrap();
     return BN_OK;
 }
 
@@ -1053,7 +1054,7 @@ const char* bn_kernel_names(void) {
     return "ingest_resample_kernel\ningest_decimate_kernel\ningest_peak_kernel\ningest_chunks_kernel\nchunk_peaknorm_kernel\npool_scores_kernel\nstft512_mag_kernel\nspec_normalize_kernel\nmelspec_finish_kernel\nf32_mel_kernel\nf32_melfin_kernel\nf32_mag_kernel\nf32_rawfe_kernel\nf32_stem_kernel\nf32_dw_kernel\n"
            "f32_pw_kernel\nf32_pw_ws_kernel\nf32_dwpw_kernel\nf32_dwpw_wave_kernel\nf32_strip_kernel\nf32_front_strip_kernel\nf32_front2_kernel\nf32_pwdw_kernel\nf32_dw_stream_kernel\nf32_front_kernel\nf32_gap_kernel\nf32_gap_dense_kernel\nf32_gap_dense_emb_kernel\nf32_dense_kernel\nf32_segate_kernel\nf32_scale_kernel\nf32_attnpool_kernel\n"
            "i8_quant_kernel\ni8_mel_kernel\ni8_stem_kernel\ni8_dw_kernel\ni8_pw_kernel\ni8_dwpw_kernel\ni8_mel_mfma_kernel\ni8_strip_kernel\ni8_strip_mf_kernel\ni8_front_strip_kernel\ni8_front_kernel\ni8_tail_kernel\ni8_tail_emb_kernel\ni8_tail2_kernel\ni8_tail2_emb_kernel\ni8_mid2_kernel\ni8_mean_kernel\ni8_fc_kernel\ni8_scale_kernel\ni8_maxnorm_kernel\ni8_rawfe_kernel\ni8_pwdw_kernel\ni8_dw_stream_kernel\ni8_stem_stream_kernel\ni8_segate_kernel\ni8_pw_wave_kernel\ni8_pw_lds_kernel\ni8_attnpool_kernel\n"
-           "i8_head_kernel\ni8_head_softmax_kernel\nemb_store_kernel\nprobe_fwd_kernel\nprobe_dw_kernel\nprobe_reduce_kernel\nprobe_update_kernel\nprobe_loss_sum_kernel\nste_kernel\nactivity_count_kernel\nsearch_inv_norms_kernel\nsearch_score_kernel\nsearch_merge_kernel\naugment_kernel\nkmeans_assign_kernel\nkmeans_keys_kernel\nkmeans_offsets_kernel\nkmeans_segments_kernel\nkmeans_partial_kernel\nkmeans_fold_kernel\nkmeans_scale_kernel";
+           "i8_head_kernel\ni8_head_softmax_kernel\nemb_store_kernel\nprobe_fwd_kernel\nprobe_dw_kernel\nprobe_reduce_kernel\nprobe_update_kernel\nprobe_loss_sum_kernel\nste_kernel\nactivity_count_kernel\nsearch_inv_norms_kernel\nsearch_score_kernel\nsearch_merge_kernel\naugment_kernel\nkmeans_assign_kernel\nkmeans_keys_kernel\nkmeans_offsets_kernel\nkmeans_segments_kernel\nkmeans_partial_kernel\nkmeans_fold_kernel\nkmeans_scale_kernel\nbootstrap_table_kernel\nbootstrap_reject_kernel\nbootstrap_prepare_kernel\nbootstrap_resample_kernel";
 }
 
 }  // extern "C"
@@ -1413,6 +1414,87 @@ int bn_augment_inputs(bn_ctx* ctx, const float* d_x, int64_t n_rows, int F, int 
     if (o0 < x1 && x0 < o1) return fail(BN_ERR_ARG, "d_out overlaps d_x");
     if (m == 0) return BN_OK;
     bn::launch_augment(d_x, (long)n_rows, W, (int)E, d_nsrc, d_src, d_gain, d_fmask, nf, d_tmask, nt, (long)m, d_out, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return BN_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------- bootstrap (bn_bootstrap.hip)
+namespace {
+
+int bootstrap_rows_check(int n) {
+    if (n < 1 || n > BN_BOOTSTRAP_MAX_N) return fail(BN_ERR_ARG, "n=%d outside 1..%d", n, BN_BOOTSTRAP_MAX_N);
+    return BN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bn_bootstrap_rejections(bn_ctx* ctx, uint64_t state_hi, uint64_t state_lo, uint64_t inc_hi, uint64_t inc_lo, uint32_t bound, int64_t p_begin,
+                            int64_t p_end, int64_t* h_positions, int64_t capacity, int64_t* h_count, void* stream) {
+    if (int rc = check_device(ctx)) return rc;
+    if (!h_count || (capacity > 0 && !h_positions)) return fail(BN_ERR_ARG, "null pointer");
+    *h_count = 0;
+    if (bound < 1) return fail(BN_ERR_ARG, "bound must be 1 .. 2^32 - 1");
+    if (p_begin < 0 || p_end < p_begin || p_end - p_begin > (1LL << 40) || p_end > (1LL << 62)) return fail(BN_ERR_ARG, "bad raw range [%lld, %lld)", (long long)p_begin, (long long)p_end);
+    if (capacity < 0 || capacity > 0x7fffffffLL) return fail(BN_ERR_ARG, "bad capacity %lld", (long long)capacity);
+    if ((0x100000000ULL - bound) % bound == 0 || p_end == p_begin) return BN_OK;   // nothing is ever rejected
+    hipStream_t s = (hipStream_t)stream;
+    const size_t need = bn::bootstrap_reject_workspace((long)capacity);
+    if (int rc = grow_device_buffer(&ctx->d_boot_work, &ctx->boot_work_bytes, need, need, s, BN_ERR_NOMEM, "bootstrap")) return rc;
+    const unsigned long long gen[4] = {state_hi, state_lo, inc_hi, inc_lo};
+    bn::launch_bootstrap_reject(gen, bound, p_begin, p_end, ctx->d_boot_work, (long)capacity, s);
+    HIP_TRY(hipGetLastError());
+    unsigned found = 0;
+    HIP_TRY(hipMemcpyAsync(&found, (char*)ctx->d_boot_work + 2048, sizeof found, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    *h_count = found;
+    if ((int64_t)found > capacity) return fail(BN_ERR_NOMEM, "%u rejected positions, the list holds %lld", found, (long long)capacity);
+    if (found) {
+        HIP_TRY(hipMemcpyAsync(h_positions, (char*)ctx->d_boot_work + 2048 + 256, (size_t)found * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    return BN_OK;
+}
+
+int bn_bootstrap_counts(bn_ctx* ctx, uint64_t state_hi, uint64_t state_lo, uint64_t inc_hi, uint64_t inc_lo, int n, int B, const int64_t* d_ranges,
+                        uint32_t* d_counts, void* stream) {
+    if (int rc = check_device(ctx)) return rc;
+    if (int rc = bootstrap_rows_check(n)) return rc;
+    if (B < 0) return fail(BN_ERR_ARG, "bad resample count %d", B);
+    if (B == 0) return BN_OK;
+    if (!d_ranges || !d_counts) return fail(BN_ERR_ARG, "null device pointer");
+    if ((uintptr_t)d_ranges % 8 || (uintptr_t)d_counts % 4) return fail(BN_ERR_ARG, "d_ranges must be 8-byte aligned, d_counts 4-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t need = bn::bootstrap_ap_workspace(n, 0);
+    if (int rc = grow_device_buffer(&ctx->d_boot_work, &ctx->boot_work_bytes, need, need, s, BN_ERR_NOMEM, "bootstrap")) return rc;
+    const unsigned long long gen[4] = {state_hi, state_lo, inc_hi, inc_lo};
+    if (!bn::launch_bootstrap_counts(gen, n, B, (const long long*)d_ranges, d_counts, ctx->d_boot_work, s))
+        return fail(BN_ERR_DEVICE, "the resample kernel's LDS request was refused");
+    HIP_TRY(hipGetLastError());
+    return BN_OK;
+}
+
+int bn_bootstrap_ap(bn_ctx* ctx, uint64_t state_hi, uint64_t state_lo, uint64_t inc_hi, uint64_t inc_lo, int n, int n_classes, const float* d_scores,
+                    const uint8_t* d_truth, const int32_t* d_cols, const int32_t* d_classes, int n_selected, int B, const int64_t* d_ranges, double* d_ap,
+                    void* stream) {
+    if (int rc = check_device(ctx)) return rc;
+    if (int rc = bootstrap_rows_check(n)) return rc;
+    if (n_classes < 1 || (int64_t)n * n_classes > 0x3fffffffLL) return fail(BN_ERR_ARG, "bad score matrix %d x %d", n, n_classes);
+    if (n_selected < 0 || n_selected > 65535 || B < 0 || (int64_t)n_selected * B > 0x7fffffffLL)
+        return fail(BN_ERR_ARG, "bad selection: %d classes x %d resamples", n_selected, B);
+    if (n_selected == 0 || B == 0) return BN_OK;
+    if (!d_scores || !d_truth || !d_cols || !d_classes || !d_ranges || !d_ap) return fail(BN_ERR_ARG, "null device pointer");
+    if ((uintptr_t)d_scores % 4 || (uintptr_t)d_cols % 4 || (uintptr_t)d_classes % 4 || (uintptr_t)d_ranges % 8 || (uintptr_t)d_ap % 8)
+        return fail(BN_ERR_ARG, "float32 / int32 arrays must be 4-byte aligned, d_ranges and d_ap 8-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t need = bn::bootstrap_ap_workspace(n, n_selected);
+    if (int rc = grow_device_buffer(&ctx->d_boot_work, &ctx->boot_work_bytes, need, need, s, BN_ERR_NOMEM, "bootstrap")) return rc;
+    const unsigned long long gen[4] = {state_hi, state_lo, inc_hi, inc_lo};
+    if (!bn::launch_bootstrap_ap(gen, n, n_classes, d_scores, d_truth, d_cols, d_classes, n_selected, B, (const long long*)d_ranges, d_ap, ctx->d_boot_work, s))
+        return fail(BN_ERR_DEVICE, "the resample kernel's LDS request was refused");
     HIP_TRY(hipGetLastError());
     return BN_OK;
 }

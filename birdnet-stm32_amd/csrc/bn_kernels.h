@@ -473,7 +473,7 @@ void launch_i8_dwpw(const DwPw8Args& a, hipStream_t s);
 // One per source file with kernels: load that file's device code object now (bn_preload_kernels)
 void preload_f32(); void preload_f32_fused(); void preload_f32_pw(); void preload_f32_strip(); void preload_i8(); void preload_i8_fused();
 void preload_i8_pw(); void preload_i8_strip(); void preload_i8_tail(); void preload_i8_tail2(); void preload_ingest(); void preload_melspec();
-void preload_stft(); void preload_stft_exact(); void preload_sort(); void preload_probe(); void preload_activity(); void preload_search(); void preload_augment(); void preload_kmeans();
+void preload_stft(); void preload_stft_exact(); void preload_sort(); void preload_probe(); void preload_activity(); void preload_search(); void preload_augment(); void preload_kmeans(); void preload_bootstrap();
 
 // bn_probe.hip: a classifier head on embeddings (bn_head_forward) and its training step (bn_probe_*)
 struct ProbeFwdArgs {
@@ -572,6 +572,15 @@ size_t kmeans_accumulate_workspace(long n, int D, int K);
 bool launch_kmeans_accumulate(const void* rows, bool i8, long n, int D, int zp, const float* row_inv, const int* label, int K, int accumulate, float* sums,
                               long long* counts, void* d_work, size_t work_bytes, hipStream_t s);
 void launch_kmeans_centroids(const float* sums, const long long* counts, int K, int D, float* cent, float* cent_inv, hipStream_t s);
+
+// bn_bootstrap.hip: numpy's bounded draws reproduced on the device and the average precision of every resample (bn_bootstrap_*);
+// gen = (state.hi, state.lo, inc.hi, inc.lo) of the PCG64
+size_t bootstrap_reject_workspace(long capacity);
+size_t bootstrap_ap_workspace(int n, int n_sel);
+void launch_bootstrap_reject(const unsigned long long gen[4], unsigned n, long long p_begin, long long p_end, void* d_work, long capacity, hipStream_t s);
+bool launch_bootstrap_counts(const unsigned long long gen[4], int n, int B, const long long* d_ranges, unsigned* d_counts, void* d_work, hipStream_t s);   // false: the runtime refused the LDS request
+bool launch_bootstrap_ap(const unsigned long long gen[4], int n, int C, const float* d_scores, const unsigned char* d_truth, const int* d_cols,
+                         const int* d_classes, int n_sel, int B, const long long* d_ranges, double* d_ap, void* d_work, hipStream_t s);
 
 // bn_augment.hip: mixup and SpecAugment over resident model-input rows of E = F * W floats (bn_augment_inputs)
 void launch_augment(const float* x, long n_rows, int W, int E, const int* nsrc, const int* src, const float* gain, const int* fmask, int nf,

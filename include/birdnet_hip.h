@@ -487,6 +487,40 @@ BN_API int bn_kmeans_accumulate(bn_ctx* ctx, const void* d_rows, int dtype, int6
 BN_API int bn_kmeans_centroids(bn_ctx* ctx, const float* d_sums, const int64_t* d_counts, int K, int D, float* d_centroids, float* d_cent_inv,
                         void* stream);
 
+/* ---- Bootstrap of the per-class average precision (csrc/bn_bootstrap.hip) -----------------------------------------------------------
+ * (reference: birdnet_stm32/evaluation/metrics.py:239-318 `bootstrap_ap_ci`: one np.random.default_rng(seed) consumed class by class,
+ * rng.integers(0, n, size=n) per resample, sklearn's average_precision_score on the picked rows.)  The draws are numpy's own, reproduced on
+ * the device; birdnet_stm32/evaluation/bootstrap.py restates them and is the specification.  The generator is a PCG64 given as
+ * (state_hi, state_lo, inc_hi, inc_lo), the two 128-bit integers of `rng.bit_generator.state`, with no spare 32-bit half.  Its 32-bit
+ * stream is indexed by RAW POSITION: 2 q is the low half of the q-th next 64-bit output, 2 q + 1 the high half.  A draw below `bound` is
+ * Lemire's: m = x * bound, rejected when (m mod 2^32) < (2^32 - bound) mod bound, else m >> 32.  A resample is a raw range [p0, p1) that
+ * holds its n accepted values; rejected values inside it are skipped.
+ *   BN_BOOTSTRAP_MAX_N   rows per class: a multiplicity is <= n, so two of them share a 32-bit LDS word and the counters of a workgroup take
+ *                        64 KiB of the CU's 160 KiB. */
+#define BN_BOOTSTRAP_MAX_N 32768
+
+/* The rejection scan (reference :286 `rng.integers`, numpy's buffered_bounded_lemire_uint32): *h_count = how many raw positions in
+ * [p_begin, p_end) hold a value that `bound` rejects, h_positions[0 .. *h_count) those positions in NO particular order (host memory; the call
+ * waits for the stream).  More than `capacity` of them: BN_ERR_NOMEM, *h_count still set, h_positions untouched.  A bound that divides 2^32
+ * rejects nothing and launches nothing.  0 <= p_begin <= p_end, p_end - p_begin <= 2^40. */
+BN_API int bn_bootstrap_rejections(bn_ctx* ctx, uint64_t state_hi, uint64_t state_lo, uint64_t inc_hi, uint64_t inc_lo, uint32_t bound,
+                            int64_t p_begin, int64_t p_end, int64_t* h_positions, int64_t capacity, int64_t* h_count, void* stream);
+/* d_counts [B, n] uint32: how often resample b draws row i (reference :286, np.bincount of the picked indices), for the resamples whose raw
+ * ranges are d_ranges [B, 2] int64 (p0, p1).  1 <= n <= BN_BOOTSTRAP_MAX_N.  The kernel cannot trust the device table: a range is clipped to
+ * 2 n + 64 positions, so a bad one gives wrong counts, never a long loop or a stray access. */
+BN_API int bn_bootstrap_counts(bn_ctx* ctx, uint64_t state_hi, uint64_t state_lo, uint64_t inc_hi, uint64_t inc_lo, int n, int B,
+                        const int64_t* d_ranges, uint32_t* d_counts, void* stream);
+/* d_ap [n_selected, B] float64: the average precision (reference :287-293, sklearn average_precision_score) of resample b of class
+ * d_classes[j], NaN where the reference drops the resample (no positive or no negative among the picked rows).
+ *   d_scores [n, n_classes] float32, finite; d_truth [n, n_classes] uint8, 0 or 1; d_cols [n_classes, n] int32 from bn_rank_orders;
+ *   d_classes [n_selected] int32 column indices; d_ranges [n_selected * B, 2] int64, class-major.
+ * Each term (tps / K - tps_prev / K) * (tps / seen) is the float64 expression the library evaluates, bit for bit; the terms are summed in a
+ * fixed order that is not numpy's pairwise one: |d_ap - library| <= 2 n 2^-53.  No floating-point atomics.  Nothing synchronises with the
+ * host inside the call unless the context's workspace has to grow. */
+BN_API int bn_bootstrap_ap(bn_ctx* ctx, uint64_t state_hi, uint64_t state_lo, uint64_t inc_hi, uint64_t inc_lo, int n, int n_classes,
+                    const float* d_scores, const uint8_t* d_truth, const int32_t* d_cols, const int32_t* d_classes, int n_selected, int B,
+                    const int64_t* d_ranges, double* d_ap, void* stream);
+
 /* ---- Probe augmentation: mixup and SpecAugment over resident model inputs (csrc/bn_augment.hip) --------------------------------------
  * (reference: audio/augmentation.py:10-120 as data/generator.py:169-170 and :406-418 apply them: every sample is masked in the loader, the
  * batch is mixed afterwards.)  d_x holds n_rows un-augmented rows of E = F * W float32 (the raw frontend: F = 1, W = T).  Output row r:
