@@ -5,7 +5,9 @@ The backbone runs once over all files (``embed``'s device path), the head is tra
 (``training/linear_probe.py``) and written as ``<output>.npz`` with ``<output>_labels.txt``, ``<output>_model_config.json`` and
 ``<output>_history.csv``.  ``analyze --head <output>.npz`` then reports those classes in recordings.  With ``--mixup_probability`` or
 ``--spec_augment`` the training rows' model inputs stay on the device and every epoch trains on fresh embeddings of augmented rows
-(``training/augment.py``).
+(``training/augment.py``).  With ``--tune`` the learning rate, dropout, label smoothing, optimizer, weight decay and gradient clip are searched:
+``--n_trials`` heads train at once on the device (``training/tune.py``), the one with the lowest validation loss is written, and
+``<output>_tune.json`` lists them all.
 """
 
 from __future__ import annotations
@@ -27,6 +29,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--weight_decay", type=float, default=0.0, help="Weight decay (adamw only)")
     p.add_argument("--grad_clip", type=float, default=1.0, help="Gradient clipping by global norm (0 to disable)")
     p.add_argument("--dropout", type=float, default=0.5, help="Dropout rate in front of the head")
+    p.add_argument("--label_smoothing", type=float, default=0.0,
+                   help="Label smoothing of the training loss, in [0, 1); 0 = off (the default here; the reference's `train` defaults to 0.1).  "
+                        "The validation loss is never smoothed")
     p.add_argument("--val_split", type=float, default=0.2, help="Validation split ratio (by file)")
     p.add_argument("--patience", type=int, default=10, help="Early stopping: epochs without a better validation loss")
     p.add_argument("--max_duration", type=float, default=30, help="Seconds read from the start of each file")
@@ -45,6 +50,12 @@ def build_parser() -> argparse.ArgumentParser:
                         "reference unless --no_spec_augment).  Spectrogram frontends only: a raw-frontend model gets no masks")
     p.add_argument("--freq_mask_max", type=int, default=8, help="With --spec_augment: widest frequency mask in bins (the reference's default)")
     p.add_argument("--time_mask_max", type=int, default=25, help="With --spec_augment: widest time mask in frames (the reference's default)")
+    p.add_argument("--tune", action="store_true",
+                   help="Search learning rate, dropout, label smoothing, optimizer, weight decay and gradient clip: --n_trials heads train at once, "
+                        "trial 0 with this command line's own values; the head with the lowest validation loss is written (no retraining) and "
+                        "<output>_tune.json lists every trial.  Needs --val_split > 0; not with --mixup_probability or --spec_augment")
+    p.add_argument("--n_trials", type=int, default=20, help="With --tune: number of trials, 1..64")
+    p.add_argument("--tune_seed", type=int, default=None, help="With --tune: seed of the trials' draws (default: --seed)")
     p.add_argument("--seed", type=int, default=42, help="Seed of the file shuffle, the initial weights, the batches and the dropout mask")
     p.add_argument("--max_batch", type=int, default=4096, help="Workspace size in chunks = inference slice of the device pipeline")
     p.add_argument("--device", type=int, default=0, help="MI355X index")
@@ -61,7 +72,7 @@ def main(argv=None, runner=None):
         selection_from_args(args)   # (bad selection flags are refused before anything is loaded, as `embed` does)
         from birdnet_stm32.training.linear_probe import augmentation_from_args
 
-        augmentation_from_args(args)   # (and bad augmentation flags)
+        augmentation_from_args(args)   # (and bad augmentation flags; run_linear_probe refuses bad --tune / --label_smoothing combinations first thing)
         return run_linear_probe(args, runner=runner)
     except (ValueError, FileNotFoundError) as exc:
         raise SystemExit(f"error: {exc}") from None

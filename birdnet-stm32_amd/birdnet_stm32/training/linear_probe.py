@@ -6,6 +6,8 @@ on the ``[N, D]`` matrix, which stays on the device for the whole fit (``csrc/bn
 
 * ``fit_probe``            the device fit,
 * ``fit_probe_reference``  the same procedure in numpy: the specification the device code is tested against,
+* ``fit_probe_sweep``      many heads with different hyperparameters trained at once on the device (``csrc/bn_probe_sweep.hip``, C ABI
+  ``bn_probe_sweep_*``; ``training/tune.py`` draws the trials), and ``fit_probe_sweep_reference``, a loop of ``fit_probe_reference``,
 * ``fit_probe_augmented``  the device fit on fresh embeddings per epoch: mixup and SpecAugment over resident model inputs
   (``training/augment.py``, ``csrc/bn_augment.hip``), and ``fit_probe_augmented_reference``, the same loop in numpy,
 * ``ProbeHead``            the result: ``W [D, C]``, ``b [C]``, activation, class names; ``save`` / ``load`` (plain ``.npz``), ``predict``,
@@ -13,7 +15,8 @@ on the ``[N, D]`` matrix, which stays on the device for the whole fit (``csrc/bn
 
 The procedure (both implementations): Glorot-uniform ``W`` from ``default_rng(seed)``, zero ``b``; per epoch a permutation from
 ``default_rng([seed, epoch])`` cut into batches (the last one short); per step dropout by a counter-based hash, logits, sigmoid + binary
-cross-entropy or softmax + categorical cross-entropy (Keras definitions, probabilities clipped to ``[1e-7, 1 - 1e-7]`` in the loss only),
+cross-entropy or softmax + categorical cross-entropy (Keras definitions, probabilities clipped to ``[1e-7, 1 - 1e-7]`` in the loss only;
+with ``label_smoothing`` the training loss and its gradient see ``smooth_targets``, the validation loss the targets as they are),
 clip by global norm, Adam / AdamW / SGD-with-momentum (Keras definitions) under a cosine schedule to zero; validation loss per epoch,
 early stopping with the best weights restored (Keras ``EarlyStopping(patience, restore_best_weights=True)``).
 """
@@ -81,9 +84,38 @@ def epoch_permutation(seed: int, epoch: int, n: int) -> np.ndarray:
 
 def step_sizes(learning_rate: float, t: int, total_steps: int) -> tuple[float, float]:
     """``(lr_t, alpha_t)`` of global step ``t`` (0-based): cosine decay to zero over ``total_steps`` (Keras ``CosineDecay(alpha=0)``) and
-    Adam's step size with the bias correction folded in.  Computed in float64 (the device code does the same on the host)."""
+    Adam's step size with the bias correction folded in.  Computed in float64 (the device code does the same on the host).  This is the
+    restatement's schedule; ``device_step_sizes`` below is its twin with the operations in ``bn_probe_epoch``'s order, which a sweep uploads:
+    the two agree to the last bit or two of the float64, and a change to the schedule goes into both (and into ``bn_probe_epoch``)."""
     lr_t = float(np.float32(learning_rate)) * 0.5 * (1.0 + math.cos(math.pi * min(t, total_steps) / total_steps))
     return lr_t, lr_t * math.sqrt(1.0 - BETA_2 ** (t + 1)) / (1.0 - BETA_1 ** (t + 1))
+
+
+def device_step_sizes(learning_rates, t0: int, steps: int, total_steps: int) -> np.ndarray:
+    """``[steps, T, 2]`` float32: ``(lr_t, alpha_t)`` of global steps ``t0 .. t0 + steps - 1`` for ``T`` learning rates, the table a sweep
+    uploads per epoch.  ``step_sizes`` with the operations in the order ``bn_probe_epoch`` has them on the host (``pi * (t / total)`` where
+    ``step_sizes`` has ``(pi * t) / total``: the two can differ in the last bit of the float64, and a sweep's trial must have a single
+    fit's bits, not just its procedure).  ``cos``, ``pow`` and ``sqrt`` are the C library's through ``math``, one call per step."""
+    lr = np.asarray([float(np.float32(v)) for v in learning_rates], np.float64) * 0.5
+    cosf, num, den = np.empty(steps), np.empty(steps), np.empty(steps)
+    for i in range(steps):
+        t = t0 + i
+        cosf[i] = 1.0 + math.cos(math.pi * (float(min(t, total_steps)) / float(total_steps)))
+        num[i] = math.sqrt(1.0 - math.pow(BETA_2, float(t + 1)))
+        den[i] = 1.0 - math.pow(BETA_1, float(t + 1))
+    lr_t = lr[None, :] * cosf[:, None]
+    return np.stack([lr_t, lr_t * num[:, None] / den[:, None]], axis=2).astype(np.float32)
+
+
+def smooth_targets(Y: np.ndarray, label_smoothing: float, activation: str) -> np.ndarray:
+    """Keras' label smoothing in ``Y``'s dtype: ``y (1 - eps) + 0.5 eps`` (sigmoid) or ``y (1 - eps) + eps / C`` (softmax), with ``eps`` the
+    float32 the C ABI takes.  The operation order is the forward kernel's (``csrc/bn_probe_step.h``): ``keep = 1 - eps`` and
+    ``add = 0.5 * eps`` or ``eps / C`` first, then ``(y * keep) + add``, each operation rounded in the dtype (no fused multiply-add)."""
+    dt = Y.dtype.type
+    eps = dt(np.float32(label_smoothing))
+    keep = dt(1.0) - eps
+    add = eps / dt(Y.shape[1]) if activation == "softmax" else dt(0.5) * eps
+    return Y * keep + add
 
 
 def head_scores(X: np.ndarray, W: np.ndarray, b: np.ndarray, activation: str) -> np.ndarray:
@@ -139,6 +171,12 @@ def _check_fit_args(X, Y, activation, optimizer, batch_size, dropout, epochs):
         raise ValueError("dropout must be in [0, 1)")
     if int(epochs) < 1:
         raise ValueError("epochs must be >= 1")
+
+
+def _check_label_smoothing(label_smoothing):
+    if not 0.0 <= float(label_smoothing) < 1.0:
+        raise ValueError("label_smoothing must be in [0, 1)")
+    return float(label_smoothing)
 
 
 def _fit_loop(backend, n: int, epochs: int, batch: int, seed: int, patience: int, has_val: bool) -> dict:
@@ -283,6 +321,8 @@ class _NumpyBackend:
             xd = np.concatenate([self.X[idx] * dropout_mask(c["seed"], self.t, B, D, c["dropout"], dt), np.ones((B, 1), dt)], axis=1)
             P = head_scores(xd[:, :D], self.P[:D], self.P[D], c["activation"])
             y = self.Y[idx]
+            if c.get("label_smoothing", 0.0) > 0:
+                y = smooth_targets(y, c["label_smoothing"], c["activation"])
             losses.append(float(probe_loss(P, y, c["activation"])))
             G = (P - y) / dt(B if c["activation"] == "softmax" else B * y.shape[1])
             g = clip_by_global_norm(xd.T @ G, c["clipnorm"])
@@ -303,16 +343,18 @@ class _NumpyBackend:
 
 
 def fit_probe_reference(X, Y, X_val=None, Y_val=None, *, activation="sigmoid", epochs=50, batch_size=32, learning_rate=1e-3, optimizer="adam",
-                        weight_decay=0.0, clipnorm=1.0, dropout=0.5, patience=10, seed=42, dtype=np.float64, class_names=None) -> ProbeHead:
+                        weight_decay=0.0, clipnorm=1.0, dropout=0.5, patience=10, seed=42, dtype=np.float64, class_names=None,
+                        label_smoothing=0.0) -> ProbeHead:
     """The procedure of ``fit_probe`` in numpy, all arithmetic in ``dtype``.  ``history["W"]`` / ``["b"]`` keep the result in ``dtype``."""
     X, Y = np.asarray(X), np.asarray(Y)
     _check_fit_args(X, Y, activation, optimizer, batch_size, dropout, epochs)
+    label_smoothing = _check_label_smoothing(label_smoothing)
     n, D = X.shape
     batch = min(int(batch_size), n)
     has_val = X_val is not None and len(X_val) > 0
     W0, b0 = init_head(D, Y.shape[1], seed)
     cfg = dict(activation=activation, optimizer=optimizer, batch=batch, seed=int(seed), dropout=float(dropout), clipnorm=float(np.float32(clipnorm)),
-               lr=float(learning_rate), weight_decay=float(weight_decay), total=int(epochs) * math.ceil(n / batch))
+               lr=float(learning_rate), weight_decay=float(weight_decay), total=int(epochs) * math.ceil(n / batch), label_smoothing=label_smoothing)
     be = _NumpyBackend(X.astype(dtype), Y.astype(dtype), np.asarray(X_val).astype(dtype) if has_val else None,
                        np.asarray(Y_val).astype(dtype) if has_val else None, W0, b0, cfg, np.dtype(dtype).type)
     history = _fit_loop(be, n, int(epochs), batch, int(seed), int(patience), has_val)
@@ -389,14 +431,19 @@ class _DeviceBackend:
 
 
 def fit_probe(ctx_or_runner, X, Y, X_val=None, Y_val=None, *, activation="sigmoid", epochs=50, batch_size=32, learning_rate=1e-3, optimizer="adam",
-              weight_decay=0.0, clipnorm=1.0, dropout=0.5, patience=10, seed=42, class_names=None) -> ProbeHead:
+              weight_decay=0.0, clipnorm=1.0, dropout=0.5, patience=10, seed=42, class_names=None, label_smoothing=0.0) -> ProbeHead:
     """Train ``scores = act(dropout(x) W + b)`` on embedding rows ``X [N, D]`` with targets ``Y [N, C]`` (float: one-hot, multi-hot or
     all-zero rows) on the device.  ``X`` / ``Y`` may be numpy arrays or CUDA tensors; they stay on the device for the whole fit, per epoch
     the host uploads one permutation and reads back the per-step losses.  The defaults are the reference CLI's.  The same inputs and seed
-    give the same bits on every run."""
+    give the same bits on every run.  ``label_smoothing > 0`` (``smooth_targets``) trains through the sweep's kernels as a sweep of one trial."""
     from birdnet_stm32 import _hip
 
     _check_fit_args(X, Y, activation, optimizer, batch_size, dropout, epochs)
+    if _check_label_smoothing(label_smoothing) > 0:
+        trial = ProbeTrial(learning_rate=learning_rate, optimizer=optimizer, weight_decay=weight_decay, clipnorm=clipnorm, dropout=dropout,
+                           label_smoothing=label_smoothing)
+        return fit_probe_sweep(ctx_or_runner, X, Y, X_val, Y_val, [trial], activation=activation, epochs=epochs, batch_size=batch_size, patience=patience,
+                               seed=seed, class_names=class_names).heads[0]
     n, D = int(X.shape[0]), int(X.shape[1])
     C = int(Y.shape[1])
     if not (1 <= D <= _hip.PROBE_MAX_D and 1 <= C <= _hip.PROBE_MAX_C):
@@ -415,6 +462,197 @@ def fit_probe(ctx_or_runner, X, Y, X_val=None, Y_val=None, *, activation="sigmoi
     finally:
         be.close()
     return ProbeHead(W, b, activation, list(class_names or []), history)
+
+
+# -- many trials at once ---------------------------------------------------------------------------------------------------------------
+@dataclass(frozen=True)
+class ProbeTrial:
+    """The hyperparameters that differ between the trials of a sweep (the reference's search space, training/tuner.py)."""
+
+    learning_rate: float = 1e-3
+    optimizer: str = "adam"
+    weight_decay: float = 0.0
+    clipnorm: float = 1.0
+    dropout: float = 0.5
+    label_smoothing: float = 0.0
+
+    def __post_init__(self):
+        if self.optimizer not in OPTIMIZERS:
+            raise ValueError(f"optimizer must be one of {OPTIMIZERS}, not {self.optimizer!r}")
+        if not float(self.learning_rate) >= 0 or not float(self.weight_decay) >= 0 or not float(self.clipnorm) >= 0:
+            raise ValueError("learning_rate, weight_decay and clipnorm must be >= 0")
+        if not 0.0 <= float(self.dropout) < 1.0:
+            raise ValueError("dropout must be in [0, 1)")
+        _check_label_smoothing(self.label_smoothing)
+
+    def fit_kwargs(self) -> dict:
+        """The trial as keyword arguments of ``fit_probe`` / ``fit_probe_reference``."""
+        return dict(learning_rate=float(self.learning_rate), optimizer=self.optimizer, weight_decay=float(self.weight_decay), clipnorm=float(self.clipnorm),
+                    dropout=float(self.dropout), label_smoothing=float(self.label_smoothing))
+
+
+@dataclass
+class SweepResult:
+    """One ``ProbeHead`` per trial (``history`` as ``fit_probe``'s) and ``best``: the trial with the smallest best-epoch validation loss,
+    the lower index on a tie; ``None`` without validation rows."""
+
+    heads: list
+    trials: list
+    best: int | None = None
+
+    @property
+    def best_head(self) -> ProbeHead:
+        return self.heads[self.best if self.best is not None else 0]
+
+
+def _best_trial(heads: list) -> int | None:
+    vals = [min(h.history["val_loss"]) if h.history.get("best_epoch") is not None else math.inf for h in heads]
+    return int(np.argmin(vals)) if vals and min(vals) < math.inf else None
+
+
+def _check_trials(trials) -> list:
+    trials = list(trials)
+    if not trials or not all(isinstance(t, ProbeTrial) for t in trials):
+        raise ValueError("trials must be a non-empty list of ProbeTrial")
+    return trials
+
+
+class _SweepBackend(_DeviceBackend):
+    """``bn_probe_sweep_*`` over resident ``X`` / ``Y``: every trial of the sweep takes the same step in the same launches."""
+
+    def __init__(self, ctx, X, Y, Xv, Yv, W, b, cfg, trials):
+        import ctypes
+
+        import torch
+
+        from birdnet_stm32 import _hip
+
+        self.torch, self.hip, self.ctx, self.cfg, self.trials = torch, _hip, ctx, cfg, trials
+        self.dev = torch.device(f"cuda:{ctx.device}")
+        self.X, self.Y, self.Xv, self.Yv = (self._dev(a) for a in (X, Y, Xv, Yv))
+        self.W, self.b = self._dev(W), self._dev(b)
+        self.n, self.D = self.X.shape
+        self.C, self.T = self.Y.shape[1], len(trials)
+        self.steps = math.ceil(self.n / cfg["batch"])
+        self.step_loss = torch.empty((self.steps, self.T), dtype=torch.float32, device=self.dev)
+        self.val = torch.empty(self.T, dtype=torch.float32, device=self.dev)
+        self.t = 0
+        rows = (_hip.ProbeTrialStruct * self.T)(*[_hip.ProbeTrialStruct(_hip.PROBE_OPTIMIZERS[t.optimizer], t.learning_rate, t.weight_decay, t.clipnorm,
+                                                                        t.dropout, t.label_smoothing) for t in trials])
+        h = ctypes.c_void_p()
+        with torch.cuda.device(self.dev):
+            _hip.check(ctx.lib.bn_probe_sweep_create(ctx.handle, self.D, self.C, _hip.PROBE_ACTIVATIONS[cfg["activation"]], self.T, rows, cfg["seed"] & 0xFFFFFFFF,
+                                                     cfg["total"], self.W.data_ptr(), self.b.data_ptr(), ctypes.byref(h), self._stream()))
+        self.handle = h
+
+    def _mask(self, mask):
+        return self.torch.from_numpy(np.ascontiguousarray(mask, np.uint8)).to(self.dev)
+
+    def epoch(self, perm, active):
+        """One epoch of the active trials: step losses ``[steps, T]`` float32 (columns of inactive trials are not written)."""
+        sizes = device_step_sizes([t.learning_rate for t in self.trials], self.t, self.steps, self.cfg["total"])
+        with self.torch.cuda.device(self.dev):
+            d_perm, d_sizes, d_active = self.torch.from_numpy(perm).to(self.dev), self.torch.from_numpy(sizes).to(self.dev), self._mask(active)
+            self.hip.check(self.ctx.lib.bn_probe_sweep_epoch(self.handle, self.X.data_ptr(), self.Y.data_ptr(), d_perm.data_ptr(), self.n, self.cfg["batch"],
+                                                             d_sizes.data_ptr(), d_active.data_ptr(), self.step_loss.data_ptr(), self._stream()))
+            self.t += self.steps
+            return self.step_loss.cpu().numpy()   # (synchronises: the uploads outlive the epoch)
+
+    def val_loss(self, active):
+        with self.torch.cuda.device(self.dev):
+            d_active = self._mask(active)
+            self.hip.check(self.ctx.lib.bn_probe_sweep_loss(self.handle, self.Xv.data_ptr(), self.Yv.data_ptr(), self.Xv.shape[0], d_active.data_ptr(),
+                                                            self.val.data_ptr(), self._stream()))
+            return self.val.cpu().numpy()
+
+    def snapshot(self, mask):
+        with self.torch.cuda.device(self.dev):
+            d_mask = self._mask(mask)
+            self.hip.check(self.ctx.lib.bn_probe_sweep_snapshot(self.handle, d_mask.data_ptr(), self._stream()))
+            self.torch.cuda.current_stream(self.dev).synchronize()
+
+    def get(self, trial, snapshot=False):
+        W, b = self.torch.empty_like(self.W), self.torch.empty_like(self.b)
+        with self.torch.cuda.device(self.dev):
+            self.hip.check(self.ctx.lib.bn_probe_sweep_get(self.handle, int(trial), self.hip.PROBE_SWEEP_SNAPSHOT if snapshot else self.hip.PROBE_SWEEP_CURRENT,
+                                                           W.data_ptr(), b.data_ptr(), self._stream()))
+        return W.cpu().numpy(), b.cpu().numpy()
+
+    def close(self):
+        if self.handle:
+            self.torch.cuda.synchronize(self.dev)
+            self.ctx.lib.bn_probe_sweep_destroy(self.handle)
+            self.handle = None
+
+
+def fit_probe_sweep(ctx_or_runner, X, Y, X_val=None, Y_val=None, trials=(), *, activation="sigmoid", epochs=50, batch_size=32, patience=10, seed=42,
+                    class_names=None) -> SweepResult:
+    """``fit_probe`` for every ``ProbeTrial`` of ``trials`` at once (at most ``_hip.PROBE_SWEEP_MAX_TRIALS``).  The trials share the rows, the
+    initial weights, the permutations and the dropout draws; one training step of all of them is the launches of a single fit's step with
+    the trial as one more grid axis, which is what makes a sweep cheap where one fit is launch-bound.  Early stopping is ``fit_probe``'s
+    rule per trial: a stopped trial goes inactive (its weights and its best-epoch snapshot, kept on the device, no longer move) and the
+    others go on.  A trial without label smoothing gives the bits of ``fit_probe`` with its hyperparameters: weights, bias, step losses
+    and validation losses.  The validation loss is never smoothed, so trials compare."""
+    from birdnet_stm32 import _hip
+
+    trials = _check_trials(trials)
+    if len(trials) > _hip.PROBE_SWEEP_MAX_TRIALS:
+        raise ValueError(f"{len(trials)} trials: a sweep takes at most {_hip.PROBE_SWEEP_MAX_TRIALS}")
+    # shapes, activation, batch and epochs; every trial's own fields were checked when it was made (ProbeTrial.__post_init__)
+    _check_fit_args(X, Y, activation, trials[0].optimizer, batch_size, trials[0].dropout, epochs)
+    n, D, C, T = int(X.shape[0]), int(X.shape[1]), int(Y.shape[1]), len(trials)
+    if not (1 <= D <= _hip.PROBE_MAX_D and 1 <= C <= _hip.PROBE_MAX_C):
+        raise ValueError(f"the device path takes 1 <= D <= {_hip.PROBE_MAX_D} and 1 <= C <= {_hip.PROBE_MAX_C}, got D={D} C={C}")
+    ctx = getattr(ctx_or_runner, "ctx", ctx_or_runner)
+    batch, epochs, patience = min(int(batch_size), n), int(epochs), int(patience)
+    has_val = X_val is not None and len(X_val) > 0
+    W0, b0 = init_head(D, C, seed)
+    cfg = dict(activation=activation, batch=batch, seed=int(seed), total=epochs * math.ceil(n / batch))
+    hist = [{"loss": [], "val_loss": [], "step_loss": [], "best_epoch": None, "stopped_epoch": None} for _ in range(T)]
+    best, wait, active = [math.inf] * T, [0] * T, np.ones(T, bool)
+    be = _SweepBackend(ctx, X, Y, X_val if has_val else None, Y_val if has_val else None, W0, b0, cfg, trials)
+    try:
+        for epoch in range(epochs):
+            if not active.any():
+                break
+            running = np.flatnonzero(active)
+            losses = be.epoch(epoch_permutation(int(seed), epoch, n), active)
+            for t in running:
+                col = np.ascontiguousarray(losses[:, t], np.float64)
+                hist[t]["step_loss"].append(col)
+                hist[t]["loss"].append(float(col.mean()))
+            if not has_val:
+                continue
+            vals = be.val_loss(active)
+            improved = np.zeros(T, bool)
+            for t in running:   # _fit_loop's rule, per trial
+                val = float(vals[t])
+                hist[t]["val_loss"].append(val)
+                if val < best[t]:
+                    best[t], wait[t], hist[t]["best_epoch"], improved[t] = val, 0, epoch, True
+                else:
+                    wait[t] += 1
+                    if wait[t] >= patience and epoch > 0:
+                        hist[t]["stopped_epoch"], active[t] = epoch, False
+            if improved.any():
+                be.snapshot(improved)
+        heads = []
+        for t in range(T):
+            W, b = be.get(t, snapshot=hist[t]["best_epoch"] is not None)
+            hist[t]["step_loss"] = np.concatenate(hist[t]["step_loss"])
+            heads.append(ProbeHead(W, b, activation, list(class_names or []), hist[t]))
+    finally:
+        be.close()
+    return SweepResult(heads, trials, _best_trial(heads))
+
+
+def fit_probe_sweep_reference(X, Y, X_val=None, Y_val=None, trials=(), *, activation="sigmoid", epochs=50, batch_size=32, patience=10, seed=42,
+                              dtype=np.float64, class_names=None) -> SweepResult:
+    """The specification of ``fit_probe_sweep``: ``fit_probe_reference`` once per trial."""
+    trials = _check_trials(trials)
+    heads = [fit_probe_reference(X, Y, X_val, Y_val, activation=activation, epochs=epochs, batch_size=batch_size, patience=patience, seed=seed, dtype=dtype,
+                                 class_names=class_names, **t.fit_kwargs()) for t in trials]
+    return SweepResult(heads, trials, _best_trial(heads))
 
 
 # -- the fit on augmented inputs ------------------------------------------------------------------------------------------------------
@@ -615,7 +853,8 @@ def targets_from_paths(paths: list, classes: list, file_index: np.ndarray, activ
 
 def probe_output_paths(output: str) -> dict:
     stem = output[:-4] if output.endswith(".npz") else output
-    return {"head": stem + ".npz", "labels": stem + "_labels.txt", "config": stem + "_model_config.json", "history": stem + "_history.csv"}
+    return {"head": stem + ".npz", "labels": stem + "_labels.txt", "config": stem + "_model_config.json", "history": stem + "_history.csv",
+            "tune": stem + "_tune.json"}
 
 
 def write_history_csv(path: str, history: dict) -> None:
@@ -653,7 +892,8 @@ def augmentation_from_args(args):
 
 def run_linear_probe(args, runner=None) -> ProbeHead:
     """The ``probe`` command: ``args.data_path_train/<class>/*`` -> embeddings (the backbone runs once) -> ``fit_probe`` ->
-    ``<output>.npz``, ``<output>_labels.txt``, ``<output>_model_config.json`` and ``<output>_history.csv``."""
+    ``<output>.npz``, ``<output>_labels.txt``, ``<output>_model_config.json`` and ``<output>_history.csv``.  With ``args.tune``:
+    ``training.tune.sample_trials`` -> ``fit_probe_sweep``; the files are the winning trial's, ``<output>_tune.json`` lists all trials."""
     import time
     from dataclasses import replace
 
@@ -662,7 +902,13 @@ def run_linear_probe(args, runner=None) -> ProbeHead:
     from birdnet_stm32.evaluation.embeddings import embed_files
     from birdnet_stm32.training.config import ModelConfig
 
+    from birdnet_stm32.training.tune import check_tune_args
+
     augment = augmentation_from_args(args)
+    check_tune_args(args)
+    label_smoothing = _check_label_smoothing(getattr(args, "label_smoothing", 0.0))
+    if augment is not None and label_smoothing > 0:
+        raise ValueError("--label_smoothing does not combine with --mixup_probability or --spec_augment")
     if not os.path.isfile(args.model_path):
         raise FileNotFoundError(f"Pretrained model not found: {args.model_path}")
     cfg = ModelConfig.load(resolve_config_path(args.model_path, getattr(args, "model_config", "")))
@@ -713,8 +959,24 @@ def run_linear_probe(args, runner=None) -> ProbeHead:
     fit_kw = dict(activation=args.activation, epochs=args.epochs, batch_size=args.batch_size, learning_rate=args.learning_rate,
                   optimizer=args.optimizer, weight_decay=args.weight_decay, clipnorm=args.grad_clip, dropout=args.dropout,
                   patience=getattr(args, "patience", 10), seed=args.seed, class_names=classes)
-    if augment is None:
-        head = fit_probe(runner, emb.embeddings[tr], Y[tr], emb.embeddings[va] if va.any() else None, Y[va] if va.any() else None, **fit_kw)
+    tuned = None
+    if getattr(args, "tune", False):
+        from birdnet_stm32.training.tune import macro_roc_auc, sample_trials, tune_report
+
+        if not va.any():
+            raise ValueError("--tune needs validation rows: the validation split came out empty")
+        base = ProbeTrial(learning_rate=args.learning_rate, optimizer=args.optimizer, weight_decay=args.weight_decay, clipnorm=args.grad_clip,
+                          dropout=args.dropout, label_smoothing=label_smoothing)
+        tune_seed = args.seed if getattr(args, "tune_seed", None) is None else args.tune_seed
+        tuned = fit_probe_sweep(runner, emb.embeddings[tr], Y[tr], emb.embeddings[va], Y[va], sample_trials(args.n_trials, tune_seed, base),
+                                activation=args.activation, epochs=args.epochs, batch_size=args.batch_size, patience=getattr(args, "patience", 10),
+                                seed=args.seed, class_names=classes)
+        head = tuned.best_head
+        auc = macro_roc_auc(Y[va], head.predict(emb.embeddings[va], runner.ctx))
+        tuned = tune_report(tuned, auc)
+    elif augment is None:
+        head = fit_probe(runner, emb.embeddings[tr], Y[tr], emb.embeddings[va] if va.any() else None, Y[va] if va.any() else None,
+                         label_smoothing=label_smoothing, **fit_kw)
     else:
         import torch
 
@@ -732,8 +994,15 @@ def run_linear_probe(args, runner=None) -> ProbeHead:
     head.save(out["head"])
     with open(out["labels"], "w") as fh:
         fh.write("\n".join(classes) + "\n")
-    replace(cfg, num_classes=len(classes), class_names=list(classes), dropout_rate=float(args.dropout)).save(out["config"])
+    dropout_used = tuned["trials"][tuned["best_trial"]]["params"]["dropout"] if tuned else args.dropout   # the written head's own
+    replace(cfg, num_classes=len(classes), class_names=list(classes), dropout_rate=float(dropout_used)).save(out["config"])
     write_history_csv(out["history"], head.history)
+    if tuned is not None:
+        with open(out["tune"], "w") as fh:
+            json.dump(tuned, fh, indent=1)
+        win = tuned["trials"][tuned["best_trial"]]
+        print(f"[probe] tuned over {tuned['n_trials']} trials: trial {tuned['best_trial']} wins with val_loss {win['best_val_loss']:.4f} "
+              f"(macro ROC-AUC {tuned['best_val_macro_roc_auc']:.4f}; trial 0, the untuned settings: {tuned['trials'][0]['best_val_loss']:.4f}) {win['params']}")
     head.history["seconds"] = {"embed": t_embed, "fit": t_fit}
     val = head.history["val_loss"]
     aug_s = head.history.get("augment_seconds")

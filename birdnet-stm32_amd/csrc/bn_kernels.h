@@ -473,7 +473,7 @@ void launch_i8_dwpw(const DwPw8Args& a, hipStream_t s);
 // One per source file with kernels: load that file's device code object now (bn_preload_kernels)
 void preload_f32(); void preload_f32_fused(); void preload_f32_pw(); void preload_f32_strip(); void preload_i8(); void preload_i8_fused();
 void preload_i8_pw(); void preload_i8_strip(); void preload_i8_tail(); void preload_i8_tail2(); void preload_ingest(); void preload_melspec();
-void preload_stft(); void preload_stft_exact(); void preload_sort(); void preload_probe(); void preload_activity(); void preload_search(); void preload_augment(); void preload_kmeans(); void preload_bootstrap();
+void preload_stft(); void preload_stft_exact(); void preload_sort(); void preload_probe(); void preload_probe_sweep(); void preload_activity(); void preload_search(); void preload_augment(); void preload_kmeans(); void preload_bootstrap();
 
 // bn_probe.hip: a classifier head on embeddings (bn_head_forward) and its training step (bn_probe_*)
 struct ProbeFwdArgs {
@@ -510,6 +510,36 @@ void launch_probe_dw(const ProbeDwArgs& a, int row_groups, hipStream_t s);
 void launch_probe_reduce(float* partial, int E, int groups, float* ss_part, hipStream_t s);
 void launch_probe_update(const ProbeUpdateArgs& a, hipStream_t s);
 void launch_probe_loss_sum(const float* part, long n, float scale, float* out, hipStream_t s);
+
+// bn_probe_sweep.hip: T heads trained in lock-step (bn_probe_sweep_*).  The kernels are those of bn_probe.hip with the trial as one more
+// grid axis; what differs per trial is read from a table in device memory, and a trial whose byte of `active` is 0 returns at once.
+struct ProbeSweepTrial {       // one row of the device table
+    int optimizer;             // BN_PROBE_OPT_*
+    float weight_decay, clip;
+    uint32_t drop_thresh;      // of the shared draw: keep iff draw >= drop_thresh (0: no dropout)
+    float drop_scale;
+    int smooth;                // label smoothing on: y' = fl(fl(y * smooth_keep) + smooth_add) (bn_probe_step.h)
+    float smooth_keep, smooth_add;
+};
+struct ProbeSweepArgs {
+    const ProbeSweepTrial* trials;
+    const uint8_t* active;     // [T] or null: every trial
+    float* state;              // [T][4][E]: parameters, m, v, best-weights snapshot
+    float* G;                  // [T][G_stride]
+    float* partial;            // [T][partial_stride]
+    float* ss_part;            // [T][ss_stride]
+    float* loss_part;          // [T][loss_stride]
+    size_t G_stride, partial_stride;
+    int ss_stride, loss_stride, T, E;
+};
+// `f.W`, `f.b`, `f.out`, `f.loss_part`, `f.drop_*` are filled per trial on the device (mode 1: no dropout, no smoothing)
+bool launch_probe_sweep_fwd(const ProbeFwdArgs& f, const ProbeSweepArgs& w, int mode, hipStream_t s);
+void launch_probe_sweep_dw(const ProbeDwArgs& g, const ProbeSweepArgs& w, int row_groups, hipStream_t s);
+void launch_probe_sweep_reduce(const ProbeSweepArgs& w, int groups, hipStream_t s);
+// `u.lr` / `u.alpha` of trial t are step_sizes[2 t], [2 t + 1]; its loss goes to u.step_loss[t]
+void launch_probe_sweep_update(const ProbeUpdateArgs& u, const ProbeSweepArgs& w, const float* step_sizes, hipStream_t s);
+void launch_probe_sweep_loss_sum(const ProbeSweepArgs& w, long n_parts, float scale, float* out, hipStream_t s);
+void launch_probe_sweep_snapshot(const ProbeSweepArgs& w, const uint8_t* mask, hipStream_t s);
 
 // bn_activity.hip: the reductions behind chunk selection.  Short-time energy (frames of 1024 at hops of 512) of windows [win_off[w], win_off[w+1])
 // of the resampled mono buffer, divided by peak[win_index[w]] first, written to ste[frame_off[w] ...]; and per row of x [B][n] the median / MAD /

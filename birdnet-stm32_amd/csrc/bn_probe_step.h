@@ -1,0 +1,433 @@
+// bn_probe_step.h — the kernels of one training step of a classifier head, written once with a compile-time switch:
+// SWEEP = false are the kernels of a single fit (bn_probe.hip), SWEEP = true the same kernels with one more grid axis, the trial of a
+// hyperparameter sweep (bn_probe_sweep.hip).  A sweep's workgroup first finds its trial, leaves at once when that trial is inactive, and
+// takes what differs per trial — its slices of the per-trial buffers, its row of the device table (ProbeSweepTrial) — where a single
+// fit takes kernel arguments; from there on both run the same statements on the same tile-to-workgroup map in the same order, so a trial
+// without label smoothing has the bits of a single fit (tests/test_gpu_probe_sweep.py compares them; `make probe-asm-check`
+// reports where the two instantiations' floating-point instructions differ: tools/probe_sweep_asm_check.py).
+//
+// Label smoothing (sweep only, training loss and G only; the validation loss takes the targets as they are), in float32 with a
+// rounding after every operation (no fused multiply-add):
+//     keep = fl(1 - eps);  add = fl(0.5 * eps) (sigmoid) or fl(eps / fl(C)) (softmax)      on the host
+//     y'   = fl(fl(y * keep) + add)                                                          per element, in the forward kernel
+// training/linear_probe.py: smooth_targets is the same in numpy.  eps == 0 skips the two operations: y' is y, bit for bit.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <type_traits>
+
+#include "../../include/birdnet_hip.h"
+#include "bn_device.h"
+#include "bn_kernels.h"
+
+namespace bn {
+
+struct ProbeNoSweep {};
+template <bool SWEEP>
+using ProbeSweepOf = std::conditional_t<SWEEP, ProbeSweepArgs, ProbeNoSweep>;   // the second kernel argument
+
+
+constexpr int kRows = 16;       // batch rows per forward workgroup (one MFMA tile)
+constexpr int kFwdWaves = 16;   // at most: 16 waves x 16 column tiles x 16 columns = C <= 4096
+constexpr int kLdsPad = 4;      // floats behind every staged row: the 16 rows of an A fragment fall into 16 different bank groups
+
+__device__ __forceinline__ uint32_t probe_fmix(uint32_t h) {   // the murmur3 finaliser
+    h ^= h >> 16;
+    h *= 0x85EBCA6Bu;
+    h ^= h >> 13;
+    h *= 0xC2B2AE35u;
+    h ^= h >> 16;
+    return h;
+}
+
+// The dropout draw of element (row in batch, column) of global step `step`: 24 bits, kept iff >= ceil(p * 2^24).
+// training/linear_probe.py: dropout_hash is the same function in numpy.
+__device__ __forceinline__ uint32_t probe_drop_hash(uint32_t seed, uint32_t step, uint32_t row, uint32_t col) {
+    uint32_t h = probe_fmix(seed ^ (step * 0x9E3779B1u));
+    h = probe_fmix(h ^ (row * 0x85EBCA77u));
+    h = probe_fmix(h ^ (col * 0xC2B2AE3Du));
+    return h >> 8;
+}
+
+__device__ __forceinline__ float group16_max(float v) {   // over the 16 lanes that share lane >> 4
+    for (int m = 1; m < 16; m <<= 1) v = fmaxf(v, __shfl_xor(v, m));
+    return v;
+}
+__device__ __forceinline__ float group16_sum(float v) {
+    for (int m = 1; m < 16; m <<= 1) v += __shfl_xor(v, m);
+    return v;
+}
+__device__ __forceinline__ float wave_sum(float v) {
+    for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m);
+    return v;
+}
+
+// sum of one value per thread of a 256-thread workgroup, the same tree every time; every thread gets the result
+__device__ __forceinline__ float block256_sum(float v, float* red) {
+    const int t = threadIdx.x;
+    __syncthreads();
+    red[t] = v;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (t < s) red[t] += red[t + s];
+        __syncthreads();
+    }
+    return red[0];
+}
+
+
+__device__ __forceinline__ float probe_smooth(float y, float keep, float add) {
+#pragma clang fp contract(off)
+    const float t = y * keep;
+    return t + add;
+}
+
+__device__ __forceinline__ bool sweep_idle(const ProbeSweepArgs& w, int t) { return w.active && !w.active[t]; }
+
+
+// ------------------------------------------------------------------------------------------------------------------------- forward
+// MODE 0: training (G and the loss partial), 1: loss partial only, 2: scores.  NT: column tiles per wave (tile t of wave w is w + t * waves).
+// SWEEP: blockIdx.y is the trial; mode 0 takes its dropout threshold and label smoothing from the table, mode 1 has neither.
+template <int NT, int MODE, bool SWEEP>
+__global__ __launch_bounds__(1024) void probe_fwd_kernel(ProbeFwdArgs a, ProbeSweepOf<SWEEP> w) {
+    const float *W = a.W, *bias = a.b;
+    float *out = a.out, *loss_part = a.loss_part;
+    uint32_t drop_thresh = a.drop_thresh;
+    float drop_scale = a.drop_scale;
+    [[maybe_unused]] bool smooth = false;
+    [[maybe_unused]] float smooth_keep = 1.0f, smooth_add = 0.0f;
+    if constexpr (SWEEP) {
+        const int t = blockIdx.y;
+        if (sweep_idle(w, t)) return;
+        W = w.state + (size_t)t * 4 * w.E;
+        bias = W + (size_t)a.D * a.C;
+        loss_part = w.loss_part + (size_t)t * w.loss_stride;
+        if constexpr (MODE == 0) {
+            const ProbeSweepTrial& tr = w.trials[t];
+            out = w.G + (size_t)t * w.G_stride;
+            drop_thresh = tr.drop_thresh;
+            drop_scale = tr.drop_scale;
+            smooth = tr.smooth != 0;
+            smooth_keep = tr.smooth_keep;
+            smooth_add = tr.smooth_add;
+        }
+    }
+    extern __shared__ float xs[];                 // [16][Dp + kLdsPad], rows beyond the batch and columns beyond D are zero
+    __shared__ float red[kFwdWaves][kRows];
+    __shared__ float red_loss[kFwdWaves];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
+    const int D = a.D, C = a.C, Dp = (D + 3) & ~3, ld = Dp + kLdsPad;
+    const long row0 = (long)blockIdx.x * kRows;
+
+    for (int e = tid; e < kRows * Dp; e += blockDim.x) {
+        const int r = e / Dp, d = e - r * Dp;
+        const long row = row0 + r;
+        float v = 0.0f;
+        if (row < a.n && d < D) {
+            const long src = a.idx ? (long)a.idx[row] : row;
+            v = a.X[src * D + d];
+            if (drop_thresh) v = probe_drop_hash(a.seed, a.step, (uint32_t)row, (uint32_t)d) >= drop_thresh ? v * drop_scale : 0.0f;
+        }
+        xs[r * ld + d] = v;
+    }
+    __syncthreads();
+
+    const int ntiles = (C + 15) >> 4;
+    const int li = lane & 15, lk = lane >> 4;
+    const int per_pass = nw * NT;                          // column tiles the workgroup holds in registers at once
+    const int npass = (ntiles + per_pass - 1) / per_pass;  // 1 unless C > 2048
+    f32x4 acc[NT];
+    bool okc[NT];
+    const float* xrow = xs + li * ld + lk;
+
+    // logits of the column tiles of one pass: lane holds rows 4 * lk + r (r = 0..3) of column tile * 16 + li
+    auto logits = [&](int pass) {
+        const int tile0 = pass * per_pass + wave;
+#pragma unroll
+        for (int t = 0; t < NT; ++t) acc[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        for (int k0 = 0; k0 < Dp; k0 += 4) {
+            const float av = xrow[k0];
+            const int k = k0 + lk;
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                const int tile = tile0 + t * nw;      // wave-uniform
+                if (tile < ntiles) {
+                    const int c = tile * 16 + li;
+                    const float bv = (k < D && c < C) ? W[(size_t)k * C + c] : 0.0f;
+                    acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc[t], 0, 0, 0);
+                }
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const int c = (tile0 + t * nw) * 16 + li;
+            okc[t] = (tile0 + t * nw) < ntiles && c < C;
+            const float bv = okc[t] ? bias[c] : 0.0f;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[t][r] += bv;
+        }
+    };
+
+    // softmax: row maximum m and sum s of exp(z - m) over all columns first — pass by pass in the online form (with one pass that is
+    // the plain max / sum); a head wider than one pass computes its logits a second time below, once m and s are known
+    float m[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY}, s[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    bool have = false;
+    if (a.softmax) {
+        for (int pass = 0; pass < npass; ++pass) {
+            logits(pass);
+            float mn[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                float v = -INFINITY;
+#pragma unroll
+                for (int t = 0; t < NT; ++t)
+                    if (okc[t]) v = fmaxf(v, acc[t][r]);
+                mn[r] = group16_max(v);
+            }
+            __syncthreads();
+            if (li == 0)
+                for (int r = 0; r < 4; ++r) red[wave][4 * lk + r] = mn[r];
+            __syncthreads();
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                float v = m[r];
+                for (int w = 0; w < nw; ++w) v = fmaxf(v, red[w][4 * lk + r]);
+                mn[r] = v;
+            }
+            float sn[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                float v = 0.0f;
+#pragma unroll
+                for (int t = 0; t < NT; ++t)
+                    if (okc[t]) v += expf(acc[t][r] - mn[r]);
+                sn[r] = group16_sum(v);
+            }
+            __syncthreads();
+            if (li == 0)
+                for (int r = 0; r < 4; ++r) red[wave][4 * lk + r] = sn[r];
+            __syncthreads();
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                float v = red[0][4 * lk + r];
+                for (int w = 1; w < nw; ++w) v += red[w][4 * lk + r];
+                s[r] = pass == 0 ? v : s[r] * expf(m[r] - mn[r]) + v;
+                m[r] = mn[r];
+            }
+        }
+        have = npass == 1;
+    }
+
+    float loss = 0.0f;
+    for (int pass = 0; pass < npass; ++pass) {
+        if (!have) logits(pass);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const int c = (pass * per_pass + wave + t * nw) * 16 + li;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const long row = row0 + 4 * lk + r;
+                if (!okc[t] || row >= a.n) continue;
+                const float p = a.softmax ? expf(acc[t][r] - m[r]) / s[r] : 1.0f / (1.0f + expf(-acc[t][r]));
+                if constexpr (MODE == 2) {
+                    out[(size_t)row * C + c] = p;
+                } else {
+                    const long src = (MODE == 0 && a.idx) ? (long)a.idx[row] : row;
+                    float y = a.Y[(size_t)src * C + c];
+                    if constexpr (SWEEP && MODE == 0)
+                        if (smooth) y = probe_smooth(y, smooth_keep, smooth_add);
+                    const float pc = fminf(fmaxf(p, 1e-7f), 1.0f - 1e-7f);
+                    if (a.softmax)
+                        loss -= y * logf(pc);
+                    else
+                        loss -= y * logf(pc) + (1.0f - y) * logf(1.0f - pc);
+                    if constexpr (MODE == 0) out[(size_t)row * C + c] = (p - y) * a.g_scale;
+                }
+            }
+        }
+    }
+    if constexpr (MODE != 2) {
+        loss = wave_sum(loss);
+        if (lane == 0) red_loss[wave] = loss;
+        __syncthreads();
+        if (tid == 0) {
+            float v = red_loss[0];
+            for (int w = 1; w < nw; ++w) v += red_loss[w];
+            loss_part[blockIdx.x] = v;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------------ gradient
+// Workgroup (bx, by, bz): rows [16 * (4 by + wave), +16) of dParams (row D is the bias), columns [64 bx, +64), batch rows of group bz.
+// SWEEP: blockIdx.z = trial * groups + group.
+template <bool SWEEP>
+__global__ __launch_bounds__(256) void probe_dw_kernel(ProbeDwArgs a, ProbeSweepOf<SWEEP> w, int sweep_groups) {
+    const float* G = a.G;
+    float *partial = a.partial, *ss_part = a.ss_part;
+    uint32_t drop_thresh = a.drop_thresh;
+    float drop_scale = a.drop_scale;
+    int group = blockIdx.z, groups = gridDim.z;
+    if constexpr (SWEEP) {
+        const int t = blockIdx.z / sweep_groups;
+        if (sweep_idle(w, t)) return;
+        const ProbeSweepTrial& tr = w.trials[t];
+        group = blockIdx.z - t * sweep_groups;
+        groups = sweep_groups;
+        G = w.G + (size_t)t * w.G_stride;
+        partial = w.partial + (size_t)t * w.partial_stride;
+        ss_part = w.ss_part + (size_t)t * w.ss_stride;
+        drop_thresh = tr.drop_thresh;
+        drop_scale = tr.drop_scale;
+    }
+    __shared__ float red[256];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, lk = lane >> 4;
+    const int D = a.D, C = a.C;
+    const int d0 = (blockIdx.y * 4 + wave) * 16, c0 = blockIdx.x * 64;
+    const int b_begin = group * a.rows_per_group;
+    const int b_end = min(a.B, b_begin + a.rows_per_group);
+    f32x4 acc[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    const int d = d0 + li;
+    if (d0 <= D) {
+        for (int k0 = b_begin; k0 < b_end; k0 += 4) {
+            const int bb = k0 + lk;
+            float av = 0.0f;
+            if (bb < b_end) {
+                if (d < D) {
+                    av = a.X[(size_t)a.idx[bb] * D + d];
+                    if (drop_thresh) av = probe_drop_hash(a.seed, a.step, (uint32_t)bb, (uint32_t)d) >= drop_thresh ? av * drop_scale : 0.0f;
+                } else if (d == D) {
+                    av = 1.0f;
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (c0 + 16 * j < C) {   // wave-uniform
+                    const int c = c0 + 16 * j + li;
+                    const float bv = (bb < b_end && c < C) ? G[(size_t)bb * C + c] : 0.0f;
+                    acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc[j], 0, 0, 0);
+                }
+            }
+        }
+    }
+    float ss = 0.0f;
+    float* part = partial + (size_t)group * a.E;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int c = c0 + 16 * j + li;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int dr = d0 + 4 * lk + r;
+            if (dr <= D && c < C) {
+                part[(size_t)dr * C + c] = acc[j][r];
+                ss += acc[j][r] * acc[j][r];
+            }
+        }
+    }
+    if (groups == 1) {   // one row group: the partial is the gradient, its squares count for the norm
+        ss = block256_sum(ss, red);
+        if (threadIdx.x == 0) ss_part[blockIdx.y * gridDim.x + blockIdx.x] = ss;
+    }
+}
+
+// partial[0] += partial[1] + ... in group order; 1024 elements and one sum of squares per workgroup
+template <bool SWEEP>
+__global__ __launch_bounds__(256) void probe_reduce_kernel(float* __restrict__ partial, int E, int groups, float* __restrict__ ss_part, ProbeSweepOf<SWEEP> w) {
+    if constexpr (SWEEP) {   // blockIdx.y is the trial
+        if (sweep_idle(w, blockIdx.y)) return;
+        partial += (size_t)blockIdx.y * w.partial_stride;
+        ss_part += (size_t)blockIdx.y * w.ss_stride;
+    }
+    __shared__ float red[256];
+    float ss = 0.0f;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int i = blockIdx.x * 1024 + q * 256 + threadIdx.x;
+        if (i < E) {
+            float v = partial[i];
+            for (int g = 1; g < groups; ++g) v += partial[(size_t)g * E + i];
+            partial[i] = v;
+            ss += v * v;
+        }
+    }
+    ss = block256_sum(ss, red);
+    if (threadIdx.x == 0) ss_part[blockIdx.x] = ss;
+}
+
+// -------------------------------------------------------------------------------------------------------------------------- update
+// SWEEP: blockIdx.y is the trial; its step sizes are step_sizes[2 t], [2 t + 1], its loss goes to a.step_loss[t].
+template <bool SWEEP>
+__global__ __launch_bounds__(256) void probe_update_kernel(ProbeUpdateArgs a, ProbeSweepOf<SWEEP> sw, const float* __restrict__ step_sizes) {
+    float *params = a.params, *pm = a.m, *pv = a.v, *step_loss = a.step_loss;
+    const float *grad = a.grad, *ss_part = a.ss_part, *loss_part = a.loss_part;
+    int optimizer = a.optimizer;
+    float lr = a.lr, alpha = a.alpha, weight_decay = a.weight_decay, clip = a.clip;
+    if constexpr (SWEEP) {
+        const int t = blockIdx.y;
+        if (sweep_idle(sw, t)) return;
+        const ProbeSweepTrial& tr = sw.trials[t];
+        params = sw.state + (size_t)t * 4 * sw.E;
+        pm = params + sw.E;
+        pv = pm + sw.E;
+        grad = sw.partial + (size_t)t * sw.partial_stride;
+        ss_part = sw.ss_part + (size_t)t * sw.ss_stride;
+        loss_part = sw.loss_part + (size_t)t * sw.loss_stride;
+        step_loss = a.step_loss + t;
+        optimizer = tr.optimizer;
+        lr = step_sizes[2 * t];
+        alpha = step_sizes[2 * t + 1];
+        weight_decay = tr.weight_decay;
+        clip = tr.clip;
+    }
+    __shared__ float red[256];
+    const int t = threadIdx.x;
+    float scale = 1.0f;
+    if (clip > 0.0f) {   // every workgroup adds the same values in the same order: one scale, bit for bit
+        float v = 0.0f;
+        for (int i = t; i < a.n_ss; i += 256) v += ss_part[i];
+        const float norm = sqrtf(block256_sum(v, red));
+        if (norm > clip) scale = clip / norm;
+    }
+    if (blockIdx.x == 0 && step_loss) {
+        float v = 0.0f;
+        for (int i = t; i < a.n_loss; i += 256) v += loss_part[i];
+        v = block256_sum(v, red);
+        if (t == 0) *step_loss = v * a.loss_scale;
+    }
+    const int i = blockIdx.x * 256 + t;
+    if (i >= a.E) return;
+    const float g = grad[i] * scale;
+    float w = params[i];
+    if (optimizer == BN_PROBE_OPT_SGD) {   // Keras SGD with momentum: v = 0.9 v - lr g; w += v
+        const float v = 0.9f * pm[i] - lr * g;
+        pm[i] = v;
+        w += v;
+    } else {
+        if (optimizer == BN_PROBE_OPT_ADAMW) w -= lr * weight_decay * w;   // decoupled, before the Adam step (Keras)
+        const float m = pm[i] + (g - pm[i]) * 0.1f;        // 1 - beta as the float32 nearest to 0.1 / 0.001 (1.0f - 0.999f is 1.3e-5 off)
+        const float v = pv[i] + (g * g - pv[i]) * 0.001f;
+        pm[i] = m;
+        pv[i] = v;
+        w -= m * alpha / (sqrtf(v) + 1e-7f);   // alpha = lr_t sqrt(1 - b2^t) / (1 - b1^t): the bias correction folded into the step size
+    }
+    params[i] = w;
+}
+
+// out[0] = scale * (part[0] + part[1] + ...), one workgroup, fixed order (bn_probe_loss)
+template <bool SWEEP>
+__global__ __launch_bounds__(256) void probe_loss_sum_kernel(const float* __restrict__ part, long n, float scale, float* __restrict__ out, ProbeSweepOf<SWEEP> w) {
+    if constexpr (SWEEP) {   // blockIdx.x is the trial
+        if (sweep_idle(w, blockIdx.x)) return;
+        part += (size_t)blockIdx.x * w.loss_stride;
+        out += blockIdx.x;
+    }
+    __shared__ float red[256];
+    float v = 0.0f;
+    for (long i = threadIdx.x; i < n; i += 256) v += part[i];
+    v = block256_sum(v, red);
+    if (threadIdx.x == 0) *out = v * scale;
+}
+
+}  // namespace bn

@@ -413,6 +413,56 @@ BN_API int bn_probe_loss(bn_probe* probe, const float* d_X, const float* d_Y, in
 BN_API int bn_probe_get(bn_probe* probe, float* d_W, float* d_b, void* stream);
 BN_API int bn_probe_set(bn_probe* probe, const float* d_W, const float* d_b, void* stream);
 
+/* ---- A hyperparameter sweep: T heads trained in lock-step on the same rows (csrc/bn_probe_sweep.hip) ---------------------------------
+ * (Reference counterpart: `train --tune`, training/tuner.py, which trains its trials one after another.)  The trials share D, C, the
+ * activation, the batch, X / Y, the permutation, the step counter, the dropout draw (each trial has its own threshold on it) and the
+ * initial weights; a training step of all T trials is the three (four) launches of bn_probe_epoch's step with the trial as one more grid
+ * axis.  A trial with label_smoothing == 0 has the bits of a bn_probe with the same hyperparameters and seed: weights, bias, step
+ * losses, validation losses.  Label smoothing (Keras): y' = y (1 - eps) + 0.5 eps (sigmoid) or + eps / C (softmax) in the training loss
+ * and its gradient; bn_probe_sweep_loss takes the targets as they are.  In float32: keep = fl(1 - eps), add = fl(0.5 eps) or
+ * fl(eps / fl(C)), y' = fl(fl(y keep) + add). */
+#define BN_PROBE_SWEEP_MAX_TRIALS 64
+/* Bound on the device memory of one sweep: per trial the parameters, Adam's m and v and the best-weights snapshot ((D + 1) * C floats
+ * each), G [batch, C], the row-group partials of its gradient (as many groups as a single fit of that batch uses, never fewer) and the
+ * loss / norm partials (one loss partial per 16 rows of a batch, or of the rows of bn_probe_sweep_loss).  A call that would need more is
+ * refused with the largest T that fits. */
+#define BN_PROBE_SWEEP_BYTES (2048ull << 20)
+#define BN_PROBE_SWEEP_CURRENT 0  /* bn_probe_sweep_get: the parameters as they are */
+#define BN_PROBE_SWEEP_SNAPSHOT 1 /* ... as bn_probe_sweep_snapshot last kept them (the initial weights before the first one) */
+
+typedef struct bn_probe_trial {
+    int32_t optimizer;     /* BN_PROBE_OPT_* */
+    float lr;              /* kept for the record: the step sizes come with every epoch (below) */
+    float weight_decay;    /* adamw only */
+    float clipnorm;        /* 0: no clipping */
+    float dropout;         /* [0, 1) */
+    float label_smoothing; /* [0, 1) */
+} bn_probe_trial;
+
+typedef struct bn_probe_sweep bn_probe_sweep;
+
+/* trials: a host array of T rows, 1 <= T <= BN_PROBE_SWEEP_MAX_TRIALS.  d_W / d_b: the initial values of every trial (copied, also into
+ * the snapshot slots; the optimiser states start at zero).  seed, total_steps: as bn_probe_create (total_steps is kept for the record). */
+BN_API int bn_probe_sweep_create(bn_ctx* ctx, int D, int C, int activation, int T, const bn_probe_trial* trials, uint32_t seed,
+                          int64_t total_steps, const float* d_W, const float* d_b, bn_probe_sweep** out, void* stream);
+/* Waits for the device to finish, then frees the sweep. */
+BN_API void bn_probe_sweep_destroy(bn_probe_sweep* sweep);
+/* The ceil(n / batch) steps of one epoch for every trial t with d_active[t] != 0 (uint8 [T]; null: all).  d_step_sizes: float32
+ * [steps, T, 2], (lr_t, alpha_t) of trial t at each step of this epoch: the cosine-decayed learning rate and Adam's step size with the
+ * bias correction folded in, as bn_probe_epoch computes them on the host in float64.  d_step_loss: float32 [steps, T]; entries of
+ * inactive trials are not written, and neither are their parameters, optimiser state or snapshot.  The step counter (the dropout
+ * draw's) advances by the steps of the epoch for all trials.  Nothing synchronises with the host; no floating-point atomics. */
+BN_API int bn_probe_sweep_epoch(bn_probe_sweep* sweep, const float* d_X, const float* d_Y, const int32_t* d_perm, int64_t n, int batch,
+                         const float* d_step_sizes, const uint8_t* d_active, float* d_step_loss, void* stream);
+/* d_out[t] = the mean loss of trial t's current weights over rows 0 .. n-1 of d_X / d_Y, without dropout or smoothing, for every trial
+ * with d_active[t] != 0 (null: all); other entries are not written. */
+BN_API int bn_probe_sweep_loss(bn_probe_sweep* sweep, const float* d_X, const float* d_Y, int64_t n, const uint8_t* d_active, float* d_out,
+                        void* stream);
+/* Copies the parameters of every trial with d_mask[t] != 0 (uint8 [T]) into its best-weights slot, on the device. */
+BN_API int bn_probe_sweep_snapshot(bn_probe_sweep* sweep, const uint8_t* d_mask, void* stream);
+/* The weights [D, C] and bias [C] of one trial (device pointers), which: BN_PROBE_SWEEP_CURRENT or BN_PROBE_SWEEP_SNAPSHOT. */
+BN_API int bn_probe_sweep_get(bn_probe_sweep* sweep, int trial, int which, float* d_W, float* d_b, void* stream);
+
 /* ---- Query by example: the k best rows of an embedding matrix per query (csrc/bn_search.hip; no reference counterpart) -------------
  * Rows and queries are BN_DTYPE_F32 values or the BN_DTYPE_I8 bytes of bn_forward_embed with their zero point; both sides have the same
  * type.  dot is the float32 inner product (its summation order is the implementation's) or, for int8, the exact int32 inner product of

@@ -6,6 +6,13 @@ D = 256, C in {12, 100, 1000}, batch in {32, 512, 4096}, random rows.  The PyTor
 fit: gather, dropout, ``torch.nn.functional.linear``, sigmoid + binary cross-entropy, backward, ``clip_grad_norm_``, ``torch.optim.Adam``
 with a cosine schedule.  Both sides are timed over whole epochs (first epoch discarded as warm-up), synchronised at the epoch's end only.
 Prints one JSON line per cell and a markdown table.
+
+    python tools/probe_bench.py --sweep 4,16,64 [--rows 262144] [--repeats 3] [--classes 12,100,1000] [--batches 32,512,4096]
+
+One sweep of T trials (``fit_probe_sweep``'s backend, ``bn_probe_sweep_*``) against T single fits one after another (``bn_probe_*``) in the
+same process: per cell one warm-up epoch of each side, then ``--repeats`` timed epochs of each, alternating.  An epoch is timed from the
+permutation's upload to the step losses on the host, as the fit runs it.  Reports the median and the spread (min .. max) of both sides and
+the ratio of the medians.
 """
 
 import argparse
@@ -39,6 +46,58 @@ def torch_epoch_fn(torch, X, Y, C, batch, total_steps):
     return epoch
 
 
+def sweep_main(args):
+    import numpy as np
+    import torch
+
+    from birdnet_stm32 import _hip
+    from birdnet_stm32.training import linear_probe as lp
+
+    n, D = args.rows, 256
+    ctx = _hip.Context(0, 1)
+    g = torch.Generator(device="cuda").manual_seed(1)
+    X = torch.rand((n, D), device="cuda", generator=g)
+    rows = []
+    for C in [int(v) for v in args.classes.split(",")]:
+        Y = torch.zeros((n, C), device="cuda")
+        Y[torch.arange(n, device="cuda"), torch.randint(0, C, (n,), device="cuda", generator=g)] = 1.0
+        for batch in [int(v) for v in args.batches.split(",")]:
+            steps = math.ceil(n / batch)
+            total = steps * (args.repeats + 1)
+            W0, b0 = lp.init_head(D, C, 1)
+            cfg = dict(activation="sigmoid", optimizer="adam", batch=batch, seed=1, dropout=0.5, clipnorm=1.0, lr=1e-3, weight_decay=0.0, total=total)
+            for T in [int(v) for v in args.sweep.split(",")]:
+                trials = [lp.ProbeTrial(learning_rate=1e-3, optimizer="adam", dropout=0.5, clipnorm=1.0)] * T
+                singles = [lp._DeviceBackend(ctx, X, Y, None, None, W0, b0, cfg) for _ in range(T)]
+                sweep = lp._SweepBackend(ctx, X, Y, None, None, W0, b0, cfg, trials)
+                active = np.ones(T, bool)
+                seq, par = [], []
+                for e in range(args.repeats + 1):
+                    perm = lp.epoch_permutation(1, e, n)
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    for be in singles:
+                        be.epoch(perm)
+                    seq.append(time.perf_counter() - t0)
+                    t0 = time.perf_counter()
+                    losses = sweep.epoch(perm, active)
+                    par.append(time.perf_counter() - t0)
+                same = bool(np.array_equal(losses[:, 0], singles[0].step_loss.cpu().numpy()))
+                for be in singles + [sweep]:
+                    be.close()
+                seq, par = sorted(seq[1:]), sorted(par[1:])
+                row = dict(D=D, C=C, batch=batch, T=T, steps_per_epoch=steps, sequential_s=float(np.median(seq)), sequential_min=seq[0], sequential_max=seq[-1],
+                           sweep_s=float(np.median(par)), sweep_min=par[0], sweep_max=par[-1], ratio=float(np.median(seq) / np.median(par)),
+                           sweep_trial_steps_per_s=T * steps / float(np.median(par)), same_losses=same)
+                rows.append(row)
+                print(json.dumps(row), flush=True)
+    print("\n| C | batch | T | T fits one by one, s/epoch (min .. max) | one sweep, s/epoch (min .. max) | ratio | trial-steps/s in the sweep |\n|---|---|---|---|---|---|---|")
+    for r in rows:
+        print(f"| {r['C']} | {r['batch']} | {r['T']} | {r['sequential_s']:.3f} ({r['sequential_min']:.3f} .. {r['sequential_max']:.3f}) | "
+              f"{r['sweep_s']:.3f} ({r['sweep_min']:.3f} .. {r['sweep_max']:.3f}) | {r['ratio']:.2f} | {r['sweep_trial_steps_per_s']:.0f} |")
+    ctx.close()
+
+
 def main():
     import numpy as np
     import torch
@@ -49,7 +108,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=262144)
     ap.add_argument("--epochs", type=int, default=2, help="timed epochs per cell (one more runs first as warm-up)")
+    ap.add_argument("--sweep", type=str, default="", help="trial counts, e.g. 4,16,64: time one sweep of T trials against T fits one after another")
+    ap.add_argument("--repeats", type=int, default=3, help="with --sweep: timed epochs per side and cell (one more runs first as warm-up)")
+    ap.add_argument("--classes", type=str, default="12,100,1000", help="with --sweep: class counts")
+    ap.add_argument("--batches", type=str, default="32,512,4096", help="with --sweep: batch sizes")
     args = ap.parse_args()
+    if args.sweep:
+        return sweep_main(args)
     n, D = args.rows, 256
     ctx = _hip.Context(0, 1)
     g = torch.Generator(device="cuda").manual_seed(1)
