@@ -7,7 +7,9 @@ The backbone runs once over all files (``embed``'s device path), the head is tra
 ``--spec_augment`` the training rows' model inputs stay on the device and every epoch trains on fresh embeddings of augmented rows
 (``training/augment.py``).  With ``--tune`` the learning rate, dropout, label smoothing, optimizer, weight decay and gradient clip are searched:
 ``--n_trials`` heads train at once on the device (``training/tune.py``), the one with the lowest validation loss is written, and
-``<output>_tune.json`` lists them all.
+``<output>_tune.json`` lists them all.  For long-tailed folders: ``--upsample_ratio`` repeats training files of the small classes,
+``--class_weights balanced`` weighs the rows by inverse class frequency and ``--loss focal`` trains on the focal loss; they combine with
+each other and with the plain fit, ``--tune`` and the augmented fit.
 """
 
 from __future__ import annotations
@@ -32,6 +34,17 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--label_smoothing", type=float, default=0.0,
                    help="Label smoothing of the training loss, in [0, 1); 0 = off (the default here; the reference's `train` defaults to 0.1).  "
                         "The validation loss is never smoothed")
+    p.add_argument("--loss", type=str, default="auto", choices=["auto", "focal"],
+                   help="auto: the activation's cross-entropy; focal: the focal loss of the sigmoid head, in training and in the validation loss "
+                        "(after label smoothing, where the reference's --loss focal replaces it).  Needs --activation sigmoid")
+    p.add_argument("--focal_gamma", type=float, default=2.0, help="With --loss focal: the focusing exponent, >= 0 (the reference's default)")
+    p.add_argument("--class_weights", type=str, default="none", choices=["none", "balanced"],
+                   help="balanced: weight every training row by total / (classes * files of its class), counted after upsampling; rows of noise "
+                        "folders weigh 1; with mixup a mixed row keeps its own file's weight.  none is the default here; the reference's `train` "
+                        "defaults to balanced")
+    p.add_argument("--upsample_ratio", type=float, default=0.0,
+                   help="Repeat training files of the small classes up to this fraction of the largest class, 0 < R <= 1 (the reference's rule "
+                        "and draws); 0 = off.  Every file is still embedded once, and files of noise folders are kept once")
     p.add_argument("--val_split", type=float, default=0.2, help="Validation split ratio (by file)")
     p.add_argument("--patience", type=int, default=10, help="Early stopping: epochs without a better validation loss")
     p.add_argument("--max_duration", type=float, default=30, help="Seconds read from the start of each file")
@@ -70,9 +83,10 @@ def main(argv=None, runner=None):
         from birdnet_stm32.audio.pipeline import selection_from_args
 
         selection_from_args(args)   # (bad selection flags are refused before anything is loaded, as `embed` does)
-        from birdnet_stm32.training.linear_probe import augmentation_from_args
+        from birdnet_stm32.training.linear_probe import augmentation_from_args, imbalance_from_args
 
         augmentation_from_args(args)   # (and bad augmentation flags; run_linear_probe refuses bad --tune / --label_smoothing combinations first thing)
+        imbalance_from_args(args)      # (and focal with softmax, a bad --focal_gamma or --upsample_ratio)
         return run_linear_probe(args, runner=runner)
     except (ValueError, FileNotFoundError) as exc:
         raise SystemExit(f"error: {exc}") from None

@@ -19,6 +19,11 @@ cross-entropy or softmax + categorical cross-entropy (Keras definitions, probabi
 with ``label_smoothing`` the training loss and its gradient see ``smooth_targets``, the validation loss the targets as they are),
 clip by global norm, Adam / AdamW / SGD-with-momentum (Keras definitions) under a cosine schedule to zero; validation loss per epoch,
 early stopping with the best weights restored (Keras ``EarlyStopping(patience, restore_best_weights=True)``).
+
+For long-tailed class folders every fit takes ``loss="focal"`` / ``focal_gamma`` (the reference's ``training/losses.py: BinaryFocalLoss``),
+``sample_weight`` (its balanced ``class_weight``: ``balanced_class_weights``, ``row_weights``) and ``rows`` (its ``--upsample_ratio``:
+``data.dataset.upsample_minority_classes``, ``upsample_rows``); all off by default, ``probe_loss`` / ``probe_loss_gradient`` are their
+definition.
 """
 
 from __future__ import annotations
@@ -33,6 +38,7 @@ import numpy as np
 
 ACTIVATIONS = ("sigmoid", "softmax")
 OPTIMIZERS = ("adam", "adamw", "sgd")
+LOSSES = ("auto", "focal")   # "auto": the activation's cross-entropy
 NOISE_CLASSES = ("noise", "silence", "background", "other")
 BETA_1, BETA_2, ADAM_EPS, MOMENTUM, LOSS_EPS = 0.9, 0.999, 1e-7, 0.9, 1e-7
 
@@ -127,13 +133,113 @@ def head_scores(X: np.ndarray, W: np.ndarray, b: np.ndarray, activation: str) ->
         return 1.0 / (1.0 + np.exp(-z))
 
 
-def probe_loss(P: np.ndarray, Y: np.ndarray, activation: str):
-    """Keras' loss on probabilities: mean binary cross-entropy over rows x classes, or mean categorical cross-entropy over rows."""
-    one = P.dtype.type(1.0)
-    Pc = np.clip(P, P.dtype.type(LOSS_EPS), one - P.dtype.type(LOSS_EPS))
+def _check_loss(loss, focal_gamma, activation) -> tuple[str, float]:
+    if loss not in LOSSES:
+        raise ValueError(f"loss must be one of {LOSSES}, not {loss!r}")
+    gamma = float(focal_gamma)
+    if not (math.isfinite(gamma) and gamma >= 0.0):
+        raise ValueError(f"focal_gamma must be finite and >= 0, got {focal_gamma!r}")
+    if loss == "focal" and activation != "sigmoid":
+        raise ValueError("loss='focal' is the sigmoid head's loss: not with activation='softmax'")
+    return loss, gamma
+
+
+def _loss_elements(P, Y, activation, loss, focal_gamma):
+    """Per element: the loss and its derivative by the logit, before weights and the mean's scale.  The operations, and their order, are
+    ``probe_loss_elem``'s (``csrc/bn_probe_step.h``).  Focal, with ``pc`` the clipped probability: ``bce = -(y log pc + (1 - y) log(1 - pc))``,
+    ``q = 1 - (y pc + (1 - y)(1 - pc))``, ``f = exp(gamma log q)``, loss ``f bce``, derivative ``f (p - y) - gamma (f / q) (2 y - 1) pc (1 - pc) bce``.
+    ``gamma = 0`` is not special-cased: ``f`` is exactly 1 and the second term exactly 0."""
+    dt = P.dtype.type
+    one = dt(1.0)
+    Pc = np.clip(P, dt(LOSS_EPS), one - dt(LOSS_EPS))
+    g = P - Y
     if activation == "softmax":
-        return -(Y * np.log(Pc)).sum() / P.dtype.type(P.shape[0])
-    return -(Y * np.log(Pc) + (one - Y) * np.log(one - Pc)).sum() / P.dtype.type(P.size)
+        return -(Y * np.log(Pc)), g
+    bce = -(Y * np.log(Pc) + (one - Y) * np.log(one - Pc))
+    if loss != "focal":
+        return bce, g
+    gamma = dt(np.float32(focal_gamma))
+    q = one - (Y * Pc + (one - Y) * (one - Pc))
+    f = np.exp(gamma * np.log(q))
+    return f * bce, f * g - gamma * (f / q) * (dt(2.0) * Y - one) * Pc * (one - Pc) * bce
+
+
+def probe_loss(P: np.ndarray, Y: np.ndarray, activation: str, *, loss="auto", focal_gamma=2.0, sample_weight=None):
+    """Keras' loss on probabilities: mean binary cross-entropy over rows x classes, or mean categorical cross-entropy over rows.
+    ``loss="focal"`` (sigmoid only): the focal form of the element loss (``_loss_elements``).  ``sample_weight [rows]`` multiplies the
+    elements of its row; the mean still divides by rows x classes (or rows): Keras' ``sum_over_batch_size``, not the sum of the weights."""
+    one = P.dtype.type(1.0)
+    if loss == "auto" and sample_weight is None:
+        Pc = np.clip(P, P.dtype.type(LOSS_EPS), one - P.dtype.type(LOSS_EPS))
+        if activation == "softmax":
+            return -(Y * np.log(Pc)).sum() / P.dtype.type(P.shape[0])
+        return -(Y * np.log(Pc) + (one - Y) * np.log(one - Pc)).sum() / P.dtype.type(P.size)
+    loss, focal_gamma = _check_loss(loss, focal_gamma, activation)
+    elem, _ = _loss_elements(P, Y, activation, loss, focal_gamma)
+    if sample_weight is not None:
+        elem = elem * np.asarray(sample_weight, P.dtype)[:, None]
+    return elem.sum() / P.dtype.type(P.shape[0] if activation == "softmax" else P.size)
+
+
+def probe_loss_gradient(P: np.ndarray, Y: np.ndarray, activation: str, *, loss="auto", focal_gamma=2.0, sample_weight=None) -> np.ndarray:
+    """``dLoss/dlogits [rows, C]`` of ``probe_loss`` with the same arguments, the mean's scale applied: what the forward kernel writes
+    as ``G``.  (Cross-entropy: ``p - y``, which for softmax is the derivative when the targets of a row sum to 1.)"""
+    scale = P.dtype.type(P.shape[0] if activation == "softmax" else P.size)
+    if loss == "auto" and sample_weight is None:
+        return (P - Y) / scale
+    loss, focal_gamma = _check_loss(loss, focal_gamma, activation)
+    _, g = _loss_elements(P, Y, activation, loss, focal_gamma)
+    if sample_weight is not None:
+        g = g * np.asarray(sample_weight, P.dtype)[:, None]
+    return g / scale
+
+
+def balanced_class_weights(paths: list, classes: list) -> np.ndarray:
+    """The reference's balanced class weights (cli/train.py): ``total / (len(classes) * count)`` over the files of ``paths`` whose folder
+    is a class, float64 ``[C]``.  A class without a file counts as 1, as the reference's ``label_counts.get(i, 1)`` does."""
+    col = {c: i for i, c in enumerate(classes)}
+    counts = np.zeros(len(classes), np.int64)
+    for p in paths:
+        i = col.get(os.path.basename(os.path.dirname(p)), -1)
+        if i >= 0:
+            counts[i] += 1
+    return float(counts.sum()) / (len(classes) * np.maximum(counts, 1).astype(np.float64))
+
+
+def row_weights(Y: np.ndarray, class_weights: np.ndarray) -> np.ndarray:
+    """One weight per row, float32 ``[N]``: ``class_weights[argmax(Y[i])]`` for rows with a positive target (the first maximum, as
+    Keras' ``class_weight`` takes it), ``1.0`` for all-zero rows (the noise folders).  A departure from Keras, which takes ``argmax`` of
+    an all-zero row too and so gives the noise rows class 0's weight by accident."""
+    Y = np.asarray(Y)
+    w = np.asarray(class_weights, np.float64)[np.argmax(Y, axis=1)]
+    return np.where(Y.max(axis=1) > 0, w, 1.0).astype(np.float32)
+
+
+def upsample_rows(file_index: np.ndarray, multiplicity: np.ndarray) -> np.ndarray:
+    """Row numbers for ``rows=``: every row repeated by the multiplicity of its file, in ascending row order (int32)."""
+    file_index = np.asarray(file_index, np.int64)
+    return np.repeat(np.arange(file_index.shape[0], dtype=np.int32), np.asarray(multiplicity, np.int64)[file_index])
+
+
+def _check_weights_rows(n: int, sample_weight, rows) -> tuple:
+    """``sample_weight`` as float32 ``[n]`` and ``rows`` as int32 ``[M]`` (or ``None`` each), refused when of another shape or out of range."""
+    if sample_weight is not None:
+        sample_weight = np.asarray(sample_weight)
+        if sample_weight.shape != (n,) or sample_weight.dtype.kind not in "fiu":
+            raise ValueError(f"sample_weight must be one number per row of X, shape ({n},), got {sample_weight.shape}")
+        sample_weight = np.ascontiguousarray(sample_weight, np.float32)
+        if not (np.isfinite(sample_weight).all() and (sample_weight >= 0).all()):
+            raise ValueError("sample_weight must be finite and >= 0")
+    if rows is not None:
+        rows = np.asarray(rows)
+        if rows.ndim != 1 or rows.shape[0] < 1 or rows.dtype.kind not in "iu":
+            raise ValueError(f"rows must be a non-empty 1-D integer array of row numbers into X, got shape {rows.shape} of {rows.dtype}")
+        if rows.min() < 0 or rows.max() >= n:
+            raise ValueError(f"rows must lie in 0..{n - 1}")
+        if rows.shape[0] > 0x7FFFFFFF:
+            raise ValueError("rows is too long")
+        rows = np.ascontiguousarray(rows, np.int32)
+    return sample_weight, rows
 
 
 def optimizer_step(params: np.ndarray, g: np.ndarray, state: dict, optimizer: str, lr_t, alpha_t, weight_decay=0.0, eps=ADAM_EPS) -> np.ndarray:
@@ -179,13 +285,19 @@ def _check_label_smoothing(label_smoothing):
     return float(label_smoothing)
 
 
-def _fit_loop(backend, n: int, epochs: int, batch: int, seed: int, patience: int, has_val: bool) -> dict:
+def _epoch_rows(seed: int, epoch: int, n: int, rows) -> np.ndarray:
+    """The row numbers of epoch ``epoch`` in training order: a permutation of ``0 .. n-1``, or of the entries of ``rows`` (``n = len(rows)``)."""
+    perm = epoch_permutation(seed, epoch, n)
+    return perm if rows is None else np.ascontiguousarray(rows[perm])
+
+
+def _fit_loop(backend, n: int, epochs: int, batch: int, seed: int, patience: int, has_val: bool, rows=None) -> dict:
     """Epochs, validation and early stopping, shared by the device and the numpy fit.  ``backend``: ``epoch(perm) -> step losses``,
-    ``val_loss()``, ``get() -> (W, b)``, ``set(W, b)``."""
+    ``val_loss()``, ``get() -> (W, b)``, ``set(W, b)``.  ``n``: the length of an epoch (``len(rows)`` with ``rows``)."""
     history = {"loss": [], "val_loss": [], "step_loss": [], "best_epoch": None, "stopped_epoch": None}
     best, best_weights, wait = math.inf, None, 0
     for epoch in range(epochs):
-        losses = np.asarray(backend.epoch(epoch_permutation(seed, epoch, n)), np.float64)
+        losses = np.asarray(backend.epoch(_epoch_rows(seed, epoch, n, rows)), np.float64)
         history["step_loss"].append(losses)
         history["loss"].append(float(losses.mean()))
         if not has_val:
@@ -306,8 +418,10 @@ class ProbeHead:
 
 # -- the specification ----------------------------------------------------------------------------------------------------------------
 class _NumpyBackend:
-    def __init__(self, X, Y, Xv, Yv, W, b, cfg, dtype):
+    def __init__(self, X, Y, Xv, Yv, W, b, cfg, dtype, sample_weight=None):
         self.X, self.Y, self.Xv, self.Yv, self.cfg, self.dt = X, Y, Xv, Yv, cfg, dtype
+        self.w = None if sample_weight is None else np.asarray(sample_weight).astype(dtype)   # [rows of X], indexed like Y
+        self.loss_kw = dict(loss=cfg.get("loss", "auto"), focal_gamma=cfg.get("focal_gamma", 2.0))
         self.P = np.concatenate([W, b[None, :]]).astype(dtype)   # the bias is row D, as on the device
         self.state = {"m": np.zeros_like(self.P), "v": np.zeros_like(self.P)}
         self.t = 0
@@ -323,17 +437,18 @@ class _NumpyBackend:
             y = self.Y[idx]
             if c.get("label_smoothing", 0.0) > 0:
                 y = smooth_targets(y, c["label_smoothing"], c["activation"])
-            losses.append(float(probe_loss(P, y, c["activation"])))
-            G = (P - y) / dt(B if c["activation"] == "softmax" else B * y.shape[1])
+            w = None if self.w is None else self.w[idx]
+            losses.append(float(probe_loss(P, y, c["activation"], sample_weight=w, **self.loss_kw)))
+            G = probe_loss_gradient(P, y, c["activation"], sample_weight=w, **self.loss_kw)
             g = clip_by_global_norm(xd.T @ G, c["clipnorm"])
             lr_t, alpha_t = step_sizes(c["lr"], self.t, c["total"])
             self.P = optimizer_step(self.P, g, self.state, c["optimizer"], np.float32(lr_t), np.float32(alpha_t), np.float32(c["weight_decay"]))
             self.t += 1
         return losses
 
-    def val_loss(self):
-        D = self.X.shape[1]
-        return probe_loss(head_scores(self.Xv, self.P[:D], self.P[D], self.cfg["activation"]), self.Yv, self.cfg["activation"])
+    def val_loss(self):   # the loss that was asked for, never weighted, never smoothed
+        D = self.P.shape[0] - 1
+        return probe_loss(head_scores(self.Xv, self.P[:D], self.P[D], self.cfg["activation"]), self.Yv, self.cfg["activation"], **self.loss_kw)
 
     def get(self):
         return self.P[:-1].copy(), self.P[-1].copy()
@@ -344,20 +459,25 @@ class _NumpyBackend:
 
 def fit_probe_reference(X, Y, X_val=None, Y_val=None, *, activation="sigmoid", epochs=50, batch_size=32, learning_rate=1e-3, optimizer="adam",
                         weight_decay=0.0, clipnorm=1.0, dropout=0.5, patience=10, seed=42, dtype=np.float64, class_names=None,
-                        label_smoothing=0.0) -> ProbeHead:
-    """The procedure of ``fit_probe`` in numpy, all arithmetic in ``dtype``.  ``history["W"]`` / ``["b"]`` keep the result in ``dtype``."""
+                        label_smoothing=0.0, loss="auto", focal_gamma=2.0, sample_weight=None, rows=None) -> ProbeHead:
+    """The procedure of ``fit_probe`` in numpy, all arithmetic in ``dtype``.  ``history["W"]`` / ``["b"]`` keep the result in ``dtype``.
+    ``loss`` / ``focal_gamma`` / ``sample_weight`` / ``rows``: see ``fit_probe``."""
     X, Y = np.asarray(X), np.asarray(Y)
     _check_fit_args(X, Y, activation, optimizer, batch_size, dropout, epochs)
     label_smoothing = _check_label_smoothing(label_smoothing)
-    n, D = X.shape
+    loss, focal_gamma = _check_loss(loss, focal_gamma, activation)
+    sample_weight, rows = _check_weights_rows(X.shape[0], sample_weight, rows)
+    D = X.shape[1]
+    n = X.shape[0] if rows is None else len(rows)   # the length of an epoch
     batch = min(int(batch_size), n)
     has_val = X_val is not None and len(X_val) > 0
     W0, b0 = init_head(D, Y.shape[1], seed)
     cfg = dict(activation=activation, optimizer=optimizer, batch=batch, seed=int(seed), dropout=float(dropout), clipnorm=float(np.float32(clipnorm)),
-               lr=float(learning_rate), weight_decay=float(weight_decay), total=int(epochs) * math.ceil(n / batch), label_smoothing=label_smoothing)
+               lr=float(learning_rate), weight_decay=float(weight_decay), total=int(epochs) * math.ceil(n / batch), label_smoothing=label_smoothing,
+               loss=loss, focal_gamma=focal_gamma)
     be = _NumpyBackend(X.astype(dtype), Y.astype(dtype), np.asarray(X_val).astype(dtype) if has_val else None,
-                       np.asarray(Y_val).astype(dtype) if has_val else None, W0, b0, cfg, np.dtype(dtype).type)
-    history = _fit_loop(be, n, int(epochs), batch, int(seed), int(patience), has_val)
+                       np.asarray(Y_val).astype(dtype) if has_val else None, W0, b0, cfg, np.dtype(dtype).type, sample_weight)
+    history = _fit_loop(be, n, int(epochs), batch, int(seed), int(patience), has_val, rows)
     W, b = be.get()
     history["W"], history["b"] = W, b
     return ProbeHead(W, b, activation, list(class_names or []), history)
@@ -365,7 +485,10 @@ def fit_probe_reference(X, Y, X_val=None, Y_val=None, *, activation="sigmoid", e
 
 # -- the device fit -------------------------------------------------------------------------------------------------------------------
 class _DeviceBackend:
-    def __init__(self, ctx, X, Y, Xv, Yv, W, b, cfg):
+    """``bn_probe_*`` over resident ``X`` / ``Y``.  ``self.n`` is the number of rows of ``X``, ``self.m`` the length of an epoch: the two
+    differ when the epoch runs over ``rows`` with repeats (``epoch_len``).  ``cfg`` may carry ``loss`` / ``focal_gamma``."""
+
+    def __init__(self, ctx, X, Y, Xv, Yv, W, b, cfg, sample_weight=None, epoch_len=None):
         import ctypes
 
         import torch
@@ -378,7 +501,7 @@ class _DeviceBackend:
         self.W, self.b = self._dev(W), self._dev(b)
         self.n, self.D = self.X.shape
         self.C = self.Y.shape[1]
-        self.steps = math.ceil(self.n / cfg["batch"])
+        self._epoch_shape(sample_weight, epoch_len)
         self.step_loss = torch.empty(self.steps, dtype=torch.float32, device=self.dev)
         self.val = torch.empty(1, dtype=torch.float32, device=self.dev)
         h = ctypes.c_void_p()
@@ -387,6 +510,20 @@ class _DeviceBackend:
                                                cfg["lr"], cfg["weight_decay"], cfg["clipnorm"], cfg["dropout"], cfg["seed"] & 0xFFFFFFFF, cfg["total"],
                                                self.W.data_ptr(), self.b.data_ptr(), ctypes.byref(h), self._stream()))
         self.handle = h
+        if cfg.get("loss", "auto") != "auto":   # (the default is the probe's own: nothing to set)
+            try:
+                _hip.check(ctx.lib.bn_probe_set_loss(h, _hip.PROBE_LOSSES[cfg["loss"]], float(cfg.get("focal_gamma", 2.0))))
+            except Exception:
+                self.close()
+                raise
+
+    def _epoch_shape(self, sample_weight, epoch_len):
+        """The row weights ``[self.n]`` on the device (or ``None``) and the epoch's length ``self.m`` with its step count."""
+        self.w = self._dev(sample_weight)
+        if self.w is not None and tuple(self.w.shape) != (self.n,):
+            raise ValueError(f"sample_weight must have shape ({self.n},), got {tuple(self.w.shape)}")
+        self.m = self.n if epoch_len is None else int(epoch_len)
+        self.steps = math.ceil(self.m / self.cfg["batch"])
 
     def _dev(self, a):
         if a is None:
@@ -400,11 +537,20 @@ class _DeviceBackend:
 
         return ctypes.c_void_p(self.torch.cuda.current_stream(self.dev).cuda_stream)
 
+    def _check_perm(self, perm):
+        if perm.shape != (self.m,) or perm.dtype != np.int32:
+            raise ValueError(f"an epoch takes {self.m} int32 row numbers, got {perm.shape} of {perm.dtype}")
+
     def epoch(self, perm):
+        self._check_perm(perm)
         with self.torch.cuda.device(self.dev):
             d_perm = self.torch.from_numpy(perm).to(self.dev)
-            self.hip.check(self.ctx.lib.bn_probe_epoch(self.handle, self.X.data_ptr(), self.Y.data_ptr(), d_perm.data_ptr(), self.n, self.cfg["batch"],
-                                                       self.step_loss.data_ptr(), self._stream()))
+            if self.w is None:
+                self.hip.check(self.ctx.lib.bn_probe_epoch(self.handle, self.X.data_ptr(), self.Y.data_ptr(), d_perm.data_ptr(), self.m, self.cfg["batch"],
+                                                           self.step_loss.data_ptr(), self._stream()))
+            else:
+                self.hip.check(self.ctx.lib.bn_probe_epoch_weighted(self.handle, self.X.data_ptr(), self.Y.data_ptr(), self.w.data_ptr(), d_perm.data_ptr(),
+                                                                    self.m, self.cfg["batch"], self.step_loss.data_ptr(), self._stream()))
             return self.step_loss.cpu().numpy()   # (synchronises: d_perm outlives the epoch)
 
     def val_loss(self):
@@ -431,20 +577,34 @@ class _DeviceBackend:
 
 
 def fit_probe(ctx_or_runner, X, Y, X_val=None, Y_val=None, *, activation="sigmoid", epochs=50, batch_size=32, learning_rate=1e-3, optimizer="adam",
-              weight_decay=0.0, clipnorm=1.0, dropout=0.5, patience=10, seed=42, class_names=None, label_smoothing=0.0) -> ProbeHead:
+              weight_decay=0.0, clipnorm=1.0, dropout=0.5, patience=10, seed=42, class_names=None, label_smoothing=0.0, loss="auto", focal_gamma=2.0,
+              sample_weight=None, rows=None) -> ProbeHead:
     """Train ``scores = act(dropout(x) W + b)`` on embedding rows ``X [N, D]`` with targets ``Y [N, C]`` (float: one-hot, multi-hot or
     all-zero rows) on the device.  ``X`` / ``Y`` may be numpy arrays or CUDA tensors; they stay on the device for the whole fit, per epoch
     the host uploads one permutation and reads back the per-step losses.  The defaults are the reference CLI's.  The same inputs and seed
-    give the same bits on every run.  ``label_smoothing > 0`` (``smooth_targets``) trains through the sweep's kernels as a sweep of one trial."""
+    give the same bits on every run.  ``label_smoothing > 0`` (``smooth_targets``) trains through the sweep's kernels as a sweep of one trial.
+
+    For long-tailed sets, all off by default (the defaults run the launches, and give the bits, of a call without them):
+
+    * ``loss="focal"`` with ``focal_gamma >= 0``: the focal form of the sigmoid head's loss (``probe_loss``), in training and in the
+      validation loss.  Smoothing comes first: the focal loss sees the smoothed target.  Not with softmax.
+    * ``sample_weight``: float ``[N]``, one weight per row of ``X`` (``row_weights``), multiplied into the training loss and its gradient;
+      the means still divide by rows x classes (or rows).  The validation loss is never weighted.
+    * ``rows``: int ``[M]``, row numbers into ``X``, repeats allowed (``upsample_rows``).  An epoch then runs over
+      ``rows[epoch_permutation(seed, e, M)]``; the steps per epoch and the short last batch follow ``M``.  ``X``, ``Y`` and
+      ``sample_weight`` are indexed through it and nothing is duplicated on the device.  The dropout draw is per position in the batch,
+      so two copies of a row in one batch get different masks."""
     from birdnet_stm32 import _hip
 
     _check_fit_args(X, Y, activation, optimizer, batch_size, dropout, epochs)
+    loss, focal_gamma = _check_loss(loss, focal_gamma, activation)
+    sample_weight, rows = _check_weights_rows(int(X.shape[0]), sample_weight, rows)
     if _check_label_smoothing(label_smoothing) > 0:
         trial = ProbeTrial(learning_rate=learning_rate, optimizer=optimizer, weight_decay=weight_decay, clipnorm=clipnorm, dropout=dropout,
                            label_smoothing=label_smoothing)
         return fit_probe_sweep(ctx_or_runner, X, Y, X_val, Y_val, [trial], activation=activation, epochs=epochs, batch_size=batch_size, patience=patience,
-                               seed=seed, class_names=class_names).heads[0]
-    n, D = int(X.shape[0]), int(X.shape[1])
+                               seed=seed, class_names=class_names, loss=loss, focal_gamma=focal_gamma, sample_weight=sample_weight, rows=rows).heads[0]
+    n, D = (int(X.shape[0]) if rows is None else len(rows)), int(X.shape[1])   # n: the length of an epoch
     C = int(Y.shape[1])
     if not (1 <= D <= _hip.PROBE_MAX_D and 1 <= C <= _hip.PROBE_MAX_C):
         raise ValueError(f"the device path takes 1 <= D <= {_hip.PROBE_MAX_D} and 1 <= C <= {_hip.PROBE_MAX_C}, got D={D} C={C}")
@@ -453,10 +613,10 @@ def fit_probe(ctx_or_runner, X, Y, X_val=None, Y_val=None, *, activation="sigmoi
     has_val = X_val is not None and len(X_val) > 0
     W0, b0 = init_head(D, C, seed)
     cfg = dict(activation=activation, optimizer=optimizer, batch=batch, seed=int(seed), dropout=float(dropout), clipnorm=float(clipnorm),
-               lr=float(learning_rate), weight_decay=float(weight_decay), total=int(epochs) * math.ceil(n / batch))
-    be = _DeviceBackend(ctx, X, Y, X_val if has_val else None, Y_val if has_val else None, W0, b0, cfg)
+               lr=float(learning_rate), weight_decay=float(weight_decay), total=int(epochs) * math.ceil(n / batch), loss=loss, focal_gamma=focal_gamma)
+    be = _DeviceBackend(ctx, X, Y, X_val if has_val else None, Y_val if has_val else None, W0, b0, cfg, sample_weight, n)
     try:
-        history = _fit_loop(be, n, int(epochs), batch, int(seed), int(patience), has_val)
+        history = _fit_loop(be, n, int(epochs), batch, int(seed), int(patience), has_val, rows)
         W, b = be.get()
         W, b = W.cpu().numpy(), b.cpu().numpy()
     finally:
@@ -520,7 +680,7 @@ def _check_trials(trials) -> list:
 class _SweepBackend(_DeviceBackend):
     """``bn_probe_sweep_*`` over resident ``X`` / ``Y``: every trial of the sweep takes the same step in the same launches."""
 
-    def __init__(self, ctx, X, Y, Xv, Yv, W, b, cfg, trials):
+    def __init__(self, ctx, X, Y, Xv, Yv, W, b, cfg, trials, sample_weight=None, epoch_len=None):
         import ctypes
 
         import torch
@@ -533,7 +693,7 @@ class _SweepBackend(_DeviceBackend):
         self.W, self.b = self._dev(W), self._dev(b)
         self.n, self.D = self.X.shape
         self.C, self.T = self.Y.shape[1], len(trials)
-        self.steps = math.ceil(self.n / cfg["batch"])
+        self._epoch_shape(sample_weight, epoch_len)
         self.step_loss = torch.empty((self.steps, self.T), dtype=torch.float32, device=self.dev)
         self.val = torch.empty(self.T, dtype=torch.float32, device=self.dev)
         self.t = 0
@@ -544,17 +704,29 @@ class _SweepBackend(_DeviceBackend):
             _hip.check(ctx.lib.bn_probe_sweep_create(ctx.handle, self.D, self.C, _hip.PROBE_ACTIVATIONS[cfg["activation"]], self.T, rows, cfg["seed"] & 0xFFFFFFFF,
                                                      cfg["total"], self.W.data_ptr(), self.b.data_ptr(), ctypes.byref(h), self._stream()))
         self.handle = h
+        if cfg.get("loss", "auto") != "auto":
+            try:
+                _hip.check(ctx.lib.bn_probe_sweep_set_loss(h, _hip.PROBE_LOSSES[cfg["loss"]], float(cfg.get("focal_gamma", 2.0))))
+            except Exception:
+                self.close()
+                raise
 
     def _mask(self, mask):
         return self.torch.from_numpy(np.ascontiguousarray(mask, np.uint8)).to(self.dev)
 
     def epoch(self, perm, active):
         """One epoch of the active trials: step losses ``[steps, T]`` float32 (columns of inactive trials are not written)."""
+        self._check_perm(perm)
         sizes = device_step_sizes([t.learning_rate for t in self.trials], self.t, self.steps, self.cfg["total"])
         with self.torch.cuda.device(self.dev):
             d_perm, d_sizes, d_active = self.torch.from_numpy(perm).to(self.dev), self.torch.from_numpy(sizes).to(self.dev), self._mask(active)
-            self.hip.check(self.ctx.lib.bn_probe_sweep_epoch(self.handle, self.X.data_ptr(), self.Y.data_ptr(), d_perm.data_ptr(), self.n, self.cfg["batch"],
-                                                             d_sizes.data_ptr(), d_active.data_ptr(), self.step_loss.data_ptr(), self._stream()))
+            if self.w is None:
+                self.hip.check(self.ctx.lib.bn_probe_sweep_epoch(self.handle, self.X.data_ptr(), self.Y.data_ptr(), d_perm.data_ptr(), self.m, self.cfg["batch"],
+                                                                 d_sizes.data_ptr(), d_active.data_ptr(), self.step_loss.data_ptr(), self._stream()))
+            else:
+                self.hip.check(self.ctx.lib.bn_probe_sweep_epoch_weighted(self.handle, self.X.data_ptr(), self.Y.data_ptr(), self.w.data_ptr(), d_perm.data_ptr(),
+                                                                          self.m, self.cfg["batch"], d_sizes.data_ptr(), d_active.data_ptr(),
+                                                                          self.step_loss.data_ptr(), self._stream()))
             self.t += self.steps
             return self.step_loss.cpu().numpy()   # (synchronises: the uploads outlive the epoch)
 
@@ -586,13 +758,15 @@ class _SweepBackend(_DeviceBackend):
 
 
 def fit_probe_sweep(ctx_or_runner, X, Y, X_val=None, Y_val=None, trials=(), *, activation="sigmoid", epochs=50, batch_size=32, patience=10, seed=42,
-                    class_names=None) -> SweepResult:
+                    class_names=None, loss="auto", focal_gamma=2.0, sample_weight=None, rows=None) -> SweepResult:
     """``fit_probe`` for every ``ProbeTrial`` of ``trials`` at once (at most ``_hip.PROBE_SWEEP_MAX_TRIALS``).  The trials share the rows, the
     initial weights, the permutations and the dropout draws; one training step of all of them is the launches of a single fit's step with
     the trial as one more grid axis, which is what makes a sweep cheap where one fit is launch-bound.  Early stopping is ``fit_probe``'s
     rule per trial: a stopped trial goes inactive (its weights and its best-epoch snapshot, kept on the device, no longer move) and the
     others go on.  A trial without label smoothing gives the bits of ``fit_probe`` with its hyperparameters: weights, bias, step losses
-    and validation losses.  The validation loss is never smoothed, so trials compare."""
+    and validation losses.  The validation loss is never smoothed, so trials compare.  ``loss`` / ``focal_gamma`` / ``sample_weight`` /
+    ``rows`` are ``fit_probe``'s and shared by all trials (no part of a ``ProbeTrial``): a trial's smoothing comes first, the focal loss
+    sees the smoothed target; the validation loss is the focal one, unweighted, unsmoothed."""
     from birdnet_stm32 import _hip
 
     trials = _check_trials(trials)
@@ -600,23 +774,25 @@ def fit_probe_sweep(ctx_or_runner, X, Y, X_val=None, Y_val=None, trials=(), *, a
         raise ValueError(f"{len(trials)} trials: a sweep takes at most {_hip.PROBE_SWEEP_MAX_TRIALS}")
     # shapes, activation, batch and epochs; every trial's own fields were checked when it was made (ProbeTrial.__post_init__)
     _check_fit_args(X, Y, activation, trials[0].optimizer, batch_size, trials[0].dropout, epochs)
-    n, D, C, T = int(X.shape[0]), int(X.shape[1]), int(Y.shape[1]), len(trials)
+    loss, focal_gamma = _check_loss(loss, focal_gamma, activation)
+    sample_weight, rows = _check_weights_rows(int(X.shape[0]), sample_weight, rows)
+    n, D, C, T = (int(X.shape[0]) if rows is None else len(rows)), int(X.shape[1]), int(Y.shape[1]), len(trials)   # n: the length of an epoch
     if not (1 <= D <= _hip.PROBE_MAX_D and 1 <= C <= _hip.PROBE_MAX_C):
         raise ValueError(f"the device path takes 1 <= D <= {_hip.PROBE_MAX_D} and 1 <= C <= {_hip.PROBE_MAX_C}, got D={D} C={C}")
     ctx = getattr(ctx_or_runner, "ctx", ctx_or_runner)
     batch, epochs, patience = min(int(batch_size), n), int(epochs), int(patience)
     has_val = X_val is not None and len(X_val) > 0
     W0, b0 = init_head(D, C, seed)
-    cfg = dict(activation=activation, batch=batch, seed=int(seed), total=epochs * math.ceil(n / batch))
+    cfg = dict(activation=activation, batch=batch, seed=int(seed), total=epochs * math.ceil(n / batch), loss=loss, focal_gamma=focal_gamma)
     hist = [{"loss": [], "val_loss": [], "step_loss": [], "best_epoch": None, "stopped_epoch": None} for _ in range(T)]
     best, wait, active = [math.inf] * T, [0] * T, np.ones(T, bool)
-    be = _SweepBackend(ctx, X, Y, X_val if has_val else None, Y_val if has_val else None, W0, b0, cfg, trials)
+    be = _SweepBackend(ctx, X, Y, X_val if has_val else None, Y_val if has_val else None, W0, b0, cfg, trials, sample_weight, n)
     try:
         for epoch in range(epochs):
             if not active.any():
                 break
             running = np.flatnonzero(active)
-            losses = be.epoch(epoch_permutation(int(seed), epoch, n), active)
+            losses = be.epoch(_epoch_rows(int(seed), epoch, n, rows), active)
             for t in running:
                 col = np.ascontiguousarray(losses[:, t], np.float64)
                 hist[t]["step_loss"].append(col)
@@ -647,11 +823,12 @@ def fit_probe_sweep(ctx_or_runner, X, Y, X_val=None, Y_val=None, trials=(), *, a
 
 
 def fit_probe_sweep_reference(X, Y, X_val=None, Y_val=None, trials=(), *, activation="sigmoid", epochs=50, batch_size=32, patience=10, seed=42,
-                              dtype=np.float64, class_names=None) -> SweepResult:
+                              dtype=np.float64, class_names=None, loss="auto", focal_gamma=2.0, sample_weight=None, rows=None) -> SweepResult:
     """The specification of ``fit_probe_sweep``: ``fit_probe_reference`` once per trial."""
     trials = _check_trials(trials)
     heads = [fit_probe_reference(X, Y, X_val, Y_val, activation=activation, epochs=epochs, batch_size=batch_size, patience=patience, seed=seed, dtype=dtype,
-                                 class_names=class_names, **t.fit_kwargs()) for t in trials]
+                                 class_names=class_names, loss=loss, focal_gamma=focal_gamma, sample_weight=sample_weight, rows=rows, **t.fit_kwargs())
+             for t in trials]
     return SweepResult(heads, trials, _best_trial(heads))
 
 
@@ -718,7 +895,7 @@ def augmented_embeddings(runner, inputs, plan, out=None, slice_buf=None):
 class _AugmentedDeviceBackend(_DeviceBackend):
     """The device fit over rows that change per epoch: ``epoch`` first builds that epoch's ``X`` / ``Y`` in place, then runs the plain epoch."""
 
-    def __init__(self, runner, inputs, Y, Xv, Yv, W, b, cfg, augment, F, W_in):
+    def __init__(self, runner, inputs, Y, Xv, Yv, W, b, cfg, augment, F, W_in, sample_weight=None, epoch_len=None):
         import time
 
         import torch
@@ -726,7 +903,7 @@ class _AugmentedDeviceBackend(_DeviceBackend):
         self.runner, self.inputs, self.aug, self.F, self.W_in, self.time = runner, inputs, augment, F, W_in, time
         self.Y_host = np.ascontiguousarray(Y, np.float32)
         n, D = int(inputs.shape[0]), int(runner.embedding_info()["dim"])
-        super().__init__(runner.ctx, torch.zeros((n, D), dtype=torch.float32, device=inputs.device), self.Y_host, Xv, Yv, W, b, cfg)
+        super().__init__(runner.ctx, torch.zeros((n, D), dtype=torch.float32, device=inputs.device), self.Y_host, Xv, Yv, W, b, cfg, sample_weight, epoch_len)
         self.slice_buf = torch.empty((min(int(runner.max_batch), n), int(inputs.shape[1])), dtype=torch.float32, device=inputs.device)
         self.epochs_done, self.augment_seconds = 0, []
 
@@ -745,7 +922,7 @@ class _AugmentedDeviceBackend(_DeviceBackend):
 
 def fit_probe_augmented(runner, inputs, Y, X_val=None, Y_val=None, *, augment, input_shape, activation="sigmoid", epochs=50, batch_size=32,
                         learning_rate=1e-3, optimizer="adam", weight_decay=0.0, clipnorm=1.0, dropout=0.5, patience=10, seed=42,
-                        class_names=None) -> ProbeHead:
+                        class_names=None, loss="auto", focal_gamma=2.0, sample_weight=None, rows=None) -> ProbeHead:
     """``fit_probe`` on fresh embeddings per epoch (reference: training/linear_probe.py:112-125, whose training loader masks and mixes).
 
     ``inputs [N, F * W]``: the un-augmented model inputs of the training rows (``HipRunner.model_inputs_device``; a CUDA tensor stays
@@ -753,7 +930,12 @@ def fit_probe_augmented(runner, inputs, Y, X_val=None, Y_val=None, *, augment, i
     ``training.augment.augment_plan(N, F, W, augment, seed, e)``, augments on the device (``bn_augment_inputs``), embeds the rows again with
     the frozen backbone and runs the plain epoch (same permutation, same dropout draws) on them with ``mixed_targets``.  ``X_val`` are
     embeddings of un-augmented validation rows, computed once by the caller.  ``history["augment_seconds"]`` holds the per-epoch time of
-    plan + augmentation + backbone.  The same inputs and seed give the same bits on every run."""
+    plan + augmentation + backbone.  The same inputs and seed give the same bits on every run.
+
+    ``loss`` / ``focal_gamma`` / ``sample_weight`` / ``rows``: as ``fit_probe``.  The plan of an epoch is drawn per row of ``inputs``, not
+    per entry of ``rows``: every row is augmented and embedded once per epoch, and the copies of a row that ``rows`` repeats share that
+    epoch's augmentation (their dropout masks still differ).  A mixed row's weight is its own: ``sample_weight[i]`` of the row it is
+    built on, whatever rows were mixed into it."""
     import torch
 
     from birdnet_stm32 import _hip
@@ -765,6 +947,9 @@ def fit_probe_augmented(runner, inputs, Y, X_val=None, Y_val=None, *, augment, i
         raise ValueError(f"inputs must be [N, F * W], got {tuple(inputs.shape)}")
     n, D = int(inputs.shape[0]), int(runner.embedding_info()["dim"])
     _check_fit_args(_Shape(n, D), Y, activation, optimizer, batch_size, dropout, epochs)
+    loss, focal_gamma = _check_loss(loss, focal_gamma, activation)
+    sample_weight, rows = _check_weights_rows(n, sample_weight, rows)
+    m = n if rows is None else len(rows)   # the length of an epoch
     C = int(Y.shape[1])
     if not (1 <= D <= _hip.PROBE_MAX_D and 1 <= C <= _hip.PROBE_MAX_C):
         raise ValueError(f"the device path takes 1 <= D <= {_hip.PROBE_MAX_D} and 1 <= C <= {_hip.PROBE_MAX_C}, got D={D} C={C}")
@@ -774,14 +959,15 @@ def fit_probe_augmented(runner, inputs, Y, X_val=None, Y_val=None, *, augment, i
         inputs = torch.from_numpy(np.ascontiguousarray(inputs, np.float32)).to(runner.device)
     if isinstance(Y, torch.Tensor):
         Y = Y.cpu().numpy()
-    batch = min(int(batch_size), n)
+    batch = min(int(batch_size), m)
     has_val = X_val is not None and len(X_val) > 0
     W0, b0 = init_head(D, C, seed)
     cfg = dict(activation=activation, optimizer=optimizer, batch=batch, seed=int(seed), dropout=float(dropout), clipnorm=float(clipnorm),
-               lr=float(learning_rate), weight_decay=float(weight_decay), total=int(epochs) * math.ceil(n / batch))
-    be = _AugmentedDeviceBackend(runner, inputs.contiguous(), Y, X_val if has_val else None, Y_val if has_val else None, W0, b0, cfg, augment, F, W_in)
+               lr=float(learning_rate), weight_decay=float(weight_decay), total=int(epochs) * math.ceil(m / batch), loss=loss, focal_gamma=focal_gamma)
+    be = _AugmentedDeviceBackend(runner, inputs.contiguous(), Y, X_val if has_val else None, Y_val if has_val else None, W0, b0, cfg, augment, F, W_in,
+                                 sample_weight, m)
     try:
-        history = _fit_loop(be, n, int(epochs), batch, int(seed), int(patience), has_val)
+        history = _fit_loop(be, m, int(epochs), batch, int(seed), int(patience), has_val, rows)
         W, b = be.get()
         W, b = W.cpu().numpy(), b.cpu().numpy()
         history["augment_seconds"] = list(be.augment_seconds)
@@ -791,9 +977,9 @@ def fit_probe_augmented(runner, inputs, Y, X_val=None, Y_val=None, *, augment, i
 
 
 class _AugmentedNumpyBackend(_NumpyBackend):
-    def __init__(self, embed, inputs, Y, Xv, Yv, W, b, cfg, dtype, augment, F, W_in):
+    def __init__(self, embed, inputs, Y, Xv, Yv, W, b, cfg, dtype, augment, F, W_in, sample_weight=None):
         self.embed, self.inputs, self.Y_host, self.aug, self.F, self.W_in, self.epochs_done = embed, inputs, Y, augment, F, W_in, 0
-        super().__init__(None, None, Xv, Yv, W, b, cfg, dtype)
+        super().__init__(None, None, Xv, Yv, W, b, cfg, dtype, sample_weight)
 
     def epoch(self, perm):
         from birdnet_stm32.training.augment import augment_plan, augment_reference, mixed_targets
@@ -804,28 +990,27 @@ class _AugmentedNumpyBackend(_NumpyBackend):
         self.epochs_done += 1
         return super().epoch(perm)
 
-    def val_loss(self):
-        D = self.P.shape[0] - 1
-        return probe_loss(head_scores(self.Xv, self.P[:D], self.P[D], self.cfg["activation"]), self.Yv, self.cfg["activation"])
-
 
 def fit_probe_augmented_reference(embed, inputs, Y, X_val=None, Y_val=None, *, augment, input_shape, activation="sigmoid", epochs=50, batch_size=32,
                                   learning_rate=1e-3, optimizer="adam", weight_decay=0.0, clipnorm=1.0, dropout=0.5, patience=10, seed=42,
-                                  dtype=np.float64, class_names=None) -> ProbeHead:
+                                  dtype=np.float64, class_names=None, loss="auto", focal_gamma=2.0, sample_weight=None, rows=None) -> ProbeHead:
     """The procedure of ``fit_probe_augmented`` in numpy over a caller-supplied ``embed(inputs [N, F * W] float32) -> X [N, D]``."""
     inputs, Y = np.ascontiguousarray(inputs, np.float32), np.asarray(Y)
     F, W_in = _check_augmented_args(augment, activation, input_shape, inputs.shape[1] if inputs.ndim == 2 else None)
     n = inputs.shape[0]
     D = int(np.asarray(embed(inputs[:1])).shape[1])
     _check_fit_args(_Shape(n, D), Y, activation, optimizer, batch_size, dropout, epochs)
-    batch = min(int(batch_size), n)
+    loss, focal_gamma = _check_loss(loss, focal_gamma, activation)
+    sample_weight, rows = _check_weights_rows(n, sample_weight, rows)
+    m = n if rows is None else len(rows)   # the length of an epoch
+    batch = min(int(batch_size), m)
     has_val = X_val is not None and len(X_val) > 0
     W0, b0 = init_head(D, Y.shape[1], seed)
     cfg = dict(activation=activation, optimizer=optimizer, batch=batch, seed=int(seed), dropout=float(dropout), clipnorm=float(np.float32(clipnorm)),
-               lr=float(learning_rate), weight_decay=float(weight_decay), total=int(epochs) * math.ceil(n / batch))
+               lr=float(learning_rate), weight_decay=float(weight_decay), total=int(epochs) * math.ceil(m / batch), loss=loss, focal_gamma=focal_gamma)
     be = _AugmentedNumpyBackend(embed, inputs, Y, np.asarray(X_val).astype(dtype) if has_val else None,
-                                np.asarray(Y_val).astype(dtype) if has_val else None, W0, b0, cfg, np.dtype(dtype).type, augment, F, W_in)
-    history = _fit_loop(be, n, int(epochs), batch, int(seed), int(patience), has_val)
+                                np.asarray(Y_val).astype(dtype) if has_val else None, W0, b0, cfg, np.dtype(dtype).type, augment, F, W_in, sample_weight)
+    history = _fit_loop(be, m, int(epochs), batch, int(seed), int(patience), has_val, rows)
     W, b = be.get()
     history["W"], history["b"] = W, b
     return ProbeHead(W, b, activation, list(class_names or []), history)
@@ -890,10 +1075,44 @@ def augmentation_from_args(args):
     return aug
 
 
+def imbalance_from_args(args) -> dict:
+    """``--loss`` / ``--focal_gamma`` / ``--class_weights`` / ``--upsample_ratio`` of ``probe`` as a dict (absent in older namespaces: all
+    off); bad values and focal with softmax are refused here, before anything is loaded."""
+    loss, gamma = _check_loss(getattr(args, "loss", "auto"), getattr(args, "focal_gamma", 2.0), getattr(args, "activation", "sigmoid"))
+    class_weights = getattr(args, "class_weights", "none")
+    if class_weights not in ("none", "balanced"):
+        raise ValueError(f"--class_weights must be none or balanced, not {class_weights!r}")
+    ratio = float(getattr(args, "upsample_ratio", 0.0) or 0.0)
+    if not 0.0 <= ratio <= 1.0:   # (NaN fails too)
+        raise ValueError(f"--upsample_ratio must be 0 (off) or in (0, 1], got {ratio}")
+    return {"loss": loss, "focal_gamma": gamma, "class_weights": class_weights, "upsample_ratio": ratio}
+
+
+def upsample_multiplicity(train_paths: list, classes: list, ratio: float) -> tuple[np.ndarray, list]:
+    """How often each file of ``train_paths`` trains per epoch under ``--upsample_ratio`` (int64 ``[len(train_paths)]``), and the
+    upsampled list of class files the counts come from.  Only the files whose folder is a class go through
+    ``data.dataset.upsample_minority_classes`` (which, like the reference's, drops the others); the files of noise folders keep
+    multiplicity 1.  ``train_paths`` must hold every file once."""
+    from collections import Counter
+
+    from birdnet_stm32.data.dataset import upsample_minority_classes
+
+    known = set(classes)
+    upsampled = upsample_minority_classes([p for p in train_paths if os.path.basename(os.path.dirname(p)) in known], classes, ratio)
+    count = Counter(upsampled)
+    return np.array([count.get(p, 1) for p in train_paths], np.int64), upsampled
+
+
 def run_linear_probe(args, runner=None) -> ProbeHead:
     """The ``probe`` command: ``args.data_path_train/<class>/*`` -> embeddings (the backbone runs once) -> ``fit_probe`` ->
     ``<output>.npz``, ``<output>_labels.txt``, ``<output>_model_config.json`` and ``<output>_history.csv``.  With ``args.tune``:
-    ``training.tune.sample_trials`` -> ``fit_probe_sweep``; the files are the winning trial's, ``<output>_tune.json`` lists all trials."""
+    ``training.tune.sample_trials`` -> ``fit_probe_sweep``; the files are the winning trial's, ``<output>_tune.json`` lists all trials.
+
+    For long-tailed folders (``imbalance_from_args``), in the reference's order: ``--upsample_ratio`` first repeats training files of the
+    small classes (``upsample_multiplicity``; the validation split is never upsampled, and every distinct file is embedded once: the
+    repeats are row numbers, ``upsample_rows``), then ``--class_weights balanced`` counts the upsampled list (``balanced_class_weights``,
+    ``row_weights``), and ``--loss focal`` picks the element loss.  All three go to the plain fit, the sweep of ``--tune`` (shared by
+    every trial) and the augmented fit alike."""
     import time
     from dataclasses import replace
 
@@ -905,6 +1124,7 @@ def run_linear_probe(args, runner=None) -> ProbeHead:
     from birdnet_stm32.training.tune import check_tune_args
 
     augment = augmentation_from_args(args)
+    imb = imbalance_from_args(args)
     check_tune_args(args)
     label_smoothing = _check_label_smoothing(getattr(args, "label_smoothing", 0.0))
     if augment is not None and label_smoothing > 0:
@@ -920,6 +1140,13 @@ def run_linear_probe(args, runner=None) -> ProbeHead:
         raise ValueError(f"{len(classes)} classes: the device path takes at most 4096")
     train_paths, val_paths = split_train_val(paths, args.val_split)
     print(f"[probe] {len(classes)} target classes, {len(train_paths)} training and {len(val_paths)} validation files")
+    multiplicity, counted = None, train_paths
+    if imb["upsample_ratio"] > 0:   # (before the model is loaded: the draws follow the shuffle's on numpy's global generator)
+        multiplicity, counted = upsample_multiplicity(train_paths, classes, imb["upsample_ratio"])
+    class_weights = None
+    if imb["class_weights"] == "balanced":
+        class_weights = balanced_class_weights(counted, classes)
+        print(f"Balanced class weights: min={class_weights.min():.2f}, max={class_weights.max():.2f}")
     if runner is None:
         from birdnet_stm32.models.runners import load_model_runner
 
@@ -955,6 +1182,13 @@ def run_linear_probe(args, runner=None) -> ProbeHead:
     tr, va = keep & is_train, keep & ~is_train
     if not tr.any():
         raise ValueError("no training rows: every training file was unreadable, empty or of a noise folder")
+    n_fit = int(tr.sum())
+    # the fits see the training rows X[tr] / Y[tr]: weights per such row, and the upsampled epoch as row numbers into them
+    imb_kw = dict(loss=imb["loss"], focal_gamma=imb["focal_gamma"],
+                  sample_weight=None if class_weights is None else row_weights(Y[tr], class_weights),
+                  rows=None if multiplicity is None else upsample_rows(np.asarray(emb.file_index)[tr], multiplicity))
+    if multiplicity is not None:
+        print(f"[probe] upsampling at ratio {imb['upsample_ratio']:g}: {n_fit} training rows -> {len(imb_kw['rows'])} rows per epoch")
     t0 = time.perf_counter()
     fit_kw = dict(activation=args.activation, epochs=args.epochs, batch_size=args.batch_size, learning_rate=args.learning_rate,
                   optimizer=args.optimizer, weight_decay=args.weight_decay, clipnorm=args.grad_clip, dropout=args.dropout,
@@ -970,13 +1204,13 @@ def run_linear_probe(args, runner=None) -> ProbeHead:
         tune_seed = args.seed if getattr(args, "tune_seed", None) is None else args.tune_seed
         tuned = fit_probe_sweep(runner, emb.embeddings[tr], Y[tr], emb.embeddings[va], Y[va], sample_trials(args.n_trials, tune_seed, base),
                                 activation=args.activation, epochs=args.epochs, batch_size=args.batch_size, patience=getattr(args, "patience", 10),
-                                seed=args.seed, class_names=classes)
+                                seed=args.seed, class_names=classes, **imb_kw)
         head = tuned.best_head
         auc = macro_roc_auc(Y[va], head.predict(emb.embeddings[va], runner.ctx))
-        tuned = tune_report(tuned, auc)
+        tuned = {**tune_report(tuned, auc), **imb}   # shared by every trial, no part of the search space
     elif augment is None:
         head = fit_probe(runner, emb.embeddings[tr], Y[tr], emb.embeddings[va] if va.any() else None, Y[va] if va.any() else None,
-                         label_smoothing=label_smoothing, **fit_kw)
+                         label_smoothing=label_smoothing, **fit_kw, **imb_kw)
     else:
         import torch
 
@@ -986,7 +1220,7 @@ def run_linear_probe(args, runner=None) -> ProbeHead:
         rows = tr[:n_train]
         inputs = train_inputs if rows.all() else train_inputs[torch.from_numpy(np.flatnonzero(rows)).to(train_inputs.device)]
         head = fit_probe_augmented(runner, inputs, Y[tr], emb.embeddings[va] if va.any() else None, Y[va] if va.any() else None, augment=augment,
-                                   input_shape=runner.input_shape(), **fit_kw)
+                                   input_shape=runner.input_shape(), **fit_kw, **imb_kw)
         del train_inputs, inputs
     t_fit = time.perf_counter() - t0
     out = probe_output_paths(args.output)

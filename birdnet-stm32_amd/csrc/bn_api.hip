@@ -1064,6 +1064,8 @@ struct bn_probe {
     bn_ctx* ctx = nullptr;
     int D = 0, C = 0, act = 0, opt = 0;
     float lr = 0, wd = 0, clip = 0, drop = 0;
+    int loss = BN_PROBE_LOSS_CE;                    // bn_probe_set_loss
+    float gamma = 0;
     uint32_t seed = 0;
     int64_t total = 1, t = 0;                       // steps of the cosine schedule, steps taken
     float *d_params = nullptr, *d_m = nullptr, *d_v = nullptr;   // [(D + 1) * C] each: W, then the bias as row D
@@ -1106,6 +1108,14 @@ void probe_groups(int B, int D, int C, int* groups, int* rows_per_group) {
 size_t probe_n_ss(int D, int C) {
     const size_t E = (size_t)(D + 1) * C;
     return std::max<size_t>((size_t)((D + 1 + 63) / 64) * ((C + 63) / 64), (E + 1023) / 1024);
+}
+
+// bn_probe_set_loss / bn_probe_sweep_set_loss: the checks they share
+int probe_loss_check(int activation, int loss, float focal_gamma) {
+    if (loss != BN_PROBE_LOSS_CE && loss != BN_PROBE_LOSS_FOCAL) return fail(BN_ERR_ARG, "unknown loss %d", loss);
+    if (loss == BN_PROBE_LOSS_FOCAL && activation != BN_PROBE_ACT_SIGMOID) return fail(BN_ERR_ARG, "the focal loss is the sigmoid head's: not with softmax");
+    if (!(focal_gamma >= 0.0f) || !std::isfinite(focal_gamma)) return fail(BN_ERR_ARG, "focal_gamma %g must be finite and >= 0", (double)focal_gamma);
+    return BN_OK;
 }
 
 int probe_grow(float** p, size_t* bytes, size_t floats, hipStream_t s) {
@@ -1174,8 +1184,20 @@ void bn_probe_destroy(bn_probe* p) {
     delete p;
 }
 
+int bn_probe_set_loss(bn_probe* p, int loss, float focal_gamma) {
+    if (!p) return fail(BN_ERR_ARG, "null probe");
+    if (int rc = probe_loss_check(p->act, loss, focal_gamma)) return rc;
+    p->loss = loss; p->gamma = focal_gamma;
+    return BN_OK;
+}
+
 int bn_probe_epoch(bn_probe* p, const float* d_X, const float* d_Y, const int32_t* d_perm, int64_t n, int batch, float* d_step_loss,
                    void* stream) {
+    return bn_probe_epoch_weighted(p, d_X, d_Y, nullptr, d_perm, n, batch, d_step_loss, stream);
+}
+
+int bn_probe_epoch_weighted(bn_probe* p, const float* d_X, const float* d_Y, const float* d_row_weight, const int32_t* d_perm, int64_t n,
+                            int batch, float* d_step_loss, void* stream) {
     if (!p) return fail(BN_ERR_ARG, "null probe");
     if (int rc = check_device(p->ctx)) return rc;
     if (!d_X || !d_Y || !d_perm || !d_step_loss) return fail(BN_ERR_ARG, "null device pointer");
@@ -1202,6 +1224,7 @@ int bn_probe_epoch(bn_probe* p, const float* d_X, const float* d_Y, const int32_
         f.n = B; f.D = D; f.C = C; f.softmax = p->act == BN_PROBE_ACT_SOFTMAX; f.drop_thresh = thresh; f.drop_scale = drop_scale;
         f.seed = p->seed; f.step = (uint32_t)p->t;
         f.g_scale = p->act == BN_PROBE_ACT_SOFTMAX ? (float)(1.0 / B) : (float)(1.0 / ((double)B * C));
+        f.row_weight = d_row_weight; f.loss_kind = p->loss; f.focal_gamma = p->gamma;
         if (!bn::launch_probe_fwd(f, 0, s)) return fail(BN_ERR_DEVICE, "the probe forward kernel's LDS request was refused");
         probe_groups(B, D, C, &groups, &rpg);
         if ((size_t)groups * E * sizeof(float) > p->partial_bytes) return fail(BN_ERR_UNSUPPORTED, "%d row groups exceed the gradient workspace", groups);
@@ -1234,7 +1257,7 @@ int bn_probe_loss(bn_probe* p, const float* d_X, const float* d_Y, int64_t n, fl
     if (int rc = probe_grow(&p->d_loss_part, &p->loss_bytes, parts, s)) return rc;
     bn::ProbeFwdArgs f{};
     f.X = d_X; f.Y = d_Y; f.W = p->d_params; f.b = p->d_params + (size_t)p->D * p->C; f.loss_part = p->d_loss_part;
-    f.n = n; f.D = p->D; f.C = p->C; f.softmax = p->act == BN_PROBE_ACT_SOFTMAX;
+    f.n = n; f.D = p->D; f.C = p->C; f.softmax = p->act == BN_PROBE_ACT_SOFTMAX; f.loss_kind = p->loss; f.focal_gamma = p->gamma;
     if (!bn::launch_probe_fwd(f, 1, s)) return fail(BN_ERR_DEVICE, "the probe forward kernel's LDS request was refused");
     const float scale = p->act == BN_PROBE_ACT_SOFTMAX ? (float)(1.0 / (double)n) : (float)(1.0 / ((double)n * p->C));
     bn::launch_probe_loss_sum(p->d_loss_part, (long)parts, scale, d_out, s);
@@ -1268,6 +1291,8 @@ int bn_probe_set(bn_probe* p, const float* d_W, const float* d_b, void* stream) 
 struct bn_probe_sweep {
     bn_ctx* ctx = nullptr;
     int D = 0, C = 0, act = 0, T = 0;
+    int loss = BN_PROBE_LOSS_CE;                            // bn_probe_sweep_set_loss: shared by the trials
+    float gamma = 0;
     uint32_t seed = 0;
     int64_t total = 1, t = 0;                               // steps of the schedule (for the record), steps taken
     bn::ProbeSweepTrial* d_trials = nullptr;                // [T]
@@ -1377,8 +1402,20 @@ void bn_probe_sweep_destroy(bn_probe_sweep* p) {
     delete p;
 }
 
+int bn_probe_sweep_set_loss(bn_probe_sweep* p, int loss, float focal_gamma) {
+    if (!p) return fail(BN_ERR_ARG, "null sweep");
+    if (int rc = probe_loss_check(p->act, loss, focal_gamma)) return rc;
+    p->loss = loss; p->gamma = focal_gamma;
+    return BN_OK;
+}
+
 int bn_probe_sweep_epoch(bn_probe_sweep* p, const float* d_X, const float* d_Y, const int32_t* d_perm, int64_t n, int batch,
                          const float* d_step_sizes, const uint8_t* d_active, float* d_step_loss, void* stream) {
+    return bn_probe_sweep_epoch_weighted(p, d_X, d_Y, nullptr, d_perm, n, batch, d_step_sizes, d_active, d_step_loss, stream);
+}
+
+int bn_probe_sweep_epoch_weighted(bn_probe_sweep* p, const float* d_X, const float* d_Y, const float* d_row_weight, const int32_t* d_perm,
+                                  int64_t n, int batch, const float* d_step_sizes, const uint8_t* d_active, float* d_step_loss, void* stream) {
     if (!p) return fail(BN_ERR_ARG, "null sweep");
     if (int rc = check_device(p->ctx)) return rc;
     if (!d_X || !d_Y || !d_perm || !d_step_sizes || !d_step_loss) return fail(BN_ERR_ARG, "null device pointer");
@@ -1402,6 +1439,7 @@ int bn_probe_sweep_epoch(bn_probe_sweep* p, const float* d_X, const float* d_Y, 
         f.X = d_X; f.Y = d_Y; f.idx = idx; f.n = B; f.D = D; f.C = C; f.softmax = p->act == BN_PROBE_ACT_SOFTMAX;
         f.seed = p->seed; f.step = (uint32_t)p->t;
         f.g_scale = p->act == BN_PROBE_ACT_SOFTMAX ? (float)(1.0 / B) : (float)(1.0 / ((double)B * C));
+        f.row_weight = d_row_weight; f.loss_kind = p->loss; f.focal_gamma = p->gamma;
         if (!bn::launch_probe_sweep_fwd(f, w, 0, s)) return fail(BN_ERR_DEVICE, "the probe forward kernel's LDS request was refused");
         probe_groups(B, D, C, &groups, &rpg);   // from (B, D, C) alone, as in a single fit
         if ((size_t)groups * E > partial_stride) return fail(BN_ERR_UNSUPPORTED, "%d row groups exceed the gradient workspace", groups);
@@ -1432,7 +1470,7 @@ int bn_probe_sweep_loss(bn_probe_sweep* p, const float* d_X, const float* d_Y, i
     if (int rc = probe_grow(&p->d_loss_part, &p->loss_bytes, (size_t)p->T * parts, s)) return rc;
     const bn::ProbeSweepArgs w = sweep_args(p, d_active, 0, 0, (int)parts);
     bn::ProbeFwdArgs f{};
-    f.X = d_X; f.Y = d_Y; f.n = n; f.D = p->D; f.C = p->C; f.softmax = p->act == BN_PROBE_ACT_SOFTMAX;
+    f.X = d_X; f.Y = d_Y; f.n = n; f.D = p->D; f.C = p->C; f.softmax = p->act == BN_PROBE_ACT_SOFTMAX; f.loss_kind = p->loss; f.focal_gamma = p->gamma;
     if (!bn::launch_probe_sweep_fwd(f, w, 1, s)) return fail(BN_ERR_DEVICE, "the probe forward kernel's LDS request was refused");
     const float scale = p->act == BN_PROBE_ACT_SOFTMAX ? (float)(1.0 / (double)n) : (float)(1.0 / ((double)n * p->C));
     bn::launch_probe_sweep_loss_sum(w, (long)parts, scale, d_out, s);

@@ -490,6 +490,11 @@ struct ProbeFwdArgs {
     float drop_scale;      // 1 / (1 - p)
     uint32_t seed, step;
     float g_scale;         // 1 / (n C) (sigmoid) or 1 / n (softmax)
+    // what a long-tailed training set needs (bn_probe_step.h); shared by all trials of a sweep.  All three off (null, CE, any gamma)
+    // launches the instantiation without them: today's statements, no multiplication by a loaded 1.0
+    const float* row_weight;   // [rows of X] one weight per row, indexed through idx like Y; mode 0 only; null: off
+    int loss_kind;             // BN_PROBE_LOSS_CE or BN_PROBE_LOSS_FOCAL (sigmoid only); modes 0 and 1
+    float focal_gamma;
 };
 struct ProbeDwArgs {
     const float* X; const int* idx; const float* G;

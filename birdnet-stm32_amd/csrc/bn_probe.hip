@@ -20,17 +20,20 @@
 
 namespace bn {
 
+template <int NT, int MODE, int EXT>
+static bool launch_fwd_one(const ProbeFwdArgs& a, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
+    if (lds > 64 * 1024 && !ensure_dynamic_lds((const void*)&probe_fwd_kernel<NT, MODE, EXT, false>, lds)) return false;
+    hipLaunchKernelGGL((probe_fwd_kernel<NT, MODE, EXT, false>), grid, block, lds, s, a, ProbeNoSweep{});
+    return true;
+}
+
+// EXT = 1 only when the call asks for row weights (mode 0) or the focal loss (modes 0 and 1): every other call runs the kernel without them
 template <int NT>
 static bool launch_fwd_nt(const ProbeFwdArgs& a, int mode, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
-    const void* k = mode == 0 ? (const void*)&probe_fwd_kernel<NT, 0, false> : mode == 1 ? (const void*)&probe_fwd_kernel<NT, 1, false> : (const void*)&probe_fwd_kernel<NT, 2, false>;
-    if (lds > 64 * 1024 && !ensure_dynamic_lds(k, lds)) return false;
-    if (mode == 0)
-        hipLaunchKernelGGL((probe_fwd_kernel<NT, 0, false>), grid, block, lds, s, a, ProbeNoSweep{});
-    else if (mode == 1)
-        hipLaunchKernelGGL((probe_fwd_kernel<NT, 1, false>), grid, block, lds, s, a, ProbeNoSweep{});
-    else
-        hipLaunchKernelGGL((probe_fwd_kernel<NT, 2, false>), grid, block, lds, s, a, ProbeNoSweep{});
-    return true;
+    const bool ext = probe_fwd_ext(a, mode);
+    if (mode == 0) return ext ? launch_fwd_one<NT, 0, 1>(a, grid, block, lds, s) : launch_fwd_one<NT, 0, 0>(a, grid, block, lds, s);
+    if (mode == 1) return ext ? launch_fwd_one<NT, 1, 1>(a, grid, block, lds, s) : launch_fwd_one<NT, 1, 0>(a, grid, block, lds, s);
+    return launch_fwd_one<NT, 2, 0>(a, grid, block, lds, s);
 }
 
 bool launch_probe_fwd(const ProbeFwdArgs& a, int mode, hipStream_t s) {

@@ -11,6 +11,17 @@
 //     keep = fl(1 - eps);  add = fl(0.5 * eps) (sigmoid) or fl(eps / fl(C)) (softmax)      on the host
 //     y'   = fl(fl(y * keep) + add)                                                          per element, in the forward kernel
 // training/linear_probe.py: smooth_targets is the same in numpy.  eps == 0 skips the two operations: y' is y, bit for bit.
+//
+// Long-tailed training sets (EXT = 1 of the forward kernel; single fit and sweep alike, shared by a sweep's trials): the focal loss of
+// the sigmoid head and one weight per row.  With y the target (after smoothing, if any), p the sigmoid and pc = clip(p, 1e-7, 1 - 1e-7):
+//     bce  = -(y log pc + (1 - y) log(1 - pc))
+//     q    = 1 - (y pc + (1 - y)(1 - pc))                 (> 0: pc is clipped)
+//     f    = expf(gamma * logf(q))
+//     loss = f bce;    dloss/dz = f (p - y) - gamma (f / q) (2 y - 1) pc (1 - pc) bce
+// and row i's elements times w_i, in the loss and in G; the means still divide by B C (or B).  The validation loss (MODE 1) takes the
+// loss kind and no weights.  Written in probe_loss_elem with a rounding after every operation, so no instantiation fuses what another
+// does not.  EXT = 0 is the kernel without any of this: the statements, and the bits, of a fit that asks for neither.
+// training/linear_probe.py: probe_loss / probe_loss_gradient are the same in numpy.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -82,13 +93,42 @@ __device__ __forceinline__ float probe_smooth(float y, float keep, float add) {
     return t + add;
 }
 
+// EXT = 1: the loss of one element and its derivative by the logit, before the mean's scale (see the head of the file)
+__device__ __forceinline__ void probe_loss_elem(float p, float pc, float y, bool softmax, bool focal, float gamma, bool weighted, float w, float& le,
+                                                float& g) {
+#pragma clang fp contract(off)
+    g = p - y;
+    if (softmax) {
+        le = -(y * logf(pc));
+    } else {
+        const float bce = -(y * logf(pc) + (1.0f - y) * logf(1.0f - pc));
+        le = bce;
+        if (focal) {
+            const float q = 1.0f - (y * pc + (1.0f - y) * (1.0f - pc));
+            const float f = expf(gamma * logf(q));
+            le = f * bce;
+            g = f * g - gamma * (f / q) * (2.0f * y - 1.0f) * pc * (1.0f - pc) * bce;
+        }
+    }
+    if (weighted) {
+        le = le * w;
+        g = g * w;
+    }
+}
+
+// host: does this launch need the EXT = 1 kernel?  Row weights count in mode 0 only, the focal loss in modes 0 and 1.
+inline bool probe_fwd_ext(const ProbeFwdArgs& a, int mode) {
+    return mode != 2 && (a.loss_kind == BN_PROBE_LOSS_FOCAL || (mode == 0 && a.row_weight != nullptr));
+}
+
 __device__ __forceinline__ bool sweep_idle(const ProbeSweepArgs& w, int t) { return w.active && !w.active[t]; }
 
 
 // ------------------------------------------------------------------------------------------------------------------------- forward
 // MODE 0: training (G and the loss partial), 1: loss partial only, 2: scores.  NT: column tiles per wave (tile t of wave w is w + t * waves).
 // SWEEP: blockIdx.y is the trial; mode 0 takes its dropout threshold and label smoothing from the table, mode 1 has neither.
-template <int NT, int MODE, bool SWEEP>
+// EXT 1 (modes 0 and 1): the loss kind and, in mode 0, the row weights of ProbeFwdArgs; 0: neither, the plain cross-entropy statements.
+template <int NT, int MODE, int EXT, bool SWEEP>
 __global__ __launch_bounds__(1024) void probe_fwd_kernel(ProbeFwdArgs a, ProbeSweepOf<SWEEP> w) {
     const float *W = a.W, *bias = a.b;
     float *out = a.out, *loss_part = a.loss_part;
@@ -218,6 +258,19 @@ __global__ __launch_bounds__(1024) void probe_fwd_kernel(ProbeFwdArgs a, ProbeSw
         have = npass == 1;
     }
 
+    [[maybe_unused]] float rw[4] = {1.0f, 1.0f, 1.0f, 1.0f};   // the weights of the lane's four rows, loaded once
+    [[maybe_unused]] bool weighted = false;
+    [[maybe_unused]] const bool focal = EXT && a.loss_kind == BN_PROBE_LOSS_FOCAL;
+    if constexpr (EXT && MODE == 0) {
+        weighted = a.row_weight != nullptr;
+        if (weighted) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const long row = row0 + 4 * lk + r;
+                if (row < a.n) rw[r] = a.row_weight[a.idx ? (long)a.idx[row] : row];
+            }
+        }
+    }
     float loss = 0.0f;
     for (int pass = 0; pass < npass; ++pass) {
         if (!have) logits(pass);
@@ -237,11 +290,18 @@ __global__ __launch_bounds__(1024) void probe_fwd_kernel(ProbeFwdArgs a, ProbeSw
                     if constexpr (SWEEP && MODE == 0)
                         if (smooth) y = probe_smooth(y, smooth_keep, smooth_add);
                     const float pc = fminf(fmaxf(p, 1e-7f), 1.0f - 1e-7f);
-                    if (a.softmax)
-                        loss -= y * logf(pc);
-                    else
-                        loss -= y * logf(pc) + (1.0f - y) * logf(1.0f - pc);
-                    if constexpr (MODE == 0) out[(size_t)row * C + c] = (p - y) * a.g_scale;
+                    if constexpr (EXT) {
+                        float le, g;
+                        probe_loss_elem(p, pc, y, a.softmax, focal, a.focal_gamma, weighted, rw[r], le, g);
+                        loss += le;
+                        if constexpr (MODE == 0) out[(size_t)row * C + c] = g * a.g_scale;
+                    } else {
+                        if (a.softmax)
+                            loss -= y * logf(pc);
+                        else
+                            loss -= y * logf(pc) + (1.0f - y) * logf(1.0f - pc);
+                        if constexpr (MODE == 0) out[(size_t)row * C + c] = (p - y) * a.g_scale;
+                    }
                 }
             }
         }

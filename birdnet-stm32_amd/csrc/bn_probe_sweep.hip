@@ -19,15 +19,18 @@
 
 namespace bn {
 
+template <int NT, int MODE, int EXT>
+static bool launch_sweep_fwd_one(const ProbeFwdArgs& a, const ProbeSweepArgs& w, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
+    if (lds > 64 * 1024 && !ensure_dynamic_lds((const void*)&probe_fwd_kernel<NT, MODE, EXT, true>, lds)) return false;
+    hipLaunchKernelGGL((probe_fwd_kernel<NT, MODE, EXT, true>), grid, block, lds, s, a, w);
+    return true;
+}
+
 template <int NT>
 static bool launch_sweep_fwd_nt(const ProbeFwdArgs& a, const ProbeSweepArgs& w, int mode, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
-    const void* k = mode == 0 ? (const void*)&probe_fwd_kernel<NT, 0, true> : (const void*)&probe_fwd_kernel<NT, 1, true>;
-    if (lds > 64 * 1024 && !ensure_dynamic_lds(k, lds)) return false;
-    if (mode == 0)
-        hipLaunchKernelGGL((probe_fwd_kernel<NT, 0, true>), grid, block, lds, s, a, w);
-    else
-        hipLaunchKernelGGL((probe_fwd_kernel<NT, 1, true>), grid, block, lds, s, a, w);
-    return true;
+    const bool ext = probe_fwd_ext(a, mode);   // as launch_fwd_nt (bn_probe.hip)
+    if (mode == 0) return ext ? launch_sweep_fwd_one<NT, 0, 1>(a, w, grid, block, lds, s) : launch_sweep_fwd_one<NT, 0, 0>(a, w, grid, block, lds, s);
+    return ext ? launch_sweep_fwd_one<NT, 1, 1>(a, w, grid, block, lds, s) : launch_sweep_fwd_one<NT, 1, 0>(a, w, grid, block, lds, s);
 }
 
 // The launch shape of launch_probe_fwd (bn_probe.hip) with the trials along y; mode 0 (training) or 1 (loss)

@@ -412,6 +412,23 @@ BN_API int bn_probe_loss(bn_probe* probe, const float* d_X, const float* d_Y, in
 /* Copy the weights [D, C] and bias [C] out of / into the probe (device pointers; the optimiser state is left alone). */
 BN_API int bn_probe_get(bn_probe* probe, float* d_W, float* d_b, void* stream);
 BN_API int bn_probe_set(bn_probe* probe, const float* d_W, const float* d_b, void* stream);
+/* Long-tailed training sets.  The loss of the steps and of bn_probe_loss from here on: BN_PROBE_LOSS_CE (the default of a new probe) or
+ * BN_PROBE_LOSS_FOCAL, the focal form of the sigmoid head's binary cross-entropy with y the target, p the sigmoid, pc = p clipped to
+ * [1e-7, 1 - 1e-7]:  bce = -(y log pc + (1 - y) log(1 - pc)),  q = 1 - (y pc + (1 - y)(1 - pc)),  f = exp(focal_gamma log q),
+ * loss = f bce,  dloss/dz = f (p - y) - focal_gamma (f / q) (2 y - 1) pc (1 - pc) bce.  focal_gamma = 0 is the cross-entropy in value
+ * (computed by the focal statements).  Refused (BN_ERR_ARG, nothing changes): a null probe, an unknown loss, focal on a softmax probe, a
+ * negative or non-finite focal_gamma (checked for either loss). */
+#define BN_PROBE_LOSS_CE 0
+#define BN_PROBE_LOSS_FOCAL 1
+BN_API int bn_probe_set_loss(bn_probe* probe, int loss, float focal_gamma);
+/* bn_probe_epoch with one weight per row: d_row_weight is float32 [rows of d_X], indexed through d_perm like d_Y; the loss and the
+ * gradient of the elements of row i are multiplied by d_row_weight[i], and the means still divide by the batch's rows x classes (or
+ * rows), not by the sum of the weights (Keras' sum_over_batch_size).  Null: no weights, bn_probe_epoch itself.  bn_probe_loss is never
+ * weighted.  Here as in bn_probe_epoch, n is the length of d_perm, not the row count of d_X: a row number may occur any number of times
+ * (upsampling a minority class without a second copy of its rows), and n may exceed the rows of d_X.  Two occurrences of a row in one
+ * batch draw different dropout masks (the draw is per position in the batch). */
+BN_API int bn_probe_epoch_weighted(bn_probe* probe, const float* d_X, const float* d_Y, const float* d_row_weight, const int32_t* d_perm,
+                            int64_t n, int batch, float* d_step_loss, void* stream);
 
 /* ---- A hyperparameter sweep: T heads trained in lock-step on the same rows (csrc/bn_probe_sweep.hip) ---------------------------------
  * (Reference counterpart: `train --tune`, training/tuner.py, which trains its trials one after another.)  The trials share D, C, the
@@ -462,6 +479,14 @@ BN_API int bn_probe_sweep_loss(bn_probe_sweep* sweep, const float* d_X, const fl
 BN_API int bn_probe_sweep_snapshot(bn_probe_sweep* sweep, const uint8_t* d_mask, void* stream);
 /* The weights [D, C] and bias [C] of one trial (device pointers), which: BN_PROBE_SWEEP_CURRENT or BN_PROBE_SWEEP_SNAPSHOT. */
 BN_API int bn_probe_sweep_get(bn_probe_sweep* sweep, int trial, int which, float* d_W, float* d_b, void* stream);
+/* bn_probe_set_loss and bn_probe_epoch_weighted for a sweep: the loss kind, focal_gamma and the row weights are shared by all trials
+ * (they are no fields of bn_probe_trial); label smoothing comes first, the focal loss sees the smoothed target.  bn_probe_sweep_loss
+ * uses the loss that was set, unweighted and unsmoothed.  A trial with label_smoothing == 0 still has the bits of a bn_probe with the
+ * same loss, weights and rows. */
+BN_API int bn_probe_sweep_set_loss(bn_probe_sweep* sweep, int loss, float focal_gamma);
+BN_API int bn_probe_sweep_epoch_weighted(bn_probe_sweep* sweep, const float* d_X, const float* d_Y, const float* d_row_weight,
+                                  const int32_t* d_perm, int64_t n, int batch, const float* d_step_sizes, const uint8_t* d_active,
+                                  float* d_step_loss, void* stream);
 
 /* ---- Query by example: the k best rows of an embedding matrix per query (csrc/bn_search.hip; no reference counterpart) -------------
  * Rows and queries are BN_DTYPE_F32 values or the BN_DTYPE_I8 bytes of bn_forward_embed with their zero point; both sides have the same

@@ -7,6 +7,12 @@ fit: gather, dropout, ``torch.nn.functional.linear``, sigmoid + binary cross-ent
 with a cosine schedule.  Both sides are timed over whole epochs (first epoch discarded as warm-up), synchronised at the epoch's end only.
 Prints one JSON line per cell and a markdown table.
 
+    python tools/probe_bench.py --loss focal [--focal_gamma 2.0] [--row_weights] [--skip_torch]
+
+The same cells with the device fit on the focal loss and / or with one weight per row (uniform in [0.5, 4), ``bn_probe_epoch_weighted``):
+the forward kernel's other instantiation (csrc/bn_probe_step.h, EXT = 1).  The PyTorch side stays the plain cross-entropy step, for
+scale; ``--skip_torch`` leaves it out.
+
     python tools/probe_bench.py --sweep 4,16,64 [--rows 262144] [--repeats 3] [--classes 12,100,1000] [--batches 32,512,4096]
 
 One sweep of T trials (``fit_probe_sweep``'s backend, ``bn_probe_sweep_*``) against T single fits one after another (``bn_probe_*``) in the
@@ -108,6 +114,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=262144)
     ap.add_argument("--epochs", type=int, default=2, help="timed epochs per cell (one more runs first as warm-up)")
+    ap.add_argument("--loss", type=str, default="auto", choices=["auto", "focal"], help="the device fit's loss (not with --sweep)")
+    ap.add_argument("--focal_gamma", type=float, default=2.0)
+    ap.add_argument("--row_weights", action="store_true", help="the device fit with one weight per row (not with --sweep)")
+    ap.add_argument("--skip_torch", action="store_true", help="time the device fit only")
     ap.add_argument("--sweep", type=str, default="", help="trial counts, e.g. 4,16,64: time one sweep of T trials against T fits one after another")
     ap.add_argument("--repeats", type=int, default=3, help="with --sweep: timed epochs per side and cell (one more runs first as warm-up)")
     ap.add_argument("--classes", type=str, default="12,100,1000", help="with --sweep: class counts")
@@ -119,6 +129,7 @@ def main():
     ctx = _hip.Context(0, 1)
     g = torch.Generator(device="cuda").manual_seed(1)
     X = torch.rand((n, D), device="cuda", generator=g)
+    weights = 0.5 + 3.5 * torch.rand(n, device="cuda", generator=g) if args.row_weights else None
     rows = []
     for C in (12, 100, 1000):
         Y = torch.zeros((n, C), device="cuda")
@@ -127,8 +138,9 @@ def main():
             steps = math.ceil(n / batch)
             total = steps * (args.epochs + 1)
             W0, b0 = lp.init_head(D, C, 1)
-            cfg = dict(activation="sigmoid", optimizer="adam", batch=batch, seed=1, dropout=0.5, clipnorm=1.0, lr=1e-3, weight_decay=0.0, total=total)
-            be = lp._DeviceBackend(ctx, X, Y, None, None, W0, b0, cfg)
+            cfg = dict(activation="sigmoid", optimizer="adam", batch=batch, seed=1, dropout=0.5, clipnorm=1.0, lr=1e-3, weight_decay=0.0, total=total,
+                       loss=args.loss, focal_gamma=args.focal_gamma)
+            be = lp._DeviceBackend(ctx, X, Y, None, None, W0, b0, cfg, sample_weight=weights)
             ours = []
             for e in range(args.epochs + 1):
                 perm = lp.epoch_permutation(1, e, n)
@@ -138,14 +150,14 @@ def main():
             be.close()
             ep = torch_epoch_fn(torch, X, Y, C, batch, total)
             theirs = []
-            for e in range(args.epochs + 1):
+            for e in range(0 if args.skip_torch else args.epochs + 1):
                 perm = torch.from_numpy(lp.epoch_permutation(1, e, n).astype(np.int64)).cuda()
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 ep(perm)
                 theirs.append(time.perf_counter() - t0)
-            a, b = min(ours[1:]), min(theirs[1:])
-            row = dict(D=D, C=C, batch=batch, steps_per_epoch=steps, fit_probe_s_per_epoch=a, fit_probe_steps_per_s=steps / a, torch_s_per_epoch=b,
+            a, b = min(ours[1:]), min(theirs[1:]) if theirs else float("nan")
+            row = dict(D=D, C=C, batch=batch, loss=args.loss, row_weights=bool(args.row_weights), steps_per_epoch=steps, fit_probe_s_per_epoch=a, fit_probe_steps_per_s=steps / a, torch_s_per_epoch=b,
                        torch_steps_per_s=steps / b, speedup=b / a)
             rows.append(row)
             print(json.dumps(row), flush=True)

@@ -9,7 +9,9 @@ the compiler fuses a multiplication into an addition is its own choice per insta
 every floating-point opcode occurs in the two instantiations.  The only difference allowed is the label smoothing of the sweep's
 training forward kernel: one multiplication and one addition more per target element a lane holds (4 rows x NT column tiles), and no
 fused form fewer; and the integer division that splits the gradient kernel's z into trial and row group, which the compiler does with
-a float32 reciprocal.  Opcodes are counted without their encoding suffix (_e32 / _e64 / _dpp / _sdwa).  Anything else is printed as a
+a float32 reciprocal.  The forward kernel's instantiations with the focal loss and the row weights (its third template argument, EXT = 1)
+are pairs like the others and take the same allowance: their loss arithmetic is written with contraction off, so there is nothing for
+the compiler to fuse in one instantiation and not in the other.  Opcodes are counted without their encoding suffix (_e32 / _e64 / _dpp / _sdwa).  Anything else is printed as a
 warning.  No part of the build (`make probe-asm-check` in csrc/ runs it): another compiler may lower these two idioms differently without
 touching the arithmetic, and the GPU tests, which compare the bits, hold the contract (tests/test_gpu_probe_sweep.py).  This is where
 to look first, on a machine without a GPU, when they fail.  --strict makes a difference the exit status.  Needs c++filt; without it, it says so and checks nothing.
