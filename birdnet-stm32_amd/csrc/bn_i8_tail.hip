@@ -27,7 +27,7 @@
 //   * the first block streams its taps from global memory (its input map, 32 KB per chunk, never enters LDS);
 //   * after the last block: MEAN per (chunk, channel) thread, FULLY_CONNECTED per (chunk, class) thread, table + dequantise.
 //
-// LDS plan per block (computed on the host, bn::tail_plan): input map, output map, pointwise weights, depthwise / pointwise
+// LDS plan per block (computed on the host, bn::tail_plan in bn_chain_plan.cpp): input map, output map, pointwise weights, depthwise / pointwise
 // constants, ADD tables, zero-point row — first fit into 160 KB; blocks whose maps do not fit make the plan fall back to the
 // per-block operators (bn_api.hip).
 #include "bn_tail_common.h"
@@ -57,7 +57,7 @@ __device__ __forceinline__ int pq_base(int kq) {
 
 // One block for the kTailG chunks of the workgroup.  `lds` = the workgroup's LDS; maps are [chunk][position][C + 4 bytes].
 // The geometry is a template parameter (H x W input map, stride S): positions turn into shifts and the padding tests into
-// comparisons with constants; tail_plan() only accepts the four shapes instantiated below.
+// comparisons with constants; tail_plan() only accepts the four shapes instantiated below (kTailShapes in bn_chain_plan.cpp).
 template <int CIN, int COUT, int S, int H, int W, bool ADD, bool SRCG>
 __device__ __forceinline__ void tail_block(const Tail8Layer& L, const Tail8Args& a, unsigned char* lds, int chunk0, int stamp_slot = -1) {
     BN_STAMP(st0);
@@ -322,6 +322,7 @@ __device__ __forceinline__ void tail_main(const Tail8Args& a) {
             const int gi = (grp - (int)blockIdx.x) / (int)gridDim.x;
             if ((int)blockIdx.x < kStampWg && gi < kStampGrp && li < 8) slot = ((int)blockIdx.x * kStampGrp + gi) * 8 + li;
 #endif
+            // (the shapes of kTailShapes in bn_chain_plan.cpp: the planner refuses every other block)
             if (L.Cin == 64) tail_block<64, 128, 2, 16, 32, false, true>(L, a, lds, chunk0, slot);
             else if (L.Cin == 128 && L.Cout == 128) tail_block<128, 128, 1, 8, 16, true, false>(L, a, lds, chunk0, slot);
             else if (L.Cin == 128) tail_block<128, 256, 2, 8, 16, false, false>(L, a, lds, chunk0, slot);
@@ -336,115 +337,7 @@ __global__ __launch_bounds__(kTailThreads) void i8_tail_kernel(Tail8Args a) { ta
 // the same with the embedding output (a.emb non-null)
 __global__ __launch_bounds__(kTailThreads) void i8_tail_emb_kernel(WithEmb<Tail8Args> w) { tail_main<true>(w.a); }
 
-// first-fit allocator over the workgroup's LDS: `used` holds [begin, end) intervals that must stay intact
-struct Span {
-    int b, e;
-};
-int first_fit(std::vector<Span>& used, int bytes, int cap) {
-    bytes = (bytes + 15) & ~15;
-    int pos = 0;
-    for (;;) {
-        bool moved = false;
-        for (const Span& s : used)
-            if (pos < s.e && pos + bytes > s.b) {
-                pos = (s.e + 15) & ~15;
-                moved = true;
-            }
-        if (!moved) break;
-    }
-    if (pos + bytes > cap) return -1;
-    used.push_back({pos, pos + bytes});
-    return pos;
-}
-
 }  // namespace
-
-// Build the kernel arguments from the descriptor table the packer wrote (24 words per block + 16 head words) and plan the LDS of
-// every block.  Returns false when the topology is not one the kernel takes or a block's maps do not fit 160 KB.
-bool tail_plan(const int32_t* desc, int n_words, int n_layers, Tail8Args& a) {
-    constexpr int LW = 24, HW = 16, CAP = 160 * 1024;
-    if (n_layers < 1 || n_layers > 8 || n_words != LW * n_layers + HW) return false;
-    a.n_layers = n_layers;
-    int cur_off = -1;   // where the current input map lives (-1: global memory)
-    int lds_need = 0;
-    for (int i = 0; i < n_layers; ++i) {
-        const int32_t* d = desc + LW * i;
-        Tail8Layer& L = a.L[i];
-        L.H = d[0]; L.W = d[1]; L.Cin = d[2]; L.Cout = d[3]; L.S = d[4]; L.OH = d[5]; L.OW = d[6]; L.pt = d[7]; L.pl = d[8]; L.has_add = d[9];
-        L.zp_in = d[10]; L.dw_lo = d[11]; L.dw_hi = d[12]; L.pw_lo = d[13]; L.pw_hi = d[14];
-        L.add_m = d[15]; L.add_c1 = d[16]; L.add_e = d[17]; L.add_lo = d[18]; L.add_hi = d[19];
-        L.g_w = d[20]; L.g_dwc = d[21]; L.g_pwc = d[22]; L.g_lut = d[23];
-        const bool first = i == 0;
-        auto is = [&](int cin, int cout, int st, int hh, int ww, int add) {
-            return L.Cin == cin && L.Cout == cout && L.S == st && L.H == hh && L.W == ww && L.has_add == add && L.pt == (st == 1) && L.pl == (st == 1);
-        };
-        // the four instantiations of tail_block (bn_i8_tail.hip: i8_tail_kernel)
-        const bool shape_ok = (first && is(64, 128, 2, 16, 32, 0)) || (!first && (is(128, 128, 1, 8, 16, 1) || is(128, 256, 2, 8, 16, 0) || is(256, 256, 1, 4, 8, 1)));
-        if (!shape_ok || (L.S != 1 && L.S != 2) || L.OH != (L.H + L.S - 1) / L.S || L.OW != (L.W + L.S - 1) / L.S || (L.OH * L.OW) % 16 ||
-            L.pt < 0 || L.pt > 1 || L.pl < 0 || L.pl > 1 || L.H < 1 || L.W < 1 || L.H * L.W > 4096)
-            return false;
-        if (L.has_add && (L.Cin != L.Cout || L.S != 1 || L.g_lut < 0 || L.add_e < 1 || L.add_e > 22 || L.add_m < 0)) return false;
-        if (i > 0 && (L.H != a.L[i - 1].OH || L.W != a.L[i - 1].OW || L.Cin != a.L[i - 1].Cout)) return false;
-        const int tiles = kTailG * L.OH * L.OW / 16;
-        if (tiles < kTailWaves && (kTailWaves % tiles || (L.Cout / 16) % (kTailWaves / tiles))) return false;
-        if ((L.g_w | L.g_dwc | L.g_pwc) & 3 || (L.has_add && (L.g_lut & 3))) return false;
-        // offsets into the constant block start at 0 (tail_const_words bounds them from above: a stale or hostile blob must not make the
-        // kernel read in front of the block), and every clamp whose result indexes a table or is stored as a byte is an int8 range
-        // (+ 128 where the pointwise value of a residual block is kept as the index of the second ADD table)
-        if (L.g_w < 0 || L.g_dwc < 0 || L.g_pwc < 0 || (L.has_add && L.g_lut < 0)) return false;
-        const int off = L.has_add ? 128 : 0;
-        if (L.dw_lo < -128 || L.dw_hi > 127 || L.dw_lo > L.dw_hi || L.pw_lo < -128 + off || L.pw_hi > 127 + off || L.pw_lo > L.pw_hi) return false;
-        if (L.has_add && (L.add_lo < -128 || L.add_hi > 127 || L.add_lo > L.add_hi)) return false;
-        std::vector<Span> used;
-        L.x_off = cur_off;
-        if (cur_off >= 0) used.push_back({cur_off, cur_off + kTailG * L.H * L.W * (L.Cin + 4)});
-        L.y_off = first_fit(used, kTailG * L.OH * L.OW * (L.Cout + 4), CAP);
-        L.w_off = first_fit(used, L.Cin * L.Cout, CAP);
-        L.dwc_off = first_fit(used, L.Cin * 32 + 64, CAP);   // staged in rq_hi form: 8 x 16 bytes per channel quad (+ up to four slots of skew),
-        L.pwc_off = first_fit(used, L.Cout * 20, CAP);  // 5 x 16 bytes per four output channels
-        L.lut_off = L.has_add ? first_fit(used, 2048, CAP) : 0;
-        L.zp_off = first_fit(used, L.Cin + 16, CAP);
-        if (L.y_off < 0 || L.w_off < 0 || L.dwc_off < 0 || L.pwc_off < 0 || L.lut_off < 0 || L.zp_off < 0) return false;
-        if (i == n_layers - 1) {
-            a.mean_off = first_fit(used, kTailG * L.Cout, CAP);
-            if (a.mean_off < 0) return false;
-        }
-        for (const Span& s : used) lds_need = s.e > lds_need ? s.e : lds_need;
-        cur_off = L.y_off;
-    }
-    const int32_t* h = desc + LW * n_layers;
-    a.mean_zp_in = h[0]; a.mean_mult = h[1]; a.mean_shift = h[2]; a.mean_zp_out = h[3];
-    a.fc_zp_out = h[4]; a.fc_lo = h[5]; a.fc_hi = h[6]; a.g_fcw = h[7]; a.g_fcb = h[8]; a.g_fcm = h[9]; a.g_fcs = h[10]; a.g_hlut = h[11];
-    a.head_zp_fc = h[12]; a.head_zp_out = h[13]; a.P = h[14]; a.C = h[15];
-    if (a.g_fcw < 0 || a.g_fcb < 0 || a.g_fcm < 0 || a.g_fcs < 0 || a.g_hlut < -1 || (a.g_fcw & 3)) return false;
-    if (a.fc_lo < -128 || a.fc_hi > 127 || a.fc_lo > a.fc_hi) return false;  // (the classifier byte + 128 indexes the head's table)
-    const Tail8Layer& last = a.L[n_layers - 1];
-    if (a.P != last.OH * last.OW || a.C != last.Cout || a.C % 4 || a.NC < 1 || kTailG * a.NC > kTailThreads * 4) return false;
-    // the head's LDS copy of the classifier matrix overlays the last block's pointwise weights (4 x 1024 threads x 16 bytes are staged at most)
-    const int fc_bytes = a.NC * (a.C / 4 + 1) * 4;
-    a.fcw_off = (a.C % 16 == 0 && fc_bytes <= last.Cin * last.Cout && a.NC * (a.C / 16) <= 4 * kTailThreads) ? last.w_off : -1;
-    a.lds_bytes = lds_need;
-    return true;
-}
-
-// words of the constant block the kernel reads (for the load-time check of the tensor's size)
-long tail_const_words(const Tail8Args& a) {
-    long need = 0;
-    auto upto = [&](long off, long words) { need = off + words > need ? off + words : need; };
-    for (int i = 0; i < a.n_layers; ++i) {
-        const Tail8Layer& L = a.L[i];
-        upto(L.g_w, (long)L.Cin * L.Cout / 4);
-        upto(L.g_dwc, (long)L.Cin * 7);
-        upto(L.g_pwc, (long)L.Cout * 4);
-        if (L.has_add) upto(L.g_lut, 512);
-    }
-    upto(a.g_fcw, (long)a.NC * a.C / 4);
-    upto(a.g_fcb, a.NC);
-    upto(a.g_fcm, a.NC);
-    upto(a.g_fcs, a.NC);
-    if (a.g_hlut >= 0) upto(a.g_hlut, 64);
-    return need;
-}
 
 #ifdef BN_TAIL_STAMPS
 // debug export of the stamps build only: where the kernel writes its stamps ([8][4][8][16][6] int64, zeroed by the caller)

@@ -36,15 +36,14 @@
 //
 // Constants never make a wave wait for memory: a block's depthwise part (expanded weights + constants) is requested while the PREVIOUS
 // block's pointwise phase runs and written to LDS behind it, its pointwise part (weights + constants) is requested before the block's
-// own depthwise phase and written behind that — two barriers per block, none of them behind a load (tail2_plan places the parts so that
-// nothing live is overwritten).  i8_mid2_kernel's constants fit beside its maps all at once: there they are staged once per launch and the
-// barriers shrink to the waves of one chunk (mid2_main, chunk_barrier; option i8_mid_split).
+// own depthwise phase and written behind that — two barriers per block, none of them behind a load (tail2_plan in bn_chain_plan.cpp places
+// the parts so that nothing live is overwritten; the parts' sizes, tail2_dw_bytes / tail2_pw_bytes, are in bn_chain_plan.h for both sides).
+// i8_mid2_kernel's constants fit beside its maps all at once: there they are staged once per launch and the barriers shrink to the waves
+// of one chunk (mid2_main, chunk_barrier; option i8_mid_split).
 //
 // The first block streams its taps from global memory (range-checked 16-byte buffer loads: a tap outside the map reads 0; what the
 // folded bias assumed for it — the zero point — is taken back through per-border variants of the bias).
 #include "bn_tail_common.h"
-
-#include <algorithm>
 
 namespace bn {
 namespace {
@@ -123,11 +122,6 @@ __device__ __forceinline__ void chunk_barrier(unsigned char* lds, int bar_off, i
     if (!done && (threadIdx.x & 63) == 0) atomicAdd(&g_tail2_giveups, 1u);
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
-
-constexpr int kTail2MaxDw16 = 7 * kTail2Threads;   // sixteen-byte pieces of the largest depthwise part a block may prefetch (256 channels: 3392)
-
-__device__ __forceinline__ int tail2_dw_bytes(const Tail2Layer& L, bool first) { return (L.Cin / 16) * (3 * 1024 + (first ? 8 : 5) * 64); }
-__device__ __forceinline__ int tail2_pw_bytes(const Tail2Layer& L) { return (L.Cin + 63) / 64 * 64 * L.Cout + (L.Cout / 16) * 5 * 64; }
 
 // MultiplyByQuantizedMultiplier for either sign in four instructions (the block's own term of a residual ADD: no activation, no clamp):
 //   hi = (x M' + C) >> 32 with M' = the dword 2 m read as signed (= 2 m - 2^32) and C = (2^(e-1) << 32) + 2^31
@@ -526,6 +520,7 @@ __device__ __forceinline__ void tail2_main(const Tail2Args& a) {
             const int gi = (grp - (int)blockIdx.x) / (int)gridDim.x;
             if ((int)blockIdx.x < 8 && gi < 4 && li < 8 && g_tail2_stamps) slot = ((int)blockIdx.x * 4 + gi) * 8 + li;
 #endif
+            // (the shapes of kTailShapes in bn_chain_plan.cpp: the planner refuses every other block)
             if (L.Cin == 64) tail2_block<kTailG, 64, 128, 2, 16, 32, false, true>(L, a, lds, chunk0, nx, seq, slot);
             else if (L.Cin == 128 && L.Cout == 128) tail2_block<kTailG, 128, 128, 1, 8, 16, true, false>(L, a, lds, chunk0, nx, seq, slot);
             else if (L.Cin == 128) tail2_block<kTailG, 128, 256, 2, 8, 16, false, false>(L, a, lds, chunk0, nx, seq, slot);
@@ -595,6 +590,7 @@ __device__ __forceinline__ void mid2_main(const Tail2Args& a) {
             const int gi = (grp - (int)blockIdx.x) / (int)gridDim.x;
             if ((int)blockIdx.x < 8 && gi < 4 && li < 8 && g_mid2_stamps) slot = ((int)blockIdx.x * 4 + gi) * 8 + li;
 #endif
+            // (the shapes of kMidShapes in bn_chain_plan.cpp)
             if (li == 0) tail2_block<kMidG, 32, 64, 2, 32, 64, false, true, RES>(L, a, lds, chunk0, nx, seq, slot);
             else tail2_block<kMidG, 64, 64, 1, 16, 32, true, false, RES>(L, a, lds, chunk0, nx, seq, slot);
         }
@@ -633,189 +629,6 @@ __global__ __launch_bounds__(kTail2Threads) void i8_mid2_kernel(Tail2Args a) {
     else mid2_main<false>(a);
 }
 
-int tail2_dw_part(const Tail2Layer& L, bool first) { return (L.Cin / 16) * (3 * 1024 + (first ? 8 : 5) * 64); }
-int tail2_pw_part(const Tail2Layer& L) { return (L.Cin + 63) / 64 * 64 * L.Cout + (L.Cout / 16) * 5 * 64; }
-
-struct Span2 {
-    int b, e;
-};
-int first_fit2(const std::vector<Span2>& used, int bytes, int cap) {
-    bytes = (bytes + 15) & ~15;
-    int pos = 0;
-    for (;;) {
-        bool moved = false;
-        for (const Span2& s : used)
-            if (pos < s.e && pos + bytes > s.b) {
-                pos = (s.e + 15) & ~15;
-                moved = true;
-            }
-        if (!moved) break;
-    }
-    return pos + bytes > cap ? -1 : pos;
-}
-bool overlap2(int b0, int e0, int b1, int e1) { return b0 < e1 && b1 < e0; }
-// the chunk barriers' counters (one dword per chunk slot) above everything else; the staged forms use them in the stamped measurement build
-// only, so a staged plan that fills the LDS to the last byte stays valid without them (bar_off = -1: that build then stamps no chunk barrier)
-void tail2_place_counters(Tail2Args& a, int cap) {
-    a.bar_off = (a.lds_bytes + 15) & ~15;
-    if (a.bar_off + 16 > cap) a.bar_off = -1;
-    else a.lds_bytes = a.bar_off + 16;
-}
-
-}  // namespace
-
-// Kernel arguments and LDS plan from the packer's descriptor table (32 words per block + 16 head words).  A block's map sits at LDS
-// offset 0 (input and output in place).  Its depthwise part and zero-point row are written while the PREVIOUS block's pointwise phase
-// runs: they avoid that block's output map (= this block's input) and pointwise part; its pointwise part is written while its own
-// depthwise phase runs: it avoids the map, the zero-point row and the depthwise part.  The first block's depthwise part is written behind
-// the last block of the previous group and stays through the head: it avoids the last map, the last pointwise part, the pooled vector and
-// the head's copy of the classifier matrix.  false = not a topology / size the kernel takes (the plan keeps i8_tail_kernel).
-bool tail2_plan(const int32_t* desc, int n_words, int n_layers, Tail2Args& a, bool mid) {
-    // (the stamped measurement build keeps the top 16 bytes free for the chunk barriers' counters: its staged plans get them too)
-    constexpr int LW = kTail2LayerWords, CAP = 160 * 1024 - (kStamped ? 16 : 0);
-    const int HW = mid ? 0 : 16, G = mid ? kMidG : kTailG;
-    if (n_layers < 1 || n_layers > 8 || n_words != LW * n_layers + HW) return false;
-    a.n_layers = n_layers;
-    int lds_need = 0;
-    Span2 prev_pw{0, 0};
-    auto grow = [&](int end) { lds_need = end > lds_need ? end : lds_need; };
-    // The first block's depthwise part is the one piece whose neighbours in time are at BOTH ends of the chain (it is written behind the last
-    // block's pointwise phase): placed by first fit like the others it can collide with the last block's parts, so a second attempt puts it at
-    // the top of the LDS.
-    for (int attempt = 0; attempt < 2; ++attempt) {
-    lds_need = 0;
-    prev_pw = {0, 0};
-    for (int i = 0; i < n_layers; ++i) {
-        const int32_t* d = desc + LW * i;
-        Tail2Layer& L = a.L[i];
-        L.H = d[0]; L.W = d[1]; L.Cin = d[2]; L.Cout = d[3]; L.S = d[4]; L.OH = d[5]; L.OW = d[6]; L.pt = d[7]; L.pl = d[8]; L.has_add = d[9];
-        L.zp_in = d[10]; L.dw_lo = d[11]; L.dw_hi = d[12]; L.pw_lo = d[13]; L.pw_hi = d[14];
-        L.add_m = d[15]; L.add_c1 = d[16]; L.add_e = d[17]; L.add_lo = d[18]; L.add_hi = d[19];
-        L.res_m = d[20]; L.res_c_lo = d[21]; L.res_c_hi = d[22]; L.res_k = d[23]; L.g_cst = d[24];
-        const bool first = i == 0;
-        auto is = [&](int cin, int cout, int st, int hh, int ww, int add) {
-            return L.Cin == cin && L.Cout == cout && L.S == st && L.H == hh && L.W == ww && L.has_add == add && L.pt == (st == 1) && L.pl == (st == 1) &&
-                   L.OH == hh / st && L.OW == ww / st;
-        };
-        // the instantiations of tail2_block: four in i8_tail2_kernel, two in i8_mid2_kernel
-        if (!mid && !((first && is(64, 128, 2, 16, 32, 0)) || (!first && (is(128, 128, 1, 8, 16, 1) || is(128, 256, 2, 8, 16, 0) || is(256, 256, 1, 4, 8, 1))))) return false;
-        if (mid && !((first && is(32, 64, 2, 32, 64, 0)) || (!first && is(64, 64, 1, 16, 32, 1)))) return false;
-        if (i > 0 && (L.H != a.L[i - 1].OH || L.W != a.L[i - 1].OW || L.Cin != a.L[i - 1].Cout)) return false;
-        if (L.g_cst < 0 || (L.g_cst & 3)) return false;
-        if (first && L.zp_in != -128) return false;   // (zero-filled taps + border biases assume it; the packer checks the same)
-        // every clamp whose result is stored as a byte is an int8 range (with the ADD the block's own term is not clamped: pw_lo / pw_hi unused)
-        if (L.dw_lo < -128 || L.dw_hi > 127 || L.dw_lo > L.dw_hi || L.pw_lo > L.pw_hi) return false;
-        if (!L.has_add && (L.pw_lo < -128 || L.pw_hi > 127)) return false;
-        if (L.has_add && (L.add_lo < -128 || L.add_hi > 127 || L.add_lo > L.add_hi || L.add_e < 1 || L.add_e > 22 || L.add_m < 0 ||
-                          L.res_m < 0 || L.res_k < 3 || L.res_k > 19))
-            return false;
-        if (tail2_dw_part(L, first) / 16 > kTail2MaxDw16) return false;
-        const int in_bytes = first ? 0 : G * L.H * L.W * (L.Cin + 16), out_bytes = G * L.OH * L.OW * (L.Cout + 16);
-        const Span2 map{0, in_bytes > out_bytes ? in_bytes : out_bytes};
-        L.x_off = first ? -1 : 0;
-        L.y_off = 0;
-        std::vector<Span2> used{map};
-        if (prev_pw.e > prev_pw.b) used.push_back(prev_pw);
-        L.zp_off = 0;
-        if (!first) {
-            L.zp_off = first_fit2(used, L.Cin + 16, CAP);
-            if (L.zp_off < 0) return false;
-            used.push_back({L.zp_off, L.zp_off + L.Cin + 16});
-        }
-        L.dw_off = first && attempt ? (CAP - tail2_dw_part(L, first)) & ~15 : first_fit2(used, tail2_dw_part(L, first), CAP);
-        if (L.dw_off < 0) return false;
-        const Span2 dw{L.dw_off, L.dw_off + tail2_dw_part(L, first)};
-        used = {map, dw};
-        if (!first) used.push_back({L.zp_off, L.zp_off + L.Cin + 16});
-        L.pw_off = first_fit2(used, tail2_pw_part(L), CAP);
-        if (L.pw_off < 0) return false;
-        prev_pw = {L.pw_off, L.pw_off + tail2_pw_part(L)};
-        grow(map.e); grow(dw.e); grow(prev_pw.e);
-    }
-    {
-        const Tail2Layer& lastL = a.L[n_layers - 1];
-        const Span2 dw0{a.L[0].dw_off, a.L[0].dw_off + tail2_dw_part(a.L[0], true)};
-        const Span2 map_lastL{0, G * lastL.OH * lastL.OW * (lastL.Cout + 16)};
-        if (!overlap2(dw0.b, dw0.e, map_lastL.b, map_lastL.e) && !overlap2(dw0.b, dw0.e, prev_pw.b, prev_pw.e)) break;
-        if (attempt) return false;
-    }
-    }  // attempt
-    const Tail2Layer& last = a.L[n_layers - 1];
-    // the first block's depthwise part of the NEXT group is written behind the last block's pointwise phase and lies there through the head
-    const Span2 dw0{a.L[0].dw_off, a.L[0].dw_off + tail2_dw_part(a.L[0], true)};
-    const Span2 map_last{0, G * last.OH * last.OW * (last.Cout + 16)};
-    if (overlap2(dw0.b, dw0.e, map_last.b, map_last.e) || overlap2(dw0.b, dw0.e, prev_pw.b, prev_pw.e)) return false;
-    a.resident = 0;
-    a.bar_off = -1;
-    if (mid) {
-        a.P = last.OH * last.OW;
-        a.C = last.Cout;
-        a.fcw_off = -1;
-        a.lds_bytes = lds_need;
-        tail2_place_counters(a, 160 * 1024);
-        return a.C % 16 == 0;
-    }
-    const int32_t* h = desc + LW * n_layers;
-    a.mean_zp_in = h[0]; a.mean_mult = h[1]; a.mean_shift = h[2]; a.mean_zp_out = h[3];
-    a.fc_zp_out = h[4]; a.fc_lo = h[5]; a.fc_hi = h[6]; a.g_fcw = h[7]; a.g_fcb = h[8]; a.g_fcm = h[9]; a.g_fcs = h[10]; a.g_hlut = h[11];
-    a.head_zp_fc = h[12]; a.head_zp_out = h[13]; a.P = h[14]; a.C = h[15];
-    if (a.g_fcw < 0 || a.g_fcb < 0 || a.g_hlut < -1 || (a.g_fcw & 3) || (a.g_fcb & 3)) return false;
-    if (a.fc_lo < -128 || a.fc_hi > 127 || a.fc_lo > a.fc_hi) return false;
-    if (a.P != last.OH * last.OW || a.C != last.Cout || a.C % 64 || a.C > 256 || a.NC < 1 || (a.NC + 15) / 16 > kTail2Waves) return false;
-    std::vector<Span2> used{map_last, dw0};
-    a.mean_off = first_fit2(used, kTailG * last.Cout, CAP);
-    if (a.mean_off < 0) return false;
-    used.push_back({a.mean_off, a.mean_off + kTailG * last.Cout});
-    grow(a.mean_off + kTailG * last.Cout);
-    a.fcw_off = -1;   // (the classifier's fragments come straight from memory)
-    a.lds_bytes = lds_need;
-    tail2_place_counters(a, 160 * 1024);
-    return true;
-}
-
-// The resident placement of a stage-2 plan (i8_mid2_kernel, option i8_mid_split): from a plan tail2_plan(..., mid = true) accepted, the same
-// blocks with LDS of its own for every block's depthwise part, pointwise part and zero-point row, laid out one behind the other above the
-// maps (the largest map of the chain times kMidG: input and output in place at offset 0), then the chunk barriers' counters.  Nothing
-// overlaps anything, so nothing is staged twice and nothing orders the two chunk slots.  false = it does not fit the 160 KB of a CU (or a
-// part is larger than the one-time staging copies): the caller keeps the staged plan and the kernel its staged form.
-bool tail2_plan_resident(Tail2Args& a) {
-    constexpr int CAP = 160 * 1024;
-    if (a.n_layers < 1 || a.n_layers > 8) return false;
-    int map_bytes = 0;
-    for (int i = 0; i < a.n_layers; ++i) {
-        const Tail2Layer& L = a.L[i];
-        const int in_bytes = i == 0 ? 0 : kMidG * L.H * L.W * (L.Cin + 16), out_bytes = kMidG * L.OH * L.OW * (L.Cout + 16);
-        map_bytes = std::max(map_bytes, std::max(in_bytes, out_bytes));
-    }
-    std::vector<Span2> used{{0, map_bytes}};
-    auto place = [&](int bytes) {
-        const int off = first_fit2(used, bytes, CAP);
-        if (off >= 0) used.push_back({off, off + bytes});
-        return off;
-    };
-    for (int i = 0; i < a.n_layers; ++i) {
-        Tail2Layer& L = a.L[i];
-        if (tail2_dw_part(L, i == 0) / 16 > kTail2MaxDw16 || tail2_pw_part(L) / 16 > kTail2MaxDw16) return false;
-        if ((L.dw_off = place(tail2_dw_part(L, i == 0))) < 0) return false;
-        if ((L.pw_off = place(tail2_pw_part(L))) < 0) return false;
-        L.zp_off = 0;
-        if (i > 0 && (L.zp_off = place(L.Cin + 16)) < 0) return false;
-    }
-    if ((a.bar_off = place(16)) < 0) return false;
-    for (size_t i = 0; i < used.size(); ++i)   // (first fit cannot produce an overlap; a cheap proof at load beats a wrong byte later)
-        for (size_t j = i + 1; j < used.size(); ++j)
-            if (overlap2(used[i].b, used[i].e, used[j].b, used[j].e)) return false;
-    const Tail2Layer& last = a.L[a.n_layers - 1];
-    if (last.OH != 16 || last.OW != 32 || last.Cout != 64 || a.P != 16 * 32 || a.C != 64) return false;   // (the wave-by-wave write-back's geometry)
-    int end = 0;
-    for (const Span2& u : used) end = std::max(end, u.e);
-    a.lds_bytes = end;
-    a.resident = 1;
-    return end <= CAP;
-}
-
-namespace {
-int tail2_cst_bytes(const Tail2Layer& L, bool first) { return tail2_dw_part(L, first) + tail2_pw_part(L); }
 }  // namespace
 
 #ifdef BN_TAIL_STAMPS
@@ -827,36 +640,11 @@ extern "C" __attribute__((visibility("default"))) int bn_debug_mid2_stamps(long 
 }
 #endif
 
-bool tail2_plan_dump(const Tail2Args& a, int* out, int n) {
-    if (n < 5 + 6 * a.n_layers) return false;
-    int map_bytes = 0;
-    for (int i = 0; i < a.n_layers; ++i) {
-        const Tail2Layer& L = a.L[i];
-        map_bytes = std::max(map_bytes, std::max(i == 0 ? 0 : kMidG * L.H * L.W * (L.Cin + 16), kMidG * L.OH * L.OW * (L.Cout + 16)));
-        int* o = out + 5 + 6 * i;
-        o[0] = L.dw_off; o[1] = tail2_dw_part(L, i == 0); o[2] = L.pw_off; o[3] = tail2_pw_part(L); o[4] = L.zp_off; o[5] = i == 0 ? 0 : L.Cin + 16;
-    }
-    out[0] = a.resident; out[1] = a.lds_bytes; out[2] = map_bytes; out[3] = a.bar_off; out[4] = a.n_layers;
-    return true;
-}
-
 // chunk barriers whose bounded spin ran out since the library was loaded (0 unless the kernel is broken: tests assert it); -1: the copy failed
 long tail2_giveups() {
     unsigned n = 0;
     if (hipDeviceSynchronize() != hipSuccess || hipMemcpyFromSymbol(&n, HIP_SYMBOL(g_tail2_giveups), sizeof n) != hipSuccess) return -1;
     return (long)n;
-}
-
-long tail2_const_words(const Tail2Args& a, bool mid) {
-    long need = 0;
-    auto upto = [&](long off, long words) { need = off + words > need ? off + words : need; };
-    for (int i = 0; i < a.n_layers; ++i) upto(a.L[i].g_cst, tail2_cst_bytes(a.L[i], i == 0) / 4);
-    if (mid) return need;
-    const long nct = (a.NC + 15) / 16;
-    upto(a.g_fcw, nct * (a.C / 64) * 256);
-    upto(a.g_fcb, nct * 48);
-    if (a.g_hlut >= 0) upto(a.g_hlut, 64);
-    return need;
 }
 
 bool launch_i8_tail2(Tail2Args a, hipStream_t s, const EmbOut* emb) {

@@ -348,17 +348,17 @@ bool check_plan(const BlobHeader& h, const std::vector<SlotRec>& slots, const st
                 namespace k = op::i8_tail;
                 c.dims({p[k::in_bytes], p[k::n_classes], p[k::n_layers], p[k::H0], p[k::W0], p[k::C0]}, "fused tail") &&
                     c.slot(o.in0, 1LL * p[k::H0] * p[k::W0] * p[k::C0], "input map") && c.slot(o.out, 4LL * p[k::n_classes], "scores") &&
-                    c.tensor(k::cst, 16, "constant block") && c.tensor(k::desc, 4LL * (24 * p[k::n_layers] + 16), "descriptor table");
+                    c.tensor(k::cst, 16, "constant block") && c.tensor(k::desc, 4LL * (kTailLayerWords * p[k::n_layers] + kTailHeadWords), "descriptor table");
                 if (c.ok && (p[k::n_classes] != (int)h.num_classes || p[k::n_layers] > 8 || p[BN_OP_TAIL_TAG] != BN_TAIL_OP)) c.bad("fused tail header");
-                break;  // the descriptor table itself is validated by bn::tail_plan at load (bn_plan_run.hip: prepare_plan)
+                break;  // the descriptor table itself is validated by bn::tail_plan (bn_chain_plan.cpp) at load (bn_plan_run.hip: prepare_plan)
             }
             case BN_OP_I8_MID: {
                 namespace k = op::i8_mid;
                 c.dims({p[k::in_bytes], p[k::n_layers], p[k::H0], p[k::W0], p[k::C0], p[k::P_last], p[k::C_last]}, "fused stage-2 chain") &&
                     c.slot(o.in0, 1LL * p[k::H0] * p[k::W0] * p[k::C0], "input map") && c.slot(o.out, 1LL * p[k::P_last] * p[k::C_last], "output map") &&
-                    c.tensor(k::cst, 16, "constant block") && c.tensor(k::desc, 4LL * 32 * p[k::n_layers], "descriptor table");
+                    c.tensor(k::cst, 16, "constant block") && c.tensor(k::desc, 4LL * kTail2LayerWords * p[k::n_layers], "descriptor table");
                 if (c.ok && (p[k::n_layers] > 8 || p[BN_OP_TAIL_TAG] != BN_MID_OP)) c.bad("fused stage-2 chain header");
-                break;  // (descriptor table: bn::tail2_plan at load)
+                break;  // (descriptor table: bn::tail2_plan, bn_chain_plan.cpp, at load)
             }
             default:
                 c.bad("unknown operator kind");

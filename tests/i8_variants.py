@@ -12,7 +12,7 @@ Plain helper module: no fixtures, no test functions.
 the tensor the original reads.  With the original's own scales on the copy's three outputs the lowering keeps every fused form (``tail =
 1``, matrix-core constants present) for one more res128 and one more res256 block, so no scale had to be adjusted; a ninth block makes
 ``_add_tail_op`` leave the tail unfused (``len(chain) > 8``).  The LIBRARY does not fuse the 8-layer chain, though: ``tail_plan`` finds no
-LDS placement for it (tests/test_gpu_i8_variants.py: TAIL_FORM has the cause), so on the device these variants run the per-block kernels.
+LDS placement for it (TAIL_FORM below has the cause), so on the device these variants run the per-block kernels.
 """
 
 from __future__ import annotations
@@ -236,6 +236,16 @@ VARIANTS.update({
 })
 GPU_VARIANTS = [n for n, v in VARIANTS.items() if v["gpu"]]
 CHAIN_VARIANTS = [n for n, v in VARIANTS.items() if v["chain"]]
+# ``runner.tail_form()[0]``: 2 = i8_tail2_kernel runs by default (i8_tail_kernel behind it), 1 = i8_tail_kernel only, 0 = per-block kernels.
+# The library's host-side planners (csrc/bn_chain_plan.cpp) compute these values from the descriptor tables; tests/test_chain_plan_host.py
+# asserts them on the CPU from the planners themselves, tests/test_gpu_i8_variants.py from the loaded model and from which kernel ran.
+# Shipped chain: what the packer and the NC conditions of tail_plan / tail2_plan say.  The chains of 2, 4 and 5 blocks take the form their NC
+# allows.  The 8-block chain is refused by tail_plan (and with it by tail2_plan, which only runs where the first form could): (0, 0), the
+# per-block kernels run.  Its first fit puts the output map of the 128 -> 256 block at 67584 when that block's input sits at 0 — which an EVEN
+# number of res128 blocks in front of it makes it do — and the 64 KB of pointwise weights of the first res256 block then fit neither below
+# the maps nor above them (100864 + 65536 > 160 KB).  A fallback of the placement, not a wrong result: pinned here, so that a planner that
+# starts to accept the chain shows up.
+TAIL_FORM = {n: (0 if v["layers"] == 8 else 2 if v["nc"] <= 128 else 1 if v["nc"] <= 256 else 0) for n, v in VARIANTS.items() if v["gpu"]}
 
 
 def build(name: str):
@@ -264,6 +274,14 @@ def case(name: str) -> dict:
     return dict(model=model, scores=scores, env=env, fc=fc, logits=(fc.astype(np.float32) - np.float32(z)) * np.float32(s), emb=emb,
                 emb_f32=(emb.astype(np.float32) - np.float32(ze)) * np.float32(se),
                 score_bytes=env[h["logistic"].outputs[0]] if h["logistic"] is not None else None)
+
+
+@functools.lru_cache(maxsize=None)
+def plan(name: str):
+    """The production plan of ``case(name)["model"]`` (cached for the host tests that only read it: treat as read-only)."""
+    from birdnet_stm32.models._lower_i8 import lower_i8
+
+    return lower_i8(case(name)["model"])
 
 
 def weight_flips(c: dict, cls: int) -> np.ndarray:

@@ -19,14 +19,7 @@ pytestmark = pytest.mark.gpu
 
 BATCHES = (16, 1, 2, 3, 5, 9)
 ALTERNATIVES = (dict(i8_tail=0), dict(i8_tail_mfdw=0), dict(i8_tail_fclds=0), dict(i8_tail_mfdw=0, i8_tail_fclds=0))
-# ``runner.tail_form()[0]``: 2 = i8_tail2_kernel runs by default (i8_tail_kernel behind it), 1 = i8_tail_kernel only, 0 = per-block kernels.
-# Shipped chain: what the packer and the NC conditions of tail_plan / tail2_plan say.  Other chains: the library's LDS placement decides;
-# the values are what it reported on an MI355X.  The chains of 2, 4 and 5 blocks take the form their NC allows.  The 8-block chain is refused
-# by tail_plan (and with it by tail2_plan, which only runs where the first form could): (0, 0), the per-block kernels run.  Its first fit puts
-# the output map of the 128 -> 256 block at 67584 when that block's input sits at 0 — which an EVEN number of res128 blocks in front of it
-# makes it do — and the 64 KB of pointwise weights of the first res256 block then fit neither below the maps nor above them (100864 + 65536 >
-# 160 KB).  A fallback of the placement, not a wrong result: pinned here, so that a planner that starts to accept the chain shows up.
-TAIL_FORM = {n: (0 if v["layers"] == 8 else 2 if v["nc"] <= 128 else 1 if v["nc"] <= 256 else 0) for n, v in iv.VARIANTS.items() if v["gpu"]}
+TAIL_FORM = iv.TAIL_FORM   # ``runner.tail_form()[0]`` per variant (tests/i8_variants.py says where the values come from)
 
 
 @pytest.fixture(scope="module")

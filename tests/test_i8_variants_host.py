@@ -12,9 +12,7 @@ import i8_variants as iv
 
 
 def _plan(name):
-    from birdnet_stm32.models._lower_i8 import lower_i8
-
-    return lower_i8(iv.case(name)["model"])
+    return iv.plan(name)   # (lowered once for this module and tests/test_chain_plan_host.py)
 
 
 @pytest.mark.parametrize("name", list(iv.VARIANTS))
