@@ -291,30 +291,110 @@ def _epoch_rows(seed: int, epoch: int, n: int, rows) -> np.ndarray:
     return perm if rows is None else np.ascontiguousarray(rows[perm])
 
 
-def _fit_loop(backend, n: int, epochs: int, batch: int, seed: int, patience: int, has_val: bool, rows=None) -> dict:
-    """Epochs, validation and early stopping, shared by the device and the numpy fit.  ``backend``: ``epoch(perm) -> step losses``,
-    ``val_loss()``, ``get() -> (W, b)``, ``set(W, b)``.  ``n``: the length of an epoch (``len(rows)`` with ``rows``)."""
-    history = {"loss": [], "val_loss": [], "step_loss": [], "best_epoch": None, "stopped_epoch": None}
-    best, best_weights, wait = math.inf, None, 0
-    for epoch in range(epochs):
-        losses = np.asarray(backend.epoch(_epoch_rows(seed, epoch, n, rows)), np.float64)
-        history["step_loss"].append(losses)
-        history["loss"].append(float(losses.mean()))
-        if not has_val:
+@dataclass(frozen=True)
+class _FitPlan:
+    """What every fit knows once its arguments are checked (``_plan_fit``)."""
+
+    activation: str
+    optimizer: str      # a sweep: the first trial's, like ``dropout``; its trials carry their own hyperparameters
+    lr: float
+    weight_decay: float
+    clipnorm: float
+    dropout: float
+    label_smoothing: float
+    loss: str
+    focal_gamma: float
+    sample_weight: np.ndarray | None   # float32 [n]
+    rows: np.ndarray | None            # int32 [m]
+    n: int              # rows of X
+    D: int
+    C: int
+    m: int              # the length of an epoch: n, or len(rows)
+    batch: int
+    epochs: int
+    patience: int
+    seed: int
+    total: int          # steps of the schedule
+    has_val: bool
+    W0: np.ndarray | None   # the initial head; None in the plan of a fit that hands over to a sweep
+    b0: np.ndarray | None
+
+
+def _plan_fit(X, Y, X_val, *, device: bool, activation, optimizer, batch_size, dropout, epochs, learning_rate=1e-3, weight_decay=0.0, clipnorm=1.0,
+              patience=10, seed=42, label_smoothing=0.0, loss="auto", focal_gamma=2.0, sample_weight=None, rows=None) -> _FitPlan:
+    """The checks every fit runs, in one order, and what follows from the arguments.  ``X``: anything with the ``shape`` of the training
+    rows.  ``device``: the fit runs on the device, which takes D and C up to ``_hip.PROBE_MAX_D`` / ``PROBE_MAX_C`` and ``clipnorm`` as the
+    Python float; the numpy fits round ``clipnorm`` through float32, as the C ABI does."""
+    _check_fit_args(X, Y, activation, optimizer, batch_size, dropout, epochs)
+    if not device:
+        label_smoothing = _check_label_smoothing(label_smoothing)
+    loss, focal_gamma = _check_loss(loss, focal_gamma, activation)
+    n, D, C = int(X.shape[0]), int(X.shape[1]), int(Y.shape[1])
+    sample_weight, rows = _check_weights_rows(n, sample_weight, rows)
+    W0 = b0 = None
+    if device:
+        from birdnet_stm32 import _hip
+
+        label_smoothing = _check_label_smoothing(label_smoothing)
+    # A single device fit with smoothing runs as a sweep of one trial, which makes its own plan: the D/C refusal and the head are that one's
+    if not (device and label_smoothing > 0):
+        if device and not (1 <= D <= _hip.PROBE_MAX_D and 1 <= C <= _hip.PROBE_MAX_C):
+            raise ValueError(f"the device path takes 1 <= D <= {_hip.PROBE_MAX_D} and 1 <= C <= {_hip.PROBE_MAX_C}, got D={D} C={C}")
+        W0, b0 = init_head(D, C, seed)
+    m = n if rows is None else len(rows)
+    batch = min(int(batch_size), m)
+    return _FitPlan(activation=activation, optimizer=optimizer, lr=float(learning_rate), weight_decay=float(weight_decay),
+                    clipnorm=float(clipnorm) if device else float(np.float32(clipnorm)), dropout=float(dropout), label_smoothing=label_smoothing,
+                    loss=loss, focal_gamma=focal_gamma, sample_weight=sample_weight, rows=rows, n=n, D=D, C=C, m=m, batch=batch, epochs=int(epochs),
+                    patience=int(patience), seed=int(seed), total=int(epochs) * math.ceil(m / batch), has_val=X_val is not None and len(X_val) > 0,
+                    W0=W0, b0=b0)
+
+
+class _EarlyStopping:
+    """Keras' ``EarlyStopping(patience)`` on the validation loss of one head, and the ``history`` its fit returns."""
+
+    def __init__(self, patience: int):
+        self.patience, self.best, self.wait = patience, math.inf, 0
+        self.history = {"loss": [], "val_loss": [], "step_loss": [], "best_epoch": None, "stopped_epoch": None}
+
+    def add_epoch(self, step_losses) -> None:
+        losses = np.ascontiguousarray(step_losses, np.float64)
+        self.history["step_loss"].append(losses)
+        self.history["loss"].append(float(losses.mean()))
+
+    def update(self, epoch: int, val: float) -> tuple[bool, bool]:
+        """``(improved, stop)`` after epoch ``epoch`` gave the validation loss ``val``."""
+        self.history["val_loss"].append(val)
+        if val < self.best:
+            self.best, self.wait, self.history["best_epoch"] = val, 0, epoch
+            return True, False
+        self.wait += 1
+        stop = self.wait >= self.patience and epoch > 0
+        if stop:
+            self.history["stopped_epoch"] = epoch
+        return False, stop
+
+    def finish(self) -> dict:
+        self.history["step_loss"] = np.concatenate(self.history["step_loss"])
+        return self.history
+
+
+def _fit_loop(backend, plan: _FitPlan) -> dict:
+    """Epochs, validation and early stopping with the best weights restored, shared by the device and the numpy fit.  ``backend``:
+    ``epoch(perm) -> step losses``, ``val_loss()``, ``get() -> (W, b)``, ``set(W, b)``."""
+    stopping, best_weights = _EarlyStopping(plan.patience), None
+    for epoch in range(plan.epochs):
+        stopping.add_epoch(backend.epoch(_epoch_rows(plan.seed, epoch, plan.m, plan.rows)))
+        if not plan.has_val:
             continue
-        val = float(backend.val_loss())
-        history["val_loss"].append(val)
-        if val < best:
-            best, best_weights, wait, history["best_epoch"] = val, backend.get(), 0, epoch
-        else:
-            wait += 1
-            if wait >= patience and epoch > 0:
-                history["stopped_epoch"] = epoch
-                break
+        improved, stop = stopping.update(epoch, float(backend.val_loss()))
+        if improved:
+            best_weights = backend.get()
+        if stop:
+            break
     if best_weights is not None:
         backend.set(*best_weights)
-    history["step_loss"] = np.concatenate(history["step_loss"])
-    return history
+    return stopping.finish()
 
 
 # -- the result -----------------------------------------------------------------------------------------------------------------------
@@ -418,37 +498,39 @@ class ProbeHead:
 
 # -- the specification ----------------------------------------------------------------------------------------------------------------
 class _NumpyBackend:
-    def __init__(self, X, Y, Xv, Yv, W, b, cfg, dtype, sample_weight=None):
-        self.X, self.Y, self.Xv, self.Yv, self.cfg, self.dt = X, Y, Xv, Yv, cfg, dtype
-        self.w = None if sample_weight is None else np.asarray(sample_weight).astype(dtype)   # [rows of X], indexed like Y
-        self.loss_kw = dict(loss=cfg.get("loss", "auto"), focal_gamma=cfg.get("focal_gamma", 2.0))
-        self.P = np.concatenate([W, b[None, :]]).astype(dtype)   # the bias is row D, as on the device
+    def __init__(self, X, Y, X_val, Y_val, plan, dtype):
+        cast = lambda a: None if a is None else np.asarray(a).astype(dtype)  # noqa: E731
+        self.X, self.Y, self.plan, self.dt = cast(X), cast(Y), plan, np.dtype(dtype).type
+        self.Xv, self.Yv = (cast(X_val), cast(Y_val)) if plan.has_val else (None, None)
+        self.w = cast(plan.sample_weight)   # [rows of X], indexed like Y
+        self.loss_kw = dict(loss=plan.loss, focal_gamma=plan.focal_gamma)
+        self.set(plan.W0, plan.b0)
         self.state = {"m": np.zeros_like(self.P), "v": np.zeros_like(self.P)}
         self.t = 0
 
     def epoch(self, perm):
-        c, dt, D = self.cfg, self.dt, self.X.shape[1]
+        c, dt, D = self.plan, self.dt, self.X.shape[1]
         losses = []
-        for s in range(0, len(perm), c["batch"]):
-            idx = perm[s : s + c["batch"]]
+        for s in range(0, len(perm), c.batch):
+            idx = perm[s : s + c.batch]
             B = len(idx)
-            xd = np.concatenate([self.X[idx] * dropout_mask(c["seed"], self.t, B, D, c["dropout"], dt), np.ones((B, 1), dt)], axis=1)
-            P = head_scores(xd[:, :D], self.P[:D], self.P[D], c["activation"])
+            xd = np.concatenate([self.X[idx] * dropout_mask(c.seed, self.t, B, D, c.dropout, dt), np.ones((B, 1), dt)], axis=1)
+            P = head_scores(xd[:, :D], self.P[:D], self.P[D], c.activation)
             y = self.Y[idx]
-            if c.get("label_smoothing", 0.0) > 0:
-                y = smooth_targets(y, c["label_smoothing"], c["activation"])
+            if c.label_smoothing > 0:
+                y = smooth_targets(y, c.label_smoothing, c.activation)
             w = None if self.w is None else self.w[idx]
-            losses.append(float(probe_loss(P, y, c["activation"], sample_weight=w, **self.loss_kw)))
-            G = probe_loss_gradient(P, y, c["activation"], sample_weight=w, **self.loss_kw)
-            g = clip_by_global_norm(xd.T @ G, c["clipnorm"])
-            lr_t, alpha_t = step_sizes(c["lr"], self.t, c["total"])
-            self.P = optimizer_step(self.P, g, self.state, c["optimizer"], np.float32(lr_t), np.float32(alpha_t), np.float32(c["weight_decay"]))
+            losses.append(float(probe_loss(P, y, c.activation, sample_weight=w, **self.loss_kw)))
+            G = probe_loss_gradient(P, y, c.activation, sample_weight=w, **self.loss_kw)
+            g = clip_by_global_norm(xd.T @ G, c.clipnorm)
+            lr_t, alpha_t = step_sizes(c.lr, self.t, c.total)
+            self.P = optimizer_step(self.P, g, self.state, c.optimizer, np.float32(lr_t), np.float32(alpha_t), np.float32(c.weight_decay))
             self.t += 1
         return losses
 
     def val_loss(self):   # the loss that was asked for, never weighted, never smoothed
         D = self.P.shape[0] - 1
-        return probe_loss(head_scores(self.Xv, self.P[:D], self.P[D], self.cfg["activation"]), self.Yv, self.cfg["activation"], **self.loss_kw)
+        return probe_loss(head_scores(self.Xv, self.P[:D], self.P[D], self.plan.activation), self.Yv, self.plan.activation, **self.loss_kw)
 
     def get(self):
         return self.P[:-1].copy(), self.P[-1].copy()
@@ -463,67 +545,61 @@ def fit_probe_reference(X, Y, X_val=None, Y_val=None, *, activation="sigmoid", e
     """The procedure of ``fit_probe`` in numpy, all arithmetic in ``dtype``.  ``history["W"]`` / ``["b"]`` keep the result in ``dtype``.
     ``loss`` / ``focal_gamma`` / ``sample_weight`` / ``rows``: see ``fit_probe``."""
     X, Y = np.asarray(X), np.asarray(Y)
-    _check_fit_args(X, Y, activation, optimizer, batch_size, dropout, epochs)
-    label_smoothing = _check_label_smoothing(label_smoothing)
-    loss, focal_gamma = _check_loss(loss, focal_gamma, activation)
-    sample_weight, rows = _check_weights_rows(X.shape[0], sample_weight, rows)
-    D = X.shape[1]
-    n = X.shape[0] if rows is None else len(rows)   # the length of an epoch
-    batch = min(int(batch_size), n)
-    has_val = X_val is not None and len(X_val) > 0
-    W0, b0 = init_head(D, Y.shape[1], seed)
-    cfg = dict(activation=activation, optimizer=optimizer, batch=batch, seed=int(seed), dropout=float(dropout), clipnorm=float(np.float32(clipnorm)),
-               lr=float(learning_rate), weight_decay=float(weight_decay), total=int(epochs) * math.ceil(n / batch), label_smoothing=label_smoothing,
-               loss=loss, focal_gamma=focal_gamma)
-    be = _NumpyBackend(X.astype(dtype), Y.astype(dtype), np.asarray(X_val).astype(dtype) if has_val else None,
-                       np.asarray(Y_val).astype(dtype) if has_val else None, W0, b0, cfg, np.dtype(dtype).type, sample_weight)
-    history = _fit_loop(be, n, int(epochs), batch, int(seed), int(patience), has_val, rows)
+    plan = _plan_fit(X, Y, X_val, device=False, activation=activation, optimizer=optimizer, batch_size=batch_size, dropout=dropout, epochs=epochs,
+                     learning_rate=learning_rate, weight_decay=weight_decay, clipnorm=clipnorm, patience=patience, seed=seed,
+                     label_smoothing=label_smoothing, loss=loss, focal_gamma=focal_gamma, sample_weight=sample_weight, rows=rows)
+    return _reference_fit(_NumpyBackend(X, Y, X_val, Y_val, plan, dtype), plan, class_names)
+
+
+def _reference_fit(be, plan: _FitPlan, class_names) -> ProbeHead:
+    history = _fit_loop(be, plan)
     W, b = be.get()
     history["W"], history["b"] = W, b
-    return ProbeHead(W, b, activation, list(class_names or []), history)
+    return ProbeHead(W, b, plan.activation, list(class_names or []), history)
 
 
 # -- the device fit -------------------------------------------------------------------------------------------------------------------
 class _DeviceBackend:
     """``bn_probe_*`` over resident ``X`` / ``Y``.  ``self.n`` is the number of rows of ``X``, ``self.m`` the length of an epoch: the two
-    differ when the epoch runs over ``rows`` with repeats (``epoch_len``).  ``cfg`` may carry ``loss`` / ``focal_gamma``."""
+    differ when the epoch runs over ``rows`` with repeats (``plan.m``).  ``per_trial``: ``()``, or ``(T,)`` in a sweep: the shape of one
+    step's loss and of the validation loss."""
 
-    def __init__(self, ctx, X, Y, Xv, Yv, W, b, cfg, sample_weight=None, epoch_len=None):
+    SET_LOSS, DESTROY = "bn_probe_set_loss", "bn_probe_destroy"
+
+    def __init__(self, ctx, X, Y, X_val, Y_val, plan, per_trial=()):
         import ctypes
 
         import torch
 
         from birdnet_stm32 import _hip
 
-        self.torch, self.hip, self.ctx, self.cfg = torch, _hip, ctx, cfg
+        self.torch, self.hip, self.ctx, self.plan = torch, _hip, ctx, plan
         self.dev = torch.device(f"cuda:{ctx.device}")
-        self.X, self.Y, self.Xv, self.Yv = (self._dev(a) for a in (X, Y, Xv, Yv))
-        self.W, self.b = self._dev(W), self._dev(b)
+        self.X, self.Y = self._dev(X), self._dev(Y)
+        self.Xv, self.Yv = (self._dev(X_val), self._dev(Y_val)) if plan.has_val else (None, None)
+        self.W, self.b, self.w = self._dev(plan.W0), self._dev(plan.b0), self._dev(plan.sample_weight)
         self.n, self.D = self.X.shape
-        self.C = self.Y.shape[1]
-        self._epoch_shape(sample_weight, epoch_len)
-        self.step_loss = torch.empty(self.steps, dtype=torch.float32, device=self.dev)
-        self.val = torch.empty(1, dtype=torch.float32, device=self.dev)
-        h = ctypes.c_void_p()
+        self.C, self.m = self.Y.shape[1], plan.m
+        if self.w is not None and tuple(self.w.shape) != (self.n,):
+            raise ValueError(f"sample_weight must have shape ({self.n},), got {tuple(self.w.shape)}")
+        self.steps = math.ceil(self.m / plan.batch)
+        self.step_loss = torch.empty((self.steps, *per_trial), dtype=torch.float32, device=self.dev)
+        self.val = torch.empty(per_trial or 1, dtype=torch.float32, device=self.dev)
+        self.handle = ctypes.c_void_p()
         with torch.cuda.device(self.dev):
-            _hip.check(ctx.lib.bn_probe_create(ctx.handle, self.D, self.C, _hip.PROBE_ACTIVATIONS[cfg["activation"]], _hip.PROBE_OPTIMIZERS[cfg["optimizer"]],
-                                               cfg["lr"], cfg["weight_decay"], cfg["clipnorm"], cfg["dropout"], cfg["seed"] & 0xFFFFFFFF, cfg["total"],
-                                               self.W.data_ptr(), self.b.data_ptr(), ctypes.byref(h), self._stream()))
-        self.handle = h
-        if cfg.get("loss", "auto") != "auto":   # (the default is the probe's own: nothing to set)
+            _hip.check(self._create(ctypes.byref(self.handle)))
+        if plan.loss != "auto":   # (the default is the handle's own: nothing to set)
             try:
-                _hip.check(ctx.lib.bn_probe_set_loss(h, _hip.PROBE_LOSSES[cfg["loss"]], float(cfg.get("focal_gamma", 2.0))))
+                _hip.check(getattr(ctx.lib, self.SET_LOSS)(self.handle, _hip.PROBE_LOSSES[plan.loss], plan.focal_gamma))
             except Exception:
                 self.close()
                 raise
 
-    def _epoch_shape(self, sample_weight, epoch_len):
-        """The row weights ``[self.n]`` on the device (or ``None``) and the epoch's length ``self.m`` with its step count."""
-        self.w = self._dev(sample_weight)
-        if self.w is not None and tuple(self.w.shape) != (self.n,):
-            raise ValueError(f"sample_weight must have shape ({self.n},), got {tuple(self.w.shape)}")
-        self.m = self.n if epoch_len is None else int(epoch_len)
-        self.steps = math.ceil(self.m / self.cfg["batch"])
+    def _create(self, out):
+        c, hip = self.plan, self.hip
+        return self.ctx.lib.bn_probe_create(self.ctx.handle, self.D, self.C, hip.PROBE_ACTIVATIONS[c.activation], hip.PROBE_OPTIMIZERS[c.optimizer], c.lr,
+                                            c.weight_decay, c.clipnorm, c.dropout, c.seed & 0xFFFFFFFF, c.total, self.W.data_ptr(), self.b.data_ptr(),
+                                            out, self._stream())
 
     def _dev(self, a):
         if a is None:
@@ -537,6 +613,10 @@ class _DeviceBackend:
 
         return ctypes.c_void_p(self.torch.cuda.current_stream(self.dev).cuda_stream)
 
+    @staticmethod
+    def _ptr(t):
+        return None if t is None else t.data_ptr()
+
     def _check_perm(self, perm):
         if perm.shape != (self.m,) or perm.dtype != np.int32:
             raise ValueError(f"an epoch takes {self.m} int32 row numbers, got {perm.shape} of {perm.dtype}")
@@ -545,12 +625,8 @@ class _DeviceBackend:
         self._check_perm(perm)
         with self.torch.cuda.device(self.dev):
             d_perm = self.torch.from_numpy(perm).to(self.dev)
-            if self.w is None:
-                self.hip.check(self.ctx.lib.bn_probe_epoch(self.handle, self.X.data_ptr(), self.Y.data_ptr(), d_perm.data_ptr(), self.m, self.cfg["batch"],
-                                                           self.step_loss.data_ptr(), self._stream()))
-            else:
-                self.hip.check(self.ctx.lib.bn_probe_epoch_weighted(self.handle, self.X.data_ptr(), self.Y.data_ptr(), self.w.data_ptr(), d_perm.data_ptr(),
-                                                                    self.m, self.cfg["batch"], self.step_loss.data_ptr(), self._stream()))
+            self.hip.check(self.ctx.lib.bn_probe_epoch_weighted(self.handle, self.X.data_ptr(), self.Y.data_ptr(), self._ptr(self.w), d_perm.data_ptr(),
+                                                                self.m, self.plan.batch, self.step_loss.data_ptr(), self._stream()))
             return self.step_loss.cpu().numpy()   # (synchronises: d_perm outlives the epoch)
 
     def val_loss(self):
@@ -572,8 +648,19 @@ class _DeviceBackend:
     def close(self):
         if self.handle:
             self.torch.cuda.synchronize(self.dev)
-            self.ctx.lib.bn_probe_destroy(self.handle)
+            getattr(self.ctx.lib, self.DESTROY)(self.handle)
             self.handle = None
+
+
+def _device_fit(be, plan: _FitPlan, class_names) -> ProbeHead:
+    """The fit on a device backend made for ``plan``, which it closes: epochs, the best weights, the head."""
+    try:
+        history = _fit_loop(be, plan)
+        W, b = be.get()
+        W, b = W.cpu().numpy(), b.cpu().numpy()
+    finally:
+        be.close()
+    return ProbeHead(W, b, plan.activation, list(class_names or []), history)
 
 
 def fit_probe(ctx_or_runner, X, Y, X_val=None, Y_val=None, *, activation="sigmoid", epochs=50, batch_size=32, learning_rate=1e-3, optimizer="adam",
@@ -594,34 +681,16 @@ def fit_probe(ctx_or_runner, X, Y, X_val=None, Y_val=None, *, activation="sigmoi
       ``rows[epoch_permutation(seed, e, M)]``; the steps per epoch and the short last batch follow ``M``.  ``X``, ``Y`` and
       ``sample_weight`` are indexed through it and nothing is duplicated on the device.  The dropout draw is per position in the batch,
       so two copies of a row in one batch get different masks."""
-    from birdnet_stm32 import _hip
-
-    _check_fit_args(X, Y, activation, optimizer, batch_size, dropout, epochs)
-    loss, focal_gamma = _check_loss(loss, focal_gamma, activation)
-    sample_weight, rows = _check_weights_rows(int(X.shape[0]), sample_weight, rows)
-    if _check_label_smoothing(label_smoothing) > 0:
+    plan = _plan_fit(X, Y, X_val, device=True, activation=activation, optimizer=optimizer, batch_size=batch_size, dropout=dropout, epochs=epochs,
+                     learning_rate=learning_rate, weight_decay=weight_decay, clipnorm=clipnorm, patience=patience, seed=seed,
+                     label_smoothing=label_smoothing, loss=loss, focal_gamma=focal_gamma, sample_weight=sample_weight, rows=rows)
+    if plan.label_smoothing > 0:
         trial = ProbeTrial(learning_rate=learning_rate, optimizer=optimizer, weight_decay=weight_decay, clipnorm=clipnorm, dropout=dropout,
                            label_smoothing=label_smoothing)
         return fit_probe_sweep(ctx_or_runner, X, Y, X_val, Y_val, [trial], activation=activation, epochs=epochs, batch_size=batch_size, patience=patience,
-                               seed=seed, class_names=class_names, loss=loss, focal_gamma=focal_gamma, sample_weight=sample_weight, rows=rows).heads[0]
-    n, D = (int(X.shape[0]) if rows is None else len(rows)), int(X.shape[1])   # n: the length of an epoch
-    C = int(Y.shape[1])
-    if not (1 <= D <= _hip.PROBE_MAX_D and 1 <= C <= _hip.PROBE_MAX_C):
-        raise ValueError(f"the device path takes 1 <= D <= {_hip.PROBE_MAX_D} and 1 <= C <= {_hip.PROBE_MAX_C}, got D={D} C={C}")
-    ctx = getattr(ctx_or_runner, "ctx", ctx_or_runner)
-    batch = min(int(batch_size), n)
-    has_val = X_val is not None and len(X_val) > 0
-    W0, b0 = init_head(D, C, seed)
-    cfg = dict(activation=activation, optimizer=optimizer, batch=batch, seed=int(seed), dropout=float(dropout), clipnorm=float(clipnorm),
-               lr=float(learning_rate), weight_decay=float(weight_decay), total=int(epochs) * math.ceil(n / batch), loss=loss, focal_gamma=focal_gamma)
-    be = _DeviceBackend(ctx, X, Y, X_val if has_val else None, Y_val if has_val else None, W0, b0, cfg, sample_weight, n)
-    try:
-        history = _fit_loop(be, n, int(epochs), batch, int(seed), int(patience), has_val, rows)
-        W, b = be.get()
-        W, b = W.cpu().numpy(), b.cpu().numpy()
-    finally:
-        be.close()
-    return ProbeHead(W, b, activation, list(class_names or []), history)
+                               seed=seed, class_names=class_names, loss=plan.loss, focal_gamma=plan.focal_gamma, sample_weight=plan.sample_weight,
+                               rows=plan.rows).heads[0]
+    return _device_fit(_DeviceBackend(getattr(ctx_or_runner, "ctx", ctx_or_runner), X, Y, X_val, Y_val, plan), plan, class_names)
 
 
 # -- many trials at once ---------------------------------------------------------------------------------------------------------------
@@ -680,36 +749,18 @@ def _check_trials(trials) -> list:
 class _SweepBackend(_DeviceBackend):
     """``bn_probe_sweep_*`` over resident ``X`` / ``Y``: every trial of the sweep takes the same step in the same launches."""
 
-    def __init__(self, ctx, X, Y, Xv, Yv, W, b, cfg, trials, sample_weight=None, epoch_len=None):
-        import ctypes
+    SET_LOSS, DESTROY = "bn_probe_sweep_set_loss", "bn_probe_sweep_destroy"
 
-        import torch
+    def __init__(self, ctx, X, Y, X_val, Y_val, plan, trials):
+        self.trials, self.T, self.t = trials, len(trials), 0
+        super().__init__(ctx, X, Y, X_val, Y_val, plan, per_trial=(self.T,))
 
-        from birdnet_stm32 import _hip
-
-        self.torch, self.hip, self.ctx, self.cfg, self.trials = torch, _hip, ctx, cfg, trials
-        self.dev = torch.device(f"cuda:{ctx.device}")
-        self.X, self.Y, self.Xv, self.Yv = (self._dev(a) for a in (X, Y, Xv, Yv))
-        self.W, self.b = self._dev(W), self._dev(b)
-        self.n, self.D = self.X.shape
-        self.C, self.T = self.Y.shape[1], len(trials)
-        self._epoch_shape(sample_weight, epoch_len)
-        self.step_loss = torch.empty((self.steps, self.T), dtype=torch.float32, device=self.dev)
-        self.val = torch.empty(self.T, dtype=torch.float32, device=self.dev)
-        self.t = 0
-        rows = (_hip.ProbeTrialStruct * self.T)(*[_hip.ProbeTrialStruct(_hip.PROBE_OPTIMIZERS[t.optimizer], t.learning_rate, t.weight_decay, t.clipnorm,
-                                                                        t.dropout, t.label_smoothing) for t in trials])
-        h = ctypes.c_void_p()
-        with torch.cuda.device(self.dev):
-            _hip.check(ctx.lib.bn_probe_sweep_create(ctx.handle, self.D, self.C, _hip.PROBE_ACTIVATIONS[cfg["activation"]], self.T, rows, cfg["seed"] & 0xFFFFFFFF,
-                                                     cfg["total"], self.W.data_ptr(), self.b.data_ptr(), ctypes.byref(h), self._stream()))
-        self.handle = h
-        if cfg.get("loss", "auto") != "auto":
-            try:
-                _hip.check(ctx.lib.bn_probe_sweep_set_loss(h, _hip.PROBE_LOSSES[cfg["loss"]], float(cfg.get("focal_gamma", 2.0))))
-            except Exception:
-                self.close()
-                raise
+    def _create(self, out):
+        c, hip = self.plan, self.hip
+        rows = (hip.ProbeTrialStruct * self.T)(*[hip.ProbeTrialStruct(hip.PROBE_OPTIMIZERS[t.optimizer], t.learning_rate, t.weight_decay, t.clipnorm,
+                                                                      t.dropout, t.label_smoothing) for t in self.trials])
+        return self.ctx.lib.bn_probe_sweep_create(self.ctx.handle, self.D, self.C, hip.PROBE_ACTIVATIONS[c.activation], self.T, rows, c.seed & 0xFFFFFFFF,
+                                                  c.total, self.W.data_ptr(), self.b.data_ptr(), out, self._stream())
 
     def _mask(self, mask):
         return self.torch.from_numpy(np.ascontiguousarray(mask, np.uint8)).to(self.dev)
@@ -717,16 +768,12 @@ class _SweepBackend(_DeviceBackend):
     def epoch(self, perm, active):
         """One epoch of the active trials: step losses ``[steps, T]`` float32 (columns of inactive trials are not written)."""
         self._check_perm(perm)
-        sizes = device_step_sizes([t.learning_rate for t in self.trials], self.t, self.steps, self.cfg["total"])
+        sizes = device_step_sizes([t.learning_rate for t in self.trials], self.t, self.steps, self.plan.total)
         with self.torch.cuda.device(self.dev):
             d_perm, d_sizes, d_active = self.torch.from_numpy(perm).to(self.dev), self.torch.from_numpy(sizes).to(self.dev), self._mask(active)
-            if self.w is None:
-                self.hip.check(self.ctx.lib.bn_probe_sweep_epoch(self.handle, self.X.data_ptr(), self.Y.data_ptr(), d_perm.data_ptr(), self.m, self.cfg["batch"],
-                                                                 d_sizes.data_ptr(), d_active.data_ptr(), self.step_loss.data_ptr(), self._stream()))
-            else:
-                self.hip.check(self.ctx.lib.bn_probe_sweep_epoch_weighted(self.handle, self.X.data_ptr(), self.Y.data_ptr(), self.w.data_ptr(), d_perm.data_ptr(),
-                                                                          self.m, self.cfg["batch"], d_sizes.data_ptr(), d_active.data_ptr(),
-                                                                          self.step_loss.data_ptr(), self._stream()))
+            self.hip.check(self.ctx.lib.bn_probe_sweep_epoch_weighted(self.handle, self.X.data_ptr(), self.Y.data_ptr(), self._ptr(self.w), d_perm.data_ptr(),
+                                                                      self.m, self.plan.batch, d_sizes.data_ptr(), d_active.data_ptr(),
+                                                                      self.step_loss.data_ptr(), self._stream()))
             self.t += self.steps
             return self.step_loss.cpu().numpy()   # (synchronises: the uploads outlive the epoch)
 
@@ -750,12 +797,6 @@ class _SweepBackend(_DeviceBackend):
                                                            W.data_ptr(), b.data_ptr(), self._stream()))
         return W.cpu().numpy(), b.cpu().numpy()
 
-    def close(self):
-        if self.handle:
-            self.torch.cuda.synchronize(self.dev)
-            self.ctx.lib.bn_probe_sweep_destroy(self.handle)
-            self.handle = None
-
 
 def fit_probe_sweep(ctx_or_runner, X, Y, X_val=None, Y_val=None, trials=(), *, activation="sigmoid", epochs=50, batch_size=32, patience=10, seed=42,
                     class_names=None, loss="auto", focal_gamma=2.0, sample_weight=None, rows=None) -> SweepResult:
@@ -773,50 +814,33 @@ def fit_probe_sweep(ctx_or_runner, X, Y, X_val=None, Y_val=None, trials=(), *, a
     if len(trials) > _hip.PROBE_SWEEP_MAX_TRIALS:
         raise ValueError(f"{len(trials)} trials: a sweep takes at most {_hip.PROBE_SWEEP_MAX_TRIALS}")
     # shapes, activation, batch and epochs; every trial's own fields were checked when it was made (ProbeTrial.__post_init__)
-    _check_fit_args(X, Y, activation, trials[0].optimizer, batch_size, trials[0].dropout, epochs)
-    loss, focal_gamma = _check_loss(loss, focal_gamma, activation)
-    sample_weight, rows = _check_weights_rows(int(X.shape[0]), sample_weight, rows)
-    n, D, C, T = (int(X.shape[0]) if rows is None else len(rows)), int(X.shape[1]), int(Y.shape[1]), len(trials)   # n: the length of an epoch
-    if not (1 <= D <= _hip.PROBE_MAX_D and 1 <= C <= _hip.PROBE_MAX_C):
-        raise ValueError(f"the device path takes 1 <= D <= {_hip.PROBE_MAX_D} and 1 <= C <= {_hip.PROBE_MAX_C}, got D={D} C={C}")
-    ctx = getattr(ctx_or_runner, "ctx", ctx_or_runner)
-    batch, epochs, patience = min(int(batch_size), n), int(epochs), int(patience)
-    has_val = X_val is not None and len(X_val) > 0
-    W0, b0 = init_head(D, C, seed)
-    cfg = dict(activation=activation, batch=batch, seed=int(seed), total=epochs * math.ceil(n / batch), loss=loss, focal_gamma=focal_gamma)
-    hist = [{"loss": [], "val_loss": [], "step_loss": [], "best_epoch": None, "stopped_epoch": None} for _ in range(T)]
-    best, wait, active = [math.inf] * T, [0] * T, np.ones(T, bool)
-    be = _SweepBackend(ctx, X, Y, X_val if has_val else None, Y_val if has_val else None, W0, b0, cfg, trials, sample_weight, n)
+    plan = _plan_fit(X, Y, X_val, device=True, activation=activation, optimizer=trials[0].optimizer, batch_size=batch_size, dropout=trials[0].dropout,
+                     epochs=epochs, patience=patience, seed=seed, loss=loss, focal_gamma=focal_gamma, sample_weight=sample_weight, rows=rows)
+    T = len(trials)
+    stopping, active = [_EarlyStopping(plan.patience) for _ in range(T)], np.ones(T, bool)
+    be = _SweepBackend(getattr(ctx_or_runner, "ctx", ctx_or_runner), X, Y, X_val, Y_val, plan, trials)
     try:
-        for epoch in range(epochs):
+        for epoch in range(plan.epochs):
             if not active.any():
                 break
             running = np.flatnonzero(active)
-            losses = be.epoch(_epoch_rows(int(seed), epoch, n, rows), active)
+            losses = be.epoch(_epoch_rows(plan.seed, epoch, plan.m, plan.rows), active)
             for t in running:
-                col = np.ascontiguousarray(losses[:, t], np.float64)
-                hist[t]["step_loss"].append(col)
-                hist[t]["loss"].append(float(col.mean()))
-            if not has_val:
+                stopping[t].add_epoch(losses[:, t])
+            if not plan.has_val:
                 continue
             vals = be.val_loss(active)
             improved = np.zeros(T, bool)
-            for t in running:   # _fit_loop's rule, per trial
-                val = float(vals[t])
-                hist[t]["val_loss"].append(val)
-                if val < best[t]:
-                    best[t], wait[t], hist[t]["best_epoch"], improved[t] = val, 0, epoch, True
-                else:
-                    wait[t] += 1
-                    if wait[t] >= patience and epoch > 0:
-                        hist[t]["stopped_epoch"], active[t] = epoch, False
+            for t in running:   # a stopped trial goes inactive
+                improved[t], stop = stopping[t].update(epoch, float(vals[t]))
+                active[t] = not stop
             if improved.any():
                 be.snapshot(improved)
         heads = []
         for t in range(T):
-            W, b = be.get(t, snapshot=hist[t]["best_epoch"] is not None)
-            hist[t]["step_loss"] = np.concatenate(hist[t]["step_loss"])
-            heads.append(ProbeHead(W, b, activation, list(class_names or []), hist[t]))
+            history = stopping[t].finish()
+            W, b = be.get(t, snapshot=history["best_epoch"] is not None)
+            heads.append(ProbeHead(W, b, activation, list(class_names or []), history))
     finally:
         be.close()
     return SweepResult(heads, trials, _best_trial(heads))
@@ -895,23 +919,22 @@ def augmented_embeddings(runner, inputs, plan, out=None, slice_buf=None):
 class _AugmentedDeviceBackend(_DeviceBackend):
     """The device fit over rows that change per epoch: ``epoch`` first builds that epoch's ``X`` / ``Y`` in place, then runs the plain epoch."""
 
-    def __init__(self, runner, inputs, Y, Xv, Yv, W, b, cfg, augment, F, W_in, sample_weight=None, epoch_len=None):
+    def __init__(self, runner, inputs, Y, X_val, Y_val, plan, augment, F, W_in):
         import time
 
         import torch
 
         self.runner, self.inputs, self.aug, self.F, self.W_in, self.time = runner, inputs, augment, F, W_in, time
         self.Y_host = np.ascontiguousarray(Y, np.float32)
-        n, D = int(inputs.shape[0]), int(runner.embedding_info()["dim"])
-        super().__init__(runner.ctx, torch.zeros((n, D), dtype=torch.float32, device=inputs.device), self.Y_host, Xv, Yv, W, b, cfg, sample_weight, epoch_len)
-        self.slice_buf = torch.empty((min(int(runner.max_batch), n), int(inputs.shape[1])), dtype=torch.float32, device=inputs.device)
+        super().__init__(runner.ctx, torch.zeros((plan.n, plan.D), dtype=torch.float32, device=inputs.device), self.Y_host, X_val, Y_val, plan)
+        self.slice_buf = torch.empty((min(int(runner.max_batch), plan.n), int(inputs.shape[1])), dtype=torch.float32, device=inputs.device)
         self.epochs_done, self.augment_seconds = 0, []
 
     def epoch(self, perm):
         from birdnet_stm32.training.augment import augment_plan, mixed_targets
 
         t0 = self.time.perf_counter()
-        plan = augment_plan(self.n, self.F, self.W_in, self.aug, self.cfg["seed"], self.epochs_done)
+        plan = augment_plan(self.n, self.F, self.W_in, self.aug, self.plan.seed, self.epochs_done)
         augmented_embeddings(self.runner, self.inputs, plan, out=self.X, slice_buf=self.slice_buf)
         self.Y.copy_(self.torch.from_numpy(mixed_targets(self.Y_host, plan)))
         self.torch.cuda.current_stream(self.dev).synchronize()
@@ -938,53 +961,35 @@ def fit_probe_augmented(runner, inputs, Y, X_val=None, Y_val=None, *, augment, i
     built on, whatever rows were mixed into it."""
     import torch
 
-    from birdnet_stm32 import _hip
-
     F, W_in = _check_augmented_args(augment, activation, input_shape, inputs.shape[1] if len(inputs.shape) == 2 else None)
     if not hasattr(runner, "predict_device"):
         raise ValueError("fit_probe_augmented needs the model's runner: the backbone runs every epoch")
     if len(inputs.shape) != 2:
         raise ValueError(f"inputs must be [N, F * W], got {tuple(inputs.shape)}")
-    n, D = int(inputs.shape[0]), int(runner.embedding_info()["dim"])
-    _check_fit_args(_Shape(n, D), Y, activation, optimizer, batch_size, dropout, epochs)
-    loss, focal_gamma = _check_loss(loss, focal_gamma, activation)
-    sample_weight, rows = _check_weights_rows(n, sample_weight, rows)
-    m = n if rows is None else len(rows)   # the length of an epoch
-    C = int(Y.shape[1])
-    if not (1 <= D <= _hip.PROBE_MAX_D and 1 <= C <= _hip.PROBE_MAX_C):
-        raise ValueError(f"the device path takes 1 <= D <= {_hip.PROBE_MAX_D} and 1 <= C <= {_hip.PROBE_MAX_C}, got D={D} C={C}")
+    plan = _plan_fit(_Shape(int(inputs.shape[0]), int(runner.embedding_info()["dim"])), Y, X_val, device=True, activation=activation, optimizer=optimizer,
+                     batch_size=batch_size, dropout=dropout, epochs=epochs, learning_rate=learning_rate, weight_decay=weight_decay, clipnorm=clipnorm,
+                     patience=patience, seed=seed, loss=loss, focal_gamma=focal_gamma, sample_weight=sample_weight, rows=rows)
     if int(inputs.shape[1]) != int(runner.input_elems):
         raise ValueError(f"inputs have {int(inputs.shape[1])} elements per row, the model takes {runner.input_elems}")
     if isinstance(inputs, np.ndarray):
         inputs = torch.from_numpy(np.ascontiguousarray(inputs, np.float32)).to(runner.device)
     if isinstance(Y, torch.Tensor):
         Y = Y.cpu().numpy()
-    batch = min(int(batch_size), m)
-    has_val = X_val is not None and len(X_val) > 0
-    W0, b0 = init_head(D, C, seed)
-    cfg = dict(activation=activation, optimizer=optimizer, batch=batch, seed=int(seed), dropout=float(dropout), clipnorm=float(clipnorm),
-               lr=float(learning_rate), weight_decay=float(weight_decay), total=int(epochs) * math.ceil(m / batch), loss=loss, focal_gamma=focal_gamma)
-    be = _AugmentedDeviceBackend(runner, inputs.contiguous(), Y, X_val if has_val else None, Y_val if has_val else None, W0, b0, cfg, augment, F, W_in,
-                                 sample_weight, m)
-    try:
-        history = _fit_loop(be, m, int(epochs), batch, int(seed), int(patience), has_val, rows)
-        W, b = be.get()
-        W, b = W.cpu().numpy(), b.cpu().numpy()
-        history["augment_seconds"] = list(be.augment_seconds)
-    finally:
-        be.close()
-    return ProbeHead(W, b, activation, list(class_names or []), history)
+    be = _AugmentedDeviceBackend(runner, inputs.contiguous(), Y, X_val, Y_val, plan, augment, F, W_in)
+    head = _device_fit(be, plan, class_names)
+    head.history["augment_seconds"] = list(be.augment_seconds)
+    return head
 
 
 class _AugmentedNumpyBackend(_NumpyBackend):
-    def __init__(self, embed, inputs, Y, Xv, Yv, W, b, cfg, dtype, augment, F, W_in, sample_weight=None):
+    def __init__(self, embed, inputs, Y, X_val, Y_val, plan, dtype, augment, F, W_in):
         self.embed, self.inputs, self.Y_host, self.aug, self.F, self.W_in, self.epochs_done = embed, inputs, Y, augment, F, W_in, 0
-        super().__init__(None, None, Xv, Yv, W, b, cfg, dtype, sample_weight)
+        super().__init__(None, None, X_val, Y_val, plan, dtype)
 
     def epoch(self, perm):
         from birdnet_stm32.training.augment import augment_plan, augment_reference, mixed_targets
 
-        plan = augment_plan(self.inputs.shape[0], self.F, self.W_in, self.aug, self.cfg["seed"], self.epochs_done)
+        plan = augment_plan(self.inputs.shape[0], self.F, self.W_in, self.aug, self.plan.seed, self.epochs_done)
         self.X = np.asarray(self.embed(augment_reference(self.inputs, plan))).astype(self.dt)
         self.Y = mixed_targets(self.Y_host, plan).astype(self.dt)
         self.epochs_done += 1
@@ -997,23 +1002,11 @@ def fit_probe_augmented_reference(embed, inputs, Y, X_val=None, Y_val=None, *, a
     """The procedure of ``fit_probe_augmented`` in numpy over a caller-supplied ``embed(inputs [N, F * W] float32) -> X [N, D]``."""
     inputs, Y = np.ascontiguousarray(inputs, np.float32), np.asarray(Y)
     F, W_in = _check_augmented_args(augment, activation, input_shape, inputs.shape[1] if inputs.ndim == 2 else None)
-    n = inputs.shape[0]
     D = int(np.asarray(embed(inputs[:1])).shape[1])
-    _check_fit_args(_Shape(n, D), Y, activation, optimizer, batch_size, dropout, epochs)
-    loss, focal_gamma = _check_loss(loss, focal_gamma, activation)
-    sample_weight, rows = _check_weights_rows(n, sample_weight, rows)
-    m = n if rows is None else len(rows)   # the length of an epoch
-    batch = min(int(batch_size), m)
-    has_val = X_val is not None and len(X_val) > 0
-    W0, b0 = init_head(D, Y.shape[1], seed)
-    cfg = dict(activation=activation, optimizer=optimizer, batch=batch, seed=int(seed), dropout=float(dropout), clipnorm=float(np.float32(clipnorm)),
-               lr=float(learning_rate), weight_decay=float(weight_decay), total=int(epochs) * math.ceil(m / batch), loss=loss, focal_gamma=focal_gamma)
-    be = _AugmentedNumpyBackend(embed, inputs, Y, np.asarray(X_val).astype(dtype) if has_val else None,
-                                np.asarray(Y_val).astype(dtype) if has_val else None, W0, b0, cfg, np.dtype(dtype).type, augment, F, W_in, sample_weight)
-    history = _fit_loop(be, m, int(epochs), batch, int(seed), int(patience), has_val, rows)
-    W, b = be.get()
-    history["W"], history["b"] = W, b
-    return ProbeHead(W, b, activation, list(class_names or []), history)
+    plan = _plan_fit(_Shape(inputs.shape[0], D), Y, X_val, device=False, activation=activation, optimizer=optimizer, batch_size=batch_size, dropout=dropout,
+                     epochs=epochs, learning_rate=learning_rate, weight_decay=weight_decay, clipnorm=clipnorm, patience=patience, seed=seed, loss=loss,
+                     focal_gamma=focal_gamma, sample_weight=sample_weight, rows=rows)
+    return _reference_fit(_AugmentedNumpyBackend(embed, inputs, Y, X_val, Y_val, plan, dtype, augment, F, W_in), plan, class_names)
 
 
 # -- from class folders to a head on disk ---------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 // bn_api.hip — the C ABI of libbirdnet_hip.so (include/birdnet_hip.h): context and model
 // lifetime, packed-blob parsing, workspace allocation and the entry points that split a
 // bn_forward()/bn_infer_audio() call into launch groups for the plan executor (bn_plan_run.hip).
+// The entry points of the classifier head and its training (bn_head_forward, bn_probe_*) are in bn_probe_api.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -69,7 +70,7 @@ using bn::ProfScope;
 bn::Options g_opt_default = options_from_env();   // the process default (bn_set_option); copied into bn::g_opt per API call
 std::mutex g_opt_mu;
 
-namespace {
+namespace bn {
 
 int check_device(bn_ctx* ctx) {
     if (!ctx) return fail(BN_ERR_ARG, "null context");
@@ -98,6 +99,12 @@ int grow_device_buffer(void** p, size_t* have, size_t need, size_t alloc, hipStr
     *have = alloc;
     return BN_OK;
 }
+
+}  // namespace bn
+using bn::check_device;
+using bn::grow_device_buffer;
+
+namespace {
 
 // What every entry point over an [n, D] matrix of embedding rows (bn_search_*, bn_kmeans_*) checks first
 int row_matrix_check(int dtype, int64_t n, int D, int max_D, int zero_point) {
@@ -1055,449 +1062,6 @@ const char* bn_kernel_names(void) {
            "f32_pw_kernel\nf32_pw_ws_kernel\nf32_dwpw_kernel\nf32_dwpw_wave_kernel\nf32_strip_kernel\nf32_front_strip_kernel\nf32_front2_kernel\nf32_pwdw_kernel\nf32_dw_stream_kernel\nf32_front_kernel\nf32_gap_kernel\nf32_gap_dense_kernel\nf32_gap_dense_emb_kernel\nf32_dense_kernel\nf32_segate_kernel\nf32_scale_kernel\nf32_attnpool_kernel\n"
            "i8_quant_kernel\ni8_mel_kernel\ni8_stem_kernel\ni8_dw_kernel\ni8_pw_kernel\ni8_dwpw_kernel\ni8_mel_mfma_kernel\ni8_strip_kernel\ni8_strip_mf_kernel\ni8_front_strip_kernel\ni8_front_kernel\ni8_tail_kernel\ni8_tail_emb_kernel\ni8_tail2_kernel\ni8_tail2_emb_kernel\ni8_mid2_kernel\ni8_mean_kernel\ni8_fc_kernel\ni8_scale_kernel\ni8_maxnorm_kernel\ni8_rawfe_kernel\ni8_pwdw_kernel\ni8_dw_stream_kernel\ni8_stem_stream_kernel\ni8_segate_kernel\ni8_pw_wave_kernel\ni8_pw_lds_kernel\ni8_attnpool_kernel\n"
            "i8_head_kernel\ni8_head_softmax_kernel\nemb_store_kernel\nprobe_fwd_kernel\nprobe_dw_kernel\nprobe_reduce_kernel\nprobe_update_kernel\nprobe_loss_sum_kernel\nprobe_sweep_snapshot_kernel\nste_kernel\nactivity_count_kernel\nsearch_inv_norms_kernel\nsearch_score_kernel\nsearch_merge_kernel\naugment_kernel\nkmeans_assign_kernel\nkmeans_keys_kernel\nkmeans_offsets_kernel\nkmeans_segments_kernel\nkmeans_partial_kernel\nkmeans_fold_kernel\nkmeans_scale_kernel\nbootstrap_table_kernel\nbootstrap_reject_kernel\nbootstrap_prepare_kernel\nbootstrap_resample_kernel";
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------------------------------------------- probe (bn_probe.hip)
-struct bn_probe {
-    bn_ctx* ctx = nullptr;
-    int D = 0, C = 0, act = 0, opt = 0;
-    float lr = 0, wd = 0, clip = 0, drop = 0;
-    int loss = BN_PROBE_LOSS_CE;                    // bn_probe_set_loss
-    float gamma = 0;
-    uint32_t seed = 0;
-    int64_t total = 1, t = 0;                       // steps of the cosine schedule, steps taken
-    float *d_params = nullptr, *d_m = nullptr, *d_v = nullptr;   // [(D + 1) * C] each: W, then the bias as row D
-    float* d_G = nullptr;         size_t G_bytes = 0;       // [batch, C] dLoss/dlogits of one step
-    float* d_partial = nullptr;   size_t partial_bytes = 0; // [row groups][(D + 1) * C]
-    float* d_loss_part = nullptr; size_t loss_bytes = 0;    // one per 16 rows
-    float* d_ss = nullptr;                                   // sums of squares per workgroup of the gradient / reduce kernel
-};
-
-namespace {
-
-int probe_shape_check(int D, int C, int activation) {
-    if (D < 1 || D > BN_PROBE_MAX_D) return fail(BN_ERR_ARG, "embedding width D=%d outside 1..%d", D, BN_PROBE_MAX_D);
-    if (C < 1 || C > BN_PROBE_MAX_C) return fail(BN_ERR_ARG, "class count C=%d outside 1..%d", C, BN_PROBE_MAX_C);
-    if (activation != BN_PROBE_ACT_SIGMOID && activation != BN_PROBE_ACT_SOFTMAX) return fail(BN_ERR_ARG, "unknown activation %d", activation);
-    return BN_OK;
-}
-
-// Most row groups the gradient kernel uses for any batch of up to B rows: enough workgroups for two per CU, at least 16 rows per
-// group, and the partials inside BN_PROBE_WORKSPACE_BYTES.  Monotone in B.
-int64_t probe_group_cap(int B, int D, int C) {
-    const size_t E = (size_t)(D + 1) * C;
-    const int tiles = ((D + 1 + 63) / 64) * ((C + 63) / 64);
-    int64_t g = std::max<int64_t>(1, 512 / tiles);
-    g = std::min<int64_t>(g, std::max<int64_t>(1, (int64_t)(BN_PROBE_WORKSPACE_BYTES / (E * sizeof(float)))));
-    return std::min<int64_t>(g, (B + 15) / 16);
-}
-
-// Row groups of the gradient kernel for a batch of B rows: from the shapes only.  The rows per group are a multiple of 4 (one MFMA
-// k-step), so groups <= probe_group_cap(B) — but NOT monotone in B: a short last batch can have more groups than the full one,
-// which is why the workspace is sized by the cap of the full batch.
-void probe_groups(int B, int D, int C, int* groups, int* rows_per_group) {
-    const int64_t g = probe_group_cap(B, D, C);
-    const int rpg = (int)((((B + g - 1) / g) + 3) & ~(int64_t)3);
-    *rows_per_group = rpg;
-    *groups = (B + rpg - 1) / rpg;
-}
-
-// Norm partials of one head: one per workgroup of the gradient kernel, or of the reduce kernel when the batch is split
-size_t probe_n_ss(int D, int C) {
-    const size_t E = (size_t)(D + 1) * C;
-    return std::max<size_t>((size_t)((D + 1 + 63) / 64) * ((C + 63) / 64), (E + 1023) / 1024);
-}
-
-// bn_probe_set_loss / bn_probe_sweep_set_loss: the checks they share
-int probe_loss_check(int activation, int loss, float focal_gamma) {
-    if (loss != BN_PROBE_LOSS_CE && loss != BN_PROBE_LOSS_FOCAL) return fail(BN_ERR_ARG, "unknown loss %d", loss);
-    if (loss == BN_PROBE_LOSS_FOCAL && activation != BN_PROBE_ACT_SIGMOID) return fail(BN_ERR_ARG, "the focal loss is the sigmoid head's: not with softmax");
-    if (!(focal_gamma >= 0.0f) || !std::isfinite(focal_gamma)) return fail(BN_ERR_ARG, "focal_gamma %g must be finite and >= 0", (double)focal_gamma);
-    return BN_OK;
-}
-
-int probe_grow(float** p, size_t* bytes, size_t floats, hipStream_t s) {
-    return grow_device_buffer((void**)p, bytes, floats * sizeof(float), floats * sizeof(float), s, BN_ERR_NOMEM, "probe");
-}
-
-}  // namespace
-
-extern "C" {
-
-int bn_head_forward(bn_ctx* ctx, const float* d_emb, int64_t n, int D, const float* d_W, const float* d_b, int C, int activation,
-                    float* d_scores, void* stream) {
-    if (int rc = check_device(ctx)) return rc;
-    if (int rc = probe_shape_check(D, C, activation)) return rc;
-    if (n < 0 || n > 0x7fffffffLL) return fail(BN_ERR_ARG, "bad row count %lld", (long long)n);
-    if (n == 0) return BN_OK;
-    if (!d_emb || !d_W || !d_b || !d_scores) return fail(BN_ERR_ARG, "null device pointer");
-    bn::ProbeFwdArgs a{};
-    a.X = d_emb; a.W = d_W; a.b = d_b; a.out = d_scores; a.n = n; a.D = D; a.C = C; a.softmax = activation == BN_PROBE_ACT_SOFTMAX;
-    if (!bn::launch_probe_fwd(a, 2, (hipStream_t)stream)) return fail(BN_ERR_DEVICE, "the head kernel's LDS request was refused");
-    HIP_TRY(hipGetLastError());
-    return BN_OK;
-}
-
-int bn_probe_create(bn_ctx* ctx, int D, int C, int activation, int optimizer, float lr, float weight_decay, float clipnorm, float dropout,
-                    uint32_t seed, int64_t total_steps, const float* d_W, const float* d_b, bn_probe** out, void* stream) {
-    if (!out) return fail(BN_ERR_ARG, "out is null");
-    *out = nullptr;
-    if (int rc = check_device(ctx)) return rc;
-    if (int rc = probe_shape_check(D, C, activation)) return rc;
-    if (optimizer < BN_PROBE_OPT_ADAM || optimizer > BN_PROBE_OPT_SGD) return fail(BN_ERR_ARG, "unknown optimizer %d", optimizer);
-    if (!(lr >= 0.0f) || !(weight_decay >= 0.0f) || !(clipnorm >= 0.0f)) return fail(BN_ERR_ARG, "lr, weight_decay and clipnorm must be >= 0");
-    if (!(dropout >= 0.0f && dropout < 1.0f)) return fail(BN_ERR_ARG, "dropout %g outside [0, 1)", (double)dropout);
-    if (total_steps < 1) return fail(BN_ERR_ARG, "total_steps must be >= 1");
-    if (!d_W || !d_b) return fail(BN_ERR_ARG, "null device pointer");
-    hipStream_t s = (hipStream_t)stream;
-    bn_probe* p = new bn_probe();
-    p->ctx = ctx; p->D = D; p->C = C; p->act = activation; p->opt = optimizer; p->lr = lr; p->wd = weight_decay; p->clip = clipnorm;
-    p->drop = dropout; p->seed = seed; p->total = total_steps;
-    const size_t E = (size_t)(D + 1) * C;
-    const size_t n_ss = probe_n_ss(D, C);
-    if (hipMalloc(&p->d_params, 3 * E * sizeof(float)) != hipSuccess || hipMalloc(&p->d_ss, n_ss * sizeof(float)) != hipSuccess) {
-        (void)hipGetLastError();
-        bn_probe_destroy(p);
-        return fail(BN_ERR_NOMEM, "hipMalloc of the probe's parameters failed");
-    }
-    p->d_m = p->d_params + E;
-    p->d_v = p->d_m + E;
-    hipError_t e = hipMemsetAsync(p->d_m, 0, 2 * E * sizeof(float), s);
-    if (e == hipSuccess) e = hipMemcpyAsync(p->d_params, d_W, (size_t)D * C * sizeof(float), hipMemcpyDeviceToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(p->d_params + (size_t)D * C, d_b, (size_t)C * sizeof(float), hipMemcpyDeviceToDevice, s);
-    if (e != hipSuccess) {
-        bn_probe_destroy(p);
-        return fail(BN_ERR_DEVICE, "copying the initial weights failed: %s", hipGetErrorString(e));
-    }
-    *out = p;
-    return BN_OK;
-}
-
-void bn_probe_destroy(bn_probe* p) {
-    if (!p) return;
-    if (p->ctx) (void)hipSetDevice(p->ctx->device);
-    (void)hipDeviceSynchronize();   // steps still in flight read and write the buffers freed below
-    for (float* q : {p->d_params, p->d_G, p->d_partial, p->d_loss_part, p->d_ss})
-        if (q) (void)hipFree(q);
-    delete p;
-}
-
-int bn_probe_set_loss(bn_probe* p, int loss, float focal_gamma) {
-    if (!p) return fail(BN_ERR_ARG, "null probe");
-    if (int rc = probe_loss_check(p->act, loss, focal_gamma)) return rc;
-    p->loss = loss; p->gamma = focal_gamma;
-    return BN_OK;
-}
-
-int bn_probe_epoch(bn_probe* p, const float* d_X, const float* d_Y, const int32_t* d_perm, int64_t n, int batch, float* d_step_loss,
-                   void* stream) {
-    return bn_probe_epoch_weighted(p, d_X, d_Y, nullptr, d_perm, n, batch, d_step_loss, stream);
-}
-
-int bn_probe_epoch_weighted(bn_probe* p, const float* d_X, const float* d_Y, const float* d_row_weight, const int32_t* d_perm, int64_t n,
-                            int batch, float* d_step_loss, void* stream) {
-    if (!p) return fail(BN_ERR_ARG, "null probe");
-    if (int rc = check_device(p->ctx)) return rc;
-    if (!d_X || !d_Y || !d_perm || !d_step_loss) return fail(BN_ERR_ARG, "null device pointer");
-    if (n < 1 || n > 0x7fffffffLL) return fail(BN_ERR_ARG, "bad row count %lld", (long long)n);
-    if (batch < 1 || batch > n) return fail(BN_ERR_ARG, "batch %d outside 1..%lld", batch, (long long)n);
-    hipStream_t s = (hipStream_t)stream;
-    const int D = p->D, C = p->C, E = (D + 1) * C;
-    int groups, rpg;
-    if (int rc = probe_grow(&p->d_G, &p->G_bytes, (size_t)batch * C, s)) return rc;
-    if (int rc = probe_grow(&p->d_partial, &p->partial_bytes, (size_t)probe_group_cap(batch, D, C) * E, s)) return rc;
-    if (int rc = probe_grow(&p->d_loss_part, &p->loss_bytes, (size_t)(batch + 15) / 16, s)) return rc;
-    const uint32_t thresh = p->drop > 0.0f ? (uint32_t)std::ceil((double)p->drop * 16777216.0) : 0u;
-    const float drop_scale = (float)(1.0 / (1.0 - (double)p->drop));
-    const int64_t steps = (n + batch - 1) / batch;
-    for (int64_t st = 0; st < steps; ++st, ++p->t) {
-        const int B = (int)std::min<int64_t>(batch, n - st * batch);
-        const int32_t* idx = d_perm + st * batch;
-        const double frac = (double)std::min<int64_t>(p->t, p->total) / (double)p->total;
-        const double lr_t = (double)p->lr * 0.5 * (1.0 + std::cos(M_PI * frac));
-        const double t1 = (double)(p->t + 1);
-        const double alpha = lr_t * std::sqrt(1.0 - std::pow(0.999, t1)) / (1.0 - std::pow(0.9, t1));
-        bn::ProbeFwdArgs f{};
-        f.X = d_X; f.Y = d_Y; f.idx = idx; f.W = p->d_params; f.b = p->d_params + (size_t)D * C; f.out = p->d_G; f.loss_part = p->d_loss_part;
-        f.n = B; f.D = D; f.C = C; f.softmax = p->act == BN_PROBE_ACT_SOFTMAX; f.drop_thresh = thresh; f.drop_scale = drop_scale;
-        f.seed = p->seed; f.step = (uint32_t)p->t;
-        f.g_scale = p->act == BN_PROBE_ACT_SOFTMAX ? (float)(1.0 / B) : (float)(1.0 / ((double)B * C));
-        f.row_weight = d_row_weight; f.loss_kind = p->loss; f.focal_gamma = p->gamma;
-        if (!bn::launch_probe_fwd(f, 0, s)) return fail(BN_ERR_DEVICE, "the probe forward kernel's LDS request was refused");
-        probe_groups(B, D, C, &groups, &rpg);
-        if ((size_t)groups * E * sizeof(float) > p->partial_bytes) return fail(BN_ERR_UNSUPPORTED, "%d row groups exceed the gradient workspace", groups);
-        bn::ProbeDwArgs g{};
-        g.X = d_X; g.idx = idx; g.G = p->d_G; g.partial = p->d_partial; g.ss_part = p->d_ss; g.B = B; g.D = D; g.C = C; g.E = E;
-        g.rows_per_group = rpg; g.drop_thresh = thresh; g.drop_scale = drop_scale; g.seed = p->seed; g.step = (uint32_t)p->t;
-        bn::launch_probe_dw(g, groups, s);
-        int n_ss = ((D + 1 + 63) / 64) * ((C + 63) / 64);
-        if (groups > 1) {
-            bn::launch_probe_reduce(p->d_partial, E, groups, p->d_ss, s);
-            n_ss = (E + 1023) / 1024;
-        }
-        bn::ProbeUpdateArgs u{};
-        u.params = p->d_params; u.m = p->d_m; u.v = p->d_v; u.grad = p->d_partial; u.ss_part = p->d_ss; u.n_ss = n_ss;
-        u.loss_part = p->d_loss_part; u.n_loss = (B + 15) / 16; u.loss_scale = f.g_scale; u.step_loss = d_step_loss + st;
-        u.E = E; u.optimizer = p->opt; u.lr = (float)lr_t; u.alpha = (float)alpha; u.weight_decay = p->wd; u.clip = p->clip;
-        bn::launch_probe_update(u, s);
-    }
-    HIP_TRY(hipGetLastError());
-    return BN_OK;
-}
-
-int bn_probe_loss(bn_probe* p, const float* d_X, const float* d_Y, int64_t n, float* d_out, void* stream) {
-    if (!p) return fail(BN_ERR_ARG, "null probe");
-    if (int rc = check_device(p->ctx)) return rc;
-    if (!d_X || !d_Y || !d_out) return fail(BN_ERR_ARG, "null device pointer");
-    if (n < 1 || n > 0x7fffffffLL) return fail(BN_ERR_ARG, "bad row count %lld", (long long)n);
-    hipStream_t s = (hipStream_t)stream;
-    const size_t parts = (size_t)(n + 15) / 16;
-    if (int rc = probe_grow(&p->d_loss_part, &p->loss_bytes, parts, s)) return rc;
-    bn::ProbeFwdArgs f{};
-    f.X = d_X; f.Y = d_Y; f.W = p->d_params; f.b = p->d_params + (size_t)p->D * p->C; f.loss_part = p->d_loss_part;
-    f.n = n; f.D = p->D; f.C = p->C; f.softmax = p->act == BN_PROBE_ACT_SOFTMAX; f.loss_kind = p->loss; f.focal_gamma = p->gamma;
-    if (!bn::launch_probe_fwd(f, 1, s)) return fail(BN_ERR_DEVICE, "the probe forward kernel's LDS request was refused");
-    const float scale = p->act == BN_PROBE_ACT_SOFTMAX ? (float)(1.0 / (double)n) : (float)(1.0 / ((double)n * p->C));
-    bn::launch_probe_loss_sum(p->d_loss_part, (long)parts, scale, d_out, s);
-    HIP_TRY(hipGetLastError());
-    return BN_OK;
-}
-
-int bn_probe_get(bn_probe* p, float* d_W, float* d_b, void* stream) {
-    if (!p) return fail(BN_ERR_ARG, "null probe");
-    if (int rc = check_device(p->ctx)) return rc;
-    if (!d_W || !d_b) return fail(BN_ERR_ARG, "null device pointer");
-    const size_t nw = (size_t)p->D * p->C;
-    HIP_TRY(hipMemcpyAsync(d_W, p->d_params, nw * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    HIP_TRY(hipMemcpyAsync(d_b, p->d_params + nw, (size_t)p->C * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return BN_OK;
-}
-
-int bn_probe_set(bn_probe* p, const float* d_W, const float* d_b, void* stream) {
-    if (!p) return fail(BN_ERR_ARG, "null probe");
-    if (int rc = check_device(p->ctx)) return rc;
-    if (!d_W || !d_b) return fail(BN_ERR_ARG, "null device pointer");
-    const size_t nw = (size_t)p->D * p->C;
-    HIP_TRY(hipMemcpyAsync(p->d_params, d_W, nw * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    HIP_TRY(hipMemcpyAsync(p->d_params + nw, d_b, (size_t)p->C * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return BN_OK;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------------------------------- probe sweep (bn_probe_sweep.hip)
-struct bn_probe_sweep {
-    bn_ctx* ctx = nullptr;
-    int D = 0, C = 0, act = 0, T = 0;
-    int loss = BN_PROBE_LOSS_CE;                            // bn_probe_sweep_set_loss: shared by the trials
-    float gamma = 0;
-    uint32_t seed = 0;
-    int64_t total = 1, t = 0;                               // steps of the schedule (for the record), steps taken
-    bn::ProbeSweepTrial* d_trials = nullptr;                // [T]
-    float* d_state = nullptr;                               // [T][4][(D + 1) * C]: parameters, m, v, snapshot
-    float* d_G = nullptr;         size_t G_bytes = 0;       // [T][batch * C]
-    float* d_partial = nullptr;   size_t partial_bytes = 0; // [T][row groups][(D + 1) * C]
-    float* d_loss_part = nullptr; size_t loss_bytes = 0;    // [T][one per 16 rows]
-    float* d_ss = nullptr;                                  // [T][n_ss]
-    int n_ss = 0;
-};
-
-namespace {
-
-// Bytes one trial of a sweep holds: its state, at batch > 0 also G, the row-group partials and the loss partials of a training step,
-// at loss_rows > 0 the loss partials of bn_probe_sweep_loss over that many rows (the same buffer as the training step's)
-size_t sweep_trial_bytes(int D, int C, int batch, int64_t loss_rows) {
-    const size_t E = (size_t)(D + 1) * C;
-    size_t floats = 4 * E + probe_n_ss(D, C);
-    if (batch > 0) floats += (size_t)batch * C + (size_t)probe_group_cap(batch, D, C) * E;
-    floats += std::max<size_t>((size_t)(batch + 15) / 16, (size_t)(loss_rows + 15) / 16);
-    return floats * sizeof(float);
-}
-
-int sweep_cap_check(int D, int C, int batch, int64_t loss_rows, int T) {
-    const size_t per = sweep_trial_bytes(D, C, batch, loss_rows);
-    if (per * (size_t)T <= BN_PROBE_SWEEP_BYTES) return BN_OK;
-    return fail(BN_ERR_UNSUPPORTED, "a sweep of %d trials of D=%d C=%d%s needs %zu bytes, over the cap of %llu: the largest T that fits is %d", T, D, C,
-                batch > 0 ? " at this batch" : loss_rows > 0 ? " over these rows" : "", per * (size_t)T, (unsigned long long)BN_PROBE_SWEEP_BYTES,
-                (int)(BN_PROBE_SWEEP_BYTES / per));
-}
-
-bn::ProbeSweepArgs sweep_args(const bn_probe_sweep* p, const uint8_t* d_active, size_t G_stride, size_t partial_stride, int loss_stride) {
-    bn::ProbeSweepArgs w{};
-    w.trials = p->d_trials; w.active = d_active; w.state = p->d_state; w.G = p->d_G; w.partial = p->d_partial; w.ss_part = p->d_ss;
-    w.loss_part = p->d_loss_part; w.G_stride = G_stride; w.partial_stride = partial_stride; w.ss_stride = p->n_ss; w.loss_stride = loss_stride;
-    w.T = p->T; w.E = (p->D + 1) * p->C;
-    return w;
-}
-
-}  // namespace
-
-extern "C" {
-
-int bn_probe_sweep_create(bn_ctx* ctx, int D, int C, int activation, int T, const bn_probe_trial* trials, uint32_t seed, int64_t total_steps,
-                          const float* d_W, const float* d_b, bn_probe_sweep** out, void* stream) {
-    if (!out) return fail(BN_ERR_ARG, "out is null");
-    *out = nullptr;
-    if (int rc = check_device(ctx)) return rc;
-    if (int rc = probe_shape_check(D, C, activation)) return rc;
-    if (T < 1 || T > BN_PROBE_SWEEP_MAX_TRIALS) return fail(BN_ERR_ARG, "trial count T=%d outside 1..%d", T, BN_PROBE_SWEEP_MAX_TRIALS);
-    if (!trials) return fail(BN_ERR_ARG, "null trial table");
-    if (total_steps < 1) return fail(BN_ERR_ARG, "total_steps must be >= 1");
-    if (!d_W || !d_b) return fail(BN_ERR_ARG, "null device pointer");
-    std::vector<bn::ProbeSweepTrial> rows((size_t)T);
-    for (int t = 0; t < T; ++t) {
-        const bn_probe_trial& h = trials[t];
-        if (h.optimizer < BN_PROBE_OPT_ADAM || h.optimizer > BN_PROBE_OPT_SGD) return fail(BN_ERR_ARG, "trial %d: unknown optimizer %d", t, h.optimizer);
-        if (!(h.lr >= 0.0f) || !(h.weight_decay >= 0.0f) || !(h.clipnorm >= 0.0f))
-            return fail(BN_ERR_ARG, "trial %d: lr, weight_decay and clipnorm must be >= 0", t);
-        if (!(h.dropout >= 0.0f && h.dropout < 1.0f)) return fail(BN_ERR_ARG, "trial %d: dropout %g outside [0, 1)", t, (double)h.dropout);
-        if (!(h.label_smoothing >= 0.0f && h.label_smoothing < 1.0f))
-            return fail(BN_ERR_ARG, "trial %d: label_smoothing %g outside [0, 1)", t, (double)h.label_smoothing);
-        bn::ProbeSweepTrial& r = rows[(size_t)t];
-        r.optimizer = h.optimizer; r.weight_decay = h.weight_decay; r.clip = h.clipnorm;
-        r.drop_thresh = h.dropout > 0.0f ? (uint32_t)std::ceil((double)h.dropout * 16777216.0) : 0u;   // as bn_probe_epoch
-        r.drop_scale = (float)(1.0 / (1.0 - (double)h.dropout));
-        const float eps = h.label_smoothing;
-        r.smooth = eps > 0.0f;
-        r.smooth_keep = 1.0f - eps;
-        r.smooth_add = activation == BN_PROBE_ACT_SOFTMAX ? eps / (float)C : 0.5f * eps;
-    }
-    if (int rc = sweep_cap_check(D, C, 0, 0, T)) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    bn_probe_sweep* p = new bn_probe_sweep();
-    p->ctx = ctx; p->D = D; p->C = C; p->act = activation; p->T = T; p->seed = seed; p->total = total_steps;
-    const size_t E = (size_t)(D + 1) * C;
-    p->n_ss = (int)probe_n_ss(D, C);
-    if (hipMalloc(&p->d_state, (size_t)T * 4 * E * sizeof(float)) != hipSuccess || hipMalloc(&p->d_ss, (size_t)T * p->n_ss * sizeof(float)) != hipSuccess ||
-        hipMalloc(&p->d_trials, (size_t)T * sizeof(bn::ProbeSweepTrial)) != hipSuccess) {
-        (void)hipGetLastError();
-        bn_probe_sweep_destroy(p);
-        return fail(BN_ERR_NOMEM, "hipMalloc of the sweep's parameters failed");
-    }
-    hipError_t e = hipMemsetAsync(p->d_state, 0, (size_t)T * 4 * E * sizeof(float), s);
-    for (int t = 0; t < T && e == hipSuccess; ++t)
-        for (int slot : {0, 3}) {   // the parameters and the snapshot
-            float* dst = p->d_state + ((size_t)t * 4 + slot) * E;
-            if (e == hipSuccess) e = hipMemcpyAsync(dst, d_W, (size_t)D * C * sizeof(float), hipMemcpyDeviceToDevice, s);
-            if (e == hipSuccess) e = hipMemcpyAsync(dst + (size_t)D * C, d_b, (size_t)C * sizeof(float), hipMemcpyDeviceToDevice, s);
-        }
-    if (e == hipSuccess) e = hipMemcpyAsync(p->d_trials, rows.data(), (size_t)T * sizeof(bn::ProbeSweepTrial), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);   // `rows` is pageable host memory that ends with this call
-    if (e != hipSuccess) {
-        bn_probe_sweep_destroy(p);
-        return fail(BN_ERR_DEVICE, "copying the initial weights failed: %s", hipGetErrorString(e));
-    }
-    *out = p;
-    return BN_OK;
-}
-
-void bn_probe_sweep_destroy(bn_probe_sweep* p) {
-    if (!p) return;
-    if (p->ctx) (void)hipSetDevice(p->ctx->device);
-    (void)hipDeviceSynchronize();   // steps still in flight read and write the buffers freed below
-    for (void* q : {(void*)p->d_trials, (void*)p->d_state, (void*)p->d_G, (void*)p->d_partial, (void*)p->d_loss_part, (void*)p->d_ss})
-        if (q) (void)hipFree(q);
-    delete p;
-}
-
-int bn_probe_sweep_set_loss(bn_probe_sweep* p, int loss, float focal_gamma) {
-    if (!p) return fail(BN_ERR_ARG, "null sweep");
-    if (int rc = probe_loss_check(p->act, loss, focal_gamma)) return rc;
-    p->loss = loss; p->gamma = focal_gamma;
-    return BN_OK;
-}
-
-int bn_probe_sweep_epoch(bn_probe_sweep* p, const float* d_X, const float* d_Y, const int32_t* d_perm, int64_t n, int batch,
-                         const float* d_step_sizes, const uint8_t* d_active, float* d_step_loss, void* stream) {
-    return bn_probe_sweep_epoch_weighted(p, d_X, d_Y, nullptr, d_perm, n, batch, d_step_sizes, d_active, d_step_loss, stream);
-}
-
-int bn_probe_sweep_epoch_weighted(bn_probe_sweep* p, const float* d_X, const float* d_Y, const float* d_row_weight, const int32_t* d_perm,
-                                  int64_t n, int batch, const float* d_step_sizes, const uint8_t* d_active, float* d_step_loss, void* stream) {
-    if (!p) return fail(BN_ERR_ARG, "null sweep");
-    if (int rc = check_device(p->ctx)) return rc;
-    if (!d_X || !d_Y || !d_perm || !d_step_sizes || !d_step_loss) return fail(BN_ERR_ARG, "null device pointer");
-    if (n < 1 || n > 0x7fffffffLL) return fail(BN_ERR_ARG, "bad row count %lld", (long long)n);
-    if (batch < 1 || batch > n) return fail(BN_ERR_ARG, "batch %d outside 1..%lld", batch, (long long)n);
-    const int D = p->D, C = p->C, E = (D + 1) * C, T = p->T;
-    if (int rc = sweep_cap_check(D, C, batch, 0, T)) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    const size_t G_stride = (size_t)batch * C, partial_stride = (size_t)probe_group_cap(batch, D, C) * E;
-    const int loss_stride = (batch + 15) / 16;
-    if (int rc = probe_grow(&p->d_G, &p->G_bytes, (size_t)T * G_stride, s)) return rc;
-    if (int rc = probe_grow(&p->d_partial, &p->partial_bytes, (size_t)T * partial_stride, s)) return rc;
-    if (int rc = probe_grow(&p->d_loss_part, &p->loss_bytes, (size_t)T * loss_stride, s)) return rc;
-    const bn::ProbeSweepArgs w = sweep_args(p, d_active, G_stride, partial_stride, loss_stride);
-    const int64_t steps = (n + batch - 1) / batch;
-    int groups, rpg;
-    for (int64_t st = 0; st < steps; ++st, ++p->t) {
-        const int B = (int)std::min<int64_t>(batch, n - st * batch);
-        const int32_t* idx = d_perm + st * batch;
-        bn::ProbeFwdArgs f{};
-        f.X = d_X; f.Y = d_Y; f.idx = idx; f.n = B; f.D = D; f.C = C; f.softmax = p->act == BN_PROBE_ACT_SOFTMAX;
-        f.seed = p->seed; f.step = (uint32_t)p->t;
-        f.g_scale = p->act == BN_PROBE_ACT_SOFTMAX ? (float)(1.0 / B) : (float)(1.0 / ((double)B * C));
-        f.row_weight = d_row_weight; f.loss_kind = p->loss; f.focal_gamma = p->gamma;
-        if (!bn::launch_probe_sweep_fwd(f, w, 0, s)) return fail(BN_ERR_DEVICE, "the probe forward kernel's LDS request was refused");
-        probe_groups(B, D, C, &groups, &rpg);   // from (B, D, C) alone, as in a single fit
-        if ((size_t)groups * E > partial_stride) return fail(BN_ERR_UNSUPPORTED, "%d row groups exceed the gradient workspace", groups);
-        bn::ProbeDwArgs g{};
-        g.X = d_X; g.idx = idx; g.B = B; g.D = D; g.C = C; g.E = E; g.rows_per_group = rpg; g.seed = p->seed; g.step = (uint32_t)p->t;
-        bn::launch_probe_sweep_dw(g, w, groups, s);
-        int n_ss = ((D + 1 + 63) / 64) * ((C + 63) / 64);
-        if (groups > 1) {
-            bn::launch_probe_sweep_reduce(w, groups, s);
-            n_ss = (E + 1023) / 1024;
-        }
-        bn::ProbeUpdateArgs u{};
-        u.n_ss = n_ss; u.n_loss = (B + 15) / 16; u.loss_scale = f.g_scale; u.step_loss = d_step_loss + st * T; u.E = E;
-        bn::launch_probe_sweep_update(u, w, d_step_sizes + st * T * 2, s);
-    }
-    HIP_TRY(hipGetLastError());
-    return BN_OK;
-}
-
-int bn_probe_sweep_loss(bn_probe_sweep* p, const float* d_X, const float* d_Y, int64_t n, const uint8_t* d_active, float* d_out, void* stream) {
-    if (!p) return fail(BN_ERR_ARG, "null sweep");
-    if (int rc = check_device(p->ctx)) return rc;
-    if (!d_X || !d_Y || !d_out) return fail(BN_ERR_ARG, "null device pointer");
-    if (n < 1 || n > 0x7fffffffLL) return fail(BN_ERR_ARG, "bad row count %lld", (long long)n);
-    if (int rc = sweep_cap_check(p->D, p->C, 0, n, p->T)) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    const size_t parts = (size_t)(n + 15) / 16;
-    if (int rc = probe_grow(&p->d_loss_part, &p->loss_bytes, (size_t)p->T * parts, s)) return rc;
-    const bn::ProbeSweepArgs w = sweep_args(p, d_active, 0, 0, (int)parts);
-    bn::ProbeFwdArgs f{};
-    f.X = d_X; f.Y = d_Y; f.n = n; f.D = p->D; f.C = p->C; f.softmax = p->act == BN_PROBE_ACT_SOFTMAX; f.loss_kind = p->loss; f.focal_gamma = p->gamma;
-    if (!bn::launch_probe_sweep_fwd(f, w, 1, s)) return fail(BN_ERR_DEVICE, "the probe forward kernel's LDS request was refused");
-    const float scale = p->act == BN_PROBE_ACT_SOFTMAX ? (float)(1.0 / (double)n) : (float)(1.0 / ((double)n * p->C));
-    bn::launch_probe_sweep_loss_sum(w, (long)parts, scale, d_out, s);
-    HIP_TRY(hipGetLastError());
-    return BN_OK;
-}
-
-int bn_probe_sweep_snapshot(bn_probe_sweep* p, const uint8_t* d_mask, void* stream) {
-    if (!p) return fail(BN_ERR_ARG, "null sweep");
-    if (int rc = check_device(p->ctx)) return rc;
-    if (!d_mask) return fail(BN_ERR_ARG, "null device pointer");
-    bn::launch_probe_sweep_snapshot(sweep_args(p, nullptr, 0, 0, 0), d_mask, (hipStream_t)stream);
-    HIP_TRY(hipGetLastError());
-    return BN_OK;
-}
-
-int bn_probe_sweep_get(bn_probe_sweep* p, int trial, int which, float* d_W, float* d_b, void* stream) {
-    if (!p) return fail(BN_ERR_ARG, "null sweep");
-    if (int rc = check_device(p->ctx)) return rc;
-    if (trial < 0 || trial >= p->T) return fail(BN_ERR_ARG, "trial %d outside 0..%d", trial, p->T - 1);
-    if (which != BN_PROBE_SWEEP_CURRENT && which != BN_PROBE_SWEEP_SNAPSHOT) return fail(BN_ERR_ARG, "unknown slot %d", which);
-    if (!d_W || !d_b) return fail(BN_ERR_ARG, "null device pointer");
-    const size_t nw = (size_t)p->D * p->C, E = nw + p->C;
-    const float* src = p->d_state + ((size_t)trial * 4 + (which == BN_PROBE_SWEEP_SNAPSHOT ? 3 : 0)) * E;
-    HIP_TRY(hipMemcpyAsync(d_W, src, nw * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    HIP_TRY(hipMemcpyAsync(d_b, src + nw, (size_t)p->C * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return BN_OK;
 }
 
 }  // extern "C"

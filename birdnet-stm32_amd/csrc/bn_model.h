@@ -1,5 +1,6 @@
-// bn_model.h — the context and model objects behind the C ABI, shared by bn_api.hip (lifetime, entry points) and bn_plan_run.hip
-// (load-time preparation of a plan and its executor).  Internal: nothing here is part of include/birdnet_hip.h.
+// bn_model.h — the context and model objects behind the C ABI, shared by bn_api.hip (lifetime, entry points), bn_plan_run.hip
+// (load-time preparation of a plan and its executor) and bn_probe_api.hip (the probe's entry points).  Internal: nothing here is part of
+// include/birdnet_hip.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -15,6 +16,8 @@
 namespace bn {
 
 int fail(int code, const char* fmt, ...);  // records the message bn_last_error() returns, passes `code` through (bn_api.hip)
+int check_device(bn_ctx* ctx);             // what an entry point does first: the context's device and option switches (bn_api.hip)
+int grow_device_buffer(void** p, size_t* have, size_t need, size_t alloc, hipStream_t s, int code, const char* what);   // (bn_api.hip)
 
 constexpr int kMaxGridBatch = 32768;  // chunks per launch group (gridDim.y/z limit is 65535)
 

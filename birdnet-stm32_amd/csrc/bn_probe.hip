@@ -18,56 +18,27 @@
 
 #include "bn_probe_step.h"
 
+// The launchers are bn_probe_step.h's, instantiated here.  The compiler emits a kernel where the file first names it, so preload stands
+// between the update and the loss sum: the kernels keep their order in the code object.
 namespace bn {
 
-template <int NT, int MODE, int EXT>
-static bool launch_fwd_one(const ProbeFwdArgs& a, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
-    if (lds > 64 * 1024 && !ensure_dynamic_lds((const void*)&probe_fwd_kernel<NT, MODE, EXT, false>, lds)) return false;
-    hipLaunchKernelGGL((probe_fwd_kernel<NT, MODE, EXT, false>), grid, block, lds, s, a, ProbeNoSweep{});
-    return true;
-}
+bool launch_probe_fwd(const ProbeFwdArgs& a, int mode, hipStream_t s) { return probe_launch_fwd<false>(a, ProbeNoSweep{}, mode, s); }
 
-// EXT = 1 only when the call asks for row weights (mode 0) or the focal loss (modes 0 and 1): every other call runs the kernel without them
-template <int NT>
-static bool launch_fwd_nt(const ProbeFwdArgs& a, int mode, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
-    const bool ext = probe_fwd_ext(a, mode);
-    if (mode == 0) return ext ? launch_fwd_one<NT, 0, 1>(a, grid, block, lds, s) : launch_fwd_one<NT, 0, 0>(a, grid, block, lds, s);
-    if (mode == 1) return ext ? launch_fwd_one<NT, 1, 1>(a, grid, block, lds, s) : launch_fwd_one<NT, 1, 0>(a, grid, block, lds, s);
-    return launch_fwd_one<NT, 2, 0>(a, grid, block, lds, s);
-}
-
-bool launch_probe_fwd(const ProbeFwdArgs& a, int mode, hipStream_t s) {
-    const int ntiles = (a.C + 15) / 16;
-    const int nw = ntiles < kFwdWaves ? ntiles : kFwdWaves;
-    const int per_wave = (ntiles + nw - 1) / nw;
-    const dim3 grid((unsigned)((a.n + kRows - 1) / kRows)), block(64 * nw);
-    const size_t lds = (size_t)kRows * (((a.D + 3) & ~3) + kLdsPad) * sizeof(float);
-    if (per_wave <= 1) return launch_fwd_nt<1>(a, mode, grid, block, lds, s);
-    if (per_wave <= 2) return launch_fwd_nt<2>(a, mode, grid, block, lds, s);
-    if (per_wave <= 4) return launch_fwd_nt<4>(a, mode, grid, block, lds, s);
-    return launch_fwd_nt<8>(a, mode, grid, block, lds, s);   // C > 2048: two passes over the columns
-}
-
-void launch_probe_dw(const ProbeDwArgs& a, int row_groups, hipStream_t s) {
-    const dim3 grid((unsigned)((a.C + 63) / 64), (unsigned)((a.D + 1 + 63) / 64), (unsigned)row_groups);
-    hipLaunchKernelGGL(probe_dw_kernel<false>, grid, dim3(256), 0, s, a, ProbeNoSweep{}, 0);
-}
+void launch_probe_dw(const ProbeDwArgs& a, int row_groups, hipStream_t s) { probe_launch_dw<false>(a, ProbeNoSweep{}, row_groups, s); }
 
 void launch_probe_reduce(float* partial, int E, int groups, float* ss_part, hipStream_t s) {
-    hipLaunchKernelGGL(probe_reduce_kernel<false>, dim3((unsigned)((E + 1023) / 1024)), dim3(256), 0, s, partial, E, groups, ss_part, ProbeNoSweep{});
+    probe_launch_reduce<false>(partial, E, groups, ss_part, ProbeNoSweep{}, s);
 }
 
-void launch_probe_update(const ProbeUpdateArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(probe_update_kernel<false>, dim3((unsigned)((a.E + 255) / 256)), dim3(256), 0, s, a, ProbeNoSweep{}, nullptr);
-}
-
-void launch_probe_loss_sum(const float* part, long n, float scale, float* out, hipStream_t s) {
-    hipLaunchKernelGGL(probe_loss_sum_kernel<false>, dim3(1), dim3(256), 0, s, part, n, scale, out, ProbeNoSweep{});
-}
+void launch_probe_update(const ProbeUpdateArgs& a, hipStream_t s) { probe_launch_update<false>(a, ProbeNoSweep{}, nullptr, s); }
 
 void preload_probe() {
     hipFuncAttributes at;
     (void)hipFuncGetAttributes(&at, reinterpret_cast<const void*>(&probe_update_kernel<false>));
+}
+
+void launch_probe_loss_sum(const float* part, long n, float scale, float* out, hipStream_t s) {
+    probe_launch_loss_sum<false>(part, n, scale, out, ProbeNoSweep{}, s);
 }
 
 }  // namespace bn

@@ -1,0 +1,445 @@
+// bn_probe_api.hip — the C ABI of a classifier head on frozen embeddings and of its training (host code only):
+// bn_head_forward, bn_probe_* (one head; kernels in bn_probe.hip) and bn_probe_sweep_* (T heads in lock-step; bn_probe_sweep.hip).
+//
+// A single fit and a sweep are one procedure: their handles share ProbeHandle, and the checks, the workspace growth and the step loop
+// are written once (probe_epoch<SWEEP>, probe_loss<SWEEP>).  They differ in where the step sizes come from (computed here, or the
+// caller's table), in the strides of the workspaces (a sweep's hold T heads) and in which launcher runs.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <initializer_list>
+#include <type_traits>
+#include <vector>
+
+#include "bn_model.h"
+
+using bn::check_device;
+using bn::fail;
+using bn::grow_device_buffer;
+
+namespace bn {
+
+struct ProbeHandle {
+    bn_ctx* ctx = nullptr;
+    int D = 0, C = 0, act = 0, T = 1;                       // T: heads trained at once: 1, or the trials of a sweep
+    int loss = BN_PROBE_LOSS_CE;                            // bn_probe_set_loss / bn_probe_sweep_set_loss (shared by a sweep's trials)
+    float gamma = 0;
+    uint32_t seed = 0;
+    int64_t total = 1, t = 0;                               // steps of the cosine schedule (a sweep: for the record), steps taken
+    // one step's workspaces of one head; a sweep holds T of each, one behind the other
+    float* d_G = nullptr;         size_t G_bytes = 0;       // [batch, C] dLoss/dlogits
+    float* d_partial = nullptr;   size_t partial_bytes = 0; // [row groups][(D + 1) * C]
+    float* d_loss_part = nullptr; size_t loss_bytes = 0;    // one per 16 rows
+    float* d_ss = nullptr;                                  // [probe_n_ss] sums of squares per workgroup of the gradient / reduce kernel
+};
+
+}  // namespace bn
+
+struct bn_probe : bn::ProbeHandle {
+    int opt = 0;
+    float lr = 0, wd = 0, clip = 0, drop = 0;
+    float *d_params = nullptr, *d_m = nullptr, *d_v = nullptr;   // [(D + 1) * C] each: W, then the bias as row D
+};
+
+struct bn_probe_sweep : bn::ProbeHandle {
+    int n_ss = 0;
+    bn::ProbeSweepTrial* d_trials = nullptr;                // [T]
+    float* d_state = nullptr;                               // [T][4][(D + 1) * C]: parameters, m, v, snapshot
+};
+
+namespace {
+
+template <bool SWEEP>
+using ProbeOf = std::conditional_t<SWEEP, bn_probe_sweep, bn_probe>;
+
+int probe_shape_check(int D, int C, int activation) {
+    if (D < 1 || D > BN_PROBE_MAX_D) return fail(BN_ERR_ARG, "embedding width D=%d outside 1..%d", D, BN_PROBE_MAX_D);
+    if (C < 1 || C > BN_PROBE_MAX_C) return fail(BN_ERR_ARG, "class count C=%d outside 1..%d", C, BN_PROBE_MAX_C);
+    if (activation != BN_PROBE_ACT_SIGMOID && activation != BN_PROBE_ACT_SOFTMAX) return fail(BN_ERR_ARG, "unknown activation %d", activation);
+    return BN_OK;
+}
+
+// The hyperparameters of bn_probe_create (trial < 0) or of row `trial` of a sweep's table, whose refusals begin "trial %d: "
+int probe_hyper_check(int trial, int optimizer, float lr, float weight_decay, float clipnorm, float dropout) {
+    char pre[24] = "";
+    if (trial >= 0) snprintf(pre, sizeof pre, "trial %d: ", trial);
+    if (optimizer < BN_PROBE_OPT_ADAM || optimizer > BN_PROBE_OPT_SGD) return fail(BN_ERR_ARG, "%sunknown optimizer %d", pre, optimizer);
+    if (!(lr >= 0.0f) || !(weight_decay >= 0.0f) || !(clipnorm >= 0.0f)) return fail(BN_ERR_ARG, "%slr, weight_decay and clipnorm must be >= 0", pre);
+    if (!(dropout >= 0.0f && dropout < 1.0f)) return fail(BN_ERR_ARG, "%sdropout %g outside [0, 1)", pre, (double)dropout);
+    return BN_OK;
+}
+
+// What a call on a handle checks first, in this order; `what`: "probe" or "sweep", `pointers`: every device pointer it needs is there
+int probe_call_check(const bn::ProbeHandle* p, const char* what, bool pointers) {
+    if (!p) return fail(BN_ERR_ARG, "null %s", what);
+    if (int rc = check_device(p->ctx)) return rc;
+    if (!pointers) return fail(BN_ERR_ARG, "null device pointer");
+    return BN_OK;
+}
+
+int probe_rows_check(int64_t n) {
+    if (n < 1 || n > 0x7fffffffLL) return fail(BN_ERR_ARG, "bad row count %lld", (long long)n);
+    return BN_OK;
+}
+
+int probe_set_loss(bn::ProbeHandle* p, const char* what, int loss, float focal_gamma) {
+    if (!p) return fail(BN_ERR_ARG, "null %s", what);
+    if (loss != BN_PROBE_LOSS_CE && loss != BN_PROBE_LOSS_FOCAL) return fail(BN_ERR_ARG, "unknown loss %d", loss);
+    if (loss == BN_PROBE_LOSS_FOCAL && p->act != BN_PROBE_ACT_SIGMOID) return fail(BN_ERR_ARG, "the focal loss is the sigmoid head's: not with softmax");
+    if (!(focal_gamma >= 0.0f) || !std::isfinite(focal_gamma)) return fail(BN_ERR_ARG, "focal_gamma %g must be finite and >= 0", (double)focal_gamma);
+    p->loss = loss; p->gamma = focal_gamma;
+    return BN_OK;
+}
+
+// Most row groups the gradient kernel uses for any batch of up to B rows: enough workgroups for two per CU, at least 16 rows per
+// group, and the partials inside BN_PROBE_WORKSPACE_BYTES.  Monotone in B.
+int64_t probe_group_cap(int B, int D, int C) {
+    const size_t E = (size_t)(D + 1) * C;
+    const int tiles = ((D + 1 + 63) / 64) * ((C + 63) / 64);
+    int64_t g = std::max<int64_t>(1, 512 / tiles);
+    g = std::min<int64_t>(g, std::max<int64_t>(1, (int64_t)(BN_PROBE_WORKSPACE_BYTES / (E * sizeof(float)))));
+    return std::min<int64_t>(g, (B + 15) / 16);
+}
+
+// Row groups of the gradient kernel for a batch of B rows: from the shapes only.  The rows per group are a multiple of 4 (one MFMA
+// k-step), so groups <= probe_group_cap(B) — but NOT monotone in B: a short last batch can have more groups than the full one,
+// which is why the workspace is sized by the cap of the full batch.
+void probe_groups(int B, int D, int C, int* groups, int* rows_per_group) {
+    const int64_t g = probe_group_cap(B, D, C);
+    const int rpg = (int)((((B + g - 1) / g) + 3) & ~(int64_t)3);
+    *rows_per_group = rpg;
+    *groups = (B + rpg - 1) / rpg;
+}
+
+// Norm partials of one head: one per workgroup of the gradient kernel, or of the reduce kernel when the batch is split into row groups
+int probe_n_ss_tiles(int D, int C) { return ((D + 1 + 63) / 64) * ((C + 63) / 64); }
+int probe_n_ss_reduce(int E) { return (E + 1023) / 1024; }
+int probe_n_ss(int D, int C) { return std::max(probe_n_ss_tiles(D, C), probe_n_ss_reduce((D + 1) * C)); }
+
+// Dropout at rate p: an element is kept iff its 24-bit draw is >= thresh (0: no dropout), and then scaled
+void probe_dropout(float p, uint32_t* thresh, float* scale) {
+    *thresh = p > 0.0f ? (uint32_t)std::ceil((double)p * 16777216.0) : 0u;
+    *scale = (float)(1.0 / (1.0 - (double)p));
+}
+
+// The scale of the loss's mean over n rows: over rows x classes (sigmoid) or over rows (softmax)
+float probe_mean_scale(bool softmax, int64_t n, int C) { return softmax ? (float)(1.0 / (double)n) : (float)(1.0 / ((double)n * C)); }
+
+// W [D, C] and b [C] from one head to another.  A (D + 1) x C parameter block is the head (block, block + D * C): its row D is the bias
+hipError_t probe_copy_head(float* dst_W, float* dst_b, const float* src_W, const float* src_b, int D, int C, hipStream_t s) {
+    const hipError_t e = hipMemcpyAsync(dst_W, src_W, (size_t)D * C * sizeof(float), hipMemcpyDeviceToDevice, s);
+    return e != hipSuccess ? e : hipMemcpyAsync(dst_b, src_b, (size_t)C * sizeof(float), hipMemcpyDeviceToDevice, s);
+}
+
+int probe_grow(float** p, size_t* bytes, size_t floats, hipStream_t s) {
+    return grow_device_buffer((void**)p, bytes, floats * sizeof(float), floats * sizeof(float), s, BN_ERR_NOMEM, "probe");
+}
+
+// the handle's own buffers (`own`) and the shared workspaces; the caller deletes the handle
+void probe_free(bn::ProbeHandle* p, std::initializer_list<void*> own) {
+    if (p->ctx) (void)hipSetDevice(p->ctx->device);
+    (void)hipDeviceSynchronize();   // steps still in flight read and write the buffers freed below
+    for (void* q : own)
+        if (q) (void)hipFree(q);
+    for (float* q : {p->d_G, p->d_partial, p->d_loss_part, p->d_ss})
+        if (q) (void)hipFree(q);
+}
+
+// T times the bytes one trial of a sweep holds stay within BN_PROBE_SWEEP_BYTES.  A trial holds its state, at batch > 0 also G, the row-group
+// partials and the loss partials of a training step, at loss_rows > 0 the loss partials of bn_probe_sweep_loss (the same buffer)
+int sweep_cap_check(int D, int C, int batch, int64_t loss_rows, int T) {
+    const size_t E = (size_t)(D + 1) * C;
+    size_t floats = 4 * E + (size_t)probe_n_ss(D, C);
+    if (batch > 0) floats += (size_t)batch * C + (size_t)probe_group_cap(batch, D, C) * E;
+    floats += std::max<size_t>((size_t)(batch + 15) / 16, (size_t)(loss_rows + 15) / 16);
+    const size_t per = floats * sizeof(float);
+    if (per * (size_t)T <= BN_PROBE_SWEEP_BYTES) return BN_OK;
+    return fail(BN_ERR_UNSUPPORTED, "a sweep of %d trials of D=%d C=%d%s needs %zu bytes, over the cap of %llu: the largest T that fits is %d", T, D, C,
+                batch > 0 ? " at this batch" : loss_rows > 0 ? " over these rows" : "", per * (size_t)T, (unsigned long long)BN_PROBE_SWEEP_BYTES,
+                (int)(BN_PROBE_SWEEP_BYTES / per));
+}
+
+bn::ProbeSweepArgs sweep_args(const bn_probe_sweep* p, const uint8_t* d_active, size_t G_stride, size_t partial_stride, int loss_stride) {
+    bn::ProbeSweepArgs w{};
+    w.trials = p->d_trials; w.active = d_active; w.state = p->d_state; w.G = p->d_G; w.partial = p->d_partial; w.ss_part = p->d_ss;
+    w.loss_part = p->d_loss_part; w.G_stride = G_stride; w.partial_stride = partial_stride; w.ss_stride = p->n_ss; w.loss_stride = loss_stride;
+    w.T = p->T; w.E = (p->D + 1) * p->C;
+    return w;
+}
+
+// One epoch of a single fit (SWEEP = false: d_step_sizes and d_active are null) or of every active trial of a sweep.  A step is three
+// launches, four when the batch is split into row groups; at small batches it is launch-bound, so nothing in the loop allocates or
+// goes through a pointer to a function: SWEEP is a constant of the instantiation.
+template <bool SWEEP>
+int probe_epoch(ProbeOf<SWEEP>* p, const float* d_X, const float* d_Y, const float* d_row_weight, const int32_t* d_perm, int64_t n, int batch,
+                const float* d_step_sizes, const uint8_t* d_active, float* d_step_loss, void* stream) {
+    if (int rc = probe_call_check(p, SWEEP ? "sweep" : "probe", d_X && d_Y && d_perm && d_step_loss && (!SWEEP || d_step_sizes))) return rc;
+    if (int rc = probe_rows_check(n)) return rc;
+    if (batch < 1 || batch > n) return fail(BN_ERR_ARG, "batch %d outside 1..%lld", batch, (long long)n);
+    const int D = p->D, C = p->C, E = (D + 1) * C, T = p->T;
+    if constexpr (SWEEP)
+        if (int rc = sweep_cap_check(D, C, batch, 0, T)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    // one head's share of the three workspaces; a sweep's trials lie at these strides
+    const size_t G_stride = (size_t)batch * C, partial_stride = (size_t)probe_group_cap(batch, D, C) * E;
+    const int loss_stride = (batch + 15) / 16;
+    if (int rc = probe_grow(&p->d_G, &p->G_bytes, (size_t)T * G_stride, s)) return rc;
+    if (int rc = probe_grow(&p->d_partial, &p->partial_bytes, (size_t)T * partial_stride, s)) return rc;
+    if (int rc = probe_grow(&p->d_loss_part, &p->loss_bytes, (size_t)T * loss_stride, s)) return rc;
+    const bool softmax = p->act == BN_PROBE_ACT_SOFTMAX;
+    const int ss_tiles = probe_n_ss_tiles(D, C), ss_reduce = probe_n_ss_reduce(E);
+    bn::ProbeFwdArgs f{}; bn::ProbeDwArgs g{}; bn::ProbeUpdateArgs u{};   // first what stays the same from step to step
+    f.X = d_X; f.Y = d_Y; f.D = D; f.C = C; f.softmax = softmax; f.seed = p->seed;
+    f.row_weight = d_row_weight; f.loss_kind = p->loss; f.focal_gamma = p->gamma;
+    g.X = d_X; g.D = D; g.C = C; g.E = E; g.seed = p->seed; u.E = E;
+    [[maybe_unused]] bn::ProbeSweepArgs w{};
+    if constexpr (SWEEP) {
+        w = sweep_args(p, d_active, G_stride, partial_stride, loss_stride);
+    } else {
+        f.W = p->d_params; f.b = p->d_params + (size_t)D * C; f.out = p->d_G; f.loss_part = p->d_loss_part;
+        probe_dropout(p->drop, &f.drop_thresh, &f.drop_scale);
+        g.G = p->d_G; g.partial = p->d_partial; g.ss_part = p->d_ss; g.drop_thresh = f.drop_thresh; g.drop_scale = f.drop_scale;
+        u.params = p->d_params; u.m = p->d_m; u.v = p->d_v; u.grad = p->d_partial; u.ss_part = p->d_ss; u.loss_part = p->d_loss_part;
+        u.optimizer = p->opt; u.weight_decay = p->wd; u.clip = p->clip;
+    }
+    const int64_t steps = (n + batch - 1) / batch;
+    for (int64_t st = 0; st < steps; ++st, ++p->t) {
+        const int B = (int)std::min<int64_t>(batch, n - st * batch);
+        f.idx = g.idx = d_perm + st * batch;
+        f.n = g.B = B;
+        f.step = g.step = (uint32_t)p->t;
+        f.g_scale = u.loss_scale = probe_mean_scale(softmax, B, C);
+        bool fits;
+        if constexpr (SWEEP) fits = bn::launch_probe_sweep_fwd(f, w, 0, s); else fits = bn::launch_probe_fwd(f, 0, s);
+        if (!fits) return fail(BN_ERR_DEVICE, "the probe forward kernel's LDS request was refused");
+        int groups;
+        probe_groups(B, D, C, &groups, &g.rows_per_group);   // from (B, D, C) alone: a sweep's trials split as a single fit does
+        if (SWEEP ? (size_t)groups * E > partial_stride : (size_t)groups * E * sizeof(float) > p->partial_bytes)
+            return fail(BN_ERR_UNSUPPORTED, "%d row groups exceed the gradient workspace", groups);
+        if constexpr (SWEEP) bn::launch_probe_sweep_dw(g, w, groups, s); else bn::launch_probe_dw(g, groups, s);
+        u.n_ss = ss_tiles;
+        if (groups > 1) {
+            if constexpr (SWEEP) bn::launch_probe_sweep_reduce(w, groups, s); else bn::launch_probe_reduce(p->d_partial, E, groups, p->d_ss, s);
+            u.n_ss = ss_reduce;
+        }
+        u.n_loss = (B + 15) / 16; u.step_loss = d_step_loss + st * T;
+        if constexpr (SWEEP) {
+            bn::launch_probe_sweep_update(u, w, d_step_sizes + st * T * 2, s);
+        } else {   // cosine decay to zero; Adam's bias correction folded into its step size (a sweep's caller uploads the same: device_step_sizes)
+            const double frac = (double)std::min<int64_t>(p->t, p->total) / (double)p->total;
+            const double lr_t = (double)p->lr * 0.5 * (1.0 + std::cos(M_PI * frac)), t1 = (double)(p->t + 1);
+            u.lr = (float)lr_t; u.alpha = (float)(lr_t * std::sqrt(1.0 - std::pow(0.999, t1)) / (1.0 - std::pow(0.9, t1)));
+            bn::launch_probe_update(u, s);
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    return BN_OK;
+}
+
+// The loss over n rows as they are (no dropout, no smoothing, no weights): out[0], or out[t] per active trial of a sweep
+template <bool SWEEP>
+int probe_loss(ProbeOf<SWEEP>* p, const float* d_X, const float* d_Y, int64_t n, const uint8_t* d_active, float* d_out, void* stream) {
+    if (int rc = probe_call_check(p, SWEEP ? "sweep" : "probe", d_X && d_Y && d_out)) return rc;
+    if (int rc = probe_rows_check(n)) return rc;
+    if constexpr (SWEEP)
+        if (int rc = sweep_cap_check(p->D, p->C, 0, n, p->T)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t parts = (size_t)(n + 15) / 16;
+    if (int rc = probe_grow(&p->d_loss_part, &p->loss_bytes, (size_t)p->T * parts, s)) return rc;
+    const bool softmax = p->act == BN_PROBE_ACT_SOFTMAX;
+    const float scale = probe_mean_scale(softmax, n, p->C);
+    bn::ProbeFwdArgs f{};
+    f.X = d_X; f.Y = d_Y; f.n = n; f.D = p->D; f.C = p->C; f.softmax = softmax; f.loss_kind = p->loss; f.focal_gamma = p->gamma;
+    [[maybe_unused]] bn::ProbeSweepArgs w{};
+    if constexpr (SWEEP) {
+        w = sweep_args(p, d_active, 0, 0, (int)parts);
+    } else {
+        f.W = p->d_params; f.b = p->d_params + (size_t)p->D * p->C; f.loss_part = p->d_loss_part;
+    }
+    bool fits;
+    if constexpr (SWEEP) fits = bn::launch_probe_sweep_fwd(f, w, 1, s); else fits = bn::launch_probe_fwd(f, 1, s);
+    if (!fits) return fail(BN_ERR_DEVICE, "the probe forward kernel's LDS request was refused");
+    if constexpr (SWEEP) bn::launch_probe_sweep_loss_sum(w, (long)parts, scale, d_out, s); else bn::launch_probe_loss_sum(p->d_loss_part, (long)parts, scale, d_out, s);
+    HIP_TRY(hipGetLastError());
+    return BN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bn_head_forward(bn_ctx* ctx, const float* d_emb, int64_t n, int D, const float* d_W, const float* d_b, int C, int activation,
+                    float* d_scores, void* stream) {
+    if (int rc = check_device(ctx)) return rc;
+    if (int rc = probe_shape_check(D, C, activation)) return rc;
+    if (n < 0 || n > 0x7fffffffLL) return fail(BN_ERR_ARG, "bad row count %lld", (long long)n);
+    if (n == 0) return BN_OK;
+    if (!d_emb || !d_W || !d_b || !d_scores) return fail(BN_ERR_ARG, "null device pointer");
+    bn::ProbeFwdArgs a{};
+    a.X = d_emb; a.W = d_W; a.b = d_b; a.out = d_scores; a.n = n; a.D = D; a.C = C; a.softmax = activation == BN_PROBE_ACT_SOFTMAX;
+    if (!bn::launch_probe_fwd(a, 2, (hipStream_t)stream)) return fail(BN_ERR_DEVICE, "the head kernel's LDS request was refused");
+    HIP_TRY(hipGetLastError());
+    return BN_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------ one head (bn_probe.hip)
+int bn_probe_create(bn_ctx* ctx, int D, int C, int activation, int optimizer, float lr, float weight_decay, float clipnorm, float dropout,
+                    uint32_t seed, int64_t total_steps, const float* d_W, const float* d_b, bn_probe** out, void* stream) {
+    if (!out) return fail(BN_ERR_ARG, "out is null");
+    *out = nullptr;
+    if (int rc = check_device(ctx)) return rc;
+    if (int rc = probe_shape_check(D, C, activation)) return rc;
+    if (int rc = probe_hyper_check(-1, optimizer, lr, weight_decay, clipnorm, dropout)) return rc;
+    if (total_steps < 1) return fail(BN_ERR_ARG, "total_steps must be >= 1");
+    if (!d_W || !d_b) return fail(BN_ERR_ARG, "null device pointer");
+    hipStream_t s = (hipStream_t)stream;
+    bn_probe* p = new bn_probe();
+    p->ctx = ctx; p->D = D; p->C = C; p->act = activation; p->opt = optimizer; p->lr = lr; p->wd = weight_decay; p->clip = clipnorm;
+    p->drop = dropout; p->seed = seed; p->total = total_steps;
+    const size_t E = (size_t)(D + 1) * C;
+    if (hipMalloc(&p->d_params, 3 * E * sizeof(float)) != hipSuccess || hipMalloc(&p->d_ss, (size_t)probe_n_ss(D, C) * sizeof(float)) != hipSuccess) {
+        (void)hipGetLastError();
+        bn_probe_destroy(p);
+        return fail(BN_ERR_NOMEM, "hipMalloc of the probe's parameters failed");
+    }
+    p->d_m = p->d_params + E; p->d_v = p->d_m + E;
+    hipError_t e = hipMemsetAsync(p->d_m, 0, 2 * E * sizeof(float), s);
+    if (e == hipSuccess) e = probe_copy_head(p->d_params, p->d_params + (size_t)D * C, d_W, d_b, D, C, s);
+    if (e != hipSuccess) {
+        bn_probe_destroy(p);
+        return fail(BN_ERR_DEVICE, "copying the initial weights failed: %s", hipGetErrorString(e));
+    }
+    *out = p;
+    return BN_OK;
+}
+
+void bn_probe_destroy(bn_probe* p) {
+    if (!p) return;
+    probe_free(p, {p->d_params});
+    delete p;
+}
+
+int bn_probe_set_loss(bn_probe* p, int loss, float focal_gamma) { return probe_set_loss(p, "probe", loss, focal_gamma); }
+
+int bn_probe_epoch(bn_probe* p, const float* d_X, const float* d_Y, const int32_t* d_perm, int64_t n, int batch, float* d_step_loss,
+                   void* stream) {
+    return probe_epoch<false>(p, d_X, d_Y, nullptr, d_perm, n, batch, nullptr, nullptr, d_step_loss, stream);
+}
+
+int bn_probe_epoch_weighted(bn_probe* p, const float* d_X, const float* d_Y, const float* d_row_weight, const int32_t* d_perm, int64_t n,
+                            int batch, float* d_step_loss, void* stream) {
+    return probe_epoch<false>(p, d_X, d_Y, d_row_weight, d_perm, n, batch, nullptr, nullptr, d_step_loss, stream);
+}
+
+int bn_probe_loss(bn_probe* p, const float* d_X, const float* d_Y, int64_t n, float* d_out, void* stream) {
+    return probe_loss<false>(p, d_X, d_Y, n, nullptr, d_out, stream);
+}
+
+int bn_probe_get(bn_probe* p, float* d_W, float* d_b, void* stream) {
+    if (int rc = probe_call_check(p, "probe", d_W && d_b)) return rc;
+    HIP_TRY(probe_copy_head(d_W, d_b, p->d_params, p->d_params + (size_t)p->D * p->C, p->D, p->C, (hipStream_t)stream));
+    return BN_OK;
+}
+
+int bn_probe_set(bn_probe* p, const float* d_W, const float* d_b, void* stream) {
+    if (int rc = probe_call_check(p, "probe", d_W && d_b)) return rc;
+    HIP_TRY(probe_copy_head(p->d_params, p->d_params + (size_t)p->D * p->C, d_W, d_b, p->D, p->C, (hipStream_t)stream));
+    return BN_OK;
+}
+
+// ------------------------------------------------------------------------------------------- T heads in lock-step (bn_probe_sweep.hip)
+int bn_probe_sweep_create(bn_ctx* ctx, int D, int C, int activation, int T, const bn_probe_trial* trials, uint32_t seed, int64_t total_steps,
+                          const float* d_W, const float* d_b, bn_probe_sweep** out, void* stream) {
+    if (!out) return fail(BN_ERR_ARG, "out is null");
+    *out = nullptr;
+    if (int rc = check_device(ctx)) return rc;
+    if (int rc = probe_shape_check(D, C, activation)) return rc;
+    if (T < 1 || T > BN_PROBE_SWEEP_MAX_TRIALS) return fail(BN_ERR_ARG, "trial count T=%d outside 1..%d", T, BN_PROBE_SWEEP_MAX_TRIALS);
+    if (!trials) return fail(BN_ERR_ARG, "null trial table");
+    if (total_steps < 1) return fail(BN_ERR_ARG, "total_steps must be >= 1");
+    if (!d_W || !d_b) return fail(BN_ERR_ARG, "null device pointer");
+    std::vector<bn::ProbeSweepTrial> rows((size_t)T);
+    for (int t = 0; t < T; ++t) {
+        const bn_probe_trial& h = trials[t];
+        if (int rc = probe_hyper_check(t, h.optimizer, h.lr, h.weight_decay, h.clipnorm, h.dropout)) return rc;
+        if (!(h.label_smoothing >= 0.0f && h.label_smoothing < 1.0f))
+            return fail(BN_ERR_ARG, "trial %d: label_smoothing %g outside [0, 1)", t, (double)h.label_smoothing);
+        bn::ProbeSweepTrial& r = rows[(size_t)t];
+        r.optimizer = h.optimizer; r.weight_decay = h.weight_decay; r.clip = h.clipnorm;
+        probe_dropout(h.dropout, &r.drop_thresh, &r.drop_scale);
+        const float eps = h.label_smoothing;
+        r.smooth = eps > 0.0f;
+        r.smooth_keep = 1.0f - eps;
+        r.smooth_add = activation == BN_PROBE_ACT_SOFTMAX ? eps / (float)C : 0.5f * eps;
+    }
+    if (int rc = sweep_cap_check(D, C, 0, 0, T)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    bn_probe_sweep* p = new bn_probe_sweep();
+    p->ctx = ctx; p->D = D; p->C = C; p->act = activation; p->T = T; p->seed = seed; p->total = total_steps;
+    const size_t E = (size_t)(D + 1) * C;
+    p->n_ss = probe_n_ss(D, C);
+    if (hipMalloc(&p->d_state, (size_t)T * 4 * E * sizeof(float)) != hipSuccess || hipMalloc(&p->d_ss, (size_t)T * p->n_ss * sizeof(float)) != hipSuccess ||
+        hipMalloc(&p->d_trials, (size_t)T * sizeof(bn::ProbeSweepTrial)) != hipSuccess) {
+        (void)hipGetLastError();
+        bn_probe_sweep_destroy(p);
+        return fail(BN_ERR_NOMEM, "hipMalloc of the sweep's parameters failed");
+    }
+    hipError_t e = hipMemsetAsync(p->d_state, 0, (size_t)T * 4 * E * sizeof(float), s);
+    for (int t = 0; t < T; ++t)
+        for (int slot : {0, 3}) {   // the parameters and the snapshot
+            float* dst = p->d_state + ((size_t)t * 4 + slot) * E;
+            if (e == hipSuccess) e = probe_copy_head(dst, dst + (size_t)D * C, d_W, d_b, D, C, s);
+        }
+    if (e == hipSuccess) e = hipMemcpyAsync(p->d_trials, rows.data(), (size_t)T * sizeof(bn::ProbeSweepTrial), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);   // `rows` is pageable host memory that ends with this call
+    if (e != hipSuccess) {
+        bn_probe_sweep_destroy(p);
+        return fail(BN_ERR_DEVICE, "copying the initial weights failed: %s", hipGetErrorString(e));
+    }
+    *out = p;
+    return BN_OK;
+}
+
+void bn_probe_sweep_destroy(bn_probe_sweep* p) {
+    if (!p) return;
+    probe_free(p, {p->d_trials, p->d_state});
+    delete p;
+}
+
+int bn_probe_sweep_set_loss(bn_probe_sweep* p, int loss, float focal_gamma) { return probe_set_loss(p, "sweep", loss, focal_gamma); }
+
+int bn_probe_sweep_epoch(bn_probe_sweep* p, const float* d_X, const float* d_Y, const int32_t* d_perm, int64_t n, int batch,
+                         const float* d_step_sizes, const uint8_t* d_active, float* d_step_loss, void* stream) {
+    return probe_epoch<true>(p, d_X, d_Y, nullptr, d_perm, n, batch, d_step_sizes, d_active, d_step_loss, stream);
+}
+
+int bn_probe_sweep_epoch_weighted(bn_probe_sweep* p, const float* d_X, const float* d_Y, const float* d_row_weight, const int32_t* d_perm,
+                                  int64_t n, int batch, const float* d_step_sizes, const uint8_t* d_active, float* d_step_loss, void* stream) {
+    return probe_epoch<true>(p, d_X, d_Y, d_row_weight, d_perm, n, batch, d_step_sizes, d_active, d_step_loss, stream);
+}
+
+int bn_probe_sweep_loss(bn_probe_sweep* p, const float* d_X, const float* d_Y, int64_t n, const uint8_t* d_active, float* d_out, void* stream) {
+    return probe_loss<true>(p, d_X, d_Y, n, d_active, d_out, stream);
+}
+
+int bn_probe_sweep_snapshot(bn_probe_sweep* p, const uint8_t* d_mask, void* stream) {
+    if (int rc = probe_call_check(p, "sweep", d_mask)) return rc;
+    bn::launch_probe_sweep_snapshot(sweep_args(p, nullptr, 0, 0, 0), d_mask, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return BN_OK;
+}
+
+int bn_probe_sweep_get(bn_probe_sweep* p, int trial, int which, float* d_W, float* d_b, void* stream) {
+    if (int rc = probe_call_check(p, "sweep", true)) return rc;
+    if (trial < 0 || trial >= p->T) return fail(BN_ERR_ARG, "trial %d outside 0..%d", trial, p->T - 1);
+    if (which != BN_PROBE_SWEEP_CURRENT && which != BN_PROBE_SWEEP_SNAPSHOT) return fail(BN_ERR_ARG, "unknown slot %d", which);
+    if (!d_W || !d_b) return fail(BN_ERR_ARG, "null device pointer");
+    const size_t E = (size_t)(p->D + 1) * p->C;
+    const float* src = p->d_state + ((size_t)trial * 4 + (which == BN_PROBE_SWEEP_SNAPSHOT ? 3 : 0)) * E;
+    HIP_TRY(probe_copy_head(d_W, d_b, src, src + (size_t)p->D * p->C, p->D, p->C, (hipStream_t)stream));
+    return BN_OK;
+}
+
+}  // extern "C"

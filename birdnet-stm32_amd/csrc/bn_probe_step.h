@@ -490,4 +490,71 @@ __global__ __launch_bounds__(256) void probe_loss_sum_kernel(const float* __rest
     if (threadIdx.x == 0) *out = v * scale;
 }
 
+// ----------------------------------------------------------------------------------------------------------------------- launchers
+// Host code, written once like the kernels: bn_probe.hip calls them with SWEEP = false and ProbeNoSweep{}, bn_probe_sweep.hip with
+// SWEEP = true and the sweep's arguments, whose trials are one more grid axis.  A file holds the kernels its calls instantiate.
+template <bool SWEEP>
+inline unsigned probe_trials(const ProbeSweepOf<SWEEP>& w) {
+    if constexpr (SWEEP) return (unsigned)w.T;
+    else return 1u;
+}
+
+template <int NT, int MODE, int EXT, bool SWEEP>
+bool probe_launch_fwd_one(const ProbeFwdArgs& a, const ProbeSweepOf<SWEEP>& w, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
+    if (lds > 64 * 1024 && !ensure_dynamic_lds((const void*)&probe_fwd_kernel<NT, MODE, EXT, SWEEP>, lds)) return false;
+    hipLaunchKernelGGL((probe_fwd_kernel<NT, MODE, EXT, SWEEP>), grid, block, lds, s, a, w);
+    return true;
+}
+
+// EXT = 1 only when the call asks for row weights (mode 0) or the focal loss (modes 0 and 1): every other call runs the kernel without
+// them.  Mode 2 (scores: bn_head_forward) is a single head's: a sweep has modes 0 and 1 only.
+template <int NT, bool SWEEP>
+bool probe_launch_fwd_nt(const ProbeFwdArgs& a, const ProbeSweepOf<SWEEP>& w, int mode, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
+    const bool ext = probe_fwd_ext(a, mode);
+    if (mode == 0)
+        return ext ? probe_launch_fwd_one<NT, 0, 1, SWEEP>(a, w, grid, block, lds, s) : probe_launch_fwd_one<NT, 0, 0, SWEEP>(a, w, grid, block, lds, s);
+    if (SWEEP || mode == 1)
+        return ext ? probe_launch_fwd_one<NT, 1, 1, SWEEP>(a, w, grid, block, lds, s) : probe_launch_fwd_one<NT, 1, 0, SWEEP>(a, w, grid, block, lds, s);
+    if constexpr (!SWEEP) return probe_launch_fwd_one<NT, 2, 0, SWEEP>(a, w, grid, block, lds, s);   // (last: the order of the kernels in the code object)
+    else return false;   // (not reached)
+}
+
+// false: the runtime refused the LDS request
+template <bool SWEEP>
+bool probe_launch_fwd(const ProbeFwdArgs& a, const ProbeSweepOf<SWEEP>& w, int mode, hipStream_t s) {
+    const int ntiles = (a.C + 15) / 16;
+    const int nw = ntiles < kFwdWaves ? ntiles : kFwdWaves;
+    const int per_wave = (ntiles + nw - 1) / nw;
+    const dim3 grid((unsigned)((a.n + kRows - 1) / kRows), probe_trials<SWEEP>(w)), block(64 * nw);
+    const size_t lds = (size_t)kRows * (((a.D + 3) & ~3) + kLdsPad) * sizeof(float);
+    if (per_wave <= 1) return probe_launch_fwd_nt<1, SWEEP>(a, w, mode, grid, block, lds, s);
+    if (per_wave <= 2) return probe_launch_fwd_nt<2, SWEEP>(a, w, mode, grid, block, lds, s);
+    if (per_wave <= 4) return probe_launch_fwd_nt<4, SWEEP>(a, w, mode, grid, block, lds, s);
+    return probe_launch_fwd_nt<8, SWEEP>(a, w, mode, grid, block, lds, s);   // C > 2048: two passes over the columns
+}
+
+// grid z: trial * row_groups + group
+template <bool SWEEP>
+void probe_launch_dw(const ProbeDwArgs& a, const ProbeSweepOf<SWEEP>& w, int row_groups, hipStream_t s) {
+    const dim3 grid((unsigned)((a.C + 63) / 64), (unsigned)((a.D + 1 + 63) / 64), probe_trials<SWEEP>(w) * (unsigned)row_groups);
+    hipLaunchKernelGGL(probe_dw_kernel<SWEEP>, grid, dim3(256), 0, s, a, w, SWEEP ? row_groups : 0);
+}
+
+template <bool SWEEP>
+void probe_launch_reduce(float* partial, int E, int groups, float* ss_part, const ProbeSweepOf<SWEEP>& w, hipStream_t s) {
+    hipLaunchKernelGGL(probe_reduce_kernel<SWEEP>, dim3((unsigned)((E + 1023) / 1024), probe_trials<SWEEP>(w)), dim3(256), 0, s, partial, E, groups, ss_part, w);
+}
+
+// a sweep: `a.lr` / `a.alpha` of trial t are step_sizes[2 t], [2 t + 1]; its loss goes to a.step_loss[t]
+template <bool SWEEP>
+void probe_launch_update(const ProbeUpdateArgs& a, const ProbeSweepOf<SWEEP>& w, const float* step_sizes, hipStream_t s) {
+    hipLaunchKernelGGL(probe_update_kernel<SWEEP>, dim3((unsigned)((a.E + 255) / 256), probe_trials<SWEEP>(w)), dim3(256), 0, s, a, w, step_sizes);
+}
+
+// one workgroup per head
+template <bool SWEEP>
+void probe_launch_loss_sum(const float* part, long n, float scale, float* out, const ProbeSweepOf<SWEEP>& w, hipStream_t s) {
+    hipLaunchKernelGGL(probe_loss_sum_kernel<SWEEP>, dim3(probe_trials<SWEEP>(w)), dim3(256), 0, s, part, n, scale, out, w);
+}
+
 }  // namespace bn

@@ -17,51 +17,31 @@
 
 #include "bn_probe_step.h"
 
+// The launchers are bn_probe_step.h's, instantiated here.  The compiler emits a kernel where the file first names it, so preload stands
+// between the update and the loss sum: the kernels keep their order in the code object.
 namespace bn {
 
-template <int NT, int MODE, int EXT>
-static bool launch_sweep_fwd_one(const ProbeFwdArgs& a, const ProbeSweepArgs& w, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
-    if (lds > 64 * 1024 && !ensure_dynamic_lds((const void*)&probe_fwd_kernel<NT, MODE, EXT, true>, lds)) return false;
-    hipLaunchKernelGGL((probe_fwd_kernel<NT, MODE, EXT, true>), grid, block, lds, s, a, w);
-    return true;
-}
+// mode 0 (training) or 1 (loss)
+bool launch_probe_sweep_fwd(const ProbeFwdArgs& a, const ProbeSweepArgs& w, int mode, hipStream_t s) { return probe_launch_fwd<true>(a, w, mode, s); }
 
-template <int NT>
-static bool launch_sweep_fwd_nt(const ProbeFwdArgs& a, const ProbeSweepArgs& w, int mode, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
-    const bool ext = probe_fwd_ext(a, mode);   // as launch_fwd_nt (bn_probe.hip)
-    if (mode == 0) return ext ? launch_sweep_fwd_one<NT, 0, 1>(a, w, grid, block, lds, s) : launch_sweep_fwd_one<NT, 0, 0>(a, w, grid, block, lds, s);
-    return ext ? launch_sweep_fwd_one<NT, 1, 1>(a, w, grid, block, lds, s) : launch_sweep_fwd_one<NT, 1, 0>(a, w, grid, block, lds, s);
-}
-
-// The launch shape of launch_probe_fwd (bn_probe.hip) with the trials along y; mode 0 (training) or 1 (loss)
-bool launch_probe_sweep_fwd(const ProbeFwdArgs& a, const ProbeSweepArgs& w, int mode, hipStream_t s) {
-    const int ntiles = (a.C + 15) / 16;
-    const int nw = ntiles < kFwdWaves ? ntiles : kFwdWaves;
-    const int per_wave = (ntiles + nw - 1) / nw;
-    const dim3 grid((unsigned)((a.n + kRows - 1) / kRows), (unsigned)w.T), block(64 * nw);
-    const size_t lds = (size_t)kRows * (((a.D + 3) & ~3) + kLdsPad) * sizeof(float);
-    if (per_wave <= 1) return launch_sweep_fwd_nt<1>(a, w, mode, grid, block, lds, s);
-    if (per_wave <= 2) return launch_sweep_fwd_nt<2>(a, w, mode, grid, block, lds, s);
-    if (per_wave <= 4) return launch_sweep_fwd_nt<4>(a, w, mode, grid, block, lds, s);
-    return launch_sweep_fwd_nt<8>(a, w, mode, grid, block, lds, s);
-}
-
-void launch_probe_sweep_dw(const ProbeDwArgs& a, const ProbeSweepArgs& w, int row_groups, hipStream_t s) {
-    const dim3 grid((unsigned)((a.C + 63) / 64), (unsigned)((a.D + 1 + 63) / 64), (unsigned)(w.T * row_groups));
-    hipLaunchKernelGGL(probe_dw_kernel<true>, grid, dim3(256), 0, s, a, w, row_groups);
-}
+void launch_probe_sweep_dw(const ProbeDwArgs& a, const ProbeSweepArgs& w, int row_groups, hipStream_t s) { probe_launch_dw<true>(a, w, row_groups, s); }
 
 void launch_probe_sweep_reduce(const ProbeSweepArgs& w, int groups, hipStream_t s) {
-    hipLaunchKernelGGL(probe_reduce_kernel<true>, dim3((unsigned)((w.E + 1023) / 1024), (unsigned)w.T), dim3(256), 0, s, w.partial, w.E, groups, w.ss_part, w);
+    probe_launch_reduce<true>(w.partial, w.E, groups, w.ss_part, w, s);
 }
 
 void launch_probe_sweep_update(const ProbeUpdateArgs& a, const ProbeSweepArgs& w, const float* step_sizes, hipStream_t s) {
-    hipLaunchKernelGGL(probe_update_kernel<true>, dim3((unsigned)((a.E + 255) / 256), (unsigned)w.T), dim3(256), 0, s, a, w, step_sizes);
+    probe_launch_update<true>(a, w, step_sizes, s);
 }
 
-// out[t] = scale * (the n_parts loss partials of trial t in order), one workgroup per trial (bn_probe_sweep_loss)
+void preload_probe_sweep() {
+    hipFuncAttributes at;
+    (void)hipFuncGetAttributes(&at, reinterpret_cast<const void*>(&probe_update_kernel<true>));
+}
+
+// out[t] = scale * (the n_parts loss partials of trial t in order) (bn_probe_sweep_loss)
 void launch_probe_sweep_loss_sum(const ProbeSweepArgs& w, long n_parts, float scale, float* out, hipStream_t s) {
-    hipLaunchKernelGGL(probe_loss_sum_kernel<true>, dim3((unsigned)w.T), dim3(256), 0, s, w.loss_part, n_parts, scale, out, w);
+    probe_launch_loss_sum<true>(w.loss_part, n_parts, scale, out, w, s);
 }
 
 // the parameters of every trial with mask[t] != 0 -> its best-weights slot (bn_probe_sweep_snapshot)
@@ -75,11 +55,6 @@ __global__ __launch_bounds__(256) void probe_sweep_snapshot_kernel(float* __rest
 
 void launch_probe_sweep_snapshot(const ProbeSweepArgs& w, const uint8_t* mask, hipStream_t s) {
     hipLaunchKernelGGL(probe_sweep_snapshot_kernel, dim3((unsigned)((w.E + 255) / 256), (unsigned)w.T), dim3(256), 0, s, w.state, w.E, mask);
-}
-
-void preload_probe_sweep() {
-    hipFuncAttributes at;
-    (void)hipFuncGetAttributes(&at, reinterpret_cast<const void*>(&probe_update_kernel<true>));
 }
 
 }  // namespace bn

@@ -179,9 +179,9 @@ def test_early_stopping_restores_the_best_epoch(torch_mod, ctx):
     best = h["best_epoch"]
     print("val_loss", [round(v, 4) for v in h["val_loss"]], "best", best, "stopped", h["stopped_epoch"])
     assert h["stopped_epoch"] is not None and h["stopped_epoch"] == best + 3 and best == int(np.argmin(h["val_loss"]))
-    W0, b0 = lp.init_head(64, 6, 5)
-    cfg = dict(activation="sigmoid", optimizer="adam", batch=32, seed=5, dropout=0.0, clipnorm=1.0, lr=2e-2, weight_decay=0.0, total=30 * 16)
-    be = lp._DeviceBackend(ctx, X, Y, None, None, W0, b0, cfg)
+    plan = lp._plan_fit(X, Y, None, device=True, activation="sigmoid", optimizer="adam", batch_size=32, dropout=0.0, epochs=30, learning_rate=2e-2,
+                        weight_decay=0.0, clipnorm=1.0, seed=5)
+    be = lp._DeviceBackend(ctx, X, Y, None, None, plan)
     try:
         for epoch in range(best + 1):
             be.epoch(lp.epoch_permutation(5, epoch, 512))

@@ -69,13 +69,12 @@ def sweep_main(args):
         Y[torch.arange(n, device="cuda"), torch.randint(0, C, (n,), device="cuda", generator=g)] = 1.0
         for batch in [int(v) for v in args.batches.split(",")]:
             steps = math.ceil(n / batch)
-            total = steps * (args.repeats + 1)
-            W0, b0 = lp.init_head(D, C, 1)
-            cfg = dict(activation="sigmoid", optimizer="adam", batch=batch, seed=1, dropout=0.5, clipnorm=1.0, lr=1e-3, weight_decay=0.0, total=total)
+            plan = lp._plan_fit(X, Y, None, device=True, activation="sigmoid", optimizer="adam", batch_size=batch, dropout=0.5, epochs=args.repeats + 1,
+                                learning_rate=1e-3, weight_decay=0.0, clipnorm=1.0, seed=1)
             for T in [int(v) for v in args.sweep.split(",")]:
                 trials = [lp.ProbeTrial(learning_rate=1e-3, optimizer="adam", dropout=0.5, clipnorm=1.0)] * T
-                singles = [lp._DeviceBackend(ctx, X, Y, None, None, W0, b0, cfg) for _ in range(T)]
-                sweep = lp._SweepBackend(ctx, X, Y, None, None, W0, b0, cfg, trials)
+                singles = [lp._DeviceBackend(ctx, X, Y, None, None, plan) for _ in range(T)]
+                sweep = lp._SweepBackend(ctx, X, Y, None, None, plan, trials)
                 active = np.ones(T, bool)
                 seq, par = [], []
                 for e in range(args.repeats + 1):
@@ -129,7 +128,7 @@ def main():
     ctx = _hip.Context(0, 1)
     g = torch.Generator(device="cuda").manual_seed(1)
     X = torch.rand((n, D), device="cuda", generator=g)
-    weights = 0.5 + 3.5 * torch.rand(n, device="cuda", generator=g) if args.row_weights else None
+    weights = np.random.default_rng(1).uniform(0.5, 4.0, n).astype(np.float32) if args.row_weights else None
     rows = []
     for C in (12, 100, 1000):
         Y = torch.zeros((n, C), device="cuda")
@@ -137,10 +136,10 @@ def main():
         for batch in (32, 512, 4096):
             steps = math.ceil(n / batch)
             total = steps * (args.epochs + 1)
-            W0, b0 = lp.init_head(D, C, 1)
-            cfg = dict(activation="sigmoid", optimizer="adam", batch=batch, seed=1, dropout=0.5, clipnorm=1.0, lr=1e-3, weight_decay=0.0, total=total,
-                       loss=args.loss, focal_gamma=args.focal_gamma)
-            be = lp._DeviceBackend(ctx, X, Y, None, None, W0, b0, cfg, sample_weight=weights)
+            plan = lp._plan_fit(X, Y, None, device=True, activation="sigmoid", optimizer="adam", batch_size=batch, dropout=0.5, epochs=args.epochs + 1,
+                                learning_rate=1e-3, weight_decay=0.0, clipnorm=1.0, seed=1, loss=args.loss, focal_gamma=args.focal_gamma,
+                                sample_weight=weights)
+            be = lp._DeviceBackend(ctx, X, Y, None, None, plan)
             ours = []
             for e in range(args.epochs + 1):
                 perm = lp.epoch_permutation(1, e, n)
