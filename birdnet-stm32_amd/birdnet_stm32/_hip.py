@@ -35,7 +35,7 @@ EXPORTS = (
     "bn_probe_set_loss", "bn_probe_epoch_weighted", "bn_probe_sweep_set_loss", "bn_probe_sweep_epoch_weighted",
     "bn_short_time_energy", "bn_activity_counts", "bn_search_inv_norms", "bn_search_topk", "bn_augment_inputs",
     "bn_kmeans_assign", "bn_kmeans_accumulate", "bn_kmeans_centroids",
-    "bn_bootstrap_rejections", "bn_bootstrap_counts", "bn_bootstrap_ap",
+    "bn_bootstrap_rejections", "bn_bootstrap_counts", "bn_bootstrap_ap", "bn_head_i8_forward", "bn_head_i8_pass_classes",
 )  # fmt: skip
 
 EMB_F32, EMB_I8 = 0, 1  # BN_EMB_* (include/birdnet_hip.h)
@@ -45,6 +45,15 @@ PROBE_LOSSES = {"auto": 0, "focal": 1}  # BN_PROBE_LOSS_* ("auto": the activatio
 PROBE_MAX_D, PROBE_MAX_C = 2048, 4096
 PROBE_SWEEP_MAX_TRIALS = 64  # BN_PROBE_SWEEP_MAX_TRIALS
 PROBE_SWEEP_CURRENT, PROBE_SWEEP_SNAPSHOT = 0, 1  # BN_PROBE_SWEEP_*
+HEAD_I8_STEP_ROWS, HEAD_I8_MIN_WG_STEPS, HEAD_I8_MAX_WGS, HEAD_I8_LDS_BYTES = 64, 8, 1024, 160 * 1024  # BN_HEAD_I8_*: how bn_head_i8_forward deals rows
+
+
+
+def head_i8_pass_classes(D: int, C: int) -> int:
+    """Classes per LDS pass of ``bn_head_i8_forward`` (``bn_head_i8_pass_classes``: the launcher's own plan); more classes take further passes."""
+    v = int(load_library().bn_head_i8_pass_classes(int(D), int(C)))
+    check(min(v, 0))
+    return v
 
 
 class ProbeTrialStruct(ctypes.Structure):
@@ -181,6 +190,9 @@ def load_library(path: str | None = None):
     lib.bn_host_alloc_pinned.restype = c_void_p
     lib.bn_host_free_pinned.argtypes = [c_void_p]
     lib.bn_head_forward.argtypes = [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]
+    lib.bn_head_i8_forward.argtypes = [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_float,
+                                       c_void_p, c_void_p, c_void_p]
+    lib.bn_head_i8_pass_classes.argtypes = [c_int, c_int]
     lib.bn_probe_create.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, ctypes.c_uint32, c_int64,
                                     c_void_p, c_void_p, POINTER(c_void_p), c_void_p]
     lib.bn_probe_destroy.argtypes = [c_void_p]

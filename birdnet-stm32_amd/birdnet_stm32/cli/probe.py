@@ -9,7 +9,9 @@ The backbone runs once over all files (``embed``'s device path), the head is tra
 ``--n_trials`` heads train at once on the device (``training/tune.py``), the one with the lowest validation loss is written, and
 ``<output>_tune.json`` lists them all.  For long-tailed folders: ``--upsample_ratio`` repeats training files of the small classes,
 ``--class_weights balanced`` weighs the rows by inverse class frequency and ``--loss focal`` trains on the focal loss; they combine with
-each other and with the plain fit, ``--tune`` and the augmented fit.
+each other and with the plain fit, ``--tune`` and the augmented fit.  With ``--export_tflite`` on an INT8 ``.tflite`` backbone the head is
+also quantised and written into ``<output>.tflite`` (``conversion/head_export.py``), next to the labels and config: a model for
+``evaluate``, ``analyze`` and the board.
 """
 
 from __future__ import annotations
@@ -69,6 +71,13 @@ def build_parser() -> argparse.ArgumentParser:
                         "<output>_tune.json lists every trial.  Needs --val_split > 0; not with --mixup_probability or --spec_augment")
     p.add_argument("--n_trials", type=int, default=20, help="With --tune: number of trials, 1..64")
     p.add_argument("--tune_seed", type=int, default=None, help="With --tune: seed of the trials' draws (default: --seed)")
+    p.add_argument("--export_tflite", action="store_true",
+                   help="Also write the trained head into <output>.tflite: the INT8 backbone with its classifier replaced by the quantised head, an "
+                        "ordinary model for evaluate / analyze / the board, and <output>_export.json with the float-vs-INT8 report.  Needs "
+                        "--model_path to be an INT8 .tflite")
+    p.add_argument("--per_tensor", action="store_true", help="With --export_tflite: one weight scale for the whole head instead of one per class")
+    p.add_argument("--min_cosine_sim", type=float, default=0.95,
+                   help="With --export_tflite: minimum mean cosine similarity of float and INT8 head scores; the export fails below (0 to disable)")
     p.add_argument("--seed", type=int, default=42, help="Seed of the file shuffle, the initial weights, the batches and the dropout mask")
     p.add_argument("--max_batch", type=int, default=4096, help="Workspace size in chunks = inference slice of the device pipeline")
     p.add_argument("--device", type=int, default=0, help="MI355X index")
@@ -87,6 +96,9 @@ def main(argv=None, runner=None):
 
         augmentation_from_args(args)   # (and bad augmentation flags; run_linear_probe refuses bad --tune / --label_smoothing combinations first thing)
         imbalance_from_args(args)      # (and focal with softmax, a bad --focal_gamma or --upsample_ratio)
+        from birdnet_stm32.training.linear_probe import check_export_args
+
+        check_export_args(args)        # (and --export_tflite on a float backbone)
         return run_linear_probe(args, runner=runner)
     except (ValueError, FileNotFoundError) as exc:
         raise SystemExit(f"error: {exc}") from None

@@ -413,7 +413,7 @@ def quantize_graph(template: TfliteModel, consts: dict[int, np.ndarray], float_w
 
 def convert_to_int8(spec: ns.NetSpec, template_path: str, rep_data_gen, per_tensor: bool = False) -> TfliteModel:
     """Counterpart of the reference's ``convert_to_tflite(model, rep_data_gen, ..., quantization='ptq', per_tensor)``: returns the
-    in-memory INT8 graph (``lower_i8`` / ``HipRunner`` consume it; there is no flatbuffer writer)."""
+    in-memory INT8 graph (``lower_i8`` / ``HipRunner`` consume it; ``models/_tflite_writer.write_tflite`` serialises it)."""
     from birdnet_stm32.models._tflite_reader import load_tflite
 
     return requantize_like(load_tflite(template_path), spec, rep_data_gen, per_tensor=per_tensor)

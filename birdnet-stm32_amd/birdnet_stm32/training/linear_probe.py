@@ -1032,7 +1032,7 @@ def targets_from_paths(paths: list, classes: list, file_index: np.ndarray, activ
 def probe_output_paths(output: str) -> dict:
     stem = output[:-4] if output.endswith(".npz") else output
     return {"head": stem + ".npz", "labels": stem + "_labels.txt", "config": stem + "_model_config.json", "history": stem + "_history.csv",
-            "tune": stem + "_tune.json"}
+            "tune": stem + "_tune.json", "tflite": stem + ".tflite", "export": stem + "_export.json"}
 
 
 def write_history_csv(path: str, history: dict) -> None:
@@ -1096,10 +1096,88 @@ def upsample_multiplicity(train_paths: list, classes: list, ratio: float) -> tup
     return np.array([count.get(p, 1) for p in train_paths], np.int64), upsampled
 
 
+def check_export_args(args) -> bool:
+    """``--export_tflite`` of ``probe`` (absent in older namespaces: off): refused unless ``--model_path`` is an INT8 ``.tflite`` — the head
+    must be trained on the embeddings the board computes — by its suffix and by the graph itself (an int8 pooled tensor in front of a
+    classifier), before any audio file is read."""
+    if not getattr(args, "export_tflite", False):
+        return False
+    if not str(args.model_path).lower().endswith(".tflite"):
+        raise ValueError(f"--export_tflite needs --model_path to be an INT8 .tflite, not {args.model_path}: the exported head must be trained on the "
+                         "embeddings the board computes, and heads on float backbones are not exported")
+    if os.path.isfile(args.model_path):   # (a missing file is reported as such by the command); a float .tflite, or one without a classifier behind pooling
+        from birdnet_stm32.conversion.head_export import int8_embedding_of
+        from birdnet_stm32.models._tflite_reader import load_tflite
+
+        try:
+            int8_embedding_of(load_tflite(args.model_path))
+        except ValueError as exc:
+            raise ValueError(f"--export_tflite: {args.model_path}: {exc}") from None
+    cos = float(getattr(args, "min_cosine_sim", 0.95))
+    if not 0.0 <= cos <= 1.0:   # (NaN fails too)
+        raise ValueError(f"--min_cosine_sim must be in [0, 1] (0 disables the check), got {cos}")
+    return True
+
+
+def embedding_bytes_device(X, scale: float, zero_point: int, device):
+    """The int8 bytes behind float32 embeddings ``X [n, D]`` of an INT8 runner, ``round(x / scale) + zero_point``, as a CUDA int8 tensor; the
+    round trip ``(q - zero_point) * scale == x`` is asserted on the device for every element."""
+    import torch
+
+    x = torch.from_numpy(np.ascontiguousarray(X, np.float32)).to(device)
+    s = torch.tensor(np.float32(scale), dtype=torch.float32, device=x.device)
+    q = torch.round(x / s) + float(zero_point)
+    if not bool(((q >= -128) & (q <= 127) & ((q - float(zero_point)) * s == x)).all()):
+        raise RuntimeError("the embeddings are not the dequantised bytes of this model: (q - zero_point) * scale does not give them back")
+    return q.to(torch.int8)
+
+
+def export_probe_tflite(head, runner, model_path: str, X, Y, report_rows, out: dict, activation: str, per_tensor: bool, min_cosine_sim: float,
+                        loss_kw: dict) -> dict:
+    """``probe --export_tflite``: ``head`` into ``out["tflite"]`` (``conversion.head_export.export_head_tflite``, calibrated on all rows
+    ``X``), the report of float head against INT8 head (``bn_head_i8_forward``) over ``report_rows`` into ``out["export"]``; raises below
+    ``min_cosine_sim`` as ``convert`` does."""
+    from birdnet_stm32.conversion.head_export import export_head_tflite
+    from birdnet_stm32.conversion.validate import cosine_similarity, pearson_correlation
+
+    info = runner.embedding_info()
+    if info["dtype"] != "int8":
+        raise ValueError("--export_tflite needs an INT8 model: this one's embeddings are float32")
+    rows = embedding_bytes_device(X, info["scale"], info["zero_point"], runner.device)
+    rep = export_head_tflite(head, model_path, rows, out["tflite"], per_tensor=per_tensor, ctx=runner.ctx)
+    qhead = rep.pop("qhead")
+    import torch
+
+    sel = torch.from_numpy(np.flatnonzero(report_rows)).to(rows.device)
+    P_q, logit = qhead.predict_device(rows[sel].contiguous(), runner.ctx, return_logit_bytes=True)
+    P_q, logit = P_q.cpu().numpy(), logit.cpu().numpy()
+    qhead.close()
+    P_f = head.predict(X[report_rows], runner.ctx)
+    a, b = P_f.astype(np.float64), P_q.astype(np.float64)
+    rep.update({"model_path": model_path, "activation": activation, "classes": int(head.num_classes), "report_rows": int(report_rows.sum()),
+                "cosine_mean": float(np.mean([cosine_similarity(u, v) for u, v in zip(a, b)])),
+                "mse_mean": float(np.mean((a - b) ** 2)), "mae_mean": float(np.mean(np.abs(a - b))),
+                "pearson_mean": float(np.mean([pearson_correlation(u, v) for u, v in zip(a, b)])),
+                "loss_float": float(probe_loss(P_f, Y[report_rows], activation, **loss_kw)),
+                "loss_int8": float(probe_loss(P_q, Y[report_rows], activation, **loss_kw)),
+                "report_clipped_share": float(np.mean((logit == -128) | (logit == 127))), "min_cosine_sim": float(min_cosine_sim)})
+    with open(out["export"], "w") as fh:
+        json.dump(rep, fh, indent=1)
+    print(f"[probe] exported {out['tflite']} ({rep['bytes']} bytes, {rep['classes']} classes, {'per-tensor' if per_tensor else 'per-channel'} weights): logits "
+          f"[{rep['logit_range'][0]:.3f}, {rep['logit_range'][1]:.3f}] at scale {rep['logit_scale']:.5f}, {100 * rep['clipped_share']:.2f} % of the logit bytes at "
+          f"a clamp; float vs INT8 head over {rep['report_rows']} rows: cosine {rep['cosine_mean']:.6f}, MSE {rep['mse_mean']:.3e}, Pearson "
+          f"{rep['pearson_mean']:.6f}, loss {rep['loss_float']:.4f} -> {rep['loss_int8']:.4f}")
+    if min_cosine_sim > 0 and rep["cosine_mean"] < min_cosine_sim:
+        raise RuntimeError(f"Quantization quality check failed: mean cosine similarity {rep['cosine_mean']:.6f} < threshold {min_cosine_sim:.4f}.")
+    return rep
+
+
 def run_linear_probe(args, runner=None) -> ProbeHead:
     """The ``probe`` command: ``args.data_path_train/<class>/*`` -> embeddings (the backbone runs once) -> ``fit_probe`` ->
     ``<output>.npz``, ``<output>_labels.txt``, ``<output>_model_config.json`` and ``<output>_history.csv``.  With ``args.tune``:
     ``training.tune.sample_trials`` -> ``fit_probe_sweep``; the files are the winning trial's, ``<output>_tune.json`` lists all trials.
+    With ``args.export_tflite`` (INT8 ``.tflite`` backbones): the written head also goes into ``<output>.tflite``, an ordinary model next
+    to the labels and config written here, with ``<output>_export.json`` (``export_probe_tflite``).
 
     For long-tailed folders (``imbalance_from_args``), in the reference's order: ``--upsample_ratio`` first repeats training files of the
     small classes (``upsample_multiplicity``; the validation split is never upsampled, and every distinct file is embedded once: the
@@ -1119,6 +1197,7 @@ def run_linear_probe(args, runner=None) -> ProbeHead:
     augment = augmentation_from_args(args)
     imb = imbalance_from_args(args)
     check_tune_args(args)
+    export = check_export_args(args)
     label_smoothing = _check_label_smoothing(getattr(args, "label_smoothing", 0.0))
     if augment is not None and label_smoothing > 0:
         raise ValueError("--label_smoothing does not combine with --mixup_probability or --spec_augment")
@@ -1230,6 +1309,11 @@ def run_linear_probe(args, runner=None) -> ProbeHead:
         win = tuned["trials"][tuned["best_trial"]]
         print(f"[probe] tuned over {tuned['n_trials']} trials: trial {tuned['best_trial']} wins with val_loss {win['best_val_loss']:.4f} "
               f"(macro ROC-AUC {tuned['best_val_macro_roc_auc']:.4f}; trial 0, the untuned settings: {tuned['trials'][0]['best_val_loss']:.4f}) {win['params']}")
+    if export:   # calibrated on all kept rows, reported over the validation rows (all rows when there are none)
+        kept = tr | va
+        export_probe_tflite(head, runner, args.model_path, emb.embeddings[kept], Y[kept], (va if va.any() else tr)[kept], out, args.activation,
+                            bool(getattr(args, "per_tensor", False)), float(getattr(args, "min_cosine_sim", 0.95)),
+                            dict(loss=imb["loss"], focal_gamma=imb["focal_gamma"]))
     head.history["seconds"] = {"embed": t_embed, "fit": t_fit}
     val = head.history["val_loss"]
     aug_s = head.history.get("augment_seconds")

@@ -1,7 +1,7 @@
 // bn_api.hip — the C ABI of libbirdnet_hip.so (include/birdnet_hip.h): context and model
 // lifetime, packed-blob parsing, workspace allocation and the entry points that split a
 // bn_forward()/bn_infer_audio() call into launch groups for the plan executor (bn_plan_run.hip).
-// The entry points of the classifier head and its training (bn_head_forward, bn_probe_*) are in bn_probe_api.hip.
+// The entry points of the classifier head and its training (bn_head_forward, bn_head_i8_forward, bn_probe_*) are in bn_probe_api.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -1042,7 +1042,7 @@ int bn_preload_kernels(bn_ctx* ctx) {
     // copies wait meanwhile).  A caller with idle time before its first batch — the evaluate pipeline while the first files are read — asks here.
     bn::preload_ingest(); bn::preload_stft(); bn::preload_stft_exact(); bn::preload_i8_fused(); bn::preload_i8_strip(); bn::preload_i8_tail2();
     bn::preload_i8_tail(); bn::preload_i8(); bn::preload_i8_pw(); bn::preload_f32(); bn::preload_f32_fused(); bn::preload_f32_strip();
-    bn::preload_f32_pw(); bn::preload_melspec(); bn::preload_sort(); bn::preload_probe(); bn::preload_probe_sweep(); bn::preload_activity(); bn::preload_search(); bn::preload_augment(); bn::preload_kmeans(); bn::preload_bootstrap();
+    bn::preload_f32_pw(); bn::preload_melspec(); bn::preload_sort(); bn::preload_probe(); bn::preload_probe_sweep(); bn::preload_activity(); bn::preload_search(); bn::preload_augment(); bn::preload_kmeans(); bn::preload_bootstrap(); bn::preload_head_i8();
     return BN_OK;
 }
 
@@ -1061,7 +1061,7 @@ const char* bn_kernel_names(void) {
     return "ingest_resample_kernel\ningest_decimate_kernel\ningest_peak_kernel\ningest_chunks_kernel\nchunk_peaknorm_kernel\npool_scores_kernel\nstft512_mag_kernel\nspec_normalize_kernel\nmelspec_finish_kernel\nf32_mel_kernel\nf32_melfin_kernel\nf32_mag_kernel\nf32_rawfe_kernel\nf32_stem_kernel\nf32_dw_kernel\n"
            "f32_pw_kernel\nf32_pw_ws_kernel\nf32_dwpw_kernel\nf32_dwpw_wave_kernel\nf32_strip_kernel\nf32_front_strip_kernel\nf32_front2_kernel\nf32_pwdw_kernel\nf32_dw_stream_kernel\nf32_front_kernel\nf32_gap_kernel\nf32_gap_dense_kernel\nf32_gap_dense_emb_kernel\nf32_dense_kernel\nf32_segate_kernel\nf32_scale_kernel\nf32_attnpool_kernel\n"
            "i8_quant_kernel\ni8_mel_kernel\ni8_stem_kernel\ni8_dw_kernel\ni8_pw_kernel\ni8_dwpw_kernel\ni8_mel_mfma_kernel\ni8_strip_kernel\ni8_strip_mf_kernel\ni8_front_strip_kernel\ni8_front_kernel\ni8_tail_kernel\ni8_tail_emb_kernel\ni8_tail2_kernel\ni8_tail2_emb_kernel\ni8_mid2_kernel\ni8_mean_kernel\ni8_fc_kernel\ni8_scale_kernel\ni8_maxnorm_kernel\ni8_rawfe_kernel\ni8_pwdw_kernel\ni8_dw_stream_kernel\ni8_stem_stream_kernel\ni8_segate_kernel\ni8_pw_wave_kernel\ni8_pw_lds_kernel\ni8_attnpool_kernel\n"
-           "i8_head_kernel\ni8_head_softmax_kernel\nemb_store_kernel\nprobe_fwd_kernel\nprobe_dw_kernel\nprobe_reduce_kernel\nprobe_update_kernel\nprobe_loss_sum_kernel\nprobe_sweep_snapshot_kernel\nste_kernel\nactivity_count_kernel\nsearch_inv_norms_kernel\nsearch_score_kernel\nsearch_merge_kernel\naugment_kernel\nkmeans_assign_kernel\nkmeans_keys_kernel\nkmeans_offsets_kernel\nkmeans_segments_kernel\nkmeans_partial_kernel\nkmeans_fold_kernel\nkmeans_scale_kernel\nbootstrap_table_kernel\nbootstrap_reject_kernel\nbootstrap_prepare_kernel\nbootstrap_resample_kernel";
+           "i8_head_kernel\ni8_head_softmax_kernel\nemb_store_kernel\nprobe_fwd_kernel\nprobe_dw_kernel\nprobe_reduce_kernel\nprobe_update_kernel\nprobe_loss_sum_kernel\nprobe_sweep_snapshot_kernel\nste_kernel\nactivity_count_kernel\nsearch_inv_norms_kernel\nsearch_score_kernel\nsearch_merge_kernel\naugment_kernel\nkmeans_assign_kernel\nkmeans_keys_kernel\nkmeans_offsets_kernel\nkmeans_segments_kernel\nkmeans_partial_kernel\nkmeans_fold_kernel\nkmeans_scale_kernel\nbootstrap_table_kernel\nbootstrap_reject_kernel\nbootstrap_prepare_kernel\nbootstrap_resample_kernel\nhead_i8_kernel";
 }
 
 }  // extern "C"

@@ -420,7 +420,7 @@ void launch_i8_dwpw(const DwPw8Args& a, hipStream_t s);
 // One per source file with kernels: load that file's device code object now (bn_preload_kernels)
 void preload_f32(); void preload_f32_fused(); void preload_f32_pw(); void preload_f32_strip(); void preload_i8(); void preload_i8_fused();
 void preload_i8_pw(); void preload_i8_strip(); void preload_i8_tail(); void preload_i8_tail2(); void preload_ingest(); void preload_melspec();
-void preload_stft(); void preload_stft_exact(); void preload_sort(); void preload_probe(); void preload_probe_sweep(); void preload_activity(); void preload_search(); void preload_augment(); void preload_kmeans(); void preload_bootstrap();
+void preload_stft(); void preload_stft_exact(); void preload_sort(); void preload_probe(); void preload_probe_sweep(); void preload_activity(); void preload_search(); void preload_augment(); void preload_kmeans(); void preload_bootstrap(); void preload_head_i8();
 
 // bn_probe.hip: a classifier head on embeddings (bn_head_forward) and its training step (bn_probe_*)
 struct ProbeFwdArgs {
@@ -527,6 +527,33 @@ bool search_geometry(long n, int D, int Q, int k, bool i8, SearchGeom* g);   // 
 void launch_search_inv_norms(const void* rows, bool i8, long n, int D, int zp, float* inv, hipStream_t s);
 bool launch_search_scores(const SearchArgs& a, const SearchGeom& g, bool i8, hipStream_t s);   // false: the runtime refused the LDS request
 void launch_search_merge(const float* part_score, const int* part_idx, int nwg, int Q, int k, int* out_idx, float* out_score, hipStream_t s);
+
+// bn_head_i8.hip: the exported INT8 classifier head over int8 embedding rows (bn_head_i8_forward)
+struct HeadI8Args {
+    const int8_t* rows;      // [n, D] embedding bytes
+    const int8_t* w;         // [C, D rounded up to 64] weights, zero beyond D
+    const int32_t* bias;     // [C] with -z_in * sum(w) folded in
+    const int32_t* mult;     // [C]
+    const int32_t* shift;    // [C]
+    const int8_t* lut;       // LOGISTIC table by byte + 128 (sigmoid head), or null
+    int8_t* logit;           // [n, C] requantised classifier output, or null
+    float* scores;           // [n, C], written when there is a table
+    long n;
+    int D, C, zp_out;
+    int pass_tiles;          // class tiles of 16 a workgroup holds in LDS
+    int wide;                // C % 4 == 0 and the outputs aligned for it: a lane's four classes go out as one store each
+    long steps_per_wg;       // steps of BN_HEAD_I8_STEP_ROWS rows a workgroup streams
+};
+struct HeadI8Geom {
+    int nt;                  // class tiles multiplied per pass over a step's rows
+    int pass_tiles;          // class tiles per LDS pass, a multiple of nt
+    int passes;              // second grid axis
+    int nwg;                 // workgroups along the rows
+    long steps_per_wg;
+    size_t lds;
+};
+bool head_i8_geometry(long n, int D, int C, HeadI8Geom* g);   // from the shapes only; false: no tile fits the LDS
+bool launch_head_i8(const HeadI8Args& a, const HeadI8Geom& g, hipStream_t s);   // false: the runtime refused the LDS request
 
 // bn_kmeans.hip: spherical k-means, one Lloyd iteration = an assignment and an update (bn_kmeans_*)
 struct KmeansAssignArgs {

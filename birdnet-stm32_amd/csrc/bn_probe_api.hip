@@ -1,5 +1,6 @@
 // bn_probe_api.hip — the C ABI of a classifier head on frozen embeddings and of its training (host code only):
-// bn_head_forward, bn_probe_* (one head; kernels in bn_probe.hip) and bn_probe_sweep_* (T heads in lock-step; bn_probe_sweep.hip).
+// bn_head_forward, bn_probe_* (one head; kernels in bn_probe.hip), bn_probe_sweep_* (T heads in lock-step; bn_probe_sweep.hip) and
+// bn_head_i8_forward (the head as exported into an INT8 model; bn_head_i8.hip).
 //
 // A single fit and a sweep are one procedure: their handles share ProbeHandle, and the checks, the workspace growth and the step loop
 // are written once (probe_epoch<SWEEP>, probe_loss<SWEEP>).  They differ in where the step sizes come from (computed here, or the
@@ -282,6 +283,47 @@ int bn_head_forward(bn_ctx* ctx, const float* d_emb, int64_t n, int D, const flo
     if (!bn::launch_probe_fwd(a, 2, (hipStream_t)stream)) return fail(BN_ERR_DEVICE, "the head kernel's LDS request was refused");
     HIP_TRY(hipGetLastError());
     return BN_OK;
+}
+
+// The exported INT8 head over int8 embedding rows (bn_head_i8.hip); a softmax head's scores come from the model's own softmax kernel
+int bn_head_i8_forward(bn_ctx* ctx, const int8_t* d_rows, int64_t n, int D, const int8_t* d_w, const int32_t* d_bias, const int32_t* d_mult,
+                       const int32_t* d_shift, int C, int zp_out, const int8_t* d_lut, int activation, float s_fc, int8_t* d_logit_bytes,
+                       float* d_scores, void* stream) {
+    if (int rc = check_device(ctx)) return rc;
+    if (int rc = probe_shape_check(D, C, activation)) return rc;
+    if (n < 0 || n > 0x7fffffffLL) return fail(BN_ERR_ARG, "bad row count %lld", (long long)n);
+    if (zp_out < -128 || zp_out > 127) return fail(BN_ERR_ARG, "zero point %d outside -128..127", zp_out);
+    const bool softmax = activation == BN_PROBE_ACT_SOFTMAX;
+    if (softmax ? d_lut != nullptr : d_lut == nullptr) return fail(BN_ERR_ARG, "a sigmoid head takes its LOGISTIC table, a softmax head none");
+    if (softmax && !d_logit_bytes) return fail(BN_ERR_ARG, "a softmax head needs d_logit_bytes: its scores are computed from them");
+    if (n == 0) return BN_OK;
+    if (!d_rows || !d_w || !d_bias || !d_mult || !d_shift || !d_scores) return fail(BN_ERR_ARG, "null device pointer");
+    if ((uintptr_t)d_w % 16 || (uintptr_t)d_bias % 4 || (uintptr_t)d_mult % 4 || (uintptr_t)d_shift % 4 || (uintptr_t)d_lut % 4 || (uintptr_t)d_scores % 4)
+        return fail(BN_ERR_ARG, "d_w must be 16-byte aligned, the int32 / float32 arrays and the table 4-byte aligned");
+    bn::HeadI8Geom g{};
+    if (!bn::head_i8_geometry((long)n, D, C, &g)) return fail(BN_ERR_ARG, "D=%d: no class tile fits the LDS", D);
+    bn::HeadI8Args a{};
+    a.rows = d_rows; a.w = d_w; a.bias = d_bias; a.mult = d_mult; a.shift = d_shift; a.lut = d_lut; a.logit = d_logit_bytes; a.scores = d_scores;
+    a.n = (long)n; a.D = D; a.C = C; a.zp_out = zp_out; a.pass_tiles = g.pass_tiles; a.steps_per_wg = g.steps_per_wg;
+    a.wide = C % 4 == 0 && (uintptr_t)d_scores % 16 == 0 && (uintptr_t)d_logit_bytes % 4 == 0;
+    hipStream_t s = (hipStream_t)stream;
+    if (!bn::launch_head_i8(a, g, s)) return fail(BN_ERR_DEVICE, "the INT8 head kernel's LDS request was refused");
+    // one workgroup of 64 threads per row: slices keep a launch's thread count below 2^32
+    constexpr int64_t kSoftmaxSlice = 1 << 24;
+    for (int64_t r0 = 0; softmax && r0 < n; r0 += kSoftmaxSlice) {
+        const int nb = (int)std::min<int64_t>(kSoftmaxSlice, n - r0);
+        bn::launch_i8_head_softmax(d_logit_bytes + (size_t)r0 * C, d_scores + (size_t)r0 * C, nullptr, nb, C, zp_out, s_fc, 1.0f, s);
+    }
+    HIP_TRY(hipGetLastError());
+    return BN_OK;
+}
+
+// Classes per LDS pass of bn_head_i8_forward (head_i8_geometry, the launcher's own plan); host only, no device needed
+int bn_head_i8_pass_classes(int D, int C) {
+    if (int rc = probe_shape_check(D, C, BN_PROBE_ACT_SIGMOID)) return rc;
+    bn::HeadI8Geom g{};
+    if (!bn::head_i8_geometry(0, D, C, &g)) return fail(BN_ERR_ARG, "D=%d: no class tile fits the LDS", D);
+    return 16 * g.pass_tiles;
 }
 
 // ------------------------------------------------------------------------------------------------------------ one head (bn_probe.hip)

@@ -1,6 +1,7 @@
-// bn_rowstream.h — streaming the rows of an [n, D] matrix of float32 or int8 embeddings into the A operand of the matrix cores, shared by
-// the two kernels that do it (search_score_kernel in bn_search.hip, kmeans_assign_kernel in bn_kmeans.hip).  It owns the row layout, the
-// padding rule and the prefetch depth; the kernels keep their B tile, their MFMA body and their epilogue.
+// bn_rowstream.h — streaming the rows of an [n, D] matrix of float32 or int8 embeddings into an operand of the matrix cores, shared by
+// the three kernels that do it (search_score_kernel in bn_search.hip, kmeans_assign_kernel in bn_kmeans.hip, head_i8_kernel in bn_head_i8.hip).  It owns the row layout, the
+// padding rule and the prefetch depth; the kernels keep the tile of the other operand, their MFMA body and their
+// epilogue (search and k-means take the rows as the A operand; the head takes them as B, a lane's 16 bytes being the same either way).
 //
 // Layout: a step is 64 rows, one 16-row MFMA tile per wave; lane (li, lk) of a wave reads row li of the tile.  A row is cut into chunks of
 // 64 bytes, of which the lane takes the 16 at 16 lk: elements 64 c + 16 lk .. + 15 (int8) or 16 c + 4 lk .. + 3 (float32) of chunk c.
@@ -10,7 +11,7 @@
 #include "../../include/birdnet_hip.h"
 #include "bn_device.h"
 
-// From here to the end of the including translation unit: every float32 operation is rounded on its own.  Both includers want that for
+// From here to the end of the including translation unit: every float32 operation is rounded on its own.  The includers want that for
 // their whole file (the specifications they are tested against count the roundings).
 #pragma clang fp contract(off)
 
@@ -26,7 +27,7 @@ constexpr int kWaves = 4;       // waves per streaming workgroup, one 16-row til
 constexpr int kStepRows = 64;   // rows of a step
 constexpr int kGroup = 4;       // chunks of a row tile whose loads are in flight together
 static_assert(kStepRows == 16 * kWaves, "a step is one MFMA row tile per wave");
-static_assert(kStepRows == BN_SEARCH_STEP_ROWS && kStepRows == BN_KMEANS_STEP_ROWS, "the public header states the step of both kernels");
+static_assert(kStepRows == BN_SEARCH_STEP_ROWS && kStepRows == BN_KMEANS_STEP_ROWS && kStepRows == BN_HEAD_I8_STEP_ROWS, "the public header states the step of every kernel");
 
 // chunks of a row: 64 bytes each, the last one padded
 template <bool I8>

@@ -392,6 +392,32 @@ typedef struct bn_probe bn_probe;
 BN_API int bn_head_forward(bn_ctx* ctx, const float* d_emb, int64_t n, int D, const float* d_W, const float* d_b, int C, int activation,
                     float* d_scores, void* stream);
 
+/* The INT8 head of an exported model (conversion/head_export.py; csrc/bn_head_i8.hip) over n rows of int8 embedding bytes, as the
+ * FULLY_CONNECTED [-> LOGISTIC] -> DEQUANTIZE [-> SOFTMAX] tail of the .tflite computes it:
+ *   q[i, c] = clamp(MultiplyByQuantizedMultiplier(sum_k rows[i, k] * w[c, k] + bias[c], mult[c], shift[c]) + zp_out, -128, 127)
+ * d_w [C, Kp] int8 with Kp = D rounded up to a multiple of 64, zero beyond D, 16-byte aligned; d_bias [C] int32 holds the layer's bias
+ * minus (embedding zero point) * sum_k w[c, k]; d_mult / d_shift [C] the per-class Q31 multiplier and exponent.  Every accumulator must
+ * fit int32 and its requantisation the fast forms' domain (csrc/bn_requant.h); the exporter refuses a head that does not.
+ * BN_PROBE_ACT_SIGMOID: d_lut is the 256-entry int8 LOGISTIC table indexed by q + 128 (output scale 1/256, zero point -128) and
+ *   d_scores[i, c] = (d_lut[q + 128] + 128) / 256; d_logit_bytes [n, C] receives q when it is not NULL.
+ * BN_PROBE_ACT_SOFTMAX: d_lut is NULL, d_logit_bytes is required, and d_scores is the float32 softmax (beta 1) of s_fc * (q - zp_out)
+ *   per row, by the kernel that ends a softmax model's plan (launched in slices of 2^24 rows).  s_fc is read for softmax only.
+ * 1 <= D <= BN_PROBE_MAX_D, 1 <= C <= BN_PROBE_MAX_C, 0 <= n < 2^31 (n == 0 launches nothing).  Rows go in steps of
+ * BN_HEAD_I8_STEP_ROWS, at least BN_HEAD_I8_MIN_WG_STEPS steps per workgroup, at most BN_HEAD_I8_MAX_WGS workgroups per pass over the
+ * classes; a pass holds as many class tiles of 16 as fit BN_HEAD_I8_LDS_BYTES.  Rows on a 16-byte boundary with D % 16 == 0 take the wide
+ * loads.  Nothing synchronises with the host inside the call. */
+#define BN_HEAD_I8_STEP_ROWS 64
+#define BN_HEAD_I8_MIN_WG_STEPS 8
+#define BN_HEAD_I8_MAX_WGS 1024
+#define BN_HEAD_I8_LDS_BYTES (160 * 1024)
+BN_API int bn_head_i8_forward(bn_ctx* ctx, const int8_t* d_rows, int64_t n, int D, const int8_t* d_w, const int32_t* d_bias,
+                       const int32_t* d_mult, const int32_t* d_shift, int C, int zp_out, const int8_t* d_lut, int activation, float s_fc,
+                       int8_t* d_logit_bytes, float* d_scores, void* stream);
+
+/* Classes a workgroup of bn_head_i8_forward holds in LDS per pass (a multiple of 16; more classes take further passes on the second grid
+ * axis), from (D, C) alone; negative on bad arguments.  No device is needed. */
+BN_API int bn_head_i8_pass_classes(int D, int C);
+
 /* A head in training.  d_W / d_b: the initial values (copied; the optimiser state starts at zero).  Learning rate of global step t
  * (0-based, counted over all bn_probe_epoch calls): lr * 0.5 * (1 + cos(pi * min(t, total_steps) / total_steps)).  clipnorm > 0: the
  * gradient of W and b together is scaled by clipnorm / norm when its norm exceeds clipnorm.  dropout in [0, 1): element (row i of the
