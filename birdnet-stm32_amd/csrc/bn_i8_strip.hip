@@ -610,7 +610,10 @@ void launch_strip(const Strip8Args& a, hipStream_t s) {
 // (stem row - 1 + kq), so a B fragment is one AND / byte-permute of the two dwords it loaded, and the result lands as the
 // four channels 4 q .. 4 q + 3 of stem column sc in lane (n, q): exactly the quad the depthwise stage of that lane needs.
 // Three MFMAs per stem row give stem columns 2 ow, 2 ow + 1, 2 ow + 2 (the three taps of the stride-2 depthwise window);
-// what remains on the vector ALU is the requantisation of each value and the byte shuffles.
+// what remains on the vector ALU is the requantisation of each value.  Every requantisation clamps IN FRONT of its shift (per-channel
+// bounds, bn_requant.h: shifted_bounds), so the shift is its last instruction and writes the byte where it is read next: stem column j
+// into byte j of the depthwise window dwords, the depthwise bytes into the pointwise B fragment, the pointwise bytes into the stored
+// dwords — no pack or transpose permutes.
 constexpr int kF_STA = 0, kF_STB = 64, kF_STC = 80, kF_DWW = 128, kF_DWB = 176, kF_DWC = 192, kF_PWA = 240, kF_PWB = 368, kF_PWC = 400;
 
 __global__ __launch_bounds__(256) void i8_front_strip_kernel(FrontStrip8Args a) {
@@ -636,6 +639,10 @@ __global__ __launch_bounds__(256) void i8_front_strip_kernel(FrontStrip8Args a) 
     const v4i stm = c4[kF_STC / 4 + kq * 3 + 0], stc1 = c4[kF_STC / 4 + kq * 3 + 1], ste = c4[kF_STC / 4 + kq * 3 + 2];
     const long stc[4] = {rq64(stc1.x), rq64(stc1.y), rq64(stc1.z), rq64(stc1.w)};
     const int ste1 = pack_shifts(ste - 1);
+    // clamp bounds in front of the shift, per channel (bn_requant.h: shifted_bounds)
+    int stlo[4], sthi[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) shifted_bounds(a.st_lo, a.st_hi, ste[e] - 1, stlo[e], sthi[e]);
     int dww[3][4];
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
@@ -643,26 +650,44 @@ __global__ __launch_bounds__(256) void i8_front_strip_kernel(FrontStrip8Args a) 
         dww[i][0] = v.x; dww[i][1] = v.y; dww[i][2] = v.z; dww[i][3] = v.w;
     }
     const v4i dwb = c4[kF_DWB / 4 + kq];
-    const v4i dwm = c4[kF_DWC / 4 + kq * 3 + 0], dwc1 = c4[kF_DWC / 4 + kq * 3 + 1], dwe = c4[kF_DWC / 4 + kq * 3 + 2];
-    const long dwc[4] = {rq64(dwc1.x), rq64(dwc1.y), rq64(dwc1.z), rq64(dwc1.w)};
-    const int dwe1 = pack_shifts(dwe - 1);
+    // The per-channel constants of the stages that run ONCE per output row (depthwise, pointwise: multiplier, C, bounds = 20 registers per
+    // quad) live in LDS and are re-read every row, as in i8_strip_kernel; the stem's, used twice per row, stay in registers.  With all of
+    // them in registers the kernel needs 166 and loses its fourth wave per SIMD.  Each wave keeps its own copy (lane (0, kq) writes the
+    // five 16-byte words of its quads): no workgroup barrier.
+    __shared__ v4i cq_lds[4][4][3][5];   // [wave][kq][depthwise, pointwise tile 0, tile 1][multiplier, C01, C23, lower, upper bounds]
+    auto stage_quad = [&](v4i* q, v4i m, v4i c1, v4i sh, int lo, int hi) {
+        int blo[4], bhi[4];
+        long c[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            c[e] = rq64(c1[e]);
+            shifted_bounds(lo, hi, sh[e] - 1, blo[e], bhi[e]);
+        }
+        if (n == 0) {
+            q[0] = m;
+            q[1] = (v4i){(int)c[0], (int)(c[0] >> 32), (int)c[1], (int)(c[1] >> 32)};
+            q[2] = (v4i){(int)c[2], (int)(c[2] >> 32), (int)c[3], (int)(c[3] >> 32)};
+            q[3] = (v4i){blo[0], blo[1], blo[2], blo[3]};
+            q[4] = (v4i){bhi[0], bhi[1], bhi[2], bhi[3]};
+        }
+        return pack_shifts(sh - 1);
+    };
+    const int dwe1 = stage_quad(cq_lds[wave][kq][0], c4[kF_DWC / 4 + kq * 3 + 0], c4[kF_DWC / 4 + kq * 3 + 1], c4[kF_DWC / 4 + kq * 3 + 2], a.dw_lo, a.dw_hi);
     long pwa[2];
-    v4i pwb[2], pwm[2], pwc1[2];
+    v4i pwb[2];
     int pwe1[2];
-    long pwc[2][4];
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
         pwa[t] = (long)(uint32_t)a.cst[kF_PWA + t * 64 + lane];
         pwb[t] = c4[kF_PWB / 4 + kq * 2 + t];
-        pwm[t] = c4[kF_PWC / 4 + (kq * 2 + t) * 3 + 0];
-        pwc1[t] = c4[kF_PWC / 4 + (kq * 2 + t) * 3 + 1];
-        pwe1[t] = pack_shifts(c4[kF_PWC / 4 + (kq * 2 + t) * 3 + 2] - 1);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) pwc[t][e] = rq64(pwc1[t][e]);
+        const v4i* pc = c4 + kF_PWC / 4 + (kq * 2 + t) * 3;
+        pwe1[t] = stage_quad(cq_lds[wave][kq][1 + t], pc[0], pc[1], pc[2], a.pw_lo, a.pw_hi);
     }
+    const v4i* my_cq = cq_lds[wave][kq][0];
 
     const int zfe4 = (a.zp_fe & 0xff) * 0x01010101;
     const int zst4 = (a.zp_st & 0xff) * 0x01010101;
+    const bool last_strip = sx == strips_x - 1;     // (wave-uniform) the strip whose last lane has the depthwise padding column
     const int zstrow = (a.zp_st & 0xff) * 0x00010101;
     const int fe_bytes = a.H0 * a.W0;
     const __amdgpu_buffer_rsrc_t rs_fe =
@@ -671,6 +696,7 @@ __global__ __launch_bounds__(256) void i8_front_strip_kernel(FrontStrip8Args a) 
         __builtin_amdgcn_make_buffer_rsrc(a.y + (size_t)chunk * a.OH * a.OW * 32, 0, a.OH * a.OW * 32, 0x00020000);
     const bool right_fe = 4 * ow + 4 >= a.W0;       // second dword of the row lies beyond the input: stem padding column
     const bool right_st = 2 * ow + 2 >= a.W0 / 2;   // third stem column lies beyond the stem map: depthwise padding column
+    const int pad_st = right_st ? 0x00ff0000 : 0;   // byte 2 of the window dwords in that lane (one v_bfi per dword, in the last strip only)
     const int voff_out = ow * 32 + 8 * kq;
     const int sr0 = 2 * oh0;                        // first stem row of the strip (depthwise: stride 2, no top padding)
     const int rows_needed = 2 * (nrows - 1) + 3;
@@ -681,12 +707,15 @@ __global__ __launch_bounds__(256) void i8_front_strip_kernel(FrontStrip8Args a) 
 
     // stem row sr0 + srel: lane (n, kq) reads input row sr - 1 + kq (the stem's top padding is row -1)
     auto fe_row = [&](int srel) { return sr0 + srel - 1 + kq; };
+    // Rows -1 and >= H0 need no clamp: their byte offset (as the unsigned number the range check sees) lies beyond the descriptor's
+    // H0 * W0 bytes, the load returns 0 and touches nothing, and stem_row() replaces the data by the zero point anyway.  The offset
+    // is the lane's own (VGPR) one, so the check does not depend on how a scalar offset enters it.
+    const int fe_off0 = (sr0 - 1 + kq) * a.W0 + 4 * ow;
+    // Rows past the strip's last one are requested as well (inside the chunk they are read and dropped, beyond it the range check
+    // answers): with every load unconditional the compiler counts the requests in flight and a row waits for ITS load only —
+    // behind a branch it waits for all of them (vmcnt(0)), the newest prefetch included.
     auto issue = [&](int slot, int srel) {
-        if (srel < rows_needed) {
-            int fr = fe_row(srel);
-            fr = fr < 0 ? 0 : (fr >= a.H0 ? a.H0 - 1 : fr);  // padding rows load a valid row, replaced below
-            raw[slot] = __builtin_bit_cast(v2i, __builtin_amdgcn_raw_buffer_load_b64(rs_fe, fr * a.W0 + 4 * ow, 0, 0));
-        }
+        raw[slot] = __builtin_bit_cast(v2i, __builtin_amdgcn_raw_buffer_load_b64(rs_fe, fe_off0 + srel * a.W0, 0, 0));
     };
     auto stem_row = [&](int slot, int srel, int ti) {
         if (srel < rows_needed && sr0 + srel < a.H0) {
@@ -695,46 +724,53 @@ __global__ __launch_bounds__(256) void i8_front_strip_kernel(FrontStrip8Args a) 
             const int A = ok ? raw[slot].x : zfe4;
             const int Bd = (ok && !right_fe) ? raw[slot].y : zfe4;
             const int x[3] = {A & 0x00ffffff, perm(Bd, A, 0x0c040302u), Bd & 0x00ffffff};
-            int pk[3];
+            // stem column j, channel e -> byte j of the window dword of channel e, written by the requantisation's own shift
 #pragma unroll
             for (int j = 0; j < 3; ++j) {
                 const v4i acc = __builtin_amdgcn_mfma_i32_16x16x32_i8(sta, (long)(uint32_t)x[j], stb, 0, 0, 0);
-                int qv[4];
+                int h[4];
 #pragma unroll
-                for (int e = 0; e < 4; ++e) qv[e] = med3(rq_hi(acc[e], stm[e], stc[e], ste1, e), a.st_lo, a.st_hi);
-                pk[j] = perm(perm(qv[3], qv[2], 0x0c0c0400u), perm(qv[1], qv[0], 0x0c0c0400u), 0x05040100u);
+                for (int e = 0; e < 4; ++e) h[e] = med3(rq_h(acc[e], stm[e], stc[e]), stlo[e], sthi[e]);
+                deposit_column(T[ti].c[0], h, ste1, j);
             }
-            if (right_st) pk[2] = zst4;
-            const int lo = perm(pk[1], pk[0], 0x05010400u);
-            const int hi = perm(pk[1], pk[0], 0x07030602u);
-            T[ti].c[0][0] = perm(pk[2], lo, 0x0c040100u);
-            T[ti].c[0][1] = perm(pk[2], lo, 0x0c050302u);
-            T[ti].c[0][2] = perm(pk[2], hi, 0x0c060100u);
-            T[ti].c[0][3] = perm(pk[2], hi, 0x0c070302u);
+            if (last_strip) {  // the padding column reads as the zero point
+#pragma unroll
+                for (int e = 0; e < 4; ++e) T[ti].c[0][e] = (T[ti].c[0][e] & ~pad_st) | (zst4 & pad_st);
+            }
         } else {
 #pragma unroll
             for (int e = 0; e < 4; ++e) T[ti].c[0][e] = zstrow;
         }
     };
     auto emit = [&](int i0, int i1, int i2, int oh) {
-        int qv[4];
+        asm volatile("" ::: "memory");  // (the per-channel constants are re-read from LDS every row, not pinned)
+        struct Quad { v4i m; long c[4]; int lo[4], hi[4]; };
+        auto quad = [&](int i) {
+            const v4i m = my_cq[5 * i], c01 = my_cq[5 * i + 1], c23 = my_cq[5 * i + 2], lo = my_cq[5 * i + 3], hi = my_cq[5 * i + 4];
+            return Quad{m, {__builtin_bit_cast(long, (v2i){c01.x, c01.y}), __builtin_bit_cast(long, (v2i){c01.z, c01.w}),
+                            __builtin_bit_cast(long, (v2i){c23.x, c23.y}), __builtin_bit_cast(long, (v2i){c23.z, c23.w})},
+                        {lo.x, lo.y, lo.z, lo.w}, {hi.x, hi.y, hi.z, hi.w}};
+        };
+        int h[4];
+        const Quad dq = quad(0);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             int acc = dot4_first(T[i0].c[0][e], dww[0][e], dwb[e]);
             acc = dot4(T[i1].c[0][e], dww[1][e], acc);
             acc = dot4(T[i2].c[0][e], dww[2][e], acc);
-            qv[e] = med3(rq_hi(acc, dwm[e], dwc[e], dwe1, e), a.dw_lo, a.dw_hi);
+            h[e] = rq_h(acc, dq.m[e], dq.c[e]);
         }
-        const long bf = (long)(uint32_t)perm(perm(qv[3], qv[2], 0x0c0c0400u), perm(qv[1], qv[0], 0x0c0c0400u), 0x05040100u);
-        int outw[2];
+        const long bf = (long)(uint32_t)clamp_deposit_quad(h, dq.lo, dq.hi, dwe1);  // the depthwise bytes ARE the pointwise B fragment
+        int ov[2][4];
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             const v4i acc = __builtin_amdgcn_mfma_i32_16x16x32_i8(pwa[t], bf, pwb[t], 0, 0, 0);
-            int ov[4];
+            const Quad pq = quad(1 + t);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) ov[e] = med3(rq_hi(acc[e], pwm[t][e], pwc[t][e], pwe1[t], e), a.pw_lo, a.pw_hi);
-            outw[t] = perm(perm(ov[3], ov[2], 0x0c0c0400u), perm(ov[1], ov[0], 0x0c0c0400u), 0x05040100u);
+            for (int e = 0; e < 4; ++e) ov[t][e] = med3(rq_h(acc[e], pq.m[e], pq.c[e]), pq.lo[e], pq.hi[e]);
         }
+        int outw[2];
+        deposit_two_quads(outw[0], outw[1], ov[0], ov[1], pwe1[0], pwe1[1]);
         __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(__attribute__((__vector_size__(2 * sizeof(int)))) int, (v2i){outw[0], outw[1]}), rs_out, voff_out, oh * a.OW * 32, 0);
     };
 

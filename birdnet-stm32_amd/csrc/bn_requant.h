@@ -117,6 +117,73 @@ __device__ __forceinline__ int rq_hi(int x, int m, long c, int e1_packed, int e)
     return ashr_byte(e1_packed, (int)(((long)x * (long)m + c) >> 32), e);
 }
 
+// h of rq_hi alone: hi32(x m + C)
+__device__ __forceinline__ int rq_h(int x, int m, long c) { return (int)(((long)x * (long)m + c) >> 32); }
+
+// The clamp IN FRONT of the shift: for every int32 h, e1 >= 0 and lo <= hi
+//     clamp(h >> e1, lo, hi) == clamp(h, lo << e1, ((hi + 1) << e1) - 1) >> e1
+// (the arithmetic shift is monotone and floors: h >> e1 >= lo iff h >= lo << e1, h >> e1 <= hi iff h < (hi + 1) << e1;
+// tests/test_front_strip_forms.py).  Shifts are 1 .. 22 (e1 <= 21), so the bounds stay inside +-2^28.  With the clamp done on h
+// against per-channel bounds the shift is the LAST instruction of a requantisation, and SDWA lets it write its low byte into
+// byte j of the register where the value is read next: no byte-packing permutes.
+__device__ __forceinline__ void shifted_bounds(int lo, int hi, int e1, int& blo, int& bhi) {
+    blo = lo << e1;
+    bhi = ((hi + 1) << e1) - 1;
+}
+// A partial (dst_sel: BYTE) write must not be followed directly by a vector-ALU instruction that reads the register (gfx940 and
+// later forward the wrong bytes; the compiler inserts the wait state for its own instructions but does not look into inline
+// assembly), and UNUSED_PRESERVE reads the destination.  So the deposits come in blocks whose neighbouring instructions write
+// DIFFERENT registers (or have an independent instruction between them), and a block whose last result a vector-ALU instruction
+// may read next ends in s_nop 0.
+#define BN_DEP(dst, src, J, E, MODE) \
+    "v_ashrrev_i32_sdwa " dst ", %[sh], " src " dst_sel:BYTE_" #J " dst_unused:UNUSED_" MODE " src0_sel:BYTE_" #E " src1_sel:DWORD\n\t"
+// column J of a byte-transposed quad: the low byte of (h[e] >> byte e of sh) -> byte J of t[e]; J = 0 starts the dwords (other bytes 0)
+#define BN_DEP_COLUMN(J, MODE, CONSTRAINT, TAIL)                                                                                  \
+    asm(BN_DEP("%[t0]", "%[h0]", J, 0, MODE) BN_DEP("%[t1]", "%[h1]", J, 1, MODE) BN_DEP("%[t2]", "%[h2]", J, 2, MODE)            \
+            BN_DEP("%[t3]", "%[h3]", J, 3, MODE) TAIL                                                                             \
+        : [t0] CONSTRAINT(t[0]), [t1] CONSTRAINT(t[1]), [t2] CONSTRAINT(t[2]), [t3] CONSTRAINT(t[3])                              \
+        : [sh] "v"(sh), [h0] "v"(h[0]), [h1] "v"(h[1]), [h2] "v"(h[2]), [h3] "v"(h[3]))
+__device__ __forceinline__ void deposit_column(int (&t)[4], const int (&h)[4], int sh, int j) {
+    switch (j) {  // j is a compile-time constant after unrolling
+        case 0: BN_DEP_COLUMN(0, "PAD", "=&v", ""); break;
+        case 1: BN_DEP_COLUMN(1, "PRESERVE", "+v", ""); break;
+        default: BN_DEP_COLUMN(2, "PRESERVE", "+v", "s_nop 0"); break;  // the window dwords are complete: any reader may follow
+    }
+}
+// the four channels of a quad into the four bytes of ONE dword, clamps included (they are the independent instructions between
+// two writes of the same register): byte e of the result = low byte of (med3(h[e], lo[e], hi[e]) >> byte e of sh)
+__device__ __forceinline__ int clamp_deposit_quad(int (&h)[4], const int (&lo)[4], const int (&hi)[4], int sh) {
+    int d;
+    asm("v_med3_i32 %[h0], %[h0], %[l0], %[u0]\n\t"
+        "v_med3_i32 %[h1], %[h1], %[l1], %[u1]\n\t"
+        BN_DEP("%[d]", "%[h0]", 0, 0, "PAD")
+        "v_med3_i32 %[h2], %[h2], %[l2], %[u2]\n\t"
+        BN_DEP("%[d]", "%[h1]", 1, 1, "PRESERVE")
+        "v_med3_i32 %[h3], %[h3], %[l3], %[u3]\n\t"
+        BN_DEP("%[d]", "%[h2]", 2, 2, "PRESERVE")
+        "s_nop 0\n\t"
+        BN_DEP("%[d]", "%[h3]", 3, 3, "PRESERVE")
+        "s_nop 0"
+        : [d] "=&v"(d), [h0] "+v"(h[0]), [h1] "+v"(h[1]), [h2] "+v"(h[2]), [h3] "+v"(h[3])
+        : [sh] "v"(sh), [l0] "v"(lo[0]), [l1] "v"(lo[1]), [l2] "v"(lo[2]), [l3] "v"(lo[3]), [u0] "v"(hi[0]), [u1] "v"(hi[1]), [u2] "v"(hi[2]),
+          [u3] "v"(hi[3]));
+    return d;
+}
+// two quads (already clamped) into two dwords, the writes alternating between them; the dwords go to a store (no vector-ALU reader)
+__device__ __forceinline__ void deposit_two_quads(int& d0, int& d1, const int (&a)[4], const int (&b)[4], int sha, int shb) {
+    asm("v_ashrrev_i32_sdwa %[d0], %[sa], %[a0] dst_sel:BYTE_0 dst_unused:UNUSED_PAD src0_sel:BYTE_0 src1_sel:DWORD\n\t"
+        "v_ashrrev_i32_sdwa %[d1], %[sb], %[b0] dst_sel:BYTE_0 dst_unused:UNUSED_PAD src0_sel:BYTE_0 src1_sel:DWORD\n\t"
+        "v_ashrrev_i32_sdwa %[d0], %[sa], %[a1] dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:BYTE_1 src1_sel:DWORD\n\t"
+        "v_ashrrev_i32_sdwa %[d1], %[sb], %[b1] dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:BYTE_1 src1_sel:DWORD\n\t"
+        "v_ashrrev_i32_sdwa %[d0], %[sa], %[a2] dst_sel:BYTE_2 dst_unused:UNUSED_PRESERVE src0_sel:BYTE_2 src1_sel:DWORD\n\t"
+        "v_ashrrev_i32_sdwa %[d1], %[sb], %[b2] dst_sel:BYTE_2 dst_unused:UNUSED_PRESERVE src0_sel:BYTE_2 src1_sel:DWORD\n\t"
+        "v_ashrrev_i32_sdwa %[d0], %[sa], %[a3] dst_sel:BYTE_3 dst_unused:UNUSED_PRESERVE src0_sel:BYTE_3 src1_sel:DWORD\n\t"
+        "v_ashrrev_i32_sdwa %[d1], %[sb], %[b3] dst_sel:BYTE_3 dst_unused:UNUSED_PRESERVE src0_sel:BYTE_3 src1_sel:DWORD"
+        : [d0] "=&v"(d0), [d1] "=&v"(d1)
+        : [sa] "v"(sha), [sb] "v"(shb), [a0] "v"(a[0]), [a1] "v"(a[1]), [a2] "v"(a[2]), [a3] "v"(a[3]), [b0] "v"(b[0]), [b1] "v"(b[1]),
+          [b2] "v"(b[2]), [b3] "v"(b[3]));
+}
+
 // int8 MEAN of `raw_sum` = sum of the P raw bytes of a channel.  Two published forms (oracle/int8_graph.py has both behind mean_form):
 //   integer (default): MultiplyByQuantizedMultiplier(raw_sum - zp_in P, mult, shift) with 1 / P folded into the multiplier (reduce.h);
 //   float (shift == kMeanFloatForm, mult = the float32 bits of s_in / s_out): TFLite's float-arithmetic QuantizedMeanOrSum —
