@@ -33,6 +33,7 @@ EXPORTS = (
     "bn_head_forward", "bn_probe_create", "bn_probe_destroy", "bn_probe_epoch", "bn_probe_loss", "bn_probe_get", "bn_probe_set",
     "bn_probe_sweep_create", "bn_probe_sweep_destroy", "bn_probe_sweep_epoch", "bn_probe_sweep_loss", "bn_probe_sweep_snapshot", "bn_probe_sweep_get",
     "bn_probe_set_loss", "bn_probe_epoch_weighted", "bn_probe_sweep_set_loss", "bn_probe_sweep_epoch_weighted",
+    "bn_probe_set_qat", "bn_probe_get_quantized", "bn_probe_scores",
     "bn_short_time_energy", "bn_activity_counts", "bn_search_inv_norms", "bn_search_topk", "bn_augment_inputs",
     "bn_kmeans_assign", "bn_kmeans_accumulate", "bn_kmeans_centroids",
     "bn_bootstrap_rejections", "bn_bootstrap_counts", "bn_bootstrap_ap", "bn_head_i8_forward", "bn_head_i8_pass_classes",
@@ -42,6 +43,7 @@ EMB_F32, EMB_I8 = 0, 1  # BN_EMB_* (include/birdnet_hip.h)
 PROBE_ACTIVATIONS = {"sigmoid": 0, "softmax": 1}  # BN_PROBE_ACT_*
 PROBE_OPTIMIZERS = {"adam": 0, "adamw": 1, "sgd": 2}  # BN_PROBE_OPT_*
 PROBE_LOSSES = {"auto": 0, "focal": 1}  # BN_PROBE_LOSS_* ("auto": the activation's cross-entropy)
+PROBE_QAT_WEIGHTS = {"off": 0, "per_class": 1, "per_tensor": 2}  # BN_PROBE_QAT_*
 PROBE_MAX_D, PROBE_MAX_C = 2048, 4096
 PROBE_SWEEP_MAX_TRIALS = 64  # BN_PROBE_SWEEP_MAX_TRIALS
 PROBE_SWEEP_CURRENT, PROBE_SWEEP_SNAPSHOT = 0, 1  # BN_PROBE_SWEEP_*
@@ -212,6 +214,9 @@ def load_library(path: str | None = None):
     lib.bn_probe_set_loss.argtypes = [c_void_p, c_int, c_float]
     lib.bn_probe_epoch_weighted.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]
     lib.bn_probe_sweep_set_loss.argtypes = [c_void_p, c_int, c_float]
+    lib.bn_probe_set_qat.argtypes = [c_void_p, c_int, c_int, c_float, c_int]
+    lib.bn_probe_get_quantized.argtypes = [c_void_p, c_void_p, c_void_p]
+    lib.bn_probe_scores.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]
     lib.bn_probe_sweep_epoch_weighted.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
     if lib.bn_version() != ABI_VERSION:
         raise RuntimeError(f"libbirdnet_hip ABI {lib.bn_version()} != binding ABI {ABI_VERSION}")

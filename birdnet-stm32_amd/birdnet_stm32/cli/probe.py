@@ -11,7 +11,8 @@ The backbone runs once over all files (``embed``'s device path), the head is tra
 ``--class_weights balanced`` weighs the rows by inverse class frequency and ``--loss focal`` trains on the focal loss; they combine with
 each other and with the plain fit, ``--tune`` and the augmented fit.  With ``--export_tflite`` on an INT8 ``.tflite`` backbone the head is
 also quantised and written into ``<output>.tflite`` (``conversion/head_export.py``), next to the labels and config: a model for
-``evaluate``, ``analyze`` and the board.
+``evaluate``, ``analyze`` and the board.  ``--qat_epochs N`` then fine-tunes the head for N epochs against that quantisation first
+(``training/probe_qat.py``) and writes whichever of the two heads scores better as INT8.
 """
 
 from __future__ import annotations
@@ -78,6 +79,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--per_tensor", action="store_true", help="With --export_tflite: one weight scale for the whole head instead of one per class")
     p.add_argument("--min_cosine_sim", type=float, default=0.95,
                    help="With --export_tflite: minimum mean cosine similarity of float and INT8 head scores; the export fails below (0 to disable)")
+    p.add_argument("--qat_epochs", type=int, default=0,
+                   help="With --export_tflite: fine-tune the trained head for N epochs with its weights and logits quantised as the export "
+                        "quantises them, then write whichever head (float-trained or fine-tuned) has the lower INT8 loss over the report rows; "
+                        "0 = off.  Label smoothing and augmentation are not applied in this phase")
+    p.add_argument("--qat_learning_rate", type=float, default=1e-4, help="With --qat_epochs: initial learning rate of the fine-tune (the reference's QAT default)")
     p.add_argument("--seed", type=int, default=42, help="Seed of the file shuffle, the initial weights, the batches and the dropout mask")
     p.add_argument("--max_batch", type=int, default=4096, help="Workspace size in chunks = inference slice of the device pipeline")
     p.add_argument("--device", type=int, default=0, help="MI355X index")
@@ -99,6 +105,9 @@ def main(argv=None, runner=None):
         from birdnet_stm32.training.linear_probe import check_export_args
 
         check_export_args(args)        # (and --export_tflite on a float backbone)
+        from birdnet_stm32.training.linear_probe import check_qat_args
+
+        check_qat_args(args)           # (and --qat_epochs without --export_tflite)
         return run_linear_probe(args, runner=runner)
     except (ValueError, FileNotFoundError) as exc:
         raise SystemExit(f"error: {exc}") from None

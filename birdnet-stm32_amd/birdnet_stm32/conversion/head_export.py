@@ -353,9 +353,10 @@ def float_logit_range(head, rows_i8, emb_scale: float, emb_zero_point: int, bloc
     return lo, hi
 
 
-def export_head_tflite(head, backbone_path: str, rows_i8, out_path: str, per_tensor: bool = False, ctx=None) -> dict:
+def export_head_tflite(head, backbone_path: str, rows_i8, out_path: str, per_tensor: bool = False, ctx=None, logit_range=None) -> dict:
     """Write ``head`` into a copy of the INT8 model at ``backbone_path`` as ``out_path``; ``rows_i8 [n, D]`` (int8 embedding bytes, CUDA
-    tensor or numpy) calibrate the logit tensor.  Returns ``{"qhead", "logit_range", "logit_scale", "logit_zero_point", "clipped_share",
+    tensor or numpy) calibrate the logit tensor.  ``logit_range = (lo, hi)`` replaces the range observed over ``rows_i8``: the range a
+    head fine-tuned by ``training.probe_qat.fit_probe_qat`` was trained against, so that the file's logit parameters are those.  Returns ``{"qhead", "logit_range", "logit_scale", "logit_zero_point", "clipped_share",
     "path", ...}``; ``clipped_share`` is the share of logit bytes at -128 or 127 over ``rows_i8`` (``bn_head_i8_forward``)."""
     import torch
 
@@ -371,7 +372,7 @@ def export_head_tflite(head, backbone_path: str, rows_i8, out_path: str, per_ten
     if rows_i8.dtype != torch.int8 or rows_i8.dim() != 2 or int(rows_i8.shape[0]) < 1:
         raise ValueError("rows_i8 must be a non-empty int8 matrix [n, D]")
     head.check_embedding_dim(rows_i8.shape[1])
-    lo, hi = float_logit_range(head, rows_i8, emb_scale, emb_zp)
+    lo, hi = float_logit_range(head, rows_i8, emb_scale, emb_zp) if logit_range is None else (float(logit_range[0]), float(logit_range[1]))
     qhead = quantize_head(head, emb_scale, emb_zp, lo, hi, per_tensor)
     raw = write_tflite(graft_head(backbone, qhead))
     with open(out_path, "wb") as fh:

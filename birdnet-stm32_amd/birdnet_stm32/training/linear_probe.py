@@ -1119,6 +1119,62 @@ def check_export_args(args) -> bool:
     return True
 
 
+def check_qat_args(args) -> int:
+    """``--qat_epochs`` / ``--qat_learning_rate`` of ``probe`` (absent in older namespaces: off): the epochs of the quantisation-aware
+    fine-tune in front of the export, 0 when off; refused without ``--export_tflite`` and with bad values, before anything is loaded."""
+    epochs = int(getattr(args, "qat_epochs", 0) or 0)
+    if epochs < 0:
+        raise ValueError(f"--qat_epochs must be >= 0 (0 = off), got {epochs}")
+    if epochs == 0:
+        return 0
+    if not getattr(args, "export_tflite", False):
+        raise ValueError("--qat_epochs needs --export_tflite: the fine-tune prepares the head for the INT8 export and is of no use without it")
+    lr = float(getattr(args, "qat_learning_rate", 1e-4))
+    if not (math.isfinite(lr) and lr > 0):
+        raise ValueError(f"--qat_learning_rate must be finite and > 0, got {lr}")
+    return epochs
+
+
+def qat_for_export(head, runner, X, Y, train_rows, val_rows, report_rows, per_tensor: bool, epochs: int, fit_kw: dict, loss_kw: dict):
+    """``probe --export_tflite --qat_epochs``: fine-tune ``head`` against the export's own quantisation (``training.probe_qat.fit_probe_qat``
+    on the rows ``train_rows`` of ``X`` / ``Y``, validated on ``val_rows``), quantise the float head and the fine-tuned one with the float
+    head's logit range over all of ``X``, and keep the one whose INT8 scores (``QuantizedHead.predict``) have the lower loss over
+    ``report_rows``.  Returns ``(the kept head, logit_range, the "qat" object of <output>_export.json)``."""
+    import torch
+
+    from birdnet_stm32.conversion.head_export import float_logit_range, quantize_head
+    from birdnet_stm32.conversion.validate import cosine_similarity
+    from birdnet_stm32.training.probe_qat import fit_probe_qat, qat_logit_codes
+
+    info = runner.embedding_info()
+    if info["dtype"] != "int8":
+        raise ValueError("--export_tflite needs an INT8 model: this one's embeddings are float32")
+    rows = embedding_bytes_device(X, info["scale"], info["zero_point"], runner.device)
+    lo, hi = float_logit_range(head, rows, info["scale"], info["zero_point"])
+    tuned = fit_probe_qat(runner, X[train_rows], Y[train_rows], X[val_rows] if val_rows.any() else None, Y[val_rows] if val_rows.any() else None,
+                          head=head, logit_range=(lo, hi), per_tensor=per_tensor, epochs=epochs, **fit_kw)
+    rep_rows = rows[torch.from_numpy(np.flatnonzero(report_rows)).to(rows.device)].contiguous()
+    X_rep, Y_rep = np.ascontiguousarray(X[report_rows]), Y[report_rows]
+    side = {}
+    for name, h in (("float", head), ("qat", tuned)):
+        with quantize_head(h, info["scale"], info["zero_point"], lo, hi, per_tensor) as qh:
+            P_q, logit = qh.predict_device(rep_rows, runner.ctx, return_logit_bytes=True)
+        P_q, P_f = P_q.cpu().numpy(), h.predict(X_rep, runner.ctx)
+        side[name] = {"loss_int8": float(probe_loss(P_q, Y_rep, h.activation, **loss_kw)), "loss_float": float(probe_loss(P_f, Y_rep, h.activation, **loss_kw)),
+                      "cosine_mean": float(np.mean([cosine_similarity(u, v) for u, v in zip(P_f.astype(np.float64), P_q.astype(np.float64))]))}
+        h.close()
+        side[name + "_logit"] = logit.cpu().numpy()
+    codes = qat_logit_codes(runner.ctx, tuned, X_rep, (lo, hi), per_tensor)
+    kept = "qat" if side["qat"]["loss_int8"] < side["float"]["loss_int8"] else "float"
+    report = {"epochs": tuned.history["qat"]["epochs"], "learning_rate": float(fit_kw["learning_rate"]), "logit_range": [lo, hi],
+              "logit_scale": tuned.history["qat"]["logit_scale"], "logit_zero_point": tuned.history["qat"]["logit_zero_point"],
+              "float": side["float"], "qat": side["qat"], "kept": kept, "code_agreement": float(np.mean(codes == side["qat_logit"]))}
+    print(f"[probe] QAT fine-tune, {report['epochs']} epochs at lr {report['learning_rate']:g}: INT8 loss {side['float']['loss_int8']:.4f} (float head) vs "
+          f"{side['qat']['loss_int8']:.4f} (fine-tuned), cosine {side['float']['cosine_mean']:.6f} vs {side['qat']['cosine_mean']:.6f}; the {kept} head is "
+          f"written; {100 * report['code_agreement']:.2f} % of the fine-tune's logit codes are the INT8 head's bytes")
+    return (tuned if kept == "qat" else head), (lo, hi), report
+
+
 def embedding_bytes_device(X, scale: float, zero_point: int, device):
     """The int8 bytes behind float32 embeddings ``X [n, D]`` of an INT8 runner, ``round(x / scale) + zero_point``, as a CUDA int8 tensor; the
     round trip ``(q - zero_point) * scale == x`` is asserted on the device for every element."""
@@ -1133,10 +1189,11 @@ def embedding_bytes_device(X, scale: float, zero_point: int, device):
 
 
 def export_probe_tflite(head, runner, model_path: str, X, Y, report_rows, out: dict, activation: str, per_tensor: bool, min_cosine_sim: float,
-                        loss_kw: dict) -> dict:
+                        loss_kw: dict, logit_range=None, qat: dict | None = None) -> dict:
     """``probe --export_tflite``: ``head`` into ``out["tflite"]`` (``conversion.head_export.export_head_tflite``, calibrated on all rows
     ``X``), the report of float head against INT8 head (``bn_head_i8_forward``) over ``report_rows`` into ``out["export"]``; raises below
-    ``min_cosine_sim`` as ``convert`` does."""
+    ``min_cosine_sim`` as ``convert`` does.  ``logit_range`` / ``qat``: what ``qat_for_export`` returned for ``head``; the range then replaces
+    the observed one and the report gains the ``"qat"`` object."""
     from birdnet_stm32.conversion.head_export import export_head_tflite
     from birdnet_stm32.conversion.validate import cosine_similarity, pearson_correlation
 
@@ -1144,7 +1201,7 @@ def export_probe_tflite(head, runner, model_path: str, X, Y, report_rows, out: d
     if info["dtype"] != "int8":
         raise ValueError("--export_tflite needs an INT8 model: this one's embeddings are float32")
     rows = embedding_bytes_device(X, info["scale"], info["zero_point"], runner.device)
-    rep = export_head_tflite(head, model_path, rows, out["tflite"], per_tensor=per_tensor, ctx=runner.ctx)
+    rep = export_head_tflite(head, model_path, rows, out["tflite"], per_tensor=per_tensor, ctx=runner.ctx, logit_range=logit_range)
     qhead = rep.pop("qhead")
     import torch
 
@@ -1161,6 +1218,8 @@ def export_probe_tflite(head, runner, model_path: str, X, Y, report_rows, out: d
                 "loss_float": float(probe_loss(P_f, Y[report_rows], activation, **loss_kw)),
                 "loss_int8": float(probe_loss(P_q, Y[report_rows], activation, **loss_kw)),
                 "report_clipped_share": float(np.mean((logit == -128) | (logit == 127))), "min_cosine_sim": float(min_cosine_sim)})
+    if qat is not None:
+        rep["qat"] = qat
     with open(out["export"], "w") as fh:
         json.dump(rep, fh, indent=1)
     print(f"[probe] exported {out['tflite']} ({rep['bytes']} bytes, {rep['classes']} classes, {'per-tensor' if per_tensor else 'per-channel'} weights): logits "
@@ -1177,7 +1236,8 @@ def run_linear_probe(args, runner=None) -> ProbeHead:
     ``<output>.npz``, ``<output>_labels.txt``, ``<output>_model_config.json`` and ``<output>_history.csv``.  With ``args.tune``:
     ``training.tune.sample_trials`` -> ``fit_probe_sweep``; the files are the winning trial's, ``<output>_tune.json`` lists all trials.
     With ``args.export_tflite`` (INT8 ``.tflite`` backbones): the written head also goes into ``<output>.tflite``, an ordinary model next
-    to the labels and config written here, with ``<output>_export.json`` (``export_probe_tflite``).
+    to the labels and config written here, with ``<output>_export.json`` (``export_probe_tflite``); with ``args.qat_epochs`` the head is
+    first fine-tuned against the export's quantisation and the better of the two heads as INT8 is the one written (``qat_for_export``).
 
     For long-tailed folders (``imbalance_from_args``), in the reference's order: ``--upsample_ratio`` first repeats training files of the
     small classes (``upsample_multiplicity``; the validation split is never upsampled, and every distinct file is embedded once: the
@@ -1198,6 +1258,7 @@ def run_linear_probe(args, runner=None) -> ProbeHead:
     imb = imbalance_from_args(args)
     check_tune_args(args)
     export = check_export_args(args)
+    qat_epochs = check_qat_args(args)
     label_smoothing = _check_label_smoothing(getattr(args, "label_smoothing", 0.0))
     if augment is not None and label_smoothing > 0:
         raise ValueError("--label_smoothing does not combine with --mixup_probability or --spec_augment")
@@ -1294,6 +1355,16 @@ def run_linear_probe(args, runner=None) -> ProbeHead:
         head = fit_probe_augmented(runner, inputs, Y[tr], emb.embeddings[va] if va.any() else None, Y[va] if va.any() else None, augment=augment,
                                    input_shape=runner.input_shape(), **fit_kw, **imb_kw)
         del train_inputs, inputs
+    qat_range = qat_report = None
+    if export and qat_epochs:   # after whichever fit was asked for; the head with the lower INT8 loss is the one written below
+        kept = tr | va
+        qat_kw = {**{k: fit_kw[k] for k in ("batch_size", "optimizer", "weight_decay", "clipnorm", "dropout", "patience", "seed")},
+                  "learning_rate": float(getattr(args, "qat_learning_rate", 1e-4)), **imb_kw}
+        if tuned is not None:   # the winner's own settings, where the search covers them
+            qat_kw.update({k: tuned["trials"][tuned["best_trial"]]["params"][k] for k in ("optimizer", "weight_decay", "clipnorm", "dropout")})
+        head, qat_range, qat_report = qat_for_export(head, runner, emb.embeddings[kept], Y[kept], tr[kept], va[kept], (va if va.any() else tr)[kept],
+                                                     bool(getattr(args, "per_tensor", False)), qat_epochs, qat_kw,
+                                                     dict(loss=imb["loss"], focal_gamma=imb["focal_gamma"]))
     t_fit = time.perf_counter() - t0
     out = probe_output_paths(args.output)
     os.makedirs(os.path.dirname(os.path.abspath(out["head"])), exist_ok=True)
@@ -1313,7 +1384,7 @@ def run_linear_probe(args, runner=None) -> ProbeHead:
         kept = tr | va
         export_probe_tflite(head, runner, args.model_path, emb.embeddings[kept], Y[kept], (va if va.any() else tr)[kept], out, args.activation,
                             bool(getattr(args, "per_tensor", False)), float(getattr(args, "min_cosine_sim", 0.95)),
-                            dict(loss=imb["loss"], focal_gamma=imb["focal_gamma"]))
+                            dict(loss=imb["loss"], focal_gamma=imb["focal_gamma"]), logit_range=qat_range, qat=qat_report)
     head.history["seconds"] = {"embed": t_embed, "fit": t_fit}
     val = head.history["val_loss"]
     aug_s = head.history.get("augment_seconds")

@@ -1,8 +1,12 @@
 """Weight fake-quantisation used by the reference's QAT fine-tuning (reference: birdnet_stm32/training/qat.py:30-61).
 
-Only ``fake_quantize_weights`` is mirrored: it is pure array arithmetic (asymmetric min/max grid of ``2**num_bits - 1``
-steps per output channel, quantise then dequantise) and serves the conversion checks as the "what survives 8 bits"
-reference point.  The Keras callback around it belongs to training, which is out of scope here.
+``fake_quantize_weights`` mirrors the reference's function: pure array arithmetic (asymmetric min/max grid of ``2**num_bits - 1``
+steps per output channel, quantise then dequantise), which serves the conversion checks as the "what survives 8 bits" reference point.
+
+The Keras callback around it fine-tunes the whole model.  Here the backbone is frozen and already INT8, so the part of it that applies
+is the fine-tune of the probe head, and that lives in ``training/probe_qat.py`` (``fit_probe_qat``, ``probe --export_tflite
+--qat_epochs``).  It does not use the grid of this file: the head's forward sees the symmetric int8 weights the exporter
+writes (``conversion.quantize.quantize_weights``) and the logit grid of the exported tensor, so that the trained weights are the exported ones.
 """
 
 from __future__ import annotations

@@ -462,6 +462,16 @@ void launch_probe_dw(const ProbeDwArgs& a, int row_groups, hipStream_t s);
 void launch_probe_reduce(float* partial, int E, int groups, float* ss_part, hipStream_t s);
 void launch_probe_update(const ProbeUpdateArgs& a, hipStream_t s);
 void launch_probe_loss_sum(const float* part, long n, float scale, float* out, hipStream_t s);
+// Quantisation-aware fine-tuning of one head (bn_probe_set_qat).  The logits on the exported logit tensor's grid: the
+// forward kernel's EXT = 2 instantiations, which take this where a sweep's take ProbeSweepArgs (a sweep has no QAT).
+struct ProbeQatArgs {
+    float s_out, z_out;    // the logit tensor's scale and its zero point as a float (an integer in -128..127)
+    int8_t* codes;         // mode 2: [n, C] the clamped codes, or null
+};
+bool launch_probe_fwd_qat(const ProbeFwdArgs& a, const ProbeQatArgs& q, int mode, hipStream_t s);   // false: the LDS request was refused
+// The weights as quantize_weights will write them: Pq [(D + 1) * C] from the shadow parameters P (row D, the bias, copied), through
+// amax [C] = max_k |P[k, c]|; per_tensor: one scale from the largest amax
+void launch_probe_qat_weights(const float* P, float* Pq, float* amax, int D, int C, bool per_tensor, hipStream_t s);
 
 // bn_probe_sweep.hip: T heads trained in lock-step (bn_probe_sweep_*).  The kernels are those of bn_probe.hip with the trial as one more
 // grid axis; what differs per trial is read from a table in device memory, and a trial whose byte of `active` is 0 returns at once.

@@ -9,6 +9,8 @@
 //                       partial per group.  The bias is row D of the parameter matrix (a feature that is always 1): db falls out of the same product.
 //   probe_reduce_kernel (only with more than one row group) adds the partials in group order.
 //   probe_update_kernel adds the per-workgroup sums of squares and loss partials in a fixed order, clips by global norm, applies the optimiser.
+// With bn_probe_set_qat two more launches stand in front of the forward, probe_qat_amax_kernel and probe_qat_quant_kernel
+// (the weights as the INT8 export will hold them, into a second buffer the forward reads), and the forward is its EXT = 2 instantiation.
 // No floating-point atomics anywhere: the map from tiles to workgroups depends on the shapes only and every sum has a fixed order, so the
 // same inputs and seed give the same bits.
 //
@@ -39,6 +41,75 @@ void preload_probe() {
 
 void launch_probe_loss_sum(const float* part, long n, float scale, float* out, hipStream_t s) {
     probe_launch_loss_sum<false>(part, n, scale, out, ProbeNoSweep{}, s);
+}
+
+// ---------------------------------------------------------------------------------- quantisation-aware fine-tuning
+// Behind the kernels above in the code object, which keep their places: the forward kernel's EXT = 2 family, and the two kernels that turn
+// the shadow parameters into the weights such a forward reads (templates, because the compiler emits a plain kernel in front of every
+// instantiation of the file).
+bool launch_probe_fwd_qat(const ProbeFwdArgs& a, const ProbeQatArgs& q, int mode, hipStream_t s) {
+    const ProbeFwdGeom g = probe_fwd_geom(a, 1u);
+    if (g.per_wave <= 1) return probe_launch_fwd_qat_nt<1>(a, q, mode, g, s);
+    if (g.per_wave <= 2) return probe_launch_fwd_qat_nt<2>(a, q, mode, g, s);
+    if (g.per_wave <= 4) return probe_launch_fwd_qat_nt<4>(a, q, mode, g, s);
+    return probe_launch_fwd_qat_nt<8>(a, q, mode, g, s);
+}
+
+constexpr int kAmaxCols = 64;                     // a workgroup of the first kernel: 64 columns x 16 row slices, one wave per slice
+constexpr int kQuantCols = 256, kQuantRows = 8;   // ... of the second: 256 columns x 8 rows, one thread per column
+
+// amax[c] = max_k |P[k, c]| over the D weight rows; a wave reads 64 consecutive floats of one row
+template <int SLICES>   // row slices = waves
+__global__ __launch_bounds__(kAmaxCols * SLICES) void probe_qat_amax_kernel(const float* __restrict__ P, int D, int C, float* __restrict__ amax) {
+    __shared__ float red[SLICES][kAmaxCols];
+    const int cx = threadIdx.x, ky = threadIdx.y, c = blockIdx.x * kAmaxCols + cx;
+    float m = 0.0f;
+    if (c < C)
+        for (int k = ky; k < D; k += SLICES) m = fmaxf(m, fabsf(P[(size_t)k * C + c]));
+    red[ky][cx] = m;
+    __syncthreads();
+    if (ky == 0 && c < C) {
+        for (int j = 1; j < SLICES; ++j) m = fmaxf(m, red[j][cx]);
+        amax[c] = m;
+    }
+}
+
+// conversion/quantize.py: quantize_weights in float64, element for element: s = max(amax_c, 5e-7) / 127, q = clip(rint(w / s), -127, 127),
+// Pq = float(q) * float(s) as a float32 product, which is q.astype(float32) * s_w bit for bit (q goes through an integer: no -0).
+// per_tensor: every class takes the largest amax, which every workgroup finds for itself (a maximum has no order).  Row D, the bias, is copied.
+template <bool PER_TENSOR>
+__global__ __launch_bounds__(kQuantCols) void probe_qat_quant_kernel(const float* __restrict__ P, float* __restrict__ Pq, const float* __restrict__ amax,
+                                                                     int D, int C) {
+    __shared__ float red[kQuantCols];
+    const int t = threadIdx.x, c = blockIdx.x * kQuantCols + t;
+    float am = c < C ? amax[c] : 0.0f;
+    if constexpr (PER_TENSOR) {
+        float v = 0.0f;
+        for (int i = t; i < C; i += kQuantCols) v = fmaxf(v, amax[i]);
+        red[t] = v;
+        __syncthreads();
+        for (int h = kQuantCols / 2; h > 0; h >>= 1) {
+            if (t < h) red[t] = fmaxf(red[t], red[t + h]);
+            __syncthreads();
+        }
+        am = red[0];
+    }
+    if (c >= C) return;
+    const double s = fmax((double)am, 5e-7) / 127.0;
+    const float sf = (float)s;
+    const int k0 = blockIdx.y * kQuantRows, k1 = min(k0 + kQuantRows, D + 1);
+    for (int k = k0; k < k1; ++k) {
+        float v = P[(size_t)k * C + c];
+        if (k < D) v = (float)(int)fmin(fmax(rint((double)v / s), -127.0), 127.0) * sf;
+        Pq[(size_t)k * C + c] = v;
+    }
+}
+
+void launch_probe_qat_weights(const float* P, float* Pq, float* amax, int D, int C, bool per_tensor, hipStream_t s) {
+    hipLaunchKernelGGL(probe_qat_amax_kernel<16>, dim3((unsigned)((C + kAmaxCols - 1) / kAmaxCols)), dim3(kAmaxCols, 16), 0, s, P, D, C, amax);
+    const dim3 grid((unsigned)((C + kQuantCols - 1) / kQuantCols), (unsigned)((D + 1 + kQuantRows - 1) / kQuantRows));
+    if (per_tensor) hipLaunchKernelGGL(probe_qat_quant_kernel<true>, grid, dim3(kQuantCols), 0, s, P, Pq, amax, D, C);
+    else hipLaunchKernelGGL(probe_qat_quant_kernel<false>, grid, dim3(kQuantCols), 0, s, P, Pq, amax, D, C);
 }
 
 }  // namespace bn

@@ -42,6 +42,10 @@ struct bn_probe : bn::ProbeHandle {
     int opt = 0;
     float lr = 0, wd = 0, clip = 0, drop = 0;
     float *d_params = nullptr, *d_m = nullptr, *d_v = nullptr;   // [(D + 1) * C] each: W, then the bias as row D
+    // bn_probe_set_qat: the forward reads d_wq, made from d_params in front of it, and / or puts the logits on a grid
+    int qat_weights = 0, qat_logits = 0;                         // 0 off, 1 per class, 2 per tensor; 0 / 1
+    float qat_s_out = 0; int qat_z_out = 0;
+    float* d_wq = nullptr;                                       // [(D + 1) * C] the fake-quantised parameters, then amax [C]
 };
 
 struct bn_probe_sweep : bn::ProbeHandle {
@@ -170,6 +174,19 @@ bn::ProbeSweepArgs sweep_args(const bn_probe_sweep* p, const uint8_t* d_active, 
     return w;
 }
 
+// What the next forward of `p` reads as its parameters: the shadow parameters themselves, or their fake-quantised copy, made here
+const float* probe_forward_params(const bn_probe* p, hipStream_t s) {
+    if (!p->qat_weights) return p->d_params;
+    bn::launch_probe_qat_weights(p->d_params, p->d_wq, p->d_wq + (size_t)(p->D + 1) * p->C, p->D, p->C, p->qat_weights == 2, s);
+    return p->d_wq;
+}
+
+// The forward of a single head under its QAT setting
+bool probe_forward(const bn_probe* p, const bn::ProbeFwdArgs& f, int mode, int8_t* d_codes, hipStream_t s) {
+    if (!p->qat_logits) return bn::launch_probe_fwd(f, mode, s);
+    return bn::launch_probe_fwd_qat(f, bn::ProbeQatArgs{p->qat_s_out, (float)p->qat_z_out, d_codes}, mode, s);
+}
+
 // One epoch of a single fit (SWEEP = false: d_step_sizes and d_active are null) or of every active trial of a sweep.  A step is three
 // launches, four when the batch is split into row groups; at small batches it is launch-bound, so nothing in the loop allocates or
 // goes through a pointer to a function: SWEEP is a constant of the instantiation.
@@ -199,7 +216,7 @@ int probe_epoch(ProbeOf<SWEEP>* p, const float* d_X, const float* d_Y, const flo
     if constexpr (SWEEP) {
         w = sweep_args(p, d_active, G_stride, partial_stride, loss_stride);
     } else {
-        f.W = p->d_params; f.b = p->d_params + (size_t)D * C; f.out = p->d_G; f.loss_part = p->d_loss_part;
+        f.out = p->d_G; f.loss_part = p->d_loss_part;
         probe_dropout(p->drop, &f.drop_thresh, &f.drop_scale);
         g.G = p->d_G; g.partial = p->d_partial; g.ss_part = p->d_ss; g.drop_thresh = f.drop_thresh; g.drop_scale = f.drop_scale;
         u.params = p->d_params; u.m = p->d_m; u.v = p->d_v; u.grad = p->d_partial; u.ss_part = p->d_ss; u.loss_part = p->d_loss_part;
@@ -213,7 +230,12 @@ int probe_epoch(ProbeOf<SWEEP>* p, const float* d_X, const float* d_Y, const flo
         f.step = g.step = (uint32_t)p->t;
         f.g_scale = u.loss_scale = probe_mean_scale(softmax, B, C);
         bool fits;
-        if constexpr (SWEEP) fits = bn::launch_probe_sweep_fwd(f, w, 0, s); else fits = bn::launch_probe_fwd(f, 0, s);
+        if constexpr (SWEEP) {
+            fits = bn::launch_probe_sweep_fwd(f, w, 0, s);
+        } else {   // (the gradient and the update act on the shadow parameters)
+            f.W = probe_forward_params(p, s); f.b = f.W + (size_t)D * C;
+            fits = probe_forward(p, f, 0, nullptr, s);
+        }
         if (!fits) return fail(BN_ERR_DEVICE, "the probe forward kernel's LDS request was refused");
         int groups;
         probe_groups(B, D, C, &groups, &g.rows_per_group);   // from (B, D, C) alone: a sweep's trials split as a single fit does
@@ -257,10 +279,10 @@ int probe_loss(ProbeOf<SWEEP>* p, const float* d_X, const float* d_Y, int64_t n,
     if constexpr (SWEEP) {
         w = sweep_args(p, d_active, 0, 0, (int)parts);
     } else {
-        f.W = p->d_params; f.b = p->d_params + (size_t)p->D * p->C; f.loss_part = p->d_loss_part;
+        f.W = probe_forward_params(p, s); f.b = f.W + (size_t)p->D * p->C; f.loss_part = p->d_loss_part;
     }
     bool fits;
-    if constexpr (SWEEP) fits = bn::launch_probe_sweep_fwd(f, w, 1, s); else fits = bn::launch_probe_fwd(f, 1, s);
+    if constexpr (SWEEP) fits = bn::launch_probe_sweep_fwd(f, w, 1, s); else fits = probe_forward(p, f, 1, nullptr, s);
     if (!fits) return fail(BN_ERR_DEVICE, "the probe forward kernel's LDS request was refused");
     if constexpr (SWEEP) bn::launch_probe_sweep_loss_sum(w, (long)parts, scale, d_out, s); else bn::launch_probe_loss_sum(p->d_loss_part, (long)parts, scale, d_out, s);
     HIP_TRY(hipGetLastError());
@@ -359,7 +381,7 @@ int bn_probe_create(bn_ctx* ctx, int D, int C, int activation, int optimizer, fl
 
 void bn_probe_destroy(bn_probe* p) {
     if (!p) return;
-    probe_free(p, {p->d_params});
+    probe_free(p, {p->d_params, p->d_wq});
     delete p;
 }
 
@@ -388,6 +410,48 @@ int bn_probe_get(bn_probe* p, float* d_W, float* d_b, void* stream) {
 int bn_probe_set(bn_probe* p, const float* d_W, const float* d_b, void* stream) {
     if (int rc = probe_call_check(p, "probe", d_W && d_b)) return rc;
     HIP_TRY(probe_copy_head(p->d_params, p->d_params + (size_t)p->D * p->C, d_W, d_b, p->D, p->C, (hipStream_t)stream));
+    return BN_OK;
+}
+
+// Quantisation-aware fine-tuning
+int bn_probe_set_qat(bn_probe* p, int weight_mode, int quantize_logits, float s_out, int z_out) {
+    if (!p) return fail(BN_ERR_ARG, "null probe");
+    if (weight_mode < BN_PROBE_QAT_OFF || weight_mode > BN_PROBE_QAT_PER_TENSOR) return fail(BN_ERR_ARG, "unknown QAT weight mode %d", weight_mode);
+    if (quantize_logits) {
+        if (!std::isfinite(s_out) || !(s_out > 0.0f)) return fail(BN_ERR_ARG, "the logit scale %g must be finite and > 0", (double)s_out);
+        if (z_out < -128 || z_out > 127) return fail(BN_ERR_ARG, "zero point %d outside -128..127", z_out);
+    }
+    if (weight_mode && !p->d_wq) {
+        if (int rc = check_device(p->ctx)) return rc;
+        if (hipMalloc(&p->d_wq, ((size_t)(p->D + 1) * p->C + p->C) * sizeof(float)) != hipSuccess) {
+            (void)hipGetLastError();
+            p->d_wq = nullptr;
+            return fail(BN_ERR_NOMEM, "hipMalloc of the probe's fake-quantised parameters failed");
+        }
+    }
+    p->qat_weights = weight_mode; p->qat_logits = quantize_logits ? 1 : 0;
+    p->qat_s_out = quantize_logits ? s_out : 0.0f; p->qat_z_out = quantize_logits ? z_out : 0;
+    return BN_OK;
+}
+
+int bn_probe_get_quantized(bn_probe* p, float* d_Wq, void* stream) {
+    if (int rc = probe_call_check(p, "probe", d_Wq)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipMemcpyAsync(d_Wq, probe_forward_params(p, s), (size_t)p->D * p->C * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipGetLastError());
+    return BN_OK;
+}
+
+int bn_probe_scores(bn_probe* p, const float* d_X, int64_t n, float* d_scores, int8_t* d_codes, void* stream) {
+    if (int rc = probe_call_check(p, "probe", d_X && d_scores)) return rc;
+    if (int rc = probe_rows_check(n)) return rc;
+    if (d_codes && !p->qat_logits) return fail(BN_ERR_ARG, "d_codes needs the logits quantised (bn_probe_set_qat)");
+    hipStream_t s = (hipStream_t)stream;
+    bn::ProbeFwdArgs f{};
+    f.X = d_X; f.out = d_scores; f.n = n; f.D = p->D; f.C = p->C; f.softmax = p->act == BN_PROBE_ACT_SOFTMAX;
+    f.W = probe_forward_params(p, s); f.b = f.W + (size_t)p->D * p->C;
+    if (!probe_forward(p, f, 2, d_codes, s)) return fail(BN_ERR_DEVICE, "the probe forward kernel's LDS request was refused");
+    HIP_TRY(hipGetLastError());
     return BN_OK;
 }
 

@@ -22,6 +22,14 @@
 // loss kind and no weights.  Written in probe_loss_elem with a rounding after every operation, so no instantiation fuses what another
 // does not.  EXT = 0 is the kernel without any of this: the statements, and the bits, of a fit that asks for neither.
 // training/linear_probe.py: probe_loss / probe_loss_gradient are the same in numpy.
+//
+// Quantisation-aware fine-tuning (EXT = 2 of the forward kernel; single fit only): the logits on the grid the exported
+// logit tensor will have, between the bias add and the activation, in float32 with a rounding after every operation and an IEEE division:
+//     t  = z / s_out;   k = rintf(t) + z_out;   kc = min(max(k, -128), 127);   zq = (kc - z_out) * s_out;   pass = (k == kc)
+// The activation, softmax's max / sum passes and the loss take zq; the loss statements are EXT = 1's, so the focal loss and row weights
+// compose.  Mode 0 writes G where `pass` holds and 0 elsewhere (the straight-through estimator with TensorFlow's clamp mask); mode 2 also
+// writes kc.  training/probe_qat.py: fake_quantize_logits is the same in numpy.  The weights such a forward reads are made by the two
+// kernels at the end of bn_probe.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -36,6 +44,9 @@ namespace bn {
 struct ProbeNoSweep {};
 template <bool SWEEP>
 using ProbeSweepOf = std::conditional_t<SWEEP, ProbeSweepArgs, ProbeNoSweep>;   // the second kernel argument
+// ... of the forward kernel: EXT = 2 (single fit only) takes the logit grid there, so every other instantiation keeps its signature
+template <bool SWEEP, int EXT>
+using ProbeFwdExtraOf = std::conditional_t<EXT == 2, ProbeQatArgs, ProbeSweepOf<SWEEP>>;
 
 
 constexpr int kRows = 16;       // batch rows per forward workgroup (one MFMA tile)
@@ -116,6 +127,20 @@ __device__ __forceinline__ void probe_loss_elem(float p, float pc, float y, bool
     }
 }
 
+// EXT = 2: the logit on the int8 grid (s_out, z_out), in two halves (see the head of the file).  The accumulators keep k, the code
+// before the clamps, which is all three results in one register: kc = probe_clamp_code(k), zq = probe_dequant(kc), pass = (k == kc).
+__device__ __forceinline__ float probe_quant_code(float z, float s_out, float z_out) {
+#pragma clang fp contract(off)
+    const float t = z / s_out;
+    return rintf(t) + z_out;
+}
+__device__ __forceinline__ float probe_clamp_code(float k) { return fminf(fmaxf(k, -128.0f), 127.0f); }
+__device__ __forceinline__ float probe_dequant(float kc, float s_out, float z_out) {
+#pragma clang fp contract(off)
+    const float d = kc - z_out;
+    return d * s_out;
+}
+
 // host: does this launch need the EXT = 1 kernel?  Row weights count in mode 0 only, the focal loss in modes 0 and 1.
 inline bool probe_fwd_ext(const ProbeFwdArgs& a, int mode) {
     return mode != 2 && (a.loss_kind == BN_PROBE_LOSS_FOCAL || (mode == 0 && a.row_weight != nullptr));
@@ -128,8 +153,10 @@ __device__ __forceinline__ bool sweep_idle(const ProbeSweepArgs& w, int t) { ret
 // MODE 0: training (G and the loss partial), 1: loss partial only, 2: scores.  NT: column tiles per wave (tile t of wave w is w + t * waves).
 // SWEEP: blockIdx.y is the trial; mode 0 takes its dropout threshold and label smoothing from the table, mode 1 has neither.
 // EXT 1 (modes 0 and 1): the loss kind and, in mode 0, the row weights of ProbeFwdArgs; 0: neither, the plain cross-entropy statements.
+// EXT 2 (all modes, no sweep): EXT 1 on fake-quantised logits; `w` is then the logit grid.
 template <int NT, int MODE, int EXT, bool SWEEP>
-__global__ __launch_bounds__(1024) void probe_fwd_kernel(ProbeFwdArgs a, ProbeSweepOf<SWEEP> w) {
+__global__ __launch_bounds__(1024) void probe_fwd_kernel(ProbeFwdArgs a, ProbeFwdExtraOf<SWEEP, EXT> w) {
+    static_assert(!(SWEEP && EXT == 2), "a sweep has no QAT instantiation");
     const float *W = a.W, *bias = a.b;
     float *out = a.out, *loss_part = a.loss_part;
     uint32_t drop_thresh = a.drop_thresh;
@@ -206,6 +233,17 @@ __global__ __launch_bounds__(1024) void probe_fwd_kernel(ProbeFwdArgs a, ProbeSw
 #pragma unroll
             for (int r = 0; r < 4; ++r) acc[t][r] += bv;
         }
+        if constexpr (EXT == 2) {   // from here on acc holds the codes k; `logit` below turns one into zq
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) acc[t][r] = probe_quant_code(acc[t][r], w.s_out, w.z_out);
+        }
+    };
+    // the logit the activation takes: the accumulator itself, or (EXT 2) the quantised logit of the code it holds
+    auto logit = [&](float v) {
+        if constexpr (EXT == 2) return probe_dequant(probe_clamp_code(v), w.s_out, w.z_out);
+        else return v;
     };
 
     // softmax: row maximum m and sum s of exp(z - m) over all columns first — pass by pass in the online form (with one pass that is
@@ -221,7 +259,7 @@ __global__ __launch_bounds__(1024) void probe_fwd_kernel(ProbeFwdArgs a, ProbeSw
                 float v = -INFINITY;
 #pragma unroll
                 for (int t = 0; t < NT; ++t)
-                    if (okc[t]) v = fmaxf(v, acc[t][r]);
+                    if (okc[t]) v = fmaxf(v, logit(acc[t][r]));
                 mn[r] = group16_max(v);
             }
             __syncthreads();
@@ -240,7 +278,7 @@ __global__ __launch_bounds__(1024) void probe_fwd_kernel(ProbeFwdArgs a, ProbeSw
                 float v = 0.0f;
 #pragma unroll
                 for (int t = 0; t < NT; ++t)
-                    if (okc[t]) v += expf(acc[t][r] - mn[r]);
+                    if (okc[t]) v += expf(logit(acc[t][r]) - mn[r]);
                 sn[r] = group16_sum(v);
             }
             __syncthreads();
@@ -281,9 +319,12 @@ __global__ __launch_bounds__(1024) void probe_fwd_kernel(ProbeFwdArgs a, ProbeSw
             for (int r = 0; r < 4; ++r) {
                 const long row = row0 + 4 * lk + r;
                 if (!okc[t] || row >= a.n) continue;
-                const float p = a.softmax ? expf(acc[t][r] - m[r]) / s[r] : 1.0f / (1.0f + expf(-acc[t][r]));
+                const float z = logit(acc[t][r]);
+                const float p = a.softmax ? expf(z - m[r]) / s[r] : 1.0f / (1.0f + expf(-z));
                 if constexpr (MODE == 2) {
                     out[(size_t)row * C + c] = p;
+                    if constexpr (EXT == 2)
+                        if (w.codes) w.codes[(size_t)row * C + c] = (int8_t)probe_clamp_code(acc[t][r]);
                 } else {
                     const long src = (MODE == 0 && a.idx) ? (long)a.idx[row] : row;
                     float y = a.Y[(size_t)src * C + c];
@@ -294,7 +335,8 @@ __global__ __launch_bounds__(1024) void probe_fwd_kernel(ProbeFwdArgs a, ProbeSw
                         float le, g;
                         probe_loss_elem(p, pc, y, a.softmax, focal, a.focal_gamma, weighted, rw[r], le, g);
                         loss += le;
-                        if constexpr (MODE == 0) out[(size_t)row * C + c] = g * a.g_scale;
+                        if constexpr (MODE == 0 && EXT == 2) out[(size_t)row * C + c] = acc[t][r] == probe_clamp_code(acc[t][r]) ? g * a.g_scale : 0.0f;
+                        else if constexpr (MODE == 0) out[(size_t)row * C + c] = g * a.g_scale;
                     } else {
                         if (a.softmax)
                             loss -= y * logf(pc);
@@ -500,7 +542,7 @@ inline unsigned probe_trials(const ProbeSweepOf<SWEEP>& w) {
 }
 
 template <int NT, int MODE, int EXT, bool SWEEP>
-bool probe_launch_fwd_one(const ProbeFwdArgs& a, const ProbeSweepOf<SWEEP>& w, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
+bool probe_launch_fwd_one(const ProbeFwdArgs& a, const ProbeFwdExtraOf<SWEEP, EXT>& w, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
     if (lds > 64 * 1024 && !ensure_dynamic_lds((const void*)&probe_fwd_kernel<NT, MODE, EXT, SWEEP>, lds)) return false;
     hipLaunchKernelGGL((probe_fwd_kernel<NT, MODE, EXT, SWEEP>), grid, block, lds, s, a, w);
     return true;
@@ -519,18 +561,35 @@ bool probe_launch_fwd_nt(const ProbeFwdArgs& a, const ProbeSweepOf<SWEEP>& w, in
     else return false;   // (not reached)
 }
 
+// The forward kernel's launch from the shapes: grid (row tiles, trials), one wave per column tile up to kFwdWaves, NT from per_wave
+struct ProbeFwdGeom {
+    dim3 grid, block;
+    size_t lds;
+    int per_wave;
+};
+inline ProbeFwdGeom probe_fwd_geom(const ProbeFwdArgs& a, unsigned trials) {
+    const int ntiles = (a.C + 15) / 16;
+    const int nw = ntiles < kFwdWaves ? ntiles : kFwdWaves;
+    return {dim3((unsigned)((a.n + kRows - 1) / kRows), trials), dim3(64 * nw), (size_t)kRows * (((a.D + 3) & ~3) + kLdsPad) * sizeof(float),
+            (ntiles + nw - 1) / nw};
+}
+
 // false: the runtime refused the LDS request
 template <bool SWEEP>
 bool probe_launch_fwd(const ProbeFwdArgs& a, const ProbeSweepOf<SWEEP>& w, int mode, hipStream_t s) {
-    const int ntiles = (a.C + 15) / 16;
-    const int nw = ntiles < kFwdWaves ? ntiles : kFwdWaves;
-    const int per_wave = (ntiles + nw - 1) / nw;
-    const dim3 grid((unsigned)((a.n + kRows - 1) / kRows), probe_trials<SWEEP>(w)), block(64 * nw);
-    const size_t lds = (size_t)kRows * (((a.D + 3) & ~3) + kLdsPad) * sizeof(float);
-    if (per_wave <= 1) return probe_launch_fwd_nt<1, SWEEP>(a, w, mode, grid, block, lds, s);
-    if (per_wave <= 2) return probe_launch_fwd_nt<2, SWEEP>(a, w, mode, grid, block, lds, s);
-    if (per_wave <= 4) return probe_launch_fwd_nt<4, SWEEP>(a, w, mode, grid, block, lds, s);
-    return probe_launch_fwd_nt<8, SWEEP>(a, w, mode, grid, block, lds, s);   // C > 2048: two passes over the columns
+    const ProbeFwdGeom g = probe_fwd_geom(a, probe_trials<SWEEP>(w));
+    if (g.per_wave <= 1) return probe_launch_fwd_nt<1, SWEEP>(a, w, mode, g.grid, g.block, g.lds, s);
+    if (g.per_wave <= 2) return probe_launch_fwd_nt<2, SWEEP>(a, w, mode, g.grid, g.block, g.lds, s);
+    if (g.per_wave <= 4) return probe_launch_fwd_nt<4, SWEEP>(a, w, mode, g.grid, g.block, g.lds, s);
+    return probe_launch_fwd_nt<8, SWEEP>(a, w, mode, g.grid, g.block, g.lds, s);   // C > 2048: two passes over the columns
+}
+
+// The EXT = 2 family (bn_probe_set_qat with quantize_logits): all three modes, single fit (bn_probe.hip: launch_probe_fwd_qat)
+template <int NT>
+bool probe_launch_fwd_qat_nt(const ProbeFwdArgs& a, const ProbeQatArgs& q, int mode, const ProbeFwdGeom& g, hipStream_t s) {
+    if (mode == 0) return probe_launch_fwd_one<NT, 0, 2, false>(a, q, g.grid, g.block, g.lds, s);
+    if (mode == 1) return probe_launch_fwd_one<NT, 1, 2, false>(a, q, g.grid, g.block, g.lds, s);
+    return probe_launch_fwd_one<NT, 2, 2, false>(a, q, g.grid, g.block, g.lds, s);
 }
 
 // grid z: trial * row_groups + group

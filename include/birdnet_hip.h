@@ -455,6 +455,28 @@ BN_API int bn_probe_set_loss(bn_probe* probe, int loss, float focal_gamma);
  * batch draw different dropout masks (the draw is per position in the batch). */
 BN_API int bn_probe_epoch_weighted(bn_probe* probe, const float* d_X, const float* d_Y, const float* d_row_weight, const int32_t* d_perm,
                             int64_t n, int batch, float* d_step_loss, void* stream);
+/* Quantisation-aware fine-tuning of the head for the INT8 export (reference counterpart: `train --qat`, training/qat.py).  From the next
+ * step and the next bn_probe_loss on, the forward sees what the exported head will compute; the gradient and the optimiser keep acting
+ * on the full-precision (shadow) parameters, which bn_probe_get returns: the plain straight-through estimator.  Off on a new probe.
+ *   weight_mode     BN_PROBE_QAT_PER_CLASS / _PER_TENSOR: in front of every forward the weights [D, C] are replaced by
+ *                   float(q) * float(s) with s = max(amax_c, 5e-7) / 127, q = clip(rint(w / s), -127, 127) in float64, amax_c the largest
+ *                   |w| of class c (of the whole matrix with _PER_TENSOR): the rule of the exporter's weight quantiser, bit for bit.  The
+ *                   bias stays full precision.  BN_PROBE_QAT_OFF: the weights as they are.
+ *   quantize_logits != 0: between the bias add and the activation, in float32 with a rounding after every operation,
+ *                   k = rintf(z / s_out) + z_out, kc = min(max(k, -128), 127), zq = (kc - z_out) * s_out; the activation and the loss take
+ *                   zq, and dLoss/dz is dLoss/dzq where k == kc and 0 where the code clamps.  (s_out, z_out) are the exported logit
+ *                   tensor's parameters.  The sigmoid's 1/256 output grid is not modelled.
+ * Refused (BN_ERR_ARG, nothing changes): a null probe, an unknown weight_mode, and with quantize_logits a non-finite or non-positive
+ * s_out or a z_out outside [-128, 127].  A sweep has no QAT: fine-tune its winner as a bn_probe. */
+#define BN_PROBE_QAT_OFF 0
+#define BN_PROBE_QAT_PER_CLASS 1
+#define BN_PROBE_QAT_PER_TENSOR 2
+BN_API int bn_probe_set_qat(bn_probe* probe, int weight_mode, int quantize_logits, float s_out, int z_out);
+/* The weights [D, C] the next forward would read (device pointer): fake-quantised under the current weight_mode, else the probe's own. */
+BN_API int bn_probe_get_quantized(bn_probe* probe, float* d_Wq, void* stream);
+/* Scores [n, C] of rows 0 .. n-1 of d_X under the probe's current QAT setting, without dropout (bn_head_forward when QAT is off).
+ * d_codes, int8 [n, C] or null: the clamped logit codes kc; needs quantize_logits. */
+BN_API int bn_probe_scores(bn_probe* probe, const float* d_X, int64_t n, float* d_scores, int8_t* d_codes, void* stream);
 
 /* ---- A hyperparameter sweep: T heads trained in lock-step on the same rows (csrc/bn_probe_sweep.hip) ---------------------------------
  * (Reference counterpart: `train --tune`, training/tuner.py, which trains its trials one after another.)  The trials share D, C, the

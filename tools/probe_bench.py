@@ -19,6 +19,14 @@ One sweep of T trials (``fit_probe_sweep``'s backend, ``bn_probe_sweep_*``) agai
 same process: per cell one warm-up epoch of each side, then ``--repeats`` timed epochs of each, alternating.  An epoch is timed from the
 permutation's upload to the step losses on the host, as the fit runs it.  Reports the median and the spread (min .. max) of both sides and
 the ratio of the medians.
+
+    python tools/probe_bench.py --qat [--rows 262144] [--large_rows 16384] [--repeats 5]
+
+An epoch of the quantisation-aware fine-tune (``fit_probe_qat``'s backend: ``bn_probe_set_qat`` with per-class weights and quantised logits,
+DESIGN.md §5j) against the plain ``bn_probe_epoch`` on the same rows in the same process: D = 256, C in {16, 100, 1000}, batch 32 and 512,
+and the largest head the device takes (D = 2048, C = 4096, over ``--large_rows`` rows), where the two weight kernels in front of every
+forward pass over 8.4 M weights.  Per cell one warm-up epoch of each side, then ``--repeats`` timed epochs of each, alternating; median,
+spread (min .. max) and the ratio of the medians.
 """
 
 import argparse
@@ -103,6 +111,52 @@ def sweep_main(args):
     ctx.close()
 
 
+def qat_main(args):
+    import numpy as np
+    import torch
+
+    from birdnet_stm32 import _hip
+    from birdnet_stm32.training import linear_probe as lp
+    from birdnet_stm32.training import probe_qat as pq
+
+    ctx = _hip.Context(0, 1)
+    g = torch.Generator(device="cuda").manual_seed(1)
+    rows = []
+    for D, C, n in [(256, 16, args.rows), (256, 100, args.rows), (256, 1000, args.rows), (2048, 4096, args.large_rows)]:
+        X = torch.rand((n, D), device="cuda", generator=g)
+        Y = torch.zeros((n, C), device="cuda")
+        Y[torch.arange(n, device="cuda"), torch.randint(0, C, (n,), device="cuda", generator=g)] = 1.0
+        head = lp.ProbeHead(*lp.init_head(D, C, 1))
+        for batch in (32, 512):
+            steps = math.ceil(n / batch)
+            kw = dict(optimizer="adam", batch_size=batch, dropout=0.5, epochs=args.repeats + 1, learning_rate=1e-4, weight_decay=0.0, clipnorm=1.0, seed=1)
+            plan = pq._plan_qat(X, Y, None, head, True, kw)
+            plain = lp._DeviceBackend(ctx, X, Y, None, None, plan)
+            qat = pq._QatDeviceBackend(ctx, X, Y, None, None, plan, False, True, 16.0 / 255.0, 0)   # logits in [-8, 8]
+            a, b = [], []
+            for e in range(args.repeats + 1):
+                perm = lp.epoch_permutation(1, e, n)
+                for be, times in ((plain, a), (qat, b)):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    be.epoch(perm)   # (uploads the permutation, reads the step losses back: synchronises)
+                    times.append(time.perf_counter() - t0)
+            plain.close()
+            qat.close()
+            a, b = sorted(a[1:]), sorted(b[1:])
+            row = dict(D=D, C=C, batch=batch, rows=n, steps_per_epoch=steps, plain_s=float(np.median(a)), plain_min=a[0], plain_max=a[-1],
+                       qat_s=float(np.median(b)), qat_min=b[0], qat_max=b[-1], ratio=float(np.median(b) / np.median(a)),
+                       plain_us_per_step=1e6 * float(np.median(a)) / steps, qat_us_per_step=1e6 * float(np.median(b)) / steps)
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+        del X, Y
+    print("\n| D | C | batch | plain epoch, s (min .. max) | QAT epoch, s (min .. max) | plain, us/step | QAT, us/step | ratio |\n|---|---|---|---|---|---|---|---|")
+    for r in rows:
+        print(f"| {r['D']} | {r['C']} | {r['batch']} | {r['plain_s']:.3f} ({r['plain_min']:.3f} .. {r['plain_max']:.3f}) | "
+              f"{r['qat_s']:.3f} ({r['qat_min']:.3f} .. {r['qat_max']:.3f}) | {r['plain_us_per_step']:.1f} | {r['qat_us_per_step']:.1f} | {r['ratio']:.2f} |")
+    ctx.close()
+
+
 def main():
     import numpy as np
     import torch
@@ -121,7 +175,11 @@ def main():
     ap.add_argument("--repeats", type=int, default=3, help="with --sweep: timed epochs per side and cell (one more runs first as warm-up)")
     ap.add_argument("--classes", type=str, default="12,100,1000", help="with --sweep: class counts")
     ap.add_argument("--batches", type=str, default="32,512,4096", help="with --sweep: batch sizes")
+    ap.add_argument("--qat", action="store_true", help="time an epoch of the quantisation-aware fine-tune against the plain epoch (uses --rows, --repeats)")
+    ap.add_argument("--large_rows", type=int, default=16384, help="with --qat: rows of the D = 2048, C = 4096 cell")
     args = ap.parse_args()
+    if args.qat:
+        return qat_main(args)
     if args.sweep:
         return sweep_main(args)
     n, D = args.rows, 256

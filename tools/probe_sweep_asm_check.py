@@ -11,7 +11,8 @@ training forward kernel: one multiplication and one addition more per target ele
 fused form fewer; and the integer division that splits the gradient kernel's z into trial and row group, which the compiler does with
 a float32 reciprocal.  The forward kernel's instantiations with the focal loss and the row weights (its third template argument, EXT = 1)
 are pairs like the others and take the same allowance: their loss arithmetic is written with contraction off, so there is nothing for
-the compiler to fuse in one instantiation and not in the other.  Opcodes are counted without their encoding suffix (_e32 / _e64 / _dpp / _sdwa).  Anything else is printed as a
+the compiler to fuse in one instantiation and not in the other.  The quantisation-aware fine-tune (EXT = 2 and the probe_qat_* kernels)
+is a single fit's only and has no pair.  Opcodes are counted without their encoding suffix (_e32 / _e64 / _dpp / _sdwa).  Anything else is printed as a
 warning.  No part of the build (`make probe-asm-check` in csrc/ runs it): another compiler may lower these two idioms differently without
 touching the arithmetic, and the GPU tests, which compare the bits, hold the contract (tests/test_gpu_probe_sweep.py).  This is where
 to look first, on a machine without a GPU, when they fail.  --strict makes a difference the exit status.  Needs c++filt; without it, it says so and checks nothing.
@@ -58,6 +59,8 @@ def main(single_path, sweep_path, strict=False):
     bad = 0
     for key, (is_sweep, ops) in sorted(single.items()):
         if key[0] == "probe_fwd_kernel" and key[1][1] == "2":   # scores only (bn_head_forward): no part of a sweep
+            continue
+        if key[0].startswith("probe_qat_") or (key[0] == "probe_fwd_kernel" and key[1][2] == "2"):   # QAT (EXT = 2): a single fit's only
             continue
         if is_sweep or key not in sweep:
             print(f"probe_sweep_asm_check: no sweep instantiation of {key}" if key not in sweep else f"{key}: a sweep kernel in {single_path}")
