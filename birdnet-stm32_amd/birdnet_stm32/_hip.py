@@ -20,7 +20,7 @@ from ctypes import POINTER, byref, c_char_p, c_float, c_int, c_int32, c_int64, c
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))  # .../birdnet-stm32_amd
 LIB_PATH = os.path.join(_PKG_ROOT, "lib", "libbirdnet_hip.so")
 
-ABI_VERSION = 1
+ABI_VERSION = 2
 
 # every symbol include/birdnet_hip.h declares
 EXPORTS = (
@@ -36,6 +36,7 @@ EXPORTS = (
     "bn_probe_set_qat", "bn_probe_get_quantized", "bn_probe_scores",
     "bn_short_time_energy", "bn_activity_counts", "bn_search_inv_norms", "bn_search_topk", "bn_augment_inputs",
     "bn_kmeans_assign", "bn_kmeans_accumulate", "bn_kmeans_centroids",
+    "bn_tsne_perplexity", "bn_tsne_gradient", "bn_tsne_update",
     "bn_bootstrap_rejections", "bn_bootstrap_counts", "bn_bootstrap_ap", "bn_head_i8_forward", "bn_head_i8_pass_classes",
 )  # fmt: skip
 
@@ -74,6 +75,8 @@ SEARCH_STEP_ROWS, SEARCH_MIN_WG_STEPS, SEARCH_MAX_WGS = 64, 8, 1024  # how bn_se
 KMEANS_MAX_K, KMEANS_MAX_D = 4096, 2048
 BOOTSTRAP_MAX_N = 32768  # BN_BOOTSTRAP_MAX_N
 KMEANS_LDS_BYTES, KMEANS_MAX_TILE, KMEANS_STEP_ROWS, KMEANS_MIN_WG_STEPS, KMEANS_MAX_WGS, KMEANS_SEGMENT_ROWS = 160 * 1024, 128, 64, 8, 1024, 256
+# bn_tsne_* (include/birdnet_hip.h): rows of a repulsion workgroup, points per LDS tile, columns per range of the second grid axis, lanes per row
+TSNE_TILE_I, TSNE_TILE_J, TSNE_SPLIT_J, TSNE_ROW_LANES, TSNE_MAX_K, TSNE_MAX_N = 256, 1024, 4096, 16, 128, 1 << 21
 
 
 def kmeans_tile_centroids(D: int, K: int) -> int:
@@ -182,6 +185,9 @@ def load_library(path: str | None = None):
                                      c_void_p, c_void_p]
     lib.bn_kmeans_accumulate.argtypes = [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]
     lib.bn_kmeans_centroids.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]
+    lib.bn_tsne_perplexity.argtypes = [c_void_p, c_void_p, c_int64, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p]
+    lib.bn_tsne_gradient.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.bn_tsne_update.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_void_p]
     u64 = ctypes.c_uint64
     lib.bn_bootstrap_rejections.argtypes = [c_void_p, u64, u64, u64, u64, ctypes.c_uint32, c_int64, c_int64, c_void_p, c_int64, POINTER(c_int64), c_void_p]
     lib.bn_bootstrap_counts.argtypes = [c_void_p, u64, u64, u64, u64, c_int, c_int, c_void_p, c_void_p, c_void_p]

@@ -219,6 +219,7 @@ void bn_ctx_destroy(bn_ctx* c) {
     if (c->d_rank_work) (void)hipFree(c->d_rank_work);
     if (c->d_search_work) (void)hipFree(c->d_search_work);
     if (c->d_kmeans_work) (void)hipFree(c->d_kmeans_work);
+    if (c->d_tsne_work) (void)hipFree(c->d_tsne_work);
     if (c->d_boot_work) (void)hipFree(c->d_boot_work);
     delete c;
 }
@@ -1042,7 +1043,7 @@ int bn_preload_kernels(bn_ctx* ctx) {
     // copies wait meanwhile).  A caller with idle time before its first batch — the evaluate pipeline while the first files are read — asks here.
     bn::preload_ingest(); bn::preload_stft(); bn::preload_stft_exact(); bn::preload_i8_fused(); bn::preload_i8_strip(); bn::preload_i8_tail2();
     bn::preload_i8_tail(); bn::preload_i8(); bn::preload_i8_pw(); bn::preload_f32(); bn::preload_f32_fused(); bn::preload_f32_strip();
-    bn::preload_f32_pw(); bn::preload_melspec(); bn::preload_sort(); bn::preload_probe(); bn::preload_probe_sweep(); bn::preload_activity(); bn::preload_search(); bn::preload_augment(); bn::preload_kmeans(); bn::preload_bootstrap(); bn::preload_head_i8();
+    bn::preload_f32_pw(); bn::preload_melspec(); bn::preload_sort(); bn::preload_probe(); bn::preload_probe_sweep(); bn::preload_activity(); bn::preload_search(); bn::preload_augment(); bn::preload_kmeans(); bn::preload_tsne(); bn::preload_bootstrap(); bn::preload_head_i8();
     return BN_OK;
 }
 
@@ -1061,7 +1062,7 @@ const char* bn_kernel_names(void) {
     return "ingest_resample_kernel\ningest_decimate_kernel\ningest_peak_kernel\ningest_chunks_kernel\nchunk_peaknorm_kernel\npool_scores_kernel\nstft512_mag_kernel\nspec_normalize_kernel\nmelspec_finish_kernel\nf32_mel_kernel\nf32_melfin_kernel\nf32_mag_kernel\nf32_rawfe_kernel\nf32_stem_kernel\nf32_dw_kernel\n"
            "f32_pw_kernel\nf32_pw_ws_kernel\nf32_dwpw_kernel\nf32_dwpw_wave_kernel\nf32_strip_kernel\nf32_front_strip_kernel\nf32_front2_kernel\nf32_pwdw_kernel\nf32_dw_stream_kernel\nf32_front_kernel\nf32_gap_kernel\nf32_gap_dense_kernel\nf32_gap_dense_emb_kernel\nf32_dense_kernel\nf32_segate_kernel\nf32_scale_kernel\nf32_attnpool_kernel\n"
            "i8_quant_kernel\ni8_mel_kernel\ni8_stem_kernel\ni8_dw_kernel\ni8_pw_kernel\ni8_dwpw_kernel\ni8_mel_mfma_kernel\ni8_strip_kernel\ni8_strip_mf_kernel\ni8_front_strip_kernel\ni8_front_kernel\ni8_tail_kernel\ni8_tail_emb_kernel\ni8_tail2_kernel\ni8_tail2_emb_kernel\ni8_mid2_kernel\ni8_mean_kernel\ni8_fc_kernel\ni8_scale_kernel\ni8_maxnorm_kernel\ni8_rawfe_kernel\ni8_pwdw_kernel\ni8_dw_stream_kernel\ni8_stem_stream_kernel\ni8_segate_kernel\ni8_pw_wave_kernel\ni8_pw_lds_kernel\ni8_attnpool_kernel\n"
-           "i8_head_kernel\ni8_head_softmax_kernel\nemb_store_kernel\nprobe_fwd_kernel\nprobe_dw_kernel\nprobe_reduce_kernel\nprobe_update_kernel\nprobe_loss_sum_kernel\nprobe_sweep_snapshot_kernel\nste_kernel\nactivity_count_kernel\nsearch_inv_norms_kernel\nsearch_score_kernel\nsearch_merge_kernel\naugment_kernel\nkmeans_assign_kernel\nkmeans_keys_kernel\nkmeans_offsets_kernel\nkmeans_segments_kernel\nkmeans_partial_kernel\nkmeans_fold_kernel\nkmeans_scale_kernel\nbootstrap_table_kernel\nbootstrap_reject_kernel\nbootstrap_prepare_kernel\nbootstrap_resample_kernel\nhead_i8_kernel";
+           "i8_head_kernel\ni8_head_softmax_kernel\nemb_store_kernel\nprobe_fwd_kernel\nprobe_dw_kernel\nprobe_reduce_kernel\nprobe_update_kernel\nprobe_loss_sum_kernel\nprobe_sweep_snapshot_kernel\nste_kernel\nactivity_count_kernel\nsearch_inv_norms_kernel\nsearch_score_kernel\nsearch_merge_kernel\naugment_kernel\nkmeans_assign_kernel\nkmeans_keys_kernel\nkmeans_offsets_kernel\nkmeans_segments_kernel\nkmeans_partial_kernel\nkmeans_fold_kernel\nkmeans_scale_kernel\ntsne_perplexity_kernel\ntsne_repulsion_kernel\ntsne_fold_kernel\ntsne_z_kernel\ntsne_attraction_kernel\ntsne_update_kernel\nbootstrap_table_kernel\nbootstrap_reject_kernel\nbootstrap_prepare_kernel\nbootstrap_resample_kernel\nhead_i8_kernel";
 }
 
 }  // extern "C"
@@ -1196,6 +1197,51 @@ int bn_kmeans_centroids(bn_ctx* ctx, const float* d_sums, const int64_t* d_count
     if ((uintptr_t)d_sums % 4 || (uintptr_t)d_centroids % 4 || (uintptr_t)d_cent_inv % 4 || (uintptr_t)d_counts % 8)
         return fail(BN_ERR_ARG, "float32 arrays must be 4-byte aligned, d_counts 8-byte aligned");
     bn::launch_kmeans_centroids(d_sums, (const long long*)d_counts, K, D, d_centroids, d_cent_inv, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return BN_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------------------------ t-SNE (bn_tsne.hip)
+extern "C" {
+
+int bn_tsne_perplexity(bn_ctx* ctx, const float* d_score, int64_t n, int k, double perplexity, float* d_p, double* d_beta, void* stream) {
+    if (int rc = check_device(ctx)) return rc;
+    if (n < 1 || n > 0x7fffffffLL) return fail(BN_ERR_ARG, "bad row count %lld", (long long)n);
+    if (k < 1 || k > BN_TSNE_MAX_K) return fail(BN_ERR_ARG, "k=%d outside 1..%d", k, BN_TSNE_MAX_K);
+    if (!(perplexity >= 1.0) || 3.0 * perplexity > (double)BN_TSNE_MAX_K) return fail(BN_ERR_ARG, "perplexity %g outside 1..%d/3", perplexity, BN_TSNE_MAX_K);
+    if (!d_score || !d_p || !d_beta) return fail(BN_ERR_ARG, "null device pointer");
+    if ((uintptr_t)d_score % 4 || (uintptr_t)d_p % 4 || (uintptr_t)d_beta % 8) return fail(BN_ERR_ARG, "float32 arrays must be 4-byte aligned, d_beta 8-byte aligned");
+    bn::launch_tsne_perplexity(d_score, (long)n, k, perplexity, d_p, d_beta, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return BN_OK;
+}
+
+int bn_tsne_gradient(bn_ctx* ctx, const float* d_y, int64_t n, const int64_t* d_rowptr, const int32_t* d_col, const float* d_val, float exaggeration,
+                     float* d_grad, double* d_z, double* d_kl_rows, void* stream) {
+    if (int rc = check_device(ctx)) return rc;
+    if (n < 2 || n > BN_TSNE_MAX_N) return fail(BN_ERR_ARG, "row count %lld outside 2..%d", (long long)n, BN_TSNE_MAX_N);
+    if (!std::isfinite(exaggeration)) return fail(BN_ERR_ARG, "the exaggeration is not finite");
+    if (!d_y || !d_rowptr || !d_col || !d_val || !d_grad || !d_z) return fail(BN_ERR_ARG, "null device pointer");
+    if ((uintptr_t)d_y % 8 || (uintptr_t)d_grad % 8 || (uintptr_t)d_rowptr % 8 || (uintptr_t)d_z % 8 || (uintptr_t)d_kl_rows % 8 || (uintptr_t)d_col % 4 ||
+        (uintptr_t)d_val % 4)
+        return fail(BN_ERR_ARG, "d_y, d_grad, d_rowptr, d_z and d_kl_rows must be 8-byte aligned, d_col and d_val 4-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t need = bn::tsne_gradient_workspace((long)n);
+    if (int rc = grow_device_buffer(&ctx->d_tsne_work, &ctx->tsne_work_bytes, need, need, s, BN_ERR_NOMEM, "t-SNE")) return rc;
+    bn::launch_tsne_gradient(d_y, (long)n, (const long long*)d_rowptr, d_col, d_val, exaggeration, d_grad, d_z, d_kl_rows, ctx->d_tsne_work, s);
+    HIP_TRY(hipGetLastError());
+    return BN_OK;
+}
+
+int bn_tsne_update(bn_ctx* ctx, float* d_y, const float* d_grad, float* d_update, float* d_gains, int64_t n, float lr, float momentum, void* stream) {
+    if (int rc = check_device(ctx)) return rc;
+    if (n < 1 || n > 0x3fffffffLL) return fail(BN_ERR_ARG, "bad row count %lld", (long long)n);
+    if (!std::isfinite(lr) || !std::isfinite(momentum)) return fail(BN_ERR_ARG, "learning rate and momentum must be finite");
+    if (!d_y || !d_grad || !d_update || !d_gains) return fail(BN_ERR_ARG, "null device pointer");
+    if ((uintptr_t)d_y % 4 || (uintptr_t)d_grad % 4 || (uintptr_t)d_update % 4 || (uintptr_t)d_gains % 4) return fail(BN_ERR_ARG, "float32 arrays must be 4-byte aligned");
+    bn::launch_tsne_update(d_y, d_grad, d_update, d_gains, (long)n, lr, momentum, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return BN_OK;
 }

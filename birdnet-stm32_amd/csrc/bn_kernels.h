@@ -420,7 +420,7 @@ void launch_i8_dwpw(const DwPw8Args& a, hipStream_t s);
 // One per source file with kernels: load that file's device code object now (bn_preload_kernels)
 void preload_f32(); void preload_f32_fused(); void preload_f32_pw(); void preload_f32_strip(); void preload_i8(); void preload_i8_fused();
 void preload_i8_pw(); void preload_i8_strip(); void preload_i8_tail(); void preload_i8_tail2(); void preload_ingest(); void preload_melspec();
-void preload_stft(); void preload_stft_exact(); void preload_sort(); void preload_probe(); void preload_probe_sweep(); void preload_activity(); void preload_search(); void preload_augment(); void preload_kmeans(); void preload_bootstrap(); void preload_head_i8();
+void preload_stft(); void preload_stft_exact(); void preload_sort(); void preload_probe(); void preload_probe_sweep(); void preload_activity(); void preload_search(); void preload_augment(); void preload_kmeans(); void preload_tsne(); void preload_bootstrap(); void preload_head_i8();
 
 // bn_probe.hip: a classifier head on embeddings (bn_head_forward) and its training step (bn_probe_*)
 struct ProbeFwdArgs {
@@ -591,6 +591,13 @@ size_t kmeans_accumulate_workspace(long n, int D, int K);
 bool launch_kmeans_accumulate(const void* rows, bool i8, long n, int D, int zp, const float* row_inv, const int* label, int K, int accumulate, float* sums,
                               long long* counts, void* d_work, size_t work_bytes, hipStream_t s);
 void launch_kmeans_centroids(const float* sums, const long long* counts, int K, int D, float* cent, float* cent_inv, hipStream_t s);
+
+// bn_tsne.hip: exact t-SNE over a 2-D map — conditional affinities, gradient (all-pairs repulsion, CSR attraction) and update (bn_tsne_*)
+void launch_tsne_perplexity(const float* score, long n, int k, double perplexity, float* p, double* beta, hipStream_t s);
+size_t tsne_gradient_workspace(long n);
+void launch_tsne_gradient(const float* y, long n, const long long* rowptr, const int* col, const float* val, float exaggeration, float* grad, double* z,
+                          double* kl_rows, void* d_work, hipStream_t s);
+void launch_tsne_update(float* y, const float* grad, float* update, float* gains, long n, float lr, float momentum, hipStream_t s);
 
 // bn_bootstrap.hip: numpy's bounded draws reproduced on the device and the average precision of every resample (bn_bootstrap_*);
 // gen = (state.hi, state.lo, inc.hi, inc.lo) of the PCG64

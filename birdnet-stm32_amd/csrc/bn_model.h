@@ -69,6 +69,8 @@ struct bn_ctx {
     size_t search_work_bytes = 0;
     void* d_kmeans_work = nullptr;   // bn_kmeans_accumulate: sort keys, row orders, segment partial sums, rocPRIM storage; grown on demand
     size_t kmeans_work_bytes = 0;
+    void* d_tsne_work = nullptr;     // bn_tsne_gradient: the column ranges' partial sums, the folded repulsion and row sums; grown on demand
+    size_t tsne_work_bytes = 0;
     void* d_boot_work = nullptr;     // bn_bootstrap_*: jump-ahead table, rejection counter and list, prepared class orders; grown on demand
     size_t boot_work_bytes = 0;
 };

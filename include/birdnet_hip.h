@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define BN_ABI_VERSION 1
+#define BN_ABI_VERSION 2
 
 #if defined(__GNUC__)
 #define BN_API __attribute__((visibility("default")))
@@ -609,6 +609,54 @@ BN_API int bn_kmeans_accumulate(bn_ctx* ctx, const void* d_rows, int dtype, int6
  * d_cent_inv [K] = the inverse norms of the centroids. */
 BN_API int bn_kmeans_centroids(bn_ctx* ctx, const float* d_sums, const int64_t* d_counts, int K, int D, float* d_centroids, float* d_cent_inv,
                         void* stream);
+
+/* ---- Projection: exact t-SNE with k-nearest-neighbour affinities and all-pairs repulsion (csrc/bn_tsne.hip; no reference counterpart) ----
+ * (van der Maaten's formulas with the constants of scikit-learn 1.7's sklearn.manifold.TSNE; birdnet_stm32/evaluation/project.py is the
+ * specification.)  A map is Y [n, 2] float32.  With w_ij = 1 / (1 + |y_i - y_j|^2):
+ *   A_i  = sum over the entries j of row i of the CSR matrix P of p_ij w_ij (y_i - y_j)
+ *   R_i  = sum over j != i of w_ij^2 (y_i - y_j),   z_i = sum over j != i of w_ij,   Z = sum over i of z_i
+ *   grad_i = 4 (exaggeration * A_i - R_i / Z)
+ * Everything per pair is float32: differences, 1 + dx^2 + dy^2 as two fused multiply-adds, the hardware reciprocal (1 ulp), products and
+ * fused accumulation.  j = i is left out by index; equal points are legal (w = 1, no force).  Within a range of BN_TSNE_SPLIT_J columns
+ * R_i and z_i are summed over j ascending in two chains, the even and the odd columns of every LDS tile (an odd last column goes to the
+ * first), which are added at the end; the ranges are then added in ascending order; a row of P is summed by 16 lanes, each over
+ * every 16th entry, then across the lanes in a fixed tree; Z is one float64 sum of the float32 z_i in a fixed order; R_i / Z is a float64
+ * division rounded once to float32.  No floating-point atomics: the same inputs give the same bits on every run.  A refused call returns
+ * BN_ERR_ARG and writes nothing.  Nothing synchronises with the host inside a call unless the context's workspace has to grow. */
+/* How the repulsion is dealt — from n alone: a workgroup owns BN_TSNE_TILE_I rows and stages the columns of its range through LDS in
+ * tiles of BN_TSNE_TILE_J points; the second grid axis holds ceil(n / BN_TSNE_SPLIT_J) column ranges.  A row of P goes to
+ * BN_TSNE_ROW_LANES lanes.  bn_tsne_perplexity gives a row to BN_TSNE_ROW_LANES lanes as well, k <= BN_TSNE_MAX_K. */
+#define BN_TSNE_TILE_I 256
+#define BN_TSNE_TILE_J 1024
+#define BN_TSNE_SPLIT_J 4096
+#define BN_TSNE_ROW_LANES 16
+#define BN_TSNE_MAX_K 128
+#define BN_TSNE_MAX_N (1 << 21)   /* rows of a map: the column ranges are the second grid axis, their partial sums n * ceil(n / BN_TSNE_SPLIT_J) * 16 bytes */
+#define BN_TSNE_MAX_PERPLEXITY_STEPS 100
+
+/* Conditional affinities from the cosine scores of bn_search_topk: d_score [n, k] float32 -> d_p [n, k] float32 and d_beta [n] float64.
+ * Per row, in float64: d2_j = max(0, fl32(2 - 2 s_j)), m = min d2, p_j = exp(-beta (d2_j - m)), S = sum p_j,
+ * H = log S + beta sum (d2_j - m) p_j / S.  beta starts at 1 and follows scikit-learn's search (_binary_search_perplexity): doubled or
+ * halved while its interval is open on that side, bisected afterwards, until |H - log(perplexity)| <= 1e-5 or
+ * BN_TSNE_MAX_PERPLEXITY_STEPS values have been tried; the last value tried stands.  d_p = fl32(p_j / S) for that beta.  Scores must be
+ * finite.  Refused: n < 1 or n >= 2^31, k outside 1..BN_TSNE_MAX_K, perplexity not in [1, BN_TSNE_MAX_K / 3], a NULL pointer, d_score /
+ * d_p not 4-byte or d_beta not 8-byte aligned. */
+BN_API int bn_tsne_perplexity(bn_ctx* ctx, const float* d_score, int64_t n, int k, double perplexity, float* d_p, double* d_beta, void* stream);
+/* d_grad [n, 2] float32 and *d_z (float64) of the map d_y [n, 2] under P = (d_rowptr [n + 1] int64, d_col int32, d_val float32), a CSR
+ * matrix whose rows may hold anything from 0 to n - 1 entries; with d_kl_rows (float64 [n], may be NULL) also
+ * kl_i = sum over the entries of row i with p_ij > 0 of p_ij log(p_ij (1 + |y_i - y_j|^2)) in float64, summed like A_i; the Kullback-Leibler
+ * divergence of P is sum kl_i + (sum p_ij) log Z.  The device tables are not trusted further than their sizes: row bounds are clipped to
+ * 0 .. d_rowptr[n] and columns to 0 .. n - 1, so a bad matrix gives wrong numbers, never a stray read beyond d_rowptr[n] entries.
+ * Refused: n < 2 or n > BN_TSNE_MAX_N, an exaggeration that is not finite, a NULL pointer other than d_kl_rows, d_y / d_grad / d_rowptr / d_z /
+ * d_kl_rows not 8-byte or d_col / d_val not 4-byte aligned. */
+BN_API int bn_tsne_gradient(bn_ctx* ctx, const float* d_y, int64_t n, const int64_t* d_rowptr, const int32_t* d_col, const float* d_val,
+                     float exaggeration, float* d_grad, double* d_z, double* d_kl_rows, void* stream);
+/* One step of scikit-learn's _gradient_descent over the 2 n elements of d_y, d_grad, d_update and d_gains, every operation rounded to
+ * float32 and nothing fused:  inc = update * grad < 0;  gains = inc ? gains + 0.2 : gains * 0.8;  gains = max(gains, 0.01);
+ * update = momentum * update - lr * (gains * grad);  y += update.  d_y, d_update and d_gains are rewritten, d_grad is only read.
+ * Refused: n < 1 or n >= 2^30, lr or momentum not finite, a NULL pointer, an array not 4-byte aligned. */
+BN_API int bn_tsne_update(bn_ctx* ctx, float* d_y, const float* d_grad, float* d_update, float* d_gains, int64_t n, float lr, float momentum,
+                   void* stream);
 
 /* ---- Bootstrap of the per-class average precision (csrc/bn_bootstrap.hip) -----------------------------------------------------------
  * (reference: birdnet_stm32/evaluation/metrics.py:239-318 `bootstrap_ap_ci`: one np.random.default_rng(seed) consumed class by class,
