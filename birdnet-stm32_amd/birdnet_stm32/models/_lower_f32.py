@@ -110,9 +110,11 @@ def _gap_dense_tail(layers, i, only_consumer):
         return None
 
 
-def lower_f32(spec: ns.NetSpec, keep_all: bool = False, fuse: bool = True) -> pk.Plan:
+def lower_f32(spec: ns.NetSpec, keep_all: bool = False, fuse: bool = True, tag_pairs: bool | None = None) -> pk.Plan:
     """Build the float32 plan for ``spec``.  ``keep_all`` disables slot reuse (debug/tests); ``fuse=False`` keeps
-    depthwise and pointwise convolutions as separate baseline kernels instead of the fused matrix-core block."""
+    depthwise and pointwise convolutions as separate baseline kernels instead of the fused matrix-core block.
+    ``tag_pairs``: mark the operator pairs the library may run as one kernel (``_tag_front2``, ``_tag_pwdw``); None: on production
+    plans only (``fuse and not keep_all``).  True on a ``keep_all`` plan lets tests run the pair kernels and still read every map they write."""
     layers = spec.layers
     consumers: dict[str, list[int]] = {}
     index_of = {ly.name: i for i, ly in enumerate(layers)}
@@ -416,7 +418,7 @@ def lower_f32(spec: ns.NetSpec, keep_all: bool = False, fuse: bool = True) -> pk
                   t=dict(w=pb.tensor(ly.weights["kernel"], np.float32), bias=pb.tensor(bias, np.float32)), name=ly.name, out_shape=(cout,))
         else:
             raise NotImplementedError(f"layer {ly.name} of kind {k} cannot be lowered on its own")
-    if fuse and not keep_all:
+    if (fuse and not keep_all) if tag_pairs is None else tag_pairs:
         _tag_front2(pb)
         _tag_pwdw(pb)
     return pb.finalize(reuse=not keep_all)
@@ -459,7 +461,8 @@ def _tag_front2(pb: pk.PlanBuilder) -> None:
 
     The pair qualifies when the residual block (reference: the second ``ds_conv_block`` of stage 1, ``models/dscnn.py:209-226``)
     reads nothing but the front block's output — as its input and as its residual — and no other operator reads that map:
-    the fused kernel keeps it in LDS and never writes it.  Debug plans (``keep_all``) are left alone, every tensor stays readable.
+    the fused kernel keeps it in LDS and never writes it.  ``lower_f32`` calls this on production plans, or where ``tag_pairs`` asks for it
+    (on a ``keep_all`` plan the covered map then has a slot of its own that stays unwritten).
     """
     ops = pb.plan.ops
     gate_slots = {ops[oi].p[pi] for oi, pi in pb._gate_refs}
