@@ -34,6 +34,8 @@ EXPORTS = (
     "bn_probe_sweep_create", "bn_probe_sweep_destroy", "bn_probe_sweep_epoch", "bn_probe_sweep_loss", "bn_probe_sweep_snapshot", "bn_probe_sweep_get",
     "bn_probe_set_loss", "bn_probe_epoch_weighted", "bn_probe_sweep_set_loss", "bn_probe_sweep_epoch_weighted",
     "bn_probe_set_qat", "bn_probe_get_quantized", "bn_probe_scores",
+    "bn_probe_mlp_create", "bn_probe_mlp_destroy", "bn_probe_mlp_set_loss", "bn_probe_mlp_epoch_weighted", "bn_probe_mlp_loss", "bn_probe_mlp_get",
+    "bn_probe_mlp_set", "bn_head_mlp_forward",
     "bn_short_time_energy", "bn_activity_counts", "bn_search_inv_norms", "bn_search_topk", "bn_augment_inputs",
     "bn_kmeans_assign", "bn_kmeans_accumulate", "bn_kmeans_centroids",
     "bn_tsne_perplexity", "bn_tsne_gradient", "bn_tsne_update",
@@ -223,6 +225,16 @@ def load_library(path: str | None = None):
     lib.bn_probe_set_qat.argtypes = [c_void_p, c_int, c_int, c_float, c_int]
     lib.bn_probe_get_quantized.argtypes = [c_void_p, c_void_p, c_void_p]
     lib.bn_probe_scores.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]
+    lib.bn_probe_mlp_create.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, ctypes.c_uint32, c_int64,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_void_p), c_void_p]
+    lib.bn_probe_mlp_destroy.argtypes = [c_void_p]
+    lib.bn_probe_mlp_destroy.restype = None
+    lib.bn_probe_mlp_set_loss.argtypes = [c_void_p, c_int, c_float]
+    lib.bn_probe_mlp_epoch_weighted.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]
+    lib.bn_probe_mlp_loss.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]
+    lib.bn_probe_mlp_get.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.bn_probe_mlp_set.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.bn_head_mlp_forward.argtypes = [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]
     lib.bn_probe_sweep_epoch_weighted.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
     if lib.bn_version() != ABI_VERSION:
         raise RuntimeError(f"libbirdnet_hip ABI {lib.bn_version()} != binding ABI {ABI_VERSION}")

@@ -9,7 +9,8 @@ The backbone runs once over all files (``embed``'s device path), the head is tra
 ``--n_trials`` heads train at once on the device (``training/tune.py``), the one with the lowest validation loss is written, and
 ``<output>_tune.json`` lists them all.  For long-tailed folders: ``--upsample_ratio`` repeats training files of the small classes,
 ``--class_weights balanced`` weighs the rows by inverse class frequency and ``--loss focal`` trains on the focal loss; they combine with
-each other and with the plain fit, ``--tune`` and the augmented fit.  With ``--export_tflite`` on an INT8 ``.tflite`` backbone the head is
+each other and with the plain fit, ``--tune`` and the augmented fit.  ``--hidden_units H`` puts one ReLU layer of H units between embedding
+and classes (the plain fit only).  With ``--export_tflite`` on an INT8 ``.tflite`` backbone the head is
 also quantised and written into ``<output>.tflite`` (``conversion/head_export.py``), next to the labels and config: a model for
 ``evaluate``, ``analyze`` and the board.  ``--qat_epochs N`` then fine-tunes the head for N epochs against that quantisation first
 (``training/probe_qat.py``) and writes whichever of the two heads scores better as INT8.
@@ -34,6 +35,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--weight_decay", type=float, default=0.0, help="Weight decay (adamw only)")
     p.add_argument("--grad_clip", type=float, default=1.0, help="Gradient clipping by global norm (0 to disable)")
     p.add_argument("--dropout", type=float, default=0.5, help="Dropout rate in front of the head")
+    p.add_argument("--hidden_units", type=int, default=0,
+                   help="Units of one ReLU layer between embedding and classes, with dropout in front of both layers; 0 = none, the linear head "
+                        "(the default).  Not with --tune, --export_tflite / --qat_epochs, --mixup_probability or --spec_augment")
     p.add_argument("--label_smoothing", type=float, default=0.0,
                    help="Label smoothing of the training loss, in [0, 1); 0 = off (the default here; the reference's `train` defaults to 0.1).  "
                         "The validation loss is never smoothed")
@@ -98,8 +102,9 @@ def main(argv=None, runner=None):
         from birdnet_stm32.audio.pipeline import selection_from_args
 
         selection_from_args(args)   # (bad selection flags are refused before anything is loaded, as `embed` does)
-        from birdnet_stm32.training.linear_probe import augmentation_from_args, imbalance_from_args
+        from birdnet_stm32.training.linear_probe import augmentation_from_args, hidden_from_args, imbalance_from_args
 
+        hidden_from_args(args)         # (--hidden_units with a path that is not built for it)
         augmentation_from_args(args)   # (and bad augmentation flags; run_linear_probe refuses bad --tune / --label_smoothing combinations first thing)
         imbalance_from_args(args)      # (and focal with softmax, a bad --focal_gamma or --upsample_ratio)
         from birdnet_stm32.training.linear_probe import check_export_args

@@ -162,11 +162,14 @@ class QuantizedHead:
 
 
 # -- quantise -------------------------------------------------------------------------------------------------------------------------
-def quantize_head(head, emb_scale: float, emb_zero_point: int, logit_lo: float, logit_hi: float, per_tensor: bool = False) -> QuantizedHead:
+def quantize_head(head, emb_scale: float, emb_zero_point: int, logit_lo: float, logit_hi: float, per_tensor: bool = False, hidden_units=0) -> QuantizedHead:
     """Quantise ``head`` (a ``ProbeHead``: ``W [D, C]``, ``b [C]``) for int8 embeddings at ``(emb_scale, emb_zero_point)`` whose logits
-    were seen in ``[logit_lo, logit_hi]``.  Deterministic: the same arguments give the same head."""
+    were seen in ``[logit_lo, logit_hi]``.  Deterministic: the same arguments give the same head.  A head with a hidden layer
+    (``head.W1``, or ``hidden_units > 0``) is refused: the export is built for the linear head only."""
     from birdnet_stm32.models._lower_i8 import _expect_acc_range
+    from birdnet_stm32.training.linear_probe import refuse_hidden
 
+    refuse_hidden("quantize_head", hidden_units, head)
     if not (np.isfinite(logit_lo) and np.isfinite(logit_hi) and logit_lo <= logit_hi):
         raise ValueError(f"bad logit range [{logit_lo}, {logit_hi}]")
     if not (np.isfinite(emb_scale) and emb_scale > 0 and -128 <= int(emb_zero_point) <= 127):
@@ -353,16 +356,19 @@ def float_logit_range(head, rows_i8, emb_scale: float, emb_zero_point: int, bloc
     return lo, hi
 
 
-def export_head_tflite(head, backbone_path: str, rows_i8, out_path: str, per_tensor: bool = False, ctx=None, logit_range=None) -> dict:
+def export_head_tflite(head, backbone_path: str, rows_i8, out_path: str, per_tensor: bool = False, ctx=None, logit_range=None, hidden_units=0) -> dict:
     """Write ``head`` into a copy of the INT8 model at ``backbone_path`` as ``out_path``; ``rows_i8 [n, D]`` (int8 embedding bytes, CUDA
     tensor or numpy) calibrate the logit tensor.  ``logit_range = (lo, hi)`` replaces the range observed over ``rows_i8``: the range a
     head fine-tuned by ``training.probe_qat.fit_probe_qat`` was trained against, so that the file's logit parameters are those.  Returns ``{"qhead", "logit_range", "logit_scale", "logit_zero_point", "clipped_share",
-    "path", ...}``; ``clipped_share`` is the share of logit bytes at -128 or 127 over ``rows_i8`` (``bn_head_i8_forward``)."""
+    "path", ...}``; ``clipped_share`` is the share of logit bytes at -128 or 127 over ``rows_i8`` (``bn_head_i8_forward``).  A head with a
+    hidden layer (``head.W1``, or ``hidden_units > 0``) is refused before anything is read."""
     import torch
 
     from birdnet_stm32.models._tflite_reader import load_tflite
     from birdnet_stm32.models._tflite_writer import write_tflite
+    from birdnet_stm32.training.linear_probe import refuse_hidden
 
+    refuse_hidden("export_head_tflite", hidden_units, head)
     if not str(backbone_path).endswith(".tflite"):
         raise ValueError(f"{backbone_path}: the head is grafted onto an INT8 .tflite (heads on float backbones are not exported)")
     backbone = load_tflite(backbone_path)

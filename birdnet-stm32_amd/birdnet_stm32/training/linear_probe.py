@@ -11,6 +11,8 @@ on the ``[N, D]`` matrix, which stays on the device for the whole fit (``csrc/bn
 * ``fit_probe_augmented``  the device fit on fresh embeddings per epoch: mixup and SpecAugment over resident model inputs
   (``training/augment.py``, ``csrc/bn_augment.hip``), and ``fit_probe_augmented_reference``, the same loop in numpy,
 * ``ProbeHead``            the result: ``W [D, C]``, ``b [C]``, activation, class names; ``save`` / ``load`` (plain ``.npz``), ``predict``,
+* ``hidden_units = H > 0`` of ``fit_probe`` / ``fit_probe_reference``: one ReLU layer between embedding and classes, with dropout in front
+  of both layers (``csrc/bn_probe_mlp.hip``, C ABI ``bn_probe_mlp_*``; ``mlp_loss_and_gradient`` is the step's definition),
 * ``run_linear_probe``     class folders -> embeddings -> head -> files on disk (the ``probe`` command).
 
 The procedure (both implementations): Glorot-uniform ``W`` from ``default_rng(seed)``, zero ``b``; per epoch a permutation from
@@ -82,6 +84,64 @@ def init_head(D: int, C: int, seed: int) -> tuple[np.ndarray, np.ndarray]:
     limit = math.sqrt(6.0 / (D + C))
     W = np.random.default_rng(seed).uniform(-limit, limit, (D, C)).astype(np.float32)
     return W, np.zeros(C, np.float32)
+
+
+DROP2_SEED_XOR = 0x48494444   # the hidden layer's dropout draws: ``dropout_mask(seed ^ DROP2_SEED_XOR, t, B, H, p)``
+
+
+def init_mlp_head(D: int, H: int, C: int, seed: int) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """``(W1 [D, H], b1 [H], W2 [H, C], b2 [C])`` of a head with ``H`` hidden units: ``init_head(D, H, seed)`` and ``init_head(H, C, seed + 1)``."""
+    return (*init_head(D, H, seed), *init_head(H, C, seed + 1))
+
+
+def refuse_hidden(what: str, hidden_units=0, head=None) -> None:
+    """The paths that are not built for a hidden layer say so: none of them drops the layer silently."""
+    if int(hidden_units or 0) > 0 or (head is not None and getattr(head, "W1", None) is not None):
+        raise ValueError(f"{what} is not built for a head with a hidden layer (hidden_units > 0): train such a head with fit_probe / "
+                         "`probe --hidden_units` alone, or drop the hidden layer")
+
+
+def check_hidden_units(hidden_units, device: bool = False) -> int:
+    H = int(hidden_units)
+    if H != hidden_units or H < 0:
+        raise ValueError(f"hidden_units must be an integer >= 0 (0 = no hidden layer), got {hidden_units!r}")
+    if device and H > 0:
+        from birdnet_stm32 import _hip
+
+        if H > _hip.PROBE_MAX_D:
+            raise ValueError(f"the device path takes hidden_units <= {_hip.PROBE_MAX_D}, got {H}")
+    return H
+
+
+def mlp_forward(X: np.ndarray, W1: np.ndarray, b1: np.ndarray, W2: np.ndarray, b2: np.ndarray, activation: str) -> np.ndarray:
+    """Scores of a head with a hidden layer, without dropout: ``act(relu(X W1 + b1) W2 + b2)``."""
+    return head_scores(np.maximum(X @ W1 + b1, X.dtype.type(0)), W2, b2, activation)
+
+
+def mlp_loss_and_gradient(params: np.ndarray, xd: np.ndarray, m2: np.ndarray, y: np.ndarray, activation: str, *, loss="auto", focal_gamma=2.0,
+                          sample_weight=None, relu_gate: bool = True):
+    """One training step of the head with a hidden layer, before clip and optimiser, in ``params``' dtype.  ``params``: the vector
+    ``[(D + 1) H | (H + 1) C]`` (``W1`` then ``b1`` as row ``D``; ``W2`` then ``b2`` as row ``H``); ``xd [B, D + 1]``: the batch after
+    ``drop1`` with the column of ones; ``m2 [B, H]``: ``drop2``'s mask (``keep / (1 - p)``).  Returns ``(loss, gradient vector, parts)``:
+
+        a = xd [W1; b1];  hd = relu(a) m2;  z = [hd, 1] [W2; b2];  G = dLoss/dz (probe_loss_gradient)
+        dW2 = [hd, 1]^T G;  dA = (G W2^T) m2 [a > 0];  dW1 = xd^T dA
+
+    ``parts``: ``a``, ``hd``, ``P``, ``G``, ``GW`` (``G W2^T``), ``dA``.  ``relu_gate=False`` leaves ``[a > 0]`` out of ``dA``: the gradient of no
+    loss, there for tests that must tell a wrong gate from rounding."""
+    dt = params.dtype.type
+    B, D1 = xd.shape
+    H, C = m2.shape[1], y.shape[1]
+    P1, P2 = params[: D1 * H].reshape(D1, H), params[D1 * H :].reshape(H + 1, C)
+    a = xd[:, : D1 - 1] @ P1[: D1 - 1] + P1[D1 - 1]
+    hd = np.concatenate([np.maximum(a, dt(0)) * m2, np.ones((B, 1), params.dtype)], axis=1)
+    P = head_scores(hd[:, :H], P2[:H], P2[H], activation)
+    value = probe_loss(P, y, activation, loss=loss, focal_gamma=focal_gamma, sample_weight=sample_weight)
+    G = probe_loss_gradient(P, y, activation, loss=loss, focal_gamma=focal_gamma, sample_weight=sample_weight)
+    GW = G @ P2[:H].T
+    dA = GW * m2 * (a > 0) if relu_gate else GW * m2
+    g = np.concatenate([(xd.T @ dA).ravel(), (hd.T @ G).ravel()])
+    return value, g, {"a": a, "hd": hd[:, :H], "P": P, "G": G, "GW": GW, "dA": dA}
 
 
 def epoch_permutation(seed: int, epoch: int, n: int) -> np.ndarray:
@@ -318,10 +378,13 @@ class _FitPlan:
     has_val: bool
     W0: np.ndarray | None   # the initial head; None in the plan of a fit that hands over to a sweep
     b0: np.ndarray | None
+    hidden: int = 0         # hidden units; > 0: W0 / b0 are the output layer [hidden, C], W1_0 / b1_0 the hidden layer [D, hidden]
+    W1_0: np.ndarray | None = None
+    b1_0: np.ndarray | None = None
 
 
 def _plan_fit(X, Y, X_val, *, device: bool, activation, optimizer, batch_size, dropout, epochs, learning_rate=1e-3, weight_decay=0.0, clipnorm=1.0,
-              patience=10, seed=42, label_smoothing=0.0, loss="auto", focal_gamma=2.0, sample_weight=None, rows=None) -> _FitPlan:
+              patience=10, seed=42, label_smoothing=0.0, loss="auto", focal_gamma=2.0, sample_weight=None, rows=None, hidden_units=0) -> _FitPlan:
     """The checks every fit runs, in one order, and what follows from the arguments.  ``X``: anything with the ``shape`` of the training
     rows.  ``device``: the fit runs on the device, which takes D and C up to ``_hip.PROBE_MAX_D`` / ``PROBE_MAX_C`` and ``clipnorm`` as the
     Python float; the numpy fits round ``clipnorm`` through float32, as the C ABI does."""
@@ -331,23 +394,28 @@ def _plan_fit(X, Y, X_val, *, device: bool, activation, optimizer, batch_size, d
     loss, focal_gamma = _check_loss(loss, focal_gamma, activation)
     n, D, C = int(X.shape[0]), int(X.shape[1]), int(Y.shape[1])
     sample_weight, rows = _check_weights_rows(n, sample_weight, rows)
-    W0 = b0 = None
+    W0 = b0 = W1_0 = b1_0 = None
+    H = check_hidden_units(hidden_units, device)
     if device:
         from birdnet_stm32 import _hip
 
         label_smoothing = _check_label_smoothing(label_smoothing)
     # A single device fit with smoothing runs as a sweep of one trial, which makes its own plan: the D/C refusal and the head are that one's
-    if not (device and label_smoothing > 0):
+    # (with a hidden layer it does not: the targets are smoothed once on the host)
+    if H > 0 or not (device and label_smoothing > 0):
         if device and not (1 <= D <= _hip.PROBE_MAX_D and 1 <= C <= _hip.PROBE_MAX_C):
             raise ValueError(f"the device path takes 1 <= D <= {_hip.PROBE_MAX_D} and 1 <= C <= {_hip.PROBE_MAX_C}, got D={D} C={C}")
-        W0, b0 = init_head(D, C, seed)
+        if H > 0:
+            W1_0, b1_0, W0, b0 = init_mlp_head(D, H, C, seed)
+        else:
+            W0, b0 = init_head(D, C, seed)
     m = n if rows is None else len(rows)
     batch = min(int(batch_size), m)
     return _FitPlan(activation=activation, optimizer=optimizer, lr=float(learning_rate), weight_decay=float(weight_decay),
                     clipnorm=float(clipnorm) if device else float(np.float32(clipnorm)), dropout=float(dropout), label_smoothing=label_smoothing,
                     loss=loss, focal_gamma=focal_gamma, sample_weight=sample_weight, rows=rows, n=n, D=D, C=C, m=m, batch=batch, epochs=int(epochs),
                     patience=int(patience), seed=int(seed), total=int(epochs) * math.ceil(m / batch), has_val=X_val is not None and len(X_val) > 0,
-                    W0=W0, b0=b0)
+                    W0=W0, b0=b0, hidden=H, W1_0=W1_0, b1_0=b1_0)
 
 
 class _EarlyStopping:
@@ -400,29 +468,43 @@ def _fit_loop(backend, plan: _FitPlan) -> dict:
 # -- the result -----------------------------------------------------------------------------------------------------------------------
 @dataclass
 class ProbeHead:
-    """A trained head: ``scores = act(x W + b)`` over embedding rows of width ``embedding_dim``."""
+    """A trained head: ``scores = act(x W + b)`` over embedding rows of width ``embedding_dim``.  With a hidden layer (``W1 [D, H]``,
+    ``b1 [H]``; ``hidden_units = H``): ``scores = act(relu(x W1 + b1) W + b)``, and ``W [H, C]``, ``b`` are the output layer."""
 
     W: np.ndarray
     b: np.ndarray
     activation: str = "sigmoid"
     class_names: list = field(default_factory=list)
     history: dict = field(default_factory=dict)
+    W1: np.ndarray | None = None
+    b1: np.ndarray | None = None
 
     def __post_init__(self):
         self.W = np.ascontiguousarray(self.W, np.float32)
         self.b = np.ascontiguousarray(self.b, np.float32)
         if self.W.ndim != 2 or self.b.shape != (self.W.shape[1],):
             raise ValueError(f"W must be [D, C] and b [C], got {self.W.shape} and {self.b.shape}")
+        if (self.W1 is None) != (self.b1 is None):
+            raise ValueError("a hidden layer is W1 and b1 together")
+        if self.W1 is not None:
+            self.W1 = np.ascontiguousarray(self.W1, np.float32)
+            self.b1 = np.ascontiguousarray(self.b1, np.float32)
+            if self.W1.ndim != 2 or self.b1.shape != (self.W1.shape[1],) or self.W1.shape[1] != self.W.shape[0]:
+                raise ValueError(f"W1 must be [D, H], b1 [H] and W [H, C], got {self.W1.shape}, {self.b1.shape} and {self.W.shape}")
         if self.activation not in ACTIVATIONS:
             raise ValueError(f"activation must be one of {ACTIVATIONS}, not {self.activation!r}")
         self.class_names = [str(c) for c in self.class_names]
         if self.class_names and len(self.class_names) != self.W.shape[1]:
             raise ValueError(f"{len(self.class_names)} class names for {self.W.shape[1]} classes")
-        self._device = {}   # per device index: [own context or None, W, b on the device]; W and b are fixed once the head exists
+        self._device = {}   # per device index: [own context or None, W, b (, W1, b1) on the device]; they are fixed once the head exists
 
     @property
     def embedding_dim(self) -> int:
-        return int(self.W.shape[0])
+        return int((self.W if self.W1 is None else self.W1).shape[0])
+
+    @property
+    def hidden_units(self) -> int:
+        return 0 if self.W1 is None else int(self.W1.shape[1])
 
     @property
     def num_classes(self) -> int:
@@ -435,23 +517,30 @@ class ProbeHead:
     def save(self, path: str) -> None:
         """A plain ``.npz`` (``np.load(path)`` reads it without this package)."""
         hist = {k: np.asarray(v, np.float64) for k, v in self.history.items() if k in ("loss", "val_loss")}
+        hidden = {} if self.W1 is None else {"W1": self.W1, "b1": self.b1, "hidden_units": np.int64(self.hidden_units)}
         np.savez(path, W=self.W, b=self.b, activation=np.str_(self.activation), class_names=np.asarray(self.class_names, dtype=np.str_),
-                 embedding_dim=np.int64(self.embedding_dim), **{f"history_{k}": v for k, v in hist.items()})
+                 embedding_dim=np.int64(self.embedding_dim), **hidden, **{f"history_{k}": v for k, v in hist.items()})
 
     @classmethod
     def load(cls, path: str) -> "ProbeHead":
         with np.load(path, allow_pickle=False) as z:
             hist = {k[len("history_"):]: z[k].tolist() for k in z.files if k.startswith("history_")}
-            head = cls(z["W"], z["b"], str(z["activation"]), [str(c) for c in z["class_names"]], hist)
+            hidden = ("W1" in z.files, "b1" in z.files, "hidden_units" in z.files)
+            if any(hidden) and not all(hidden):
+                raise ValueError(f"{path}: a hidden layer is W1, b1 and hidden_units together")
+            head = cls(z["W"], z["b"], str(z["activation"]), [str(c) for c in z["class_names"]], hist, *((z["W1"], z["b1"]) if all(hidden) else ()))
+            if all(hidden) and int(z["hidden_units"]) != head.hidden_units:
+                raise ValueError(f"{path}: hidden_units {int(z['hidden_units'])} does not match W1 {head.W1.shape}")
             if "embedding_dim" in z.files and int(z["embedding_dim"]) != head.embedding_dim:
-                raise ValueError(f"{path}: embedding_dim {int(z['embedding_dim'])} does not match W {head.W.shape}")
+                raise ValueError(f"{path}: embedding_dim {int(z['embedding_dim'])} does not match {'W' if head.W1 is None else 'W1'} "
+                                 f"{(head.W if head.W1 is None else head.W1).shape}")
         return head
 
     def close(self) -> None:
         """Drop the device copies of ``W`` / ``b`` and close the contexts ``predict`` opened for itself (none when it was given one)."""
-        for own_ctx, _w, _b in self._device.values():
-            if own_ctx is not None:
-                own_ctx.close()
+        for slot in self._device.values():
+            if slot[0] is not None:
+                slot[0].close()
         self._device = {}
 
     def __enter__(self):
@@ -462,7 +551,8 @@ class ProbeHead:
         return False
 
     def predict_device(self, emb, ctx=None):
-        """Scores ``[N, C]`` of a contiguous float32 CUDA tensor ``[N, D]`` (``bn_head_forward``), as a CUDA tensor.  ``ctx``: the
+        """Scores ``[N, C]`` of a contiguous float32 CUDA tensor ``[N, D]`` (``bn_head_forward``; with a hidden layer
+        ``bn_head_mlp_forward``), as a CUDA tensor.  ``ctx``: the
         caller's ``_hip.Context`` (a runner's ``ctx``); without one the head opens its own per device and keeps it until ``close()``."""
         import ctypes
 
@@ -475,13 +565,18 @@ class ProbeHead:
         self.check_embedding_dim(emb.shape[1])
         dev = emb.device.index or 0
         if dev not in self._device:
-            self._device[dev] = [None, torch.from_numpy(self.W).to(emb.device), torch.from_numpy(self.b).to(emb.device)]
+            self._device[dev] = [None, *(torch.from_numpy(a).to(emb.device) for a in ((self.W, self.b) if self.W1 is None else (self.W, self.b, self.W1, self.b1)))]
         slot = self._device[dev]
         if ctx is None:
             ctx = slot[0] = slot[0] or _hip.Context(dev, 1)
         out = torch.empty((emb.shape[0], self.num_classes), dtype=torch.float32, device=emb.device)
         with torch.cuda.device(emb.device):
             stream = ctypes.c_void_p(torch.cuda.current_stream(emb.device).cuda_stream)
+            if self.W1 is not None:
+                _hip.check(ctx.lib.bn_head_mlp_forward(ctx.handle, emb.data_ptr(), emb.shape[0], self.embedding_dim, slot[3].data_ptr(), slot[4].data_ptr(),
+                                                       self.hidden_units, slot[1].data_ptr(), slot[2].data_ptr(), self.num_classes,
+                                                       _hip.PROBE_ACTIVATIONS[self.activation], out.data_ptr(), stream))
+                return out
             _hip.check(ctx.lib.bn_head_forward(ctx.handle, emb.data_ptr(), emb.shape[0], self.embedding_dim, slot[1].data_ptr(), slot[2].data_ptr(),
                                                self.num_classes, _hip.PROBE_ACTIVATIONS[self.activation], out.data_ptr(), stream))
         return out
@@ -539,15 +634,68 @@ class _NumpyBackend:
         self.P = np.concatenate([W, b[None, :]]).astype(self.dt)
 
 
+class _NumpyMlpBackend(_NumpyBackend):
+    """The head with a hidden layer: the parameters are one vector ``[(D + 1) H | (H + 1) C]``, so clip and optimiser see one norm and one
+    schedule; a step is ``mlp_loss_and_gradient``.  The training targets are smoothed once, here; the validation loss takes them raw."""
+
+    def __init__(self, X, Y, X_val, Y_val, plan, dtype):
+        cast = lambda a: None if a is None else np.asarray(a).astype(dtype)  # noqa: E731
+        self.X, self.Y, self.plan, self.dt = cast(X), cast(Y), plan, np.dtype(dtype).type
+        self.Xv, self.Yv = (cast(X_val), cast(Y_val)) if plan.has_val else (None, None)
+        self.w = cast(plan.sample_weight)
+        self.loss_kw = dict(loss=plan.loss, focal_gamma=plan.focal_gamma)
+        self.Yt = smooth_targets(self.Y, plan.label_smoothing, plan.activation) if plan.label_smoothing > 0 else self.Y
+        self.D, self.H, self.C = self.X.shape[1], plan.hidden, self.Y.shape[1]
+        self.set(plan.W1_0, plan.b1_0, plan.W0, plan.b0)
+        self.state = {"m": np.zeros_like(self.P), "v": np.zeros_like(self.P)}
+        self.t = 0
+
+    def epoch(self, perm):
+        c, dt, D, H = self.plan, self.dt, self.D, self.H
+        losses = []
+        for s in range(0, len(perm), c.batch):
+            idx = perm[s : s + c.batch]
+            B = len(idx)
+            xd = np.concatenate([self.X[idx] * dropout_mask(c.seed, self.t, B, D, c.dropout, dt), np.ones((B, 1), dt)], axis=1)
+            m2 = dropout_mask(c.seed ^ DROP2_SEED_XOR, self.t, B, H, c.dropout, dt)
+            w = None if self.w is None else self.w[idx]
+            value, g, _ = mlp_loss_and_gradient(self.P, xd, m2, self.Yt[idx], c.activation, sample_weight=w, **self.loss_kw)
+            losses.append(float(value))
+            g = clip_by_global_norm(g, c.clipnorm)
+            lr_t, alpha_t = step_sizes(c.lr, self.t, c.total)
+            self.P = optimizer_step(self.P, g, self.state, c.optimizer, np.float32(lr_t), np.float32(alpha_t), np.float32(c.weight_decay))
+            self.t += 1
+        return losses
+
+    def val_loss(self):   # the loss that was asked for, never weighted, never smoothed
+        return probe_loss(mlp_forward(self.Xv, *self.get(), self.plan.activation), self.Yv, self.plan.activation, **self.loss_kw)
+
+    def get(self):
+        D, H, C = self.D, self.H, self.C
+        P1, P2 = self.P[: (D + 1) * H].reshape(D + 1, H), self.P[(D + 1) * H :].reshape(H + 1, C)
+        return P1[:D].copy(), P1[D].copy(), P2[:H].copy(), P2[H].copy()
+
+    def set(self, W1, b1, W2, b2):
+        self.P = np.concatenate([np.asarray(W1).ravel(), np.asarray(b1).ravel(), np.asarray(W2).ravel(), np.asarray(b2).ravel()]).astype(self.dt)
+
+
 def fit_probe_reference(X, Y, X_val=None, Y_val=None, *, activation="sigmoid", epochs=50, batch_size=32, learning_rate=1e-3, optimizer="adam",
                         weight_decay=0.0, clipnorm=1.0, dropout=0.5, patience=10, seed=42, dtype=np.float64, class_names=None,
-                        label_smoothing=0.0, loss="auto", focal_gamma=2.0, sample_weight=None, rows=None) -> ProbeHead:
-    """The procedure of ``fit_probe`` in numpy, all arithmetic in ``dtype``.  ``history["W"]`` / ``["b"]`` keep the result in ``dtype``.
-    ``loss`` / ``focal_gamma`` / ``sample_weight`` / ``rows``: see ``fit_probe``."""
+                        label_smoothing=0.0, loss="auto", focal_gamma=2.0, sample_weight=None, rows=None, hidden_units=0) -> ProbeHead:
+    """The procedure of ``fit_probe`` in numpy, all arithmetic in ``dtype``.  ``history["W"]`` / ``["b"]`` keep the result in ``dtype``
+    (with ``hidden_units > 0`` also ``["W1"]`` / ``["b1"]``).  ``loss`` / ``focal_gamma`` / ``sample_weight`` / ``rows`` / ``hidden_units``: see
+    ``fit_probe``."""
     X, Y = np.asarray(X), np.asarray(Y)
     plan = _plan_fit(X, Y, X_val, device=False, activation=activation, optimizer=optimizer, batch_size=batch_size, dropout=dropout, epochs=epochs,
                      learning_rate=learning_rate, weight_decay=weight_decay, clipnorm=clipnorm, patience=patience, seed=seed,
-                     label_smoothing=label_smoothing, loss=loss, focal_gamma=focal_gamma, sample_weight=sample_weight, rows=rows)
+                     label_smoothing=label_smoothing, loss=loss, focal_gamma=focal_gamma, sample_weight=sample_weight, rows=rows,
+                     hidden_units=hidden_units)
+    if plan.hidden > 0:
+        be = _NumpyMlpBackend(X, Y, X_val, Y_val, plan, dtype)
+        history = _fit_loop(be, plan)
+        W1, b1, W, b = be.get()
+        history.update(W1=W1, b1=b1, W=W, b=b)
+        return ProbeHead(W, b, plan.activation, list(class_names or []), history, W1, b1)
     return _reference_fit(_NumpyBackend(X, Y, X_val, Y_val, plan, dtype), plan, class_names)
 
 
@@ -652,6 +800,60 @@ class _DeviceBackend:
             self.handle = None
 
 
+class _MlpDeviceBackend(_DeviceBackend):
+    """``bn_probe_mlp_*`` over resident ``X`` / ``Y``: ``self.W`` / ``self.b`` are the output layer, ``self.W1`` / ``self.b1`` the hidden one.
+    ``Y`` is what the steps train on (smoothed by the caller when asked for), ``Y_val`` the raw validation targets."""
+
+    SET_LOSS, DESTROY = "bn_probe_mlp_set_loss", "bn_probe_mlp_destroy"
+
+    def _create(self, out):
+        c, hip = self.plan, self.hip
+        self.W1, self.b1 = self._dev(c.W1_0), self._dev(c.b1_0)
+        return self.ctx.lib.bn_probe_mlp_create(self.ctx.handle, self.D, c.hidden, self.C, hip.PROBE_ACTIVATIONS[c.activation],
+                                                hip.PROBE_OPTIMIZERS[c.optimizer], c.lr, c.weight_decay, c.clipnorm, c.dropout, c.seed & 0xFFFFFFFF, c.total,
+                                                self.W1.data_ptr(), self.b1.data_ptr(), self.W.data_ptr(), self.b.data_ptr(), out, self._stream())
+
+    def epoch(self, perm):
+        self._check_perm(perm)
+        with self.torch.cuda.device(self.dev):
+            d_perm = self.torch.from_numpy(perm).to(self.dev)
+            self.hip.check(self.ctx.lib.bn_probe_mlp_epoch_weighted(self.handle, self.X.data_ptr(), self.Y.data_ptr(), self._ptr(self.w), d_perm.data_ptr(),
+                                                                    self.m, self.plan.batch, self.step_loss.data_ptr(), self._stream()))
+            return self.step_loss.cpu().numpy()   # (synchronises: d_perm outlives the epoch)
+
+    def val_loss(self):
+        with self.torch.cuda.device(self.dev):
+            self.hip.check(self.ctx.lib.bn_probe_mlp_loss(self.handle, self.Xv.data_ptr(), self.Yv.data_ptr(), self.Xv.shape[0], self.val.data_ptr(),
+                                                          self._stream()))
+            return float(self.val.item())
+
+    def get(self):
+        out = [self.torch.empty_like(t) for t in (self.W1, self.b1, self.W, self.b)]
+        with self.torch.cuda.device(self.dev):
+            self.hip.check(self.ctx.lib.bn_probe_mlp_get(self.handle, *(t.data_ptr() for t in out), self._stream()))
+        return tuple(out)
+
+    def set(self, W1, b1, W, b):
+        with self.torch.cuda.device(self.dev):
+            self.hip.check(self.ctx.lib.bn_probe_mlp_set(self.handle, W1.data_ptr(), b1.data_ptr(), W.data_ptr(), b.data_ptr(), self._stream()))
+            self.torch.cuda.current_stream(self.dev).synchronize()
+
+
+def _mlp_device_fit(ctx, X, Y, X_val, Y_val, plan: _FitPlan, class_names) -> ProbeHead:
+    """``fit_probe`` with a hidden layer: the targets smoothed once on the host, then epochs, the best weights, the head."""
+    if plan.label_smoothing > 0:
+        import torch
+
+        Y = smooth_targets(np.ascontiguousarray(Y.cpu().numpy() if isinstance(Y, torch.Tensor) else Y, np.float32), plan.label_smoothing, plan.activation)
+    be = _MlpDeviceBackend(ctx, X, Y, X_val, Y_val, plan)
+    try:
+        history = _fit_loop(be, plan)
+        W1, b1, W, b = (t.cpu().numpy() for t in be.get())
+    finally:
+        be.close()
+    return ProbeHead(W, b, plan.activation, list(class_names or []), history, W1, b1)
+
+
 def _device_fit(be, plan: _FitPlan, class_names) -> ProbeHead:
     """The fit on a device backend made for ``plan``, which it closes: epochs, the best weights, the head."""
     try:
@@ -665,7 +867,7 @@ def _device_fit(be, plan: _FitPlan, class_names) -> ProbeHead:
 
 def fit_probe(ctx_or_runner, X, Y, X_val=None, Y_val=None, *, activation="sigmoid", epochs=50, batch_size=32, learning_rate=1e-3, optimizer="adam",
               weight_decay=0.0, clipnorm=1.0, dropout=0.5, patience=10, seed=42, class_names=None, label_smoothing=0.0, loss="auto", focal_gamma=2.0,
-              sample_weight=None, rows=None) -> ProbeHead:
+              sample_weight=None, rows=None, hidden_units=0) -> ProbeHead:
     """Train ``scores = act(dropout(x) W + b)`` on embedding rows ``X [N, D]`` with targets ``Y [N, C]`` (float: one-hot, multi-hot or
     all-zero rows) on the device.  ``X`` / ``Y`` may be numpy arrays or CUDA tensors; they stay on the device for the whole fit, per epoch
     the host uploads one permutation and reads back the per-step losses.  The defaults are the reference CLI's.  The same inputs and seed
@@ -680,10 +882,18 @@ def fit_probe(ctx_or_runner, X, Y, X_val=None, Y_val=None, *, activation="sigmoi
     * ``rows``: int ``[M]``, row numbers into ``X``, repeats allowed (``upsample_rows``).  An epoch then runs over
       ``rows[epoch_permutation(seed, e, M)]``; the steps per epoch and the short last batch follow ``M``.  ``X``, ``Y`` and
       ``sample_weight`` are indexed through it and nothing is duplicated on the device.  The dropout draw is per position in the batch,
-      so two copies of a row in one batch get different masks."""
+      so two copies of a row in one batch get different masks.
+
+    ``hidden_units = H > 0`` trains ``scores = act(dropout2(relu(dropout(x) W1 + b1)) W2 + b2)`` instead (``bn_probe_mlp_*``): one ReLU layer of
+    ``H`` units, ``1 <= H <= _hip.PROBE_MAX_D``, dropout at the same rate in front of both layers (the second mask is drawn with
+    ``seed ^ DROP2_SEED_XOR``), one global norm and one schedule over all four arrays.  Everything above composes; label smoothing is
+    applied to the training targets once on the host.  The head's ``W`` / ``b`` are then the output layer, ``W1`` / ``b1`` the hidden one."""
     plan = _plan_fit(X, Y, X_val, device=True, activation=activation, optimizer=optimizer, batch_size=batch_size, dropout=dropout, epochs=epochs,
                      learning_rate=learning_rate, weight_decay=weight_decay, clipnorm=clipnorm, patience=patience, seed=seed,
-                     label_smoothing=label_smoothing, loss=loss, focal_gamma=focal_gamma, sample_weight=sample_weight, rows=rows)
+                     label_smoothing=label_smoothing, loss=loss, focal_gamma=focal_gamma, sample_weight=sample_weight, rows=rows,
+                     hidden_units=hidden_units)
+    if plan.hidden > 0:
+        return _mlp_device_fit(getattr(ctx_or_runner, "ctx", ctx_or_runner), X, Y, X_val, Y_val, plan, class_names)
     if plan.label_smoothing > 0:
         trial = ProbeTrial(learning_rate=learning_rate, optimizer=optimizer, weight_decay=weight_decay, clipnorm=clipnorm, dropout=dropout,
                            label_smoothing=label_smoothing)
@@ -799,7 +1009,7 @@ class _SweepBackend(_DeviceBackend):
 
 
 def fit_probe_sweep(ctx_or_runner, X, Y, X_val=None, Y_val=None, trials=(), *, activation="sigmoid", epochs=50, batch_size=32, patience=10, seed=42,
-                    class_names=None, loss="auto", focal_gamma=2.0, sample_weight=None, rows=None) -> SweepResult:
+                    class_names=None, loss="auto", focal_gamma=2.0, sample_weight=None, rows=None, hidden_units=0) -> SweepResult:
     """``fit_probe`` for every ``ProbeTrial`` of ``trials`` at once (at most ``_hip.PROBE_SWEEP_MAX_TRIALS``).  The trials share the rows, the
     initial weights, the permutations and the dropout draws; one training step of all of them is the launches of a single fit's step with
     the trial as one more grid axis, which is what makes a sweep cheap where one fit is launch-bound.  Early stopping is ``fit_probe``'s
@@ -810,6 +1020,7 @@ def fit_probe_sweep(ctx_or_runner, X, Y, X_val=None, Y_val=None, trials=(), *, a
     sees the smoothed target; the validation loss is the focal one, unweighted, unsmoothed."""
     from birdnet_stm32 import _hip
 
+    refuse_hidden("fit_probe_sweep", hidden_units)
     trials = _check_trials(trials)
     if len(trials) > _hip.PROBE_SWEEP_MAX_TRIALS:
         raise ValueError(f"{len(trials)} trials: a sweep takes at most {_hip.PROBE_SWEEP_MAX_TRIALS}")
@@ -945,7 +1156,7 @@ class _AugmentedDeviceBackend(_DeviceBackend):
 
 def fit_probe_augmented(runner, inputs, Y, X_val=None, Y_val=None, *, augment, input_shape, activation="sigmoid", epochs=50, batch_size=32,
                         learning_rate=1e-3, optimizer="adam", weight_decay=0.0, clipnorm=1.0, dropout=0.5, patience=10, seed=42,
-                        class_names=None, loss="auto", focal_gamma=2.0, sample_weight=None, rows=None) -> ProbeHead:
+                        class_names=None, loss="auto", focal_gamma=2.0, sample_weight=None, rows=None, hidden_units=0) -> ProbeHead:
     """``fit_probe`` on fresh embeddings per epoch (reference: training/linear_probe.py:112-125, whose training loader masks and mixes).
 
     ``inputs [N, F * W]``: the un-augmented model inputs of the training rows (``HipRunner.model_inputs_device``; a CUDA tensor stays
@@ -961,6 +1172,7 @@ def fit_probe_augmented(runner, inputs, Y, X_val=None, Y_val=None, *, augment, i
     built on, whatever rows were mixed into it."""
     import torch
 
+    refuse_hidden("fit_probe_augmented", hidden_units)
     F, W_in = _check_augmented_args(augment, activation, input_shape, inputs.shape[1] if len(inputs.shape) == 2 else None)
     if not hasattr(runner, "predict_device"):
         raise ValueError("fit_probe_augmented needs the model's runner: the backbone runs every epoch")
@@ -1079,6 +1291,20 @@ def imbalance_from_args(args) -> dict:
     if not 0.0 <= ratio <= 1.0:   # (NaN fails too)
         raise ValueError(f"--upsample_ratio must be 0 (off) or in (0, 1], got {ratio}")
     return {"loss": loss, "focal_gamma": gamma, "class_weights": class_weights, "upsample_ratio": ratio}
+
+
+def hidden_from_args(args) -> int:
+    """``--hidden_units`` of ``probe`` (absent in older namespaces: 0, no hidden layer); refused, before anything is loaded, with what is
+    not built for such a head: ``--tune``, ``--export_tflite`` / ``--qat_epochs``, ``--mixup_probability`` / ``--spec_augment``."""
+    H = check_hidden_units(getattr(args, "hidden_units", 0) or 0, device=True)
+    if H == 0:
+        return 0
+    for flag, on in (("--tune", getattr(args, "tune", False)), ("--export_tflite", getattr(args, "export_tflite", False)),
+                     ("--qat_epochs", int(getattr(args, "qat_epochs", 0) or 0) > 0),
+                     ("--mixup_probability", float(getattr(args, "mixup_probability", 0.0) or 0.0) > 0), ("--spec_augment", getattr(args, "spec_augment", False))):
+        if on:
+            raise ValueError(f"--hidden_units does not combine with {flag}: that path is not built for a head with a hidden layer")
+    return H
 
 
 def upsample_multiplicity(train_paths: list, classes: list, ratio: float) -> tuple[np.ndarray, list]:
@@ -1233,7 +1459,8 @@ def export_probe_tflite(head, runner, model_path: str, X, Y, report_rows, out: d
 
 def run_linear_probe(args, runner=None) -> ProbeHead:
     """The ``probe`` command: ``args.data_path_train/<class>/*`` -> embeddings (the backbone runs once) -> ``fit_probe`` ->
-    ``<output>.npz``, ``<output>_labels.txt``, ``<output>_model_config.json`` and ``<output>_history.csv``.  With ``args.tune``:
+    ``<output>.npz``, ``<output>_labels.txt``, ``<output>_model_config.json`` and ``<output>_history.csv``.  With ``args.hidden_units = H > 0``
+    the head has one ReLU layer of ``H`` units (``hidden_from_args``: on its own only).  With ``args.tune``:
     ``training.tune.sample_trials`` -> ``fit_probe_sweep``; the files are the winning trial's, ``<output>_tune.json`` lists all trials.
     With ``args.export_tflite`` (INT8 ``.tflite`` backbones): the written head also goes into ``<output>.tflite``, an ordinary model next
     to the labels and config written here, with ``<output>_export.json`` (``export_probe_tflite``); with ``args.qat_epochs`` the head is
@@ -1254,6 +1481,7 @@ def run_linear_probe(args, runner=None) -> ProbeHead:
 
     from birdnet_stm32.training.tune import check_tune_args
 
+    hidden = hidden_from_args(args)
     augment = augmentation_from_args(args)
     imb = imbalance_from_args(args)
     check_tune_args(args)
@@ -1343,7 +1571,7 @@ def run_linear_probe(args, runner=None) -> ProbeHead:
         tuned = {**tune_report(tuned, auc), **imb}   # shared by every trial, no part of the search space
     elif augment is None:
         head = fit_probe(runner, emb.embeddings[tr], Y[tr], emb.embeddings[va] if va.any() else None, Y[va] if va.any() else None,
-                         label_smoothing=label_smoothing, **fit_kw, **imb_kw)
+                         label_smoothing=label_smoothing, **fit_kw, **imb_kw, **({"hidden_units": hidden} if hidden else {}))
     else:
         import torch
 

@@ -173,14 +173,16 @@ def qat_logit_codes(ctx_or_runner, head, X, logit_range, per_tensor: bool = Fals
 
 def fit_probe_qat(ctx_or_runner, X, Y, X_val=None, Y_val=None, *, head, logit_range, per_tensor=False, quantize_logits=True, epochs=10,
                   learning_rate=1e-4, batch_size=32, optimizer="adam", weight_decay=0.0, clipnorm=1.0, dropout=0.5, patience=10, seed=42,
-                  class_names=None, loss="auto", focal_gamma=2.0, sample_weight=None, rows=None, label_smoothing=0.0, augment=None) -> lp.ProbeHead:
+                  class_names=None, loss="auto", focal_gamma=2.0, sample_weight=None, rows=None, label_smoothing=0.0, augment=None,
+                  hidden_units=0) -> lp.ProbeHead:
     """Fine-tune ``head`` on the device with the forward the INT8 export will compute: weights fake-quantised per class (one scale with
     ``per_tensor``), logits on the grid of ``choose_activation_params(*logit_range)`` (``quantize_logits``).  ``logit_range`` is the range
     the export will be given (``float_logit_range`` of the float head over the calibration rows).  The other keywords are ``fit_probe``'s;
     the procedure is ``fit_probe``'s too, starting from ``head`` instead of a fresh one, so the validation loss and early stopping are on
     the fake-quantised forward.  Returns a ``ProbeHead`` of the full-precision shadow weights, for ``quantize_head`` /
     ``export_head_tflite`` with the same ``logit_range``; ``history["qat"]`` holds the range, scale, zero point and flags.
-    ``label_smoothing`` and ``augment`` are refused: they are no part of the QAT phase."""
+    ``label_smoothing`` and ``augment`` are refused: they are no part of the QAT phase; so is a head with a hidden layer."""
+    lp.refuse_hidden("fit_probe_qat", hidden_units, head)
     lo, hi, s_out, z_out = _check_qat_args(head, logit_range, label_smoothing, augment)
     plan = _plan_qat(X, Y, X_val, head, True, dict(optimizer=optimizer, batch_size=batch_size, dropout=dropout, epochs=epochs, learning_rate=learning_rate,
                                                    weight_decay=weight_decay, clipnorm=clipnorm, patience=patience, seed=seed, loss=loss,

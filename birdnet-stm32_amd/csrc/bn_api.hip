@@ -221,6 +221,7 @@ void bn_ctx_destroy(bn_ctx* c) {
     if (c->d_kmeans_work) (void)hipFree(c->d_kmeans_work);
     if (c->d_tsne_work) (void)hipFree(c->d_tsne_work);
     if (c->d_boot_work) (void)hipFree(c->d_boot_work);
+    if (c->d_mlp_work) (void)hipFree(c->d_mlp_work);
     delete c;
 }
 
@@ -1043,7 +1044,7 @@ int bn_preload_kernels(bn_ctx* ctx) {
     // copies wait meanwhile).  A caller with idle time before its first batch — the evaluate pipeline while the first files are read — asks here.
     bn::preload_ingest(); bn::preload_stft(); bn::preload_stft_exact(); bn::preload_i8_fused(); bn::preload_i8_strip(); bn::preload_i8_tail2();
     bn::preload_i8_tail(); bn::preload_i8(); bn::preload_i8_pw(); bn::preload_f32(); bn::preload_f32_fused(); bn::preload_f32_strip();
-    bn::preload_f32_pw(); bn::preload_melspec(); bn::preload_sort(); bn::preload_probe(); bn::preload_probe_sweep(); bn::preload_activity(); bn::preload_search(); bn::preload_augment(); bn::preload_kmeans(); bn::preload_tsne(); bn::preload_bootstrap(); bn::preload_head_i8();
+    bn::preload_f32_pw(); bn::preload_melspec(); bn::preload_sort(); bn::preload_probe(); bn::preload_probe_sweep(); bn::preload_probe_mlp(); bn::preload_activity(); bn::preload_search(); bn::preload_augment(); bn::preload_kmeans(); bn::preload_tsne(); bn::preload_bootstrap(); bn::preload_head_i8();
     return BN_OK;
 }
 

@@ -473,6 +473,35 @@ bool launch_probe_fwd_qat(const ProbeFwdArgs& a, const ProbeQatArgs& q, int mode
 // amax [C] = max_k |P[k, c]|; per_tensor: one scale from the largest amax
 void launch_probe_qat_weights(const float* P, float* Pq, float* amax, int D, int C, bool per_tensor, hipStream_t s);
 
+// bn_probe_mlp.hip: the hidden layer of a head with one (bn_probe_mlp_*, bn_head_mlp_forward).  Its output layer, both
+// weight gradients, the reduction and the update are the launches above, on buffers in batch order.
+struct ProbeMlpFwdArgs {
+    const float* X;        // [*, D] embedding rows
+    const int* idx;        // [n] row of X / Y behind batch row i, or null: row i itself
+    const float* W1;       // [D, H]
+    const float* b1;       // [H]
+    float* hd;             // [n, H] relu(drop1(x) W1 + b1) * drop2, in batch order
+    // training only: what the output layer's forward reads through idx, copied into batch order next to hd
+    const float* Y; float* Yb;                 // [*, C] -> [n, C]
+    const float* row_weight; float* wb;        // [*] -> [n], or null: no weights
+    long n;
+    int D, H, C;
+    uint32_t drop_thresh;  // of both masks: keep iff draw >= drop_thresh (0: no dropout)
+    float drop_scale;
+    uint32_t seed, seed2, step;   // drop1's seed (the linear head's) and drop2's
+};
+struct ProbeMlpBwdArgs {
+    const float* G;        // [B, C] dLoss/dlogits
+    const float* W2;       // [H, C]
+    const float* hd;       // [B, H]: dA is zero where hd is (the ReLU gate and drop2's mask in one)
+    float* dA;             // [B, H]
+    int B, H, C;
+    float scale2;          // drop2's 1 / (1 - p), 1 without dropout
+};
+bool launch_probe_mlp_hidden(const ProbeMlpFwdArgs& a, bool train, hipStream_t s);   // false: the runtime refused the LDS request
+void launch_probe_mlp_bwd(const ProbeMlpBwdArgs& a, hipStream_t s);
+void preload_probe_mlp();
+
 // bn_probe_sweep.hip: T heads trained in lock-step (bn_probe_sweep_*).  The kernels are those of bn_probe.hip with the trial as one more
 // grid axis; what differs per trial is read from a table in device memory, and a trial whose byte of `active` is 0 returns at once.
 struct ProbeSweepTrial {       // one row of the device table

@@ -73,6 +73,8 @@ struct bn_ctx {
     size_t tsne_work_bytes = 0;
     void* d_boot_work = nullptr;     // bn_bootstrap_*: jump-ahead table, rejection counter and list, prepared class orders; grown on demand
     size_t boot_work_bytes = 0;
+    void* d_mlp_work = nullptr;      // bn_head_mlp_forward: the hidden activations of one step of rows; grown on demand
+    size_t mlp_work_bytes = 0;
 };
 
 struct bn_model {

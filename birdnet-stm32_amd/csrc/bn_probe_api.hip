@@ -54,6 +54,19 @@ struct bn_probe_sweep : bn::ProbeHandle {
     float* d_state = nullptr;                               // [T][4][(D + 1) * C]: parameters, m, v, snapshot
 };
 
+// A head with one hidden layer (bn_probe_mlp.hip).  D and C are the handle's; the shared workspaces hold G [batch, C],
+// the row-group partials of the whole parameter vector and the output layer's loss partials.
+struct bn_probe_mlp : bn::ProbeHandle {
+    int H = 0, opt = 0;
+    float lr = 0, wd = 0, clip = 0, drop = 0;
+    float *d_params = nullptr, *d_m = nullptr, *d_v = nullptr;   // [(D + 1) * H | (H + 1) * C] each
+    float* d_hd = nullptr;   size_t hd_bytes = 0;                // [rows, H] the hidden activations of a batch, or of a step of bn_probe_mlp_loss
+    float* d_dA = nullptr;   size_t dA_bytes = 0;                // [batch, H]
+    float* d_Yb = nullptr;   size_t Yb_bytes = 0;                // [batch, C] the batch's targets in batch order
+    float* d_wb = nullptr;   size_t wb_bytes = 0;                // [batch] ... and its row weights
+    void* d_iota = nullptr;  size_t iota_bytes = 0;              // [batch] int32 0, 1, ...: hd's rows as the gradient kernel indexes them
+};
+
 namespace {
 
 template <bool SWEEP>
@@ -289,9 +302,240 @@ int probe_loss(ProbeOf<SWEEP>* p, const float* d_X, const float* d_Y, int64_t n,
     return BN_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ one hidden layer (bn_probe_mlp.hip)
+int mlp_shape_check(int D, int H, int C, int activation) {
+    if (int rc = probe_shape_check(D, C, activation)) return rc;
+    if (H < 1 || H > BN_PROBE_MAX_D) return fail(BN_ERR_ARG, "hidden width H=%d outside 1..%d", H, BN_PROBE_MAX_D);
+    return BN_OK;
+}
+
+size_t mlp_E1(int D, int H) { return (size_t)(D + 1) * H; }
+size_t mlp_E(int D, int H, int C) { return mlp_E1(D, H) + (size_t)(H + 1) * C; }
+
+// Rows per step of bn_probe_mlp_loss and bn_head_mlp_forward: the hidden activations of a step take at most 64 MiB; a multiple of 16
+int64_t mlp_step_rows(int H) { return std::max<int64_t>(16, (int64_t)((64u << 20) / ((size_t)H * sizeof(float))) & ~(int64_t)15); }
+
+// What a training step at `batch` rows holds besides the row-group partials: hd, dA, G, Yb, wb, the identity index and the loss partials
+size_t mlp_batch_bytes(int batch, int H, int C) {
+    return ((size_t)batch * (2 * (size_t)H + 2 * (size_t)C + 2) + (size_t)(batch + 15) / 16) * sizeof(float);
+}
+
+// Most row groups of both gradient launches for B rows of a fit at `batch` rows per step, as probe_group_cap has them: two workgroups per
+// CU, at least 16 rows per group, everything inside BN_PROBE_WORKSPACE_BYTES.  0: not even one group fits.  Monotone in B.
+int64_t mlp_group_cap(int B, int batch, int D, int H, int C) {
+    const size_t E = mlp_E(D, H, C), other = mlp_batch_bytes(batch, H, C);
+    if (other > BN_PROBE_WORKSPACE_BYTES || E * sizeof(float) > BN_PROBE_WORKSPACE_BYTES - other) return 0;
+    const int tiles = probe_n_ss_tiles(D, H) + probe_n_ss_tiles(H, C);
+    int64_t g = std::max<int64_t>(1, 512 / tiles);
+    g = std::min<int64_t>(g, (int64_t)((BN_PROBE_WORKSPACE_BYTES - other) / (E * sizeof(float))));
+    return std::min<int64_t>(g, (B + 15) / 16);
+}
+
+int mlp_n_ss(int D, int H, int C) { return std::max(probe_n_ss_tiles(D, H) + probe_n_ss_tiles(H, C), probe_n_ss_reduce((int)mlp_E(D, H, C))); }
+
+// the four arrays of a head <-> the parameter vector (dir: true = into the vector)
+hipError_t mlp_copy_head(float* P, float* W1, float* b1, float* W2, float* b2, int D, int H, int C, bool into, hipStream_t s) {
+    float* at[4] = {P, P + (size_t)D * H, P + mlp_E1(D, H), P + mlp_E1(D, H) + (size_t)H * C};
+    float* arr[4] = {W1, b1, W2, b2};
+    const size_t n[4] = {(size_t)D * H, (size_t)H, (size_t)H * C, (size_t)C};
+    for (int i = 0; i < 4; ++i) {
+        const hipError_t e = hipMemcpyAsync(into ? at[i] : arr[i], into ? arr[i] : at[i], n[i] * sizeof(float), hipMemcpyDeviceToDevice, s);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// One epoch: per step hidden forward, output forward, dW2, hidden backward, dW1, [reduce], update
+int mlp_epoch(bn_probe_mlp* p, const float* d_X, const float* d_Y, const float* d_row_weight, const int32_t* d_perm, int64_t n, int batch,
+              float* d_step_loss, void* stream) {
+    if (int rc = probe_call_check(p, "probe", d_X && d_Y && d_perm && d_step_loss)) return rc;
+    if (int rc = probe_rows_check(n)) return rc;
+    if (batch < 1 || batch > n) return fail(BN_ERR_ARG, "batch %d outside 1..%lld", batch, (long long)n);
+    const int D = p->D, H = p->H, C = p->C, E1 = (int)mlp_E1(D, H), E = (int)mlp_E(D, H, C);
+    const int64_t cap = mlp_group_cap(batch, batch, D, H, C);
+    if (cap < 1)
+        return fail(BN_ERR_UNSUPPORTED, "a step of %d rows of D=%d H=%d C=%d needs %zu bytes of workspace, over the cap of %u", batch, D, H, C,
+                    mlp_batch_bytes(batch, H, C) + (size_t)E * sizeof(float), (unsigned)BN_PROBE_WORKSPACE_BYTES);
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = probe_grow(&p->d_G, &p->G_bytes, (size_t)batch * C, s)) return rc;
+    if (int rc = probe_grow(&p->d_partial, &p->partial_bytes, (size_t)cap * E, s)) return rc;
+    if (int rc = probe_grow(&p->d_loss_part, &p->loss_bytes, (size_t)(batch + 15) / 16, s)) return rc;
+    if (int rc = probe_grow(&p->d_hd, &p->hd_bytes, (size_t)batch * H, s)) return rc;
+    if (int rc = probe_grow(&p->d_dA, &p->dA_bytes, (size_t)batch * H, s)) return rc;
+    if (int rc = probe_grow(&p->d_Yb, &p->Yb_bytes, (size_t)batch * C, s)) return rc;
+    if (int rc = probe_grow(&p->d_wb, &p->wb_bytes, (size_t)batch, s)) return rc;
+    if ((size_t)batch * sizeof(int32_t) > p->iota_bytes) {
+        if (int rc = grow_device_buffer(&p->d_iota, &p->iota_bytes, (size_t)batch * sizeof(int32_t), (size_t)batch * sizeof(int32_t), s, BN_ERR_NOMEM, "probe"))
+            return rc;
+        std::vector<int32_t> iota((size_t)batch);
+        for (int i = 0; i < batch; ++i) iota[(size_t)i] = i;
+        HIP_TRY(hipMemcpy(p->d_iota, iota.data(), (size_t)batch * sizeof(int32_t), hipMemcpyHostToDevice));   // (synchronous: `iota` ends here)
+    }
+    const bool softmax = p->act == BN_PROBE_ACT_SOFTMAX;
+    const int tiles1 = probe_n_ss_tiles(D, H), tiles2 = probe_n_ss_tiles(H, C);
+    float *P1 = p->d_params, *P2 = p->d_params + E1;
+    bn::ProbeMlpFwdArgs h{}; bn::ProbeFwdArgs f{}; bn::ProbeDwArgs g2{}, g1{}; bn::ProbeMlpBwdArgs b{}; bn::ProbeUpdateArgs u{};
+    h.X = d_X; h.W1 = P1; h.b1 = P1 + (size_t)D * H; h.hd = p->d_hd; h.Y = d_Y; h.Yb = p->d_Yb; h.row_weight = d_row_weight; h.wb = p->d_wb;
+    h.D = D; h.H = H; h.C = C; h.seed = p->seed; h.seed2 = p->seed ^ 0x48494444u;
+    probe_dropout(p->drop, &h.drop_thresh, &h.drop_scale);
+    // the output layer over (hd, Yb) in batch order: no idx, no dropout (hd carries drop2)
+    f.X = p->d_hd; f.Y = p->d_Yb; f.W = P2; f.b = P2 + (size_t)H * C; f.out = p->d_G; f.loss_part = p->d_loss_part; f.D = H; f.C = C; f.softmax = softmax;
+    f.drop_thresh = 0; f.drop_scale = 1.0f; f.seed = p->seed; f.row_weight = d_row_weight ? p->d_wb : nullptr; f.loss_kind = p->loss; f.focal_gamma = p->gamma;
+    // both gradients write their slice of one vector: the stride between row groups is the whole vector
+    g2.X = p->d_hd; g2.idx = (const int*)p->d_iota; g2.G = p->d_G; g2.partial = p->d_partial + E1; g2.ss_part = p->d_ss + tiles1;
+    g2.D = H; g2.C = C; g2.E = E; g2.drop_thresh = 0; g2.drop_scale = 1.0f; g2.seed = p->seed;
+    g1.X = d_X; g1.G = p->d_dA; g1.partial = p->d_partial; g1.ss_part = p->d_ss; g1.D = D; g1.C = H; g1.E = E;
+    g1.drop_thresh = h.drop_thresh; g1.drop_scale = h.drop_scale; g1.seed = p->seed;
+    b.G = p->d_G; b.W2 = P2; b.hd = p->d_hd; b.dA = p->d_dA; b.H = H; b.C = C; b.scale2 = h.drop_thresh ? h.drop_scale : 1.0f;
+    u.params = p->d_params; u.m = p->d_m; u.v = p->d_v; u.grad = p->d_partial; u.ss_part = p->d_ss; u.loss_part = p->d_loss_part;
+    u.E = E; u.optimizer = p->opt; u.weight_decay = p->wd; u.clip = p->clip;
+    const int64_t steps = (n + batch - 1) / batch;
+    for (int64_t st = 0; st < steps; ++st, ++p->t) {
+        const int B = (int)std::min<int64_t>(batch, n - st * batch);
+        h.idx = g1.idx = d_perm + st * batch;
+        h.n = f.n = B; g1.B = g2.B = b.B = B;
+        h.step = g1.step = g2.step = f.step = (uint32_t)p->t;
+        f.g_scale = u.loss_scale = probe_mean_scale(softmax, B, C);
+        if (!bn::launch_probe_mlp_hidden(h, true, s) || !bn::launch_probe_fwd(f, 0, s))
+            return fail(BN_ERR_DEVICE, "the probe forward kernel's LDS request was refused");
+        const int64_t gc = mlp_group_cap(B, batch, D, H, C);   // from the shapes alone
+        const int rpg = (int)((((B + gc - 1) / gc) + 3) & ~(int64_t)3), groups = (B + rpg - 1) / rpg;
+        if ((size_t)groups * E * sizeof(float) > p->partial_bytes) return fail(BN_ERR_UNSUPPORTED, "%d row groups exceed the gradient workspace", groups);
+        g1.rows_per_group = g2.rows_per_group = rpg;
+        bn::launch_probe_dw(g2, groups, s);
+        bn::launch_probe_mlp_bwd(b, s);
+        bn::launch_probe_dw(g1, groups, s);
+        u.n_ss = tiles1 + tiles2;
+        if (groups > 1) {
+            bn::launch_probe_reduce(p->d_partial, E, groups, p->d_ss, s);
+            u.n_ss = probe_n_ss_reduce(E);
+        }
+        u.n_loss = (B + 15) / 16; u.step_loss = d_step_loss + st;
+        const double frac = (double)std::min<int64_t>(p->t, p->total) / (double)p->total;   // the schedule of bn_probe_epoch
+        const double lr_t = (double)p->lr * 0.5 * (1.0 + std::cos(M_PI * frac)), t1 = (double)(p->t + 1);
+        u.lr = (float)lr_t; u.alpha = (float)(lr_t * std::sqrt(1.0 - std::pow(0.999, t1)) / (1.0 - std::pow(0.9, t1)));
+        bn::launch_probe_update(u, s);
+    }
+    HIP_TRY(hipGetLastError());
+    return BN_OK;
+}
+
+// hd of rows [r0, r0 + nb) as they lie, without dropout, into d_hd
+bool mlp_hidden_plain(const float* d_X, int64_t r0, int64_t nb, int D, int H, const float* W1, const float* b1, float* d_hd, hipStream_t s) {
+    bn::ProbeMlpFwdArgs h{};
+    h.X = d_X + (size_t)r0 * D; h.W1 = W1; h.b1 = b1; h.hd = d_hd; h.n = nb; h.D = D; h.H = H;
+    return bn::launch_probe_mlp_hidden(h, false, s);
+}
+
 }  // namespace
 
 extern "C" {
+
+int bn_probe_mlp_create(bn_ctx* ctx, int D, int H, int C, int activation, int optimizer, float lr, float weight_decay, float clipnorm, float dropout,
+                        uint32_t seed, int64_t total_steps, const float* d_W1, const float* d_b1, const float* d_W2, const float* d_b2, bn_probe_mlp** out,
+                        void* stream) {
+    if (!out) return fail(BN_ERR_ARG, "out is null");
+    *out = nullptr;
+    if (int rc = check_device(ctx)) return rc;
+    if (int rc = mlp_shape_check(D, H, C, activation)) return rc;
+    if (int rc = probe_hyper_check(-1, optimizer, lr, weight_decay, clipnorm, dropout)) return rc;
+    if (total_steps < 1) return fail(BN_ERR_ARG, "total_steps must be >= 1");
+    if (!d_W1 || !d_b1 || !d_W2 || !d_b2) return fail(BN_ERR_ARG, "null device pointer");
+    hipStream_t s = (hipStream_t)stream;
+    bn_probe_mlp* p = new bn_probe_mlp();
+    p->ctx = ctx; p->D = D; p->H = H; p->C = C; p->act = activation; p->opt = optimizer; p->lr = lr; p->wd = weight_decay; p->clip = clipnorm;
+    p->drop = dropout; p->seed = seed; p->total = total_steps;
+    const size_t E = mlp_E(D, H, C);
+    if (hipMalloc(&p->d_params, 3 * E * sizeof(float)) != hipSuccess || hipMalloc(&p->d_ss, (size_t)mlp_n_ss(D, H, C) * sizeof(float)) != hipSuccess) {
+        (void)hipGetLastError();
+        bn_probe_mlp_destroy(p);
+        return fail(BN_ERR_NOMEM, "hipMalloc of the probe's parameters failed");
+    }
+    p->d_m = p->d_params + E; p->d_v = p->d_m + E;
+    hipError_t e = hipMemsetAsync(p->d_m, 0, 2 * E * sizeof(float), s);
+    if (e == hipSuccess)
+        e = mlp_copy_head(p->d_params, const_cast<float*>(d_W1), const_cast<float*>(d_b1), const_cast<float*>(d_W2), const_cast<float*>(d_b2), D, H, C, true, s);
+    if (e != hipSuccess) {
+        bn_probe_mlp_destroy(p);
+        return fail(BN_ERR_DEVICE, "copying the initial weights failed: %s", hipGetErrorString(e));
+    }
+    *out = p;
+    return BN_OK;
+}
+
+void bn_probe_mlp_destroy(bn_probe_mlp* p) {
+    if (!p) return;
+    probe_free(p, {p->d_params, p->d_hd, p->d_dA, p->d_Yb, p->d_wb, p->d_iota});
+    delete p;
+}
+
+int bn_probe_mlp_set_loss(bn_probe_mlp* p, int loss, float focal_gamma) { return probe_set_loss(p, "probe", loss, focal_gamma); }
+
+int bn_probe_mlp_epoch_weighted(bn_probe_mlp* p, const float* d_X, const float* d_Y, const float* d_row_weight, const int32_t* d_perm, int64_t n,
+                                int batch, float* d_step_loss, void* stream) {
+    return mlp_epoch(p, d_X, d_Y, d_row_weight, d_perm, n, batch, d_step_loss, stream);
+}
+
+int bn_probe_mlp_loss(bn_probe_mlp* p, const float* d_X, const float* d_Y, int64_t n, float* d_out, void* stream) {
+    if (int rc = probe_call_check(p, "probe", d_X && d_Y && d_out)) return rc;
+    if (int rc = probe_rows_check(n)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int D = p->D, H = p->H, C = p->C;
+    const size_t parts = (size_t)(n + 15) / 16;
+    const int64_t step = std::min<int64_t>(mlp_step_rows(H), (n + 15) & ~(int64_t)15);
+    if (int rc = probe_grow(&p->d_loss_part, &p->loss_bytes, parts, s)) return rc;
+    if (int rc = probe_grow(&p->d_hd, &p->hd_bytes, (size_t)step * H, s)) return rc;
+    const bool softmax = p->act == BN_PROBE_ACT_SOFTMAX;
+    const float *P1 = p->d_params, *P2 = p->d_params + mlp_E1(D, H);
+    bn::ProbeFwdArgs f{};
+    f.X = p->d_hd; f.D = H; f.C = C; f.softmax = softmax; f.loss_kind = p->loss; f.focal_gamma = p->gamma; f.W = P2; f.b = P2 + (size_t)H * C;
+    for (int64_t r0 = 0; r0 < n; r0 += step) {   // (a step is a multiple of 16 rows: the loss partials of the steps lie one behind the other)
+        const int64_t nb = std::min<int64_t>(step, n - r0);
+        f.Y = d_Y + (size_t)r0 * C; f.n = nb; f.loss_part = p->d_loss_part + r0 / 16;
+        if (!mlp_hidden_plain(d_X, r0, nb, D, H, P1, P1 + (size_t)D * H, p->d_hd, s) || !bn::launch_probe_fwd(f, 1, s))
+            return fail(BN_ERR_DEVICE, "the probe forward kernel's LDS request was refused");
+    }
+    bn::launch_probe_loss_sum(p->d_loss_part, (long)parts, probe_mean_scale(softmax, n, C), d_out, s);
+    HIP_TRY(hipGetLastError());
+    return BN_OK;
+}
+
+int bn_probe_mlp_get(bn_probe_mlp* p, float* d_W1, float* d_b1, float* d_W2, float* d_b2, void* stream) {
+    if (int rc = probe_call_check(p, "probe", d_W1 && d_b1 && d_W2 && d_b2)) return rc;
+    HIP_TRY(mlp_copy_head(p->d_params, d_W1, d_b1, d_W2, d_b2, p->D, p->H, p->C, false, (hipStream_t)stream));
+    return BN_OK;
+}
+
+int bn_probe_mlp_set(bn_probe_mlp* p, const float* d_W1, const float* d_b1, const float* d_W2, const float* d_b2, void* stream) {
+    if (int rc = probe_call_check(p, "probe", d_W1 && d_b1 && d_W2 && d_b2)) return rc;
+    HIP_TRY(mlp_copy_head(p->d_params, const_cast<float*>(d_W1), const_cast<float*>(d_b1), const_cast<float*>(d_W2), const_cast<float*>(d_b2), p->D, p->H,
+                          p->C, true, (hipStream_t)stream));
+    return BN_OK;
+}
+
+int bn_head_mlp_forward(bn_ctx* ctx, const float* d_emb, int64_t n, int D, const float* d_W1, const float* d_b1, int H, const float* d_W2,
+                        const float* d_b2, int C, int activation, float* d_scores, void* stream) {
+    if (int rc = check_device(ctx)) return rc;
+    if (int rc = mlp_shape_check(D, H, C, activation)) return rc;
+    if (n < 0 || n > 0x7fffffffLL) return fail(BN_ERR_ARG, "bad row count %lld", (long long)n);
+    if (n == 0) return BN_OK;
+    if (!d_emb || !d_W1 || !d_b1 || !d_W2 || !d_b2 || !d_scores) return fail(BN_ERR_ARG, "null device pointer");
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t step = std::min<int64_t>(mlp_step_rows(H), (n + 15) & ~(int64_t)15);
+    const size_t need = (size_t)step * H * sizeof(float);
+    if (int rc = grow_device_buffer(&ctx->d_mlp_work, &ctx->mlp_work_bytes, need, need, s, BN_ERR_NOMEM, "hidden layer")) return rc;
+    float* d_hd = (float*)ctx->d_mlp_work;
+    bn::ProbeFwdArgs a{};
+    a.X = d_hd; a.W = d_W2; a.b = d_b2; a.D = H; a.C = C; a.softmax = activation == BN_PROBE_ACT_SOFTMAX;
+    for (int64_t r0 = 0; r0 < n; r0 += step) {
+        const int64_t nb = std::min<int64_t>(step, n - r0);
+        a.out = d_scores + (size_t)r0 * C; a.n = nb;
+        if (!mlp_hidden_plain(d_emb, r0, nb, D, H, d_W1, d_b1, d_hd, s) || !bn::launch_probe_fwd(a, 2, s))
+            return fail(BN_ERR_DEVICE, "the head kernel's LDS request was refused");
+    }
+    HIP_TRY(hipGetLastError());
+    return BN_OK;
+}
 
 int bn_head_forward(bn_ctx* ctx, const float* d_emb, int64_t n, int D, const float* d_W, const float* d_b, int C, int activation,
                     float* d_scores, void* stream) {

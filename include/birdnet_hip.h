@@ -478,6 +478,32 @@ BN_API int bn_probe_get_quantized(bn_probe* probe, float* d_Wq, void* stream);
  * d_codes, int8 [n, C] or null: the clamped logit codes kc; needs quantize_logits. */
 BN_API int bn_probe_scores(bn_probe* probe, const float* d_X, int64_t n, float* d_scores, int8_t* d_codes, void* stream);
 
+/* ---- A head with one hidden layer (csrc/bn_probe_mlp.hip) --------------------------------------------------------------------------
+ *   a = drop1(x) W1 + b1 [B, H];  h = relu(a);  z = drop2(h) W2 + b2 [B, C];  scores = act(z)
+ * W1 [D, H], b1 [H], W2 [H, C], b2 [C], row-major float32; 1 <= D, H <= BN_PROBE_MAX_D, 1 <= C <= BN_PROBE_MAX_C.  drop1 is bn_probe's
+ * mask (seed, step, row in batch, column of x), drop2 the same draw and rate over [B, H] with seed ^ 0x48494444.  The loss, the row
+ * weights, the schedule, the clip (one global norm over all four arrays) and the optimisers are bn_probe's; the entries mirror
+ * bn_probe_create / _destroy / _set_loss / _epoch_weighted / _loss / _get / _set, with the same checks.  The buffers of a training step
+ * (activations, gradients of the batch, row-group partials) stay within BN_PROBE_WORKSPACE_BYTES: a batch that would need more is refused
+ * with BN_ERR_UNSUPPORTED.  The same inputs and seed give the same bits. */
+typedef struct bn_probe_mlp bn_probe_mlp;
+BN_API int bn_probe_mlp_create(bn_ctx* ctx, int D, int H, int C, int activation, int optimizer, float lr, float weight_decay, float clipnorm,
+                        float dropout, uint32_t seed, int64_t total_steps, const float* d_W1, const float* d_b1, const float* d_W2,
+                        const float* d_b2, bn_probe_mlp** out, void* stream);
+BN_API void bn_probe_mlp_destroy(bn_probe_mlp* probe);
+BN_API int bn_probe_mlp_set_loss(bn_probe_mlp* probe, int loss, float focal_gamma);
+/* d_row_weight: float32 [rows of d_X] or null.  d_step_loss: float32 [ceil(n / batch)]. */
+BN_API int bn_probe_mlp_epoch_weighted(bn_probe_mlp* probe, const float* d_X, const float* d_Y, const float* d_row_weight, const int32_t* d_perm,
+                                int64_t n, int batch, float* d_step_loss, void* stream);
+/* d_out[0]: the loss over rows 0 .. n-1 as they are (no dropout, no weights). */
+BN_API int bn_probe_mlp_loss(bn_probe_mlp* probe, const float* d_X, const float* d_Y, int64_t n, float* d_out, void* stream);
+BN_API int bn_probe_mlp_get(bn_probe_mlp* probe, float* d_W1, float* d_b1, float* d_W2, float* d_b2, void* stream);
+BN_API int bn_probe_mlp_set(bn_probe_mlp* probe, const float* d_W1, const float* d_b1, const float* d_W2, const float* d_b2, void* stream);
+/* d_scores[n, C] = act(relu(d_emb[n, D] d_W1 + d_b1) d_W2 + d_b2): the scores of such a head.  0 <= n < 2^31 (n == 0 launches nothing).
+ * Rows go in steps whose hidden activations take at most 64 MiB of a workspace the context keeps. */
+BN_API int bn_head_mlp_forward(bn_ctx* ctx, const float* d_emb, int64_t n, int D, const float* d_W1, const float* d_b1, int H, const float* d_W2,
+                        const float* d_b2, int C, int activation, float* d_scores, void* stream);
+
 /* ---- A hyperparameter sweep: T heads trained in lock-step on the same rows (csrc/bn_probe_sweep.hip) ---------------------------------
  * (Reference counterpart: `train --tune`, training/tuner.py, which trains its trials one after another.)  The trials share D, C, the
  * activation, the batch, X / Y, the permutation, the step counter, the dropout draw (each trial has its own threshold on it) and the

@@ -27,6 +27,12 @@ DESIGN.md §5j) against the plain ``bn_probe_epoch`` on the same rows in the sam
 and the largest head the device takes (D = 2048, C = 4096, over ``--large_rows`` rows), where the two weight kernels in front of every
 forward pass over 8.4 M weights.  Per cell one warm-up epoch of each side, then ``--repeats`` timed epochs of each, alternating; median,
 spread (min .. max) and the ratio of the medians.
+
+    python tools/probe_bench.py --hidden 64 [--classes 12,100] [--batches 32,512] [--rows 262144] [--epochs 2]
+
+The step of a head with one hidden layer of H units (``fit_probe(hidden_units=H)``'s backend, ``bn_probe_mlp_*``), timed as
+the linear step is: whole epochs, first one discarded.  Next to it the same step in PyTorch ops (dropout, linear, ReLU, dropout, linear,
+the rest as above) and, for context, the linear step (``bn_probe_*``) on the same rows in the same process.
 """
 
 import argparse
@@ -40,7 +46,9 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [REPO, os.path.join(REPO, "birdnet-stm32_amd")]
 
 
-def torch_epoch_fn(torch, X, Y, C, batch, total_steps):
+def torch_epoch_fn(torch, X, Y, C, batch, total_steps, hidden=0):
+    if hidden:
+        return torch_mlp_epoch_fn(torch, X, Y, C, batch, total_steps, hidden)
     lin = torch.nn.Linear(X.shape[1], C, device=X.device)
     opt = torch.optim.Adam(lin.parameters(), lr=1e-3, eps=1e-7)
     sched = torch.optim.lr_scheduler.CosineAnnealingLR(opt, total_steps)
@@ -53,6 +61,26 @@ def torch_epoch_fn(torch, X, Y, C, batch, total_steps):
             opt.zero_grad(set_to_none=True)
             loss.backward()
             torch.nn.utils.clip_grad_norm_(lin.parameters(), 1.0)
+            opt.step()
+            sched.step()
+        torch.cuda.synchronize()
+
+    return epoch
+
+
+def torch_mlp_epoch_fn(torch, X, Y, C, batch, total_steps, hidden):
+    net = torch.nn.Sequential(torch.nn.Dropout(0.5), torch.nn.Linear(X.shape[1], hidden), torch.nn.ReLU(), torch.nn.Dropout(0.5),
+                              torch.nn.Linear(hidden, C)).to(X.device)
+    opt = torch.optim.Adam(net.parameters(), lr=1e-3, eps=1e-7)
+    sched = torch.optim.lr_scheduler.CosineAnnealingLR(opt, total_steps)
+
+    def epoch(perm):
+        for s in range(0, X.shape[0], batch):
+            idx = perm[s : s + batch]
+            loss = torch.nn.functional.binary_cross_entropy(torch.sigmoid(net(X[idx])), Y[idx])
+            opt.zero_grad(set_to_none=True)
+            loss.backward()
+            torch.nn.utils.clip_grad_norm_(net.parameters(), 1.0)
             opt.step()
             sched.step()
         torch.cuda.synchronize()
@@ -177,6 +205,7 @@ def main():
     ap.add_argument("--batches", type=str, default="32,512,4096", help="with --sweep: batch sizes")
     ap.add_argument("--qat", action="store_true", help="time an epoch of the quantisation-aware fine-tune against the plain epoch (uses --rows, --repeats)")
     ap.add_argument("--large_rows", type=int, default=16384, help="with --qat: rows of the D = 2048, C = 4096 cell")
+    ap.add_argument("--hidden", type=int, default=0, help="time the step of a head with this many hidden units (cells: --classes x --batches)")
     args = ap.parse_args()
     if args.qat:
         return qat_main(args)
@@ -188,24 +217,33 @@ def main():
     X = torch.rand((n, D), device="cuda", generator=g)
     weights = np.random.default_rng(1).uniform(0.5, 4.0, n).astype(np.float32) if args.row_weights else None
     rows = []
-    for C in (12, 100, 1000):
+    cells_C, cells_batch = ([int(v) for v in a.split(",")] for a in (args.classes, args.batches)) if args.hidden else ((12, 100, 1000), (32, 512, 4096))
+    for C in cells_C:
         Y = torch.zeros((n, C), device="cuda")
         Y[torch.arange(n, device="cuda"), torch.randint(0, C, (n,), device="cuda", generator=g)] = 1.0
-        for batch in (32, 512, 4096):
+        for batch in cells_batch:
             steps = math.ceil(n / batch)
             total = steps * (args.epochs + 1)
             plan = lp._plan_fit(X, Y, None, device=True, activation="sigmoid", optimizer="adam", batch_size=batch, dropout=0.5, epochs=args.epochs + 1,
                                 learning_rate=1e-3, weight_decay=0.0, clipnorm=1.0, seed=1, loss=args.loss, focal_gamma=args.focal_gamma,
-                                sample_weight=weights)
-            be = lp._DeviceBackend(ctx, X, Y, None, None, plan)
-            ours = []
+                                sample_weight=weights, hidden_units=args.hidden)
+            be = (lp._MlpDeviceBackend if args.hidden else lp._DeviceBackend)(ctx, X, Y, None, None, plan)
+            lin = lp._DeviceBackend(ctx, X, Y, None, None, lp._plan_fit(X, Y, None, device=True, activation="sigmoid", optimizer="adam", batch_size=batch,
+                                                                       dropout=0.5, epochs=args.epochs + 1, seed=1)) if args.hidden else None
+            ours, linear = [], []
             for e in range(args.epochs + 1):
                 perm = lp.epoch_permutation(1, e, n)
                 t0 = time.perf_counter()
                 be.epoch(perm)   # (uploads the permutation, reads the step losses back: synchronises)
                 ours.append(time.perf_counter() - t0)
+                if lin is not None:
+                    t0 = time.perf_counter()
+                    lin.epoch(perm)
+                    linear.append(time.perf_counter() - t0)
             be.close()
-            ep = torch_epoch_fn(torch, X, Y, C, batch, total)
+            if lin is not None:
+                lin.close()
+            ep = torch_epoch_fn(torch, X, Y, C, batch, total, args.hidden)
             theirs = []
             for e in range(0 if args.skip_torch else args.epochs + 1):
                 perm = torch.from_numpy(lp.epoch_permutation(1, e, n).astype(np.int64)).cuda()
@@ -216,12 +254,15 @@ def main():
             a, b = min(ours[1:]), min(theirs[1:]) if theirs else float("nan")
             row = dict(D=D, C=C, batch=batch, loss=args.loss, row_weights=bool(args.row_weights), steps_per_epoch=steps, fit_probe_s_per_epoch=a, fit_probe_steps_per_s=steps / a, torch_s_per_epoch=b,
                        torch_steps_per_s=steps / b, speedup=b / a)
+            if args.hidden:
+                row.update(hidden=args.hidden, linear_steps_per_s=steps / min(linear[1:]))
             rows.append(row)
             print(json.dumps(row), flush=True)
-    print("\n| C | batch | fit_probe steps/s | s/epoch | PyTorch steps/s | s/epoch | ratio |\n|---|---|---|---|---|---|---|")
+    extra = ("H | ", "---|", " linear step, steps/s |", "---|") if args.hidden else ("", "", "", "")
+    print(f"\n| {extra[0]}C | batch | fit_probe steps/s | s/epoch | PyTorch steps/s | s/epoch | ratio |{extra[2]}\n|{extra[1]}---|---|---|---|---|---|---|{extra[3]}")
     for r in rows:
-        print(f"| {r['C']} | {r['batch']} | {r['fit_probe_steps_per_s']:.0f} | {r['fit_probe_s_per_epoch']:.3f} | {r['torch_steps_per_s']:.0f} | "
-              f"{r['torch_s_per_epoch']:.3f} | {r['speedup']:.2f} |")
+        print((f"| {r['hidden']} " if args.hidden else "") + f"| {r['C']} | {r['batch']} | {r['fit_probe_steps_per_s']:.0f} | {r['fit_probe_s_per_epoch']:.3f} | "
+              f"{r['torch_steps_per_s']:.0f} | {r['torch_s_per_epoch']:.3f} | {r['speedup']:.2f} |" + (f" {r['linear_steps_per_s']:.0f} |" if args.hidden else ""))
     ctx.close()
 
 
