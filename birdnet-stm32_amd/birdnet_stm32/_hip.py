@@ -28,7 +28,7 @@ EXPORTS = (
     "bn_model_free", "bn_model_get_info", "bn_stft_mag", "bn_forward", "bn_infer_audio", "bn_debug_op_output",
     "bn_kernel_names", "bn_profile_enable", "bn_profile_collect", "bn_ingest_resample", "bn_ingest_chunks",
     "bn_pool_scores", "bn_mel_spectrogram", "bn_profile_only", "bn_chunk_peak_normalize", "bn_set_option", "bn_get_option", "bn_ctx_set_option", "bn_ctx_get_option", "bn_ctx_reset_options", "bn_preload_kernels", "bn_host_alloc_pinned", "bn_host_free_pinned", "bn_rank_orders",
-    "bn_blob_check", "bn_debug_requant", "bn_stft_mag_exact", "bn_debug_input_bytes", "bn_debug_guard_stats", "bn_debug_tail_form", "bn_debug_mid_form", "bn_debug_mid_plan", "bn_debug_mid_split_giveups",
+    "bn_blob_check", "bn_debug_requant", "bn_stft_mag_exact", "bn_debug_input_bytes", "bn_debug_guard_stats", "bn_debug_tail_form", "bn_debug_mid_form", "bn_debug_mid_plan", "bn_debug_mid_split_giveups", "bn_debug_satpack", "bn_debug_satpack_form",
     "bn_forward_embed", "bn_infer_audio_embed", "bn_model_get_embedding_info", "bn_ingest_resample_span",
     "bn_head_forward", "bn_probe_create", "bn_probe_destroy", "bn_probe_epoch", "bn_probe_loss", "bn_probe_get", "bn_probe_set",
     "bn_probe_sweep_create", "bn_probe_sweep_destroy", "bn_probe_sweep_epoch", "bn_probe_sweep_loss", "bn_probe_sweep_snapshot", "bn_probe_sweep_get",
@@ -96,7 +96,8 @@ def kmeans_tile_centroids(D: int, K: int) -> int:
 OPTION_NAMES = ("f32_strip", "f32_strip_th", "f32_front_staged", "f32_front2", "f32_pwdw", "f32_tile_slice", "f32_pw_ws", "i8_pwdw", "i8_pw_lds", "i8_pw_forms", "i8_add_tab", "front_tpw", "wave_dwpw", "i8_strip", "i8_strip_mfdw", "i8_strip_th", "i8_dw_pool", "i8_tail_fclds", "i8_tail", "i8_tail_mfdw", "i8_mid",
                 "i8_mel_generic", "stft_rowmajor", "stft_exact", "stft_flagcap", "stft_guard", "stft_audit", "stft_minint", "ingest_blk", "ingest_generic")
 # scheduling switches that change no result and no kernel's name (same bn_set_option; listed apart from the tuple above)
-SCHEDULING_OPTION_NAMES = ("i8_mid_split",)
+# ("i8_satpack": bit 0 = the fused chains' shift-saturate-pack epilogues, bit 1 = the front strip's stem rows; same bytes in fewer instructions)
+SCHEDULING_OPTION_NAMES = ("i8_mid_split", "i8_satpack")
 
 
 class BnModelInfo(ctypes.Structure):
@@ -149,6 +150,8 @@ def load_library(path: str | None = None):
     lib.bn_debug_mid_form.argtypes = [c_void_p, POINTER(c_int), POINTER(c_int)]
     lib.bn_debug_mid_plan.argtypes = [c_void_p, POINTER(c_int), c_int]
     lib.bn_debug_mid_split_giveups.argtypes = [c_void_p, POINTER(c_int64)]
+    lib.bn_debug_satpack.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]
+    lib.bn_debug_satpack_form.argtypes = [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_int)]
     lib.bn_forward.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]
     lib.bn_infer_audio.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
     lib.bn_forward_embed.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]

@@ -297,6 +297,14 @@ class HipRunner:
         _hip.check(self.lib.bn_debug_mid_form(self.model.handle, ctypes.byref(form), ctypes.byref(lds)))
         return form.value, lds.value
 
+    def satpack_form(self) -> tuple[int, int, int]:
+        """Test hook: the requantisation tail of (``i8_mid2_kernel``, ``i8_tail2_kernel``, the stem rows of ``i8_front_strip_kernel``) in this
+        plan — 1 the packed shift-and-saturate form (every clamp in front of a stored byte is the int8 range), 0 the clamp-shift-pack form,
+        -1 the plan does not run that kernel."""
+        mid, tail, front = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+        _hip.check(self.lib.bn_debug_satpack_form(self.model.handle, ctypes.byref(mid), ctypes.byref(tail), ctypes.byref(front)))
+        return mid.value, tail.value, front.value
+
     def mid_plan(self) -> dict | None:
         """Test hook: the resident LDS placement of the fused stage-2 chain (option ``i8_mid_split``), ``None`` where the plan has none.
         ``parts`` = (offset, bytes) of every block's depthwise part, pointwise part and zero-point row."""

@@ -30,7 +30,7 @@ const OptName kOptions[] = {
     {"f32_strip", &bn::Options::f32_strip},       {"f32_strip_th", &bn::Options::f32_strip_th},
     {"f32_front_staged", &bn::Options::f32_front_staged}, {"f32_front2", &bn::Options::f32_front2}, {"f32_pwdw", &bn::Options::f32_pwdw}, {"f32_tile_slice", &bn::Options::f32_tile_slice}, {"f32_pw_ws", &bn::Options::f32_pw_ws}, {"i8_pwdw", &bn::Options::i8_pwdw}, {"i8_pw_lds", &bn::Options::i8_pw_lds}, {"i8_pw_forms", &bn::Options::i8_pw_forms}, {"i8_add_tab", &bn::Options::i8_add_tab}, {"front_tpw", &bn::Options::front_tpw},
     {"wave_dwpw", &bn::Options::wave_dwpw},       {"i8_strip", &bn::Options::i8_strip},
-    {"i8_strip_th", &bn::Options::i8_strip_th}, {"i8_dw_pool", &bn::Options::i8_dw_pool}, {"i8_tail_fclds", &bn::Options::i8_tail_fclds},   {"i8_tail", &bn::Options::i8_tail}, {"i8_tail_mfdw", &bn::Options::i8_tail_mfdw}, {"i8_mid", &bn::Options::i8_mid}, {"i8_mid_split", &bn::Options::i8_mid_split},
+    {"i8_strip_th", &bn::Options::i8_strip_th}, {"i8_dw_pool", &bn::Options::i8_dw_pool}, {"i8_tail_fclds", &bn::Options::i8_tail_fclds},   {"i8_tail", &bn::Options::i8_tail}, {"i8_tail_mfdw", &bn::Options::i8_tail_mfdw}, {"i8_mid", &bn::Options::i8_mid}, {"i8_mid_split", &bn::Options::i8_mid_split}, {"i8_satpack", &bn::Options::i8_satpack},
     {"i8_mel_generic", &bn::Options::i8_mel_generic}, {"stft_rowmajor", &bn::Options::stft_rowmajor},
     {"i8_strip_mfdw", &bn::Options::i8_strip_mfdw}, {"stft_exact", &bn::Options::stft_exact}, {"stft_flagcap", &bn::Options::stft_flagcap}, {"stft_guard", &bn::Options::stft_guard}, {"stft_audit", &bn::Options::stft_audit}, {"stft_minint", &bn::Options::stft_minint},
     {"ingest_blk", &bn::Options::ingest_blk},
@@ -650,6 +650,22 @@ int bn_debug_mid_form(const bn_model* m, int* form, int* lds_bytes) {
     return BN_OK;
 }
 
+int bn_debug_satpack_form(const bn_model* m, int* mid, int* tail, int* front) {
+    if (!m || !mid || !tail || !front) return fail(BN_ERR_ARG, "null argument");
+    *mid = *tail = *front = -1;
+    for (size_t oi = 0; oi < m->ops.size(); ++oi) {
+        const bn::OpPrep& pr = *m->prep[oi];
+        namespace k = bn::op::i8_front;
+        const OpRec& o = m->ops[oi];
+        if (o.kind == BN_OP_I8_FRONT && o.p[k::strip] && o.t[k::strip_cst] >= 0 &&
+            bn::i8_front_strip_supported(o.p[k::H0], o.p[k::W0], o.p[k::C], o.p[k::N], o.p[k::OH], o.p[k::OW]))
+            *front = bn::front_strip_satpack_ok(o.p[k::stem_amin], o.p[k::stem_amax]) ? 1 : 0;
+        if (m->ops[oi].kind == BN_OP_I8_MID && pr.ok) *mid = pr.chain.satpack;
+        if (m->ops[oi].kind == BN_OP_I8_TAIL && pr.ok && pr.alt_ok) *tail = pr.chain.satpack;
+    }
+    return BN_OK;
+}
+
 int bn_debug_mid_plan(const bn_model* m, int* out, int n) {
     if (!m || !out || n < 1) return fail(BN_ERR_ARG, "null argument");
     out[0] = 0;
@@ -928,6 +944,16 @@ int bn_debug_requant(bn_ctx* ctx, const int32_t* d_x, const int32_t* d_mult, con
     if (n == 0) return BN_OK;
     if (!d_x || !d_mult || !d_shift || !d_out) return fail(BN_ERR_ARG, "null device pointer");
     bn::launch_debug_requant(d_x, d_mult, d_shift, n, mode, zero_point, d_out, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return BN_OK;
+}
+
+int bn_debug_satpack(bn_ctx* ctx, const int32_t* d_a, const int32_t* d_b, const int32_t* d_s, int n, int mode, uint32_t* d_out, void* stream) {
+    if (int rc = check_device(ctx)) return rc;
+    if (n < 0 || mode < 0 || mode > 1) return fail(BN_ERR_ARG, "bad n / mode");
+    if (n == 0) return BN_OK;
+    if (!d_a || !d_b || !d_s || !d_out) return fail(BN_ERR_ARG, "null device pointer");
+    bn::launch_debug_satpack(d_a, d_b, d_s, n, mode, d_out, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return BN_OK;
 }

@@ -228,6 +228,7 @@ bool tail2_plan(const int32_t* desc, int n_words, int n_layers, Tail2Args& a, bo
     }
     const Tail2Layer& last = a.L[n_layers - 1];
     a.resident = 0;
+    a.satpack = tail2_satpack_ok(a) ? 1 : 0;
     a.bar_off = -1;
     a.fcw_off = -1;   // (tail: the classifier's fragments come straight from memory)
     if (mid) {
@@ -247,6 +248,19 @@ bool tail2_plan(const int32_t* desc, int n_words, int n_layers, Tail2Args& a, bo
     grow(a.mean_off + kTailG * last.Cout);
     a.lds_bytes = lds_need;
     tail2_place_counters(a);
+    return true;
+}
+
+// Which epilogue form a chain's kernel may run (bn_i8_tail2.hip: SAT).  The packed shift-and-saturate instruction clamps to [-128, 127] and
+// to nothing else, so ONE narrower bound anywhere in the chain (a ReLU6 output whose 6 / scale stays below 127, an ADD output whose zero
+// point is above -128) keeps the whole launch on the med3 form: the choice is per launch, not per block.
+bool tail2_satpack_ok(const Tail2Args& a) {
+    if (a.n_layers < 1 || a.n_layers > 8) return false;
+    for (int i = 0; i < a.n_layers; ++i) {
+        const Tail2Layer& L = a.L[i];
+        if (L.dw_lo != -128 || L.dw_hi != 127) return false;
+        if (L.has_add ? (L.add_lo != -128 || L.add_hi != 127) : (L.pw_lo != -128 || L.pw_hi != 127)) return false;
+    }
     return true;
 }
 

@@ -67,6 +67,7 @@ struct Tail2Args {
     int fcw_off;
     int bar_off;          // LDS byte offset of the chunk barriers' counters (one dword per chunk slot)
     int resident;         // i8_mid2_kernel: every block's constants have LDS of their own (tail2_plan_resident) — staged once, chunk-local barriers
+    int satpack;          // the kernels' shift-saturate-pack epilogues (v_ashr_pk_i8_i32): set by tail2_plan from tail2_satpack_ok, cleared by option i8_satpack
     Tail2Layer L[8];};
 constexpr int kTail2MaxDw16 = 7 * kTail2Threads;   // sixteen-byte pieces of the largest depthwise part a block may prefetch (256 channels: 3392)
 // bytes of a block's depthwise part (expanded weights + constants) and pointwise part (weights + constants) in the constant block and in LDS:
@@ -74,6 +75,9 @@ constexpr int kTail2MaxDw16 = 7 * kTail2Threads;   // sixteen-byte pieces of the
 BN_HOST_DEVICE inline int tail2_dw_bytes(const Tail2Layer& L, bool first) { return (L.Cin / 16) * (3 * 1024 + (first ? 8 : 5) * 64); }
 BN_HOST_DEVICE inline int tail2_pw_bytes(const Tail2Layer& L) { return (L.Cin + 63) / 64 * 64 * L.Cout + (L.Cout / 16) * 5 * 64; }
 bool tail2_plan(const int32_t* desc, int n_words, int n_layers, Tail2Args& a, bool mid = false);  // a.NC must be set (tail); mid: the stage-2 chain, no head
+// every clamp in front of a stored byte of the chain is the int8 range itself: (dw_lo, dw_hi) and, without the ADD, (pw_lo, pw_hi), with it
+// (add_lo, add_hi), all (-128, 127) in every block — the saturation of v_ashr_pk_i8_i32 then IS the clamp; false: the chain keeps med3
+bool tail2_satpack_ok(const Tail2Args& a);
 bool tail2_plan_resident(Tail2Args& a);   // a stage-2 plan tail2_plan accepted -> its resident placement; false (a unspecified): it does not fit, keep the staged one
 bool tail2_plan_dump(const Tail2Args& a, int* out, int n);   // bn_debug_mid_plan (include/birdnet_hip.h has the layout)
 long tail2_const_words(const Tail2Args& a, bool mid = false);

@@ -775,6 +775,23 @@ __global__ void debug_requant_kernel(const int32_t* x, const int32_t* mult, cons
     out[i] = r;
 }
 
+// Test hook (bn_debug_satpack): the packed shift-and-saturate primitives of bn_requant.h, one pair per thread
+__global__ void debug_satpack_kernel(const int32_t* a, const int32_t* b, const int32_t* s, int n, int mode, uint32_t* out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    int r;
+    if (mode == 0) {
+        r = sat_pack2(a[i], b[i], s[i]);
+    } else {
+        r = 0x1234BEEF;
+        sat_pack2_hi(r, a[i], b[i], s[i]);
+    }
+    out[i] = (uint32_t)r;
+}
+void launch_debug_satpack(const int32_t* a, const int32_t* b, const int32_t* s, int n, int mode, uint32_t* out, hipStream_t st) {
+    hipLaunchKernelGGL(debug_satpack_kernel, dim3((n + 255) / 256), dim3(256), 0, st, a, b, s, n, mode, out);
+}
+
 void launch_debug_requant(const int32_t* x, const int32_t* mult, const int32_t* shift, int n, int mode, int zp, int32_t* out, hipStream_t s) {
     hipLaunchKernelGGL(debug_requant_kernel, dim3((n + 255) / 256), dim3(256), 0, s, x, mult, shift, n, mode, zp, out);
 }

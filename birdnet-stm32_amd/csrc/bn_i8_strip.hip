@@ -616,7 +616,12 @@ void launch_strip(const Strip8Args& a, hipStream_t s) {
 // dwords — no pack or transpose permutes.
 constexpr int kF_STA = 0, kF_STB = 64, kF_STC = 80, kF_DWW = 128, kF_DWB = 176, kF_DWC = 192, kF_PWA = 240, kF_PWB = 368, kF_PWC = 400;
 
-__global__ __launch_bounds__(256) void i8_front_strip_kernel(FrontStrip8Args a) {
+// SAT (option i8_satpack bit 1, a stem whose clamp is the int8 range): the three stem columns of a row go into the window dwords with
+// v_ashr_pk_i8_i32 — columns (0, 1) of a channel share its shift and fill bytes 0-1, column 2 goes to the high half (bn_requant.h:
+// sat_window_lo / sat_window_hi) — 20 vector instructions per stem row and lane instead of 36, four shift registers instead of eight bounds.
+// The depthwise and pointwise stages have no two values behind one shift in a lane and keep the clamp-first form.
+template <bool SAT>
+__device__ __forceinline__ void front_strip_main(const FrontStrip8Args& a, v4i (*cq_lds)[4][3][5]) {
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -639,10 +644,11 @@ __global__ __launch_bounds__(256) void i8_front_strip_kernel(FrontStrip8Args a) 
     const v4i stm = c4[kF_STC / 4 + kq * 3 + 0], stc1 = c4[kF_STC / 4 + kq * 3 + 1], ste = c4[kF_STC / 4 + kq * 3 + 2];
     const long stc[4] = {rq64(stc1.x), rq64(stc1.y), rq64(stc1.z), rq64(stc1.w)};
     const int ste1 = pack_shifts(ste - 1);
-    // clamp bounds in front of the shift, per channel (bn_requant.h: shifted_bounds)
+    // clamp bounds in front of the shift, per channel (bn_requant.h: shifted_bounds); SAT: the shifts alone, one register each
     int stlo[4], sthi[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) shifted_bounds(a.st_lo, a.st_hi, ste[e] - 1, stlo[e], sthi[e]);
+    const int stsh[4] = {ste.x - 1, ste.y - 1, ste.z - 1, ste.w - 1};
     int dww[3][4];
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
@@ -654,7 +660,7 @@ __global__ __launch_bounds__(256) void i8_front_strip_kernel(FrontStrip8Args a) 
     // quad) live in LDS and are re-read every row, as in i8_strip_kernel; the stem's, used twice per row, stay in registers.  With all of
     // them in registers the kernel needs 166 and loses its fourth wave per SIMD.  Each wave keeps its own copy (lane (0, kq) writes the
     // five 16-byte words of its quads): no workgroup barrier.
-    __shared__ v4i cq_lds[4][4][3][5];   // [wave][kq][depthwise, pointwise tile 0, tile 1][multiplier, C01, C23, lower, upper bounds]
+    // cq_lds: [wave][kq][depthwise, pointwise tile 0, tile 1][multiplier, C01, C23, lower, upper bounds]
     auto stage_quad = [&](v4i* q, v4i m, v4i c1, v4i sh, int lo, int hi) {
         int blo[4], bhi[4];
         long c[4];
@@ -725,13 +731,25 @@ __global__ __launch_bounds__(256) void i8_front_strip_kernel(FrontStrip8Args a) 
             const int Bd = (ok && !right_fe) ? raw[slot].y : zfe4;
             const int x[3] = {A & 0x00ffffff, perm(Bd, A, 0x0c040302u), Bd & 0x00ffffff};
             // stem column j, channel e -> byte j of the window dword of channel e, written by the requantisation's own shift
+            if constexpr (SAT) {
+                int h[3][4];
 #pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                const v4i acc = __builtin_amdgcn_mfma_i32_16x16x32_i8(sta, (long)(uint32_t)x[j], stb, 0, 0, 0);
-                int h[4];
+                for (int j = 0; j < 3; ++j) {
+                    const v4i acc = __builtin_amdgcn_mfma_i32_16x16x32_i8(sta, (long)(uint32_t)x[j], stb, 0, 0, 0);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) h[e] = med3(rq_h(acc[e], stm[e], stc[e]), stlo[e], sthi[e]);
-                deposit_column(T[ti].c[0], h, ste1, j);
+                    for (int e = 0; e < 4; ++e) h[j][e] = rq_h(acc[e], stm[e], stc[e]);
+                    if (j == 1) sat_window_lo(T[ti].c[0], h[0], h[1], stsh);
+                }
+                sat_window_hi(T[ti].c[0], h[2], stsh);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+                    const v4i acc = __builtin_amdgcn_mfma_i32_16x16x32_i8(sta, (long)(uint32_t)x[j], stb, 0, 0, 0);
+                    int h[4];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) h[e] = med3(rq_h(acc[e], stm[e], stc[e]), stlo[e], sthi[e]);
+                    deposit_column(T[ti].c[0], h, ste1, j);
+                }
             }
             if (last_strip) {  // the padding column reads as the zero point
 #pragma unroll
@@ -791,6 +809,13 @@ __global__ __launch_bounds__(256) void i8_front_strip_kernel(FrontStrip8Args a) 
             emit((2 * u) % 3, (2 * u + 1) % 3, (2 * u + 2) % 3, oh0 + k + u);
         }
     }
+}
+
+// (one kernel, a workgroup-uniform choice of the stem's form: the name the profiles and the benchmark key on stays whatever the option says)
+__global__ __launch_bounds__(256) void i8_front_strip_kernel(FrontStrip8Args a) {
+    __shared__ v4i cq_lds[4][4][3][5];
+    if (a.satpack) front_strip_main<true>(a, cq_lds);
+    else front_strip_main<false>(a, cq_lds);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -241,7 +241,10 @@ __device__ __forceinline__ void tail2_head(const Tail2Args& a_, unsigned char* l
 // 8-wide map is two rows) and walks them in passes of at most four.
 // RES (i8_mid2_kernel with every block's constants resident in LDS, tail2_plan_resident): nothing is staged here, and the two barriers
 // order the WPC waves of the wave's chunk slot only (chunk_barrier; `seq` = the barriers the wave has passed).
-template <int G, int CIN, int COUT, int S, int H, int W, bool ADD, bool SRCG, bool RES = false>
+// SAT (option i8_satpack, a chain whose every stored clamp is the int8 range: tail2_satpack_ok): shift, clamp and packing of the stored bytes
+// as v_ashr_pk_i8_i32 (bn_requant.h: sat_pack_2x4 over two tiles of a wave wherever it walks an even number at a time — the two positions
+// share every channel's shift —, sat_pack_quads behind the ADD's per-layer shift).  Same bytes as the !SAT form.
+template <int G, int CIN, int COUT, int S, int H, int W, bool ADD, bool SRCG, bool RES = false, bool SAT = false>
 __device__ __forceinline__ void tail2_block(const Tail2Layer& L, const Tail2Args& a, unsigned char* lds, int chunk0, int nxi, unsigned& seq, int stamp_slot = -1) {
 #ifdef BN_TAIL_STAMPS
     long long st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -367,12 +370,28 @@ __device__ __forceinline__ void tail2_block(const Tail2Layer& L, const Tail2Args
         if (ct > 0) {
             const int pt = ct - 1, b = pt & 1, c = b;
             const long cc[4] = {pair(rq01[c].x, rq01[c].y), pair(rq01[c].z, rq01[c].w), pair(rq23[c].x, rq23[c].y), pair(rq23[c].z, rq23[c].w)};
+            if constexpr (SAT && UPW % 2 == 0) {
+                const int se[4] = {rqe[c], rqe[c] >> 8, rqe[c] >> 16, rqe[c] >> 24};   // (the instruction reads the low five bits)
 #pragma unroll
-            for (int t = 0; t < UPW; ++t) {
-                int qv[4];
+                for (int t = 0; t < UPW; t += 2) {
+                    int ha[4], hb[4], ra, rb;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) qv[e] = med3(rq_hi(acc[b][t][e], rqm[c][e], cc[e], rqe[c], e), dw_lo, dw_hi);
-                bf[pass * UPW + t][pt >> 2][pt & 3] = pack4(qv);
+                    for (int e = 0; e < 4; ++e) {
+                        ha[e] = rq_h(acc[b][t][e], rqm[c][e], cc[e]);
+                        hb[e] = rq_h(acc[b][t + 1][e], rqm[c][e], cc[e]);
+                    }
+                    sat_pack_2x4(ra, rb, ha, hb, se);
+                    bf[pass * UPW + t][pt >> 2][pt & 3] = perm(rb, ra, kSatSelA);
+                    bf[pass * UPW + t + 1][pt >> 2][pt & 3] = perm(rb, ra, kSatSelB);
+                }
+            } else {
+#pragma unroll
+                for (int t = 0; t < UPW; ++t) {
+                    int qv[4];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) qv[e] = med3(rq_hi(acc[b][t][e], rqm[c][e], cc[e], rqe[c], e), dw_lo, dw_hi);
+                    bf[pass * UPW + t][pt >> 2][pt & 3] = pack4(qv);
+                }
             }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -448,24 +467,62 @@ __device__ __forceinline__ void tail2_block(const Tail2Layer& L, const Tail2Args
         }
         if (nt + 2 < NT) request_a(nt + 2);   // (into the fragments' slot of tile nt: its matrix instructions were issued an iteration ago)
         const long cc[4] = {pair(pc01[b].x, pc01[b].y), pair(pc01[b].z, pc01[b].w), pair(pc23[b].x, pc23[b].y), pair(pc23[b].z, pc23[b].w)};
+        // h of the stored value of tile t, channel e: behind the ADD hi32(total add_m + add_c), else hi32(x m + C) — what is left is shift, clamp, pack
+        auto out_h = [&](int t, int e) -> int {
+            if constexpr (ADD) {
+                const int xr = pres[b][t] ^ (int)0x80808080u;  // residual bytes + 128
+                const int v = rq_signed(pacc[b][t][e], pm[b][e], cc[e], pe1[b], e);                       // the block's own value minus its zero point
+                const uint32_t xt = (uint32_t)perm(0, xr, ((uint32_t)e << 24) | 0x000c0c0cu);            // (b + 128) << 24
+                const int f = (int)((uint32_t)(((unsigned long)xt * (unsigned long)res_m + (unsigned long)res_c) >> 32) >> res_k);
+                const int total = (v << 19) + f;
+                return (int)(((long)total * (long)add_m + add_c) >> 32);
+            } else {
+                return rq_h(pacc[b][t][e], pm[b][e], cc[e]);
+            }
+        };
+        auto out_at = [&](int t) -> int* { return reinterpret_cast<int*>(lds + L.y_off + (pbase + PSTEP * t) * POUT + 4 * g + 16 * nt); };
+        if constexpr (SAT && (ADD || UPW % 2 == 0)) {
+            if constexpr (UPW % 2 == 0) {
 #pragma unroll
-        for (int t = 0; t < UPW; ++t) {
-            const int p = pbase + PSTEP * t;
-            const int xr = ADD ? pres[b][t] ^ (int)0x80808080u : 0;  // residual bytes + 128
-            int qv[4];
+                for (int t = 0; t < UPW; t += 2) {
+                    int ha[4], hb[4], d0, d1;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                if constexpr (ADD) {
-                    const int v = rq_signed(pacc[b][t][e], pm[b][e], cc[e], pe1[b], e);                       // the block's own value minus its zero point
-                    const uint32_t xt = (uint32_t)perm(0, xr, ((uint32_t)e << 24) | 0x000c0c0cu);            // (b + 128) << 24
-                    const int f = (int)((uint32_t)(((unsigned long)xt * (unsigned long)res_m + (unsigned long)res_c) >> 32) >> res_k);
-                    const int total = (v << 19) + f;
-                    qv[e] = med3((int)(((long)total * (long)add_m + add_c) >> 32) >> add_e1, L.add_lo, L.add_hi);
-                } else {
-                    qv[e] = med3(rq_hi(pacc[b][t][e], pm[b][e], cc[e], pe1[b], e), pw_lo, pw_hi);
+                    for (int e = 0; e < 4; ++e) {
+                        ha[e] = out_h(t, e);
+                        hb[e] = out_h(t + 1, e);
+                    }
+                    if constexpr (ADD) {
+                        sat_pack_quads(d0, d1, ha, hb, add_e1);
+                    } else {
+                        const int se[4] = {pe1[b], pe1[b] >> 8, pe1[b] >> 16, pe1[b] >> 24};   // (the instruction reads the low five bits)
+                        int ra, rb;
+                        sat_pack_2x4(ra, rb, ha, hb, se);
+                        d0 = perm(rb, ra, kSatSelA);
+                        d1 = perm(rb, ra, kSatSelB);
+                    }
+                    *out_at(t) = d0;
+                    *out_at(t + 1) = d1;
+                }
+            } else {
+#pragma unroll
+                for (int t = 0; t < UPW; ++t) {
+                    int ha[4];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) ha[e] = out_h(t, e);
+                    *out_at(t) = sat_pack_quad(ha, add_e1);
                 }
             }
-            *reinterpret_cast<int*>(lds + L.y_off + p * POUT + 4 * g + 16 * nt) = pack4(qv);
+        } else {
+#pragma unroll
+            for (int t = 0; t < UPW; ++t) {
+                int qv[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    if constexpr (ADD) qv[e] = med3(out_h(t, e) >> add_e1, L.add_lo, L.add_hi);
+                    else qv[e] = med3(ashr_byte(pe1[b], out_h(t, e), e), pw_lo, pw_hi);
+                }
+                *out_at(t) = pack4(qv);
+            }
         }
         __builtin_amdgcn_sched_barrier(0);
     }
@@ -494,7 +551,7 @@ __device__ __forceinline__ void tail2_block(const Tail2Layer& L, const Tail2Args
 #endif
 }
 
-template <bool EMB>
+template <bool EMB, bool SAT>
 __device__ __forceinline__ void tail2_main(const Tail2Args& a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int ngroups = (a.B + kTailG - 1) / kTailG;
@@ -521,10 +578,10 @@ __device__ __forceinline__ void tail2_main(const Tail2Args& a) {
             if ((int)blockIdx.x < 8 && gi < 4 && li < 8 && g_tail2_stamps) slot = ((int)blockIdx.x * 4 + gi) * 8 + li;
 #endif
             // (the shapes of kTailShapes in bn_chain_plan.cpp: the planner refuses every other block)
-            if (L.Cin == 64) tail2_block<kTailG, 64, 128, 2, 16, 32, false, true>(L, a, lds, chunk0, nx, seq, slot);
-            else if (L.Cin == 128 && L.Cout == 128) tail2_block<kTailG, 128, 128, 1, 8, 16, true, false>(L, a, lds, chunk0, nx, seq, slot);
-            else if (L.Cin == 128) tail2_block<kTailG, 128, 256, 2, 8, 16, false, false>(L, a, lds, chunk0, nx, seq, slot);
-            else tail2_block<kTailG, 256, 256, 1, 4, 8, true, false>(L, a, lds, chunk0, nx, seq, slot);
+            if (L.Cin == 64) tail2_block<kTailG, 64, 128, 2, 16, 32, false, true, false, SAT>(L, a, lds, chunk0, nx, seq, slot);
+            else if (L.Cin == 128 && L.Cout == 128) tail2_block<kTailG, 128, 128, 1, 8, 16, true, false, false, SAT>(L, a, lds, chunk0, nx, seq, slot);
+            else if (L.Cin == 128) tail2_block<kTailG, 128, 256, 2, 8, 16, false, false, false, SAT>(L, a, lds, chunk0, nx, seq, slot);
+            else tail2_block<kTailG, 256, 256, 1, 4, 8, true, false, false, SAT>(L, a, lds, chunk0, nx, seq, slot);
         }
         int hslot = -1;
 #ifdef BN_TAIL_STAMPS
@@ -539,9 +596,16 @@ __device__ __forceinline__ void tail2_main(const Tail2Args& a) {
     }
 }
 
-__global__ __launch_bounds__(kTail2Threads) void i8_tail2_kernel(Tail2Args a) { tail2_main<false>(a); }
+// (one kernel, a workgroup-uniform choice of the epilogue form, as in i8_mid2_kernel below)
+__global__ __launch_bounds__(kTail2Threads) void i8_tail2_kernel(Tail2Args a) {
+    if (a.satpack) tail2_main<false, true>(a);
+    else tail2_main<false, false>(a);
+}
 // the same with the embedding output: the pooled vectors are stored where they are packed for the classifier
-__global__ __launch_bounds__(kTail2Threads) void i8_tail2_emb_kernel(WithEmb<Tail2Args> w) { tail2_main<true>(w.a); }
+__global__ __launch_bounds__(kTail2Threads) void i8_tail2_emb_kernel(WithEmb<Tail2Args> w) {
+    if (w.a.satpack) tail2_main<true, true>(w.a);
+    else tail2_main<true, false>(w.a);
+}
 
 // Stage 2 of the shipped graph with the same blocks: kMidG = 2 chunks per workgroup (a 16 x 32 map of 64 channels is 40 KB in LDS), the first
 // block's taps from memory, the last map written back for the tail kernel (coalesced 16-byte pieces).
@@ -558,7 +622,7 @@ __global__ __launch_bounds__(kTail2Threads) void i8_tail2_emb_kernel(WithEmb<Tai
 // wave by wave over the wave's own tiles): a wave's LDS operations complete in order, no barrier is needed there.
 // !RES: parts staged block by block into re-used LDS behind workgroup barriers (i8_tail2_kernel's way; the plan when the resident one
 // does not fit, and option i8_mid_split = 0).
-template <bool RES>
+template <bool RES, bool SAT>
 __device__ __forceinline__ void mid2_main(const Tail2Args& a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int ngroups = (a.B + kMidG - 1) / kMidG;
@@ -591,8 +655,8 @@ __device__ __forceinline__ void mid2_main(const Tail2Args& a) {
             if ((int)blockIdx.x < 8 && gi < 4 && li < 8 && g_mid2_stamps) slot = ((int)blockIdx.x * 4 + gi) * 8 + li;
 #endif
             // (the shapes of kMidShapes in bn_chain_plan.cpp)
-            if (li == 0) tail2_block<kMidG, 32, 64, 2, 32, 64, false, true, RES>(L, a, lds, chunk0, nx, seq, slot);
-            else tail2_block<kMidG, 64, 64, 1, 16, 32, true, false, RES>(L, a, lds, chunk0, nx, seq, slot);
+            if (li == 0) tail2_block<kMidG, 32, 64, 2, 32, 64, false, true, RES, SAT>(L, a, lds, chunk0, nx, seq, slot);
+            else tail2_block<kMidG, 64, 64, 1, 16, 32, true, false, RES, SAT>(L, a, lds, chunk0, nx, seq, slot);
         }
         // the last map: [chunk slot][position][C + 16] in LDS -> [chunk][position][C] in memory
         const Tail2Layer& L = a.L[a.n_layers - 1];
@@ -625,8 +689,13 @@ __device__ __forceinline__ void mid2_main(const Tail2Args& a) {
 
 // (one kernel, a workgroup-uniform choice of the form: the name the profiles and the benchmark key on stays whatever the option says)
 __global__ __launch_bounds__(kTail2Threads) void i8_mid2_kernel(Tail2Args a) {
-    if (a.resident) mid2_main<true>(a);
-    else mid2_main<false>(a);
+    if (a.resident) {
+        if (a.satpack) mid2_main<true, true>(a);
+        else mid2_main<true, false>(a);
+    } else {
+        if (a.satpack) mid2_main<false, true>(a);
+        else mid2_main<false, false>(a);
+    }
 }
 
 }  // namespace

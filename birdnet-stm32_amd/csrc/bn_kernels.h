@@ -50,6 +50,8 @@ struct Options {
     int stft_rowmajor = 0;     // keep the reference spectrogram layout inside bn_infer_audio (default: tile-major)
     int i8_mid_split = 1;      // i8_mid2_kernel with every block's constants resident in LDS (staged once) and barriers over the 4 waves of a chunk slot instead of the
                                // workgroup: its two halves run as independent streams; 0 (or a plan whose resident placement does not fit): parts staged per block
+    int i8_satpack = 3;        // shift, clamp and byte packing of a requantisation as v_ashr_pk_i8_i32 where the clamp is the int8 range (bn_requant.h: sat_pack2):
+                               // bit 0 = the fused chains (i8_mid2_kernel, i8_tail2_kernel; tail2_satpack_ok decides per plan), bit 1 = the stem rows of i8_front_strip_kernel (front_strip_satpack_ok); 0: med3 + shift + v_perm everywhere
     int i8_strip_mfdw = 1;     // stage1_ds2-shaped blocks (32 -> 32 channels, stride 1, residual ADD): depthwise 3x3 on the matrix cores (i8_strip_mf_kernel); 0: i8_strip_kernel
     int stft_exact = 2;        // INT8 plans from audio: 2 = float32 STFT + float64 pass over the doubtful elements (bit-exact input bytes,
                                // bn_stft_exact.hip; plans / options the guarded kernels do not cover take 1), 1 = every bin as a float64
@@ -314,6 +316,8 @@ void launch_i8_head_softmax(const int8_t* x, float* scores, float* logits, int B
 void launch_i8_head(const int8_t* x, float* scores, float* logits, int B, int C, int zp_fc, int zp_out, float s_fc,
                     float s_out, const int8_t* lut, hipStream_t s);
 
+// mode 0: sat_pack2(a, b, s); mode 1: sat_pack2_hi on a destination of 0x1234BEEF; out[i] = the whole register
+void launch_debug_satpack(const int32_t* a, const int32_t* b, const int32_t* s, int n, int mode, uint32_t* out, hipStream_t st);
 void launch_debug_requant(const int32_t* x, const int32_t* mult, const int32_t* shift, int n, int mode, int zp, int32_t* out, hipStream_t s);
 
 // Fused INT8 depthwise 3x3 -> pointwise 1x1 block on the int8 matrix cores (bn_i8_fused.hip).
@@ -378,7 +382,10 @@ struct FrontStrip8Args {
     const int32_t* cst; // models/_lower_i8.py: front_strip_constants
     int B, H0, W0, OH, OW, TH;
     int zp_fe, st_lo, st_hi, zp_st, dw_lo, dw_hi, pw_lo, pw_hi;
+    int satpack;        // the stem rows' shift-saturate-pack form: (st_lo, st_hi) = (-128, 127) and option i8_satpack bit 1 (front_strip_satpack_ok)
 };
+// the stem's clamp is the int8 range: the saturation of v_ashr_pk_i8_i32 is the clamp
+inline bool front_strip_satpack_ok(int st_lo, int st_hi) { return st_lo == -128 && st_hi == 127; }
 bool i8_front_strip_supported(int H0, int W0, int C, int N, int OH, int OW);
 void launch_i8_front_strip(FrontStrip8Args a, hipStream_t s);
 bool i8_strip_supported(int Cin, int Cout, int stride, int OW, bool add);

@@ -549,7 +549,8 @@ struct PlanRun {
         q.rq_right = m->prep[oi]->rq_right;
         if (p[k::strip] && o->t[k::strip_cst] >= 0 && g_opt.i8_strip && i8_front_strip_supported(q.H0, q.W0, q.C, q.N, q.OH, q.OW)) {
             FrontStrip8Args fa{(const int8_t*)in0, (int8_t*)out, t32(*o, k::strip_cst), B, q.H0, q.W0, q.OH, q.OW, 0, q.stem_zp_in, q.stem_amin, q.stem_amax,
-                               q.stem_zp_out, q.dw_amin, q.dw_amax, q.pw_amin, q.pw_amax};
+                               q.stem_zp_out, q.dw_amin, q.dw_amax, q.pw_amin, q.pw_amax, 0};
+            fa.satpack = (g_opt.i8_satpack & 2) && front_strip_satpack_ok(q.stem_amin, q.stem_amax);
             launch_i8_front_strip(fa, s);
             return BN_OK;
         }
@@ -565,6 +566,7 @@ struct PlanRun {
         ma.y = (int8_t*)out;
         ma.cst = t32(*o, op::i8_mid::cst);
         ma.B = B;
+        if (!(g_opt.i8_satpack & 1)) ma.satpack = 0;
         if (!launch_i8_mid2(ma, s)) return fail(BN_ERR_DEVICE, "could not raise the LDS limit of the fused stage-2 kernel");
         return BN_OK;
     }
@@ -583,6 +585,7 @@ struct PlanRun {
             t2.logits = a.d_logits;
             t2.cst = t32(*o, k::cst2);
             t2.B = B;
+            if (!(g_opt.i8_satpack & 1)) t2.satpack = 0;
             launched = launch_i8_tail2(t2, s, emb);
         } else {
             Tail8Args ta = pr.tail;

@@ -184,6 +184,75 @@ __device__ __forceinline__ void deposit_two_quads(int& d0, int& d1, const int (&
           [b2] "v"(b[2]), [b3] "v"(b[3]));
 }
 
+// Shift, clamp and pack as ONE instruction where the clamp is the int8 range: v_ashr_pk_i8_i32 d, a, b, s shifts two int32 right
+// arithmetically by s[4:0], saturates each to [-128, 127] and writes the two bytes into one half of d (byte 0 of the half from a, byte 1
+// from b); op_sel:[0,0,0,1] picks the high half.  Either form leaves the other half of d as it was (tests/test_gpu_satpack.py holds the
+// hardware to all of this).  clamp(h >> e1, -128, 127) == sat_i8(h >> e1) for every int32 h, so where (lo, hi) = (-128, 127) the tail
+// med3 + shift + byte packing of a requantisation collapses into it — for two values that share their shift: two positions of one
+// channel, or two channels behind a per-layer shift (tests/test_satpack_forms.py has the algebra of every use).
+// The high-half write is a partial write under the rule above: a block that a vector-ALU instruction may read next ends in s_nop 0, and
+// two writes of the same register have a write of another register (or s_nop 0) between them.
+//
+// the pair in the low half, the high half zero
+__device__ __forceinline__ int sat_pack2(int h0, int h1, int s) { return (int)(uint16_t)__builtin_amdgcn_ashr_pk_i8_i32(h0, h1, s); }
+// the pair into the high half of dst, its low half kept
+__device__ __forceinline__ void sat_pack2_hi(int& dst, int h0, int h1, int s) {
+    asm("v_ashr_pk_i8_i32 %0, %1, %2, %3 op_sel:[0,0,0,1]\n\ts_nop 0" : "+v"(dst) : "v"(h0), "v"(h1), "v"(s));
+}
+// Two positions (a, b) x four channels behind per-channel shifts s[0..3] (low five bits): ra = bytes (a0 b0 a1 b1), rb = (a2 b2 a3 b3).
+// The byte selectors kSatSelA / kSatSelB of perm(rb, ra, .) then give position a's and position b's dword of NHWC bytes.
+constexpr uint32_t kSatSelA = 0x06040200u, kSatSelB = 0x07050301u;
+__device__ __forceinline__ void sat_pack_2x4(int& ra, int& rb, const int (&a)[4], const int (&b)[4], const int (&s)[4]) {
+    asm("v_ashr_pk_i8_i32 %[ra], %[a0], %[b0], %[s0]\n\t"
+        "v_ashr_pk_i8_i32 %[rb], %[a2], %[b2], %[s2]\n\t"
+        "v_ashr_pk_i8_i32 %[ra], %[a1], %[b1], %[s1] op_sel:[0,0,0,1]\n\t"
+        "v_ashr_pk_i8_i32 %[rb], %[a3], %[b3], %[s3] op_sel:[0,0,0,1]\n\t"
+        "s_nop 0"
+        : [ra] "=&v"(ra), [rb] "=&v"(rb)
+        : [a0] "v"(a[0]), [a1] "v"(a[1]), [a2] "v"(a[2]), [a3] "v"(a[3]), [b0] "v"(b[0]), [b1] "v"(b[1]), [b2] "v"(b[2]), [b3] "v"(b[3]),
+          [s0] "v"(s[0]), [s1] "v"(s[1]), [s2] "v"(s[2]), [s3] "v"(s[3]));
+}
+// The four channels of ONE position behind a shift all four share (wave-uniform: the ADD's output rescale) -> its dword of NHWC bytes.
+// Two positions at a time, the writes alternating between the dwords; the dwords go to a store (no vector-ALU reader).
+__device__ __forceinline__ void sat_pack_quads(int& d0, int& d1, const int (&a)[4], const int (&b)[4], int s) {
+    asm("v_ashr_pk_i8_i32 %[d0], %[a0], %[a1], %[s]\n\t"
+        "v_ashr_pk_i8_i32 %[d1], %[b0], %[b1], %[s]\n\t"
+        "v_ashr_pk_i8_i32 %[d0], %[a2], %[a3], %[s] op_sel:[0,0,0,1]\n\t"
+        "v_ashr_pk_i8_i32 %[d1], %[b2], %[b3], %[s] op_sel:[0,0,0,1]"
+        : [d0] "=&v"(d0), [d1] "=&v"(d1)
+        : [a0] "v"(a[0]), [a1] "v"(a[1]), [a2] "v"(a[2]), [a3] "v"(a[3]), [b0] "v"(b[0]), [b1] "v"(b[1]), [b2] "v"(b[2]), [b3] "v"(b[3]), [s] "s"(s));
+}
+// Three columns (h0, h1, h2) of four channels behind per-channel shifts s[0..3] -> byte j of t[e] = column j of channel e: the depthwise
+// window dwords deposit_column builds, in two steps so that a third column may be computed between them.  Byte 3 repeats column 2
+// (the window's fourth tap weight is 0).  The second step ends the block for any reader.
+__device__ __forceinline__ void sat_window_lo(int (&t)[4], const int (&h0)[4], const int (&h1)[4], const int (&s)[4]) {
+    asm("v_ashr_pk_i8_i32 %[t0], %[a0], %[b0], %[s0]\n\t"
+        "v_ashr_pk_i8_i32 %[t1], %[a1], %[b1], %[s1]\n\t"
+        "v_ashr_pk_i8_i32 %[t2], %[a2], %[b2], %[s2]\n\t"
+        "v_ashr_pk_i8_i32 %[t3], %[a3], %[b3], %[s3]"
+        : [t0] "=&v"(t[0]), [t1] "=&v"(t[1]), [t2] "=&v"(t[2]), [t3] "=&v"(t[3])
+        : [a0] "v"(h0[0]), [a1] "v"(h0[1]), [a2] "v"(h0[2]), [a3] "v"(h0[3]), [b0] "v"(h1[0]), [b1] "v"(h1[1]), [b2] "v"(h1[2]), [b3] "v"(h1[3]),
+          [s0] "v"(s[0]), [s1] "v"(s[1]), [s2] "v"(s[2]), [s3] "v"(s[3]));
+}
+__device__ __forceinline__ void sat_window_hi(int (&t)[4], const int (&h2)[4], const int (&s)[4]) {
+    asm("v_ashr_pk_i8_i32 %[t0], %[a0], %[a0], %[s0] op_sel:[0,0,0,1]\n\t"
+        "v_ashr_pk_i8_i32 %[t1], %[a1], %[a1], %[s1] op_sel:[0,0,0,1]\n\t"
+        "v_ashr_pk_i8_i32 %[t2], %[a2], %[a2], %[s2] op_sel:[0,0,0,1]\n\t"
+        "v_ashr_pk_i8_i32 %[t3], %[a3], %[a3], %[s3] op_sel:[0,0,0,1]\n\t"
+        "s_nop 0"
+        : [t0] "+v"(t[0]), [t1] "+v"(t[1]), [t2] "+v"(t[2]), [t3] "+v"(t[3])
+        : [a0] "v"(h2[0]), [a1] "v"(h2[1]), [a2] "v"(h2[2]), [a3] "v"(h2[3]), [s0] "v"(s[0]), [s1] "v"(s[1]), [s2] "v"(s[2]), [s3] "v"(s[3]));
+}
+__device__ __forceinline__ int sat_pack_quad(const int (&a)[4], int s) {
+    int d;
+    asm("v_ashr_pk_i8_i32 %[d], %[a0], %[a1], %[s]\n\t"
+        "s_nop 0\n\t"
+        "v_ashr_pk_i8_i32 %[d], %[a2], %[a3], %[s] op_sel:[0,0,0,1]"
+        : [d] "=&v"(d)
+        : [a0] "v"(a[0]), [a1] "v"(a[1]), [a2] "v"(a[2]), [a3] "v"(a[3]), [s] "s"(s));
+    return d;
+}
+
 // int8 MEAN of `raw_sum` = sum of the P raw bytes of a channel.  Two published forms (oracle/int8_graph.py has both behind mean_form):
 //   integer (default): MultiplyByQuantizedMultiplier(raw_sum - zp_in P, mult, shift) with 1 / P folded into the multiplier (reduce.h);
 //   float (shift == kMeanFloatForm, mult = the float32 bits of s_in / s_out): TFLite's float-arithmetic QuantizedMeanOrSum —

@@ -330,10 +330,19 @@ BN_API int bn_debug_mid_form(const bn_model* model, int* form, int* lds_bytes);
  * n >= 5 + 6 * blocks.  bn_debug_mid_split_giveups: *count = chunk barriers whose bounded wait ran out since the library was loaded (waits
  * for the device; 0 in a working build). */
 BN_API int bn_debug_mid_plan(const bn_model* model, int* out, int n);
+/* Test hook: which requantisation tail the plan's fused INT8 kernels run by default — *mid for i8_mid2_kernel, *tail for i8_tail2_kernel, *front
+ * for the stem rows of i8_front_strip_kernel: 1 = shift, clamp and byte packing as one packed shift-and-saturate instruction (every stored
+ * clamp of the chain / the stem's clamp is the int8 range; option i8_satpack bit 0 switches the chains' off, bit 1 the stem's), 0 = a narrower
+ * clamp keeps the three-instruction form, -1 = the plan does not run that kernel. */
+BN_API int bn_debug_satpack_form(const bn_model* model, int* mid, int* tail, int* front);
 BN_API int bn_debug_mid_split_giveups(bn_ctx* ctx, int64_t* count);
 
 BN_API int bn_debug_requant(bn_ctx* ctx, const int32_t* d_x, const int32_t* d_mult, const int32_t* d_shift, int n, int mode,
                      int zero_point, int32_t* d_out, void* stream);
+/* Test hook: the kernels' packed shift-and-saturate primitives on arrays — d_out[i] = the whole destination register.  mode 0: bytes
+ * (sat_i8(a >> s), sat_i8(b >> s)) in the low half, the high half zero; mode 1: the same pair into the high half of a register that held
+ * 0x1234BEEF, its low half kept.  s counts with its low five bits. */
+BN_API int bn_debug_satpack(bn_ctx* ctx, const int32_t* d_a, const int32_t* d_b, const int32_t* d_s, int n, int mode, uint32_t* d_out, void* stream);
 
 /* Per-operator timing with HIP events recorded on the launch stream.  While enabled, every plan
  * operator of bn_forward / bn_infer_audio is bracketed by an event pair (index n_ops = the STFT
@@ -349,7 +358,7 @@ BN_API int bn_profile_collect(bn_model* model, double* total_ms, int64_t* launch
 
 /* Run-time switches of the kernel launchers, for A/B measurements and tests (process-wide; the defaults are the production
  * choices).  Names: "f32_strip", "f32_strip_th", "f32_front_staged", "f32_front2", "f32_pwdw", "f32_tile_slice", "f32_pw_ws", "i8_pwdw", "i8_pw_lds", "i8_pw_forms", "i8_add_tab", "front_tpw", "wave_dwpw", "i8_strip", "i8_strip_mfdw", "i8_strip_th",
- * "i8_dw_pool", "i8_tail_fclds", "i8_tail", "i8_tail_mfdw", "i8_mid", "i8_mid_split", "i8_mel_generic", "stft_rowmajor", "stft_exact", "stft_flagcap", "stft_guard", "stft_audit", "stft_minint", "ingest_blk", "ingest_generic" (csrc/bn_kernels.h: Options says
+ * "i8_dw_pool", "i8_tail_fclds", "i8_tail", "i8_tail_mfdw", "i8_mid", "i8_mid_split", "i8_satpack", "i8_mel_generic", "stft_rowmajor", "stft_exact", "stft_flagcap", "stft_guard", "stft_audit", "stft_minint", "ingest_blk", "ingest_generic" (csrc/bn_kernels.h: Options says
  * what each selects).  An environment variable BN_<NAME IN CAPITALS> seeds the value once when the library is loaded; no
  * launch reads the environment.  The reference has no counterpart (tf.lite.Interpreter's delegates / num_threads arguments,
  * birdnet_stm32/models/runners.py:57, are the closest thing).  Unknown name: BN_ERR_ARG. */
