@@ -38,6 +38,7 @@ EXPORTS = (
     "bn_probe_mlp_set", "bn_head_mlp_forward",
     "bn_short_time_energy", "bn_activity_counts", "bn_search_inv_norms", "bn_search_topk", "bn_augment_inputs",
     "bn_kmeans_assign", "bn_kmeans_accumulate", "bn_kmeans_centroids",
+    "bn_density_nearest",
     "bn_tsne_perplexity", "bn_tsne_gradient", "bn_tsne_update",
     "bn_bootstrap_rejections", "bn_bootstrap_counts", "bn_bootstrap_ap", "bn_head_i8_forward", "bn_head_i8_pass_classes",
 )  # fmt: skip
@@ -79,6 +80,27 @@ BOOTSTRAP_MAX_N = 32768  # BN_BOOTSTRAP_MAX_N
 KMEANS_LDS_BYTES, KMEANS_MAX_TILE, KMEANS_STEP_ROWS, KMEANS_MIN_WG_STEPS, KMEANS_MAX_WGS, KMEANS_SEGMENT_ROWS = 160 * 1024, 128, 64, 8, 1024, 256
 # bn_tsne_* (include/birdnet_hip.h): rows of a repulsion workgroup, points per LDS tile, columns per range of the second grid axis, lanes per row
 TSNE_TILE_I, TSNE_TILE_J, TSNE_SPLIT_J, TSNE_ROW_LANES, TSNE_MAX_K, TSNE_MAX_N = 256, 1024, 4096, 16, 128, 1 << 21
+# bn_density_nearest (include/birdnet_hip.h): limits, and the constants the staged tile and the streamed row ranges follow from
+DENSITY_MAX_N, DENSITY_MAX_D = 1 << 20, 2048
+DENSITY_LDS_BYTES, DENSITY_MAX_TILE, DENSITY_STEP_ROWS, DENSITY_MIN_WG_STEPS, DENSITY_MAX_ROW_WGS = 160 * 1024, 128, 64, 32, 256
+
+
+def density_tile_rows(n: int, D: int, int8: bool) -> int:
+    """Rows per LDS tile of ``bn_density_nearest`` (``density_geometry`` of csrc/bn_density.hip)."""
+    pitch_bytes = -(-int(D) // 64) * 64 + 16 if int8 else (-(-int(D) // 64) * 64 + 4) * 4
+    nt = DENSITY_MAX_TILE // 16
+    while nt > 1 and 16 * nt * pitch_bytes > DENSITY_LDS_BYTES:
+        nt //= 2
+    while nt > 1 and 16 * (nt // 2) >= n:
+        nt //= 2
+    return 16 * nt
+
+
+def density_rows_per_workgroup(n: int) -> int:
+    """Rows of the range a workgroup of ``bn_density_nearest`` streams (``split_rows`` of csrc/bn_rowstream.h)."""
+    steps = -(-int(n) // DENSITY_STEP_ROWS)
+    wgs = min(max(-(-steps // DENSITY_MIN_WG_STEPS), 1), DENSITY_MAX_ROW_WGS)
+    return -(-steps // wgs) * DENSITY_STEP_ROWS
 
 
 def kmeans_tile_centroids(D: int, K: int) -> int:
@@ -190,6 +212,7 @@ def load_library(path: str | None = None):
                                      c_void_p, c_void_p]
     lib.bn_kmeans_accumulate.argtypes = [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]
     lib.bn_kmeans_centroids.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]
+    lib.bn_density_nearest.argtypes = [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.bn_tsne_perplexity.argtypes = [c_void_p, c_void_p, c_int64, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p]
     lib.bn_tsne_gradient.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.bn_tsne_update.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_void_p]

@@ -427,7 +427,7 @@ void launch_i8_dwpw(const DwPw8Args& a, hipStream_t s);
 // One per source file with kernels: load that file's device code object now (bn_preload_kernels)
 void preload_f32(); void preload_f32_fused(); void preload_f32_pw(); void preload_f32_strip(); void preload_i8(); void preload_i8_fused();
 void preload_i8_pw(); void preload_i8_strip(); void preload_i8_tail(); void preload_i8_tail2(); void preload_ingest(); void preload_melspec();
-void preload_stft(); void preload_stft_exact(); void preload_sort(); void preload_probe(); void preload_probe_sweep(); void preload_activity(); void preload_search(); void preload_augment(); void preload_kmeans(); void preload_tsne(); void preload_bootstrap(); void preload_head_i8();
+void preload_stft(); void preload_stft_exact(); void preload_sort(); void preload_probe(); void preload_probe_sweep(); void preload_activity(); void preload_search(); void preload_augment(); void preload_kmeans(); void preload_density(); void preload_tsne(); void preload_bootstrap(); void preload_head_i8();
 
 // bn_probe.hip: a classifier head on embeddings (bn_head_forward) and its training step (bn_probe_*)
 struct ProbeFwdArgs {
@@ -627,6 +627,26 @@ size_t kmeans_accumulate_workspace(long n, int D, int K);
 bool launch_kmeans_accumulate(const void* rows, bool i8, long n, int D, int zp, const float* row_inv, const int* label, int K, int accumulate, float* sums,
                               long long* counts, void* d_work, size_t work_bytes, hipStream_t s);
 void launch_kmeans_centroids(const float* sums, const long long* counts, int K, int D, float* cent, float* cent_inv, hipStream_t s);
+
+// bn_density.hip: one Borůvka round over the mutual-reachability graph of the rows (bn_density_nearest)
+struct DensityArgs {
+    const void* rows;        // [n, D] float32 or int8 rows
+    const float* inv;        // [n] inverse norms
+    const float* core;       // [n] core scores
+    const int* comp;         // [n] component of every row, < 0: the row takes no part
+    unsigned long long* best;   // [n] keys, zeroed by the launcher's caller; the kernel only raises them
+    int n, D, zp;
+    long steps_per_wg;       // steps of BN_DENSITY_STEP_ROWS rows a workgroup streams
+};
+struct DensityGeom {
+    int nt;                  // staged subtiles of 16 rows per LDS tile
+    int tiles;               // first grid axis: LDS tiles the n rows take
+    int nwg;                 // second grid axis: workgroups along the streamed rows
+    long steps_per_wg;
+    size_t lds;
+};
+bool density_geometry(long n, int D, bool i8, DensityGeom* g);   // from the shapes only; false: no tile fits the LDS
+bool launch_density_nearest(const DensityArgs& a, const DensityGeom& g, bool i8, hipStream_t s);   // false: the runtime refused the LDS request
 
 // bn_tsne.hip: exact t-SNE over a 2-D map — conditional affinities, gradient (all-pairs repulsion, CSR attraction) and update (bn_tsne_*)
 void launch_tsne_perplexity(const float* score, long n, int k, double perplexity, float* p, double* beta, hipStream_t s);

@@ -645,6 +645,31 @@ BN_API int bn_kmeans_accumulate(bn_ctx* ctx, const void* d_rows, int dtype, int6
 BN_API int bn_kmeans_centroids(bn_ctx* ctx, const float* d_sums, const int64_t* d_counts, int K, int D, float* d_centroids, float* d_cent_inv,
                         void* stream);
 
+/* ---- Density clustering: one Borůvka round of the mutual-reachability spanning tree (csrc/bn_density.hip; no reference counterpart) ----
+ * (HDBSCAN over cosine scores; birdnet_stm32/evaluation/density.py is the specification.)  Rows, dot and inv have bn_search's meaning.
+ *   s_ij = fl(dot_ij * fl(inv_i * inv_j))      one value per pair, whichever end it is looked at from
+ *   m_ij = min(s_ij, core_i, core_j)           the mutual-reachability score; a negative zero counts as the positive one
+ *   d_best[i] = the key of the best (m_ij, j) over the rows j with comp[j] >= 0 and comp[j] != comp[i]: m descending, then j ascending.
+ *               key = (image of m) << 32 | (0xFFFFFFFF - j), where the image of a float32 with bits u is ~u for a set sign bit and
+ *               u | 0x80000000 otherwise, so a larger key is a better pair; 0 where there is no such row or comp[i] < 0.
+ * Cores are finite or +inf.  The bests of the tiles and workgroups meet in a 64-bit integer atomicMax: a maximum under a total order, so
+ * the same inputs give the same bits on every run; no floating-point atomics.  1 <= D <= BN_DENSITY_MAX_D, 0 <= n <= BN_DENSITY_MAX_N.
+ * float32 rows need 4-byte alignment (16 with D % 4 == 0 takes the wide loads; int8: 16 with D % 16 == 0), d_best 8-byte alignment.  A
+ * refused call returns BN_ERR_ARG and writes nothing.  Nothing synchronises with the host inside the call. */
+#define BN_DENSITY_MAX_N (1 << 20)
+#define BN_DENSITY_MAX_D 2048
+/* How the work is dealt — from (n, D, dtype) alone.  A workgroup stages a tile of 16, 32, 64 or BN_DENSITY_MAX_TILE rows in LDS: the largest
+ * whose rows (D rounded up to 64 elements, plus 16 bytes) fit BN_DENSITY_LDS_BYTES, halved while half of it still holds all n rows.  The
+ * first grid axis holds the ceil(n / tile) tiles.  Against its tile a workgroup streams a range of all rows in steps of BN_DENSITY_STEP_ROWS,
+ * at least BN_DENSITY_MIN_WG_STEPS steps per workgroup, at most BN_DENSITY_MAX_ROW_WGS ranges: the second grid axis. */
+#define BN_DENSITY_LDS_BYTES (160 * 1024)
+#define BN_DENSITY_MAX_TILE 128
+#define BN_DENSITY_STEP_ROWS 64
+#define BN_DENSITY_MIN_WG_STEPS 32
+#define BN_DENSITY_MAX_ROW_WGS 256
+BN_API int bn_density_nearest(bn_ctx* ctx, const void* d_rows, int dtype, int64_t n, int D, int zero_point, const float* d_inv,
+                       const float* d_core, const int32_t* d_comp, uint64_t* d_best, void* stream);
+
 /* ---- Projection: exact t-SNE with k-nearest-neighbour affinities and all-pairs repulsion (csrc/bn_tsne.hip; no reference counterpart) ----
  * (van der Maaten's formulas with the constants of scikit-learn 1.7's sklearn.manifold.TSNE; birdnet_stm32/evaluation/project.py is the
  * specification.)  A map is Y [n, 2] float32.  With w_ij = 1 / (1 + |y_i - y_j|^2):
