@@ -20,7 +20,7 @@ from ctypes import POINTER, byref, c_char_p, c_float, c_int, c_int32, c_int64, c
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))  # .../birdnet-stm32_amd
 LIB_PATH = os.path.join(_PKG_ROOT, "lib", "libbirdnet_hip.so")
 
-ABI_VERSION = 2
+ABI_VERSION = 3
 
 # every symbol include/birdnet_hip.h declares
 EXPORTS = (
@@ -40,6 +40,7 @@ EXPORTS = (
     "bn_kmeans_assign", "bn_kmeans_accumulate", "bn_kmeans_centroids",
     "bn_density_nearest",
     "bn_tsne_perplexity", "bn_tsne_gradient", "bn_tsne_update",
+    "bn_pca_colsum", "bn_pca_gram", "bn_pca_transform",
     "bn_bootstrap_rejections", "bn_bootstrap_counts", "bn_bootstrap_ap", "bn_head_i8_forward", "bn_head_i8_pass_classes",
 )  # fmt: skip
 
@@ -83,6 +84,30 @@ TSNE_TILE_I, TSNE_TILE_J, TSNE_SPLIT_J, TSNE_ROW_LANES, TSNE_MAX_K, TSNE_MAX_N =
 # bn_density_nearest (include/birdnet_hip.h): limits, and the constants the staged tile and the streamed row ranges follow from
 DENSITY_MAX_N, DENSITY_MAX_D = 1 << 20, 2048
 DENSITY_LDS_BYTES, DENSITY_MAX_TILE, DENSITY_STEP_ROWS, DENSITY_MIN_WG_STEPS, DENSITY_MAX_ROW_WGS = 160 * 1024, 128, 64, 32, 256
+# bn_pca_* (include/birdnet_hip.h): the limit, the rows whose products stay in float32 accumulators, and the constants the row ranges follow from
+PCA_MAX_D, PCA_RUN_ROWS, PCA_STAGE_ROWS, PCA_MACRO, PCA_GRAM_TARGET_WGS, PCA_GRAM_MAX_RANGES = 2048, 256, 64, 64, 1024, 256
+PCA_COLSUM_COLS, PCA_COLSUM_MIN_ROWS, PCA_COLSUM_MAX_WGS = 256, 256, 1024
+PCA_LDS_BYTES, PCA_MAX_TILE, PCA_STEP_ROWS, PCA_MIN_WG_STEPS, PCA_MAX_WGS = 160 * 1024, 128, 64, 8, 1024
+
+
+def pca_gram_rows_per_range(n: int, D: int) -> int:
+    """Rows of the range a workgroup of ``bn_pca_gram`` sums, a whole number of runs (``pca_gram_geometry`` of csrc/bn_pca.hip)."""
+    m = -(-int(D) // PCA_MACRO)
+    pairs = m * (m + 1) // 2
+    runs = -(-int(n) // PCA_RUN_ROWS)
+    ranges = max(1, min(-(-PCA_GRAM_TARGET_WGS // pairs), PCA_GRAM_MAX_RANGES, runs))
+    return max(1, -(-runs // ranges)) * PCA_RUN_ROWS
+
+
+def pca_tile_rows(D: int, r: int) -> int:
+    """Rows of ``W`` per LDS tile of ``bn_pca_transform`` (``pca_transform_geometry`` of csrc/bn_pca.hip)."""
+    dp = -(-int(D) // 64) * 64
+    nt = 1
+    while nt < PCA_MAX_TILE // 16 and 16 * nt < r:
+        nt *= 2
+    while nt > 1 and 16 * nt * (dp + 4) * 4 + dp * 4 > PCA_LDS_BYTES:
+        nt //= 2
+    return 16 * nt
 
 
 def density_tile_rows(n: int, D: int, int8: bool) -> int:
@@ -216,6 +241,9 @@ def load_library(path: str | None = None):
     lib.bn_tsne_perplexity.argtypes = [c_void_p, c_void_p, c_int64, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p]
     lib.bn_tsne_gradient.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.bn_tsne_update.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_void_p]
+    lib.bn_pca_colsum.argtypes = [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p]
+    lib.bn_pca_gram.argtypes = [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]
+    lib.bn_pca_transform.argtypes = [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]
     u64 = ctypes.c_uint64
     lib.bn_bootstrap_rejections.argtypes = [c_void_p, u64, u64, u64, u64, ctypes.c_uint32, c_int64, c_int64, c_void_p, c_int64, POINTER(c_int64), c_void_p]
     lib.bn_bootstrap_counts.argtypes = [c_void_p, u64, u64, u64, u64, c_int, c_int, c_void_p, c_void_p, c_void_p]

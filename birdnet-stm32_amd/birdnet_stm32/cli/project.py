@@ -29,7 +29,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--early_exaggeration", type=float, default=12.0, help="Factor on the affinities during the first iterations")
     p.add_argument("--exaggeration_iter", type=int, default=250, help="Iterations with early exaggeration")
     p.add_argument("--learning_rate", type=float, default=None, help="Step size (default: max(rows / early_exaggeration / 4, 50))")
-    p.add_argument("--seed", type=int, default=42, help="Seed of the initial map")
+    p.add_argument("--seed", type=int, default=42, help="Seed of the initial map (--init random)")
+    p.add_argument("--init", type=str, default="random", choices=("random", "pca"),
+                   help="Initial map: a seeded Gaussian, or the first two principal components (scikit-learn's default: maps keep their global arrangement)")
     p.add_argument("--chunk_duration", type=float, default=0.0, help="Seconds per row, for end_s")
     p.add_argument("--npz_out", type=str, default="", help="Write the map as an .npz archive as well")
     p.add_argument("--device", type=int, default=0, help="MI355X index")
@@ -91,7 +93,8 @@ def main(argv=None):
     try:
         index = EmbeddingIndex.from_npz(*args.database)
         result = project_index(index, perplexity=args.perplexity, n_iter=args.n_iter, early_exaggeration=args.early_exaggeration,
-                               exaggeration_iter=args.exaggeration_iter, learning_rate=args.learning_rate, seed=args.seed, device=args.device)
+                               exaggeration_iter=args.exaggeration_iter, learning_rate=args.learning_rate, seed=args.seed, device=args.device,
+                               init=args.init)
     except ValueError as exc:
         raise SystemExit(f"error: {exc}") from None
     write_map_csv(args.output, index, result, args.chunk_duration)

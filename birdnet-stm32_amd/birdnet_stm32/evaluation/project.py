@@ -17,7 +17,10 @@ scikit-learn 1.7's ``sklearn.manifold.TSNE``; no Barnes-Hut, no FFT.
    been tried; the last value tried stands.  ``P_cond[i, j] = p_j / S``, stored as float32.
 4. Symmetrisation (host).  ``P = (P_cond + P_cond^T) / (2 n)`` over the union of the two patterns, float64, stored as float32 in CSR with
    ascending columns; a row holds anything from 0 to n - 1 entries.
-5. Start.  ``Y = float32(1e-4 * default_rng([seed]).standard_normal((n, 2)))``, update 0, gains 1.
+5. Start.  ``Y = float32(1e-4 * default_rng([seed]).standard_normal((n, 2)))``, update 0, gains 1 (``init="random"``, the default).  With
+   ``init="pca"`` (scikit-learn's own default) the start is the first two principal-component scores of the non-zero rows, unwhitened
+   (``evaluation/reduce.py``), scaled by scikit-learn's rule ``Y = float32(scores / std(scores[:, 0]) * 1e-4)``, the standard deviation with
+   ddof 0 in float64 (``initial_map_pca``); it needs at least 3 non-zero rows and two components of positive variance.
 6. Gradient.  With ``w_ij = 1 / (1 + |y_i - y_j|^2)`` and exaggeration E: ``A_i = sum_{j in row i of P} p_ij w_ij (y_i - y_j)``,
    ``R_i = sum_{j != i} w_ij^2 (y_i - y_j)``, ``Z = sum_i sum_{j != i} w_ij``, ``grad_i = 4 (E A_i - R_i / Z)``.  Summation orders and the
    reciprocal are the implementation's; Z is a float64 sum of float32 row sums on the device.  ``kl_i = sum_j p_ij log(p_ij / w_ij)`` over
@@ -205,6 +208,40 @@ def initial_map(n: int, seed: int) -> np.ndarray:
     return (1e-4 * np.random.default_rng([int(seed)]).standard_normal((n, 2))).astype(np.float32)
 
 
+INITS = ("random", "pca")
+
+
+def check_init(init: str) -> str:
+    if init not in INITS:
+        raise ValueError(f"init must be one of {INITS}, not {init!r}")
+    return init
+
+
+def initial_map_pca(scores) -> np.ndarray:
+    """scikit-learn's ``init="pca"`` start from the first two unwhitened scores ``[n, >= 2]``: ``scores / std(scores[:, 0]) * 1e-4``, the
+    standard deviation with ddof 0, all in float64, rounded to float32 once."""
+    s = np.asarray(scores, np.float64)
+    if s.ndim != 2 or s.shape[0] < 3 or s.shape[1] < 2:
+        raise ValueError(f"a PCA start needs at least 3 non-zero rows and 2 components, got scores of shape {s.shape}")
+    s = s[:, :2]
+    std = s.std(axis=0)
+    if not (np.isfinite(std).all() and (std > 0).all()):
+        raise ValueError("a PCA start needs two components of positive variance")
+    return (s / std[0] * 1e-4).astype(np.float32)
+
+
+def _pca_model_for_start(fit, n: int):
+    """The two-component model of a PCA start from ``fit(n_components)``, its refusals worded for the map."""
+    if n < 3:
+        raise ValueError(f"init='pca' needs at least 3 non-zero rows, the archive holds {n}")
+    from birdnet_stm32.evaluation.reduce import WHITEN_FLOOR
+
+    model = fit(2)
+    if not model.explained_variance[1] > WHITEN_FLOOR * model.explained_variance[0]:   # (anything below is the rounding noise of the spectrum)
+        raise ValueError("init='pca' needs two components of positive variance")
+    return model
+
+
 @dataclass
 class ProjectionResult:
     """``xy`` [N, 2] float32 (NaN for a zero row), ``kl`` of the final map, ``kl_history`` as (iteration, kl) pairs (every ``kl_every``
@@ -286,17 +323,25 @@ def neighbours_reference(rows, k: int, zero_point: int = 0):
 
 
 def tsne_reference(rows, perplexity: float = 30, n_iter: int = 1000, early_exaggeration: float = 12, exaggeration_iter: int = 250, learning_rate=None,
-                   seed: int = 42, kl_every: int = 0, zero_point: int = 0, snapshots=()) -> ProjectionResult:
+                   seed: int = 42, kl_every: int = 0, zero_point: int = 0, snapshots=(), init: str = "random") -> ProjectionResult:
     """The fit of the module docstring in numpy, float64 gradient over dense pairs: for small N."""
+    check_init(init)
     rows, nonzero = _rows_and_nonzero(rows, zero_point)
     n = int(nonzero.size)
     check_project_args(n, perplexity, n_iter, early_exaggeration, exaggeration_iter, learning_rate, kl_every)
     live = np.ascontiguousarray(rows[nonzero])
+    if init == "pca":
+        from birdnet_stm32.evaluation.reduce import pca_reference, transform_reference
+
+        model = _pca_model_for_start(lambda r: pca_reference(live, zero_point, 1.0, r)[0], n)
+        Y0 = initial_map_pca(transform_reference(live, model))
+    else:
+        Y0 = initial_map(n, seed)
     idx, score = neighbours_reference(live, neighbour_count(n, perplexity), zero_point)
     p_cond, beta = conditional_p_reference(score, perplexity)
     csr = symmetrize(idx, p_cond.astype(np.float32), n)
     lr = default_learning_rate(n, early_exaggeration) if learning_rate is None else float(learning_rate)
-    b = _NumpyBackend(csr, initial_map(n, seed))
+    b = _NumpyBackend(csr, Y0)
     kl, history, trajectory = _descend(b, n, n_iter, early_exaggeration, exaggeration_iter, lr, kl_every, snapshots)
     return _finish(rows.shape[0], nonzero, b.Y, beta, kl, history, trajectory, n_iter)
 
@@ -388,12 +433,26 @@ def device_affinities(ctx, rows: np.ndarray, zero_point: int, k: int, perplexity
         return d_idx.cpu().numpy().astype(np.int64), d_p.cpu().numpy(), d_beta.cpu().numpy()
 
 
+def device_pca_scores(index, nonzero, ctx) -> np.ndarray:
+    """The first two unwhitened principal-component scores ``[n, 2]`` of the non-zero rows, fitted and projected on the device."""
+    from birdnet_stm32.evaluation.reduce import fit_pca, transform_index
+
+    model = _pca_model_for_start(lambda r: fit_pca(index, r, ctx=ctx), int(nonzero.size))
+    return transform_index(index, model, ctx=ctx)[nonzero]
+
+
+def device_initial_map_pca(index, nonzero, ctx) -> np.ndarray:
+    return initial_map_pca(device_pca_scores(index, nonzero, ctx))
+
+
 def project_index(index, perplexity: float = 30, n_iter: int = 1000, early_exaggeration: float = 12, exaggeration_iter: int = 250, learning_rate=None,
-                  seed: int = 42, kl_every: int = 0, device: int = 0, ctx=None) -> ProjectionResult:
+                  seed: int = 42, kl_every: int = 0, device: int = 0, ctx=None, init: str = "random", snapshots=()) -> ProjectionResult:
     """The t-SNE map of the rows of an ``EmbeddingIndex`` on the device.  The non-zero rows go to the device in one piece, whatever the
-    index's block budget: an archive that does not fit is refused."""
+    index's block budget: an archive that does not fit is refused.  ``snapshots`` asks for the uncentred maps after those iterations
+    (``ProjectionResult.trajectory``; 0 is the start)."""
     import torch
 
+    check_init(init)
     rows, zp = index.embeddings, index.zero_point
     nonzero = np.flatnonzero(inv_norms_reference(rows, zp) != 0)
     n = int(nonzero.size)
@@ -411,6 +470,6 @@ def project_index(index, perplexity: float = 30, n_iter: int = 1000, early_exagg
     idx, p_cond, beta = device_affinities(ctx, live, zp, k, float(perplexity))
     csr = symmetrize(idx, p_cond, n)
     lr = default_learning_rate(n, early_exaggeration) if learning_rate is None else float(learning_rate)
-    b = _DeviceBackend(ctx, csr, initial_map(n, seed))
-    kl, history, _ = _descend(b, n, n_iter, early_exaggeration, exaggeration_iter, lr, kl_every)
-    return _finish(len(index), nonzero, b.map(), beta, kl, history, {}, n_iter)
+    b = _DeviceBackend(ctx, csr, device_initial_map_pca(index, nonzero, ctx) if init == "pca" else initial_map(n, seed))
+    kl, history, trajectory = _descend(b, n, n_iter, early_exaggeration, exaggeration_iter, lr, kl_every, snapshots)
+    return _finish(len(index), nonzero, b.map(), beta, kl, history, trajectory, n_iter)

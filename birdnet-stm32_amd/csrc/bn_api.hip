@@ -220,6 +220,7 @@ void bn_ctx_destroy(bn_ctx* c) {
     if (c->d_search_work) (void)hipFree(c->d_search_work);
     if (c->d_kmeans_work) (void)hipFree(c->d_kmeans_work);
     if (c->d_tsne_work) (void)hipFree(c->d_tsne_work);
+    if (c->d_pca_work) (void)hipFree(c->d_pca_work);
     if (c->d_boot_work) (void)hipFree(c->d_boot_work);
     if (c->d_mlp_work) (void)hipFree(c->d_mlp_work);
     delete c;
@@ -1070,7 +1071,7 @@ int bn_preload_kernels(bn_ctx* ctx) {
     // copies wait meanwhile).  A caller with idle time before its first batch — the evaluate pipeline while the first files are read — asks here.
     bn::preload_ingest(); bn::preload_stft(); bn::preload_stft_exact(); bn::preload_i8_fused(); bn::preload_i8_strip(); bn::preload_i8_tail2();
     bn::preload_i8_tail(); bn::preload_i8(); bn::preload_i8_pw(); bn::preload_f32(); bn::preload_f32_fused(); bn::preload_f32_strip();
-    bn::preload_f32_pw(); bn::preload_melspec(); bn::preload_sort(); bn::preload_probe(); bn::preload_probe_sweep(); bn::preload_probe_mlp(); bn::preload_activity(); bn::preload_search(); bn::preload_augment(); bn::preload_kmeans(); bn::preload_density(); bn::preload_tsne(); bn::preload_bootstrap(); bn::preload_head_i8();
+    bn::preload_f32_pw(); bn::preload_melspec(); bn::preload_sort(); bn::preload_probe(); bn::preload_probe_sweep(); bn::preload_probe_mlp(); bn::preload_activity(); bn::preload_search(); bn::preload_augment(); bn::preload_kmeans(); bn::preload_density(); bn::preload_tsne(); bn::preload_pca(); bn::preload_bootstrap(); bn::preload_head_i8();
     return BN_OK;
 }
 
@@ -1089,7 +1090,7 @@ const char* bn_kernel_names(void) {
     return "ingest_resample_kernel\ningest_decimate_kernel\ningest_peak_kernel\ningest_chunks_kernel\nchunk_peaknorm_kernel\npool_scores_kernel\nstft512_mag_kernel\nspec_normalize_kernel\nmelspec_finish_kernel\nf32_mel_kernel\nf32_melfin_kernel\nf32_mag_kernel\nf32_rawfe_kernel\nf32_stem_kernel\nf32_dw_kernel\n"
            "f32_pw_kernel\nf32_pw_ws_kernel\nf32_dwpw_kernel\nf32_dwpw_wave_kernel\nf32_strip_kernel\nf32_front_strip_kernel\nf32_front2_kernel\nf32_pwdw_kernel\nf32_dw_stream_kernel\nf32_front_kernel\nf32_gap_kernel\nf32_gap_dense_kernel\nf32_gap_dense_emb_kernel\nf32_dense_kernel\nf32_segate_kernel\nf32_scale_kernel\nf32_attnpool_kernel\n"
            "i8_quant_kernel\ni8_mel_kernel\ni8_stem_kernel\ni8_dw_kernel\ni8_pw_kernel\ni8_dwpw_kernel\ni8_mel_mfma_kernel\ni8_strip_kernel\ni8_strip_mf_kernel\ni8_front_strip_kernel\ni8_front_kernel\ni8_tail_kernel\ni8_tail_emb_kernel\ni8_tail2_kernel\ni8_tail2_emb_kernel\ni8_mid2_kernel\ni8_mean_kernel\ni8_fc_kernel\ni8_scale_kernel\ni8_maxnorm_kernel\ni8_rawfe_kernel\ni8_pwdw_kernel\ni8_dw_stream_kernel\ni8_stem_stream_kernel\ni8_segate_kernel\ni8_pw_wave_kernel\ni8_pw_lds_kernel\ni8_attnpool_kernel\n"
-           "i8_head_kernel\ni8_head_softmax_kernel\nemb_store_kernel\nprobe_fwd_kernel\nprobe_dw_kernel\nprobe_reduce_kernel\nprobe_update_kernel\nprobe_loss_sum_kernel\nprobe_sweep_snapshot_kernel\nste_kernel\nactivity_count_kernel\nsearch_inv_norms_kernel\nsearch_score_kernel\nsearch_merge_kernel\naugment_kernel\nkmeans_assign_kernel\nkmeans_keys_kernel\nkmeans_offsets_kernel\nkmeans_segments_kernel\nkmeans_partial_kernel\nkmeans_fold_kernel\nkmeans_scale_kernel\ndensity_nearest_kernel\ntsne_perplexity_kernel\ntsne_repulsion_kernel\ntsne_fold_kernel\ntsne_z_kernel\ntsne_attraction_kernel\ntsne_update_kernel\nbootstrap_table_kernel\nbootstrap_reject_kernel\nbootstrap_prepare_kernel\nbootstrap_resample_kernel\nhead_i8_kernel";
+           "i8_head_kernel\ni8_head_softmax_kernel\nemb_store_kernel\nprobe_fwd_kernel\nprobe_dw_kernel\nprobe_reduce_kernel\nprobe_update_kernel\nprobe_loss_sum_kernel\nprobe_sweep_snapshot_kernel\nste_kernel\nactivity_count_kernel\nsearch_inv_norms_kernel\nsearch_score_kernel\nsearch_merge_kernel\naugment_kernel\nkmeans_assign_kernel\nkmeans_keys_kernel\nkmeans_offsets_kernel\nkmeans_segments_kernel\nkmeans_partial_kernel\nkmeans_fold_kernel\nkmeans_scale_kernel\ndensity_nearest_kernel\ntsne_perplexity_kernel\ntsne_repulsion_kernel\ntsne_fold_kernel\ntsne_z_kernel\ntsne_attraction_kernel\ntsne_update_kernel\npca_colsum_kernel\npca_colsum_fold_kernel\npca_gram_kernel\npca_gram_fold_kernel\npca_transform_kernel\nbootstrap_table_kernel\nbootstrap_reject_kernel\nbootstrap_prepare_kernel\nbootstrap_resample_kernel\nhead_i8_kernel";
 }
 
 }  // extern "C"
@@ -1297,6 +1298,68 @@ int bn_tsne_update(bn_ctx* ctx, float* d_y, const float* d_grad, float* d_update
     if (!d_y || !d_grad || !d_update || !d_gains) return fail(BN_ERR_ARG, "null device pointer");
     if ((uintptr_t)d_y % 4 || (uintptr_t)d_grad % 4 || (uintptr_t)d_update % 4 || (uintptr_t)d_gains % 4) return fail(BN_ERR_ARG, "float32 arrays must be 4-byte aligned");
     bn::launch_tsne_update(d_y, d_grad, d_update, d_gains, (long)n, lr, momentum, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return BN_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------------ principal components (bn_pca.hip)
+extern "C" {
+
+int bn_pca_colsum(bn_ctx* ctx, const void* d_rows, int dtype, int64_t n, int D, int zero_point, double* d_sum, void* stream) {
+    if (int rc = check_device(ctx)) return rc;
+    if (int rc = row_matrix_check(dtype, n, D, BN_PCA_MAX_D, zero_point)) return rc;
+    if (!d_sum || (n > 0 && !d_rows)) return fail(BN_ERR_ARG, "null device pointer");
+    if (dtype == BN_DTYPE_F32 && (uintptr_t)d_rows % 4) return fail(BN_ERR_ARG, "float32 rows must be 4-byte aligned");
+    if ((uintptr_t)d_sum % 8) return fail(BN_ERR_ARG, "d_sum must be 8-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(d_sum, 0, (size_t)D * sizeof(double), s));
+        return BN_OK;
+    }
+    const size_t need = bn::pca_colsum_workspace((long)n, D);
+    if (int rc = grow_device_buffer(&ctx->d_pca_work, &ctx->pca_work_bytes, need, need, s, BN_ERR_NOMEM, "PCA")) return rc;
+    bn::launch_pca_colsum(d_rows, dtype == BN_DTYPE_I8, (long)n, D, zero_point, d_sum, ctx->d_pca_work, s);
+    HIP_TRY(hipGetLastError());
+    return BN_OK;
+}
+
+int bn_pca_gram(bn_ctx* ctx, const void* d_rows, int dtype, int64_t n, int D, int zero_point, const float* d_mean, double* d_gram, void* stream) {
+    if (int rc = check_device(ctx)) return rc;
+    if (int rc = row_matrix_check(dtype, n, D, BN_PCA_MAX_D, zero_point)) return rc;
+    if (!d_gram || (n > 0 && !d_rows)) return fail(BN_ERR_ARG, "null device pointer");
+    if (dtype == BN_DTYPE_I8 && d_mean) return fail(BN_ERR_ARG, "int8 rows take no mean: the result is the exact integer matrix");
+    if (dtype == BN_DTYPE_F32 && (uintptr_t)d_rows % 4) return fail(BN_ERR_ARG, "float32 rows must be 4-byte aligned");
+    if ((uintptr_t)d_mean % 4 || (uintptr_t)d_gram % 8) return fail(BN_ERR_ARG, "d_mean must be 4-byte aligned, d_gram 8-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(d_gram, 0, (size_t)D * D * sizeof(double), s));
+        return BN_OK;
+    }
+    const size_t need = bn::pca_gram_workspace((long)n, D);
+    if (int rc = grow_device_buffer(&ctx->d_pca_work, &ctx->pca_work_bytes, need, need, s, BN_ERR_NOMEM, "PCA")) return rc;
+    bn::launch_pca_gram(d_rows, dtype == BN_DTYPE_I8, (long)n, D, zero_point, d_mean, d_gram, ctx->d_pca_work, s);
+    HIP_TRY(hipGetLastError());
+    return BN_OK;
+}
+
+int bn_pca_transform(bn_ctx* ctx, const void* d_rows, int dtype, int64_t n, int D, int zero_point, const float* d_mean, const float* d_W, int r,
+                     float* d_out, void* stream) {
+    if (int rc = check_device(ctx)) return rc;
+    if (int rc = row_matrix_check(dtype, n, D, BN_PCA_MAX_D, zero_point)) return rc;
+    if (r < 1 || r > D) return fail(BN_ERR_ARG, "r=%d outside 1..D=%d", r, D);
+    if (!d_W || (n > 0 && (!d_rows || !d_out))) return fail(BN_ERR_ARG, "null device pointer");
+    if (dtype == BN_DTYPE_F32 && (uintptr_t)d_rows % 4) return fail(BN_ERR_ARG, "float32 rows must be 4-byte aligned");
+    if ((uintptr_t)d_mean % 4 || (uintptr_t)d_W % 4 || (uintptr_t)d_out % 4) return fail(BN_ERR_ARG, "float32 arrays must be 4-byte aligned");
+    if (n == 0) return BN_OK;
+    const bool i8 = dtype == BN_DTYPE_I8;
+    bn::PcaTransformGeom g{};
+    if (!bn::pca_transform_geometry((long)n, D, r, &g)) return fail(BN_ERR_ARG, "D=%d: no tile of W fits the LDS", D);
+    bn::PcaTransformArgs a{};
+    a.rows = d_rows; a.mean = d_mean; a.W = d_W; a.out = d_out;
+    a.n = (int)n; a.D = D; a.r = r; a.zp = i8 ? zero_point : 0; a.steps_per_wg = g.steps_per_wg;
+    if (!bn::launch_pca_transform(a, g, i8, (hipStream_t)stream)) return fail(BN_ERR_DEVICE, "the transform kernel's LDS request was refused");
     HIP_TRY(hipGetLastError());
     return BN_OK;
 }

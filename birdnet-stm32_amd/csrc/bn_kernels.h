@@ -427,7 +427,7 @@ void launch_i8_dwpw(const DwPw8Args& a, hipStream_t s);
 // One per source file with kernels: load that file's device code object now (bn_preload_kernels)
 void preload_f32(); void preload_f32_fused(); void preload_f32_pw(); void preload_f32_strip(); void preload_i8(); void preload_i8_fused();
 void preload_i8_pw(); void preload_i8_strip(); void preload_i8_tail(); void preload_i8_tail2(); void preload_ingest(); void preload_melspec();
-void preload_stft(); void preload_stft_exact(); void preload_sort(); void preload_probe(); void preload_probe_sweep(); void preload_activity(); void preload_search(); void preload_augment(); void preload_kmeans(); void preload_density(); void preload_tsne(); void preload_bootstrap(); void preload_head_i8();
+void preload_stft(); void preload_stft_exact(); void preload_sort(); void preload_probe(); void preload_probe_sweep(); void preload_activity(); void preload_search(); void preload_augment(); void preload_kmeans(); void preload_density(); void preload_tsne(); void preload_pca(); void preload_bootstrap(); void preload_head_i8();
 
 // bn_probe.hip: a classifier head on embeddings (bn_head_forward) and its training step (bn_probe_*)
 struct ProbeFwdArgs {
@@ -654,6 +654,41 @@ size_t tsne_gradient_workspace(long n);
 void launch_tsne_gradient(const float* y, long n, const long long* rowptr, const int* col, const float* val, float exaggeration, float* grad, double* z,
                           double* kl_rows, void* d_work, hipStream_t s);
 void launch_tsne_update(float* y, const float* grad, float* update, float* gains, long n, float lr, float momentum, hipStream_t s);
+
+// bn_pca.hip: column sums, scatter matrix and projection of embedding rows (bn_pca_*)
+struct PcaColsumGeom {
+    int dc;                  // columns a workgroup's lanes cover at a time (a power of two)
+    int nwg;                 // row ranges
+    long rows_per_wg;
+};
+struct PcaGramGeom {
+    int pairs;               // first grid axis: pairs of macro tiles of the upper triangle
+    int ranges;              // second grid axis: row ranges of whole runs
+    long rows_per_range;
+};
+struct PcaTransformArgs {
+    const void* rows;        // [n, D] float32 or int8 rows
+    const float* mean;       // [D] or null
+    const float* W;          // [r, D]
+    float* out;              // [n, r]
+    int n, D, r, zp;
+    long steps_per_wg;       // steps of BN_PCA_STEP_ROWS rows a workgroup streams
+};
+struct PcaTransformGeom {
+    int nt;                  // subtiles of 16 rows of W per LDS tile
+    int tiles;               // LDS tiles the r rows of W take
+    int nwg;                 // workgroups along the rows
+    long steps_per_wg;
+    size_t lds;
+};
+void pca_colsum_geometry(long n, int D, PcaColsumGeom* g);   // from the shapes only
+void pca_gram_geometry(long n, int D, PcaGramGeom* g);
+bool pca_transform_geometry(long n, int D, int r, PcaTransformGeom* g);   // false: no tile fits the LDS
+size_t pca_colsum_workspace(long n, int D);
+size_t pca_gram_workspace(long n, int D);
+void launch_pca_colsum(const void* rows, bool i8, long n, int D, int zp, double* sum, void* d_work, hipStream_t s);
+void launch_pca_gram(const void* rows, bool i8, long n, int D, int zp, const float* mean, double* gram, void* d_work, hipStream_t s);
+bool launch_pca_transform(const PcaTransformArgs& a, const PcaTransformGeom& g, bool i8, hipStream_t s);   // false: the runtime refused the LDS request
 
 // bn_bootstrap.hip: numpy's bounded draws reproduced on the device and the average precision of every resample (bn_bootstrap_*);
 // gen = (state.hi, state.lo, inc.hi, inc.lo) of the PCG64

@@ -71,6 +71,8 @@ struct bn_ctx {
     size_t kmeans_work_bytes = 0;
     void* d_tsne_work = nullptr;     // bn_tsne_gradient: the column ranges' partial sums, the folded repulsion and row sums; grown on demand
     size_t tsne_work_bytes = 0;
+    void* d_pca_work = nullptr;      // bn_pca_colsum / bn_pca_gram: the row ranges' float64 partial sums; grown on demand
+    size_t pca_work_bytes = 0;
     void* d_boot_work = nullptr;     // bn_bootstrap_*: jump-ahead table, rejection counter and list, prepared class orders; grown on demand
     size_t boot_work_bytes = 0;
     void* d_mlp_work = nullptr;      // bn_head_mlp_forward: the hidden activations of one step of rows; grown on demand

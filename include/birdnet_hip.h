@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define BN_ABI_VERSION 2
+#define BN_ABI_VERSION 3
 
 #if defined(__GNUC__)
 #define BN_API __attribute__((visibility("default")))
@@ -717,6 +717,52 @@ BN_API int bn_tsne_gradient(bn_ctx* ctx, const float* d_y, int64_t n, const int6
  * Refused: n < 1 or n >= 2^30, lr or momentum not finite, a NULL pointer, an array not 4-byte aligned. */
 BN_API int bn_tsne_update(bn_ctx* ctx, float* d_y, const float* d_grad, float* d_update, float* d_gains, int64_t n, float lr, float momentum,
                    void* stream);
+
+/* ---- Principal components: column sums, scatter matrix and projection of embedding rows (csrc/bn_pca.hip; no reference counterpart) ----
+ * (birdnet_stm32/evaluation/reduce.py is the specification; the eigen-decomposition stays on the host.)  Rows have bn_search's meaning: an
+ * int8 row is byte - zero_point.  With c_i = fl32(x_i - mean) (x_i itself where d_mean is NULL; an int8 x is made float32 first, which is exact):
+ *   bn_pca_colsum      d_sum[d]     = sum_i x_id                float64, rows in a fixed order; the int8 result is the exact integer
+ *   bn_pca_gram        d_gram[a][b] = sum_i c_ia c_ib           float32 products of the matrix cores accumulate in float32 for at most
+ *                                                               BN_PCA_RUN_ROWS rows, the runs' sums are added in float64 in ascending order.
+ *                                                               Per entry |error| <= (BN_PCA_RUN_ROWS + 1) 2^-24 sum_i |c_ia c_ib|.  int8 needs
+ *                                                               d_mean == NULL and gives the exact integer sum_i x_ia x_ib (a run stays
+ *                                                               below 2^24).  Only the upper triangle is multiplied: d_gram == d_gram^T bit
+ *                                                               for bit.
+ *   bn_pca_transform   d_out[i][k]  = sum_d W_kd c_id           one float32 fused chain of the matrix cores over d ascending (zeros beyond D):
+ *                                                               |error| <= (D + 2) 2^-24 sum_d |W_kd c_id|
+ * 1 <= D <= BN_PCA_MAX_D, 1 <= r <= D, 0 <= n < 2^31.  float32 rows need 4-byte alignment (16 with D % 4 == 0 takes the wide loads; int8: 16
+ * with D % 16 == 0), d_sum and d_gram 8-byte alignment.  A refused call returns BN_ERR_ARG and writes nothing; n = 0 writes zeros (nothing
+ * for the transform).  No floating-point atomics: the same inputs give the same bits on every run.  Nothing synchronises with the host
+ * inside a call unless the context's workspace has to grow. */
+#define BN_PCA_MAX_D 2048
+/* How the work is dealt — from (n, D, dtype[, r]) alone.
+ * Column sums: lanes across min(BN_PCA_COLSUM_COLS, D rounded up to a power of two) columns at a time, the other lanes of the 256 take
+ * every G-th row; ceil(n / BN_PCA_COLSUM_MIN_ROWS) row ranges, at most BN_PCA_COLSUM_MAX_WGS.
+ * Scatter matrix: features in macro tiles of BN_PCA_MACRO; the first grid axis holds the M (M + 1) / 2 pairs of the upper triangle.  Rows in
+ * runs of BN_PCA_RUN_ROWS, staged through LDS BN_PCA_STAGE_ROWS at a time; the second grid axis holds
+ * min(ceil(BN_PCA_GRAM_TARGET_WGS / pairs), BN_PCA_GRAM_MAX_RANGES, runs) ranges of whole runs, evened out.
+ * Transform: a tile of 16, 32, 64 or BN_PCA_MAX_TILE rows of W in LDS, the smallest that holds r and the largest that fits
+ * BN_PCA_LDS_BYTES with the mean; rows in steps of BN_PCA_STEP_ROWS, at least BN_PCA_MIN_WG_STEPS per workgroup, at most BN_PCA_MAX_WGS. */
+#define BN_PCA_RUN_ROWS 256
+#define BN_PCA_STAGE_ROWS 64
+#define BN_PCA_MACRO 64
+#define BN_PCA_GRAM_TARGET_WGS 1024
+#define BN_PCA_GRAM_MAX_RANGES 256
+#define BN_PCA_COLSUM_COLS 256
+#define BN_PCA_COLSUM_MIN_ROWS 256
+#define BN_PCA_COLSUM_MAX_WGS 1024
+#define BN_PCA_LDS_BYTES (160 * 1024)
+#define BN_PCA_MAX_TILE 128
+#define BN_PCA_STEP_ROWS 64
+#define BN_PCA_MIN_WG_STEPS 8
+#define BN_PCA_MAX_WGS 1024
+BN_API int bn_pca_colsum(bn_ctx* ctx, const void* d_rows, int dtype, int64_t n, int D, int zero_point, double* d_sum /* [D] */, void* stream);
+/* d_mean [D] float32 or NULL (required NULL for BN_DTYPE_I8); d_gram [D, D] float64. */
+BN_API int bn_pca_gram(bn_ctx* ctx, const void* d_rows, int dtype, int64_t n, int D, int zero_point, const float* d_mean, double* d_gram,
+                       void* stream);
+/* d_mean [D] float32 or NULL, d_W [r, D] float32, d_out [n, r] float32; d_out must not overlap the inputs. */
+BN_API int bn_pca_transform(bn_ctx* ctx, const void* d_rows, int dtype, int64_t n, int D, int zero_point, const float* d_mean, const float* d_W,
+                            int r, float* d_out, void* stream);
 
 /* ---- Bootstrap of the per-class average precision (csrc/bn_bootstrap.hip) -----------------------------------------------------------
  * (reference: birdnet_stm32/evaluation/metrics.py:239-318 `bootstrap_ap_ci`: one np.random.default_rng(seed) consumed class by class,
