@@ -115,14 +115,20 @@ struct StftTables {
 // Exactness pass of the INT8 audio path (bn_stft_exact.hip explains the five kernels).
 // Record of one (chunk, 16-frame tile) of stft512_mag_kernel<., GUARD> for stft_minmax_exact_kernel, in ints:
 //   [0] L bits  [1] U bits  [2] n_max  [3] n_min   (lower end of the tile's largest element, upper end of its smallest, candidate threads counted)
-//   [kRecIds ..)   kGuardCand thread ids of the maximum, then kGuardCand of the minimum
-//   [kRecExtra ..) lower end of the tile's smallest element (bits), the thread that gave U, 2 unused
-//   [kRecVals ..)  per recorded thread the upper (maximum) / lower (minimum) end of what its extreme element can be
+//   [kRecExtra ..) lower end of the tile's smallest element (bits), the thread that gave U
+//   [kRecEnt ..)   candidate threads as (thread id, upper (maximum) / lower (minimum) end of what its extreme element can be), the s-th of
+//                  the maximum at rec_max_entry(s), of the minimum at rec_min_entry(s): they alternate, so that what is used comes first —
+//                  header, extras, three threads of the maximum and two of the minimum are the record's first 64-byte line, which is all
+//                  that an ordinary tile writes and stft_minmax_exact_kernel reads of it.  Only min(n, kGuardCand) entries of each kind are
+//                  written; the rest of the record holds whatever it held.
 // kGuardCand = 62 (round 5; 30 before): a STATIONARY tone has every frame's peak within the bound of every other's — 16 frames x 2-4 threads of a
 // tile are candidates of the maximum, and an overflowing record gave such chunks to the float64 STFT as a whole.
 constexpr int kGuardCand = 62;
-constexpr int kRecIds = 4, kRecExtra = kRecIds + 2 * kGuardCand, kRecVals = kRecExtra + 4;
-constexpr int kGuardRec = kRecVals + 2 * kGuardCand;   // 256
+constexpr int kRecExtra = 4, kRecEnt = 6;
+constexpr int rec_max_entry(int s) { return kRecEnt + 4 * s; }
+constexpr int rec_min_entry(int s) { return kRecEnt + 4 * s + 2; }
+constexpr int kGuardRec = 256;   // pitch between records, in ints
+static_assert(rec_min_entry(kGuardCand - 1) + 2 <= kGuardRec && kRecEnt % 2 == 0, "a record holds kGuardCand entries of each kind, each 8-byte aligned");
 constexpr int kGuardBudget = 48;    // candidates of the MINIMUM stft_minmax_exact_kernel settles one by one (half of it) before it encloses the minimum in an interval
 constexpr int kGuardMaxBudget = 1024;   // float64 re-evaluations it spends on a chunk's MAXIMUM before it gives the chunk up (a wave per chunk: ~1.3 us per four)
 struct StftGuard {

@@ -161,10 +161,14 @@ __device__ __forceinline__ float row16_min(float v) { BN_ROW16(fminf, v) return 
 // that can hold the chunk's largest / smallest value: with Lt = max (S' - eps) and Ut = min (S' + eps) over the tile, those whose
 // largest element reaches Lt within the bound, resp. whose smallest comes down to Ut.  The chunk's min / max themselves are left
 // to stft_minmax_exact_kernel (no atomics here).
-template <bool MEL_OUT, bool GUARD = false>
+//
+// TILED (the tile-major layout [W/16][257][16] private to bn_infer_audio, W a multiple of 16): the workgroup's tile is one contiguous,
+// 16-byte aligned block of 1028 float4, and the magnitude tile in LDS is laid out for reading it that way (mag_at below).
+template <bool MEL_OUT, bool GUARD = false, bool TILED = false>
 __global__ __launch_bounds__(256) void stft512_mag_kernel(StftTables tb, const float* __restrict__ audio, int T, int hop,
                                                           int W, float* __restrict__ spec, float* minmax, MelOut mel,
                                                           int tiles_per_wg, StftGuard guard) {
+    static_assert(!(MEL_OUT && (GUARD || TILED)), "the mel mixer writes its own layout and takes no guard");
     // The magnitude tile [257][kFT + 1] (17.5 KB) re-uses the exchange buffer (34.8 KB): every lane takes its sixteen conjugate
     // partners into registers, one workgroup barrier later the buffer is free.  35 KB instead of 52 KB of LDS = four
     // workgroups per CU instead of three.
@@ -174,10 +178,17 @@ __global__ __launch_bounds__(256) void stft512_mag_kernel(StftTables tb, const f
     __shared__ float xch[kFT][kFS];
     float (*mag)[kFT + 1] = reinterpret_cast<float (*)[kFT + 1]>(&xch[0][0]);
     static_assert(sizeof(float) * 257 * (kFT + 1) <= sizeof(float) * kFT * kFS, "magnitude tile must fit the exchange buffer");
+    // TILED: rows of 16 floats (pitch 16), the four float4 of row k stored at positions p ^ ((k >> 1) & 3).  A thread's 16-byte read of
+    // (row, four frames) is then one ds_read_b128, and the rows a 16-lane group of that instruction reads tile the 64 banks (linear
+    // addresses: no conflict).  The writes mag[j + 16 k2][f] of a 32-lane half (16 j x 2 frames) land two per bank — (j & 1) picks
+    // the half of the 32 banks, (j >> 1) & 3 the float4 in it — and a 2-way conflict costs a ds_write_b32 nothing.  Unswizzled, pitch 16
+    // puts sixteen of them on one bank; pitch 17 (the other layouts) cannot be read 16 bytes at a time.
+    float* const magt = &xch[0][0];
+    static_assert(257 * kFT <= kFT * kFS, "magnitude tile must fit the exchange buffer");
+    auto mag_at = [&](int k, int ff) -> float& { return TILED ? magt[k * kFT + (ff ^ ((k & 6) << 1))] : mag[k][ff]; };
     __shared__ float red_min[4], red_max[4];
     __shared__ float g_red[3][kFT], g_eps[kFT];  // GUARD: per-frame (lower end of the largest, upper end of the smallest, lower end of the smallest element), eps (-1: frame beyond W)
-    __shared__ int g_cnt[2], g_rec[2 * kGuardCand], g_arg;
-    __shared__ float g_recv[2 * kGuardCand], g_LU[3];
+    __shared__ int g_cnt[2], g_arg, g_done;      // GUARD: candidate threads counted (maximum, minimum), the thread that gave U, waves that have listed theirs
     // mel mixer tables (MEL_OUT): up to 1024 band-sparse values and 3 x 128 band entries (the launcher refuses more mel bins)
     constexpr int kMelW = MEL_OUT ? 1024 : 1, kMelT = MEL_OUT ? 384 : 1;
     __shared__ float mel_w[kMelW];
@@ -208,16 +219,29 @@ __global__ __launch_bounds__(256) void stft512_mag_kernel(StftTables tb, const f
 
     // Raw buffer loads through a descriptor that covers exactly this chunk: samples before the chunk (negative offset = huge
     // unsigned) or after it fail the hardware range check and read as 0, which is librosa's centre padding — no address
-    // clamping, no selects, all 32 loads of a tile in flight at once.
+    // clamping, no selects, all loads of a tile in flight at once.  A lane's (x, y) pairs are adjacent samples: one 8-byte load each
+    // (sixteen loads where the compiler had merged eight pairs and left sixteen single loads).  The range check is made per dword, and a pair that straddles the chunk's
+    // LAST sample keeps its in-range half; one that straddles samples -1 / 0 (byte offset -4) does not — measured: the second dword's
+    // offset does not wrap to 0 and sample 0 reads as 0 (hop 33, frames 1, 3, 5, 7: tests/test_gpu_stft_stores.py).  Only a lane that
+    // starts on an odd sample before the chunk can hold such a pair; a wave with one takes single loads, whose offsets wrap in the
+    // vector ALU (none in the flagship geometry: hop 281, frame 0 starts on an even sample and frame 1 inside the chunk).
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x), 0, T * 4, 0x00020000);
     (void)tiles_per_wg;  // one tile per workgroup (see stft_tiles_per_wg)
     auto fetch = [&](int tile, v2f (&dst)[16]) {
         const int off0 = (int)(((long)(tile * kFT + f) * hop - 256 + 2 * j) * 4);
+        // (a pair at byte offset -4 has 128 n1 = -4 - off0 <= 1020: n1 < 8)
+        if (__ballot(off0 < 0 && (off0 & 4)) != 0) {
 #pragma unroll
-        for (int n1 = 0; n1 < 16; ++n1) {
-            dst[n1].x = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, off0 + 128 * n1, 0, 0));
-            dst[n1].y = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, off0 + 128 * n1 + 4, 0, 0));
+            for (int n1 = 0; n1 < 8; ++n1) {
+                dst[n1].x = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, off0 + 128 * n1, 0, 0));
+                dst[n1].y = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, off0 + 128 * n1 + 4, 0, 0));
+            }
+        } else {
+#pragma unroll
+            for (int n1 = 0; n1 < 8; ++n1) dst[n1] = __builtin_bit_cast(v2f, __builtin_amdgcn_raw_buffer_load_b64(rsrc, off0 + 128 * n1, 0, 0));
         }
+#pragma unroll
+        for (int n1 = 8; n1 < 16; ++n1) dst[n1] = __builtin_bit_cast(v2f, __builtin_amdgcn_raw_buffer_load_b64(rsrc, off0 + 128 * n1, 0, 0));
     };
     float lmin = __uint_as_float(0x7f800000u), lmax = 0.0f;
 
@@ -307,12 +331,12 @@ __global__ __launch_bounds__(256) void stft512_mag_kernel(StftTables tb, const f
             const v2f xr = cmul_add(o, tk, e);  // o.y (-tk.y, tk.x) + (o.x tk + e)
             const v2f sq = xr * xr;
             const float m = __builtin_amdgcn_sqrtf(sq.x + sq.y);
-            mag[k][f] = m;
+            mag_at(k, f) = m;
             tmin = fminf(tmin, m);
             tmax = fmaxf(tmax, m);
             if (k == 0) {  // lane 0, k2 = 0: the Nyquist bin is Re Z[0] - Im Z[0]
                 const float ny = fabsf(e.x - o.y);
-                mag[256][f] = ny;
+                mag_at(256, f) = ny;
                 tmin = fminf(tmin, ny);
                 tmax = fmaxf(tmax, ny);
             }
@@ -334,13 +358,17 @@ __global__ __launch_bounds__(256) void stft512_mag_kernel(StftTables tb, const f
             }
             if (threadIdx.x < 2) g_cnt[threadIdx.x] = 0;
             if (threadIdx.x == 2) g_arg = -1;
+            if (threadIdx.x == 3) g_done = 0;
         }
         __syncthreads();
+        // GUARD: the tile's record (bn_kernels.h).  Only what stft_minmax_exact_kernel reads is written: every candidate thread its own entry,
+        // the last wave to get here the header.
+        int* const rec = GUARD ? guard.rec + ((size_t)b * gridDim.x + blockIdx.x) * kGuardRec : nullptr;
+        float Lt = 0.0f, Ut = 0.0f, Lm = 0.0f;
         if constexpr (GUARD) {
-            const float Lt = fmaxf(row16_max(g_red[0][threadIdx.x & 15]), 0.0f), Ut = row16_min(g_red[1][threadIdx.x & 15]);
-            g_LU[0] = Lt;  // (every thread writes the same values: read back for the record below)
-            g_LU[1] = Ut;
-            g_LU[2] = fmaxf(row16_min(g_red[2][threadIdx.x & 15]), 0.0f);  // no element of the tile lies below this (stft_minmax_exact_kernel: interval minimum)
+            Lt = fmaxf(row16_max(g_red[0][threadIdx.x & 15]), 0.0f);
+            Ut = row16_min(g_red[1][threadIdx.x & 15]);
+            Lm = fmaxf(row16_min(g_red[2][threadIdx.x & 15]), 0.0f);  // no element of the tile lies below this (stft_minmax_exact_kernel: interval minimum)
             // candidates for the chunk's extrema: a THREAD whose largest (smallest) of its 16 bins j + 16 k2 of frame f comes within the
             // bound of the tile's extremum is recorded as (j, f) with the upper (lower) end of what that element can be;
             // stft_minmax_exact_kernel looks at its bins (re-reading the tile here, even only in the waves with a hit, cost 30 us of
@@ -350,20 +378,14 @@ __global__ __launch_bounds__(256) void stft512_mag_kernel(StftTables tb, const f
                 const float top = guard_hi(tmax, e_f), bot = guard_lo(tmin, e_f);
                 if (top >= Lt) {
                     const int sl = atomicAdd(&g_cnt[0], 1);
-                    if (sl < kGuardCand) {
-                        g_rec[sl] = threadIdx.x;
-                        g_recv[sl] = top;
-                    }
+                    if (sl < kGuardCand) *reinterpret_cast<int2*>(rec + rec_max_entry(sl)) = make_int2(threadIdx.x, __float_as_int(top));
                 }
                 // the thread whose smallest element gives the tile's upper end Ut is recorded on its own as well: an overflowing record keeps the first
                 // kGuardCand candidates it meets, and the interval form of the minimum wants THE candidate most likely to be it (any writer will do)
                 if (guard_hi(tmin, e_f) <= Ut) g_arg = threadIdx.x;
                 if (bot <= Ut) {
                     const int sl = atomicAdd(&g_cnt[1], 1);
-                    if (sl < kGuardCand) {
-                        g_rec[kGuardCand + sl] = threadIdx.x;
-                        g_recv[kGuardCand + sl] = bot;
-                    }
+                    if (sl < kGuardCand) *reinterpret_cast<int2*>(rec + rec_min_entry(sl)) = make_int2(threadIdx.x, __float_as_int(bot));
                 }
             }
         }
@@ -371,25 +393,39 @@ __global__ __launch_bounds__(256) void stft512_mag_kernel(StftTables tb, const f
         if (!MEL_OUT) {
             // frequency-major rows, 16 consecutive frames each
             float* out = spec + (size_t)b * 257 * W;
-            if (tiles_per_wg < 0) {
+            if constexpr (TILED) {
                 // tile-major layout [W/16][257][16] (private to bn_infer_audio, read by i8_mel_mfma_kernel<QIN>): the workgroup's
-                // tile is ONE contiguous 16 KB block — 256-byte store instructions instead of four 64-byte pieces 1 KB apart
-                // (0.548 -> 0.466 ms per 4096 chunks, 4.84 TB/s)
-                float* ob = out + (size_t)(t0 / kFT) * 257 * kFT;
-                for (int idx = threadIdx.x; idx < 257 * kFT; idx += 256) ob[idx] = mag[idx / kFT][idx % kFT];
+                // tile is ONE contiguous 16 KB block (0.548 -> 0.466 ms per 4096 chunks against four 64-byte pieces 1 KB apart), stored
+                // 16 bytes per lane: float4 q = threadIdx.x + 256 i holds frames 4 (q & 3) .. + 3 of row q >> 2.  Rows 64 apart share
+                // their swizzle, so one LDS address and one global offset serve all four, 4 KB apart; the Nyquist row's four follow.
+                // Buffer stores through a descriptor of exactly this tile: the lane's byte offset 16 q in one register, the 4 KB steps in the
+                // scalar offset, and nothing can land outside the tile.  Every LDS read is issued before the first store.
+                float* ob = out + (size_t)blockIdx.x * 257 * kFT;
+                const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(ob, 0, 257 * kFT * 4, 0x00020000);
+                const int q = threadIdx.x, k = q >> 2;
+                const float* src = magt + k * kFT + 4 * ((q & 3) ^ ((k >> 1) & 3));
+                f32x4 v[5];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) v[i] = *reinterpret_cast<const f32x4*>(src + i * 64 * kFT);
+                if (q < 4) v[4] = *reinterpret_cast<const f32x4*>(magt + 256 * kFT + 4 * q);   // (row 256: swizzle 0)
+                typedef unsigned u32x4 __attribute__((__vector_size__(4 * sizeof(unsigned))));
+#pragma unroll
+                for (int i = 0; i < 4; ++i) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v[i]), orsrc, 16 * q, 4096 * i, 0);
+                if (q < 4) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v[4]), orsrc, 16 * q, 4096 * 4, 0);
             } else
             for (int idx = threadIdx.x; idx < 257 * kFT; idx += 256) {
                 const int k = idx / kFT, ff = idx % kFT;
                 if (t0 + ff < W) out[(size_t)k * W + t0 + ff] = mag[k][ff];
             }
             if constexpr (GUARD) {
-                __syncthreads();
-                static_assert(kGuardRec <= 256, "one record entry per thread");
-                if (threadIdx.x < kGuardRec) {
-                    const int i = threadIdx.x;
-                    const int v = i < 2 ? __float_as_int(g_LU[i]) : i < kRecIds ? g_cnt[i - 2] : i < kRecExtra ? g_rec[i - kRecIds]
-                                : i == kRecExtra ? __float_as_int(g_LU[2]) : i == kRecExtra + 1 ? g_arg : i < kRecVals ? 0 : __float_as_int(g_recv[i - kRecVals]);
-                    guard.rec[((size_t)b * gridDim.x + blockIdx.x) * kGuardRec + i] = v;
+                // The header needs the final counts.  No workgroup barrier for that: a wave that has listed its candidates adds one to g_done
+                // (release: behind its counts and its g_arg), and the wave that finds the other three there (acquire) reads what they left.
+                wave_sync();
+                int done = 0;
+                if ((threadIdx.x & 63) == 0) done = __hip_atomic_fetch_add(&g_done, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if (__builtin_amdgcn_readfirstlane(done) == 3 && (threadIdx.x & 63) == 0) {
+                    *reinterpret_cast<int4*>(rec) = make_int4(__float_as_int(Lt), __float_as_int(Ut), g_cnt[0], g_cnt[1]);
+                    *reinterpret_cast<int2*>(rec + kRecExtra) = make_int2(__float_as_int(Lm), g_arg);
                 }
                 return;  // min / max of the chunk: stft_minmax_exact_kernel
             }
@@ -464,19 +500,27 @@ void launch_minmax_init(float* minmax, int B, hipStream_t s) {
 }
 
 // One tile per workgroup: a loop that prefetches the next tile's samples needs > 170 VGPRs and drops the kernel to 2 waves per SIMD
-// (measured 0.27 ms against 0.20 ms per 1024 chunks); the kernel's last argument only carries the tile-major flag (-1) now.
+// (measured 0.27 ms against 0.20 ms per 1024 chunks); the kernel's `tiles_per_wg` argument is unused now (-1 beside the TILED instantiations).
 static int stft_tiles_per_wg(int, int) { return 1; }
 
 void launch_stft512(const StftTables& tb, const float* audio, int B, int T, int hop, int W, float* spec, float* minmax,
                     hipStream_t s, bool tile_major, const StftGuard* guard) {
     const int n_tiles = (W + kFT - 1) / kFT;
     const int tpw = stft_tiles_per_wg(B, n_tiles);
-    if (guard)
-        hipLaunchKernelGGL((stft512_mag_kernel<false, true>), dim3(n_tiles, B), dim3(256), 0, s, tb, audio, T, hop, W, spec, minmax, MelOut{},
-                           (tile_major && W % kFT == 0) ? -1 : tpw, *guard);
-    else
-        hipLaunchKernelGGL((stft512_mag_kernel<false>), dim3((n_tiles + tpw - 1) / tpw, B), dim3(256), 0, s, tb, audio, T, hop, W, spec,
-                           minmax, MelOut{}, (tile_major && W % kFT == 0) ? -1 : tpw, StftGuard{});
+    // The tile-major form stores whole float4: every tile is full (W a multiple of 16), and with `spec` 16-byte aligned (the layout is private
+    // to bn_infer_audio, which passes its own allocation) so is every tile's base, 257 * 16 floats past the one before.
+    const bool tiled = tile_major && W % kFT == 0;
+    const dim3 grid((n_tiles + tpw - 1) / tpw, B);
+#define BN_STFT_LAUNCH(G, TL, g) \
+    hipLaunchKernelGGL((stft512_mag_kernel<false, G, TL>), grid, dim3(256), 0, s, tb, audio, T, hop, W, spec, minmax, MelOut{}, TL ? -1 : tpw, g)
+    if (guard) {
+        if (tiled) BN_STFT_LAUNCH(true, true, *guard);
+        else BN_STFT_LAUNCH(true, false, *guard);
+    } else {
+        if (tiled) BN_STFT_LAUNCH(false, true, StftGuard{});
+        else BN_STFT_LAUNCH(false, false, StftGuard{});
+    }
+#undef BN_STFT_LAUNCH
 }
 
 bool launch_stft512_mel(const StftTables& tb, const float* audio, int B, int T, int hop, int W, float* mel_out, int M,

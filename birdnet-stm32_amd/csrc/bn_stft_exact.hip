@@ -296,7 +296,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         U = __int_as_float(h.y);
         n_max = h.z;
         n_min = h.w;
-        Lm = __int_as_float(rec[lane * kGuardRec + kRecExtra]);  // no element of the tile lies below this
+        Lm = __int_as_float(rec[lane * kGuardRec + kRecExtra]);  // no element of the tile lies below this (the same 64-byte line as the header)
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
@@ -329,14 +329,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     for (int s_ = 0; s_ < kGuardCand && !hard; ++s_) {
         // (the record holds, per thread, the upper / lower end of what its extreme element can be: most tiles' entries stop here)
         if (!__ballot(s_ < n_max)) break;
-        const bool p_max = s_ < n_max && __int_as_float(rec[lane * kGuardRec + kRecVals + s_]) >= L;
+        const int2 ent = s_ < n_max ? *reinterpret_cast<const int2*>(rec + lane * kGuardRec + rec_max_entry(s_)) : make_int2(0, 0);   // (thread id, upper end)
+        const bool p_max = s_ < n_max && __int_as_float(ent.y) >= L;
         const unsigned long long m_max = __ballot(p_max);
         const unsigned long long below = (1ull << lane) - 1;
         if (n_thr + __popcll(m_max) > kK2MaxThr) {
             hard = true;
             break;
         }
-        if (p_max) thr[n_thr + __popcll(m_max & below)] = (unsigned short)((lane << 8) | rec[lane * kGuardRec + kRecIds + s_]);
+        if (p_max) thr[n_thr + __popcll(m_max & below)] = (unsigned short)((lane << 8) | ent.x);
         n_thr += __popcll(m_max);
     }
     const int n_thr_max = n_thr;
@@ -349,7 +350,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     }
     for (int s_ = 0; s_ < kGuardCand && !hard; ++s_) {
         if (!__ballot(s_ < n_min)) break;
-        const bool p_min = s_ < n_min && __int_as_float(rec[lane * kGuardRec + kRecVals + kGuardCand + s_]) <= U;
+        const int2 ent = s_ < n_min ? *reinterpret_cast<const int2*>(rec + lane * kGuardRec + rec_min_entry(s_)) : make_int2(0, 0);   // (thread id, lower end)
+        const bool p_min = s_ < n_min && __int_as_float(ent.y) <= U;
         const unsigned long long m_min = __ballot(p_min);
         const unsigned long long below = (1ull << lane) - 1;
         if (n_thr - n_thr_max + __popcll(m_min) > kK2Thr) {
@@ -357,7 +359,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             wide = may_wide;   // (the threads collected so far are candidates enough)
             break;
         }
-        if (p_min) thr[n_thr + __popcll(m_min & below)] = (unsigned short)((lane << 8) | rec[lane * kGuardRec + kRecIds + kGuardCand + s_]);
+        if (p_min) thr[n_thr + __popcll(m_min & below)] = (unsigned short)((lane << 8) | ent.x);
         n_thr += __popcll(m_min);
     }
     wave_sync();
