@@ -38,6 +38,7 @@ EXPORTS = (
     "bn_probe_mlp_set", "bn_head_mlp_forward",
     "bn_short_time_energy", "bn_activity_counts", "bn_search_inv_norms", "bn_search_topk", "bn_augment_inputs",
     "bn_kmeans_assign", "bn_kmeans_accumulate", "bn_kmeans_centroids",
+    "bn_silhouette_means",
     "bn_density_nearest",
     "bn_tsne_perplexity", "bn_tsne_gradient", "bn_tsne_update",
     "bn_pca_colsum", "bn_pca_gram", "bn_pca_transform",
@@ -75,7 +76,8 @@ SEARCH_METRICS = {"cosine": 0, "dot": 1}  # BN_SEARCH_*
 SEARCH_MAX_K, SEARCH_MAX_D = 128, 2048
 AUGMENT_MAX_MASKS = 4  # BN_AUGMENT_MAX_MASKS
 SEARCH_STEP_ROWS, SEARCH_MIN_WG_STEPS, SEARCH_MAX_WGS = 64, 8, 1024  # how bn_search_topk deals rows to workgroups (include/birdnet_hip.h)
-# bn_kmeans_* (include/birdnet_hip.h): limits, and the constants the centroid tiles, the row steps and the update's segments follow from
+# bn_kmeans_* (include/birdnet_hip.h): limits, and the constants the centroid tiles, the row steps and the update's segments follow from;
+# bn_silhouette_means has the same limits and deals its work by the same constants (the cluster sums take the centroids' place in LDS)
 KMEANS_MAX_K, KMEANS_MAX_D = 4096, 2048
 BOOTSTRAP_MAX_N = 32768  # BN_BOOTSTRAP_MAX_N
 KMEANS_LDS_BYTES, KMEANS_MAX_TILE, KMEANS_STEP_ROWS, KMEANS_MIN_WG_STEPS, KMEANS_MAX_WGS, KMEANS_SEGMENT_ROWS = 160 * 1024, 128, 64, 8, 1024, 256
@@ -237,6 +239,8 @@ def load_library(path: str | None = None):
                                      c_void_p, c_void_p]
     lib.bn_kmeans_accumulate.argtypes = [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]
     lib.bn_kmeans_centroids.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]
+    lib.bn_silhouette_means.argtypes = [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                        c_void_p, c_void_p]
     lib.bn_density_nearest.argtypes = [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.bn_tsne_perplexity.argtypes = [c_void_p, c_void_p, c_int64, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p]
     lib.bn_tsne_gradient.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p]

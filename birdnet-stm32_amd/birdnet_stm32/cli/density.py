@@ -10,6 +10,10 @@ The first file has ``cluster``'s columns and lines up with ``cluster``'s and ``p
 membership (1 at a cluster's core, towards 0 at its rim, 0 for noise).  ``end_s`` is ``start_s`` plus ``--chunk_duration`` (the archive
 does not record it; 0 leaves ``end_s = start_s``).  ``--exemplars`` are a cluster's densest members, found on the host, so int8 archives
 have them too; sorted into class folders they feed ``probe``.
+
+``--silhouette`` scores the clusters with the exact cosine silhouette (``evaluation/silhouette.py``), noise and zero rows excluded:
+``<output>`` gets the columns ``silhouette`` and ``nearest_cluster`` (empty and -1 for noise), the summary a ``silhouette`` column behind
+``stability``.  It needs at least 2 clusters and is refused, after the fit, where there are fewer.
 """
 
 from __future__ import annotations
@@ -18,7 +22,7 @@ import argparse
 import csv
 import os
 
-from birdnet_stm32.cli.cluster import CSV_COLUMNS, summary_path, write_clusters_csv
+from birdnet_stm32.cli.cluster import CSV_COLUMNS, SILHOUETTE_COLUMNS, SUMMARY_SILHOUETTE_COLUMN, cluster_mean_cell, summary_path, write_clusters_csv
 
 SUMMARY_COLUMNS = ("cluster", "count", "stability")
 
@@ -32,6 +36,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--min_cluster_size", type=int, default=15, help="Fewest rows a cluster holds (>= 2)")
     p.add_argument("--min_samples", type=int, default=None, help="Rows, the row itself included, whose neighbourhood sets a row's density (1..129; default: --min_cluster_size)")
     p.add_argument("--exemplars", type=int, default=5, help="Densest members per cluster in the summary")
+    p.add_argument("--silhouette", action="store_true", help="Add each clustered row's silhouette and nearest other cluster, and each cluster's mean silhouette")
     p.add_argument("--chunk_duration", type=float, default=0.0, help="Seconds per row, for end_s")
     p.add_argument("--device", type=int, default=0, help="MI355X index")
     return p
@@ -52,15 +57,17 @@ def validate_args(args) -> None:
             raise FileNotFoundError(f"archive not found: {path}")
 
 
-def write_summary_csv(path: str, index, result) -> int:
-    """One line per cluster: its member count, its stability and its exemplars as ``path@start_s``."""
+def write_summary_csv(path: str, index, result, silhouette=None) -> int:
+    """One line per cluster: its member count, its stability, with a ``SilhouetteResult`` its mean silhouette, and its exemplars as
+    ``path@start_s``."""
     E = result.exemplar_idx.shape[1]
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
-        w.writerow(SUMMARY_COLUMNS + tuple(f"exemplar_{e + 1}" for e in range(E)))
+        w.writerow(SUMMARY_COLUMNS + ((SUMMARY_SILHOUETTE_COLUMN,) if silhouette is not None else ()) + tuple(f"exemplar_{e + 1}" for e in range(E)))
         for c in range(result.n_clusters):
             ex = [f"{index.paths[int(index.file_index[i])]}@{float(index.start_s[i]):.3f}" if i >= 0 else "" for i in result.exemplar_idx[c]]
-            w.writerow([c, int((result.labels == c).sum()), f"{float(result.stability[c]):.7g}"] + ex)
+            w.writerow([c, int((result.labels == c).sum()), f"{float(result.stability[c]):.7g}"]
+                       + ([cluster_mean_cell(silhouette, c)] if silhouette is not None else []) + ex)
     return result.n_clusters
 
 
@@ -76,13 +83,20 @@ def main(argv=None):
     try:
         index = EmbeddingIndex.from_npz(*args.database)
         result = density_index(index, args.min_cluster_size, args.min_samples, exemplars=args.exemplars, device=args.device)
+        silhouette = None
+        if args.silhouette:
+            if result.n_clusters < 2:
+                raise ValueError(f"--silhouette needs at least 2 clusters; the fit found {result.n_clusters}")
+            from birdnet_stm32.evaluation.silhouette import silhouette_index
+
+            silhouette = silhouette_index(index, result.labels, result.n_clusters, device=args.device)
     except ValueError as exc:
         raise SystemExit(f"error: {exc}") from None
-    write_clusters_csv(args.output, index, result, args.chunk_duration)
-    write_summary_csv(summary_path(args.output), index, result)
+    write_clusters_csv(args.output, index, result, args.chunk_duration, silhouette)
+    write_summary_csv(summary_path(args.output), index, result, silhouette)
     noise = int((result.labels < 0).sum())
     print(f"Clustered {len(index)} rows x {index.dim} ({index.dtype}) by density: {result.n_clusters} clusters, {noise} rows of noise, "
-          f"spanning tree in {result.rounds} rounds -> {args.output}")
+          f"spanning tree in {result.rounds} rounds" + (f", mean silhouette {silhouette.mean:.4f}" if silhouette is not None else "") + f" -> {args.output}")
     index.close()
     return result
 

@@ -1071,7 +1071,7 @@ int bn_preload_kernels(bn_ctx* ctx) {
     // copies wait meanwhile).  A caller with idle time before its first batch — the evaluate pipeline while the first files are read — asks here.
     bn::preload_ingest(); bn::preload_stft(); bn::preload_stft_exact(); bn::preload_i8_fused(); bn::preload_i8_strip(); bn::preload_i8_tail2();
     bn::preload_i8_tail(); bn::preload_i8(); bn::preload_i8_pw(); bn::preload_f32(); bn::preload_f32_fused(); bn::preload_f32_strip();
-    bn::preload_f32_pw(); bn::preload_melspec(); bn::preload_sort(); bn::preload_probe(); bn::preload_probe_sweep(); bn::preload_probe_mlp(); bn::preload_activity(); bn::preload_search(); bn::preload_augment(); bn::preload_kmeans(); bn::preload_density(); bn::preload_tsne(); bn::preload_pca(); bn::preload_bootstrap(); bn::preload_head_i8();
+    bn::preload_f32_pw(); bn::preload_melspec(); bn::preload_sort(); bn::preload_probe(); bn::preload_probe_sweep(); bn::preload_probe_mlp(); bn::preload_activity(); bn::preload_search(); bn::preload_augment(); bn::preload_kmeans(); bn::preload_silhouette(); bn::preload_density(); bn::preload_tsne(); bn::preload_pca(); bn::preload_bootstrap(); bn::preload_head_i8();
     return BN_OK;
 }
 
@@ -1090,7 +1090,7 @@ const char* bn_kernel_names(void) {
     return "ingest_resample_kernel\ningest_decimate_kernel\ningest_peak_kernel\ningest_chunks_kernel\nchunk_peaknorm_kernel\npool_scores_kernel\nstft512_mag_kernel\nspec_normalize_kernel\nmelspec_finish_kernel\nf32_mel_kernel\nf32_melfin_kernel\nf32_mag_kernel\nf32_rawfe_kernel\nf32_stem_kernel\nf32_dw_kernel\n"
            "f32_pw_kernel\nf32_pw_ws_kernel\nf32_dwpw_kernel\nf32_dwpw_wave_kernel\nf32_strip_kernel\nf32_front_strip_kernel\nf32_front2_kernel\nf32_pwdw_kernel\nf32_dw_stream_kernel\nf32_front_kernel\nf32_gap_kernel\nf32_gap_dense_kernel\nf32_gap_dense_emb_kernel\nf32_dense_kernel\nf32_segate_kernel\nf32_scale_kernel\nf32_attnpool_kernel\n"
            "i8_quant_kernel\ni8_mel_kernel\ni8_stem_kernel\ni8_dw_kernel\ni8_pw_kernel\ni8_dwpw_kernel\ni8_mel_mfma_kernel\ni8_strip_kernel\ni8_strip_mf_kernel\ni8_front_strip_kernel\ni8_front_kernel\ni8_tail_kernel\ni8_tail_emb_kernel\ni8_tail2_kernel\ni8_tail2_emb_kernel\ni8_mid2_kernel\ni8_mean_kernel\ni8_fc_kernel\ni8_scale_kernel\ni8_maxnorm_kernel\ni8_rawfe_kernel\ni8_pwdw_kernel\ni8_dw_stream_kernel\ni8_stem_stream_kernel\ni8_segate_kernel\ni8_pw_wave_kernel\ni8_pw_lds_kernel\ni8_attnpool_kernel\n"
-           "i8_head_kernel\ni8_head_softmax_kernel\nemb_store_kernel\nprobe_fwd_kernel\nprobe_dw_kernel\nprobe_reduce_kernel\nprobe_update_kernel\nprobe_loss_sum_kernel\nprobe_sweep_snapshot_kernel\nste_kernel\nactivity_count_kernel\nsearch_inv_norms_kernel\nsearch_score_kernel\nsearch_merge_kernel\naugment_kernel\nkmeans_assign_kernel\nkmeans_keys_kernel\nkmeans_offsets_kernel\nkmeans_segments_kernel\nkmeans_partial_kernel\nkmeans_fold_kernel\nkmeans_scale_kernel\ndensity_nearest_kernel\ntsne_perplexity_kernel\ntsne_repulsion_kernel\ntsne_fold_kernel\ntsne_z_kernel\ntsne_attraction_kernel\ntsne_update_kernel\npca_colsum_kernel\npca_colsum_fold_kernel\npca_gram_kernel\npca_gram_fold_kernel\npca_transform_kernel\nbootstrap_table_kernel\nbootstrap_reject_kernel\nbootstrap_prepare_kernel\nbootstrap_resample_kernel\nhead_i8_kernel";
+           "i8_head_kernel\ni8_head_softmax_kernel\nemb_store_kernel\nprobe_fwd_kernel\nprobe_dw_kernel\nprobe_reduce_kernel\nprobe_update_kernel\nprobe_loss_sum_kernel\nprobe_sweep_snapshot_kernel\nste_kernel\nactivity_count_kernel\nsearch_inv_norms_kernel\nsearch_score_kernel\nsearch_merge_kernel\naugment_kernel\nkmeans_assign_kernel\nkmeans_keys_kernel\nkmeans_offsets_kernel\nkmeans_segments_kernel\nkmeans_partial_kernel\nkmeans_fold_kernel\nkmeans_scale_kernel\nsilhouette_means_kernel\ndensity_nearest_kernel\ntsne_perplexity_kernel\ntsne_repulsion_kernel\ntsne_fold_kernel\ntsne_z_kernel\ntsne_attraction_kernel\ntsne_update_kernel\npca_colsum_kernel\npca_colsum_fold_kernel\npca_gram_kernel\npca_gram_fold_kernel\npca_transform_kernel\nbootstrap_table_kernel\nbootstrap_reject_kernel\nbootstrap_prepare_kernel\nbootstrap_resample_kernel\nhead_i8_kernel";
 }
 
 }  // extern "C"
@@ -1253,6 +1253,32 @@ int bn_kmeans_centroids(bn_ctx* ctx, const float* d_sums, const int64_t* d_count
     if ((uintptr_t)d_sums % 4 || (uintptr_t)d_centroids % 4 || (uintptr_t)d_cent_inv % 4 || (uintptr_t)d_counts % 8)
         return fail(BN_ERR_ARG, "float32 arrays must be 4-byte aligned, d_counts 8-byte aligned");
     bn::launch_kmeans_centroids(d_sums, (const long long*)d_counts, K, D, d_centroids, d_cent_inv, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return BN_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------------- silhouette (bn_silhouette.hip)
+extern "C" {
+
+int bn_silhouette_means(bn_ctx* ctx, const void* d_rows, int dtype, int64_t n, int D, int zero_point, const float* d_row_inv, const int32_t* d_label,
+                        const float* d_sums, const float* d_weight, int K, float* d_own, float* d_other, int32_t* d_nearest, void* stream) {
+    if (int rc = check_device(ctx)) return rc;
+    if (int rc = kmeans_shape_check(dtype, n, D, K, zero_point)) return rc;
+    if (!d_rows || !d_row_inv || !d_label || !d_sums || !d_weight || !d_own || !d_other || !d_nearest) return fail(BN_ERR_ARG, "null device pointer");
+    if (dtype == BN_DTYPE_F32 && (uintptr_t)d_rows % 4) return fail(BN_ERR_ARG, "float32 rows must be 4-byte aligned");
+    if ((uintptr_t)d_row_inv % 4 || (uintptr_t)d_label % 4 || (uintptr_t)d_sums % 4 || (uintptr_t)d_weight % 4 || (uintptr_t)d_own % 4 ||
+        (uintptr_t)d_other % 4 || (uintptr_t)d_nearest % 4)
+        return fail(BN_ERR_ARG, "float32 / int32 arrays must be 4-byte aligned");
+    const bool i8 = dtype == BN_DTYPE_I8;
+    bn::KmeansGeom g{};
+    if (!bn::kmeans_geometry((long)n, D, K, &g)) return fail(BN_ERR_ARG, "D=%d: no tile of sums fits the LDS", D);
+    if (n == 0) return BN_OK;
+    bn::SilhouetteArgs a{};
+    a.rows = d_rows; a.row_inv = d_row_inv; a.label = d_label; a.sums = d_sums; a.weight = d_weight; a.own = d_own; a.other = d_other; a.nearest = d_nearest;
+    a.n = (int)n; a.D = D; a.K = K; a.zp = i8 ? zero_point : 0; a.steps_per_wg = g.steps_per_wg;
+    if (!bn::launch_silhouette_means(a, g, i8, (hipStream_t)stream)) return fail(BN_ERR_DEVICE, "the silhouette kernel's LDS request was refused");
     HIP_TRY(hipGetLastError());
     return BN_OK;
 }

@@ -433,7 +433,7 @@ void launch_i8_dwpw(const DwPw8Args& a, hipStream_t s);
 // One per source file with kernels: load that file's device code object now (bn_preload_kernels)
 void preload_f32(); void preload_f32_fused(); void preload_f32_pw(); void preload_f32_strip(); void preload_i8(); void preload_i8_fused();
 void preload_i8_pw(); void preload_i8_strip(); void preload_i8_tail(); void preload_i8_tail2(); void preload_ingest(); void preload_melspec();
-void preload_stft(); void preload_stft_exact(); void preload_sort(); void preload_probe(); void preload_probe_sweep(); void preload_activity(); void preload_search(); void preload_augment(); void preload_kmeans(); void preload_density(); void preload_tsne(); void preload_pca(); void preload_bootstrap(); void preload_head_i8();
+void preload_stft(); void preload_stft_exact(); void preload_sort(); void preload_probe(); void preload_probe_sweep(); void preload_activity(); void preload_search(); void preload_augment(); void preload_kmeans(); void preload_silhouette(); void preload_density(); void preload_tsne(); void preload_pca(); void preload_bootstrap(); void preload_head_i8();
 
 // bn_probe.hip: a classifier head on embeddings (bn_head_forward) and its training step (bn_probe_*)
 struct ProbeFwdArgs {
@@ -633,6 +633,21 @@ size_t kmeans_accumulate_workspace(long n, int D, int K);
 bool launch_kmeans_accumulate(const void* rows, bool i8, long n, int D, int zp, const float* row_inv, const int* label, int K, int accumulate, float* sums,
                               long long* counts, void* d_work, size_t work_bytes, hipStream_t s);
 void launch_kmeans_centroids(const float* sums, const long long* counts, int K, int D, float* cent, float* cent_inv, hipStream_t s);
+
+// bn_silhouette.hip: a labelling's mean cosines, the rows against the K sums of their clusters (bn_silhouette_means)
+struct SilhouetteArgs {
+    const void* rows;        // [n, D] float32 or int8 rows
+    const float* row_inv;    // [n] inverse norms
+    const int* label;        // [n] the labelling; outside 0 .. K-1: the row takes no part
+    const float* sums;       // [K, D] float32 sums of the normalised members
+    const float* weight;     // [K] 1 / members, 0 for an empty cluster
+    float* own;              // [n] mean cosine to the row's own cluster
+    float* other;            // [n] the highest mean cosine to another non-empty cluster
+    int* nearest;            // [n] that cluster, -1 without one
+    int n, D, K, zp;
+    long steps_per_wg;       // steps of BN_KMEANS_STEP_ROWS rows a workgroup streams
+};
+bool launch_silhouette_means(const SilhouetteArgs& a, const KmeansGeom& g, bool i8, hipStream_t s);   // g: kmeans_geometry(n, D, K); false: the runtime refused the LDS request
 
 // bn_density.hip: one Borůvka round over the mutual-reachability graph of the rows (bn_density_nearest)
 struct DensityArgs {

@@ -1,7 +1,7 @@
 // bn_rowstream.h — streaming the rows of an [n, D] matrix of float32 or int8 embeddings into an operand of the matrix cores, shared by
-// the four kernels that do it (search_score_kernel in bn_search.hip, kmeans_assign_kernel in bn_kmeans.hip, density_nearest_kernel in bn_density.hip, head_i8_kernel in bn_head_i8.hip).  It owns the row layout, the
+// the five kernels that do it (search_score_kernel in bn_search.hip, kmeans_assign_kernel in bn_kmeans.hip, silhouette_means_kernel in bn_silhouette.hip, density_nearest_kernel in bn_density.hip, head_i8_kernel in bn_head_i8.hip).  It owns the row layout, the
 // padding rule and the prefetch depth; the kernels keep the tile of the other operand, their MFMA body and their
-// epilogue (search, k-means and density take the rows as the A operand; the head takes them as B, a lane's 16 bytes being the same either way).
+// epilogue (search, k-means, silhouette and density take the rows as the A operand; the head takes them as B, a lane's 16 bytes being the same either way).
 //
 // Layout: a step is 64 rows, one 16-row MFMA tile per wave; lane (li, lk) of a wave reads row li of the tile.  A row is cut into chunks of
 // 64 bytes, of which the lane takes the 16 at 16 lk: elements 64 c + 16 lk .. + 15 (int8) or 16 c + 4 lk .. + 3 (float32) of chunk c.

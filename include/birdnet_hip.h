@@ -645,6 +645,27 @@ BN_API int bn_kmeans_accumulate(bn_ctx* ctx, const void* d_rows, int dtype, int6
 BN_API int bn_kmeans_centroids(bn_ctx* ctx, const float* d_sums, const int64_t* d_counts, int K, int D, float* d_centroids, float* d_cent_inv,
                         void* stream);
 
+/* ---- Silhouette: the mean cosines of a labelling's rows to its clusters (csrc/bn_silhouette.hip; no reference counterpart) -------------
+ * (birdnet_stm32/evaluation/silhouette.py is the specification.)  With x^_i the normalised row and S_c the sum of the normalised members
+ * of cluster c (bn_kmeans_accumulate's d_sums), sum over j in c of (1 - x^_i . x^_j) = n_c - x^_i . S_c: the exact cosine silhouette of
+ * every row needs the rows against the K sums once.  Rows, dtypes, inverse norms and the dot product have bn_kmeans_assign's meaning.
+ *   m[i, c]    = fl(fl(dot(x_i, S_c) * inv_row[i]) * w[c])       w[c] = float32(1 / n_c), 0 for an empty cluster: the caller's d_weight
+ *   live(i)    = inv_row[i] != 0 and 0 <= label[i] < K
+ *   own[i]     = m[i, label[i]]
+ *   other[i]   = the highest m[i, c] over c != label[i] with w[c] != 0;  nearest[i] = that c, the lowest index among equal values
+ * A row that is not live gets own = other = 0 and nearest = -1; a live row without another non-empty cluster gets other = 0 and
+ * nearest = -1.  The silhouette itself is the host's: a = (1 - own) n_A / (n_A - 1), b = 1 - other, s = (b - a) / max(a, b).
+ * The limits and the alignment rules are bn_kmeans_assign's, and so is the deal of the work (the sums take the centroids' place in LDS).
+ * No atomics: the same inputs give the same bits on every run.  A refused call returns BN_ERR_ARG and writes nothing. */
+
+/* d_own [n], d_other [n] float32 and d_nearest [n] int32 of the rows of d_rows [n, D] with labels d_label [n] against d_sums [K, D] and
+ * d_weight [K].  With more sums than one LDS tile holds, the three outputs carry the values of the tiles seen so far while the call runs:
+ * they hold the result once it has finished, and nothing else may read or write them meanwhile.  Nothing synchronises with the host
+ * inside the call. */
+BN_API int bn_silhouette_means(bn_ctx* ctx, const void* d_rows, int dtype, int64_t n, int D, int zero_point, const float* d_row_inv,
+                        const int32_t* d_label, const float* d_sums, const float* d_weight, int K, float* d_own, float* d_other,
+                        int32_t* d_nearest, void* stream);
+
 /* ---- Density clustering: one Borůvka round of the mutual-reachability spanning tree (csrc/bn_density.hip; no reference counterpart) ----
  * (HDBSCAN over cosine scores; birdnet_stm32/evaluation/density.py is the specification.)  Rows, dot and inv have bn_search's meaning.
  *   s_ij = fl(dot_ij * fl(inv_i * inv_j))      one value per pair, whichever end it is looked at from
