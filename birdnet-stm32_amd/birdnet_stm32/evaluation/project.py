@@ -404,9 +404,9 @@ def device_bytes_needed(n: int, D: int, itemsize: int, k: int) -> int:
     return max(search, fit)
 
 
-def device_affinities(ctx, rows: np.ndarray, zero_point: int, k: int, perplexity: float):
-    """``(idx [n, k] int64, p_cond [n, k] float32, beta [n] float64)`` of the non-zero rows ``rows``: ``bn_search_topk`` of the rows against
-    themselves, every row its own group, then ``bn_tsne_perplexity``."""
+def device_neighbours(ctx, rows: np.ndarray, zero_point: int, k: int):
+    """``(idx [n, k] int32, score [n, k] float32)``, tensors on ``ctx``'s device, of the non-zero rows ``rows``: ``bn_search_topk`` of the rows
+    against themselves, every row its own group."""
     import ctypes
 
     import torch
@@ -424,12 +424,29 @@ def device_affinities(ctx, rows: np.ndarray, zero_point: int, k: int, perplexity
         d_grp = torch.arange(n, dtype=torch.int32, device=dev)
         d_idx = torch.empty((n, k), dtype=torch.int32, device=dev)
         d_score = torch.empty((n, k), dtype=torch.float32, device=dev)
-        d_p = torch.empty((n, k), dtype=torch.float32, device=dev)
-        d_beta = torch.empty(n, dtype=torch.float64, device=dev)
         _hip.check(lib.bn_search_inv_norms(h, d_rows.data_ptr(), code, n, D, zero_point, d_inv.data_ptr(), sp))
         _hip.check(lib.bn_search_topk(h, d_rows.data_ptr(), code, n, D, zero_point, d_inv.data_ptr(), d_rows.data_ptr(), n, d_inv.data_ptr(),
                                       _hip.SEARCH_METRICS["cosine"], d_grp.data_ptr(), d_grp.data_ptr(), k, d_idx.data_ptr(), d_score.data_ptr(), sp))
-        _hip.check(lib.bn_tsne_perplexity(h, d_score.data_ptr(), n, k, ctypes.c_double(perplexity), d_p.data_ptr(), d_beta.data_ptr(), sp))
+    return d_idx, d_score
+
+
+def device_affinities(ctx, rows: np.ndarray, zero_point: int, k: int, perplexity: float):
+    """``(idx [n, k] int64, p_cond [n, k] float32, beta [n] float64)`` of the non-zero rows ``rows``: their neighbours
+    (``device_neighbours``), then ``bn_tsne_perplexity``."""
+    import ctypes
+
+    import torch
+
+    from birdnet_stm32 import _hip
+
+    n = rows.shape[0]
+    d_idx, d_score = device_neighbours(ctx, rows, zero_point, k)
+    dev = d_idx.device
+    with torch.cuda.device(dev):
+        sp = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        d_p = torch.empty((n, k), dtype=torch.float32, device=dev)
+        d_beta = torch.empty(n, dtype=torch.float64, device=dev)
+        _hip.check(ctx.lib.bn_tsne_perplexity(ctx.handle, d_score.data_ptr(), n, k, ctypes.c_double(perplexity), d_p.data_ptr(), d_beta.data_ptr(), sp))
         return d_idx.cpu().numpy().astype(np.int64), d_p.cpu().numpy(), d_beta.cpu().numpy()
 
 

@@ -433,7 +433,7 @@ void launch_i8_dwpw(const DwPw8Args& a, hipStream_t s);
 // One per source file with kernels: load that file's device code object now (bn_preload_kernels)
 void preload_f32(); void preload_f32_fused(); void preload_f32_pw(); void preload_f32_strip(); void preload_i8(); void preload_i8_fused();
 void preload_i8_pw(); void preload_i8_strip(); void preload_i8_tail(); void preload_i8_tail2(); void preload_ingest(); void preload_melspec();
-void preload_stft(); void preload_stft_exact(); void preload_sort(); void preload_probe(); void preload_probe_sweep(); void preload_activity(); void preload_search(); void preload_augment(); void preload_kmeans(); void preload_silhouette(); void preload_density(); void preload_tsne(); void preload_pca(); void preload_bootstrap(); void preload_head_i8();
+void preload_stft(); void preload_stft_exact(); void preload_sort(); void preload_probe(); void preload_probe_sweep(); void preload_activity(); void preload_search(); void preload_augment(); void preload_kmeans(); void preload_silhouette(); void preload_density(); void preload_tsne(); void preload_propagate(); void preload_pca(); void preload_bootstrap(); void preload_head_i8();
 
 // bn_probe.hip: a classifier head on embeddings (bn_head_forward) and its training step (bn_probe_*)
 struct ProbeFwdArgs {
@@ -675,6 +675,12 @@ size_t tsne_gradient_workspace(long n);
 void launch_tsne_gradient(const float* y, long n, const long long* rowptr, const int* col, const float* val, float exaggeration, float* grad, double* z,
                           double* kl_rows, void* d_work, hipStream_t s);
 void launch_tsne_update(float* y, const float* grad, float* update, float* gains, long n, float lr, float momentum, hipStream_t s);
+
+// bn_propagate.hip: label spreading over a fixed CSR matrix — one update with its float64 change, and the decision per row (bn_propagate_*)
+size_t propagate_workspace(long n);   // the rows' parts of the change
+void launch_propagate_step(const long long* rowptr, const int* col, const float* val, const float* f, const int* seed_label, long n, int C, float alpha,
+                           float* f_next, double* delta, void* d_work, hipStream_t s);
+void launch_propagate_decide(const float* f, long n, int C, int* label, float* score, hipStream_t s);
 
 // bn_pca.hip: column sums, scatter matrix and projection of embedding rows (bn_pca_*)
 struct PcaColsumGeom {

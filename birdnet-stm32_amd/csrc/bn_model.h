@@ -73,6 +73,8 @@ struct bn_ctx {
     size_t tsne_work_bytes = 0;
     void* d_pca_work = nullptr;      // bn_pca_colsum / bn_pca_gram: the row ranges' float64 partial sums; grown on demand
     size_t pca_work_bytes = 0;
+    void* d_propagate_work = nullptr;   // bn_propagate_step: the rows' float64 parts of the change; grown on demand
+    size_t propagate_work_bytes = 0;
     void* d_boot_work = nullptr;     // bn_bootstrap_*: jump-ahead table, rejection counter and list, prepared class orders; grown on demand
     size_t boot_work_bytes = 0;
     void* d_mlp_work = nullptr;      // bn_head_mlp_forward: the hidden activations of one step of rows; grown on demand

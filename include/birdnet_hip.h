@@ -739,6 +739,35 @@ BN_API int bn_tsne_gradient(bn_ctx* ctx, const float* d_y, int64_t n, const int6
 BN_API int bn_tsne_update(bn_ctx* ctx, float* d_y, const float* d_grad, float* d_update, float* d_gains, int64_t n, float lr, float momentum,
                    void* stream);
 
+/* ---- Label spreading over a fixed sparse graph (csrc/bn_propagate.hip; no reference counterpart) ------------------------------------
+ * (Zhou et al. 2004, scikit-learn's LabelSpreading; birdnet_stm32/evaluation/propagate.py is the specification.)  S = (d_rowptr [n + 1]
+ * int64, d_col int32, d_val float32) is a CSR matrix whose rows may hold anything from 0 to n - 1 entries, F [n, C] float32 the label
+ * matrix, d_seed_label [n] int32 the class of a labelled row and -1 (or anything outside 0 .. C - 1) for the others.  One update:
+ *   acc = 0;  for the entries of row i in stored order: acc = fl(acc + fl(S_ij * F[j, c]));  F_next[i, c] = fl(fl(alpha * acc) + y),
+ *   y = fl(1 - alpha) where d_seed_label[i] == c, else 0
+ * in float32, every operation rounded on its own, nothing fused.  One lane adds all the entries of an (i, c), so the order is the matrix's:
+ * no sum across lanes, no floating-point atomics, the same inputs give the same bits on every run and numpy reproduces them.  The device
+ * tables are not trusted further than their sizes: row bounds are clipped to 0 .. d_rowptr[n], and an entry whose column lies outside
+ * 0 .. n - 1 contributes nothing, so a bad matrix gives wrong numbers, never a stray read beyond d_rowptr[n] entries.  A refused call
+ * returns BN_ERR_ARG and writes nothing.  Nothing synchronises with the host inside a call unless the context's workspace has to grow. */
+/* How the rows are dealt — from C and the alignment of the two F arrays alone: with C % 4 == 0 and both arrays 16-byte aligned a lane owns
+ * four neighbouring classes (16-byte loads), otherwise one; a row goes to the smallest power of two of lanes that covers its classes, at
+ * most BN_PROPAGATE_MAX_ROW_LANES, and a lane takes every further class (or four) at that stride. */
+#define BN_PROPAGATE_MAX_CLASSES 4096
+#define BN_PROPAGATE_MAX_N (1 << 21)
+#define BN_PROPAGATE_MAX_ROW_LANES 64
+/* d_f_next [n, C] = one update of d_f [n, C]; with d_delta (float64, may be NULL) also *d_delta = sum over (i, c) of |F_next - F|, every
+ * difference exact in float64: per row each lane over its classes in ascending order, the row's lanes in a fixed tree, then the rows in
+ * one fixed order.  *d_delta stays on the device; a NULL d_delta is left alone and costs nothing.
+ * Refused: n < 1 or n > BN_PROPAGATE_MAX_N, C outside 1..BN_PROPAGATE_MAX_CLASSES, alpha not in (0, 1), a NULL pointer other than d_delta,
+ * d_rowptr / d_delta not 8-byte or another array not 4-byte aligned, d_f_next overlapping d_f. */
+BN_API int bn_propagate_step(bn_ctx* ctx, const int64_t* d_rowptr, const int32_t* d_col, const float* d_val, const float* d_f,
+                             const int32_t* d_seed_label, int64_t n, int C, float alpha, float* d_f_next, double* d_delta, void* stream);
+/* Per row of d_f [n, C]: d_label = the first class with the largest value (float32 comparison), d_score = fl(F[i, label] / sum_c F[i, c]),
+ * the sum in float32 in the implementation's fixed order; a row whose sum is 0 gets -1 and 0.  Values are finite and >= 0.
+ * Refused: n < 1 or n > BN_PROPAGATE_MAX_N, C outside 1..BN_PROPAGATE_MAX_CLASSES, a NULL pointer, an array not 4-byte aligned. */
+BN_API int bn_propagate_decide(bn_ctx* ctx, const float* d_f, int64_t n, int C, int32_t* d_label, float* d_score, void* stream);
+
 /* ---- Principal components: column sums, scatter matrix and projection of embedding rows (csrc/bn_pca.hip; no reference counterpart) ----
  * (birdnet_stm32/evaluation/reduce.py is the specification; the eigen-decomposition stays on the host.)  Rows have bn_search's meaning: an
  * int8 row is byte - zero_point.  With c_i = fl32(x_i - mean) (x_i itself where d_mean is NULL; an int8 x is made float32 first, which is exact):
