@@ -42,6 +42,7 @@ EXPORTS = (
     "bn_density_nearest",
     "bn_tsne_perplexity", "bn_tsne_gradient", "bn_tsne_update",
     "bn_propagate_step", "bn_propagate_decide",
+    "bn_select_run",
     "bn_pca_colsum", "bn_pca_gram", "bn_pca_transform",
     "bn_bootstrap_rejections", "bn_bootstrap_counts", "bn_bootstrap_ap", "bn_head_i8_forward", "bn_head_i8_pass_classes",
 )  # fmt: skip
@@ -86,6 +87,8 @@ KMEANS_LDS_BYTES, KMEANS_MAX_TILE, KMEANS_STEP_ROWS, KMEANS_MIN_WG_STEPS, KMEANS
 TSNE_TILE_I, TSNE_TILE_J, TSNE_SPLIT_J, TSNE_ROW_LANES, TSNE_MAX_K, TSNE_MAX_N = 256, 1024, 4096, 16, 128, 1 << 21
 # bn_propagate_* (include/birdnet_hip.h): limits, and the most lanes a row's classes are dealt to
 PROPAGATE_MAX_CLASSES, PROPAGATE_MAX_N, PROPAGATE_MAX_ROW_LANES = 4096, 1 << 21, 64
+# bn_select_run (include/birdnet_hip.h): how the rows are dealt to workgroups; a pass folds at most SELECT_MAX_WGS partial picks
+SELECT_STEP_ROWS, SELECT_MIN_WG_STEPS, SELECT_MAX_WGS = 64, 2, 1024
 # bn_density_nearest (include/birdnet_hip.h): limits, and the constants the staged tile and the streamed row ranges follow from
 DENSITY_MAX_N, DENSITY_MAX_D = 1 << 20, 2048
 DENSITY_LDS_BYTES, DENSITY_MAX_TILE, DENSITY_STEP_ROWS, DENSITY_MIN_WG_STEPS, DENSITY_MAX_ROW_WGS = 160 * 1024, 128, 64, 32, 256
@@ -250,6 +253,7 @@ def load_library(path: str | None = None):
     lib.bn_tsne_update.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_void_p]
     lib.bn_propagate_step.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_float, c_void_p, c_void_p, c_void_p]
     lib.bn_propagate_decide.argtypes = [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]
+    lib.bn_select_run.argtypes = [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]
     lib.bn_pca_colsum.argtypes = [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p]
     lib.bn_pca_gram.argtypes = [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]
     lib.bn_pca_transform.argtypes = [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]

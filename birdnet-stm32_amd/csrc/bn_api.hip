@@ -222,6 +222,7 @@ void bn_ctx_destroy(bn_ctx* c) {
     if (c->d_tsne_work) (void)hipFree(c->d_tsne_work);
     if (c->d_pca_work) (void)hipFree(c->d_pca_work);
     if (c->d_propagate_work) (void)hipFree(c->d_propagate_work);
+    if (c->d_select_work) (void)hipFree(c->d_select_work);
     if (c->d_boot_work) (void)hipFree(c->d_boot_work);
     if (c->d_mlp_work) (void)hipFree(c->d_mlp_work);
     delete c;
@@ -1072,7 +1073,7 @@ int bn_preload_kernels(bn_ctx* ctx) {
     // copies wait meanwhile).  A caller with idle time before its first batch — the evaluate pipeline while the first files are read — asks here.
     bn::preload_ingest(); bn::preload_stft(); bn::preload_stft_exact(); bn::preload_i8_fused(); bn::preload_i8_strip(); bn::preload_i8_tail2();
     bn::preload_i8_tail(); bn::preload_i8(); bn::preload_i8_pw(); bn::preload_f32(); bn::preload_f32_fused(); bn::preload_f32_strip();
-    bn::preload_f32_pw(); bn::preload_melspec(); bn::preload_sort(); bn::preload_probe(); bn::preload_probe_sweep(); bn::preload_probe_mlp(); bn::preload_activity(); bn::preload_search(); bn::preload_augment(); bn::preload_kmeans(); bn::preload_silhouette(); bn::preload_density(); bn::preload_tsne(); bn::preload_propagate(); bn::preload_pca(); bn::preload_bootstrap(); bn::preload_head_i8();
+    bn::preload_f32_pw(); bn::preload_melspec(); bn::preload_sort(); bn::preload_probe(); bn::preload_probe_sweep(); bn::preload_probe_mlp(); bn::preload_activity(); bn::preload_search(); bn::preload_augment(); bn::preload_kmeans(); bn::preload_silhouette(); bn::preload_density(); bn::preload_tsne(); bn::preload_propagate(); bn::preload_select(); bn::preload_pca(); bn::preload_bootstrap(); bn::preload_head_i8();
     return BN_OK;
 }
 
@@ -1091,7 +1092,7 @@ const char* bn_kernel_names(void) {
     return "ingest_resample_kernel\ningest_decimate_kernel\ningest_peak_kernel\ningest_chunks_kernel\nchunk_peaknorm_kernel\npool_scores_kernel\nstft512_mag_kernel\nspec_normalize_kernel\nmelspec_finish_kernel\nf32_mel_kernel\nf32_melfin_kernel\nf32_mag_kernel\nf32_rawfe_kernel\nf32_stem_kernel\nf32_dw_kernel\n"
            "f32_pw_kernel\nf32_pw_ws_kernel\nf32_dwpw_kernel\nf32_dwpw_wave_kernel\nf32_strip_kernel\nf32_front_strip_kernel\nf32_front2_kernel\nf32_pwdw_kernel\nf32_dw_stream_kernel\nf32_front_kernel\nf32_gap_kernel\nf32_gap_dense_kernel\nf32_gap_dense_emb_kernel\nf32_dense_kernel\nf32_segate_kernel\nf32_scale_kernel\nf32_attnpool_kernel\n"
            "i8_quant_kernel\ni8_mel_kernel\ni8_stem_kernel\ni8_dw_kernel\ni8_pw_kernel\ni8_dwpw_kernel\ni8_mel_mfma_kernel\ni8_strip_kernel\ni8_strip_mf_kernel\ni8_front_strip_kernel\ni8_front_kernel\ni8_tail_kernel\ni8_tail_emb_kernel\ni8_tail2_kernel\ni8_tail2_emb_kernel\ni8_mid2_kernel\ni8_mean_kernel\ni8_fc_kernel\ni8_scale_kernel\ni8_maxnorm_kernel\ni8_rawfe_kernel\ni8_pwdw_kernel\ni8_dw_stream_kernel\ni8_stem_stream_kernel\ni8_segate_kernel\ni8_pw_wave_kernel\ni8_pw_lds_kernel\ni8_attnpool_kernel\n"
-           "i8_head_kernel\ni8_head_softmax_kernel\nemb_store_kernel\nprobe_fwd_kernel\nprobe_dw_kernel\nprobe_reduce_kernel\nprobe_update_kernel\nprobe_loss_sum_kernel\nprobe_sweep_snapshot_kernel\nste_kernel\nactivity_count_kernel\nsearch_inv_norms_kernel\nsearch_score_kernel\nsearch_merge_kernel\naugment_kernel\nkmeans_assign_kernel\nkmeans_keys_kernel\nkmeans_offsets_kernel\nkmeans_segments_kernel\nkmeans_partial_kernel\nkmeans_fold_kernel\nkmeans_scale_kernel\nsilhouette_means_kernel\ndensity_nearest_kernel\ntsne_perplexity_kernel\ntsne_repulsion_kernel\ntsne_fold_kernel\ntsne_z_kernel\ntsne_attraction_kernel\ntsne_update_kernel\npropagate_step_kernel\npropagate_delta_kernel\npropagate_decide_kernel\npca_colsum_kernel\npca_colsum_fold_kernel\npca_gram_kernel\npca_gram_fold_kernel\npca_transform_kernel\nbootstrap_table_kernel\nbootstrap_reject_kernel\nbootstrap_prepare_kernel\nbootstrap_resample_kernel\nhead_i8_kernel";
+           "i8_head_kernel\ni8_head_softmax_kernel\nemb_store_kernel\nprobe_fwd_kernel\nprobe_dw_kernel\nprobe_reduce_kernel\nprobe_update_kernel\nprobe_loss_sum_kernel\nprobe_sweep_snapshot_kernel\nste_kernel\nactivity_count_kernel\nsearch_inv_norms_kernel\nsearch_score_kernel\nsearch_merge_kernel\naugment_kernel\nkmeans_assign_kernel\nkmeans_keys_kernel\nkmeans_offsets_kernel\nkmeans_segments_kernel\nkmeans_partial_kernel\nkmeans_fold_kernel\nkmeans_scale_kernel\nsilhouette_means_kernel\ndensity_nearest_kernel\ntsne_perplexity_kernel\ntsne_repulsion_kernel\ntsne_fold_kernel\ntsne_z_kernel\ntsne_attraction_kernel\ntsne_update_kernel\npropagate_step_kernel\npropagate_delta_kernel\npropagate_decide_kernel\nselect_pass_kernel\npca_colsum_kernel\npca_colsum_fold_kernel\npca_gram_kernel\npca_gram_fold_kernel\npca_transform_kernel\nbootstrap_table_kernel\nbootstrap_reject_kernel\nbootstrap_prepare_kernel\nbootstrap_resample_kernel\nhead_i8_kernel";
 }
 
 }  // extern "C"
@@ -1363,6 +1364,30 @@ int bn_propagate_decide(bn_ctx* ctx, const float* d_f, int64_t n, int C, int32_t
     if (!d_f || !d_label || !d_score) return fail(BN_ERR_ARG, "null device pointer");
     if ((uintptr_t)d_f % 4 || (uintptr_t)d_label % 4 || (uintptr_t)d_score % 4) return fail(BN_ERR_ARG, "float32 / int32 arrays must be 4-byte aligned");
     bn::launch_propagate_decide(d_f, (long)n, C, d_label, d_score, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return BN_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------- farthest-first traversal (bn_select.hip)
+extern "C" {
+
+int bn_select_run(bn_ctx* ctx, const void* d_rows, int dtype, int64_t n, int D, int zero_point, const float* d_inv, const float* d_weight, float* d_m,
+                  int32_t* d_nearest, int32_t* d_picked, int forced, int steps, float* d_key, void* stream) {
+    if (int rc = check_device(ctx)) return rc;
+    if (int rc = row_matrix_check(dtype, n, D, BN_SEARCH_MAX_D, zero_point)) return rc;
+    if (steps < 0 || forced < 0 || forced > steps) return fail(BN_ERR_ARG, "forced=%d steps=%d: 0 <= forced <= steps", forced, steps);
+    if (!d_rows || !d_inv || !d_m || !d_nearest || !d_picked || !d_key) return fail(BN_ERR_ARG, "null device pointer");
+    if (dtype == BN_DTYPE_F32 && (uintptr_t)d_rows % 4) return fail(BN_ERR_ARG, "float32 rows must be 4-byte aligned");
+    if ((uintptr_t)d_inv % 4 || (uintptr_t)d_weight % 4 || (uintptr_t)d_m % 4 || (uintptr_t)d_nearest % 4 || (uintptr_t)d_picked % 4 || (uintptr_t)d_key % 4)
+        return fail(BN_ERR_ARG, "float32 / int32 arrays must be 4-byte aligned");
+    if (steps == 0) return BN_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t need = bn::select_workspace();
+    if (int rc = grow_device_buffer(&ctx->d_select_work, &ctx->select_work_bytes, need, need, s, BN_ERR_NOMEM, "selection")) return rc;
+    bn::launch_select_run(d_rows, dtype == BN_DTYPE_I8, (long)n, D, zero_point, d_inv, d_weight, d_m, d_nearest, d_picked, forced, steps, d_key,
+                          ctx->d_select_work, s);
     HIP_TRY(hipGetLastError());
     return BN_OK;
 }

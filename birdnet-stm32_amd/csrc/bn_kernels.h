@@ -433,7 +433,7 @@ void launch_i8_dwpw(const DwPw8Args& a, hipStream_t s);
 // One per source file with kernels: load that file's device code object now (bn_preload_kernels)
 void preload_f32(); void preload_f32_fused(); void preload_f32_pw(); void preload_f32_strip(); void preload_i8(); void preload_i8_fused();
 void preload_i8_pw(); void preload_i8_strip(); void preload_i8_tail(); void preload_i8_tail2(); void preload_ingest(); void preload_melspec();
-void preload_stft(); void preload_stft_exact(); void preload_sort(); void preload_probe(); void preload_probe_sweep(); void preload_activity(); void preload_search(); void preload_augment(); void preload_kmeans(); void preload_silhouette(); void preload_density(); void preload_tsne(); void preload_propagate(); void preload_pca(); void preload_bootstrap(); void preload_head_i8();
+void preload_stft(); void preload_stft_exact(); void preload_sort(); void preload_probe(); void preload_probe_sweep(); void preload_activity(); void preload_search(); void preload_augment(); void preload_kmeans(); void preload_silhouette(); void preload_density(); void preload_tsne(); void preload_propagate(); void preload_select(); void preload_pca(); void preload_bootstrap(); void preload_head_i8();
 
 // bn_probe.hip: a classifier head on embeddings (bn_head_forward) and its training step (bn_probe_*)
 struct ProbeFwdArgs {
@@ -681,6 +681,26 @@ size_t propagate_workspace(long n);   // the rows' parts of the change
 void launch_propagate_step(const long long* rowptr, const int* col, const float* val, const float* f, const int* seed_label, long n, int C, float alpha,
                            float* f_next, double* delta, void* d_work, hipStream_t s);
 void launch_propagate_decide(const float* f, long n, int C, int* label, float* score, hipStream_t s);
+
+// bn_select.hip: farthest-first traversal, one launch per pass over the rows (bn_select_run)
+struct SelectArgs {
+    const void* rows;        // [n, D] float32 or int8 rows
+    const float* inv;        // [n] inverse norms
+    const float* weight;     // [n] or null: all 1
+    float* m;                // [n] the highest score to a row taken so far, +inf for a taken row
+    int* nearest;            // [n] the row that gave it
+    int* picked;             // [steps]
+    float* key;              // [steps]
+    const float* part_key_in;   // the previous pass's partials, nprev of them
+    const int* part_row_in;
+    float* part_key_out;     // this pass's, one per workgroup
+    int* part_row_out;
+    int n, D, zp, t, pass, nprev;
+    long steps_per_wg;       // steps of BN_SELECT_STEP_ROWS rows a workgroup streams
+};
+size_t select_workspace();   // the two alternating partial buffers
+void launch_select_run(const void* rows, bool i8, long n, int D, int zp, const float* inv, const float* weight, float* m, int* nearest, int* picked, int forced,
+                       int steps, float* key, void* d_work, hipStream_t s);
 
 // bn_pca.hip: column sums, scatter matrix and projection of embedding rows (bn_pca_*)
 struct PcaColsumGeom {

@@ -75,6 +75,8 @@ struct bn_ctx {
     size_t pca_work_bytes = 0;
     void* d_propagate_work = nullptr;   // bn_propagate_step: the rows' float64 parts of the change; grown on demand
     size_t propagate_work_bytes = 0;
+    void* d_select_work = nullptr;      // bn_select_run: the two alternating buffers of per-workgroup partial picks; allocated on first use
+    size_t select_work_bytes = 0;
     void* d_boot_work = nullptr;     // bn_bootstrap_*: jump-ahead table, rejection counter and list, prepared class orders; grown on demand
     size_t boot_work_bytes = 0;
     void* d_mlp_work = nullptr;      // bn_head_mlp_forward: the hidden activations of one step of rows; grown on demand

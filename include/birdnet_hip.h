@@ -768,6 +768,35 @@ BN_API int bn_propagate_step(bn_ctx* ctx, const int64_t* d_rowptr, const int32_t
  * Refused: n < 1 or n > BN_PROPAGATE_MAX_N, C outside 1..BN_PROPAGATE_MAX_CLASSES, a NULL pointer, an array not 4-byte aligned. */
 BN_API int bn_propagate_decide(bn_ctx* ctx, const float* d_f, int64_t n, int C, int32_t* d_label, float* d_score, void* stream);
 
+/* ---- Selection: farthest-first traversal over an embedding matrix (csrc/bn_select.hip; no reference counterpart) ----------------------
+ * (k-centre greedy, the core-set selection of Sener & Savarese 2018; birdnet_stm32/evaluation/select.py is the specification.)  Rows, dot
+ * and inv have bn_search's meaning.  The state is d_m [n] float32 — the highest score of a row to any row taken so far, -inf for none yet,
+ * +inf for a taken row — and d_nearest [n] int32, the row that gave it.
+ *   score(i, c) = fl(fl(dot(x_i, x_c) * inv[i]) * inv[c])
+ *   key[i]      = fl(u_i * fl(1 - m_i)), u_i = d_weight[i] (finite, >= 0; 1 without weights); -inf for a zero row (inv == 0), for a taken
+ *                 row and for a NaN
+ *   a pick      = the row with the highest key, the lowest index among equal keys (float comparison); -1 with key -inf when no key is
+ *                 above -inf, and then nothing changes
+ *   taking c    = for every live, untaken row i != c: s = score(i, c); s > m_i sets m_i = s, nearest_i = c (strict: the earlier centre
+ *                 stands on a tie); then m_c = +inf, nearest_c = c
+ * The float32 dot product of a row is four fused multiply-add chains, one per lane over the lane's 16-byte pieces of every 64 bytes in
+ * ascending order, added as (l0 + l1) + (l2 + l3); the int8 one is exact in int32.  No atomics: the same inputs give the same bits on
+ * every run, and a run of a + b steps equals a run of a steps followed by one of b.
+ * 1 <= D <= BN_SEARCH_MAX_D, 0 <= n < 2^31, 0 <= forced <= steps.  float32 rows need 4-byte alignment (16 with D % 4 == 0 takes the wide
+ * loads; int8: 16 with D % 16 == 0).  A refused call returns BN_ERR_ARG and writes nothing. */
+/* How the rows are dealt to workgroups — from n alone: steps of BN_SELECT_STEP_ROWS rows (the row streamer's step), at least
+ * BN_SELECT_MIN_WG_STEPS steps per workgroup, at most BN_SELECT_MAX_WGS workgroups.  A pass is one launch; every workgroup leaves one
+ * partial (key, row), and every workgroup of the next pass folds all of them: BN_SELECT_MAX_WGS bounds that fold at 8 KiB. */
+#define BN_SELECT_STEP_ROWS 64
+#define BN_SELECT_MIN_WG_STEPS 2
+#define BN_SELECT_MAX_WGS 1024
+/* `steps` picks over d_rows [n, D].  The first `forced` entries of d_picked [steps] are given and are taken in order (an entry outside
+ * 0 .. n-1, or one naming a zero row, is skipped; their d_key entries are left alone); entries forced .. steps-1 are chosen as above and
+ * written with their keys to d_key [steps].  d_weight may be NULL.  forced = 0 starts from the state as given.  All launches (steps + 1 at
+ * the most) are enqueued by the call; nothing synchronises with the host inside it unless the context's workspace has to be allocated. */
+BN_API int bn_select_run(bn_ctx* ctx, const void* d_rows, int dtype, int64_t n, int D, int zero_point, const float* d_inv, const float* d_weight,
+                         float* d_m, int32_t* d_nearest, int32_t* d_picked, int forced, int steps, float* d_key, void* stream);
+
 /* ---- Principal components: column sums, scatter matrix and projection of embedding rows (csrc/bn_pca.hip; no reference counterpart) ----
  * (birdnet_stm32/evaluation/reduce.py is the specification; the eigen-decomposition stays on the host.)  Rows have bn_search's meaning: an
  * int8 row is byte - zero_point.  With c_i = fl32(x_i - mean) (x_i itself where d_mean is NULL; an int8 x is made float32 first, which is exact):
