@@ -1,12 +1,12 @@
 """``python -m birdnet_stm32 <command>`` dispatcher (reference: birdnet_stm32/__main__.py:12-47).
 
-``evaluate``, ``embed`` (embeddings of audio files, this build only), ``analyze`` (per-chunk detections over whole recordings, this build only), ``probe`` (a new classifier head on frozen embeddings, the reference's ``train --linear_probe``), ``search`` (nearest embeddings of query clips, this build only), ``cluster`` (k-means over embed archives, this build only), ``project`` (2-D t-SNE maps of embed archives, this build only), ``density`` (HDBSCAN over embed archives, this build only), ``reduce`` (PCA and whitening of embed archives, this build only), ``propagate`` (a few labels spread over embed archives, this build only), ``select`` (which rows of embed archives to label next, this build only) and ``convert`` (own post-training quantisation, no TensorFlow) exist in this build; the reference's train /
+``evaluate``, ``embed`` (embeddings of audio files, this build only), ``analyze`` (per-chunk detections over whole recordings, this build only), ``probe`` (a new classifier head on frozen embeddings, the reference's ``train --linear_probe``), ``search`` (nearest embeddings of query clips, this build only), ``cluster`` (k-means over embed archives, this build only), ``project`` (2-D t-SNE maps of embed archives, this build only), ``density`` (HDBSCAN over embed archives, this build only), ``reduce`` (PCA and whitening of embed archives, this build only), ``propagate`` (a few labels spread over embed archives, this build only), ``select`` (which rows of embed archives to label next, this build only), ``indices`` (acoustic indices of whole recordings, no model, this build only) and ``convert`` (own post-training quantisation, no TensorFlow) exist in this build; the reference's train /
 deploy / board-test commands are outside the accelerated path and answer with a pointer to the reference package.
 """
 
 import sys
 
-USAGE = "Usage: birdnet-stm32 {train,convert,evaluate,embed,analyze,probe,search,cluster,project,density,reduce,propagate,select,deploy,board-test}"
+USAGE = "Usage: birdnet-stm32 {train,convert,evaluate,embed,analyze,probe,search,cluster,project,density,reduce,propagate,select,indices,deploy,board-test}"
 
 
 def main():
@@ -57,6 +57,10 @@ def main():
         run()
     elif command == "select":
         from birdnet_stm32.cli.select import main as run
+
+        run()
+    elif command == "indices":
+        from birdnet_stm32.cli.indices import main as run
 
         run()
     elif command == "convert":

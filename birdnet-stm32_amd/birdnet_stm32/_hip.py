@@ -43,6 +43,7 @@ EXPORTS = (
     "bn_tsne_perplexity", "bn_tsne_gradient", "bn_tsne_update",
     "bn_propagate_step", "bn_propagate_decide",
     "bn_select_run",
+    "bn_acoustic_indices",
     "bn_pca_colsum", "bn_pca_gram", "bn_pca_transform",
     "bn_bootstrap_rejections", "bn_bootstrap_counts", "bn_bootstrap_ap", "bn_head_i8_forward", "bn_head_i8_pass_classes",
 )  # fmt: skip
@@ -254,6 +255,7 @@ def load_library(path: str | None = None):
     lib.bn_propagate_step.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_float, c_void_p, c_void_p, c_void_p]
     lib.bn_propagate_decide.argtypes = [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]
     lib.bn_select_run.argtypes = [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]
+    lib.bn_acoustic_indices.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.bn_pca_colsum.argtypes = [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p]
     lib.bn_pca_gram.argtypes = [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]
     lib.bn_pca_transform.argtypes = [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]

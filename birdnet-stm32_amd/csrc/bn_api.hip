@@ -1073,7 +1073,7 @@ int bn_preload_kernels(bn_ctx* ctx) {
     // copies wait meanwhile).  A caller with idle time before its first batch — the evaluate pipeline while the first files are read — asks here.
     bn::preload_ingest(); bn::preload_stft(); bn::preload_stft_exact(); bn::preload_i8_fused(); bn::preload_i8_strip(); bn::preload_i8_tail2();
     bn::preload_i8_tail(); bn::preload_i8(); bn::preload_i8_pw(); bn::preload_f32(); bn::preload_f32_fused(); bn::preload_f32_strip();
-    bn::preload_f32_pw(); bn::preload_melspec(); bn::preload_sort(); bn::preload_probe(); bn::preload_probe_sweep(); bn::preload_probe_mlp(); bn::preload_activity(); bn::preload_search(); bn::preload_augment(); bn::preload_kmeans(); bn::preload_silhouette(); bn::preload_density(); bn::preload_tsne(); bn::preload_propagate(); bn::preload_select(); bn::preload_pca(); bn::preload_bootstrap(); bn::preload_head_i8();
+    bn::preload_f32_pw(); bn::preload_melspec(); bn::preload_sort(); bn::preload_probe(); bn::preload_probe_sweep(); bn::preload_probe_mlp(); bn::preload_activity(); bn::preload_search(); bn::preload_augment(); bn::preload_kmeans(); bn::preload_silhouette(); bn::preload_density(); bn::preload_tsne(); bn::preload_propagate(); bn::preload_select(); bn::preload_indices(); bn::preload_pca(); bn::preload_bootstrap(); bn::preload_head_i8();
     return BN_OK;
 }
 
@@ -1092,7 +1092,7 @@ const char* bn_kernel_names(void) {
     return "ingest_resample_kernel\ningest_decimate_kernel\ningest_peak_kernel\ningest_chunks_kernel\nchunk_peaknorm_kernel\npool_scores_kernel\nstft512_mag_kernel\nspec_normalize_kernel\nmelspec_finish_kernel\nf32_mel_kernel\nf32_melfin_kernel\nf32_mag_kernel\nf32_rawfe_kernel\nf32_stem_kernel\nf32_dw_kernel\n"
            "f32_pw_kernel\nf32_pw_ws_kernel\nf32_dwpw_kernel\nf32_dwpw_wave_kernel\nf32_strip_kernel\nf32_front_strip_kernel\nf32_front2_kernel\nf32_pwdw_kernel\nf32_dw_stream_kernel\nf32_front_kernel\nf32_gap_kernel\nf32_gap_dense_kernel\nf32_gap_dense_emb_kernel\nf32_dense_kernel\nf32_segate_kernel\nf32_scale_kernel\nf32_attnpool_kernel\n"
            "i8_quant_kernel\ni8_mel_kernel\ni8_stem_kernel\ni8_dw_kernel\ni8_pw_kernel\ni8_dwpw_kernel\ni8_mel_mfma_kernel\ni8_strip_kernel\ni8_strip_mf_kernel\ni8_front_strip_kernel\ni8_front_kernel\ni8_tail_kernel\ni8_tail_emb_kernel\ni8_tail2_kernel\ni8_tail2_emb_kernel\ni8_mid2_kernel\ni8_mean_kernel\ni8_fc_kernel\ni8_scale_kernel\ni8_maxnorm_kernel\ni8_rawfe_kernel\ni8_pwdw_kernel\ni8_dw_stream_kernel\ni8_stem_stream_kernel\ni8_segate_kernel\ni8_pw_wave_kernel\ni8_pw_lds_kernel\ni8_attnpool_kernel\n"
-           "i8_head_kernel\ni8_head_softmax_kernel\nemb_store_kernel\nprobe_fwd_kernel\nprobe_dw_kernel\nprobe_reduce_kernel\nprobe_update_kernel\nprobe_loss_sum_kernel\nprobe_sweep_snapshot_kernel\nste_kernel\nactivity_count_kernel\nsearch_inv_norms_kernel\nsearch_score_kernel\nsearch_merge_kernel\naugment_kernel\nkmeans_assign_kernel\nkmeans_keys_kernel\nkmeans_offsets_kernel\nkmeans_segments_kernel\nkmeans_partial_kernel\nkmeans_fold_kernel\nkmeans_scale_kernel\nsilhouette_means_kernel\ndensity_nearest_kernel\ntsne_perplexity_kernel\ntsne_repulsion_kernel\ntsne_fold_kernel\ntsne_z_kernel\ntsne_attraction_kernel\ntsne_update_kernel\npropagate_step_kernel\npropagate_delta_kernel\npropagate_decide_kernel\nselect_pass_kernel\npca_colsum_kernel\npca_colsum_fold_kernel\npca_gram_kernel\npca_gram_fold_kernel\npca_transform_kernel\nbootstrap_table_kernel\nbootstrap_reject_kernel\nbootstrap_prepare_kernel\nbootstrap_resample_kernel\nhead_i8_kernel";
+           "i8_head_kernel\ni8_head_softmax_kernel\nemb_store_kernel\nprobe_fwd_kernel\nprobe_dw_kernel\nprobe_reduce_kernel\nprobe_update_kernel\nprobe_loss_sum_kernel\nprobe_sweep_snapshot_kernel\nste_kernel\nactivity_count_kernel\nsearch_inv_norms_kernel\nsearch_score_kernel\nsearch_merge_kernel\naugment_kernel\nkmeans_assign_kernel\nkmeans_keys_kernel\nkmeans_offsets_kernel\nkmeans_segments_kernel\nkmeans_partial_kernel\nkmeans_fold_kernel\nkmeans_scale_kernel\nsilhouette_means_kernel\ndensity_nearest_kernel\ntsne_perplexity_kernel\ntsne_repulsion_kernel\ntsne_fold_kernel\ntsne_z_kernel\ntsne_attraction_kernel\ntsne_update_kernel\npropagate_step_kernel\npropagate_delta_kernel\npropagate_decide_kernel\nselect_pass_kernel\nacoustic_indices_kernel\npca_colsum_kernel\npca_colsum_fold_kernel\npca_gram_kernel\npca_gram_fold_kernel\npca_transform_kernel\nbootstrap_table_kernel\nbootstrap_reject_kernel\nbootstrap_prepare_kernel\nbootstrap_resample_kernel\nhead_i8_kernel";
 }
 
 }  // extern "C"
@@ -1388,6 +1388,36 @@ int bn_select_run(bn_ctx* ctx, const void* d_rows, int dtype, int64_t n, int D, 
     if (int rc = grow_device_buffer(&ctx->d_select_work, &ctx->select_work_bytes, need, need, s, BN_ERR_NOMEM, "selection")) return rc;
     bn::launch_select_run(d_rows, dtype == BN_DTYPE_I8, (long)n, D, zero_point, d_inv, d_weight, d_m, d_nearest, d_picked, forced, steps, d_key,
                           ctx->d_select_work, s);
+    HIP_TRY(hipGetLastError());
+    return BN_OK;
+}
+
+}  // extern "C"
+
+// --------------------------------------------------------------------------------------------------------- acoustic indices (bn_indices.hip)
+extern "C" {
+
+int bn_acoustic_indices(bn_ctx* ctx, const float* d_spec, const float* d_minmax, int B, int F, int W, const bn_indices_params* params, float* d_out,
+                        float* d_spectral, void* stream) {
+    if (int rc = check_device(ctx)) return rc;
+    if (F != BN_INDICES_BINS) return fail(BN_ERR_UNSUPPORTED, "F=%d: only %d bins (n_fft = 512) are implemented", F, BN_INDICES_BINS);
+    if (W < BN_INDICES_MIN_W || W > BN_INDICES_MAX_W) return fail(BN_ERR_ARG, "W=%d: %d .. %d frames", W, BN_INDICES_MIN_W, BN_INDICES_MAX_W);
+    if (B < 0) return fail(BN_ERR_ARG, "B=%d", B);
+    if (!d_spec || !d_minmax || !params || !d_out) return fail(BN_ERR_ARG, "null pointer");
+    if ((uintptr_t)d_spec % 4 || (uintptr_t)d_minmax % 4 || (uintptr_t)d_out % 4 || (uintptr_t)d_spectral % 4)
+        return fail(BN_ERR_ARG, "float32 arrays must be 4-byte aligned");
+    const bn_indices_params& p = *params;
+    if (p.anthro_k0 < 0 || p.anthro_k0 > p.anthro_k1 || p.anthro_k1 > F)
+        return fail(BN_ERR_ARG, "anthrophony bins [%d, %d): 0 <= k0 <= k1 <= %d", p.anthro_k0, p.anthro_k1, F);
+    if (p.bio_k0 < 0 || p.bio_k0 > p.bio_k1 || p.bio_k1 > F) return fail(BN_ERR_ARG, "biophony bins [%d, %d): 0 <= k0 <= k1 <= %d", p.bio_k0, p.bio_k1, F);
+    if (p.n_bands < 0 || p.n_bands > BN_INDICES_MAX_BANDS) return fail(BN_ERR_ARG, "n_bands=%d: 0 .. %d", p.n_bands, BN_INDICES_MAX_BANDS);
+    for (int i = 0; i <= p.n_bands; ++i)
+        if (p.band_edge[i] < 0 || p.band_edge[i] > F || (i > 0 && p.band_edge[i] < p.band_edge[i - 1]))
+            return fail(BN_ERR_ARG, "band edge %d is bin %d: edges ascend within 0 .. %d", i, p.band_edge[i], F);
+    if (!(p.cover_ratio >= 0.0f) || !std::isfinite(p.cover_ratio) || !(p.df_khz >= 0.0f) || !std::isfinite(p.df_khz))
+        return fail(BN_ERR_ARG, "cover_ratio and df_khz must be finite and >= 0");
+    if (B == 0) return BN_OK;
+    bn::launch_acoustic_indices(d_spec, d_minmax, B, W, p, d_out, d_spectral, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return BN_OK;
 }

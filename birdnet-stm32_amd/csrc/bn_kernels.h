@@ -11,6 +11,7 @@
 
 #include "bn_blob.h"
 #include "bn_chain_plan.h"
+#include "../../include/birdnet_hip.h"
 
 namespace bn {
 
@@ -433,7 +434,7 @@ void launch_i8_dwpw(const DwPw8Args& a, hipStream_t s);
 // One per source file with kernels: load that file's device code object now (bn_preload_kernels)
 void preload_f32(); void preload_f32_fused(); void preload_f32_pw(); void preload_f32_strip(); void preload_i8(); void preload_i8_fused();
 void preload_i8_pw(); void preload_i8_strip(); void preload_i8_tail(); void preload_i8_tail2(); void preload_ingest(); void preload_melspec();
-void preload_stft(); void preload_stft_exact(); void preload_sort(); void preload_probe(); void preload_probe_sweep(); void preload_activity(); void preload_search(); void preload_augment(); void preload_kmeans(); void preload_silhouette(); void preload_density(); void preload_tsne(); void preload_propagate(); void preload_select(); void preload_pca(); void preload_bootstrap(); void preload_head_i8();
+void preload_stft(); void preload_stft_exact(); void preload_sort(); void preload_probe(); void preload_probe_sweep(); void preload_activity(); void preload_search(); void preload_augment(); void preload_kmeans(); void preload_silhouette(); void preload_density(); void preload_tsne(); void preload_propagate(); void preload_select(); void preload_indices(); void preload_pca(); void preload_bootstrap(); void preload_head_i8();
 
 // bn_probe.hip: a classifier head on embeddings (bn_head_forward) and its training step (bn_probe_*)
 struct ProbeFwdArgs {
@@ -701,6 +702,10 @@ struct SelectArgs {
 size_t select_workspace();   // the two alternating partial buffers
 void launch_select_run(const void* rows, bool i8, long n, int D, int zp, const float* inv, const float* weight, float* m, int* nearest, int* picked, int forced,
                        int steps, float* key, void* d_work, hipStream_t s);
+
+// bn_indices.hip: acoustic indices of raw STFT magnitudes, one workgroup per chunk (bn_acoustic_indices)
+void launch_acoustic_indices(const float* spec, const float* minmax, int B, int W, const bn_indices_params& prm, float* out, float* spectral,
+                             hipStream_t s);
 
 // bn_pca.hip: column sums, scatter matrix and projection of embedding rows (bn_pca_*)
 struct PcaColsumGeom {

@@ -797,6 +797,43 @@ BN_API int bn_propagate_decide(bn_ctx* ctx, const float* d_f, int64_t n, int C, 
 BN_API int bn_select_run(bn_ctx* ctx, const void* d_rows, int dtype, int64_t n, int D, int zero_point, const float* d_inv, const float* d_weight,
                          float* d_m, int32_t* d_nearest, int32_t* d_picked, int forced, int steps, float* d_key, void* stream);
 
+/* ---- Acoustic indices of raw STFT magnitudes (csrc/bn_indices.hip; no reference counterpart) -------------------------------------------
+ * (birdnet_stm32/evaluation/indices.py is the specification: ACI, spectral and temporal entropy, NDSI, the bioacoustic index, ADI and AEI
+ * per chunk, and the three per-bin channels of false-colour long-duration spectrograms.)  With S [F, W] one chunk's magnitudes as
+ * bn_stft_mag(normalize = 0) leaves them, P = S * S, r_f = sum_t S, p_f = sum_t P, e_t = sum_f P, smax the chunk's maximum (d_minmax[b][1];
+ * the minimum is not read), thr = fl32(smax * cover_ratio), H(v) = -sum q ln q / ln(len v) over q = v / sum v (0 for an all-zero v):
+ *   d_out[b]      = { aci, hf, ht, h, ndsi, bi, adi, aei }                                            BN_INDICES_SCALARS float32
+ *     aci  = sum_f ACI_f              hf = H(p)      ht = H(e)      h = hf * ht
+ *     ndsi = (B - A) / (B + A), A / B = sum of p_f over bins [anthro_k0, anthro_k1) / [bio_k0, bio_k1); 0 when A + B = 0
+ *     bi   = sum over [bio_k0, bio_k1) of (L_f - min L_f) * df_khz, L_f = 10 log10(max(p_f / W, 1e-12 smax^2)); 0 when smax = 0
+ *     adi  = -sum q ln q, q = c / sum c, c_b = (cells of bins [band_edge[b], band_edge[b+1]) with S > thr) / (cells of the band)
+ *     aei  = 2 sum_i i x_(i) / (n sum x) - (n + 1) / n over the ascending c (i from 1); adi = aei = 0 when sum c = 0
+ *   d_spectral[b] = { ACI_f [F], ENT_f [F], CVR_f [F] } (may be NULL: the scalars are the same)
+ *     ACI_f = sum_{t >= 1} |S[f,t] - S[f,t-1]| / r_f (0 where r_f = 0)    ENT_f = 1 - H(P[f, :]) (0 where p_f = 0)
+ *     CVR_f = fl32(count_t(S[f,t] > thr)) / fl32(W)
+ * One workgroup per chunk and one pass over its F * W floats.  Sums are float32 in a fixed order (a lane's elements, then a tree over the
+ * lanes), counts are integers, and ACI_f, CVR_f and ndsi are single correctly rounded divisions of their sums; no atomics: the same input
+ * gives the same bits on every run.  Rows are read with 16-byte loads where d_spec is 16-byte aligned and W % 4 == 0, with the same bits
+ * from any other layout.  F must be BN_INDICES_BINS (the STFT's own limit): BN_ERR_UNSUPPORTED otherwise.  Refused with BN_ERR_ARG, nothing
+ * launched: W outside BN_INDICES_MIN_W .. BN_INDICES_MAX_W, B < 0, a NULL pointer other than d_spectral, an array not 4-byte aligned, a
+ * bin range outside 0 <= k0 <= k1 <= F, n_bands outside 0 .. BN_INDICES_MAX_BANDS, band edges that decrease or leave 0 .. F, a
+ * cover_ratio or df_khz that is negative or not finite.  B = 0 does nothing. */
+#define BN_INDICES_SCALARS 8
+#define BN_INDICES_BINS 257
+#define BN_INDICES_MIN_W 2
+#define BN_INDICES_MAX_W 1024
+#define BN_INDICES_MAX_BANDS 16
+typedef struct bn_indices_params {
+    int32_t anthro_k0, anthro_k1;                     /* bins of the anthrophony band (NDSI) */
+    int32_t bio_k0, bio_k1;                           /* bins of the biophony band (NDSI, BI) */
+    int32_t n_bands;                                  /* bands of ADI / AEI */
+    int32_t band_edge[BN_INDICES_MAX_BANDS + 1];      /* band b holds bins [band_edge[b], band_edge[b + 1]); entries past n_bands are ignored */
+    float cover_ratio;                                /* fl32(10^(db / 20)): the cover threshold as a share of the chunk's maximum */
+    float df_khz;                                     /* sample_rate / 512 / 1000 */
+} bn_indices_params;
+BN_API int bn_acoustic_indices(bn_ctx* ctx, const float* d_spec, const float* d_minmax, int B, int F, int W, const bn_indices_params* params,
+                               float* d_out, float* d_spectral, void* stream);
+
 /* ---- Principal components: column sums, scatter matrix and projection of embedding rows (csrc/bn_pca.hip; no reference counterpart) ----
  * (birdnet_stm32/evaluation/reduce.py is the specification; the eigen-decomposition stays on the host.)  Rows have bn_search's meaning: an
  * int8 row is byte - zero_point.  With c_i = fl32(x_i - mean) (x_i itself where d_mean is NULL; an int8 x is made float32 first, which is exact):
